@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- depth maps/sec of the MI355X-native MVSNet depth path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,11 @@ resident in HBM -> depth + confidence), i.e. reference models/mvsnet.py:145-218.
 processes its own independent maps (reference views shard embarrassingly); the
 only collective is one RCCL all-gather of the [K,2,h,w] results at the end (inside the timed
 region).  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR: rank 0 writes what the timed path returned for its last timed step -- the depth and
+photometric-confidence maps of every rank's last map, [world, h, w] float32 -- as DIR/depth.npy and
+DIR/photometric_confidence.npy.  The inputs are seeded (synthetic.*), so the same arguments give the same
+inputs on every run and two builds can be compared map for map.
 
 The timed region is K x one mvs_depth_infer call per map (what the drop-in's forward enqueues),
 nothing else.  Per-kernel durations -- and the roofline figure of the dominant kernel -- are
@@ -316,6 +321,8 @@ def parse_args(argv=None):
                          "HIP event after each kernel); 0 = skip it (no `stages` / `roofline` objects)")
     ap.add_argument("--staged-timed", action="store_true",
                     help="diagnostic: the TIMED steps go through the per-stage calls with events too")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the maps the last timed step produced as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -467,6 +474,7 @@ def measure(ctx, config, storage, K, Wm, prewarm_ms, S, KS, staged_timed=False):
         torch.cuda.synchronize()
         dist.barrier()
     per_rank = []   # seconds of the last timed pass on each rank's own clock
+    last_maps = []  # [world, 2, h, w]: every rank's map of the last timed step (in unit order)
 
     def timed_pass():
         """EXACTLY K steps between barrier + synchronize on both sides -> seconds (max over ranks)."""
@@ -488,6 +496,8 @@ def measure(ctx, config, storage, K, Wm, prewarm_ms, S, KS, staged_timed=False):
             dist.barrier()
         torch.cuda.synchronize()
         dt_s = time.perf_counter() - t0
+        # units world*(K-1) .. world*K-1 of the gather: step K-1 of every rank
+        last_maps[:] = [gathered[-world:] if world > 1 else out[K - 1:K]]
         own = None
         if world > 1:
             # every rank's own clock around the same region (a slow rank shows up), then the max over ranks
@@ -517,6 +527,8 @@ def measure(ctx, config, storage, K, Wm, prewarm_ms, S, KS, staged_timed=False):
             effective_warmup += K
             torch.cuda.synchronize()
         elapsed = timed_pass()
+    # what the reported pass returned, copied before the per-stage pass below rewrites `out`
+    final_maps = last_maps[0].clone()
 
     # ---- per-kernel durations: the same kernels on the same inputs through the per-stage C-ABI
     # calls, a HIP event (on the launch stream) after each, one stream, right after the timed region
@@ -555,7 +567,7 @@ def measure(ctx, config, storage, K, Wm, prewarm_ms, S, KS, staged_timed=False):
                stages=stages, roofline=roofline, path_bytes=path_bytes, path_flops=path_flops,
                stagewise_floor_s=stagewise_floor_s, executed_floor_s=executed_floor_s, in_image_frac=in_image_frac,
                call=("staged C-ABI calls with HIP events" if staged_timed else "one mvs_depth_infer call per map"),
-               last_depth=out[K - 1, 0], inputs=(feats_np, proj_np, dv_np, sd), streams=streams)
+               last_maps=final_maps, inputs=(feats_np, proj_np, dv_np, sd), streams=streams)
     return res
 
 
@@ -579,6 +591,16 @@ def brief(res, world=1):
     out["stages_ms"] = {n: e["ms"] for n, e in st.items()}
     out["stages_frac"] = {n: e["frac"] for n, e in st.items() if "frac" in e}
     return out
+
+
+def dump_outputs(out_dir, last_maps):
+    """DIR/depth.npy and DIR/photometric_confidence.npy: [world, h, w] float32 (the keys of the drop-in's output
+    dict).  At most 8 ranks x 2 maps of the largest config (cfg3: 296x400) -- about 7.6 MB, under 64 MB."""
+    maps = last_maps.detach().float().cpu().numpy()
+    assert maps.nbytes <= 64 << 20, maps.nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for i, name in enumerate(("depth", "photometric_confidence")):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(maps[:, i]))
 
 
 def main(argv=None):
@@ -666,7 +688,7 @@ def main(argv=None):
                         "kind": "port",
                         "sample": f"1 full {args.config} map (N={N}, {h}x{w}x{D}) through oracle/ "
                                   f"(C + OpenMP restatement), {tc:.1f} s"}
-        got = res["last_depth"].cpu().numpy()
+        got = res["last_maps"][0, 0].cpu().numpy()
         parity = float(np.abs(got - depth_o).mean() / np.abs(depth_o).mean())
 
     # ---- end-to-end figure, outside the timed region, never `value`: the drop-in
@@ -788,6 +810,8 @@ def main(argv=None):
             "other_configs": other_configs,
             "parity_rel_l1_vs_oracle": parity,
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res["last_maps"])
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

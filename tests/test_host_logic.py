@@ -401,6 +401,22 @@ def test_bench_self_launch_command_and_defaults():
         "scene_3dreconstruction_mvsnet_amd.synthetic", fromlist=["CONFIGS"]).CONFIGS)
 
 
+def test_bench_dump_outputs_writes_the_last_step_maps(tmp_path):
+    """--dump-outputs DIR: the [world, 2, h, w] maps of the last timed step -> DIR/depth.npy and
+    DIR/photometric_confidence.npy, float32 [world, h, w]."""
+    bench = _bench()
+    assert bench.parse_args([]).dump_outputs is None
+    assert bench.parse_args(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    maps = torch.arange(2 * 2 * 3 * 5, dtype=torch.float32).reshape(2, 2, 3, 5)
+    bench.dump_outputs(str(tmp_path / "d"), maps)
+    assert sorted(os.listdir(tmp_path / "d")) == ["depth.npy", "photometric_confidence.npy"]
+    depth = np.load(tmp_path / "d" / "depth.npy")
+    conf = np.load(tmp_path / "d" / "photometric_confidence.npy")
+    assert depth.dtype == np.float32 and depth.shape == (2, 3, 5)
+    np.testing.assert_array_equal(depth, maps[:, 0].numpy())
+    np.testing.assert_array_equal(conf, maps[:, 1].numpy())
+
+
 def test_bench_path_totals_equal_survey_d3():
     """algorithmic bytes / FLOPs per map, layer by layer, no fusion credited -- whichever
     kernels ran (conv11 + prob count once, not again as the fused `conv11_prob` stage)."""
