@@ -38,24 +38,6 @@
 #include "storage.h"
 #include "split_ops.h"
 
-// Diagnostic builds (`make ablate21` .. `ablate24`, wrong results, timing only): 21 = no stencil, 22 = no
-// scatter of the accumulators, 23 = no MFMAs, 24 = no skip loads; the split-operand kernel: 81 = no stencil, 82 = no
-// MFMAs, 83 = no split arithmetic, 84 = no scatter / skip add, 85 / 86 = one B / A fragment read per chunk and piece.  Product builds leave MVS_ABLATE at 0.
-#ifndef MVS_ABLATE
-#define MVS_ABLATE 0
-#endif
-// 87: the split-operand kernel without its four block barriers per step, 88: without the two around the odd plane's scatter
-#if MVS_ABLATE == 87
-#define SPLIT_SYNC_A() __builtin_amdgcn_wave_barrier()
-#define SPLIT_SYNC_B() __builtin_amdgcn_wave_barrier()
-#elif MVS_ABLATE == 88
-#define SPLIT_SYNC_A() __syncthreads()
-#define SPLIT_SYNC_B() __builtin_amdgcn_wave_barrier()
-#else
-#define SPLIT_SYNC_A() __syncthreads()
-#define SPLIT_SYNC_B() __syncthreads()
-#endif
-
 namespace mvs {
 
 namespace cp {
@@ -87,7 +69,7 @@ typedef float f32x2v __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------
 // 512 threads per block; everything before the stencil is private to a wave (the first form, with a shared
-// input halo and six block barriers per step, is in attic/conv11_prob_form1.hip).  Wave w owns M-tile w (2 x 8 input voxels -> a 4 x 16 strip of both conv11 planes): it
+// input halo and six block barriers per step, is csrc/attic/conv11_prob_form1.hip in commit c2f08ac).  Wave w owns M-tile w (2 x 8 input voxels -> a 4 x 16 strip of both conv11 planes): it
 // stages its own 3 x 9 voxel input halo per chunk (1.4x the loads of the shared halo, L1 hits), runs its
 // 72 MFMAs, scatters and adds the skip values of its own strip -- LDS operations of one wave execute in
 // order, so none of this needs a barrier.  Two block barriers per step (tile complete / tile consumed)
@@ -654,11 +636,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
         const bool ok = pin && (pre_z1 || phz == 0);
         const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
         g_u32x4 p1, p2, p3;
-#if MVS_ABLATE == 83
-        p1 = __builtin_bit_cast(g_u32x4, ok ? pre[0] : z4); p2 = __builtin_bit_cast(g_u32x4, ok ? pre[1] : z4); p3 = p1;
-#else
         gs_split8(ok ? pre[0] : z4, ok ? pre[1] : z4, p1, p2, p3);
-#endif
         *reinterpret_cast<g_u32x4*>(my + ploff) = p1;             // lanes >= NPC rewrite the last voxel with its own value
         *reinterpret_cast<g_u32x4*>(my + WIN + ploff) = p2;
         *reinterpret_cast<g_u32x4*>(my + 2 * WIN + ploff) = p3;
@@ -703,22 +681,11 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
     const g_u32x4* bsrc = reinterpret_cast<const g_u32x4*>(bpan) + lane;
     f32x4 acc[4];
     auto mfma_chunk = [&](int c) {
-#if MVS_ABLATE == 82
-        return;
-#endif
 #pragma unroll
         for (int ks = 0; ks < 5; ++ks) {
             const int cls = deconv16_tap(ks, 0).cls;
-#if MVS_ABLATE == 86
-            const int kq = koff[0];
-#else
             const int kq = koff[ks];
-#endif
-#if MVS_ABLATE == 85
-            const int bq = c * 5;
-#else
             const int bq = c * 5 + ks;
-#endif
             const g_u32x4 a1 = *reinterpret_cast<const g_u32x4*>(my + kq);
             const g_u32x4 a2 = *reinterpret_cast<const g_u32x4*>(my + WIN + kq);
             const g_u32x4 a3 = *reinterpret_cast<const g_u32x4*>(my + 2 * WIN + kq);
@@ -735,9 +702,6 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
     };
     // conv11 plane pz of this step -> the tile: ReLU(sum + bias) + skip, zero beyond the volume (the prob layer's padding)
     auto scatter = [&](int pz, const f32x4& s0, const f32x4& s1) {   // s0, s1: the sums of classes (pz, py = 0 / 1), bias included
-#if MVS_ABLATE == 84
-        return;
-#endif
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             float* dst = ct + c * RS + sbase0;
@@ -757,9 +721,6 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
     const size_t pout = (size_t)gyo * Wo + gxo;
     const int cbase = ly * RS + lx * 4;   // LDS row r = tile row r - 1, x index lx = tile column lx - 1
     auto stencil = [&](f32x2v& k2, f32x2v& k1, f32x2v& k0) {
-#if MVS_ABLATE == 81
-        return;
-#endif
         const float* base = ct + cbase;
 #pragma unroll 1
         for (int kx = 0; kx < 3; ++kx) {
@@ -828,42 +789,29 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
         stage(min(i + 1, i_last), 0);                // after chunk 0's reads in this wave's LDS order; unconditional
         mfma_chunk(1);
         if (de) scatter(0, acc[0], acc[1]);
-        SPLIT_SYNC_A();
+        __syncthreads();
         if (de) stencil(A, B, C);              // even plane 2i: completes logit 2i - 1
         emit(max(2 * i - 1, 0), A, de && i > za);
         A = fresh;
-        SPLIT_SYNC_B();
+        __syncthreads();
         if (dodd) scatter(1, acc[2], acc[3]);
         load_skip(min(i + 1, i_last));                // unconditional
-        SPLIT_SYNC_B();
+        __syncthreads();
         if (dodd) stencil(B, C, A);            // odd plane 2i + 1: completes logit 2i
         emit(2 * i, B, dodd && de);
         const f32x2v t = A;  // (A, B, C) <- logits (2i+1, 2i+2, 2i+3)
         A = C;
         B = t;
         C = fresh;
-        SPLIT_SYNC_A();
+        __syncthreads();
     }
     emit(Do - 1, A, zb == Di);   // the volume's last plane has no successor to complete it
 }
 
 bool conv11_prob_enabled(int dtype) {   // MVS_FUSE_PROB=0: conv11 and prob as two launches (A/B runs)
-    static const bool on = [] {
-        const char* e = getenv("MVS_FUSE_PROB");
-        return !(e && e[0] == '0');
-    }();
     // 16-bit storage: the fused kernel runs the transposed convolution on the 16-bit matrix cores, so it stands in
     // for the 16-bit MFMA layer kernels only (MVS_MFMA16=0 = fp32 arithmetic on the narrowed operands: two launches)
-    return on && (dtype == MVS_F32 || mfma16_enabled());
-}
-
-// MVS_TAIL_SPLIT=0: the fp32-MFMA form of the fused tail (conv11_prob_priv_kernel)
-static bool tail_split_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("MVS_TAIL_SPLIT");
-        return !(e && e[0] == '0');
-    }();
-    return on;
+    return options().fuse_prob && (dtype == MVS_F32 || mfma16_enabled());
 }
 
 int launch_conv11_prob(const void* x, const void* skip, float* cost, const float* blob, int Di, int Hi, int Wi,
@@ -877,10 +825,7 @@ int launch_conv11_prob(const void* x, const void* skip, float* cost, const float
     const int Ho = 2 * Hi, Wo = 2 * Wi;
     const int nbx = (Wo - 2 + PX - 1) / PX > 0 ? (Wo - 2 + PX - 1) / PX : 1;
     const int nby = (Ho - 2 + PY - 1) / PY > 0 ? (Ho - 2 + PY - 1) / PY : 1;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
+    const int cus = device_cus();
     // z chunks of >= 4 input planes (every chunk recomputes one input plane and pays a prologue of about half a step):
     // the split that fills the last round of two-blocks-per-CU best.  (Round 2 took the largest split that keeps all
     // blocks resident at once: fine at cfg2 (60 tiles x 8 chunks = 480 blocks for 512 slots), 57 % at cfg3 (294 tiles,
@@ -899,8 +844,9 @@ int launch_conv11_prob(const void* x, const void* skip, float* cost, const float
     if (ZC > Di) ZC = Di;
     const int nzc = (Di + ZC - 1) / ZC;
     const dim3 grid(nbx * nby * nzc);
-    // the split-operand kernel addresses the skip tensor through a buffer descriptor (32-bit byte offsets)
-    if (dtype == MVS_F32 && tail_split_enabled() && (size_t)Di * Hi * Wi * 256 < ((size_t)1 << 32)) {
+    // the split-operand kernel addresses the skip tensor through a buffer descriptor (32-bit byte offsets);
+    // MVS_TAIL_SPLIT=0: the fp32-MFMA form of the fused tail (conv11_prob_priv_kernel)
+    if (dtype == MVS_F32 && options().tail_split && (size_t)Di * Hi * Wi * 256 < ((size_t)1 << 32)) {
         conv11_prob_split_kernel<<<grid, 512, 0, s>>>(
             static_cast<const float*>(x), reinterpret_cast<const unsigned short*>(blob + L.s16_off[9]), blob + L.b_off[9],
             static_cast<const float*>(skip), blob + L.w_off[10], blob + L.b_off[10], cost, Di, Hi, Wi, ZC, nbx, nby);

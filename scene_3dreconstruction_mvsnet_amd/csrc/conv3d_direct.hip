@@ -17,10 +17,6 @@
 #include "mvs_internal.h"
 #include "storage.h"
 
-#ifndef MVS_ABLATE
-#define MVS_ABLATE 0
-#endif
-
 namespace mvs {
 
 template <int CIN, int COUT, int CPT, int STRIDE, bool DECONV, bool RELU, bool SKIP>
@@ -282,24 +278,16 @@ __global__ __launch_bounds__(256, 2) void prob_lds_kernel(const void* __restrict
         if (interior) {            // wave-uniform: no masks at all
 #pragma unroll
             for (int i = 0; i < PPT; ++i) {
-#if MVS_ABLATE == 6  // diagnostic: no staging loads
-                stg[i] = make_float4(1.f, 2.f, 3.f, 4.f);
-#else
                 const f32x4 val = St<DT>::load4(x, (size_t)(base + (pos[i] != 0x00FFFFFFu ? rel[i] : (int)(-base))));
                 stg[i] = make_float4(val[0], val[1], val[2], val[3]);
-#endif
             }
         } else {
 #pragma unroll
             for (int i = 0; i < PPT; ++i) {
                 const int hz = pos[i] & 255, hy = (pos[i] >> 8) & 255, hx = pos[i] >> 16;
                 const bool ok = hz >= zl && hz <= zh && hy >= yl && hy <= yh && hx >= xl && hx <= xh;
-#if MVS_ABLATE == 6
-                stg[i] = make_float4(1.f, 2.f, 3.f, 4.f);
-#else
                 const f32x4 val = St<DT>::load4(x, ok ? (size_t)(base + rel[i]) : (size_t)0);
                 stg[i] = ok ? make_float4(val[0], val[1], val[2], val[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
             }
         }
     };
@@ -316,11 +304,6 @@ __global__ __launch_bounds__(256, 2) void prob_lds_kernel(const void* __restrict
     __syncthreads();
     const int tx = tid & 31, ty = tid >> 5;  // thread -> (y, x) of the tile, 4 z outputs
     const float bv = bias[0];
-#if MVS_ABLATE == 5  // diagnostic: one tap only
-#define MVS_PROB_KH 1
-#else
-#define MVS_PROB_KH 3
-#endif
     for (;;) {
         const int cx0 = x0, cy0 = y0, cz0 = z0;      // origin of the tile now in LDS
         const int tn = t + gridDim.x;
@@ -332,9 +315,9 @@ __global__ __launch_bounds__(256, 2) void prob_lds_kernel(const void* __restrict
 #pragma unroll
         for (int j = 0; j < TZ; ++j) acc[j] = (f32x2p){bv, 0.0f};
 #pragma unroll 1
-        for (int kh = 0; kh < MVS_PROB_KH; ++kh)
+        for (int kh = 0; kh < 3; ++kh)
 #pragma unroll 1
-            for (int kw = 0; kw < MVS_PROB_KH; ++kw) {
+            for (int kw = 0; kw < 3; ++kw) {
                 const int hx = tx + kw;
                 const int sw = ((hx >> 3) & 1) * 4;
                 const float* vp = tile + ((ty + kh) * HX + hx) * 8;
@@ -379,10 +362,7 @@ static int run_prob(const void* x, void* y, const float* wgt, const float* bias,
     using namespace pl;
     const int ntiles = ((W + TX - 1) / TX) * ((H + TY - 1) / TY) * ((D + TZ - 1) / TZ);
     // persistent grid: two blocks per CU (65 KB of LDS each), next tile requested under this tile's FMAs
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
+    const int cus = device_cus();
     const int nb = ntiles < 2 * cus ? ntiles : 2 * cus;
     float* yo = static_cast<float*>(y);
     if (dtype == MVS_F32) prob_lds_kernel<MVS_F32><<<nb, 256, 0, s>>>(x, wgt, bias, yo, D, H, W);
@@ -426,27 +406,14 @@ int launch_conv_layer_direct(int layer, const void* x, const void* skip, void* y
 }
 
 // MVS_MFMA16=0: fp32 MFMA arithmetic on the 16-bit stored operands instead of the 16-bit matrix cores
-bool mfma16_enabled() {
-    static const bool v = [] {
-        const char* e = getenv("MVS_MFMA16");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
-// MVS_FORCE_DIRECT=1 routes every layer through the direct kernels (A/B checks in tests).
-static bool force_direct() {
-    static const bool v = [] {
-        const char* e = getenv("MVS_FORCE_DIRECT");
-        return e && e[0] == '1';
-    }();
-    return v;
-}
+bool mfma16_enabled() { return options().mfma16; }
 
 int launch_conv_layer(int layer, const void* x, const void* skip, void* y, const float* blob,
                       int Di, int Hi, int Wi, int dtype, hipStream_t s) {
     const BlobLayout L = blob_layout();
-    if (force_direct()) {
+    const Options& opt = options();
+    // MVS_FORCE_DIRECT=1 routes every layer through the direct kernels (A/B checks in tests)
+    if (opt.force_direct) {
         if (dtype != MVS_F32)
             return fail(MVS_ERR_BAD_DTYPE, "MVS_FORCE_DIRECT kernels are fp32-storage only (dtype %d)", dtype);
         return launch_conv_layer_direct(layer, x, skip, y, blob + L.w_off[layer], blob + L.b_off[layer],
@@ -454,26 +421,18 @@ int launch_conv_layer(int layer, const void* x, const void* skip, void* y, const
     }
     // 16-bit storage: 16-bit MFMA arithmetic (conv3d_mfma16.hip) unless MVS_MFMA16=0 asks for fp32
     // arithmetic on the narrowed operands
-    if (mfma16_enabled() && (dtype == MVS_F16 || dtype == MVS_BF16) && layer <= 9)
+    if (opt.mfma16 && (dtype == MVS_F16 || dtype == MVS_BF16) && layer <= 9)
         return launch_layer_mfma16(layer, x, skip, y, blob + L.h16_off[dtype == MVS_F16 ? 0 : 1][layer],
                                    blob + L.b_off[layer], Di, Hi, Wi, dtype, s);
     if (layer == 0) {
         // conv0: Winograd F(4,3) along z on the 4x4x1 MFMA (1/2 of the direct form's MFMAs; conv_winograd.hip)
         // unless MVS_CONV0_WINO=0 asks for the direct form (cross-check) or the volume needs 64-bit offsets
-        static const bool wino = [] {
-            const char* e = getenv("MVS_CONV0_WINO");
-            return !(e && e[0] == '0');
-        }();
         // fp32 volumes: the same F(4,3) scheme with every operand split into three bf16 pieces, six cross products per
         // fp32 product on the bf16 matrix cores, fp32 accumulation (conv0_split.hip: fp32-equivalent arithmetic -- the
         // per-layer bounds of the fp32 kernel hold unchanged -- at 0.28 instead of 0.36 ms).  MVS_CONV0_SPLIT=0: the
-        // fp32-MFMA kernel below; =2: the split kernel's first form (one tile per block)
-        static const bool split = [] {
-            const char* e = getenv("MVS_CONV0_SPLIT");
-            return !(e && e[0] == '0');
-        }();
-        if (wino && Di % 4 == 0 && (size_t)Di * Hi * Wi * 32 < ((size_t)1 << 31)) {
-            if (split && dtype == MVS_F32)
+        // fp32-MFMA kernel below
+        if (opt.conv0_wino && Di % 4 == 0 && (size_t)Di * Hi * Wi * 32 < ((size_t)1 << 31)) {
+            if (opt.conv0_split && dtype == MVS_F32)
                 return launch_conv0_wino43_split(x, y, blob + L.c0w43s_off, blob + L.b_off[0], Di, Hi, Wi, dtype, s);
             return launch_conv0_wino43(x, y, blob + L.c0w43_off, blob + L.b_off[0], Di, Hi, Wi, dtype, s);
         }
@@ -481,21 +440,13 @@ int launch_conv_layer(int layer, const void* x, const void* skip, void* y, const
     }
     // fp32 volumes: the level-1 .. 3 layers on the bf16 matrix cores with split operands (conv3d_mfma16.hip, round 4)
     // unless MVS_SPLIT_LAYERS=0 keeps the fp32-MFMA kernels below
-    static const bool split_layers = [] {
-        const char* e = getenv("MVS_SPLIT_LAYERS");
-        return !(e && e[0] == '0');
-    }();
-    if (split_layers && dtype == MVS_F32 && split_layer_covers(layer))
+    if (opt.split_layers && dtype == MVS_F32 && split_layer_covers(layer))
         return launch_layer_split(layer, x, skip, y, blob + L.s16_off[layer], blob + L.b_off[layer], Di, Hi, Wi, s);
     if (layer == 2 || layer == 4) {
         // stride-1 layers conv2 / conv4: Winograd F(2,3) along z (conv_winograd.hip) unless
         // MVS_CONV_WINO=0.  conv6 (64 -> 64 on 7,680 voxels) stays direct: with two-plane tiles it has
         // only 240 blocks for 256 CUs and measured 0.035 vs 0.033 ms.
-        static const bool wz = [] {
-            const char* e = getenv("MVS_CONV_WINO");
-            return !(e && e[0] == '0');
-        }();
-        if (wz) return launch_convwz_mfma(layer, x, y, blob + L.wz_off[layer], blob + L.b_off[layer], Di, Hi, Wi, dtype, s);
+        if (opt.conv_wino) return launch_convwz_mfma(layer, x, y, blob + L.wz_off[layer], blob + L.b_off[layer], Di, Hi, Wi, dtype, s);
     }
     // the 1/8-resolution layers conv5 / conv6 / conv7: all-K-resident split-K kernels (conv3d_small.hip)
     if (convs_covers(layer)) {

@@ -23,18 +23,11 @@ namespace mvs {
 
 typedef unsigned u32x4r __attribute__((__vector_size__(4 * sizeof(unsigned))));
 
-// Diagnostic builds only (make ABLATE=n -> libmvs_hip_ablate<n>.so, wrong results by design):
-//   1 = conv0 without epilogue stores, 2 = without chunk re-staging, 3 = also without the
-//   staging loads.  Product builds leave MVS_ABLATE at 0.
-#ifndef MVS_ABLATE
-#define MVS_ABLATE 0
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // conv0 on v_mfma_f32_4x4x1_16b_f32: 16 independent 4x4 outer products per instruction (512 FLOP
 // in 8 cycles = the same 64 FLOP/clk/SIMD as the 16x16x4 form), so N = 4 output channels per
 // tile and Cout = 8 is two exact N-tiles: no padded or Toeplitz-wasted columns (a 16x16x4 form with
-// N = 2 x-adjacent outputs x 8 channels spends 4/3 of the useful MFMA cycles: attic/conv0_pair_mfma.hip).
+// N = 2 x-adjacent outputs x 8 channels spends 4/3 of the useful MFMA cycles: csrc/attic/conv0_pair_mfma.hip in commit c2f08ac).
 //   lane l = 4*blk + i supplies A = in[voxel l of the 64-voxel M-group][k] and B = w[k][4*nt + i];
 //   D: lane 4*blk + j, register i' = out[voxel 4*blk + i'][4*nt + j]   (probed on gfx950:
 //   tools/probes/mfma4x4_probe.hip)
@@ -216,17 +209,8 @@ int launch_conv0_mfma(const void* x, void* y, const float* bq, const float* bias
 
 // number of CUs of the current device (persistent grids are sized from it); MVS_PERSIST_CUS overrides
 static int persistent_blocks_per_cu_scale() {
-    static const int cus = [] {
-        const char* e = getenv("MVS_PERSIST_CUS");
-        const int v = e ? atoi(e) : 0;
-        if (v > 0) return v;
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            n = 256;
-        return n;
-    }();
-    return cus;
+    const int v = options().persist_cus;
+    return v > 0 ? v : device_cus();
 }
 
 // =============================================================================================
@@ -823,10 +807,7 @@ static int launch_convg_dt(int layer, const void* x, void* y, const float* bp, c
             // fp32 storage, a volume whose (y, x) columns fill the chip: the z-marching kernel (MVS_CONV1Z=0/1 = never /
             // always); else the persistent tile kernel
             if constexpr (DT == MVS_F32) {
-                static const int zm = [] {
-                    const char* e = getenv("MVS_CONV1Z");
-                    return e ? atoi(e) : -1;
-                }();
+                const int zm = options().conv1z;
                 const int Do = (Di - 1) / 2 + 1, Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
                 const long ncol = (long)((Wo + c1z::TXO - 1) / c1z::TXO) * ((Ho + c1z::TYO - 1) / c1z::TYO);
                 if (zm != 0 && (size_t)Do * Ho * Wo * 16 * 4 < ((size_t)1 << 32) - 64 && (size_t)Di * Hi * Wi * 8 < ((size_t)1 << 31) &&

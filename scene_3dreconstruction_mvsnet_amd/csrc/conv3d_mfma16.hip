@@ -248,17 +248,9 @@ static int run_convg16(const void* x, void* y, const unsigned short* bp, const f
 // does a grid of BZ x BY x BX M-tiles (2 x 8 outputs each) over the OUTPUT of a stride-S layer (S = 1 with the input
 // dims for the transposed layers) still give every CU a block and a half?
 static bool tile_fills_chip(int Di, int Hi, int Wi, int S, int BZ, int BY, int BX) {
-    static const int cus = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            n = 256;
-        return n;
-    }();
-    static const int force = [] {   // MVS_DEEP_TILES=1 / 0: always / never (tests, A/B runs)
-        const char* e = getenv("MVS_DEEP_TILES");
-        return e ? atoi(e) : -1;
-    }();
+    const int force = options().deep_tiles;   // MVS_DEEP_TILES=1 / 0: always / never (tests, A/B runs)
     if (force >= 0) return force != 0;
+    const int cus = device_cus();
     const int Do = (Di - 1) / S + 1, Ho = (Hi - 1) / S + 1, Wo = (Wi - 1) / S + 1;
     const long nb = (long)((Wo + 8 * BX - 1) / (8 * BX)) * ((Ho + 2 * BY - 1) / (2 * BY)) * ((Do + BZ - 1) / BZ);
     return 2 * nb >= 3 * (long)cus;
@@ -839,17 +831,11 @@ template <int DT>
 static int try_convz16(int layer, const void* x, void* y, const unsigned short* bp, const float* bias, int Di, int Hi,
                        int Wi, hipStream_t s, bool* taken) {
     *taken = false;
-    static const int zm = [] {
-        const char* e = getenv("MVS_CONVZ16");
-        return e ? atoi(e) : -1;
-    }();
+    const int zm = options().convz16;
     if (zm == 0 || layer < 1 || layer > 3) return MVS_OK;
     const int S = layer == 2 ? 1 : 2, cout = layer == 3 ? 32 : 16;
     const int Do = (Di - 1) / S + 1, Ho = (Hi - 1) / S + 1, Wo = (Wi - 1) / S + 1;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
+    const int cus = device_cus();
     const int tx = S == 1 ? 32 : 16;
     const long ncol = (long)((Wo + tx - 1) / tx) * ((Ho + 7) / 8);
     if ((size_t)Do * Ho * Wo * cout * 2 >= ((size_t)1 << 32) - 64 || Do < 4) return MVS_OK;
@@ -1120,15 +1106,9 @@ static int launch_layer16_dt(int layer, const void* x, const void* skip, void* y
         if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
             return fail(MVS_ERR_BAD_SHAPE, "conv0p16_mfma: plane exceeds 31-bit offsets");
         // z-marching kernel once its (y, x) columns can fill the chip; MVS_CONV0Z16=0 keeps the tile kernel (A/B runs)
-        static const int zmarch = [] {   // 1 = also at small shapes (tests), 0 = never
-            const char* e = getenv("MVS_CONV0Z16");
-            return e ? atoi(e) : -1;
-        }();
+        const int zmarch = options().conv0z16;   // 1 = also at small shapes (tests), 0 = never
         const int ncol = ((Wi + c0z::TX - 1) / c0z::TX) * ((Hi + c0z::TY - 1) / c0z::TY);
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 256;
+        const int cus = device_cus();
         if (zmarch != 0 && Di >= 8 && (size_t)Di * Hi * Wi * 16 < ((size_t)1 << 32) - 64 &&
             (zmarch == 1 || (size_t)ncol * (Di / 8) >= (size_t)cus / 2)) {
             // z chunks (>= 8 planes each; every chunk re-reads 2 planes): the split that fills the last round of
@@ -1585,16 +1565,13 @@ static int run_deconvgs(const void* x, const void* skip, void* y, const unsigned
 // (tools/gpu/tile_sweep.sh, BZ x BY x BX M-tiles of 2 x 8 outputs): conv3 1x2x2 -> 2x2x1 0.0275 -> 0.0238, conv4 1x2x2 ->
 // 4x2x1 0.0325 -> 0.0254 -- z-deep, x-narrow tiles re-use the halo planes --, conv2 stays at 2x4x2).  Measured and NOT selected: conv5 / conv6 on this tile kernel (0.0182 / 0.0289
 // against 0.0176 / 0.0242 ms for the all-K-resident split-K fp32 kernels: on 7,680 voxels the chunk pipeline is the cost,
-// not the matrix pipe), conv1 on it (0.083 ms) and as a z-marching kernel with three bf16 rings (attic/conv1_split_zmarch.hip:
+// not the matrix pipe), conv1 on it (0.083 ms) and as a z-marching kernel with three bf16 rings (csrc/attic/conv1_split_zmarch.hip in commit c2f08ac:
 // 0.054 against 0.046 ms for the fp32-MFMA z-marching kernel)
 // conv9 likewise (deconvgs<32, 16, 2, 4, 1>: 0.0354 -> 0.0266 ms at cfg2; tiles of 1x4x1 / 2x2x1 / 1x2x2 / 1x2x1 M-tiles per
 // block: 0.0278 / 0.0277 / 0.0301 / 0.0316); conv7 on the same kernel measured 0.0248 against 0.0234 ms for the split-K
 // fp32 kernel and is not selected.
 bool split_layer_covers(int layer) {
-    static const int deconv = [] {   // MVS_SPLIT_DECONV: bit 0 = conv7, bit 1 = conv9; default 2
-        const char* e = getenv("MVS_SPLIT_DECONV");
-        return e ? atoi(e) : 2;
-    }();
+    const int deconv = options().split_deconv;   // MVS_SPLIT_DECONV: bit 0 = conv7, bit 1 = conv9; default 2
     return (layer >= 2 && layer <= 4) || (layer == 7 && (deconv & 1)) || (layer == 8 && (deconv & 2));
 }
 int launch_layer_split(int layer, const void* x, const void* skip, void* y, const void* panel, const float* bias,

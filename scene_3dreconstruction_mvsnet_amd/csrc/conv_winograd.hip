@@ -1,14 +1,14 @@
 // conv_winograd.hip -- Winograd-along-z convolutions on the fp32 MFMA: conv0 with F(4,3) (below) and the stride-1
 // layers conv2 / conv4 with F(2,3) (second half of the file; the F(2,3) form of conv0 -- the transformed planes
 // U0 = d0 - d2, U1 = d1 + d2, U2 = d2 - d1, U3 = d1 - d3 take the place of the four halo planes of a two-plane tile,
-// G = (g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2), y0 = m0 + m1 + m2, y1 = m1 - m2 - m3 -- is in attic/conv0_wz_f23.hip).
+// G = (g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2), y0 = m0 + m1 + m2, y1 = m1 - m2 - m3 -- is csrc/attic/conv0_wz_f23.hip in commit c2f08ac).
 //
 // conv0 (32 -> 8 channels, 68 % of the path's FLOPs; reference models/mvsnet.py:36,
 // block models/module.py:26-33) with Winograd F(4,3) along z on the 4x4x1 fp32 MFMA.
 //
 // conv0 is bound by the matrix pipe AND by the chip's power management (the same kernel runs 17 % faster
 // on an all-zero volume: the clock gives way under fp32 MFMA load), so the lever is fewer multiplications
-// and fewer bytes moved, not a tighter issue stream.  F(2,3) along z (attic/conv0_wz_f23.hip) issues 2/3 of
+// and fewer bytes moved, not a tighter issue stream.  F(2,3) along z (see above) issues 2/3 of
 // the direct form's MFMAs and re-reads every input plane twice (4 halo planes per 2 output planes).
 // F(4,3) computes FOUR output planes from SIX transformed planes:
 //     U0 = 4 d0 - 5 d2 + d4            U5 = 4 d1 - 5 d3 + d5
@@ -35,12 +35,6 @@
 // The sums are re-associated and the transform constants are not powers of two, so the result differs
 // from an fmaf chain by a few 1e-7 relative (tests bound it per layer against the oracle).
 #include "mvs_internal.h"
-
-// `make ablate49`: phase clocks (s_memtime) of the four waves of one block, printed to stderr
-// (profiles/r02_conv0_clocks.txt).  Product builds leave MVS_ABLATE at 0.
-#ifndef MVS_ABLATE
-#define MVS_ABLATE 0
-#endif
 #include "storage.h"
 
 namespace mvs {
@@ -106,16 +100,8 @@ __global__ __launch_bounds__(256, 2) void conv0_w43_mfma_kernel(
     const float* __restrict__ bias,  // [8]
     void* __restrict__ y,            // [D][H][W][8] storage dtype DT
     int D, int H, int W
-#if MVS_ABLATE == 49
-    , long long* __restrict__ dbg
-#endif
     ) {
     using namespace c43;
-#if MVS_ABLATE == 49   // phase clocks of the four waves of one block (diagnostic build)
-#define MVS_TICK(slot) if (dbg && blockIdx.x == 2000 && (threadIdx.x & 63) == 0) dbg[(threadIdx.x >> 6) * 32 + (slot)] = clock64();
-#else
-#define MVS_TICK(slot)
-#endif
     __shared__ __attribute__((aligned(16))) float tile[TILE_FLOATS + BW_FLOATS];
     float* wlds = tile + TILE_FLOATS;
 
@@ -247,27 +233,19 @@ __global__ __launch_bounds__(256, 2) void conv0_w43_mfma_kernel(
             if (tid + i * 256 < WPIECES) reinterpret_cast<f32x4*>(wlds)[tid + i * 256] = wst[i];
     };
 
-    MVS_TICK(0)
     load_chunk(0);
     store_chunk();
-    MVS_TICK(1)
     __syncthreads();
-    MVS_TICK(2)
 
 #pragma unroll 1
     for (int c = 0; c < 4; ++c) {
         if (c < 3) load_chunk(c + 1);
-        MVS_TICK(3 + 5 * c)
         if (wave & 1) c43_chunk_mfmas<1>(ab[0], ab[1], ab[2], wA, wB, acc);
         else c43_chunk_mfmas<0>(ab[0], ab[1], ab[2], wA, wB, acc);
-        MVS_TICK(4 + 5 * c)
         if (c < 3) {
             __syncthreads();  // every wave is done reading chunk c's planes and weights
-            MVS_TICK(5 + 5 * c)
             store_chunk();
-            MVS_TICK(6 + 5 * c)
             __syncthreads();
-            MVS_TICK(7 + 5 * c)
         }
     }
 
@@ -308,8 +286,6 @@ __global__ __launch_bounds__(256, 2) void conv0_w43_mfma_kernel(
         const f32x4 v = __builtin_elementwise_max(o[q] + bv, zero);
         St<DT>::store4(y, (((size_t)(z0 + q) * H + gy) * W + gx) * 8 + ch * 4, v);
     }
-    MVS_TICK(24)
-#undef MVS_TICK
 }
 
 template <int DT>
@@ -317,28 +293,7 @@ static int run_conv0_w43(const void* x, void* y, const float* bw, const float* b
                          hipStream_t s) {
     using namespace c43;
     const int nb = ((W + TX - 1) / TX) * ((H + TY - 1) / TY) * ((D + TZ - 1) / TZ);
-#if MVS_ABLATE == 49
-    static long long* dbg = nullptr;
-    if (!dbg && hipMalloc(&dbg, 128 * sizeof(long long)) != hipSuccess) dbg = nullptr;
-    if (dbg) (void)hipMemsetAsync(dbg, 0, 128 * sizeof(long long), s);
-    conv0_w43_mfma_kernel<DT><<<nb, 256, 0, s>>>(x, bw, bias, y, D, H, W, dbg);
-    if (dbg && nb > 2000) {
-        long long h[128];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-        for (int w = 0; w < 4; ++w) {
-            const long long* t = h + w * 32;
-            fprintf(stderr, "conv0 wave %d: stage0 %lld bar %lld |", w, t[1] - t[0], t[2] - t[1]);
-            for (int c = 0; c < 4; ++c)
-                fprintf(stderr, " c%d: ld %lld mfma %lld bar %lld st %lld bar %lld |", c, t[3 + 5 * c] - (c ? t[2 + 5 * c] : t[2]),
-                        t[4 + 5 * c] - t[3 + 5 * c], c < 3 ? t[5 + 5 * c] - t[4 + 5 * c] : 0, c < 3 ? t[6 + 5 * c] - t[5 + 5 * c] : 0,
-                        c < 3 ? t[7 + 5 * c] - t[6 + 5 * c] : 0);
-            fprintf(stderr, " end %lld total %lld\n", t[24] - t[19], t[24] - t[0]);
-        }
-    }
-#else
     conv0_w43_mfma_kernel<DT><<<nb, 256, 0, s>>>(x, bw, bias, y, D, H, W);
-#endif
     return check_hip(hipGetLastError(), "conv0_w43_mfma launch");
 }
 

@@ -448,11 +448,7 @@ int launch_feature_net_c8(const void* imgs, int fmt, const float* blob, float* f
                           int N, int H, int W, hipStream_t s) {
     const int H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1, H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
     int st;
-    static const bool split01 = [] {   // MVS_FEAT_SPLIT01=1: conv0 and conv1 as separate kernels
-        const char* e = getenv("MVS_FEAT_SPLIT01");
-        return e && e[0] == '1';
-    }();
-    if (split01) {
+    if (options().feat_split01) {   // MVS_FEAT_SPLIT01=1: conv0 and conv1 as separate kernels
         if (fmt != MVS_IMG_F32_CHW)
             return fail(MVS_ERR_BAD_DTYPE, "MVS_FEAT_SPLIT01=1 (cross-check kernels) takes fp32 images only");
         if ((st = launch_feature_layer(0, static_cast<const float*>(imgs), bufA, blob, N, H, W, s))) return st;

@@ -1,6 +1,7 @@
 // mvs_host.hip -- C-ABI entry points of libmvs_hip.so (declared in include/mvs_abi.h).
 // Host-side orchestration only: argument validation, workspace carve-up, weight packing and
 // the per-layer launch sequence of CostRegNet (reference models/mvsnet.py:64-73).
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -43,17 +44,64 @@ static int check_dims(int N, int C, int D, int h, int w, int dtype) {
     return MVS_OK;
 }
 
+// the only place the library reads its environment; a function-local static is initialised once, thread-safely
+const Options& options() {
+    static const Options o = [] {
+        auto off0 = [](const char* name) {   // on unless the value starts with '0'
+            const char* e = getenv(name);
+            return !(e && e[0] == '0');
+        };
+        auto on1 = [](const char* name) {    // off unless the value starts with '1'
+            const char* e = getenv(name);
+            return e && e[0] == '1';
+        };
+        auto num = [](const char* name, int unset) {
+            const char* e = getenv(name);
+            return e ? atoi(e) : unset;
+        };
+        Options v{};
+        v.conv0_wino = off0("MVS_CONV0_WINO");
+        v.conv_wino = off0("MVS_CONV_WINO");
+        v.conv0_split = off0("MVS_CONV0_SPLIT");
+        v.split_layers = off0("MVS_SPLIT_LAYERS");
+        v.mfma16 = off0("MVS_MFMA16");
+        v.fuse_prob = off0("MVS_FUSE_PROB");
+        v.tail_split = off0("MVS_TAIL_SPLIT");
+        v.warp_tc = off0("MVS_WARP_TC");
+        v.warp_tc16 = off0("MVS_WARP_TC16");
+        v.force_direct = on1("MVS_FORCE_DIRECT");
+        v.feat16 = on1("MVS_FEAT16");
+        v.feat_split01 = on1("MVS_FEAT_SPLIT01");
+        v.conv1z = num("MVS_CONV1Z", -1);
+        v.convz16 = num("MVS_CONVZ16", -1);
+        v.conv0z16 = num("MVS_CONV0Z16", -1);
+        v.deep_tiles = num("MVS_DEEP_TILES", -1);
+        v.split_deconv = num("MVS_SPLIT_DECONV", 2);
+        v.persist_cus = num("MVS_PERSIST_CUS", 0);
+        v.warp_depth_fastest = on1("MVS_WARP_DEPTH_FASTEST");
+        v.warp_depth_fastest_tc = num("MVS_WARP_DEPTH_FASTEST", -1);
+        return v;
+    }();
+    return o;
+}
+
+int device_cus() {
+    static std::atomic<int> cache[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int n = cache[dev].load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cache[dev].store(n, std::memory_order_relaxed);
+    }
+    return n;
+}
+
 // 16-bit modes: the warp gathers from the fp32 feature copy (round 4: the kernel is bound by vector-instruction issue,
 // and widening 16-bit taps on every re-gather costs more than the halved gather bytes save -- cfg3 bf16 1.379 -> 1.347
 // ms, cfg5 fp16 0.1226 -> 0.1131; the features then are not rounded at all).  MVS_FEAT16=1: the narrowed copy (the
 // default of rounds 2-3)
-bool feat16_gather() {
-    static const bool on = [] {
-        const char* e = getenv("MVS_FEAT16");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
+bool feat16_gather() { return options().feat16; }
 
 }  // namespace mvs
 
@@ -283,7 +331,7 @@ static int depth_infer_impl(const float* feats, const float* proj, const float* 
     char* sub = ws + (W.act[0] - W1.act[0]);
     const size_t sub_bytes = workspace_bytes - (size_t)(sub - ws);
     // The variance volume is materialised and conv0 runs as its own kernel: a fused producer/consumer
-    // kernel measured 1.40 ms against 0.16 + 0.34 ms at cfg2 (csrc/attic/warp_conv0_fused.hip).
+    // kernel measured 1.40 ms against 0.16 + 0.34 ms at cfg2 (csrc/attic/warp_conv0_fused.hip in commit c2f08ac).
     if ((st = warp_variance_impl(feats, rt, depth_values, var, workspace, workspace_bytes, N, C, D, h, w, dtype,
                                  stream, fold_proj ? proj : nullptr)))
         return st;

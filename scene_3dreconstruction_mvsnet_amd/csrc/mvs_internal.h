@@ -222,6 +222,35 @@ __host__ __device__ constexpr Deconv16Tap deconv16_tap(int ks, int q) {
 int fail(int code, const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);
 
+// Kernel-selection switches (environment variables MVS_*), read once on first use (DESIGN.md lists why each exists).
+// Unless noted, a bool switch is on by default and "0" (first character) turns it off.
+struct Options {
+    bool conv0_wino;              // MVS_CONV0_WINO: conv0 as Winograd F(4,3) along z; off = the direct 4x4x1 MFMA form
+    bool conv_wino;               // MVS_CONV_WINO: conv2 / conv4 as Winograd F(2,3) along z (fp32 MFMA path)
+    bool conv0_split;             // MVS_CONV0_SPLIT: conv0 of fp32 volumes with split bf16 operands; off = fp32 MFMA
+    bool split_layers;            // MVS_SPLIT_LAYERS: conv2 .. conv4 (+ MVS_SPLIT_DECONV) of fp32 volumes, split operands
+    bool mfma16;                  // MVS_MFMA16: 16-bit storage on the 16-bit matrix cores; off = fp32 MFMA arithmetic
+    bool fuse_prob;               // MVS_FUSE_PROB: conv11 + prob as one kernel; off = two launches
+    bool tail_split;              // MVS_TAIL_SPLIT: the fused tail of fp32 volumes with split operands; off = fp32 MFMA
+    bool warp_tc;                 // MVS_WARP_TC: the tap-cache warp + variance kernel (fp32 features); off = plain gather
+    bool warp_tc16;               // MVS_WARP_TC16: the same for 16-bit features
+    bool force_direct;            // MVS_FORCE_DIRECT, "1" = on (default off): VALU direct kernels for every layer
+    bool feat16;                  // MVS_FEAT16, "1" = on (default off): the 16-bit modes gather from a narrowed feature copy
+    bool feat_split01;            // MVS_FEAT_SPLIT01, "1" = on (default off): FeatureNet conv0 and conv1 as two kernels
+    int conv1z;                   // MVS_CONV1Z: fp32 conv1 z-marching kernel never (0) / always (1); -1 (unset) = by size
+    int convz16;                  // MVS_CONVZ16: the same for the 16-bit conv1 .. conv3
+    int conv0z16;                 // MVS_CONV0Z16: the same for the 16-bit conv0
+    int deep_tiles;               // MVS_DEEP_TILES: z-deep 16-bit block tiles never (0) / always (1); -1 (unset) = by size
+    int split_deconv;             // MVS_SPLIT_DECONV: split-operand transposed layers, bit 0 = conv7, bit 1 = conv9; default 2
+    int persist_cus;              // MVS_PERSIST_CUS: > 0 replaces the CU count in conv3d_mfma.hip's persistent grid sizing
+    // MVS_WARP_DEPTH_FASTEST, parsed two ways: the plain kernel forces the depth-slab-fastest order on "1" (default by
+    // size); the tap-cache kernel takes its integer value, 1 / 0 = always / never, -1 (unset) = by size
+    bool warp_depth_fastest;
+    int warp_depth_fastest_tc;
+};
+const Options& options();
+int device_cus();   // CU count of the current device, cached per device id (256 if the query fails)
+
 // kernel launchers (implemented in the .hip files); all enqueue on `s` and return a status
 // proj/rt != NULL: the relative projections are computed by an extra block row of the same launch
 int launch_nchw_to_c8(const float* in, void* out, int N, int C, int h, int w, int dtype, hipStream_t s,

@@ -19,10 +19,6 @@
 #include "storage.h"
 #include "warp_common.h"
 
-#ifndef MVS_ABLATE
-#define MVS_ABLATE 0
-#endif
-
 namespace mvs {
 
 // ---------------------------------------------------------------------------------------------
@@ -201,15 +197,10 @@ __global__ __launch_bounds__(256) void warp_variance_kernel(const float* __restr
 #pragma unroll
             for (int pl = 0; pl < 4; ++pl) {
                 const float* f = f0 + pl * plane_stride;
-#if MVS_ABLATE == 4  // diagnostic build: no gathers (timing floor of VALU + volume write)
-                (void)f;
-                const float4 a = ref[pl], b = ref[pl], c = ref[pl], e = ref[pl];
-#else
                 const float4 a = *reinterpret_cast<const float4*>(f + (size_t)t.o00 * 8);
                 const float4 b = *reinterpret_cast<const float4*>(f + (size_t)t.o01 * 8);
                 const float4 c = *reinterpret_cast<const float4*>(f + (size_t)t.o10 * 8);
                 const float4 e = *reinterpret_cast<const float4*>(f + (size_t)t.o11 * 8);
-#endif
                 float4 wv;
                 wv.x = fmaf(a.x, t.w00, fmaf(b.x, t.w01, fmaf(c.x, t.w10, e.x * t.w11)));
                 wv.y = fmaf(a.y, t.w00, fmaf(b.y, t.w01, fmaf(c.y, t.w10, e.y * t.w11)));
@@ -308,13 +299,7 @@ __global__ __launch_bounds__(256) void warp_variance16_kernel(const void* __rest
 
 // MVS_WARP_DEPTH_FASTEST=1 forces the depth-slab-fastest block order (default: only when the feature
 // maps exceed the L2s), so tests can reach it at small shapes
-static bool force_depth_fastest() {
-    static const bool f = [] {
-        const char* e = getenv("MVS_WARP_DEPTH_FASTEST");
-        return e && e[0] == '1';
-    }();
-    return f;
-}
+static bool force_depth_fastest() { return options().warp_depth_fastest; }
 
 int launch_warp_variance16(const void* feats16, const float* rt, const float* dv, void* var, int N, int D,
                            int h, int w, int dtype, hipStream_t s) {
@@ -322,11 +307,7 @@ int launch_warp_variance16(const void* feats16, const float* rt, const float* dv
     // The tap-cache kernel (second form, warp_variance_tc.hip) is the default here too: cfg5 0.20 ->
     // 0.15 ms, cfg3 1.84 -> 1.39 ms against the plain kernel below (MVS_WARP_TC16=0 selects it; the
     // FIRST form of the tap-cache kernel had been slower than the plain kernel with 16-bit features).
-    static const bool use_tc = [] {
-        const char* e = getenv("MVS_WARP_TC16");
-        return !(e && e[0] == '0');
-    }();
-    if (use_tc && warp_tc_fits(N, D, h, w, 2, 2))
+    if (options().warp_tc16 && warp_tc_fits(N, D, h, w, 2, 2))
         return launch_warp_variance_tc16(feats16, rt, dv, var, N, D, h, w, dtype, s);
     const unsigned nd = (D + kWarpDepthSlab - 1) / kWarpDepthSlab;
     const unsigned np = (h * w + kWarpPixPerBlock - 1) / kWarpPixPerBlock;
@@ -348,11 +329,7 @@ int launch_warp_variance(const float* feats_p, const float* rt, const float* dv,
                          int D, int h, int w, int dtype, hipStream_t s) {
     if (h < 2 || w < 2) return fail(MVS_ERR_BAD_SHAPE, "warp_variance: h,w must be >= 2");
     // Tap-cache kernel (warp_variance_tc.hip) for 2..5 views; MVS_WARP_TC=0 keeps the plain gather
-    static const bool use_tc = [] {
-        const char* e = getenv("MVS_WARP_TC");
-        return !(e && e[0] == '0');
-    }();
-    if (use_tc && warp_tc_fits(N, D, h, w, 4, dtype == MVS_F32 ? 4 : 2))
+    if (options().warp_tc && warp_tc_fits(N, D, h, w, 4, dtype == MVS_F32 ? 4 : 2))
         return launch_warp_variance_tc(feats_p, rt, dv, var, N, D, h, w, dtype, s);
     const unsigned nd = (D + kWarpDepthSlab - 1) / kWarpDepthSlab;
     const unsigned np = (h * w + kWarpPixPerBlock - 1) / kWarpPixPerBlock;

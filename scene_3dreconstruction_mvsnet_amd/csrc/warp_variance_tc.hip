@@ -21,13 +21,6 @@
 #include "storage.h"
 #include "warp_common.h"
 
-// Diagnostic builds (`make ablate11` .. `ablate14`, wrong results, timing only): 11 = 20 extra VALU per depth
-// step, 12 = volume stores predicated off at run time (the arithmetic stays), 13 = no re-gathers after a
-// block's first, 14 = 12 + 13.  Product builds leave MVS_ABLATE at 0.
-#ifndef MVS_ABLATE
-#define MVS_ABLATE 0
-#endif
-
 namespace mvs {
 
 namespace {
@@ -55,8 +48,8 @@ __device__ __forceinline__ int quad_bcast(int v, int lane) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// The tap-cache kernel (second form; the first form, 8 channels per thread, is in attic/), templated on the
-// channels per thread CPT.
+// The tap-cache kernel (second form; the first form, 8 channels per thread, is csrc/attic/warp_variance_tc_form1.hip
+// in commit c2f08ac), templated on the channels per thread CPT.
 //
 // What rocprofv3 showed for the first form (profiles/r02_warp_pmc.md): only ~240 VALU and ~5 load
 // instructions are executed per wave and depth step -- the re-gather branches are skipped at wave
@@ -82,10 +75,8 @@ __device__ __forceinline__ int quad_bcast(int v, int lane) {
 //     of depth d + q, so one pass through make_samp_key serves two depth steps; the step for d + q moves
 //     quad q's record into both quads (one bank-masked DPP row shift per field), then broadcasts lane v as
 //     before: 136 instead of 152 VALU per wave and step.
-// Measured at cfg2: 0.2345 ms (first form) -> 0.157 ms -> 0.152 ms with the pairing.  Ablation builds
-// (make ablate11 .. ablate14, kernel only): +20 VALU per step +5 us, stores predicated off -20 us, no
-// re-gathers after a block's first -23 us, neither -36 us (0.121 ms: the vector-instruction floor).  Tried
-// on top and dropped: distributing the sampling records through a per-wave LDS ring (0.159 ms, no gain);
+// Measured at cfg2: 0.2345 ms (first form) -> 0.157 ms -> 0.152 ms with the pairing (where the time goes: the
+// warp_variance_tc2 row of DESIGN.md's kernel table).  Tried on top and dropped: distributing the sampling records through a per-wave LDS ring (0.159 ms, no gain);
 // non-temporal stores (slower); depth slabs of 48 / 96 (the 5,120 blocks of slab 24 are exactly five
 // rounds of the 1,024 resident blocks).
 // ---------------------------------------------------------------------------------------------
@@ -223,20 +214,10 @@ __device__ __forceinline__ int pair_pick(int v) {
 template <int Q>
 __device__ __forceinline__ float pair_pick(float v) { return __int_as_float(pair_pick<Q>(__float_as_int(v))); }
 
-// PK = 1 (16-bit features, CPT = 4 only; experiment of round 4): the cached taps stay PACKED (8 instead of
-// 16 VGPRs per view) and are widened inside the blend at every step -- bit-identical results (widening is exact), fewer
-// registers (more resident waves), more vector instructions per step.  Measured: section 10 of DESIGN.md.
 // four waves per SIMD: the N = 5 fp32 kernel allocates 130 VGPRs when left alone and fits 128 without spills when asked to
-// (every other variant is below 128 anyway); `make ablate61`: no occupancy request, `ablate62`: five waves (spills)
-#if MVS_ABLATE == 61
-#define MVS_WARP_LB __launch_bounds__(256)
-#elif MVS_ABLATE == 62
-#define MVS_WARP_LB __launch_bounds__(256, 5)
-#else
-#define MVS_WARP_LB __launch_bounds__(256, 4)
-#endif
-template <int DT, int FDT, int NV, int CPT, int NTS, int PAIR, int PK = 0>
-__global__ MVS_WARP_LB void warp_variance_tc2_kernel(const void* __restrict__ feats_p,   // [4][N][hw][8] FDT
+// (every other variant is below 128 anyway; five waves spill)
+template <int DT, int FDT, int NV, int CPT, int NTS, int PAIR>
+__global__ __launch_bounds__(256, 4) void warp_variance_tc2_kernel(const void* __restrict__ feats_p,   // [4][N][hw][8] FDT
                                                                 const float* __restrict__ rt,
                                                                 const float* __restrict__ dv,
                                                                 void* __restrict__ var, int N, int D, int h,
@@ -291,9 +272,7 @@ __global__ MVS_WARP_LB void warp_variance_tc2_kernel(const void* __restrict__ fe
     const float qz = fmaf(r[6], fx, fmaf(r[7], fy, r[8]));
     const float tx = r[9], ty = r[10], tz = r[11];
 
-    static_assert(!PK || (CPT == 4 && FDT != MVS_F32), "packed tap cache: 16-bit features, 4 channels per thread");
-    f32x4 tap[PK ? 1 : NV][4][NH];  // cached taps: [view][00,01,10,11][16-byte piece]
-    u32x2 tapk[PK ? NV : 1][4];     // PK: the same taps as stored (4 x 16 bit)
+    f32x4 tap[NV][4][NH];  // cached taps: [view][00,01,10,11][16-byte piece]
     int key[NV];           // cell key of the cached taps
 #pragma unroll
     for (int v = 0; v < NV; ++v) key[v] = -1;
@@ -304,25 +283,14 @@ __global__ MVS_WARP_LB void warp_variance_tc2_kernel(const void* __restrict__ fe
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
             const int k = quad_bcast(keys, v);
-#if MVS_ABLATE == 13 || MVS_ABLATE == 14
-            if (k != key[v] && (key[v] == -1 || slab < 0)) {
-#else
             if (k != key[v]) {   // uniform over the lanes of a pixel: they share key and cache state
-#endif
                 const unsigned o00 = (unsigned)k >> 2, dx = (unsigned)k & 1u, dyw = (k & 2) ? (unsigned)w : 0u;
                 const unsigned b00 = plane_b + o00 * (8u * FES);
                 const unsigned soff = (unsigned)(v + 1) * view_b;
-                if constexpr (PK) {
-                    tapk[v][0] = __builtin_amdgcn_raw_buffer_load_b64(frs, (int)b00, (int)soff, 0);
-                    tapk[v][1] = __builtin_amdgcn_raw_buffer_load_b64(frs, (int)(b00 + dx * (8u * FES)), (int)soff, 0);
-                    tapk[v][2] = __builtin_amdgcn_raw_buffer_load_b64(frs, (int)(b00 + dyw * (8u * FES)), (int)soff, 0);
-                    tapk[v][3] = __builtin_amdgcn_raw_buffer_load_b64(frs, (int)(b00 + (dyw + dx) * (8u * FES)), (int)soff, 0);
-                } else {
-                    gather_tap_buf<FDT, CPT>(tap[v][0], frs, b00, soff);
-                    gather_tap_buf<FDT, CPT>(tap[v][1], frs, b00 + dx * (8u * FES), soff);
-                    gather_tap_buf<FDT, CPT>(tap[v][2], frs, b00 + dyw * (8u * FES), soff);
-                    gather_tap_buf<FDT, CPT>(tap[v][3], frs, b00 + (dyw + dx) * (8u * FES), soff);
-                }
+                gather_tap_buf<FDT, CPT>(tap[v][0], frs, b00, soff);
+                gather_tap_buf<FDT, CPT>(tap[v][1], frs, b00 + dx * (8u * FES), soff);
+                gather_tap_buf<FDT, CPT>(tap[v][2], frs, b00 + dyw * (8u * FES), soff);
+                gather_tap_buf<FDT, CPT>(tap[v][3], frs, b00 + (dyw + dx) * (8u * FES), soff);
                 key[v] = k;
             }
         }
@@ -343,20 +311,7 @@ __global__ MVS_WARP_LB void warp_variance_tc2_kernel(const void* __restrict__ fe
             // plain kernel's nesting, per component
             auto tapv = [&](int t, int j) -> f32x2 {
                 const int hh = j >> 1, q = (j & 1) * 2;
-                if constexpr (PK) {
-                    auto widen = [](unsigned d) -> f32x2 {   // two 16-bit values of one dword -> fp32 (exact)
-                        if constexpr (FDT == MVS_F16) {
-                            typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                            const h2 h = __builtin_bit_cast(h2, d);
-                            return (f32x2){(float)h[0], (float)h[1]};
-                        } else {
-                            return (f32x2){__uint_as_float(d << 16), __uint_as_float(d & 0xFFFF0000u)};
-                        }
-                    };
-                    return widen(tapk[v][t][j]);
-                } else {
-                    return (f32x2){tap[v][t][hh][q], tap[v][t][hh][q + 1]};
-                }
+                return (f32x2){tap[v][t][hh][q], tap[v][t][hh][q + 1]};
             };
             f32x2 wv[NP];
             {
@@ -398,18 +353,8 @@ __global__ MVS_WARP_LB void warp_variance_tc2_kernel(const void* __restrict__ fe
             const f32x2 m = S[j] * IN;
             o[j] = __builtin_elementwise_fma(-m, m, Q[j] * IN);
         }
-#if MVS_ABLATE == 12 || MVS_ABLATE == 14
-        if (slab < 0)
-#endif
         store_voxel_buf<DT, CPT, NTS>(vrs, out_v, o);
         out_v += dstep_v;
-#if MVS_ABLATE == 11
-        asm volatile("v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n"
-                     "v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n"
-                     "v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n"
-                     "v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n"
-                     : "+v"(out_v));
-#endif
     };
 
     if constexpr (PAIR && LPP == 8) {
@@ -483,24 +428,13 @@ int launch_tc2_dt(const void* feats_p, const float* rt, const float* dv, void* v
     }
     constexpr int pix = 256 / (32 / CPT);
     constexpr size_t fes = FDT == MVS_F32 ? 4 : 2;
-    // all views' features against the 32 MB of aggregate L2 (MVS_WARP_DEPTH_FASTEST=1 forces the order)
-    static const int force_df = [] {   // 1 = always, 0 = never (A/B runs), unset = by size
-        const char* e = getenv("MVS_WARP_DEPTH_FASTEST");
-        return e ? atoi(e) : -1;
-    }();
+    // all views' features against the 32 MB of aggregate L2 (MVS_WARP_DEPTH_FASTEST=1 / 0: always / never)
+    const int force_df = options().warp_depth_fastest_tc;
     const int df = force_df >= 0 ? force_df : ((size_t)N * h * w * 32 * fes > ((size_t)24 << 20) ? 1 : 0);
     const unsigned npb = (h * w + pix - 1) / pix, nsl = (D + slab - 1) / slab;
     const dim3 grid = df ? dim3(nsl, npb) : dim3(npb, nsl);
     // PAIR = 1: one projection pass per two depth steps (quad q of a pixel evaluates depth d + q)
-    // MVS_WARP_PACKED=1 (16-bit features only): the packed tap cache
-    static const bool packed = [] {
-        const char* e = getenv("MVS_WARP_PACKED");
-        return e && e[0] == '1';
-    }();
-    constexpr int CANPK = FDT != MVS_F32 ? 1 : 0;
-#define MVS_TC2(NV)                                                                                                        \
-    if (CANPK && packed) warp_variance_tc2_kernel<DT, FDT, NV, CPT, 0, 1, CANPK><<<grid, 256, 0, s>>>(feats_p, rt, dv, var, N, D, h, w, slab, df); \
-    else warp_variance_tc2_kernel<DT, FDT, NV, CPT, 0, 1><<<grid, 256, 0, s>>>(feats_p, rt, dv, var, N, D, h, w, slab, df);
+#define MVS_TC2(NV) warp_variance_tc2_kernel<DT, FDT, NV, CPT, 0, 1><<<grid, 256, 0, s>>>(feats_p, rt, dv, var, N, D, h, w, slab, df);
     switch (N - 1) {
         case 1: MVS_TC2(1) break;
         case 2: MVS_TC2(2) break;

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Child-process helper of tests/test_gpu_fullsize.py::test_cfg2_conv0_kernel_variants_match_oracle: conv0 at the bench
 size (cfg2) against the oracle with the bounds of test_cfg2_every_layer_matches_oracle[0], and on the heavy-tailed volume
-of test_winograd_layers_on_a_heavy_tailed_nonnegative_volume[0], under whatever MVS_CONV0_SPLIT the parent set (the
-kernel selection is read once per process)."""
+of test_winograd_layers_on_a_heavy_tailed_nonnegative_volume[0], with the conv0 kernel MVS_CONV0_SPLIT selects (the
+parent sets it: the selection is read once per process)."""
 import os
 import sys
 

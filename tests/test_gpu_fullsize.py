@@ -213,11 +213,11 @@ def test_winograd_layers_on_a_heavy_tailed_nonnegative_volume(cfg2, layer, shape
     assert rel_l1(got, want) < 5e-6
 
 
-@pytest.mark.parametrize("split", ["0", "2"])
+@pytest.mark.parametrize("split", ["0"])
 def test_cfg2_conv0_kernel_variants_match_oracle(split):
-    """conv0's other kernels at FULL size with the per-layer bounds of test_cfg2_every_layer_matches_oracle[0]: the
-    fp32-MFMA Winograd kernel (MVS_CONV0_SPLIT=0; the default until round 4) and the first form of the split-operand
-    kernel (=2).  Selection is read once per process -> child process (tests/conv0_check.py)."""
+    """conv0's other kernel at FULL size with the per-layer bounds of test_cfg2_every_layer_matches_oracle[0]: the
+    fp32-MFMA Winograd kernel (MVS_CONV0_SPLIT=0; the default until round 4).  Selection is read once per process ->
+    child process (tests/conv0_check.py)."""
     import os
     import subprocess
     import sys

@@ -317,7 +317,6 @@ def test_nonfinite_coordinates_give_nan_like_torch():
     {"MVS_CONV0_WINO": "0", "MVS_CONV_WINO": "0"},   # direct MFMA kernels (no Winograd transform anywhere)
     {"MVS_CONV0_SPLIT": "0"},    # conv0 on the fp32 MFMA (Winograd F(4,3)) instead of split bf16 operands
     {"MVS_SPLIT_LAYERS": "0"},   # conv2 .. conv4 on the fp32 MFMA (Winograd F(2,3) / generic kernels)
-    {"MVS_CONV0_SPLIT": "2"},    # the split-operand conv0 in its first form (one tile per 4-wave block)
     {"MVS_FORCE_DIRECT": "1"},   # VALU direct convolutions for every layer
     {"MVS_FUSE_PROB": "0"},      # conv11 and prob as two launches
     {"MVS_TAIL_SPLIT": "0"},     # the fused tail's transposed convolution on the fp32 MFMA (conv11_prob_priv)
@@ -335,33 +334,6 @@ def test_optin_kernel_variants(env):
     r = subprocess.run([sys.executable, os.path.join(here, "variant_check.py")], env=child_env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
-
-
-def test_packed_tap_cache_is_bit_identical():
-    """MVS_WARP_PACKED=1 (round-4 experiment): the 16-bit taps stay packed in the register cache and are
-    widened inside the blend -- the variance volume must be the default kernel's, bit for bit, for fp16 and bf16."""
-    import os
-    import subprocess
-    import sys
-    code = (
-        "import sys, hashlib, torch; sys.path.insert(0, %r)\n"
-        "from scene_3dreconstruction_mvsnet_amd import _lib, synthetic\n"
-        "for st in ('f16', 'bf16'):\n"
-        "    dt = _lib.dtype_code(st); N, h, w, D = 5, 40, 56, 48\n"
-        "    f = torch.from_numpy(synthetic.random_features(N, 32, h, w, seed=3)).cuda()\n"
-        "    p = torch.from_numpy(synthetic.cameras(N, h, w, yaw_deg=1.0)).cuda()\n"
-        "    dv = torch.from_numpy(synthetic.depth_values(D)).cuda()\n"
-        "    ws = _lib.alloc_workspace(N, 32, D, h, w, 'cuda:0', dt)\n"
-        "    v = _lib.warp_variance(f, _lib.relative_proj(p), dv, ws, dtype=dt)\n"
-        "    print(st, hashlib.sha1(v.cpu().view(torch.int16).numpy().tobytes()).hexdigest())\n"
-    ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),)
-    outs = []
-    for pk in ("0", "1"):
-        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MVS_WARP_PACKED=pk), capture_output=True,
-                           text=True, timeout=600)
-        assert r.returncode == 0, r.stdout + r.stderr
-        outs.append(r.stdout)
-    assert outs[0] == outs[1] and outs[0].count("\n") == 2, outs
 
 
 @pytest.mark.parametrize("storage", ["f16", "bf16"])
