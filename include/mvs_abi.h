@@ -35,7 +35,8 @@ extern "C" {
 /* 2 (round 4): + mvs_feature_net_fmt / mvs_forward_images_fmt (uint8 images); mvs_warp_conv0 removed (it left in round
  * 3 without a bump); the packed weight blob grew (split-operand conv0 panel) and lost the round-2 conv0 panels.
  * A packed blob (mvs_pack_weights / mvs_pack_feature_weights) is valid ONLY for the library version that produced it:
- * never cache one across builds -- re-pack from the state_dict (4 MB, milliseconds). */
+ * never cache one across builds -- re-pack from the state_dict (4 MB, milliseconds).
+ * Added within version 2, without a bump (additive; packed blobs unchanged): mvs_depth_infer_views. */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {
@@ -145,6 +146,22 @@ int mvs_depth_infer(const float* feats, const float* proj, const float* depth_va
                     const void* weights_blob, float* depth_out, float* conf_out, void* workspace,
                     size_t workspace_bytes, int N, int C, int D, int h, int w, int dtype,
                     void* stream);
+
+/* mvs_depth_infer with the N views taken from a bank of V NCHW feature maps, so that FeatureNet runs
+ * once per image of a scan instead of once per map that reads it (reference models/mvsnet.py:125 runs
+ * it on every view of every sample).  Results are bit-identical to mvs_depth_infer on the gathered
+ * features feats[view_idx[0]], ..., feats[view_idx[N-1]].
+ *   feats     dev fp32 [V][C][h][w]  (any V >= 1; e.g. FeatureNet outputs of every view of a scan)
+ *   view_idx  HOST int32 [N]: view_idx[0] = reference view, 1..N-1 = source views; each in [0, V);
+ *             repeats allowed.  Copied into the launch; not read after the call returns.
+ *   proj      dev fp32 [N][4][4] in view_idx order; other arguments as mvs_depth_infer
+ *             (workspace of mvs_query_workspace(N, ...) bytes).
+ * An index outside [0, V) or V < 1 returns MVS_ERR_BAD_SHAPE, a NULL view_idx MVS_ERR_NULL; nothing
+ * is enqueued then. */
+int mvs_depth_infer_views(const float* feats, int V, const int* view_idx, const float* proj,
+                          const float* depth_values, const void* weights_blob, float* depth_out,
+                          float* conf_out, void* workspace, size_t workspace_bytes, int N, int C,
+                          int D, int h, int w, int dtype, void* stream);
 
 /* Stand-alone ops with reference layouts (API parity with models/module.py).
  * mvs_homo_warp: src_fea dev fp32 [C][h][w], rt dev fp32 [12] -> out dev fp32 [C][D][h][w]

@@ -46,7 +46,7 @@ SYMBOLS = (
     "mvs_filter_compose", "mvs_filter_depth",
     "mvs_query_feature_blob", "mvs_pack_feature_weights", "mvs_query_feature_workspace",
     "mvs_feature_layer", "mvs_feature_net", "mvs_query_forward_workspace", "mvs_forward_images",
-    "mvs_feature_net_fmt", "mvs_forward_images_fmt",
+    "mvs_feature_net_fmt", "mvs_forward_images_fmt", "mvs_depth_infer_views",
 )
 
 # mvs_image_format (include/mvs_abi.h)
@@ -97,6 +97,8 @@ def load():
         lib.mvs_softargmin_conf.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]
         lib.mvs_depth_infer.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                         _i, _i, _i, _i, _i, _i, _vp]
+        lib.mvs_depth_infer_views.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                              _i, _i, _i, _i, _i, _i, _vp]
         lib.mvs_homo_warp.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]
         lib.mvs_depth_regression.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp]
         lib.mvs_query_feature_blob.argtypes = [ctypes.POINTER(_sz)]
@@ -297,6 +299,55 @@ def depth_infer(feats, proj, depth_values, blob, workspace, depth_out, conf_out,
                                  _stream(feats.device)))
 
 
+def _view_ids_arg(view_ids):
+    """view_ids (a sequence of ints or a CPU integer tensor) -> contiguous host int32 array [N].  A tensor
+    on another device is refused: reading it here would synchronise with that device."""
+    import numpy as np
+    if isinstance(view_ids, torch.Tensor):
+        if view_ids.device.type != "cpu":
+            raise RuntimeError(f"view_ids must be a host sequence or a CPU tensor (got a tensor on {view_ids.device}): "
+                               "the view table travels in the kernel arguments, reading device memory would sync")
+        if view_ids.is_floating_point() or view_ids.is_complex():
+            raise RuntimeError(f"view_ids must be integers, got {view_ids.dtype}")
+        view_ids = view_ids.numpy()
+    ids = np.asarray(view_ids)
+    if ids.ndim != 1 or ids.size < 1 or ids.dtype.kind not in "iu":
+        raise RuntimeError(f"view_ids must be a non-empty 1-D sequence of integers, got shape {ids.shape} "
+                           f"dtype {ids.dtype}")
+    if ids.min() < np.iinfo(np.int32).min or ids.max() > np.iinfo(np.int32).max:
+        raise RuntimeError("view_ids do not fit int32")
+    return np.ascontiguousarray(ids, dtype=np.int32)
+
+
+def depth_infer_views(feats, view_ids, proj, depth_values, blob, workspace, depth_out, conf_out, dtype=MVS_F32):
+    """depth_infer with the N views picked from a bank: feats [V,32,h,w] fp32 (any V), view_ids [N] host ints
+    (entry 0 = reference view; repeats allowed; the library rejects any outside [0, V)), proj [N,4,4] in
+    view_ids order, depth_values [D]; outputs are written into depth_out / conf_out [h,w]."""
+    ids = _view_ids_arg(view_ids)
+    N = ids.shape[0]
+    if feats.dim() != 4 or feats.shape[1] != 32:
+        raise RuntimeError(f"depth_infer_views: feats must be [V,32,h,w], got {tuple(feats.shape)}")
+    V, C, h, w = feats.shape
+    if tuple(proj.shape) != (N, 4, 4):
+        raise RuntimeError(f"depth_infer_views: proj must be [N,4,4] = [{N},4,4] for {N} view ids, got {tuple(proj.shape)}")
+    if depth_values.dim() != 1:
+        raise RuntimeError(f"depth_infer_views: depth_values must be [D], got {tuple(depth_values.shape)}")
+    for name, t in (("depth_out", depth_out), ("conf_out", conf_out)):
+        if tuple(t.shape) != (h, w) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"depth_infer_views: {name} must be a contiguous float32 [{h},{w}] tensor, "
+                               f"got {t.dtype} {tuple(t.shape)}")
+    feats = _dev_f32(feats, "features")
+    proj = _dev_f32(proj, "proj_matrices")
+    depth_values = _dev_f32(depth_values, "depth_values")
+    if not (depth_out.is_cuda and conf_out.is_cuda and workspace.is_cuda):
+        raise RuntimeError("depth_infer_views: outputs and workspace must live on the GPU")
+    D = depth_values.shape[0]
+    check(load().mvs_depth_infer_views(feats.data_ptr(), V, ids.ctypes.data, proj.data_ptr(), depth_values.data_ptr(),
+                                       blob.data_ptr(), depth_out.data_ptr(), conf_out.data_ptr(),
+                                       workspace.data_ptr(), workspace.numel(), N, C, D, h, w, dtype,
+                                       _stream(feats.device)))
+
+
 def alloc_workspace(N, C, D, h, w, device, dtype=MVS_F32) -> torch.Tensor:
     nbytes = query_workspace(N, C, D, h, w, dtype)
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -467,14 +518,19 @@ def _image_arg(imgs, what):
     return imgs, MVS_IMG_F32_CHW, imgs.shape[0], imgs.shape[2], imgs.shape[3]
 
 
-def feature_net(imgs, fblob, workspace=None):
-    """FeatureNet.forward on the GPU: imgs [N,3,H,W] fp32 (or uint8, see _image_arg) -> [N,32,H/4,W/4] fp32 (NCHW)."""
+def feature_net(imgs, fblob, workspace=None, out=None):
+    """FeatureNet.forward on the GPU: imgs [N,3,H,W] fp32 (or uint8, see _image_arg) -> [N,32,H/4,W/4] fp32 (NCHW),
+    written into `out` when given (a contiguous tensor of that shape)."""
     imgs, fmt, N, H, W = _image_arg(imgs, "feature_net")
     nbytes = query_feature_workspace(N, H, W)
     if workspace is None:
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=imgs.device)
     h4, w4 = ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1
-    out = torch.empty((N, 32, h4, w4), dtype=torch.float32, device=imgs.device)
+    if out is None:
+        out = torch.empty((N, 32, h4, w4), dtype=torch.float32, device=imgs.device)
+    elif tuple(out.shape) != (N, 32, h4, w4) or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != imgs.device:
+        raise RuntimeError(f"feature_net: out must be a contiguous float32 [{N},32,{h4},{w4}] tensor on {imgs.device}")
     check(load().mvs_feature_net_fmt(imgs.data_ptr(), fmt, fblob.data_ptr(), out.data_ptr(), workspace.data_ptr(),
                                      workspace.numel(), N, H, W, _stream(imgs.device)))
     return out

@@ -193,8 +193,9 @@ int mvs_relative_proj(const float* proj, float* rt_out, int N, void* stream) {
 
 // feats == NULL: the C8-planar feature copy (fp32, or the storage dtype when the 16-bit gather is
 // on) already sits in the workspace -- written there by FeatureNet's last layer (featnet.hip).
+// Otherwise view n of the map is feats[views.v[n]] (an identity table for N contiguous views).
 // proj != NULL (and feats != NULL): `rt` is an OUTPUT, filled by an extra block of the transpose launch
-static int warp_variance_impl(const float* feats, const float* rt, const float* depth_values,
+static int warp_variance_impl(const float* feats, const ViewTable& views, const float* rt, const float* depth_values,
                               void* var_out, void* workspace, size_t workspace_bytes, int N, int C, int D,
                               int h, int w, int dtype, void* stream, const float* proj = nullptr) {
     if (!depth_values || !var_out || !workspace || (N > 1 && !rt))
@@ -209,11 +210,13 @@ static int warp_variance_impl(const float* feats, const float* rt, const float* 
     float* feats_t = reinterpret_cast<float*>(static_cast<char*>(workspace) + W.feats_t);
     if (feat16_gather() && dtype != MVS_F32) {
         if (feats)
-            if (int st = launch_nchw_to_c8(feats, feats_t, N, C, h, w, dtype, s, proj, const_cast<float*>(rt))) return st;
+            if (int st = launch_nchw_to_c8(feats, views, feats_t, N, C, h, w, dtype, s, proj, const_cast<float*>(rt)))
+                return st;
         return launch_warp_variance16(feats_t, rt, depth_values, var_out, N, D, h, w, dtype, s);
     }
     if (feats)
-        if (int st = launch_nchw_to_c8(feats, feats_t, N, C, h, w, MVS_F32, s, proj, const_cast<float*>(rt))) return st;
+        if (int st = launch_nchw_to_c8(feats, views, feats_t, N, C, h, w, MVS_F32, s, proj, const_cast<float*>(rt)))
+            return st;
     return launch_warp_variance(feats_t, rt, depth_values, var_out, N, D, h, w, dtype, s);
 }
 
@@ -221,8 +224,8 @@ int mvs_warp_variance(const float* feats, const float* rt, const float* depth_va
                       void* var_out, void* workspace, size_t workspace_bytes, int N, int C, int D,
                       int h, int w, int dtype, void* stream) {
     if (!feats) return fail(MVS_ERR_NULL, "mvs_warp_variance: NULL argument");
-    return warp_variance_impl(feats, rt, depth_values, var_out, workspace, workspace_bytes, N, C, D, h, w,
-                              dtype, stream);
+    return warp_variance_impl(feats, identity_views(N), rt, depth_values, var_out, workspace, workspace_bytes, N, C,
+                              D, h, w, dtype, stream);
 }
 
 // CostRegNet from the variance volume (models/mvsnet.py:64-73)
@@ -303,8 +306,9 @@ int mvs_softargmin_conf(const float* cost, const float* depth_values, float* dep
                              static_cast<hipStream_t>(stream));
 }
 
-// feats == NULL: features already in the workspace's C8 slot (see warp_variance_impl)
-static int depth_infer_impl(const float* feats, const float* proj, const float* depth_values,
+// feats == NULL: features already in the workspace's C8 slot (see warp_variance_impl); otherwise
+// view n is feats[views.v[n]], with the table validated by the caller
+static int depth_infer_impl(const float* feats, const ViewTable& views, const float* proj, const float* depth_values,
                             const void* weights_blob, float* depth_out, float* conf_out, void* workspace,
                             size_t workspace_bytes, int N, int C, int D, int h, int w, int dtype,
                             void* stream) {
@@ -332,8 +336,8 @@ static int depth_infer_impl(const float* feats, const float* proj, const float* 
     const size_t sub_bytes = workspace_bytes - (size_t)(sub - ws);
     // The variance volume is materialised and conv0 runs as its own kernel: a fused producer/consumer
     // kernel measured 1.40 ms against 0.16 + 0.34 ms at cfg2 (csrc/attic/warp_conv0_fused.hip in commit c2f08ac).
-    if ((st = warp_variance_impl(feats, rt, depth_values, var, workspace, workspace_bytes, N, C, D, h, w, dtype,
-                                 stream, fold_proj ? proj : nullptr)))
+    if ((st = warp_variance_impl(feats, views, rt, depth_values, var, workspace, workspace_bytes, N, C, D, h, w,
+                                 dtype, stream, fold_proj ? proj : nullptr)))
         return st;
     if ((st = costreg_impl(var, weights_blob, cost, sub, sub_bytes, D, h, w, dtype, stream))) return st;
     return mvs_softargmin_conf(cost, depth_values, depth_out, conf_out, D, h, w, stream);
@@ -344,7 +348,26 @@ int mvs_depth_infer(const float* feats, const float* proj, const float* depth_va
                     size_t workspace_bytes, int N, int C, int D, int h, int w, int dtype,
                     void* stream) {
     if (!feats) return fail(MVS_ERR_NULL, "mvs_depth_infer: NULL argument");
-    return depth_infer_impl(feats, proj, depth_values, weights_blob, depth_out, conf_out, workspace,
+    return depth_infer_impl(feats, identity_views(N), proj, depth_values, weights_blob, depth_out, conf_out,
+                            workspace, workspace_bytes, N, C, D, h, w, dtype, stream);
+}
+
+// mvs_depth_infer with its N views picked from a bank of V feature maps: only the table the
+// transpose reads differs (the identity table with V = N is mvs_depth_infer)
+int mvs_depth_infer_views(const float* feats, int V, const int* view_idx, const float* proj,
+                          const float* depth_values, const void* weights_blob, float* depth_out,
+                          float* conf_out, void* workspace, size_t workspace_bytes, int N, int C,
+                          int D, int h, int w, int dtype, void* stream) {
+    if (!feats || !view_idx) return fail(MVS_ERR_NULL, "mvs_depth_infer_views: NULL argument");
+    if (V < 1) return fail(MVS_ERR_BAD_SHAPE, "mvs_depth_infer_views: bank of V=%d feature maps", V);
+    if (int st = check_dims(N, C, D, h, w, dtype)) return st;   // N <= kMaxViews before the table is read
+    ViewTable views{};
+    for (int n = 0; n < N; ++n) {
+        if (view_idx[n] < 0 || view_idx[n] >= V)
+            return fail(MVS_ERR_BAD_SHAPE, "mvs_depth_infer_views: view_idx[%d]=%d outside [0,%d)", n, view_idx[n], V);
+        views.v[n] = view_idx[n];
+    }
+    return depth_infer_impl(feats, views, proj, depth_values, weights_blob, depth_out, conf_out, workspace,
                             workspace_bytes, N, C, D, h, w, dtype, stream);
 }
 
@@ -499,8 +522,8 @@ int mvs_forward_images_fmt(const void* imgs, int image_format, const float* proj
         return st;
     if (narrow)
         if (int st = launch_narrow_features(c8, feats_t, (size_t)N * kC * h * w, dtype, s)) return st;
-    return depth_infer_impl(nullptr, proj, depth_values, weights_blob, depth_out, conf_out, workspace,
-                            Wd.total, N, kC, D, h, w, dtype, stream);
+    return depth_infer_impl(nullptr, identity_views(N), proj, depth_values, weights_blob, depth_out, conf_out,
+                            workspace, Wd.total, N, kC, D, h, w, dtype, stream);
 }
 
 int mvs_homo_warp(const float* src_fea, const float* rt, const float* depth_values, float* out,

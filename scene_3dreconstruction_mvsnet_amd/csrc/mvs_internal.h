@@ -251,10 +251,22 @@ struct Options {
 const Options& options();
 int device_cus();   // CU count of the current device, cached per device id (256 if the query fails)
 
+// Which feature map of a bank [V][C][h][w] each of the N views of a map reads: v[0] = reference view.
+// A kernel argument by value (256 bytes), never device memory.  N <= kMaxViews is check_dims' bound.
+constexpr int kMaxViews = 64;
+struct ViewTable {
+    int32_t v[kMaxViews];
+};
+inline ViewTable identity_views(int N) {
+    ViewTable t{};
+    for (int n = 0; n < N && n < kMaxViews; ++n) t.v[n] = n;
+    return t;
+}
+
 // kernel launchers (implemented in the .hip files); all enqueue on `s` and return a status
 // proj/rt != NULL: the relative projections are computed by an extra block row of the same launch
-int launch_nchw_to_c8(const float* in, void* out, int N, int C, int h, int w, int dtype, hipStream_t s,
-                      const float* proj = nullptr, float* rt = nullptr);
+int launch_nchw_to_c8(const float* in, const ViewTable& views, void* out, int N, int C, int h, int w, int dtype,
+                      hipStream_t s, const float* proj = nullptr, float* rt = nullptr);
 int launch_warp_variance16(const void* feats16, const float* rt, const float* dv, void* var, int N, int D,
                            int h, int w, int dtype, hipStream_t s);
 int launch_relative_proj(const float* proj, float* rt, int N, hipStream_t s);

@@ -82,13 +82,14 @@ __global__ void relative_proj_kernel(const float* __restrict__ proj, float* __re
 }
 
 // ---------------------------------------------------------------------------------------------
-// [N][C=32][h][w] -> C8-planar [4][N][h][w][8]; one block transposes 32 channels x 64 pixels
-// through LDS.
+// in[views.v[n]] of a bank [V][C=32][h][w] -> C8-planar [4][N][h][w][8]; one block transposes 32
+// channels x 64 pixels through LDS.  The view table travels by value in the kernel arguments (an
+// identity table for N contiguous views), so picking views costs no copy and no lifetime rule.
 // ---------------------------------------------------------------------------------------------
 // proj != NULL: one extra block row (blockIdx.y == N) computes the relative projections of
 // models/module.py:107-109 on the side -- a separate 1-block launch costs 7-8 us of a 950 us map.
 template <int DT>
-__global__ __launch_bounds__(256) void nchw_to_c8_kernel(const float* __restrict__ in,
+__global__ __launch_bounds__(256) void nchw_to_c8_kernel(const float* __restrict__ in, const ViewTable views,
                                                          void* __restrict__ out, int N, int hw,
                                                          const float* __restrict__ proj, float* __restrict__ rt) {
     __shared__ float tile[32][65];
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(256) void nchw_to_c8_kernel(const float* __restrict
     const int n = blockIdx.y;
     const int p0 = blockIdx.x * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // 64 x 4
-    const float* src = in + (size_t)n * 32 * hw;
+    const float* src = in + (size_t)views.v[n] * 32 * hw;
 #pragma unroll
     for (int c = ty; c < 32; c += 4) {
         const int p = p0 + tx;
@@ -116,15 +117,15 @@ __global__ __launch_bounds__(256) void nchw_to_c8_kernel(const float* __restrict
         }
 }
 
-int launch_nchw_to_c8(const float* in, void* out, int N, int C, int h, int w, int dtype, hipStream_t s,
-                      const float* proj, float* rt) {
+int launch_nchw_to_c8(const float* in, const ViewTable& views, void* out, int N, int C, int h, int w, int dtype,
+                      hipStream_t s, const float* proj, float* rt) {
     (void)C;
+    if (N < 1 || N > kMaxViews) return fail(MVS_ERR_BAD_SHAPE, "nchw_to_c8: N=%d outside [1,%d]", N, kMaxViews);
     const int hw = h * w;
-    if (N > 256) proj = nullptr;   // the side block has one thread per source view
     dim3 grid((hw + 63) / 64, proj ? N + 1 : N);
-    if (dtype == MVS_F32) nchw_to_c8_kernel<MVS_F32><<<grid, 256, 0, s>>>(in, out, N, hw, proj, rt);
-    else if (dtype == MVS_F16) nchw_to_c8_kernel<MVS_F16><<<grid, 256, 0, s>>>(in, out, N, hw, proj, rt);
-    else if (dtype == MVS_BF16) nchw_to_c8_kernel<MVS_BF16><<<grid, 256, 0, s>>>(in, out, N, hw, proj, rt);
+    if (dtype == MVS_F32) nchw_to_c8_kernel<MVS_F32><<<grid, 256, 0, s>>>(in, views, out, N, hw, proj, rt);
+    else if (dtype == MVS_F16) nchw_to_c8_kernel<MVS_F16><<<grid, 256, 0, s>>>(in, views, out, N, hw, proj, rt);
+    else if (dtype == MVS_BF16) nchw_to_c8_kernel<MVS_BF16><<<grid, 256, 0, s>>>(in, views, out, N, hw, proj, rt);
     else return fail(MVS_ERR_BAD_DTYPE, "nchw_to_c8: unknown dtype %d", dtype);
     return check_hip(hipGetLastError(), "nchw_to_c8 launch");
 }

@@ -52,6 +52,15 @@ def _worker(dataset, shm_name, slot_bytes, tasks, results):
         shm.close()
 
 
+def _unpin(pool):
+    """Undo a consumer's page-locking of the segment (eval_driver._pin_pool_memory sets `_unpin`) while it is still
+    mapped: a registration outliving the mapping would make the HIP runtime treat later allocations at the same
+    addresses as page-locked memory and copy from pages that are gone."""
+    unpin = pool.__dict__.pop("_unpin", None)
+    if unpin is not None:
+        unpin()
+
+
 class DecoderPool:
     """`for sample in pool.imap(indices): ...; pool.release(sample)` -- samples in order."""
 
@@ -100,6 +109,7 @@ class DecoderPool:
                 p.terminate()
         self._workers, self._tasks = [], []
         if self._shm is not None:
+            _unpin(self)
             self._shm.close()
             try:
                 self._shm.unlink()
@@ -245,6 +255,7 @@ class ViewDecoderPool:
                 p.terminate()
         self._workers = []
         if self._shm is not None:
+            _unpin(self)
             try:
                 self._shm.close()
             except BufferError:      # the consumer still holds views of the cache (or page-locked it)

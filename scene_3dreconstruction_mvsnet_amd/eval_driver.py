@@ -15,6 +15,10 @@ Sharding replaces `nn.DataParallel` (eval.py:309): rank r of R processes dataset
 (scene_3dreconstruction_mvsnet_amd.sharding); every rank writes its own files, so no collective is
 needed here.  Loading + H2D of the next sample, the forward pass and the D2H + file encoding of the
 previous ones run concurrently (loader thread + copy stream, compute stream, writer pool).
+
+`reuse_features=True` keeps a device bank of FeatureNet outputs keyed by image path (FeatureSlots):
+each view's image is copied to the device and run through FeatureNet once while it stays resident,
+instead of once per sample that reads it (reference models/mvsnet.py:125).
 """
 from __future__ import annotations
 
@@ -126,10 +130,16 @@ def _pin_pool_memory(pool) -> bool:
         return shm is not None
     import ctypes
     addr = ctypes.addressof(ctypes.c_char.from_buffer(shm.buf))
-    rc = torch.cuda.cudart().cudaHostRegister(addr, shm.size, 0)
+    cudart = torch.cuda.cudart()
+    rc = cudart.cudaHostRegister(addr, shm.size, 0)
     if int(rc) != 0:
         return False            # not fatal: the copies stay pageable
     pool._pinned_name = shm.name
+
+    def unpin():                # called by the pool's close() before it unmaps the segment
+        cudart.cudaHostUnregister(addr)
+        pool._pinned_name = None
+    pool._unpin = unpin
     return True
 
 
@@ -153,11 +163,55 @@ def _decoded_samples(dataset, indices, decoders, decoder_pool):
             yield futs.pop(pos).result(), (lambda: None)
 
 
+class FeatureSlots:
+    """Assigns the slots of a feature bank of `capacity` views to view keys (image paths), least
+    recently used out.  Pure bookkeeping: `plan(keys)` for one sample returns
+      slots  the bank slot of each of the sample's views (entry 0 = reference view), and
+      new    [(i, slot)]: views not resident before, whose features must be written into `slot` from
+             the sample's image i (once per distinct key, even if the sample repeats it).
+    A view of the sample being planned is never evicted for another view of the same sample.
+    """
+
+    def __init__(self, capacity: int):
+        if capacity < 1:
+            raise ValueError(f"a feature bank needs at least one slot, got {capacity}")
+        self.capacity = capacity
+        self._slot_of = {}       # key -> slot, least recently used first
+        self._free = list(range(capacity - 1, -1, -1))
+
+    def plan(self, keys):
+        keys = list(keys)
+        if len(set(keys)) > self.capacity:
+            raise ValueError(f"a sample with {len(set(keys))} distinct views does not fit a feature bank of "
+                             f"{self.capacity} slots")
+        mine = set(keys)
+        slots, new = [], []
+        for i, k in enumerate(keys):
+            slot = self._slot_of.pop(k, None)
+            if slot is None:
+                if not self._free:
+                    victim = next(v for v in self._slot_of if v not in mine)   # oldest entry of another sample
+                    self._free.append(self._slot_of.pop(victim))
+                slot = self._free.pop()
+                new.append((i, slot))
+            self._slot_of[k] = slot            # (re-)inserted last = most recently used
+            slots.append(slot)
+        return slots, new
+
+    def resident(self):
+        """Keys with a slot, least recently used first."""
+        return list(self._slot_of)
+
+
 def _loader(dataset, indices, device, copy_stream, q: "queue.Queue", decoders: int = 16, decoder_pool=None,
-            keep_ref_image: bool = True):
+            keep_ref_image: bool = True, feature_slots: int = 0):
     """Producer thread: decoded samples (see _decoded_samples) are handed over in order and copied to
-    the device on `copy_stream` while the GPU computes the previous sample."""
+    the device on `copy_stream` while the GPU computes the previous sample.
+    feature_slots > 0 (reuse_features): the slot bookkeeping of the feature bank runs here, in sample
+    order; only the images of views that are not resident are copied, and the item carries
+    (new images or None, proj, depth_values) plus (their slots, the sample's slot ids)."""
     in_flight = []      # (copy-done event, release callback) of samples whose pinned-slot copies may still run
+    planner = FeatureSlots(feature_slots) if feature_slots > 0 else None
     try:
         it = _decoded_samples(dataset, indices, decoders, decoder_pool)
         for pos, idx in enumerate(indices):
@@ -169,10 +223,21 @@ def _loader(dataset, indices, device, copy_stream, q: "queue.Queue", decoders: i
             t0 = _now()
             per_view = isinstance(s["imgs"], (list, tuple))     # ViewDecoderPool: one shared-memory array per view
             pinned = False
+            plan, pick = None, None
+            if planner is not None:
+                slot_ids, new = planner.plan([p for p, _ in dataset.view_plan(idx)[1]])
+                pick = [i for i, _ in new]      # the sample's images that go to FeatureNet
+                plan = ([slot for _, slot in new], slot_ids)
             # uint8 pixels (EvalDataset(image_dtype="uint8")) travel as they are: the model divides by 255 on the device
             u8 = (np.asarray(s["imgs"][0]) if per_view else np.asarray(s["imgs"])).dtype == np.uint8
             idt = torch.uint8 if u8 else torch.float32
-            src = [None if per_view else torch.as_tensor(np.asarray(s["imgs"]), dtype=idt)[None]] + \
+            if per_view or pick == []:
+                first = None                    # per-view copies below / every view resident
+            elif pick is not None:
+                first = torch.as_tensor(np.ascontiguousarray(np.asarray(s["imgs"])[pick]), dtype=idt)
+            else:
+                first = torch.as_tensor(np.asarray(s["imgs"]), dtype=idt)[None]
+            src = [first] + \
                   [torch.as_tensor(np.asarray(s[k]), dtype=torch.float32)[None] for k in ("proj_matrices", "depth_values")]
             _tick("loader.prep", t0)
             t0 = _now()
@@ -181,14 +246,18 @@ def _loader(dataset, indices, device, copy_stream, q: "queue.Queue", decoders: i
                 # faster here than an explicit host copy into a torch pinned buffer (1.5-2 GB/s)
                 if per_view:   # N copies straight from the cache slots into the [1,N,3,H,W] device tensor
                     pinned = _pin_pool_memory(decoder_pool)
-                    views = [torch.from_numpy(v) for v in s["imgs"]]
-                    imgs_dev = torch.empty((1, len(views)) + tuple(views[0].shape), dtype=idt, device=device)
+                    views = [torch.from_numpy(s["imgs"][i]) for i in (range(len(s["imgs"])) if pick is None else pick)]
                     small = [t.to(device) for t in src[1:]]   # pageable (synchronous) copies first: behind the
-                    for i, v in enumerate(views):             # asynchronous ones they would wait for them
-                        imgs_dev[0, i].copy_(v, non_blocking=pinned)
+                    imgs_dev = None                           # asynchronous ones they would wait for them
+                    if views:                                 # (reuse_features: [k,3,H,W], only the new views)
+                        shape = ((1, len(views)) if pick is None else (len(views),)) + tuple(views[0].shape)
+                        imgs_dev = torch.empty(shape, dtype=idt, device=device)
+                        flat = imgs_dev[0] if pick is None else imgs_dev
+                        for i, v in enumerate(views):
+                            flat[i].copy_(v, non_blocking=pinned)
                     dev = [imgs_dev] + small
                 else:
-                    dev = [t.to(device) for t in src]
+                    dev = [None if t is None else t.to(device) for t in src]
                 ready = torch.cuda.Event()
                 ready.record(copy_stream)
             _tick("loader.h2d", t0)
@@ -204,7 +273,7 @@ def _loader(dataset, indices, device, copy_stream, q: "queue.Queue", decoders: i
             else:
                 release()                            # pageable copies have left the slot when .to() returns
             t0 = _now()
-            q.put((idx, s, dev, ready))
+            q.put((idx, s, dev, ready, plan))
             _tick("loader.q_put", t0)
         for ev, rel in in_flight:
             ev.synchronize()
@@ -216,7 +285,7 @@ def _loader(dataset, indices, device, copy_stream, q: "queue.Queue", decoders: i
 
 def save_depth_sharded(model, dataset, outdir: str, rank: int = 0, world: int = 1, device=None,
                        writers: int = 16, save_images: bool = True, decoders: int = 16, decoder_procs: int = 0,
-                       decoder_pool=None):
+                       decoder_pool=None, reuse_features: bool = False, feature_slots: int = 64):
     """Run `model` over dataset items rank::world and write the reference's per-view files.
 
     dataset[i] -> dict with "imgs" [N,3,H,W], "proj_matrices" [N,4,4], "depth_values" [D],
@@ -229,11 +298,26 @@ def save_depth_sharded(model, dataset, outdir: str, rank: int = 0, world: int = 
     host time went.  `decoder_procs` > 0 (or a ready `decoder_pool`) decodes in worker processes with a
     shared-memory ring instead of threads (decoder_pool.DecoderPool: the counterpart of the reference's
     DataLoader workers, eval.py:305).
+    `reuse_features` runs FeatureNet once per view while the view stays in a device bank of
+    `feature_slots` feature maps (keyed by image path from `dataset.view_plan`, least recently used
+    out) and computes each map from that bank (model.extract_features / model.forward_features).  The
+    files and the return value are byte-identical to reuse_features=False.  It needs a dataset with
+    `view_plan` and at least one sample's views of slots.  Reuse happens within this rank's items: with
+    the interleaved rank::world sharding, many ranks see few common views.
     Returns the list of dataset indices this rank processed.
     """
     device = device or torch.device("cuda", torch.cuda.current_device())
-    model = model.to(device).eval()
     mine = sharding.shard_units(len(dataset), rank, world)
+    if reuse_features:   # refused before any work starts
+        if not hasattr(dataset, "view_plan"):
+            raise ValueError("reuse_features needs a dataset with view_plan() (image path of every view), "
+                             "e.g. dataset_eval.EvalDataset")
+        if not all(hasattr(model, a) for a in ("extract_features", "forward_features")):
+            raise ValueError("reuse_features needs a model with extract_features / forward_features (MVSNet)")
+        n_max = max((len(dataset.view_plan(i)[1]) for i in mine[:1]), default=0)
+        if feature_slots < max(1, n_max):
+            raise ValueError(f"feature_slots={feature_slots} is below the {n_max} views of one sample")
+    model = model.to(device).eval()
     from concurrent.futures import ThreadPoolExecutor
     q: "queue.Queue" = queue.Queue(maxsize=4)
     with torch.cuda.device(device):
@@ -246,10 +330,12 @@ def save_depth_sharded(model, dataset, outdir: str, rank: int = 0, world: int = 
             by_view = all(hasattr(dataset, a) for a in ("view_plan", "decode_view", "assemble"))
             own_pool = decoder_pool = (ViewDecoderPool if by_view else DecoderPool)(dataset, procs=decoder_procs)
         th = threading.Thread(target=_loader, args=(dataset, mine, device, copy_stream, q, decoders, decoder_pool,
-                                                    save_images), daemon=True)
+                                                    save_images, feature_slots if reuse_features else 0),
+                              daemon=True)
         th.start()
         futures = []
         cq: "queue.Queue" = queue.Queue(maxsize=4 * max(1, writers))
+        bank = None     # reuse_features: [feature_slots, 32, h, w], allocated at the first sample
         with ThreadPoolExecutor(max_workers=max(1, writers)) as pool, torch.no_grad():
             errors: list = []
             comp = threading.Thread(target=_completer, args=(cq, pool, futures, device, errors), daemon=True)
@@ -265,12 +351,30 @@ def save_depth_sharded(model, dataset, outdir: str, rank: int = 0, world: int = 
                         raise item
                     if errors:      # the completer failed: stop enqueuing forwards
                         break
-                    idx, s, dev, ready = item
+                    idx, s, dev, ready, plan = item
                     compute.wait_event(ready)
                     for t in dev:
-                        t.record_stream(compute)
+                        if t is not None:
+                            t.record_stream(compute)
                     t0 = _now()
-                    out = model(*dev)
+                    if plan is None:
+                        out = model(*dev)
+                    else:
+                        # Slot reuse is safe because everything that touches the bank is enqueued here, on
+                        # the one compute stream, in sample order: a slot the planner gave to a new view is
+                        # overwritten only after every earlier map that read its old view was enqueued.
+                        new_slots, slot_ids = plan
+                        if dev[0] is not None:
+                            feats = model.extract_features(dev[0])
+                            if bank is None:
+                                bank = torch.empty((feature_slots,) + tuple(feats.shape[1:]), dtype=feats.dtype,
+                                                   device=device)
+                            elif bank.shape[1:] != feats.shape[1:]:
+                                raise RuntimeError(f"reuse_features: image size changed within the run (features "
+                                                   f"{tuple(feats.shape[1:])}, bank {tuple(bank.shape[1:])})")
+                            for j, slot in enumerate(new_slots):
+                                bank[slot].copy_(feats[j])
+                        out = model.forward_features(bank, [slot_ids], dev[1], dev[2])
                     _tick("main.forward_enqueue", t0)
                     t0 = _now()
                     done = torch.cuda.Event()

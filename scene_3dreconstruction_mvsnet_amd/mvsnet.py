@@ -12,6 +12,11 @@ stream, one mvs_forward_images per batch item.  `model.feature_impl = "torch"` k
 PyTorch-ROCm (MIOpen) and hands NCHW features to mvs_depth_infer (the round-1 arrangement; kept
 for A/B timing).  The `feature` sub-module is a parameter container either way.
 
+Shared features: `extract_features(imgs)` runs FeatureNet once on every image of a scan and
+`forward_features(feats, view_ids, proj_matrices, depth_values)` computes maps whose views are picked
+from that bank by index (mvs_depth_infer_views) -- bit-identical to `forward` on the gathered images,
+with FeatureNet run once per image instead of once per map that reads it.
+
 Inference only: forward() raises in training mode, on CPU tensors, or if libmvs_hip.so is
 missing -- there is deliberately no PyTorch fallback for the HIP path.
 """
@@ -195,6 +200,96 @@ class MVSNet(nn.Module):
     def _workspace(self, device, N, D, h, w, dtype):
         key = (device.index, _lib._stream(device), N, D, h, w, dtype)
         return self._cached_workspace(key, lambda: _lib.query_workspace(N, 32, D, h, w, dtype), device)
+
+    def _check_inference(self, what, t):
+        """The refusals forward() makes: training mode, refine=True, CPU tensors."""
+        if self.training:
+            raise RuntimeError("this MVSNet is the MI355X inference path; call .eval() "
+                               "(training, models/mvsnet.py:167-169, is out of scope)")
+        if not t.is_cuda:
+            raise RuntimeError(f"MVSNet.{what} needs CUDA(ROCm) tensors: the depth path has no CPU "
+                               f"implementation (got a tensor on {t.device})")
+        if self.refine:
+            raise NotImplementedError("refine=True: the reference's RefineNet path is broken "
+                                      "(F.cat at models/mvsnet.py:85); every working caller passes "
+                                      "refine=False (eval.py:308)")
+
+    # -- shared features ---------------------------------------------------------------------
+    # FeatureNet workspace bytes one extract_features chunk may use (about 11 cfg2 images)
+    _FEATURE_CHUNK_BYTES = 256 << 20
+
+    def _feature_chunk(self, V, H, W):
+        """Images per mvs_feature_net_fmt call: within the library's 31-bit N*H*W*8 offsets and the
+        workspace budget above, for any V."""
+        per_image = _lib.query_feature_workspace(1, H, W)
+        by_offsets = max(1, ((1 << 31) - 1) // (H * W * 8))
+        return max(1, min(V, by_offsets, self._FEATURE_CHUNK_BYTES // per_image))
+
+    def extract_features(self, imgs, chunk=None):
+        """FeatureNet on a stack of images, for forward_features: imgs [V,3,H,W] float32, or uint8 [V,3,H,W] /
+        [V,H,W,3], on the GPU with H, W multiples of 32 -> [V,32,H/4,W/4] float32 NCHW, the reference's
+        `self.feature(img)` of every image.  `chunk` overrides the number of images per library call."""
+        self._check_inference("extract_features", imgs)
+        if imgs.dim() != 4:
+            raise RuntimeError(f"extract_features wants [V,3,H,W] or uint8 [V,H,W,3] images, got {tuple(imgs.shape)}")
+        u8_hwc = imgs.dtype == torch.uint8 and imgs.shape[1] != 3 and imgs.shape[-1] == 3
+        V, H, W = (imgs.shape[0], imgs.shape[1], imgs.shape[2]) if u8_hwc else (imgs.shape[0], imgs.shape[2], imgs.shape[3])
+        if (not u8_hwc and imgs.shape[1] != 3) or H % 32 or W % 32 or V < 1:
+            raise RuntimeError(f"extract_features wants [V,3,H,W] images with H, W multiples of 32, got {tuple(imgs.shape)}")
+        if self.feature_impl not in ("hip", "torch"):
+            raise RuntimeError(f"feature_impl must be 'hip' or 'torch', got {self.feature_impl!r}")
+        device = imgs.device
+        with torch.cuda.device(device), torch.no_grad():
+            if self.feature_impl == "torch":
+                if imgs.dtype == torch.uint8:   # the loader's conversion, on the device (as forward does)
+                    imgs = (imgs.permute(0, 3, 1, 2) if u8_hwc else imgs).to(torch.float32) / 255.0
+                return self.feature(imgs.to(torch.float32)).contiguous()
+            imgs = imgs.contiguous() if imgs.dtype == torch.uint8 else _lib._dev_f32(imgs.to(torch.float32), "imgs")
+            fblob = self._feature_blob(device)
+            c = int(chunk) if chunk else self._feature_chunk(V, H, W)
+            if c < 1:
+                raise ValueError(f"chunk must be >= 1, got {chunk}")
+            key = ("feat", device.index, _lib._stream(device), c, H, W)
+            ws = self._cached_workspace(key, lambda: _lib.query_feature_workspace(c, H, W), device)
+            feats = torch.empty((V, 32, H // 4, W // 4), dtype=torch.float32, device=device)
+            for i in range(0, V, c):
+                _lib.feature_net(imgs[i:i + c], fblob, ws, out=feats[i:i + c])
+        return feats
+
+    def forward_features(self, feats, view_ids, proj_matrices, depth_values):
+        """`forward` with the features given: feats [V,32,h,w] float32 on the GPU (e.g. extract_features of every
+        image of a scan), view_ids [B,N] host ints (or a CPU tensor) indexing feats, entry 0 of a row = the
+        reference view, proj_matrices [B,N,4,4] in view_ids order, depth_values [B,D].  Returns forward's dict,
+        bit-identical to forward(imgs[view_ids], ...) with the same storage_dtype and feature_impl."""
+        self._check_inference("forward_features", feats)
+        if isinstance(view_ids, torch.Tensor) and view_ids.device.type != "cpu":
+            raise RuntimeError(f"view_ids must be host integers or a CPU tensor (got a tensor on {view_ids.device})")
+        rows = [list(r) for r in (view_ids.tolist() if isinstance(view_ids, torch.Tensor) else view_ids)]
+        if feats.dim() != 4 or feats.shape[1] != 32:
+            raise RuntimeError(f"forward_features: feats must be [V,32,h,w], got {tuple(feats.shape)}")
+        if proj_matrices.dim() != 4 or proj_matrices.shape[0] != len(rows) \
+                or any(len(r) != proj_matrices.shape[1] for r in rows):
+            raise RuntimeError(f"forward_features: view_ids ({len(rows)} rows) and proj_matrices "
+                               f"{tuple(proj_matrices.shape)} must both be [B,N,...]")
+        if depth_values.dim() != 2 or depth_values.shape[0] != len(rows):
+            raise RuntimeError(f"forward_features: depth_values must be [B,D], got {tuple(depth_values.shape)}")
+        device = feats.device
+        B, N = proj_matrices.shape[0], proj_matrices.shape[1]
+        D = depth_values.shape[1]
+        h, w = feats.shape[2], feats.shape[3]
+        with torch.cuda.device(device), torch.no_grad():
+            feats = _lib._dev_f32(feats, "features")
+            proj = _lib._dev_f32(proj_matrices.to(device), "proj_matrices")
+            dv = _lib._dev_f32(depth_values.to(device), "depth_values")
+            blob = self._weights_blob(device)
+            dt = _lib.dtype_code(self.storage_dtype)
+            ws = self._workspace(device, N, D, h, w, dt)
+            depth = torch.empty((B, h, w), dtype=torch.float32, device=device)
+            conf = torch.empty((B, h, w), dtype=torch.float32, device=device)
+            # one enqueue per batch item on the current stream, as forward
+            for b in range(B):
+                _lib.depth_infer_views(feats, rows[b], proj[b], dv[b], blob, ws, depth[b], conf[b], dtype=dt)
+        return {"depth": depth, "photometric_confidence": conf}
 
     # -- forward -----------------------------------------------------------------------------
     def forward(self, imgs, proj_matrices, depth_values):
