@@ -1,0 +1,393 @@
+"""The depth path at the volume-size limits of its kernels and of the ABI.
+
+`check_dims` (csrc/mvs_host.hip) accepts any volume with D*h*w*32 < 2^32, but several kernels change form well below
+that: the tap-cache warp (32-bit raw-buffer offsets plus a 48-plane parking margin), the Winograd / split conv0
+(31-bit descriptors), the softargmin instantiations.  Each case below takes its depth D from the guard it straddles,
+at h x w = 512 x 640 (features of 2048 x 2560 images), and checks the GPU against the C oracle.
+
+At these sizes the whole-volume oracle would need tens of GB of host memory, so stages are checked on WINDOWS of depth
+planes: a variance plane depends only on its own depth value, and a convolution's output planes depend only on a few
+input planes, which are copied from the GPU's own input of that layer.  The first, a middle and the last window are
+checked at full h x w; the last one holds the largest offsets and the ragged last pixel block.
+"""
+import gc
+import hashlib
+import os
+import resource
+import subprocess
+import sys
+import time
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import assert_conf_close, rel_l1
+from oracle import oracle as orc
+from scene_3dreconstruction_mvsnet_amd import _lib, synthetic
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+H4, W4 = 512, 640               # feature maps of 2048 x 2560 images
+HW = H4 * W4
+C = 32
+VAR_PLANES = 8                  # depth planes per variance window
+LAYER_PLANES = 4                # output planes per layer window
+LAYER_ATOL = 2e-4               # x max|want|, the per-layer bounds of test_gpu_fullsize.py
+# Variance rel-L1: test_gpu_fullsize's 1e-5 at w = 160 (measured 2.8e-6 there: one v_rcp_f32, 1 ulp in the
+# projection), scaled with the sampling coordinates, whose fp32 rounding grows with the image width.  In the oracle
+# alone, a 1-ulp change of the projected coordinates moves the volume by 6.7e-6 (rel-L1) at 128 x 160 and by 2.7e-5
+# at 512 x 640; the kernels measured 1.6e-5 .. 1.8e-5 here.
+VAR_REL_L1 = 1e-5 * W4 / 160
+STRIDES = {1: 2, 3: 2, 5: 2}
+DECONV = {7: "conv7", 8: "conv9", 9: "conv11"}
+SD = synthetic.random_costreg_state(seed=5)
+
+
+# ---------------------------------------------------------------- the guards, restated (each case straddles one)
+def tc_fits(D, ves):
+    """warp_tc_fits (warp_variance_tc.hip): the volume plus 48 parking planes of one channel plane below 2^32 - 64
+    bytes; `ves` = bytes per volume element."""
+    return 4 * D * HW * 8 * ves + 48 * HW * 8 * ves < 2 ** 32 - 64
+
+
+def conv0_wino_fits(D):
+    """launch_conv_layer (conv3d_direct.hip): Winograd / split conv0 needs D*h*w*32 < 2^31, else conv0_4x4_mfma."""
+    return D % 4 == 0 and D * HW * 32 < 2 ** 31
+
+
+def abi_fits(D):
+    """check_dims (mvs_host.hip): D*h*w*32 < 2^32."""
+    return D * HW * C < 2 ** 32
+
+
+def largest_d(fits):
+    return max(D for D in range(8, 1 << 13, 8) if fits(D))
+
+
+D_TC32 = largest_d(lambda D: tc_fits(D, 4))     # 88: fp32 volume 100 MB under the tap-cache limit
+D_TC16 = largest_d(lambda D: tc_fits(D, 2))     # 192: 16-bit volume 16.8 MB under it
+D_C0 = largest_d(conv0_wino_fits)               # 200: conv0_w48t descriptors at 0.98 of 2^31
+D_MAX = largest_d(abi_fits)                     # 408: the largest problem the ABI accepts
+
+# (id, N, D, storage, per-layer windows + composition, conv0 against a MVS_CONV0_WINO=0 child)
+CASES = [
+    ("tc-fp32-in", 5, D_TC32, "f32", False, None),
+    ("tc-fp32-out", 5, D_TC32 + 8, "f32", False, None),     # rejected by the 48-plane margin alone
+    ("tc16-in-bf16", 5, D_TC16, "bf16", False, None),
+    ("tc16-in-f16", 5, D_TC16, "f16", False, None),
+    ("tc16-out", 5, D_TC16 + 8, "bf16", False, None),
+    ("conv0-split-in", 3, D_C0, "f32", True, "differs"),     # conv0_w48t; also the checker's self-test
+    ("conv0-direct", 3, D_C0 + 8, "f32", True, "equal"),     # conv0_4x4_mfma, as with MVS_CONV0_WINO=0
+    ("abi-max", 3, D_MAX, "f32", True, None),                # plain warp, direct conv0, softargmin loop form
+]
+
+
+def cu(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
+
+
+def inputs(N, D, seed):
+    feats = synthetic.random_features(N, C, H4, W4, seed=seed)
+    proj = synthetic.cameras(N, H4, W4, yaw_deg=0.5)
+    dv = synthetic.depth_values(D)
+    return feats, proj, dv
+
+
+def warp(feats_d, proj_d, dv_d, code):
+    """mvs_warp_variance with a workspace of just the transposed-feature region it uses (mvs_abi.h)."""
+    N = feats_d.shape[0]
+    ws = torch.empty(N * C * HW * 4, dtype=torch.uint8, device=DEV)
+    return _lib.warp_variance(feats_d, _lib.relative_proj(proj_d), dv_d, ws, dtype=code)
+
+
+def digest(t):
+    a = np.ascontiguousarray(t.cpu().numpy())
+    return hashlib.blake2b(a.view(np.uint8).reshape(-1)).hexdigest()
+
+
+# ---------------------------------------------------------------- windowed oracle checks
+def planes(t, z0, z1):
+    """Depth planes z0..z1-1 of a GPU volume on the host in the reference layout: C8-planar [P,D,h,w,8] ->
+    [8P,n,h,w] fp32; a cost volume [D,h,w] -> [n,h,w]."""
+    if t.dim() == 3:
+        return t[z0:z1].float().cpu().numpy()
+    return _lib.from_c8(t[:, z0:z1].float().cpu()).numpy()
+
+
+def input_slab(layer, zo0, zo1, Di):
+    """Input planes [a, b) that output planes [zo0, zo1) of `layer` read, and the index of zo0 among the outputs the
+    oracle computes from that slab.  The oracle pads the slab with zeros, which is the volume's own padding where the
+    slab ends at a volume edge.  Stride 1 reads zo-1..zo+1; stride 2 reads 2zo-1..2zo+1, and the slab starts on an
+    even plane so that the oracle's stride-2 grid lines up with the volume's; transposed (k3 s2 p1 op1) output o reads
+    inputs o//2..(o+1)//2."""
+    if layer in DECONV:
+        a = zo0 // 2
+        return a, min(zo1 // 2, Di - 1) + 1, zo0 - 2 * a
+    s = STRIDES.get(layer, 1)
+    a = max(s * zo0 - 1, 0)
+    a -= a % s
+    return a, min(s * (zo1 - 1) + 1, Di - 1) + 1, zo0 - a // s
+
+
+def ref_layer(layer, xs):
+    """One CostRegNet layer on the host, with BN as in test_gpu_fullsize.oracle_chain."""
+    if layer in DECONV:
+        key = DECONV[layer]
+        return orc.deconv3d(xs, SD[f"{key}.0.weight"], bn=orc._bn(SD, f"{key}.1"))
+    if layer == 10:
+        return orc.conv3d(xs, SD["prob.weight"], bias=SD["prob.bias"], bn=None, relu=False)[0]
+    return orc.conv3d(xs, SD[f"conv{layer}.conv.weight"], bn=orc._bn(SD, f"conv{layer}.bn"),
+                      stride=STRIDES.get(layer, 1))
+
+
+def ref_window(layer, x, skip, zo0, zo1):
+    """The oracle's output planes [zo0, zo1) of `layer` from the GPU's input `x` (and skip).  layer "tail" is the
+    fused conv11_prob: prob(conv11(x) + skip), through the d11 planes zo0-1..zo1."""
+    if layer == "tail":
+        Do = skip.shape[1]
+        t0, t1 = max(zo0 - 1, 0), min(zo1 + 1, Do)
+        return ref_layer(10, ref_window(9, x, skip, t0, t1))[zo0 - t0:zo1 - t0]
+    a, b, k = input_slab(layer, zo0, zo1, x.shape[1])
+    want = ref_layer(layer, planes(x, a, b))[..., k:k + zo1 - zo0, :, :]
+    assert want.shape[-3] == zo1 - zo0, (layer, zo0, zo1, want.shape)
+    if skip is not None:
+        want = want + planes(skip, zo0, zo1)
+    return want
+
+
+def window_check(layer, x, skip, y, zo0, zo1):
+    """Output planes [zo0, zo1) of the GPU's `y = layer(x, skip)` against the oracle on the same input planes."""
+    want = ref_window(layer, x, skip, zo0, zo1)
+    got = planes(y, zo0, zo1)
+    assert got.shape == want.shape, (layer, got.shape, want.shape)
+    np.testing.assert_allclose(got, want, rtol=0, atol=LAYER_ATOL * max(float(np.abs(want).max()), 1.0),
+                               err_msg=f"layer {layer}, planes {zo0}..{zo1 - 1}")
+    r = rel_l1(got, want)
+    assert r < 2e-6, (layer, zo0, zo1, r)
+
+
+def windows(D, n):
+    n = min(n, D)
+    return [(0, n), (D // 2 - n // 2, D // 2 - n // 2 + n), (D - n, D)]
+
+
+def check_layer(layer, x, skip, y):
+    depth = y.shape[0] if y.dim() == 3 else y.shape[1]
+    for zo0, zo1 in windows(depth, LAYER_PLANES):
+        window_check(layer, x, skip, y, zo0, zo1)
+
+
+def check_variance(var, feats, proj, dv, storage):
+    """Variance windows against orc.variance_volume on the same depth values (a plane depends only on its own
+    depth value); 16-bit volumes against the fp32 window rounded to the storage type."""
+    eps = {"f32": 0.0, "f16": 2.0 ** -10, "bf16": 2.0 ** -7}[storage]
+    for d0, d1 in windows(dv.shape[0], VAR_PLANES):
+        want = orc.variance_volume(feats, proj, dv[d0:d1])
+        got = planes(var, d0, d1)
+        if storage == "f32":
+            np.testing.assert_allclose(got, want, rtol=0, atol=5e-4, err_msg=f"variance planes {d0}..{d1 - 1}")
+            assert rel_l1(got, want) < VAR_REL_L1, (d0, d1, rel_l1(got, want))
+        else:
+            np.testing.assert_allclose(got, orc.round_storage(want, storage), rtol=eps, atol=5e-4,
+                                       err_msg=f"variance planes {d0}..{d1 - 1}")
+
+
+def conv0_self_test(var, c0):
+    """The checker covers the end of the buffer: one error of 1e-3 x the window's scale (5x the bound) at the highest
+    flat offset, and a stale last plane, must both fail the last window.  The output is restored bit for bit."""
+    D = c0.shape[1]
+    last = (D - LAYER_PLANES, D)
+    window_check(0, var, None, c0, *last)
+    flat = c0.view(-1)
+    keep = flat[-1:].clone()
+    flat[-1:] += 1e-3 * float(c0[:, last[0]:].abs().max())
+    with pytest.raises(AssertionError):
+        window_check(0, var, None, c0, *last)
+    flat[-1:] = keep
+    keep = c0[:, -1].clone()
+    c0[:, -1] = c0[:, -2]
+    with pytest.raises(AssertionError):
+        window_check(0, var, None, c0, *last)
+    c0[:, -1] = keep
+
+
+def conv0_digest_child(N, D, seed, env):
+    """conv0's output digest from a child process (kernel selection is read once per process)."""
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "conv0-digest", str(N), str(D), str(seed)],
+                       env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+    if r.returncode < 0 or r.returncode in (134, 139):   # killed by a signal: no further GPU work in this run
+        pytest.exit(f"conv0-digest child died with status {r.returncode}:\n{r.stderr[-4000:]}", returncode=3)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r.stdout.strip().splitlines()[-1]
+
+
+def device_bytes_needed(N, D, storage, chain):
+    code = _lib.dtype_code(storage)
+    feats = N * C * HW * 4
+    if chain:   # mvs_depth_infer's workspace; afterwards the chain holds at most var + c0 + the small levels
+        return _lib.query_workspace(N, C, D, H4, W4, code) + 2 * feats + (1 << 30)
+    return D * HW * C * (4 if storage == "f32" else 2) + 2 * feats + (1 << 30)
+
+
+@pytest.fixture(autouse=True)
+def _release_gpu_memory():
+    yield
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("name,N,D,storage,chain,conv0_vs_direct", CASES, ids=[c[0] for c in CASES])
+def test_volume_limit_case(name, N, D, storage, chain, conv0_vs_direct):
+    need = device_bytes_needed(N, D, storage, chain)
+    total = torch.cuda.get_device_properties(0).total_memory
+    if total < need:
+        pytest.skip(f"{name} needs {need / 2**30:.1f} GiB of device memory; the device has {total / 2**30:.1f} GiB")
+    # which side of which guard this shape sits on
+    ves = 4 if storage == "f32" else 2
+    assert abi_fits(D)
+    if name.startswith("tc"):
+        assert tc_fits(D, ves) == ("-in" in name), (name, D)
+    if name == "tc-fp32-out":
+        assert 4 * D * HW * 8 * ves < 2 ** 32 - 64   # the volume alone fits: only the parking margin rejects it
+    if chain:
+        assert conv0_wino_fits(D) == (name == "conv0-split-in"), (name, D)
+    if name == "abi-max":
+        assert not abi_fits(D + 8) and D > 256 and not tc_fits(D, ves)   # softargmin loop form, plain warp
+    t_start = time.perf_counter()
+    torch.cuda.reset_peak_memory_stats()
+    code = _lib.dtype_code(storage)
+    seed = 1000 + D
+    feats, proj, dv = inputs(N, D, seed)
+    g = {}   # every device tensor of the case, dropped in `finally` even when an assertion fails
+    try:
+        g["feats"], g["proj"], g["dv"] = cu(feats), cu(proj), cu(dv)
+        blob = _lib.pack_weights(SD).to(DEV)
+        if chain:   # the whole path in one call first: its workspace is the largest allocation of the case
+            g["ws"] = _lib.alloc_workspace(N, C, D, H4, W4, DEV)
+            g["depth_w"] = torch.empty((H4, W4), dtype=torch.float32, device=DEV)
+            g["conf_w"] = torch.empty_like(g["depth_w"])
+            _lib.depth_infer(g["feats"], g["proj"], g["dv"], blob, g["ws"], g["depth_w"], g["conf_w"])
+            torch.cuda.synchronize()
+            del g["ws"]
+            torch.cuda.empty_cache()
+
+        g["var"] = warp(g["feats"], g["proj"], g["dv"], code)
+        check_variance(g["var"], feats, proj, dv, storage)
+        if not chain:
+            return
+
+        # the stage-by-stage chain of mvs_depth_infer, each layer checked on its windows
+        g["c0"] = _lib.conv_layer(0, g["var"], None, blob)
+        check_layer(0, g["var"], None, g["c0"])
+        if name == "conv0-split-in":
+            conv0_self_test(g["var"], g["c0"])
+        del g["var"]
+        if conv0_vs_direct:
+            mine = digest(g["c0"])
+            direct = conv0_digest_child(N, D, seed, {"MVS_CONV0_WINO": "0"})
+            if conv0_vs_direct == "equal":       # both ran conv0_4x4_mfma
+                assert mine == direct
+            else:                                # the default ran conv0_w48t, not the direct kernel
+                assert mine != direct
+        for layer in range(1, 7):
+            g[f"c{layer}"] = _lib.conv_layer(layer, g[f"c{layer - 1}"], None, blob)
+            check_layer(layer, g[f"c{layer - 1}"], None, g[f"c{layer}"])
+        g["d7"] = _lib.conv_layer(7, g["c6"], g["c4"], blob)
+        check_layer(7, g["c6"], g["c4"], g["d7"])
+        for k in ("c1", "c3", "c5", "c6", "c4"):
+            del g[k]
+        g["d9"] = _lib.conv_layer(8, g["d7"], g["c2"], blob)
+        check_layer(8, g["d7"], g["c2"], g["d9"])
+        del g["d7"], g["c2"]
+        g["cost"] = _lib.conv11_prob(g["d9"], g["c0"], blob)
+        check_layer("tail", g["d9"], g["c0"], g["cost"])
+        del g["d9"], g["c0"]
+        depth, conf = _lib.softargmin_conf(g["cost"], g["dv"])
+
+        # composition: mvs_depth_infer is this chain, bit for bit (workspace carve-up at > 4 GiB activations)
+        assert torch.equal(depth, g["depth_w"]), int((depth != g["depth_w"]).sum())
+        assert torch.equal(conf, g["conf_w"]), int((conf != g["conf_w"]).sum())
+
+        # softargmin on the whole cost volume
+        depth_o, conf_o, idx_o, prob_o = orc.softargmin_conf(g["cost"].cpu().numpy(), dv, want_prob=True)
+        depth, conf = depth.cpu().numpy(), conf.cpu().numpy()
+        assert rel_l1(depth, depth_o) < 2e-6, rel_l1(depth, depth_o)
+        assert_conf_close(conf, conf_o, idx_o, prob=prob_o, atol=2e-5)
+    finally:
+        g.clear()
+        gc.collect()
+        torch.cuda.empty_cache()
+        print(f"[limits] {name} N={N} D={D} {storage}: {time.perf_counter() - t_start:.1f} s, "
+              f"peak device {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB, "
+              f"peak host RSS {resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2**20:.2f} GiB")
+
+
+# ---------------------------------------------------------------- softargmin: every instantiation
+# launch_softargmin (softargmin.hip): hw >= 16384 and D <= 256 -> <16|24|32, 32, 8> by (D+7)/8 <= 16 / 24 / 32;
+# otherwise <8|16, 16, 16> by (D+15)/16 <= 8 / 16, and the loop form above that
+@pytest.mark.parametrize("D,h,w,gain", [
+    (64, 128, 128, 1.0),     # <16,32,8>
+    (64, 120, 136, 3.0),     # <8,16,16>: hw = 16320, just below 16384
+    (128, 128, 128, 10.0),   # <16,32,8> at its largest D
+    (128, 120, 136, 1.0),    # <8,16,16> at its largest D
+    (136, 128, 128, 3.0),    # <24,32,8>
+    (256, 128, 128, 1.0),    # <32,32,8>
+    (264, 512, 640, 3.0),    # loop form at large hw (D > 256)
+])
+def test_softargmin_every_form_against_oracle(D, h, w, gain):
+    rng = np.random.default_rng(D * 7 + h)
+    cost = (gain * rng.standard_normal((D, h, w))).astype(np.float32)
+    dv = synthetic.depth_values(D)
+    depth_o, conf_o, idx_o, prob_o = orc.softargmin_conf(cost, dv, want_prob=True)
+    depth, conf = _lib.softargmin_conf(cu(cost), cu(dv))
+    depth, conf = depth.cpu().numpy(), conf.cpu().numpy()
+    assert rel_l1(depth, depth_o) < 2e-6
+    assert_conf_close(conf, conf_o, idx_o, prob=prob_o, atol=2e-5)
+
+
+# ---------------------------------------------------------------- the view count at the ABI maximum
+@pytest.mark.parametrize("N", [6, 64])
+def test_many_views_against_oracle(N):
+    """check_dims accepts N <= 64; N > 5 runs the plain warp kernel's many-view loop."""
+    D, h, w = 16, 32, 48
+    feats = synthetic.random_features(N, C, h, w, seed=N)
+    proj = synthetic.cameras(N, h, w, baseline=(-2.0, 0.5, 0.0), yaw_deg=0.1)
+    dv = synthetic.depth_values(D)
+    cost = orc.costreg_forward(orc.variance_volume(feats, proj, dv), SD)
+    depth_o, conf_o, idx_o, prob_o = orc.softargmin_conf(cost, dv, want_prob=True)
+    ws = _lib.alloc_workspace(N, C, D, h, w, DEV)
+    depth = torch.empty((h, w), dtype=torch.float32, device=DEV)
+    conf = torch.empty_like(depth)
+    _lib.depth_infer(cu(feats), cu(proj), cu(dv), _lib.pack_weights(SD).to(DEV), ws, depth, conf)
+    depth, conf = depth.cpu().numpy(), conf.cpu().numpy()
+    assert rel_l1(depth, depth_o) < 1e-5, rel_l1(depth, depth_o)
+    assert_conf_close(conf, conf_o, idx_o, prob=prob_o, atol=1e-3)
+
+
+def test_64_views_from_a_bank_with_a_permuted_table():
+    """mvs_depth_infer_views with the full 64-entry view table (passed by value to nchw_to_c8), permuted: bit-identical
+    to mvs_depth_infer on the gathered features."""
+    V, D, h, w = 64, 16, 32, 48
+    bank = synthetic.random_features(V, C, h, w, seed=64)
+    proj_bank = synthetic.cameras(V, h, w, baseline=(-2.0, 0.5, 0.0), yaw_deg=0.1)
+    ids = np.random.default_rng(64).permutation(V)
+    assert ids[0] != 0 and ids[-1] != V - 1
+    dv = cu(synthetic.depth_values(D))
+    blob = _lib.pack_weights(SD).to(DEV)
+    ws = _lib.alloc_workspace(V, C, D, h, w, DEV)
+    out = [torch.empty((h, w), dtype=torch.float32, device=DEV) for _ in range(4)]
+    _lib.depth_infer_views(cu(bank), ids, cu(proj_bank[ids]), dv, blob, ws, out[0], out[1])
+    _lib.depth_infer(cu(bank[ids]), cu(proj_bank[ids]), dv, blob, ws, out[2], out[3])
+    assert torch.isfinite(out[0]).all()
+    assert torch.equal(out[0], out[2]) and torch.equal(out[1], out[3])
+
+
+if __name__ == "__main__":
+    # child of conv0_digest_child: conv0's output on a case's inputs, with the environment's kernel selection
+    assert sys.argv[1] == "conv0-digest", sys.argv
+    n_, d_, s_ = (int(a) for a in sys.argv[2:5])
+    f_, p_, v_ = inputs(n_, d_, s_)
+    x_ = warp(cu(f_), cu(p_), cu(v_), _lib.MVS_F32)
+    print(digest(_lib.conv_layer(0, x_, None, _lib.pack_weights(SD).to(DEV))))

@@ -39,6 +39,28 @@ def test_query_workspace_and_shape_errors():
     assert "dtype" in str(e.value)
 
 
+@pytest.mark.parametrize("dtype", [_lib.MVS_F32, _lib.MVS_F16])
+def test_workspace_queries_at_the_volume_limit(dtype):
+    """check_dims (mvs_host.hip) accepts D*h*w*32 < 2^32.  At h x w = 512 x 640 (2048 x 2560 images) the largest such
+    D is 408, where the variance volume alone is 17.1 GB (fp32): a 32-bit wrap in the workspace carve-up would
+    return less than the volumes it must hold.  The next multiple of 8 is refused with MVS_ERR_BAD_SHAPE."""
+    h, w = 512, 640
+    d_max = max(D for D in range(8, 1024, 8) if D * h * w * 32 < 2 ** 32)
+    es = 4 if dtype == _lib.MVS_F32 else 2
+    var_cost = d_max * h * w * 32 * es + d_max * h * w * 4    # variance volume + fp32 cost volume
+    n = _lib.query_workspace(3, 32, d_max, h, w, dtype)
+    assert n > var_cost > 2 ** 32
+    assert n % 256 == 0
+    f = _lib.query_forward_workspace(3, 4 * h, 4 * w, d_max, dtype)
+    assert f == n + _lib.query_feature_workspace(3, 4 * h, 4 * w)
+    for query, args in ((_lib.query_workspace, (3, 32, d_max + 8, h, w)),
+                        (_lib.query_forward_workspace, (3, 4 * h, 4 * w, d_max + 8))):
+        with pytest.raises(_lib.MvsError) as e:
+            query(*args, dtype=dtype)
+        assert e.value.code == 1, (query.__name__, args)     # MVS_ERR_BAD_SHAPE
+        assert "32-bit" in str(e.value)
+
+
 def test_null_pointer_is_an_error_not_a_crash():
     lib = _lib.load()
     assert lib.mvs_query_workspace(5, 32, 192, 128, 160, 0, None) == 5  # MVS_ERR_NULL
