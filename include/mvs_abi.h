@@ -36,7 +36,8 @@ extern "C" {
  * 3 without a bump); the packed weight blob grew (split-operand conv0 panel) and lost the round-2 conv0 panels.
  * A packed blob (mvs_pack_weights / mvs_pack_feature_weights) is valid ONLY for the library version that produced it:
  * never cache one across builds -- re-pack from the state_dict (4 MB, milliseconds).
- * Added within version 2, without a bump (additive; packed blobs unchanged): mvs_depth_infer_views. */
+ * Added within version 2, without a bump (additive; packed blobs unchanged): mvs_depth_infer_views,
+ * mvs_query_metrics_workspace, mvs_depth_metrics. */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {
@@ -238,6 +239,23 @@ int mvs_forward_images_fmt(const void* imgs, int image_format, const float* proj
                            const void* feature_blob, const void* weights_blob, float* depth_out,
                            float* conf_out, void* workspace, size_t workspace_bytes, int N, int H, int W,
                            int D, int dtype, void* stream);
+
+/* ---- Depth error against ground truth (reference train.py:302-358 test mode: mvsnet_loss models/mvsnet.py:242-244,
+ * AbsDepthError_metrics / Thres_metrics utils.py:128-158, errormap train.py:315).
+ *
+ * mvs_depth_metrics: depth_est, depth_gt, mask dev fp32 [B][h][w] (mask as the loaders produce it, PNG / 255);
+ *   thresholds HOST fp32 [n_thres] (0 <= n_thres <= 8).  A pixel is valid where mask > 0.5; e = est - gt in fp32.
+ *   sums_out dev fp64 [B][3 + n_thres], one row per image:
+ *     [n_valid, sum |e|, sum smooth_l1(e) (beta 1, fp32 per pixel), count(|e| > t_k) for each k]
+ *   accumulated in fp64 (counts exact); |e| > t is an fp32 comparison, so a NaN error enters the sums and no count.
+ *   errmap_out (dev fp32 [B][h][w], or NULL) = |e| * mask for every pixel, as torch computes it (inf * 0 = NaN).
+ *   Per-block partials go to the workspace (mvs_query_metrics_workspace(B,h,w) bytes, 8-byte aligned) and a
+ *   second kernel adds them per image in a fixed order: no atomics, bit-identical across runs and streams.
+ *   Any h, w >= 1; B >= 1; B*h*w < 2^31; else MVS_ERR_BAD_SHAPE.  Nothing is enqueued on an error. */
+int mvs_query_metrics_workspace(int B, int h, int w, size_t* bytes);
+int mvs_depth_metrics(const float* depth_est, const float* depth_gt, const float* mask, int B, int h, int w,
+                      const float* thresholds, int n_thres, double* sums_out, float* errmap_out, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@ SYMBOLS = (
     "mvs_query_feature_blob", "mvs_pack_feature_weights", "mvs_query_feature_workspace",
     "mvs_feature_layer", "mvs_feature_net", "mvs_query_forward_workspace", "mvs_forward_images",
     "mvs_feature_net_fmt", "mvs_forward_images_fmt", "mvs_depth_infer_views",
+    "mvs_query_metrics_workspace", "mvs_depth_metrics",
 )
 
 # mvs_image_format (include/mvs_abi.h)
@@ -117,6 +118,8 @@ def load():
         _d = ctypes.c_double
         lib.mvs_filter_depth.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                                          _d, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]
+        lib.mvs_query_metrics_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_sz)]
+        lib.mvs_depth_metrics.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]
         for name in SYMBOLS:
             if name not in ("mvs_last_error_string",):
                 getattr(lib, name).restype = _i
@@ -552,3 +555,58 @@ def forward_images(imgs, proj, depth_values, fblob, blob, workspace, depth_out, 
                                         fblob.data_ptr(), blob.data_ptr(), depth_out.data_ptr(),
                                         conf_out.data_ptr(), workspace.data_ptr(), workspace.numel(),
                                         N, H, W, D, dtype, _stream(imgs.device)))
+
+
+# ---- depth error against ground truth (reference train.py:302-358) ---------------------------
+METRICS_MAX_THRES = 8
+
+
+def query_metrics_workspace(B, h, w) -> int:
+    n = _sz(0)
+    check(load().mvs_query_metrics_workspace(B, h, w, ctypes.byref(n)))
+    return int(n.value)
+
+
+def depth_metrics(depth_est, depth_gt, mask, thresholds=(1.0, 2.0, 4.0, 8.0), sums_out=None, errmap=False,
+                  workspace=None):
+    """Per-image masked error sums of depth maps [B,h,w] (or [h,w]) against ground truth, on the GPU.
+
+    mask is float32 as the loaders produce it (PNG / 255) or bool (converted on the device); valid = mask > 0.5.
+    Returns (sums float64 [B, 3 + len(thresholds)] on the device -- rows [n_valid, sum |e|, sum smooth_l1(e),
+    count(|e| > t) ...] -- and the error map |est - gt| * mask float32 [B,h,w] or None).  `sums_out` (a
+    contiguous float64 CUDA tensor of that shape, e.g. rows of a larger buffer) receives the sums when given.
+    Enqueued on the current stream; nothing synchronises."""
+    import numpy as np
+    if not isinstance(mask, torch.Tensor):
+        raise RuntimeError("depth_metrics: mask must be a tensor")
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.float32)
+    est = _dev_f32(depth_est, "depth_est")
+    gt = _dev_f32(depth_gt, "depth_gt")
+    mask = _dev_f32(mask, "mask")
+    if est.dim() == 2:
+        est, gt, mask = est[None], gt[None], mask[None]
+    if est.dim() != 3 or gt.shape != est.shape or mask.shape != est.shape:
+        raise RuntimeError(f"depth_metrics: depth_est {tuple(depth_est.shape)}, depth_gt {tuple(depth_gt.shape)} and "
+                           f"mask {tuple(mask.shape)} must all be [B,h,w]")
+    if gt.device != est.device or mask.device != est.device:
+        raise RuntimeError("depth_metrics: depth_est, depth_gt and mask must be on one device")
+    B, h, w = est.shape
+    th = np.ascontiguousarray([float(t) for t in thresholds], dtype=np.float32)
+    K = 3 + th.size
+    dev = est.device
+    if sums_out is None:
+        sums_out = torch.empty((B, K), dtype=torch.float64, device=dev)
+    elif tuple(sums_out.shape) != (B, K) or sums_out.dtype != torch.float64 or not sums_out.is_contiguous() \
+            or sums_out.device != dev:
+        raise RuntimeError(f"depth_metrics: sums_out must be a contiguous float64 [{B},{K}] tensor on {dev}")
+    err = torch.empty((B, h, w), dtype=torch.float32, device=dev) if errmap else None
+    with torch.cuda.device(dev):
+        nbytes = query_metrics_workspace(B, h, w)
+        if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(load().mvs_depth_metrics(est.data_ptr(), gt.data_ptr(), mask.data_ptr(), B, h, w,
+                                       th.ctypes.data if th.size else None, int(th.size), sums_out.data_ptr(),
+                                       err.data_ptr() if err is not None else None, workspace.data_ptr(),
+                                       workspace.numel(), _stream(dev)))
+    return sums_out, err

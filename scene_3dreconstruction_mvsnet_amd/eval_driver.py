@@ -204,9 +204,11 @@ class FeatureSlots:
 
 
 def _loader(dataset, indices, device, copy_stream, q: "queue.Queue", decoders: int = 16, decoder_pool=None,
-            keep_ref_image: bool = True, feature_slots: int = 0):
+            keep_ref_image: bool = True, feature_slots: int = 0, extra_keys=()):
     """Producer thread: decoded samples (see _decoded_samples) are handed over in order and copied to
-    the device on `copy_stream` while the GPU computes the previous sample.
+    the device on `copy_stream` while the GPU computes the previous sample.  The device list is
+    [images, proj, depth_values] followed by the float32 arrays of `extra_keys` (e.g. GT depth and mask), each
+    with a leading batch dimension of 1.
     feature_slots > 0 (reuse_features): the slot bookkeeping of the feature bank runs here, in sample
     order; only the images of views that are not resident are copied, and the item carries
     (new images or None, proj, depth_values) plus (their slots, the sample's slot ids)."""
@@ -238,7 +240,8 @@ def _loader(dataset, indices, device, copy_stream, q: "queue.Queue", decoders: i
             else:
                 first = torch.as_tensor(np.asarray(s["imgs"]), dtype=idt)[None]
             src = [first] + \
-                  [torch.as_tensor(np.asarray(s[k]), dtype=torch.float32)[None] for k in ("proj_matrices", "depth_values")]
+                  [torch.as_tensor(np.asarray(s[k]), dtype=torch.float32)[None]
+                   for k in ("proj_matrices", "depth_values") + tuple(extra_keys)]
             _tick("loader.prep", t0)
             t0 = _now()
             with torch.cuda.stream(copy_stream):

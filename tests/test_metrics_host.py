@@ -1,0 +1,155 @@
+"""Ground-truth metrics, host side: the C-ABI refusals of mvs_depth_metrics (no kernel is launched) and the
+sums -> scalar-dict step of metrics.py against the reference's values (tests/golden/fx_gt.npz)."""
+import ctypes
+import math
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN
+from scene_3dreconstruction_mvsnet_amd import _lib
+from scene_3dreconstruction_mvsnet_amd.metrics import KEYS, batch_scalars, final_scalars
+
+THRES = (1, 2, 4, 8)
+
+
+@pytest.fixture(scope="module")
+def fx():
+    with np.load(os.path.join(GOLDEN, "fx_gt.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+def host_sums(est, gt, mask, thresholds=THRES):
+    """numpy statement of the kernel's rows: fp32 error, fp64 sums, exact counts."""
+    rows = []
+    for e, g, m in zip(est, gt, mask):
+        with np.errstate(invalid="ignore"):
+            z = np.abs(e - g)[m > np.float32(0.5)]
+            sl1 = np.where(z < 1, np.float32(0.5) * z * z, z - np.float32(0.5)).astype(np.float32)
+            rows.append([z.size, z.astype(np.float64).sum(), sl1.astype(np.float64).sum()] +
+                        [int((z > np.float32(t)).sum()) for t in thresholds])
+    return np.array(rows, np.float64)
+
+
+# ---- the C ABI refuses bad arguments and enqueues nothing -----------------------------------------
+def _call(B=2, h=8, w=8, n_thres=4, null=None, ws_bytes=None):
+    lib = _lib.load()
+    fake = [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(5)]   # never dereferenced: refused first
+    th = (ctypes.c_float * 9)(*([1.0] * 9))
+    ptrs = {"est": fake[0], "gt": fake[1], "mask": fake[2], "sums": fake[3], "ws": fake[4], "thres": th}
+    if null:
+        ptrs[null] = None
+    if ws_bytes is None:     # a workspace that would be large enough, so the shape is what gets refused
+        ws_bytes = 1 << 40
+    return lib.mvs_depth_metrics(ptrs["est"], ptrs["gt"], ptrs["mask"], B, h, w, ptrs["thres"], n_thres,
+                                 ptrs["sums"], None, ptrs["ws"], ws_bytes, None)
+
+
+@pytest.mark.parametrize("null", ["est", "gt", "mask", "sums", "ws", "thres"])
+def test_null_pointer_is_refused(null):
+    assert _call(null=null) == 5                                  # MVS_ERR_NULL
+    assert b"NULL" in _lib.load().mvs_last_error_string()
+
+
+@pytest.mark.parametrize("shape", [dict(B=0), dict(h=0), dict(w=0), dict(n_thres=9), dict(n_thres=-1),
+                                   dict(B=2, h=32768, w=32768), dict(B=-1)])
+def test_bad_shape_is_refused(shape):
+    assert _call(**shape) == 1                                    # MVS_ERR_BAD_SHAPE
+
+
+def test_short_workspace_is_refused():
+    lib = _lib.load()
+    need = ctypes.c_size_t(0)
+    assert lib.mvs_query_metrics_workspace(2, 37, 53, ctypes.byref(need)) == 0 and need.value > 0
+    assert _call(B=2, h=37, w=53, ws_bytes=need.value - 1) == 3   # MVS_ERR_WORKSPACE
+    assert _call(B=2, h=37, w=53, ws_bytes=0) == 3
+
+
+def test_workspace_query():
+    lib = _lib.load()
+    assert lib.mvs_query_metrics_workspace(1, 1, 1, None) == 5
+    n = ctypes.c_size_t(0)
+    assert lib.mvs_query_metrics_workspace(0, 4, 4, ctypes.byref(n)) == 1
+    assert lib.mvs_query_metrics_workspace(1, 1 << 16, 1 << 15, ctypes.byref(n)) == 1   # B*h*w = 2^31
+    small = _lib.query_metrics_workspace(3, 37, 53)
+    big = _lib.query_metrics_workspace(3, 512, 640)
+    assert small % 8 == 0 and big >= small and _lib.query_metrics_workspace(6, 512, 640) == 2 * big
+
+
+def test_depth_metrics_refuses_cpu_tensors():
+    import torch
+    from scene_3dreconstruction_mvsnet_amd import metrics
+    t = torch.zeros(1, 4, 4)
+    for f in (metrics.mvsnet_loss, metrics.AbsDepthError_metrics):
+        with pytest.raises(RuntimeError, match="CUDA"):
+            f(t, t, t > 0.5)
+    with pytest.raises(RuntimeError, match="CUDA"):
+        metrics.Thres_metrics(t, t, t > 0.5, 2)
+
+
+# ---- sums -> the reference's scalars ---------------------------------------------------------------
+def test_host_sums_restate_the_reference_per_image(fx):
+    s = host_sums(fx["m_est"], fx["m_gt"], fx["m_mask"])
+    per = fx["m_per_image"]
+    assert s[1, 0] == 0 and s[0, 0] > 0 and s[2, 0] > 0
+    for b in (0, 2):
+        assert np.float32(s[b, 1] / s[b, 0]) == pytest.approx(per[b, 0], rel=1e-6)
+        for k in range(4):
+            assert np.float32(s[b, 3 + k]) / np.float32(s[b, 0]) == per[b, 1 + k]   # count / n in fp32, exact
+        assert s[b, 2] / s[b, 0] == pytest.approx(per[b, 5], rel=1e-6)
+    # errors of exactly 1, 2, 4 and 8 are not above their threshold
+    for k, t in enumerate(THRES):
+        z = np.abs(fx["m_est"][0, k, :8] - fx["m_gt"][0, k, :8])
+        assert (z == t).all()
+
+
+def test_batch_scalars_reproduce_the_reference(fx):
+    s = host_sums(fx["m_est"], fx["m_gt"], fx["m_mask"])
+    d = batch_scalars(s)
+    assert tuple(d) == KEYS
+    assert d["loss"] == pytest.approx(float(fx["m_loss"]), rel=1e-6)           # pooled over the batch
+    assert math.isnan(d["abs_depth_error"]) and math.isnan(float(fx["m_abs"]))  # the empty image
+    for k, t in enumerate(THRES):
+        assert math.isnan(d[f"thres{t}mm_error"]) and math.isnan(float(fx["m_thres"][k]))
+
+
+def test_nan_error_propagates_like_torch(fx):
+    s = host_sums(fx["nan_est"], fx["nan_gt"], fx["nan_mask"])
+    d = batch_scalars(s)
+    assert math.isnan(d["loss"]) and math.isnan(float(fx["nan_loss"]))
+    assert math.isnan(d["abs_depth_error"]) and math.isnan(float(fx["nan_abs"]))
+    for k, t in enumerate(THRES):      # a NaN error is never above a threshold
+        assert d[f"thres{t}mm_error"] == pytest.approx(float(fx["nan_thres"][k]), rel=1e-6)
+
+
+def test_final_scalars_average_per_batch(fx):
+    s = host_sums(fx["nan_est"], fx["nan_gt"], fx["nan_mask"])
+    per = fx["nan_per_image"].astype(np.float64)
+    d = final_scalars(s, [1, 1])
+    ok = per[0]
+    assert math.isnan(d["loss"])            # the second batch's loss is NaN
+    for k, t in enumerate(THRES):
+        assert d[f"thres{t}mm_error"] == pytest.approx((per[0, 1 + k] + per[1, 1 + k]) / 2, rel=1e-6)
+    d0 = final_scalars(s[:1], [1])
+    assert d0["loss"] == pytest.approx(ok[5], rel=1e-6) and d0["abs_depth_error"] == pytest.approx(ok[0], rel=1e-6)
+    two = final_scalars(np.concatenate([s[:1], s[:1]]), [1, 1])
+    assert two == pytest.approx(d0)
+    with pytest.raises(ValueError):
+        final_scalars(s, [1])
+
+
+def test_checkpoint_loading_strips_the_dataparallel_prefix(tmp_path):
+    import torch
+    from scene_3dreconstruction_mvsnet_amd import MVSNet
+    from scene_3dreconstruction_mvsnet_amd.eval_gt import _load_checkpoint
+    src = MVSNet(refine=False)
+    with torch.no_grad():
+        for p in src.parameters():
+            p.normal_()
+    path = str(tmp_path / "model_000000.ckpt")
+    torch.save({"epoch": 0, "model": {"module." + k: v for k, v in src.state_dict().items()}, "optimizer": {}}, path)
+    dst = MVSNet(refine=False)
+    _load_checkpoint(dst, path)
+    for k, v in src.state_dict().items():
+        assert torch.equal(dst.state_dict()[k], v), k
