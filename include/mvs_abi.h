@@ -37,7 +37,7 @@ extern "C" {
  * A packed blob (mvs_pack_weights / mvs_pack_feature_weights) is valid ONLY for the library version that produced it:
  * never cache one across builds -- re-pack from the state_dict (4 MB, milliseconds).
  * Added within version 2, without a bump (additive; packed blobs unchanged): mvs_depth_infer_views,
- * mvs_query_metrics_workspace, mvs_depth_metrics. */
+ * mvs_query_metrics_workspace, mvs_depth_metrics, mvs_warp_variance_backward, mvs_softargmin_backward. */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {
@@ -256,6 +256,30 @@ int mvs_query_metrics_workspace(int B, int h, int w, size_t* bytes);
 int mvs_depth_metrics(const float* depth_est, const float* depth_gt, const float* mask, int B, int h, int w,
                       const float* thresholds, int n_thres, double* sums_out, float* errmap_out, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* ---- Training: adjoints of the cost volume and of the soft-argmin (csrc/train_backward.hip).
+ * Replace the autograd backward of models/module.py:96-139 (grid_sample), models/mvsnet.py:145-177 (the training
+ * branch's out-of-place sums and squares, 167-169, and the variance), models/mvsnet.py:192-193 (softmax) and
+ * models/module.py:144-147 (depth_regression).  The projections and depth values carry no gradient (the reference
+ * builds the sampling grid under no_grad, module.py:106-133), nor does the photometric confidence (mvsnet.py:213).
+ *
+ * mvs_warp_variance_backward: the exact adjoint of mvs_warp_variance in fp32 (same bilinear taps and weights,
+ *   including zero weights outside the image and NaN weights for non-finite sampling coordinates).
+ *     feats       dev fp32 [N][C][h][w]     the forward's input (view 0 = reference view)
+ *     rt          dev fp32 [(N-1)][12]      from mvs_relative_proj (may be NULL for N = 1)
+ *     grad_var    dev fp32 [C][D][h][w]     gradient w.r.t. the variance volume, NCDHW as conv3d's backward hands it
+ *     grad_feats  dev fp32 [N][C][h][w]     written (zero-filled inside the call, on `stream`); must not alias inputs
+ *   Any shape mvs_warp_variance accepts (N in [1,64], C = 32, D,h,w positive multiples of 8, D*h*w*C < 2^32), else
+ *   MVS_ERR_BAD_SHAPE and nothing is enqueued.  Float atomics reorder the sums: not bit-reproducible run to run.
+ * mvs_softargmin_backward: grad_cost[d][p] = grad_depth[p] * p_d * (depth_values[d] - depth[p]), with the softmax
+ *   p and the depth recomputed from the logits in mvs_softargmin_conf's max-subtracted form.
+ *     cost dev fp32 [D][h][w]; grad_depth dev fp32 [h][w]; grad_cost dev fp32 [D][h][w] (written, no atomics)
+ *   D, h, w >= 1 and h*w < 2^31, else MVS_ERR_BAD_SHAPE.
+ * Neither allocates, needs a workspace or synchronises. */
+int mvs_warp_variance_backward(const float* feats, const float* rt, const float* depth_values, const float* grad_var,
+                               float* grad_feats, int N, int C, int D, int h, int w, void* stream);
+int mvs_softargmin_backward(const float* cost, const float* depth_values, const float* grad_depth,
+                            float* grad_cost, int D, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }

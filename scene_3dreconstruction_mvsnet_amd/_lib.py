@@ -48,6 +48,7 @@ SYMBOLS = (
     "mvs_feature_layer", "mvs_feature_net", "mvs_query_forward_workspace", "mvs_forward_images",
     "mvs_feature_net_fmt", "mvs_forward_images_fmt", "mvs_depth_infer_views",
     "mvs_query_metrics_workspace", "mvs_depth_metrics",
+    "mvs_warp_variance_backward", "mvs_softargmin_backward",
 )
 
 # mvs_image_format (include/mvs_abi.h)
@@ -120,6 +121,8 @@ def load():
                                          _d, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]
         lib.mvs_query_metrics_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_sz)]
         lib.mvs_depth_metrics.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]
+        lib.mvs_warp_variance_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]
+        lib.mvs_softargmin_backward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]
         for name in SYMBOLS:
             if name not in ("mvs_last_error_string",):
                 getattr(lib, name).restype = _i
@@ -290,6 +293,39 @@ def softargmin_conf(cost, depth_values):
                                      depth.data_ptr(), conf.data_ptr(), D, h, w,
                                      _stream(cost.device)))
     return depth, conf
+
+
+def warp_variance_backward(feats, rt, depth_values, grad_var, out=None):
+    """Adjoint of warp_variance (fp32): feats [N,32,h,w], rt [(N-1),12], depth_values [D], grad_var [32,D,h,w]
+    (NCDHW) -> grad_feats [N,32,h,w] (into `out` when given).  Enqueued on the current stream."""
+    feats = _dev_f32(feats, "features")
+    grad_var = _dev_f32(grad_var, "grad_var")
+    N, C, h, w = feats.shape
+    D = depth_values.shape[0]
+    if tuple(grad_var.shape) != (C, D, h, w):
+        raise RuntimeError(f"grad_var {tuple(grad_var.shape)} must be [{C},{D},{h},{w}]")
+    if out is None:
+        out = torch.empty_like(feats)
+    elif tuple(out.shape) != tuple(feats.shape) or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != feats.device:
+        raise RuntimeError("warp_variance_backward: out must be a contiguous float32 tensor shaped like feats")
+    check(load().mvs_warp_variance_backward(feats.data_ptr(), _dev_f32(rt, "rt").data_ptr(),
+                                            _dev_f32(depth_values, "depth_values").data_ptr(), grad_var.data_ptr(),
+                                            out.data_ptr(), N, C, D, h, w, _stream(feats.device)))
+    return out
+
+
+def softargmin_backward(cost, depth_values, grad_depth):
+    """Adjoint of softargmin_conf's depth: cost [D,h,w], depth_values [D], grad_depth [h,w] -> grad_cost [D,h,w]."""
+    cost = _dev_f32(cost, "cost")
+    D, h, w = cost.shape
+    grad_depth = _dev_f32(grad_depth, "grad_depth")
+    if tuple(grad_depth.shape) != (h, w):
+        raise RuntimeError(f"grad_depth {tuple(grad_depth.shape)} must be [{h},{w}]")
+    gc = torch.empty_like(cost)
+    check(load().mvs_softargmin_backward(cost.data_ptr(), _dev_f32(depth_values, "depth_values").data_ptr(),
+                                         grad_depth.data_ptr(), gc.data_ptr(), D, h, w, _stream(cost.device)))
+    return gc
 
 
 def depth_infer(feats, proj, depth_values, blob, workspace, depth_out, conf_out, dtype=MVS_F32):

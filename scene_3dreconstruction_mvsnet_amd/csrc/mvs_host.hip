@@ -306,6 +306,29 @@ int mvs_softargmin_conf(const float* cost, const float* depth_values, float* dep
                              static_cast<hipStream_t>(stream));
 }
 
+// adjoint of mvs_warp_variance (fp32): train_backward.hip
+int mvs_warp_variance_backward(const float* feats, const float* rt, const float* depth_values, const float* grad_var,
+                               float* grad_feats, int N, int C, int D, int h, int w, void* stream) {
+    if (!feats || !depth_values || !grad_var || !grad_feats || (N > 1 && !rt))
+        return fail(MVS_ERR_NULL, "mvs_warp_variance_backward: NULL argument");
+    // the forward's shape domain; every index of the kernel stays inside it (size_t volume offsets, int texel
+    // offsets below h*w < 2^24)
+    if (int st = check_dims(N, C, D, h, w, MVS_F32)) return st;
+    return launch_warp_variance_backward(feats, rt, depth_values, grad_var, grad_feats, N, D, h, w,
+                                         static_cast<hipStream_t>(stream));
+}
+
+// adjoint of the depth output of mvs_softargmin_conf: train_backward.hip
+int mvs_softargmin_backward(const float* cost, const float* depth_values, const float* grad_depth,
+                            float* grad_cost, int D, int h, int w, void* stream) {
+    if (!cost || !depth_values || !grad_depth || !grad_cost)
+        return fail(MVS_ERR_NULL, "mvs_softargmin_backward: NULL argument");
+    if (D < 1 || h < 1 || w < 1 || (size_t)h * w >= ((size_t)1 << 31))
+        return fail(MVS_ERR_BAD_SHAPE, "mvs_softargmin_backward: D,h,w = %d,%d,%d", D, h, w);
+    return launch_softargmin_backward(cost, depth_values, grad_depth, grad_cost, D, h, w,
+                                      static_cast<hipStream_t>(stream));
+}
+
 // feats == NULL: features already in the workspace's C8 slot (see warp_variance_impl); otherwise
 // view n is feats[views.v[n]], with the table validated by the caller
 static int depth_infer_impl(const float* feats, const ViewTable& views, const float* proj, const float* depth_values,

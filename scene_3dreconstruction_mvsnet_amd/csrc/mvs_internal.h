@@ -325,5 +325,10 @@ int launch_softargmin(const float* cost, const float* dv, float* depth, float* c
                       int w, hipStream_t s);
 int launch_depth_regression(const float* p, const float* dv, float* depth, int D, int h, int w,
                             hipStream_t s);
+// adjoints for training (train_backward.hip)
+int launch_warp_variance_backward(const float* feats, const float* rt, const float* dv, const float* g, float* gf,
+                                  int N, int D, int h, int w, hipStream_t s);
+int launch_softargmin_backward(const float* cost, const float* dv, const float* grad_depth, float* grad_cost, int D,
+                               int h, int w, hipStream_t s);
 
 }  // namespace mvs

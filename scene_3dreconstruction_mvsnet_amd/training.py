@@ -1,0 +1,230 @@
+"""Training path: the reference's `train.py --mode train` step on the MI355X (models/mvsnet.py:91-244, train.py:241-298).
+
+The cost volume and the soft-argmin -- the parts of a training step whose torch autograd graph is largest -- run as
+HIP kernels with hand-written adjoints (csrc/train_backward.hip); FeatureNet and CostRegNet run in torch (MIOpen)
+with autograd:
+
+  cost_volume(feats, proj_matrices, depth_values)   mvs_relative_proj + mvs_warp_variance (fp32) forward,
+                                                    mvs_warp_variance_backward; saves only its inputs, rt and the
+                                                    depth values (no volume)
+  soft_argmin(cost, depth_values)                   mvs_softargmin_conf forward, mvs_softargmin_backward; only the
+                                                    depth is differentiable (the confidence is no_grad, mvsnet.py:213)
+  mvsnet_loss(depth_est, depth_gt, mask)            masked-mean smooth-L1 (mvsnet.py:242-244) without boolean
+                                                    indexing, so it never synchronises
+  TrainableMVSNet                                   MVSNet whose train-mode forward builds an autograd graph
+  train_sample(model, optimizer, sample)            one optimisation step, train.py:241-298
+
+Everything is enqueued on torch's current stream; nothing here synchronises except train_sample's one copy of its
+scalars to the host at the end, where the reference's tensor2float makes one copy per scalar.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import _lib, metrics
+from .mvsnet import MVSNet
+
+
+def feature_workspace_bytes(N, h, w):
+    """Workspace bytes mvs_warp_variance needs on its own: the feature-transpose region only (include/mvs_abi.h),
+    N*32*h*w fp32 rounded to 256 bytes -- not mvs_query_workspace's whole depth-path workspace, whose volume and
+    activation regions make it 0.90 GB instead of 7.9 MB at the training shape (512 x 640, D = 192).
+    tests/test_training_host.py and tests/test_gpu_training.py pin this size against the library from both sides."""
+    return (N * 32 * h * w * 4 + 255) // 256 * 256
+
+
+def _feature_workspace(N, h, w, device):
+    return torch.empty(feature_workspace_bytes(N, h, w), dtype=torch.uint8, device=device)
+
+
+class _CostVolume(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats, proj_matrices, depth_values):
+        B, N, C, h, w = feats.shape
+        D = depth_values.shape[1]
+        device = feats.device
+        with torch.cuda.device(device):
+            feats = _lib._dev_f32(feats.detach(), "features")
+            proj = _lib._dev_f32(proj_matrices.detach().to(device), "proj_matrices")
+            dv = _lib._dev_f32(depth_values.detach().to(device), "depth_values")
+            ws = _feature_workspace(N, h, w, device)
+            out = torch.empty((B, C, D, h, w), dtype=torch.float32, device=device)
+            rts = []
+            for b in range(B):
+                rt = _lib.relative_proj(proj[b])
+                var = _lib.warp_variance(feats[b], rt, dv[b], ws, _lib.MVS_F32)   # C8-planar [4,D,h,w,8]
+                out[b].view(C // 8, 8, D, h, w).copy_(var.permute(0, 4, 1, 2, 3))
+                rts.append(rt)
+        ctx.save_for_backward(feats, torch.stack(rts), dv)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_var):
+        feats, rts, dv = ctx.saved_tensors
+        if grad_var is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        with torch.cuda.device(feats.device):
+            grad_var = grad_var.contiguous()
+            grad = torch.empty_like(feats)
+            for b in range(feats.shape[0]):
+                _lib.warp_variance_backward(feats[b], rts[b], dv[b], grad_var[b], out=grad[b])
+        return grad, None, None
+
+
+def cost_volume(feats, proj_matrices, depth_values):
+    """Variance cost volume with autograd (models/module.py:96-139 + models/mvsnet.py:145-177, training branch).
+
+    feats [B,N,32,h,w] float32 CUDA (view 0 = reference view), proj_matrices [B,N,4,4], depth_values [B,D]
+    -> variance [B,32,D,h,w] float32, NCDHW as CostRegNet's Conv3d takes it.  Gradients flow to feats only."""
+    if not feats.is_cuda:
+        raise RuntimeError(f"cost_volume needs CUDA(ROCm) tensors: the depth path has no CPU implementation "
+                           f"(got feats on {feats.device})")
+    if feats.dim() != 5 or feats.shape[2] != 32:
+        raise RuntimeError(f"cost_volume: feats must be [B,N,32,h,w], got {tuple(feats.shape)}")
+    if proj_matrices.shape[:2] != feats.shape[:2] or depth_values.dim() != 2 \
+            or depth_values.shape[0] != feats.shape[0]:
+        raise RuntimeError(f"cost_volume: proj_matrices {tuple(proj_matrices.shape)} must be [B,N,4,4] and "
+                           f"depth_values {tuple(depth_values.shape)} [B,D] for feats {tuple(feats.shape)}")
+    return _CostVolume.apply(feats, proj_matrices, depth_values)
+
+
+class _SoftArgmin(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cost, depth_values):
+        B, D, h, w = cost.shape
+        device = cost.device
+        with torch.cuda.device(device):
+            cost = _lib._dev_f32(cost.detach(), "cost")
+            dv = _lib._dev_f32(depth_values.detach().to(device), "depth_values")
+            depth = torch.empty((B, h, w), dtype=torch.float32, device=device)
+            conf = torch.empty_like(depth)
+            for b in range(B):
+                d, c = _lib.softargmin_conf(cost[b], dv[b])
+                depth[b].copy_(d)
+                conf[b].copy_(c)
+        ctx.save_for_backward(cost, dv)
+        ctx.mark_non_differentiable(conf)
+        return depth, conf
+
+    @staticmethod
+    def backward(ctx, grad_depth, grad_conf):
+        cost, dv = ctx.saved_tensors
+        if grad_depth is None or not ctx.needs_input_grad[0]:
+            return None, None
+        with torch.cuda.device(cost.device):
+            grad_depth = grad_depth.contiguous()
+            grad = torch.empty_like(cost)
+            for b in range(cost.shape[0]):
+                grad[b].copy_(_lib.softargmin_backward(cost[b], dv[b], grad_depth[b]))
+        return grad, None
+
+
+def soft_argmin(cost, depth_values):
+    """cost logits [B,D,h,w], depth_values [B,D] -> (depth [B,h,w], photometric_confidence [B,h,w])
+    (models/mvsnet.py:192-218).  Only depth carries a gradient."""
+    if not cost.is_cuda:
+        raise RuntimeError(f"soft_argmin needs CUDA(ROCm) tensors (got cost on {cost.device})")
+    if cost.dim() != 4 or depth_values.shape != cost.shape[:2]:
+        raise RuntimeError(f"soft_argmin: cost {tuple(cost.shape)} must be [B,D,h,w] and depth_values "
+                           f"{tuple(depth_values.shape)} [B,D]")
+    return _SoftArgmin.apply(cost, depth_values)
+
+
+def mvsnet_loss(depth_est, depth_gt, mask):
+    """smooth_l1_loss(depth_est[mask > 0.5], depth_gt[mask > 0.5]) averaged over the selected pixels
+    (models/mvsnet.py:242-244), differentiable and without boolean indexing.  No valid pixel gives NaN, as the
+    reference's mean over an empty selection does."""
+    valid = mask > 0.5
+    est = torch.where(valid, depth_est, torch.zeros_like(depth_est))
+    gt = torch.where(valid, depth_gt, torch.zeros_like(depth_gt))
+    return F.smooth_l1_loss(est, gt, reduction="sum") / valid.sum().to(depth_est.dtype)
+
+
+def _conv_bn_relu(block, x):
+    return F.relu(block.bn(block.conv(x)), inplace=True)   # models/module.py:32-33
+
+
+def _costreg(cr, x):
+    """CostRegNet.forward (models/mvsnet.py:64-73) in torch, through the blocks' .conv / .bn modules."""
+    conv0 = _conv_bn_relu(cr.conv0, x)
+    conv2 = _conv_bn_relu(cr.conv2, _conv_bn_relu(cr.conv1, conv0))
+    conv4 = _conv_bn_relu(cr.conv4, _conv_bn_relu(cr.conv3, conv2))
+    x = _conv_bn_relu(cr.conv6, _conv_bn_relu(cr.conv5, conv4))
+    x = conv4 + cr.conv7(x)
+    x = conv2 + cr.conv9(x)
+    x = conv0 + cr.conv11(x)
+    return cr.prob(x)
+
+
+class TrainableMVSNet(MVSNet):
+    """MVSNet with a training-mode forward.  Same constructor, parameters and state_dict keys as MVSNet.
+
+    eval(): MVSNet.forward unchanged (all HIP).  train(): the reference's forward with an autograd graph --
+    FeatureNet in torch once per view (models/mvsnet.py:125: per-view BN batch statistics, running statistics
+    updated N times), cost_volume, CostRegNet in torch, soft_argmin.  The HIP inference blobs are re-packed from
+    the parameters after every train-mode forward (BN statistics) and whenever a parameter's `_version` changes
+    (optimizer steps, MVSNet._param_versions)."""
+
+    def forward(self, imgs, proj_matrices, depth_values):
+        if not self.training:
+            return super().forward(imgs, proj_matrices, depth_values)
+        n_imgs, n_proj = imgs.shape[1], proj_matrices.shape[1]
+        assert n_imgs == n_proj, "Different number of images and projection matrices"
+        if self.refine:
+            raise NotImplementedError("refine=True: the reference's RefineNet path is broken "
+                                      "(F.cat at models/mvsnet.py:85); every working caller passes "
+                                      "refine=False (eval.py:308)")
+        if _lib.dtype_code(self.storage_dtype) != _lib.MVS_F32:
+            raise RuntimeError(f"training needs storage_dtype 'f32' (got {self.storage_dtype!r}): 16-bit training "
+                               "is not implemented")
+        if not imgs.is_cuda:
+            raise RuntimeError("MVSNet.forward needs CUDA(ROCm) tensors: the depth path has no CPU "
+                               "implementation (got imgs on {})".format(imgs.device))
+        # BatchNorm updates its running statistics inside the backend's kernel, which need not bump the `_version`
+        # that MVSNet._param_versions compares; drop the packed inference blobs, the next eval forward re-packs them
+        # (parameter updates by the optimizer are in-place ops and are seen through `_version`)
+        with self._cache_lock:
+            self._blob_cache.clear()
+        device = imgs.device
+        if imgs.dtype == torch.uint8:   # the loader's conversion, on the device (as forward does)
+            if imgs.shape[2] != 3 and imgs.shape[-1] == 3:
+                imgs = imgs.permute(0, 1, 4, 2, 3)
+            imgs = imgs.to(torch.float32) / 255.0
+        with torch.cuda.device(device):
+            # step 1. feature extraction, one call per view (models/mvsnet.py:125)
+            feats = torch.stack([self.feature(imgs[:, v]) for v in range(imgs.shape[1])], dim=1)
+            # step 2. cost volume (models/mvsnet.py:145-177)
+            proj = proj_matrices.to(device=device, dtype=torch.float32)
+            dv = depth_values.to(device=device, dtype=torch.float32)
+            volume = cost_volume(feats, proj, dv)
+            # step 3. cost regularisation (models/mvsnet.py:180, 192)
+            cost = _costreg(self.cost_regularization, volume).squeeze(1)
+            # step 4. soft-argmin and photometric confidence (models/mvsnet.py:193-218)
+            depth, conf = soft_argmin(cost, dv)
+        return {"depth": depth, "photometric_confidence": conf}
+
+
+def train_sample(model, optimizer, sample):
+    """One training step as train.py:241-298: model.train(), zero_grad, forward, mvsnet_loss, backward, step.
+
+    sample: the reference loader's dict (imgs [B,N,3,H,W], proj_matrices [B,N,4,4], depth_values [B,D],
+    depth [B,h,w], mask [B,h,w]).  Returns (loss, scalar_outputs) as Python floats with the reference's keys:
+    loss, abs_depth_error, thres1mm_error .. thres8mm_error (the metrics.py drop-ins)."""
+    model.train()
+    optimizer.zero_grad()
+    device = next(model.parameters()).device
+    sc = {k: (v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v) for k, v in sample.items()}
+    depth_gt, mask = sc["depth"], sc["mask"]
+    outputs = model(sc["imgs"], sc["proj_matrices"], sc["depth_values"])
+    depth_est = outputs["depth"]
+    loss = mvsnet_loss(depth_est, depth_gt, mask)
+    with torch.no_grad():
+        est = depth_est.detach()
+        scalars = {"loss": loss.detach(),
+                   "abs_depth_error": metrics.AbsDepthError_metrics(est, depth_gt, mask)}
+        for t in metrics.THRESHOLDS:
+            scalars[f"thres{t}mm_error"] = metrics.Thres_metrics(est, depth_gt, mask, t)
+    loss.backward()
+    optimizer.step()
+    values = torch.stack([v.to(torch.float32) for v in scalars.values()]).tolist()   # one device-to-host copy
+    out = dict(zip(scalars.keys(), values))
+    return out["loss"], out

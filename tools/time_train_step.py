@@ -1,0 +1,203 @@
+#!/usr/bin/env python3
+"""Time the training path at the training shape (reference train.py defaults: N = 3 views, 512 x 640 images ->
+128 x 160 features, D = 192, B = 1) with device events after warm-up:
+
+  cost_volume   forward + backward of the variance cost volume: training.cost_volume (HIP) against the torch
+                autograd form written below (grid_sample + the reference's out-of-place sums, mvsnet.py:145-177)
+  train_step    one whole optimisation step: training.train_sample on TrainableMVSNet against the same step with
+                every stage in torch (FeatureNet, the torch cost volume, CostRegNet, softmax + depth regression)
+  soft_argmin   forward + backward of training.soft_argmin against torch softmax + depth regression
+
+and the peak torch.cuda.max_memory_allocated of each.  Prints one JSON document (and writes it to --out).
+    python tools/time_train_step.py [--warmup 3] [--iters 10] [--only cost_volume,train_step,soft_argmin]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from scene_3dreconstruction_mvsnet_amd import _lib, synthetic, training  # noqa: E402
+
+DEV = torch.device("cuda:0")
+N, H, W, D = 3, 512, 640, 192
+
+
+# ---------------------------------------------------------------- the all-torch forms
+def torch_cost_volume(feats, proj, dv):
+    """feats [B,N,C,h,w], proj [B,N,4,4], dv [B,D] -> variance [B,C,D,h,w]: models/module.py:96-139 and the
+    training branch of models/mvsnet.py:145-177 (grid under no_grad, out-of-place sums)."""
+    B, n, C, h, w = feats.shape
+    Dn = dv.shape[1]
+    ref = feats[:, 0]
+    ref_volume = ref.unsqueeze(2).repeat(1, 1, Dn, 1, 1)
+    volume_sum = ref_volume
+    volume_sq_sum = ref_volume ** 2
+    del ref_volume
+    for v in range(1, n):
+        with torch.no_grad():
+            pr = torch.matmul(proj[:, v], torch.inverse(proj[:, 0]))
+            rot, trans = pr[:, :3, :3], pr[:, :3, 3:4]
+            y, x = torch.meshgrid(torch.arange(h, dtype=torch.float32, device=DEV),
+                                  torch.arange(w, dtype=torch.float32, device=DEV), indexing="ij")
+            xyz = torch.stack((x.reshape(-1), y.reshape(-1), torch.ones(h * w, device=DEV)))
+            xyz = xyz.unsqueeze(0).repeat(B, 1, 1)
+            p = torch.matmul(rot, xyz).unsqueeze(2).repeat(1, 1, Dn, 1) * dv.view(B, 1, Dn, 1) + trans.view(B, 3, 1, 1)
+            pxy = p[:, :2] / p[:, 2:3]
+            gx = pxy[:, 0] / ((w - 1) / 2) - 1
+            gy = pxy[:, 1] / ((h - 1) / 2) - 1
+            grid = torch.stack((gx, gy), dim=3)
+        warped = F.grid_sample(feats[:, v], grid.view(B, Dn * h, w, 2), mode="bilinear", padding_mode="zeros",
+                               align_corners=False).view(B, C, Dn, h, w)
+        volume_sum = volume_sum + warped
+        volume_sq_sum = volume_sq_sum + warped ** 2
+        del warped
+    return volume_sq_sum.div_(n).sub_(volume_sum.div_(n).pow_(2))
+
+
+def torch_soft_argmin(cost, dv):
+    prob = F.softmax(cost, dim=1)
+    return torch.sum(prob * dv.view(*dv.shape, 1, 1), 1)
+
+
+def torch_train_step(model, opt, sample):
+    """train_sample with every stage in torch (the reference's step, train.py:241-298, minus its logging)."""
+    model.train()
+    opt.zero_grad()
+    imgs, proj, dv = sample["imgs"], sample["proj_matrices"], sample["depth_values"]
+    feats = torch.stack([model.feature(imgs[:, v]) for v in range(imgs.shape[1])], dim=1)
+    volume = torch_cost_volume(feats, proj, dv)
+    cost = training._costreg(model.cost_regularization, volume).squeeze(1)
+    depth = torch_soft_argmin(cost, dv)
+    loss = training.mvsnet_loss(depth, sample["depth"], sample["mask"])
+    loss.backward()
+    opt.step()
+    return loss
+
+
+# ---------------------------------------------------------------- timing
+def timed(fn, warmup, iters):
+    """(median ms, min ms, peak bytes) of fn() over `iters` runs after `warmup`, each bracketed by events."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(DEV)
+    base = torch.cuda.memory_allocated(DEV)
+    times = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    peak = torch.cuda.max_memory_allocated(DEV) - base
+    return {"median_ms": float(np.median(times)), "min_ms": float(np.min(times)), "peak_bytes": int(peak)}
+
+
+def make_sample():
+    imgs, proj, dv = synthetic.make_inputs(N, H, W, D, seed=1)
+    rng = np.random.default_rng(2)
+    gt = rng.uniform(dv[0, 10], dv[0, -10], size=(1, H // 4, W // 4)).astype(np.float32)
+    mask = (rng.uniform(size=gt.shape) > 0.2).astype(np.float32)
+    t = lambda a: torch.from_numpy(a).to(DEV)  # noqa: E731
+    return {"imgs": t(imgs), "proj_matrices": t(proj), "depth_values": t(dv), "depth": t(gt), "mask": t(mask)}
+
+
+def bench_cost_volume(sample, warmup, iters):
+    h, w = H // 4, W // 4
+    feats = torch.randn((1, N, 32, h, w), generator=torch.Generator().manual_seed(0)).to(DEV).requires_grad_(True)
+    g = torch.randn((1, 32, D, h, w), generator=torch.Generator().manual_seed(1)).to(DEV)
+    proj, dv = sample["proj_matrices"], sample["depth_values"]
+
+    def run(fn):
+        def step():
+            feats.grad = None
+            fn(feats, proj, dv).backward(g)
+        return step
+
+    out = {"hip": timed(run(training.cost_volume), warmup, iters),
+           "torch": timed(run(torch_cost_volume), warmup, iters)}
+    # the HIP backward alone (the new kernel plus its zero-fill), for the atomic-byte floor below
+    rt = _lib.relative_proj(proj[0])
+    out["hip_backward_only"] = timed(lambda: _lib.warp_variance_backward(feats.detach()[0], rt, dv[0], g[0]),
+                                     warmup, iters)
+    # direct global atomics of a naive scatter: 4 taps x 32 channels x D x h x w per source view, 4 bytes each
+    naive_bytes = 4 * 32 * D * h * w * (N - 1) * 4
+    out["naive_atomic_bytes"] = naive_bytes
+    out["naive_atomic_floor_ms_at_1.3TBps"] = naive_bytes / 1.3e12 * 1e3
+    return out
+
+
+def bench_soft_argmin(warmup, iters):
+    h, w = H // 4, W // 4
+    cost = (torch.randn((1, D, h, w), generator=torch.Generator().manual_seed(3)) * 5).to(DEV).requires_grad_(True)
+    dv = torch.from_numpy(synthetic.depth_values(D))[None].to(DEV)
+    gd = torch.randn((1, h, w), device=DEV)
+
+    def hip():
+        cost.grad = None
+        training.soft_argmin(cost, dv)[0].backward(gd)
+
+    def tor():
+        cost.grad = None
+        torch_soft_argmin(cost, dv).backward(gd)
+
+    return {"hip": timed(hip, warmup, iters), "torch": timed(tor, warmup, iters)}
+
+
+def bench_train_step(sample, warmup, iters):
+    out = {}
+    for name in ("hip", "torch"):
+        torch.manual_seed(0)
+        model = training.TrainableMVSNet(refine=False).to(DEV)
+        opt = torch.optim.Adam(model.parameters(), lr=1e-3, betas=(0.9, 0.999), weight_decay=0.0)
+        if name == "hip":
+            out[name] = timed(lambda: training.train_sample(model, opt, sample), warmup, iters)
+        else:
+            out[name] = timed(lambda: torch_train_step(model, opt, sample), warmup, iters)
+        del model, opt
+        torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--only", default="cost_volume,soft_argmin,train_step")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    _lib.load()
+    sample = make_sample()
+    res = {"shape": {"N": N, "H": H, "W": W, "D": D, "B": 1}, "warmup": args.warmup, "iters": args.iters,
+           "device": torch.cuda.get_device_name(DEV), "torch": torch.__version__}
+    t0 = time.time()
+    for part in args.only.split(","):
+        if part == "cost_volume":
+            res[part] = bench_cost_volume(sample, args.warmup, args.iters)
+        elif part == "soft_argmin":
+            res[part] = bench_soft_argmin(args.warmup, args.iters)
+        elif part == "train_step":
+            res[part] = bench_train_step(sample, args.warmup, args.iters)
+        else:
+            raise SystemExit(f"unknown part {part!r}")
+    res["wall_s"] = round(time.time() - t0, 1)
+    text = json.dumps(res, indent=1)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
