@@ -205,6 +205,20 @@ __device__ __forceinline__ void store_voxel_buf(__amdgpu_buffer_rsrc_t rs, unsig
     }
 }
 
+// Depth slabs launch_tc2_dt chooses from, and the largest of them.  A block's out-of-image lanes park their volume offset
+// `slab` planes of one channel plane below 0xFFFFFFE0 and advance one plane per depth step, so warp_tc_fits keeps the
+// volume kMaxSlab + 4 planes clear of that range.  The PAIR loop steps four depths at a time with guards for a last pair or
+// step cut short; D is a multiple of 8 (check_dims), so with slabs that are multiples of 4 every slab, the ragged last
+// one included, runs whole iterations only -- the guarded partial steps never run, and no test covers them.
+constexpr int kTcSlabs[] = {40, 44, 36, 32, 28, 24};
+constexpr int kMaxSlab = 44;
+constexpr bool tc_slabs_ok() {
+    for (const int s : kTcSlabs)
+        if (s > kMaxSlab || s % 4 != 0) return false;
+    return true;
+}
+static_assert(tc_slabs_ok(), "every slab candidate must be <= kMaxSlab (the parking margin) and a multiple of 4");
+
 // the lanes 4q .. 4q+3 of every 8-lane pixel group hand their value to the group's other quad
 template <int Q>
 __device__ __forceinline__ int pair_pick(int v) {
@@ -422,7 +436,7 @@ int launch_tc2_dt(const void* feats_p, const float* rt, const float* dv, void* v
     // 32 / 64 = 1.95 / 1.86 / 1.78 ms): the linear block id then sends slab s of EVERY pixel block to XCD s % 8, so every
     // XCD's L2 streams the whole feature set
     int slab = 40;
-    for (const int cand : {40, 44, 36, 32, 28, 24}) {   // the first whose slab count is not a multiple of 8 (D = 320: 36)
+    for (const int cand : kTcSlabs) {   // the first whose slab count is not a multiple of 8 (D = 320: 36)
         slab = cand;
         if (((D + cand - 1) / cand) % 8 != 0) break;
     }
@@ -452,9 +466,11 @@ int launch_tc2_dt(const void* feats_p, const float* rt, const float* dv, void* v
 // (16 VGPRs of cached taps per source view).  Other problems run the plain kernel (warp_variance.hip).
 bool warp_tc_fits(int N, int D, int h, int w, int fes, int ves) {
     const size_t hw = (size_t)h * w;
-    // (+ 48 depth planes of one channel plane: the parking range of the last block's out-of-image lanes, slab <= 44)
+    // (+ kMaxSlab + 4 = 48 depth planes of one channel plane: the parking range of the last block's out-of-image lanes)
+    constexpr size_t park = kMaxSlab + 4;
+    static_assert(park == 48, "tests/test_gpu_limits.py's tc_fits restates the 48-plane margin");
     return N >= 2 && N <= 5 && 4 * (size_t)N * hw * 8 * fes < ((size_t)1 << 31) &&
-           4 * (size_t)D * hw * 8 * ves + 48 * hw * 8 * ves < ((size_t)1 << 32) - 64 && hw < ((size_t)1 << 29);
+           4 * (size_t)D * hw * 8 * ves + park * hw * 8 * ves < ((size_t)1 << 32) - 64 && hw < ((size_t)1 << 29);
 }
 
 // fp32 features [4][N][h][w][8], volume in `dtype`
