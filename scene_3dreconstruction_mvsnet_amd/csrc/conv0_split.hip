@@ -36,16 +36,11 @@
 
 #include "mvs_internal.h"
 #include "storage.h"
+#include "mfma16_ops.h"
 
 namespace mvs {
 
-typedef unsigned int su32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int su32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 sbf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x4 mfma_bf16(su32x4 a, su32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(sbf16x8, a), __builtin_bit_cast(sbf16x8, b), c, 0, 0, 0);
-}
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 namespace c48t {
 constexpr int TZ = 4, TY = 8, TX = 32;
@@ -71,28 +66,17 @@ constexpr unsigned bstep(int s) { return (unsigned)(((s >> 1) * NT_PLANES + 3 * 
 __device__ __forceinline__ int chunk_of(int k, int c) { return (k & 1) ? 3 - c : c; }
 __device__ __forceinline__ unsigned bofs(int chunk, int h) { return (unsigned)((chunk * NT_PLANES + 3 * h) * 9) * 1024u; }
 }  // namespace c48t
-typedef float sf32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 sbf16x2 __attribute__((ext_vector_type(2)));
 
-// packed = (bf16(a.x), bf16(a.y)) RNE; returns a - widen(packed) (exact).  (Tried: the residual as one
-// v_dot2c_f32_bf16 per value, D += h . (-1, 0) -- 14 instead of 18 instructions per 4 values.  The build was not faster
-// (0.283 vs 0.276-0.283 ms) and its results were WRONG (heavy-tailed test 7.5e4 x its bound): the packed-bf16 inline
-// constant hipcc emits for (-1, 0) is not what the instruction reads.  Dropped.)
-__device__ __forceinline__ sf32x2 split_stage(const sf32x2 a, unsigned& packed) {
-    const sbf16x2 h = __builtin_convertvector(a, sbf16x2);
-    packed = __builtin_bit_cast(unsigned, h);
-    const sf32x2 w = {__uint_as_float(packed << 16), __uint_as_float(packed & 0xFFFF0000u)};
-    return a - w;
-}
-__device__ __forceinline__ void split3x(const f32x4 v, su32x2& p1, su32x2& p2, su32x2& p3) {
+// 4 fp32 values -> three 8-byte bf16 pairs (split_stage: mfma16_ops.h)
+__device__ __forceinline__ void split3x(const f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
     unsigned a0, a1, b0, b1, c0, c1;
-    const sf32x2 r0 = split_stage((sf32x2){v.x, v.y}, a0), r1 = split_stage((sf32x2){v.z, v.w}, a1);
-    const sf32x2 q0 = split_stage(r0, b0), q1 = split_stage(r1, b1);
-    c0 = __builtin_bit_cast(unsigned, __builtin_convertvector(q0, sbf16x2));
-    c1 = __builtin_bit_cast(unsigned, __builtin_convertvector(q1, sbf16x2));
-    p1 = (su32x2){a0, a1};
-    p2 = (su32x2){b0, b1};
-    p3 = (su32x2){c0, c1};
+    const f32x2 r0 = split_stage((f32x2){v.x, v.y}, a0), r1 = split_stage((f32x2){v.z, v.w}, a1);
+    const f32x2 q0 = split_stage(r0, b0), q1 = split_stage(r1, b1);
+    c0 = __builtin_bit_cast(unsigned, __builtin_convertvector(q0, bf16x2));
+    c1 = __builtin_bit_cast(unsigned, __builtin_convertvector(q1, bf16x2));
+    p1 = (u32x2){a0, a1};
+    p2 = (u32x2){b0, b1};
+    p3 = (u32x2){c0, c1};
 }
 
 // One half-step of a consumer wave: 9 (A piece p, unit i) combos; a combo reads its 4 A fragments (halo rows) once for
@@ -102,17 +86,17 @@ __device__ __forceinline__ void split3x(const f32x4 v, su32x2& p1, su32x2& p2, s
 // combo's MFMAs) was exposed at every combo.  The scheduler is held to this order (sched_barrier): left alone it hoists
 // every ds_read of the unrolled step and spills.
 __device__ __forceinline__ void c48t_step_mfmas(const unsigned short* __restrict__ tile, const int (&aoff)[3],
-                                                const su32x4 (&B)[2][3][3], su32x4 (&Bn)[2][3][3],
+                                                const u32x4 (&B)[2][3][3], u32x4 (&Bn)[2][3][3],
                                                 __amdgpu_buffer_rsrc_t brs, const unsigned (&bvoff)[2], unsigned bnext,
                                                 f32x4 (&acc)[3][2]) {
     using namespace c48t;
     constexpr int NC = 9;
-    su32x4 a[3][4];
+    u32x4 a[3][4];
     auto request = [&](int n) {
         const int pn = n / 3, in = n % 3;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            a[n % 3][j] = *reinterpret_cast<const su32x4*>(tile + pn * PIECE_E + aoff[in] + j * HX * 8);
+            a[n % 3][j] = *reinterpret_cast<const u32x4*>(tile + pn * PIECE_E + aoff[in] + j * HX * 8);
     };
     request(0);
     request(1);
@@ -125,7 +109,7 @@ __device__ __forceinline__ void c48t_step_mfmas(const unsigned short* __restrict
         // producers' activation loads share the queue) with the MFMAs waiting behind them
 #pragma unroll
         for (int f = 2 * n; f < 2 * n + 2; ++f)
-            Bn[f / 9][(f / 3) % 3][f % 3] = __builtin_bit_cast(su32x4, __builtin_amdgcn_raw_buffer_load_b128(
+            Bn[f / 9][(f / 3) % 3][f % 3] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
                 brs, (int)bvoff[f / 9], (int)(bnext + (unsigned)(f % 9) * 1024u), 0));
         const int pl = i == 2 ? 1 : 0;
 #pragma unroll
@@ -134,7 +118,7 @@ __device__ __forceinline__ void c48t_step_mfmas(const unsigned short* __restrict
             for (int q = 0; q < 3 - p; ++q)
 #pragma unroll
                 for (int rr = 0; rr < 2; ++rr)
-                    acc[i][rr] = mfma_bf16(a[n % 3][rr + ky], B[pl][ky][q], acc[i][rr]);
+                    acc[i][rr] = mfma16<MVS_BF16>(a[n % 3][rr + ky], B[pl][ky][q], acc[i][rr]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -207,14 +191,14 @@ __global__ __launch_bounds__(512) void conv0_w48t_kernel(
         for (int i = 0; i < 3; ++i) aoff[i] = upl[i] * PLANE_E + ((2 * urp[i]) * HX + 2 * r + g) * 8;
         // B fragments by raw buffer loads: the lane's 16 bytes + the plane in the vector offset, the fragment in the
         // scalar offset -- plain pointers made hipcc materialise (and spill) 35 64-bit addresses
-        su32x4 B[2][2][3][3];   // two sets: the next step's 18 fragments are requested during a step
+        u32x4 B[2][2][3][3];   // two sets: the next step's 18 fragments are requested during a step
         const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<unsigned short*>(bp), (short)0, 4 * NT_PLANES * 9 * 1024, 0x00020000);
         const unsigned bvoff[2] = {(unsigned)lane * 16u + (unsigned)pa * 9u * 1024u,
                                    (unsigned)lane * 16u + (unsigned)pb * 9u * 1024u};
 #pragma unroll
         for (int f = 0; f < 18; ++f)
-            B[0][f / 9][(f / 3) % 3][f % 3] = __builtin_bit_cast(su32x4, __builtin_amdgcn_raw_buffer_load_b128(
+            B[0][f / 9][(f / 3) % 3][f % 3] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
                 brs, (int)bvoff[f / 9], (int)(bstep(0) + (unsigned)(f % 9) * 1024u), 0));
         f32x4 acc[2][3][2];   // [half][unit][row of the pair]
 #pragma unroll
@@ -263,7 +247,7 @@ __global__ __launch_bounds__(512) void conv0_w48t_kernel(
             for (int q = 0; q < TZ; ++q) {
                 const f32x4 v = __builtin_elementwise_max(o[q] + obias, zero);
                 const unsigned off = (ok && z0 + q < D) ? base + (unsigned)q * (unsigned)(HW8 * 4) : 0xFFFFFFF0u;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(su32x4, v), yrs, (int)off, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yrs, (int)off, 0, 0);
             }
         };
         int kk = 0;
@@ -339,9 +323,9 @@ __global__ __launch_bounds__(512) void conv0_w48t_kernel(
         f32x4 stg[CPT][NT_PLANES];   // the staged chunk
         f32x4 hold[CPT][NPL];        // U3..U5 of the chunk transformed a step ago
         auto put = [&](unsigned short* dstbuf, int i, int t, const f32x4 u) {
-            su32x2 p1, p2, p3;
+            u32x2 p1, p2, p3;
             split3x(u, p1, p2, p3);
-            su32x2* dst = reinterpret_cast<su32x2*>(dstbuf) + t * (PLANE_E / 4) + loff[i];
+            u32x2* dst = reinterpret_cast<u32x2*>(dstbuf) + t * (PLANE_E / 4) + loff[i];
             dst[0] = p1;
             dst[PIECE_E / 4] = p2;
             dst[2 * (PIECE_E / 4)] = p3;

@@ -36,7 +36,7 @@
 
 #include "mvs_internal.h"
 #include "storage.h"
-#include "split_ops.h"
+#include "mfma16_ops.h"
 
 namespace mvs {
 
@@ -65,8 +65,6 @@ __host__ __device__ constexpr int win_slot(int rho, int c) {
 }
 }  // namespace cp
 
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-
 // ---------------------------------------------------------------------------------------------
 // 512 threads per block; everything before the stencil is private to a wave (the first form, with a shared
 // input halo and six block barriers per step, is csrc/attic/conv11_prob_form1.hip in commit c2f08ac).  Wave w owns M-tile w (2 x 8 input voxels -> a 4 x 16 strip of both conv11 planes): it
@@ -93,14 +91,9 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_priv_kernel(
     __shared__ __attribute__((aligned(16))) float bpan[2 * 9 * 64 * 4];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // blocks are dealt round-robin over the 8 XCDs (blockIdx.x % 8 names the XCD: speed only, never correctness) and
-    // every XCD has its own L2: XCD k works through the k-th eighth of the (z chunk, row, column) sequence, so that
-    // tiles sharing a halo column / row (and the skip planes both read) run on the same L2 at about the same time
-    int b;
-    {
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;   // XCD k runs q (+1 if k < rem) blocks
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
+    // XCD-aware order of the (z chunk, row, column) sequence: tiles sharing a halo column / row (and the skip planes both
+    // read) run on the same L2 at about the same time
+    int b = xcd_block();
     const int bx = b % nbx; b /= nbx;
     const int by = b % nby;
     const int bz = b / nby;
@@ -215,7 +208,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_priv_kernel(
                         (lx >= 1 || ix0 == 0) && (lx <= OX - 2 || gxo == Wo - 1);
     const size_t pout = (size_t)gyo * Wo + gxo;
     const int cbase = ly * RS + lx * 4;   // LDS row r = tile row r - 1, x index lx = tile column lx - 1
-    auto stencil = [&](int plane, f32x2v& k2, f32x2v& k1, f32x2v& k0) {
+    auto stencil = [&](int plane, f32x2& k2, f32x2& k1, f32x2& k0) {
         const float* base = ct + plane * PS + cbase;
 #pragma unroll 1
         for (int kx = 0; kx < 3; ++kx) {
@@ -234,10 +227,10 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_priv_kernel(
 #pragma unroll
                 for (int c2 = 0; c2 < 4; ++c2) {
                     const f32x4 q = v[ky][c2 >> 1];
-                    const f32x2v d = (c2 & 1) ? (f32x2v){q.z, q.w} : (f32x2v){q.x, q.y};
-                    k2 = __builtin_elementwise_fma(d, (f32x2v){w2[2 * c2], w2[2 * c2 + 1]}, k2);
-                    k1 = __builtin_elementwise_fma(d, (f32x2v){w1[2 * c2], w1[2 * c2 + 1]}, k1);
-                    k0 = __builtin_elementwise_fma(d, (f32x2v){w0[2 * c2], w0[2 * c2 + 1]}, k0);
+                    const f32x2 d = (c2 & 1) ? (f32x2){q.z, q.w} : (f32x2){q.x, q.y};
+                    k2 = __builtin_elementwise_fma(d, (f32x2){w2[2 * c2], w2[2 * c2 + 1]}, k2);
+                    k1 = __builtin_elementwise_fma(d, (f32x2){w1[2 * c2], w1[2 * c2 + 1]}, k1);
+                    k0 = __builtin_elementwise_fma(d, (f32x2){w0[2 * c2], w0[2 * c2 + 1]}, k0);
                 }
             }
         }
@@ -245,14 +238,14 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_priv_kernel(
     // logits leave by raw buffer stores: a position that is not this block's to write gets an offset beyond the
     // descriptor (dropped by the hardware) -- no branch around a VMEM instruction (see conv11_prob16_kernel)
     const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(cost, (short)0, (int)((size_t)Do * HWo * 4), 0x00020000);
-    auto emit = [&](int oz, const f32x2v& sv, bool live) {
+    auto emit = [&](int oz, const f32x2& sv, bool live) {
         const unsigned off = (pvalid && live) ? (unsigned)(((size_t)oz * HWo + pout) * 4) : 0xFFFFFFFCu;
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sv.x + sv.y), crs, (int)off, 0, 0);
     };
 
     const float pb = pbias[0];
-    const f32x2v fresh = {pb, 0.0f};
-    f32x2v A = fresh, B = fresh, C = fresh;
+    const f32x2 fresh = {pb, 0.0f};
+    f32x2 A = fresh, B = fresh, C = fresh;
 
     for (int k = tid; k < C_FLOATS / 4; k += 512) reinterpret_cast<f32x4*>(ct)[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int k = tid; k < 2 * 9 * 64; k += 512) reinterpret_cast<f32x4*>(bpan)[k] = reinterpret_cast<const f32x4*>(bp)[k];
@@ -314,7 +307,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_priv_kernel(
         A = fresh;
         if (dodd) stencil(1, B, C, A);         // odd plane 2i + 1: completes logit 2i
         emit(2 * i, B, dodd && de);
-        const f32x2v t = A;  // (A, B, C) <- logits (2i+1, 2i+2, 2i+3)
+        const f32x2 t = A;  // (A, B, C) <- logits (2i+1, 2i+2, 2i+3)
         A = C;
         B = t;
         C = fresh;
@@ -338,28 +331,6 @@ constexpr int WIN = WSLOTS * 8;              // one chunk, 16-bit elements: [pla
 constexpr int NPC = 2 * 27;                  // 16-byte pieces of it: [plane][3 x 9 voxels]
 }  // namespace cpv16
 
-typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16v(u32x4v a, u32x4v b, f32x4 c) {
-    if (DT == MVS_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8v, a), __builtin_bit_cast(f16x8v, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8v, a), __builtin_bit_cast(bf16x8v, b), c, 0, 0, 0);
-}
-template <int DT>
-__device__ __forceinline__ void unpack8(u32x4v v, float (&o)[8]) {
-    if (DT == MVS_F16) {
-        const f16x8v h = __builtin_bit_cast(f16x8v, v);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (float)h[i];
-    } else {
-        const bf16x8v h = __builtin_bit_cast(bf16x8v, v);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (float)h[i];
-    }
-}
 template <int DT>
 __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
     const void* __restrict__ x, const unsigned short* __restrict__ bp, const float* __restrict__ bias,
@@ -373,14 +344,9 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
     __shared__ __attribute__((aligned(16))) unsigned short win[8 * 2 * WIN];   // [wave][chunk][win_slot(plane, row, voxel)]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // blocks are dealt round-robin over the 8 XCDs (blockIdx.x % 8 names the XCD: speed only, never correctness) and
-    // every XCD has its own L2: XCD k works through the k-th eighth of the (z chunk, row, column) sequence, so that
-    // tiles sharing a halo column / row (and the skip planes both read) run on the same L2 at about the same time
-    int b;
-    {
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;   // XCD k runs q (+1 if k < rem) blocks
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
+    // XCD-aware order of the (z chunk, row, column) sequence: tiles sharing a halo column / row (and the skip planes both
+    // read) run on the same L2 at about the same time
+    int b = xcd_block();
     const int bx = b % nbx; b /= nbx;
     const int by = b % nby;
     const int bz = b / nby;
@@ -400,21 +366,21 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
     const bool pin = lane < NPC && pgy < Hi && pgx < Wi;
     const size_t prel = pin ? (((size_t)phz * Hi + pgy) * Wi + pgx) * 8 : 0;
     const int ploff = win_slot(phz * 3 + phr, phc) * 8;
-    u32x4v pre[2];
+    u32x4 pre[2];
     bool pre_z1 = true;
     auto load_a = [&](int i) {    // both chunks of input planes i, i + 1; raw loads, masked when they go to LDS
         pre_z1 = i + 1 < Di;
         const bool ok = pin && (pre_z1 || phz == 0);
 #pragma unroll
         for (int c = 0; c < 2; ++c)
-            pre[c] = *reinterpret_cast<const u32x4v*>(xs + (ok ? ((size_t)c * Vin + (size_t)i * HWi) * 8 + prel : (size_t)0));
+            pre[c] = *reinterpret_cast<const u32x4*>(xs + (ok ? ((size_t)c * Vin + (size_t)i * HWi) * 8 + prel : (size_t)0));
     };
     auto store_a = [&]() {
         const bool ok = pin && (pre_z1 || phz == 0);
         if (lane < NPC) {
 #pragma unroll
             for (int c = 0; c < 2; ++c)
-                *reinterpret_cast<u32x4v*>(my + c * WIN + ploff) = ok ? pre[c] : (u32x4v){0u, 0u, 0u, 0u};
+                *reinterpret_cast<u32x4*>(my + c * WIN + ploff) = ok ? pre[c] : (u32x4){0u, 0u, 0u, 0u};
         }
     };
     // MFMA lane roles (deconvg16_mfma_kernel): row r -> input voxel (r >> 3, r & 7) of the M-tile; g: dx = g & 1,
@@ -436,20 +402,20 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
     const bool sok = 2 * iy0 + soy < Ho && 2 * ix0 + sox < Wo;
     const size_t srel = sok ? ((size_t)(2 * iy0 + soy) * Wo + 2 * ix0 + sox) * 8 : 0;
     const int sl = (soy + 1) * RS + (sox + 1) * 4;
-    u32x4v sk[2];
+    u32x4 sk[2];
     auto load_skip = [&](int i, bool de, bool dodd) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const bool ok = sok && (j ? dodd : de);
-            sk[j] = *reinterpret_cast<const u32x4v*>(sks + (ok ? (size_t)(2 * i + j) * HWo * 8 + srel : (size_t)0));   // masked when added
+            sk[j] = *reinterpret_cast<const u32x4*>(sks + (ok ? (size_t)(2 * i + j) * HWo * 8 + srel : (size_t)0));   // masked when added
         }
     };
     // the whole panel (2 chunks x 5 k-steps) in registers
-    u32x4v breg[2][5];
+    u32x4 breg[2][5];
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
-        for (int ks = 0; ks < 5; ++ks) breg[c][ks] = reinterpret_cast<const u32x4v*>(bp)[(c * 5 + ks) * 64 + lane];
+        for (int ks = 0; ks < 5; ++ks) breg[c][ks] = reinterpret_cast<const u32x4*>(bp)[(c * 5 + ks) * 64 + lane];
     f32x4 acc[4];
     auto mfma_all = [&]() {
 #pragma unroll
@@ -459,8 +425,8 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
                 constexpr int dummy = 0;
                 (void)dummy;
                 const int cls = deconv16_tap(ks, 0).cls;
-                const u32x4v a = *reinterpret_cast<const u32x4v*>(my + c * WIN + koff[ks]);
-                acc[cls] = mfma16v<DT>(a, breg[c][ks], acc[cls]);
+                const u32x4 a = *reinterpret_cast<const u32x4*>(my + c * WIN + koff[ks]);
+                acc[cls] = mfma16<DT>(a, breg[c][ks], acc[cls]);
             }
     };
 
@@ -471,7 +437,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
                         (lx >= 1 || ix0 == 0) && (lx <= OX - 2 || gxo == Wo - 1);
     const size_t pout = (size_t)gyo * Wo + gxo;
     const int cbase = ly * RS + lx * 4;   // LDS row r = tile row r - 1, x index lx = tile column lx - 1
-    auto stencil = [&](int plane, f32x2v& k2, f32x2v& k1, f32x2v& k0) {
+    auto stencil = [&](int plane, f32x2& k2, f32x2& k1, f32x2& k0) {
         const float* base = ct + plane * PS + cbase;
 #pragma unroll 1
         for (int kx = 0; kx < 3; ++kx) {
@@ -490,10 +456,10 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
 #pragma unroll
                 for (int c2 = 0; c2 < 4; ++c2) {
                     const f32x4 q = v[ky][c2 >> 1];
-                    const f32x2v d = (c2 & 1) ? (f32x2v){q.z, q.w} : (f32x2v){q.x, q.y};
-                    k2 = __builtin_elementwise_fma(d, (f32x2v){w2[2 * c2], w2[2 * c2 + 1]}, k2);
-                    k1 = __builtin_elementwise_fma(d, (f32x2v){w1[2 * c2], w1[2 * c2 + 1]}, k1);
-                    k0 = __builtin_elementwise_fma(d, (f32x2v){w0[2 * c2], w0[2 * c2 + 1]}, k0);
+                    const f32x2 d = (c2 & 1) ? (f32x2){q.z, q.w} : (f32x2){q.x, q.y};
+                    k2 = __builtin_elementwise_fma(d, (f32x2){w2[2 * c2], w2[2 * c2 + 1]}, k2);
+                    k1 = __builtin_elementwise_fma(d, (f32x2){w1[2 * c2], w1[2 * c2 + 1]}, k1);
+                    k0 = __builtin_elementwise_fma(d, (f32x2){w0[2 * c2], w0[2 * c2 + 1]}, k0);
                 }
             }
         }
@@ -503,14 +469,14 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
     // for the loads requested a step ahead (round 4: with conditional loads / stores the ISA had vmcnt(1) / vmcnt(0)
     // right behind the prefetch of the NEXT step)
     const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(cost, (short)0, (int)((size_t)Do * HWo * 4), 0x00020000);
-    auto emit = [&](int oz, const f32x2v& sv, bool live) {
+    auto emit = [&](int oz, const f32x2& sv, bool live) {
         const unsigned off = (pvalid && live) ? (unsigned)(((size_t)oz * HWo + pout) * 4) : 0xFFFFFFFCu;
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sv.x + sv.y), crs, (int)off, 0, 0);
     };
 
     const float pb = pbias[0];
-    const f32x2v fresh = {pb, 0.0f};
-    f32x2v A = fresh, B = fresh, C = fresh;
+    const f32x2 fresh = {pb, 0.0f};
+    f32x2 A = fresh, B = fresh, C = fresh;
 
     for (int k = tid; k < C_FLOATS / 4; k += 512) reinterpret_cast<f32x4*>(ct)[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // VMEM order of the prologue = the order a step leaves behind (inputs oldest, then the skip values): the wait in
@@ -561,7 +527,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
         A = fresh;
         if (dodd) stencil(1, B, C, A);         // odd plane 2i + 1: completes logit 2i
         emit(2 * i, B, dodd && de);
-        const f32x2v t = A;  // (A, B, C) <- logits (2i+1, 2i+2, 2i+3)
+        const f32x2 t = A;  // (A, B, C) <- logits (2i+1, 2i+2, 2i+3)
         A = C;
         B = t;
         C = fresh;
@@ -573,7 +539,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
 // ---------------------------------------------------------------------------------------------
 // fp32 storage, SPLIT OPERANDS (round 4): the fp32 kernel's data flow with the transposed convolution on
 // v_mfma_f32_16x16x32_bf16 in the tap scheme of the 16-bit kernel.  Every fp32 input value is written, on its way into
-// the wave's private LDS window, as the sum of three bf16 numbers (split_ops.h), the folded weights likewise on the
+// the wave's private LDS window, as the sum of three bf16 numbers (mfma16_ops.h), the folded weights likewise on the
 // host (pack_split_panels(9): three panels in the bf16 layout), and a product is the six leading cross terms, small
 // ones first, accumulated in fp32 -- fp32-equivalent (dropped terms <= 2^-26 of a product; csrc/conv0_split.hip), the
 // bounds of the fp32 kernel hold unchanged.  60 bf16 MFMAs (960 cycles of a pipe that leaves half its issue slots to
@@ -599,11 +565,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
     __shared__ __attribute__((aligned(16))) unsigned short bpan[3 * PAN];          // [piece][chunk][k-step][lane][8]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int b;   // XCD k works through the k-th eighth of the (z chunk, row, column) sequence (conv11_prob_priv_kernel)
-    {
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
+    int b = xcd_block();   // XCD-aware order of the (z chunk, row, column) sequence (conv11_prob_priv_kernel)
     const int bx = b % nbx; b /= nbx;
     const int by = b % nby;
     const int bz = b / nby;
@@ -635,11 +597,11 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
     auto store_a = [&]() {
         const bool ok = pin && (pre_z1 || phz == 0);
         const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-        g_u32x4 p1, p2, p3;
+        u32x4 p1, p2, p3;
         gs_split8(ok ? pre[0] : z4, ok ? pre[1] : z4, p1, p2, p3);
-        *reinterpret_cast<g_u32x4*>(my + ploff) = p1;             // lanes >= NPC rewrite the last voxel with its own value
-        *reinterpret_cast<g_u32x4*>(my + WIN + ploff) = p2;
-        *reinterpret_cast<g_u32x4*>(my + 2 * WIN + ploff) = p3;
+        *reinterpret_cast<u32x4*>(my + ploff) = p1;             // lanes >= NPC rewrite the last voxel with its own value
+        *reinterpret_cast<u32x4*>(my + WIN + ploff) = p2;
+        *reinterpret_cast<u32x4*>(my + 2 * WIN + ploff) = p3;
     };
     // MFMA lane roles (conv11_prob16_kernel): row r -> input voxel (r >> 3, r & 7) of the M-tile; g: dx = g & 1,
     // (z, y)-tap combo g >> 1; a lane's A fragment = the 8 channels of one voxel; column n = r -> (px, co)
@@ -678,7 +640,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
                 sk[c][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srs, (int)(sbase + 64 * e), (int)so, 0));
         }
     };
-    const g_u32x4* bsrc = reinterpret_cast<const g_u32x4*>(bpan) + lane;
+    const u32x4* bsrc = reinterpret_cast<const u32x4*>(bpan) + lane;
     f32x4 acc[4];
     auto mfma_chunk = [&](int c) {
 #pragma unroll
@@ -686,18 +648,18 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
             const int cls = deconv16_tap(ks, 0).cls;
             const int kq = koff[ks];
             const int bq = c * 5 + ks;
-            const g_u32x4 a1 = *reinterpret_cast<const g_u32x4*>(my + kq);
-            const g_u32x4 a2 = *reinterpret_cast<const g_u32x4*>(my + WIN + kq);
-            const g_u32x4 a3 = *reinterpret_cast<const g_u32x4*>(my + 2 * WIN + kq);
-            const g_u32x4 b1 = bsrc[(0 * 10 + bq) * 64];
-            const g_u32x4 b2 = bsrc[(1 * 10 + bq) * 64];
-            const g_u32x4 b3 = bsrc[(2 * 10 + bq) * 64];
-            acc[cls] = gs_mfma(a3, b1, acc[cls]);   // the small terms first
-            acc[cls] = gs_mfma(a1, b3, acc[cls]);
-            acc[cls] = gs_mfma(a2, b2, acc[cls]);
-            acc[cls] = gs_mfma(a2, b1, acc[cls]);
-            acc[cls] = gs_mfma(a1, b2, acc[cls]);
-            acc[cls] = gs_mfma(a1, b1, acc[cls]);
+            const u32x4 a1 = *reinterpret_cast<const u32x4*>(my + kq);
+            const u32x4 a2 = *reinterpret_cast<const u32x4*>(my + WIN + kq);
+            const u32x4 a3 = *reinterpret_cast<const u32x4*>(my + 2 * WIN + kq);
+            const u32x4 b1 = bsrc[(0 * 10 + bq) * 64];
+            const u32x4 b2 = bsrc[(1 * 10 + bq) * 64];
+            const u32x4 b3 = bsrc[(2 * 10 + bq) * 64];
+            acc[cls] = mfma16<MVS_BF16>(a3, b1, acc[cls]);   // the small terms first
+            acc[cls] = mfma16<MVS_BF16>(a1, b3, acc[cls]);
+            acc[cls] = mfma16<MVS_BF16>(a2, b2, acc[cls]);
+            acc[cls] = mfma16<MVS_BF16>(a2, b1, acc[cls]);
+            acc[cls] = mfma16<MVS_BF16>(a1, b2, acc[cls]);
+            acc[cls] = mfma16<MVS_BF16>(a1, b1, acc[cls]);
         }
     };
     // conv11 plane pz of this step -> the tile: ReLU(sum + bias) + skip, zero beyond the volume (the prob layer's padding)
@@ -720,7 +682,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
                         (lx >= 1 || ix0 == 0) && (lx <= OX - 2 || gxo == Wo - 1);
     const size_t pout = (size_t)gyo * Wo + gxo;
     const int cbase = ly * RS + lx * 4;   // LDS row r = tile row r - 1, x index lx = tile column lx - 1
-    auto stencil = [&](f32x2v& k2, f32x2v& k1, f32x2v& k0) {
+    auto stencil = [&](f32x2& k2, f32x2& k1, f32x2& k0) {
         const float* base = ct + cbase;
 #pragma unroll 1
         for (int kx = 0; kx < 3; ++kx) {
@@ -739,27 +701,27 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
 #pragma unroll
                 for (int c2 = 0; c2 < 4; ++c2) {
                     const f32x4 q = v[ky][c2 >> 1];
-                    const f32x2v d = (c2 & 1) ? (f32x2v){q.z, q.w} : (f32x2v){q.x, q.y};
-                    k2 = __builtin_elementwise_fma(d, (f32x2v){w2[2 * c2], w2[2 * c2 + 1]}, k2);
-                    k1 = __builtin_elementwise_fma(d, (f32x2v){w1[2 * c2], w1[2 * c2 + 1]}, k1);
-                    k0 = __builtin_elementwise_fma(d, (f32x2v){w0[2 * c2], w0[2 * c2 + 1]}, k0);
+                    const f32x2 d = (c2 & 1) ? (f32x2){q.z, q.w} : (f32x2){q.x, q.y};
+                    k2 = __builtin_elementwise_fma(d, (f32x2){w2[2 * c2], w2[2 * c2 + 1]}, k2);
+                    k1 = __builtin_elementwise_fma(d, (f32x2){w1[2 * c2], w1[2 * c2 + 1]}, k1);
+                    k0 = __builtin_elementwise_fma(d, (f32x2){w0[2 * c2], w0[2 * c2 + 1]}, k0);
                 }
             }
         }
     };
     // logits leave by raw buffer stores: no branch around a VMEM instruction (conv11_prob16_kernel)
     const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(cost, (short)0, (int)((size_t)Do * HWo * 4), 0x00020000);
-    auto emit = [&](int oz, const f32x2v& sv, bool live) {
+    auto emit = [&](int oz, const f32x2& sv, bool live) {
         const unsigned off = (pvalid && live) ? (unsigned)(((size_t)oz * HWo + pout) * 4) : 0xFFFFFFFCu;
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sv.x + sv.y), crs, (int)off, 0, 0);
     };
 
     const float pb = pbias[0];
-    const f32x2v fresh = {pb, 0.0f};
-    f32x2v A = fresh, B = fresh, C = fresh;
+    const f32x2 fresh = {pb, 0.0f};
+    f32x2 A = fresh, B = fresh, C = fresh;
 
     for (int k = tid; k < PS / 4; k += 512) reinterpret_cast<f32x4*>(ct)[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int k = tid; k < 3 * PAN / 8; k += 512) reinterpret_cast<g_u32x4*>(bpan)[k] = reinterpret_cast<const g_u32x4*>(bp)[k];
+    for (int k = tid; k < 3 * PAN / 8; k += 512) reinterpret_cast<u32x4*>(bpan)[k] = reinterpret_cast<const u32x4*>(bp)[k];
     // VMEM order of the prologue = the order a step leaves behind (input chunk 0 oldest, then the skip values): the
     // waits in front of store_a() are then COUNTED vmcnt on both paths into the loop
     load_a(i_first, 0);
@@ -799,7 +761,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
         __syncthreads();
         if (dodd) stencil(B, C, A);            // odd plane 2i + 1: completes logit 2i
         emit(2 * i, B, dodd && de);
-        const f32x2v t = A;  // (A, B, C) <- logits (2i+1, 2i+2, 2i+3)
+        const f32x2 t = A;  // (A, B, C) <- logits (2i+1, 2i+2, 2i+3)
         A = C;
         B = t;
         C = fresh;

@@ -18,6 +18,7 @@
 
 #include "mvs_internal.h"
 #include "storage.h"
+#include "mfma16_ops.h"
 
 namespace mvs {
 
@@ -644,11 +645,7 @@ __global__ __launch_bounds__(c1z::THREADS) void conv1z_mfma_kernel(
     __shared__ __attribute__((aligned(16))) float strips[8 * STRIP];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int b;
-    {   // XCD k works through the k-th eighth of the (z chunk, row, column) sequence (blockIdx % 8 names the XCD)
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
+    int b = xcd_block();   // XCD-aware order of the (z chunk, row, column) sequence
     const int bx = b % nbx; b /= nbx;
     const int by = b % nby;
     const int bz = b / nby;

@@ -14,27 +14,19 @@
 //   conv0p16  : conv0 in the Toeplitz-pair form (N = 2 x-outputs x 8 channels): the 4 x-taps of a
 //               pair at fixed (kz, ky) are one k-step, 9 per chunk
 //   deconvg16 : conv7/9/11, (z,y) parity classes with the x parity folded into N; 5 k-steps per chunk
+// The two tile kernels, convg16 and deconvg16, also run conv2..conv4 and conv7 / conv9 of fp32 volumes with SPLIT
+// OPERANDS (each fp32 value as the sum of three bf16 numbers on the bf16 MFMA): their operand policy (Op16 / OpSplit)
+// holds what differs.
 #include <cstdlib>
 #include <cstring>
 
 #include "mvs_internal.h"
 #include "storage.h"
-#include "split_ops.h"
+#include "mfma16_ops.h"
 
 namespace mvs {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-    if (DT == MVS_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // ---------------------------------------------------------------------------------------------
 // host: fp32 -> 16-bit (RNE) for the weight panels
@@ -55,7 +47,100 @@ static inline uint16_t to_bits16(float v, int dt) {
 }
 
 // =============================================================================================
-// convg16: conv1..conv6
+// operand policies of the tile kernels (convg16_mfma_kernel, deconvg16_mfma_kernel): what 16-bit storage and fp32
+// storage with split operands do differently.  The tile geometry, block order, k-step scheme, chunk pipeline and
+// epilogue are the kernels' own and the same for both.
+//   Op16<DT> : fp16 / bf16 volumes.  A staged voxel is one 16-byte piece, one panel, one 16-bit MFMA per k-step;
+//              threads past the last halo voxel are masked (loff = -1).
+//   OpSplit  : fp32 volumes (round 4).  Every fp32 operand is written as the sum of three bf16 numbers (a = a1 + a2 + a3,
+//              RNE, exact residuals) and the fp32 product evaluated as the six leading cross products a1 b1 + a1 b2 +
+//              a2 b1 + a2 b2 + a1 b3 + a3 b1 on v_mfma_f32_16x16x32_bf16 with fp32 accumulation: the dropped terms are
+//              <= 2^-26 of the product (csrc/conv0_split.hip has the argument), the per-layer bounds of the fp32-MFMA
+//              kernels hold unchanged, and six bf16 MFMAs cost 6/16 of the fp32 MFMA time they replace.  A staged voxel
+//              (8 channels, two 16-byte loads) is split once, on its way into LDS, into three 16-byte bf16 fragments
+//              (three tiles); the weights are split on the host (three panels in the layout of the 16-bit kernels:
+//              pack_split_panels).  Threads past the last halo voxel shadow it (no branch in the staging code).
+// =============================================================================================
+template <int DT>
+struct Op16 {
+    using T = unsigned short;           // storage element
+    static constexpr int NPC = 1;       // pieces: tiles in LDS, panels of the B operand
+    static constexpr bool CLAMP = false;   // threads past the last halo voxel: masked (false) / shadow it (true)
+    struct Stage {                      // one staged voxel
+        u32x4 v;
+        __device__ __forceinline__ void load(const T* plane, int goff) { v = *reinterpret_cast<const u32x4*>(plane + goff); }
+        __device__ __forceinline__ void stage(unsigned short* tile, int tile_elems, int loff, bool inside) const {
+            if (loff >= 0) *reinterpret_cast<u32x4*>(tile + loff) = inside ? v : (u32x4){0u, 0u, 0u, 0u};
+        }
+    };
+    // k-step ks on the A position ap (b: the panels' fragments in registers, [piece][k-step])
+    template <int N>
+    static __device__ __forceinline__ void mac(f32x4& acc, const unsigned short* ap, int tile_elems, const u32x4 (&b)[N], int ks) {
+        acc = mfma16<DT>(*reinterpret_cast<const u32x4*>(ap), b[ks], acc);
+    }
+    // 8 channels of one voxel at a C8 offset: skip values in, lo / hi (+ skip) out
+    struct Skip { float v[8]; };
+    static __device__ __forceinline__ void load8(const T* p, size_t idx, Skip& s) { load8_16<DT>(p, idx, s.v); }
+    static __device__ __forceinline__ void store8(T* p, size_t idx, f32x4 lo, f32x4 hi) {
+        const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        store8_16<DT>(p, idx, v);
+    }
+    static __device__ __forceinline__ void store8(T* p, size_t idx, f32x4 lo, f32x4 hi, const Skip& s) {
+        const float v[8] = {lo.x + s.v[0], lo.y + s.v[1], lo.z + s.v[2], lo.w + s.v[3],
+                            hi.x + s.v[4], hi.y + s.v[5], hi.z + s.v[6], hi.w + s.v[7]};
+        store8_16<DT>(p, idx, v);
+    }
+};
+
+struct OpSplit {
+    using T = float;
+    static constexpr int NPC = 3;
+    static constexpr bool CLAMP = true;
+    struct Stage {
+        f32x4 lo, hi;
+        __device__ __forceinline__ void load(const T* plane, int goff) {
+            lo = *reinterpret_cast<const f32x4*>(plane + goff);
+            hi = *reinterpret_cast<const f32x4*>(plane + goff + 4);
+        }
+        __device__ __forceinline__ void stage(unsigned short* tile, int tile_elems, int loff, bool inside) const {
+            const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+            u32x4 p1, p2, p3;
+            gs_split8(inside ? lo : z4, inside ? hi : z4, p1, p2, p3);
+            *reinterpret_cast<u32x4*>(tile + loff) = p1;
+            *reinterpret_cast<u32x4*>(tile + tile_elems + loff) = p2;
+            *reinterpret_cast<u32x4*>(tile + 2 * tile_elems + loff) = p3;
+        }
+    };
+    template <int N>
+    static __device__ __forceinline__ void mac(f32x4& acc, const unsigned short* ap, int tile_elems, const u32x4 (&b)[N], int ks) {
+        constexpr int KS = N / NPC;
+        const u32x4 a1 = *reinterpret_cast<const u32x4*>(ap);
+        const u32x4 a2 = *reinterpret_cast<const u32x4*>(ap + tile_elems);
+        const u32x4 a3 = *reinterpret_cast<const u32x4*>(ap + 2 * tile_elems);
+        acc = mfma16<MVS_BF16>(a3, b[ks], acc);   // the small terms first
+        acc = mfma16<MVS_BF16>(a1, b[2 * KS + ks], acc);
+        acc = mfma16<MVS_BF16>(a2, b[KS + ks], acc);
+        acc = mfma16<MVS_BF16>(a2, b[ks], acc);
+        acc = mfma16<MVS_BF16>(a1, b[KS + ks], acc);
+        acc = mfma16<MVS_BF16>(a1, b[ks], acc);
+    }
+    struct Skip { f32x4 lo, hi; };
+    static __device__ __forceinline__ void load8(const T* p, size_t idx, Skip& s) {
+        s.lo = *reinterpret_cast<const f32x4*>(p + idx);
+        s.hi = *reinterpret_cast<const f32x4*>(p + idx + 4);
+    }
+    static __device__ __forceinline__ void store8(T* p, size_t idx, f32x4 lo, f32x4 hi) {
+        *reinterpret_cast<f32x4*>(p + idx) = lo;
+        *reinterpret_cast<f32x4*>(p + idx + 4) = hi;
+    }
+    static __device__ __forceinline__ void store8(T* p, size_t idx, f32x4 lo, f32x4 hi, const Skip& s) {
+        *reinterpret_cast<f32x4*>(p + idx) = lo + s.lo;
+        *reinterpret_cast<f32x4*>(p + idx + 4) = hi + s.hi;
+    }
+};
+
+// =============================================================================================
+// convg16: conv1..conv6 (16-bit storage), conv2..conv4 (fp32 storage, split operands)
 // =============================================================================================
 template <int CIN, int COUT, int S, int BZ, int BY, int BX>
 struct ConvG16 {
@@ -80,12 +165,12 @@ struct ConvG16 {
     }
 };
 
-template <int DT, int CIN, int COUT, int S, int BZ, int BY, int BX>
+template <class Op, int CIN, int COUT, int S, int BZ, int BY, int BX>
 __global__ __launch_bounds__(256) void convg16_mfma_kernel(
-    const void* __restrict__ x,               // [CIN/8][Di][Hi][Wi][8] 16-bit
-    const unsigned short* __restrict__ bp,    // [NCH][NT][7][64][8] 16-bit
+    const typename Op::T* __restrict__ x,     // [CIN/8][Di][Hi][Wi][8]
+    const unsigned short* __restrict__ bp,    // [Op::NPC pieces][NCH][NT][7][64][8] 16-bit
     const float* __restrict__ bias,           // [COUT]
-    void* __restrict__ y,                     // [COUT/8][Do][Ho][Wo][8] 16-bit
+    typename Op::T* __restrict__ y,           // [COUT/8][Do][Ho][Wo][8]
     int Di, int Hi, int Wi, int Do, int Ho, int Wo) {
     using G = ConvG16<CIN, COUT, S, BZ, BY, BX>;
     // epilogue staging tile (fp32): the block's BZ x 2BY x 8BX output voxels x COUT channels, rows padded (16 floats per 8
@@ -93,39 +178,38 @@ __global__ __launch_bounds__(256) void convg16_mfma_kernel(
     constexpr int OY = 2 * BY, OX = 8 * BX;
     constexpr int RP0 = OX * COUT + 16 * (OX / 8), RP = (RP0 % 32 == 16) ? RP0 : RP0 + 16;
     constexpr int OUT_FLOATS = BZ * OY * RP, NUNIT = BZ * OY * OX * (COUT / 8), UPT = (NUNIT + 255) / 256;
-    constexpr int LDS_BYTES = G::TILE_ELEMS * 2 > OUT_FLOATS * 4 ? G::TILE_ELEMS * 2 : OUT_FLOATS * 4;
+    constexpr int TILE_BYTES = Op::NPC * G::TILE_ELEMS * 2;
+    constexpr int LDS_BYTES = TILE_BYTES > OUT_FLOATS * 4 ? TILE_BYTES : OUT_FLOATS * 4;
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
     unsigned short* tile = reinterpret_cast<unsigned short*>(lds_raw);
     float* otile = reinterpret_cast<float*>(lds_raw);
-    const unsigned short* xs = static_cast<const unsigned short*>(x);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nt = wave % G::NT, mg = wave / G::NT;
     const int nbx = (Wo + 8 * BX - 1) / (8 * BX), nby = (Ho + 2 * BY - 1) / (2 * BY);
-    int b;   // XCD-aware tile order (see convgs_mfma_kernel)
-    {
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
+    int b = xcd_block();   // XCD-aware order of the (z, row, column) tile sequence: tiles sharing halo planes / rows meet in one L2
     const int bx = b % nbx; b /= nbx;
     const int by = b % nby;
     const int bz = b / nby;
     const int ox0 = bx * 8 * BX, oy0 = by * 2 * BY, oz0 = bz * BZ;
     const int ix0 = ox0 * S - 1, iy0 = oy0 * S - 1, iz0 = oz0 * S - 1;
     const size_t Vin = (size_t)Di * Hi * Wi, Vout = (size_t)Do * Ho * Wo;
+    constexpr size_t PANEL = (size_t)G::NCH * G::NT * G::KS * 64;   // u32x4 fragments per piece
 
+    // staging: piece p = tid + i * 256 = one voxel (8 channels) of the halo tile
     int goff[G::PPT], loff[G::PPT];
     unsigned inside = 0;
 #pragma unroll
     for (int i = 0; i < G::PPT; ++i) {
-        const int v = tid + i * 256;
+        const int v = Op::CLAMP ? min(tid + i * 256, G::NPIECE - 1) : tid + i * 256;
         const int hx = v % G::HX, t = v / G::HX;
         const int hy = t % G::HY, hz = t / G::HY;
         const int gz = iz0 + hz, gy = iy0 + hy, gx = ix0 + hx;
-        const bool ok = v < G::NPIECE && gz >= 0 && gz < Di && gy >= 0 && gy < Hi && gx >= 0 && gx < Wi;
+        const bool live = Op::CLAMP || v < G::NPIECE;   // else: a thread past the last halo voxel (masked)
+        const bool ok = live && gz >= 0 && gz < Di && gy >= 0 && gy < Hi && gx >= 0 && gx < Wi;
         goff[i] = ok ? (int)((((size_t)gz * Hi + gy) * Wi + gx) * 8) : 0;
         inside |= ok ? (1u << i) : 0u;
-        loff[i] = (v < G::NPIECE) ? ((hz * G::HY + hy) * G::HXP + hx) * G::VS : -1;
+        loff[i] = live ? ((hz * G::HY + hy) * G::HXP + hx) * G::VS : -1;
     }
 
     // A fragment: lane (r = lane&15 -> voxel (ry, rx) of the M-tile, g = lane>>4 -> tap 4ks+g)
@@ -147,55 +231,46 @@ __global__ __launch_bounds__(256) void convg16_mfma_kernel(
     f32x4 acc[G::MPW];
 #pragma unroll
     for (int i = 0; i < G::MPW; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    u32x4 breg[G::KS];
-    u32x4 stg[G::PPT];
+    u32x4 breg[Op::NPC * G::KS];   // [piece][k-step]
+    typename Op::Stage stg[G::PPT];
 
-#define MVS_LOAD_B(C)                                                                               \
-    {                                                                                               \
-        const u32x4* bsrc =                                                                         \
-            reinterpret_cast<const u32x4*>(bp) + ((size_t)((C) * G::NT + nt) * G::KS) * 64 + lane;  \
-        _Pragma("unroll") for (int ks = 0; ks < G::KS; ++ks) breg[ks] = bsrc[ks * 64];              \
-    }
-#define MVS_LOAD_A(C)                                                                               \
-    {                                                                                               \
-        const unsigned short* plane = xs + (size_t)(C) * Vin * 8;                                   \
-        _Pragma("unroll") for (int i = 0; i < G::PPT; ++i)                                          \
-            stg[i] = *reinterpret_cast<const u32x4*>(plane + goff[i]);                              \
-    }
-#define MVS_STORE_A()                                                                               \
-    {                                                                                               \
-        _Pragma("unroll") for (int i = 0; i < G::PPT; ++i)                                          \
-            if (loff[i] >= 0)                                                                       \
-                *reinterpret_cast<u32x4*>(tile + loff[i]) =                                         \
-                    ((inside >> i) & 1u) ? stg[i] : (u32x4){0u, 0u, 0u, 0u};                        \
-    }
+    auto load_b = [&](int c) {
+        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NT + nt) * G::KS) * 64 + lane;
+#pragma unroll
+        for (int q = 0; q < Op::NPC; ++q)
+#pragma unroll
+            for (int ks = 0; ks < G::KS; ++ks) breg[q * G::KS + ks] = bsrc[q * PANEL + ks * 64];
+    };
+    auto load_a = [&](int c) {
+        const typename Op::T* plane = x + (size_t)c * Vin * 8;
+#pragma unroll
+        for (int i = 0; i < G::PPT; ++i) stg[i].load(plane, goff[i]);
+    };
+    auto store_a = [&]() {
+#pragma unroll
+        for (int i = 0; i < G::PPT; ++i) stg[i].stage(tile, G::TILE_ELEMS, loff[i], (inside >> i) & 1u);
+    };
 
-    MVS_LOAD_B(0)
-    MVS_LOAD_A(0)
-    MVS_STORE_A()
+    load_b(0);
+    load_a(0);
+    store_a();
     __syncthreads();
 
 #pragma unroll 1
     for (int c = 0; c < G::NCH; ++c) {
-        if (c + 1 < G::NCH) MVS_LOAD_A(c + 1)
+        if (c + 1 < G::NCH) load_a(c + 1);
 #pragma unroll
         for (int ks = 0; ks < G::KS; ++ks) {
 #pragma unroll
-            for (int i = 0; i < G::MPW; ++i) {
-                const u32x4 a = *reinterpret_cast<const u32x4*>(tile + abase[i] + koff[ks]);
-                acc[i] = mfma16<DT>(a, breg[ks], acc[i]);
-            }
+            for (int i = 0; i < G::MPW; ++i) Op::mac(acc[i], tile + abase[i] + koff[ks], G::TILE_ELEMS, breg, ks);
         }
         if (c + 1 < G::NCH) {
-            MVS_LOAD_B(c + 1)
+            load_b(c + 1);
             __syncthreads();
-            MVS_STORE_A()
+            store_a();
             __syncthreads();
         }
     }
-#undef MVS_LOAD_B
-#undef MVS_LOAD_A
-#undef MVS_STORE_A
 
     // epilogue: ReLU(acc + bias) scattered into the LDS tile [oz][oy][ox][co], then every thread owns whole voxels of one C8
     // plane (8 channels) and stores them 16 bytes at a time, contiguous across the wave (the scalar form stored single
@@ -226,22 +301,21 @@ __global__ __launch_bounds__(256) void convg16_mfma_kernel(
         if (u < NUNIT && gz < Do && gy < Ho && gx < Wo) {
             const float* src = otile + (ozl * OY + oy) * RP + ox * COUT + (ox >> 3) * 16 + pl * 8;
             const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
-            const size_t uo = ((size_t)pl * Vout + ((size_t)gz * Ho + gy) * Wo + gx) * 8;
-            const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            store8_16<DT>(y, uo, v);
+            Op::store8(y, ((size_t)pl * Vout + ((size_t)gz * Ho + gy) * Wo + gx) * 8, lo, hi);
         }
     }
 }
 
-template <int DT, int CIN, int COUT, int S, int BZ, int BY, int BX>
+template <class Op, int CIN, int COUT, int S, int BZ, int BY, int BX>
 static int run_convg16(const void* x, void* y, const unsigned short* bp, const float* bias, int Di, int Hi,
                        int Wi, hipStream_t s) {
+    using T = typename Op::T;
     const int Do = (Di - 1) / S + 1, Ho = (Hi - 1) / S + 1, Wo = (Wi - 1) / S + 1;
     if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
         return fail(MVS_ERR_BAD_SHAPE, "convg16_mfma: plane exceeds 31-bit offsets");
     const int nb = ((Wo + 8 * BX - 1) / (8 * BX)) * ((Ho + 2 * BY - 1) / (2 * BY)) * ((Do + BZ - 1) / BZ);
-    convg16_mfma_kernel<DT, CIN, COUT, S, BZ, BY, BX><<<nb, 256, 0, s>>>(x, bp, bias, y, Di, Hi, Wi, Do,
-                                                                         Ho, Wo);
+    convg16_mfma_kernel<Op, CIN, COUT, S, BZ, BY, BX><<<nb, 256, 0, s>>>(static_cast<const T*>(x), bp, bias,
+                                                                         static_cast<T*>(y), Di, Hi, Wi, Do, Ho, Wo);
     return check_hip(hipGetLastError(), "convg16_mfma launch");
 }
 
@@ -260,22 +334,22 @@ template <int DT>
 static int launch_convg16_dt(int layer, const void* x, void* y, const unsigned short* bp, const float* bias,
                              int Di, int Hi, int Wi, hipStream_t s) {
     switch (layer) {
-        case 1: return run_convg16<DT, 8, 16, 2, 2, 2, 2>(x, y, bp, bias, Di, Hi, Wi, s);
-        case 2: return run_convg16<DT, 16, 16, 1, 2, 4, 2>(x, y, bp, bias, Di, Hi, Wi, s);
-        case 3: return run_convg16<DT, 16, 32, 2, 4, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);   // cfg5 sweep: 1x2x2 0.0115, 4x1x1 0.0107 ms
+        case 1: return run_convg16<Op16<DT>, 8, 16, 2, 2, 2, 2>(x, y, bp, bias, Di, Hi, Wi, s);
+        case 2: return run_convg16<Op16<DT>, 16, 16, 1, 2, 4, 2>(x, y, bp, bias, Di, Hi, Wi, s);
+        case 3: return run_convg16<Op16<DT>, 16, 32, 2, 4, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);   // cfg5 sweep: 1x2x2 0.0115, 4x1x1 0.0107 ms
         // conv4 .. conv6: z-deep block tiles (halo planes re-used) wherever they still give every CU a block and a half --
         // round-4 sweep, cfg3 bf16 (1600x1184x256): conv4 1x2x2 -> 4x2x1 0.0574 -> 0.0456 ms, conv5 1x1x1 -> 2x1x1 0.0296 -> 0.0236,
         // conv6 1x1x1 -> 4x1x1 0.0479 -> 0.0243; cfg5 fp16 (640x512x192): conv4 0.0133 -> 0.0118, conv5 / conv6 keep 1x1x1
         // (2x1x1 / 4x1x1 would leave 240 / 120 blocks for 256 CUs: 0.0104 / 0.0145 against 0.0106 / 0.0134)
         case 4:
-            if (tile_fills_chip(Di, Hi, Wi, 1, 4, 2, 1)) return run_convg16<DT, 32, 32, 1, 4, 2, 1>(x, y, bp, bias, Di, Hi, Wi, s);
-            return run_convg16<DT, 32, 32, 1, 1, 2, 2>(x, y, bp, bias, Di, Hi, Wi, s);
+            if (tile_fills_chip(Di, Hi, Wi, 1, 4, 2, 1)) return run_convg16<Op16<DT>, 32, 32, 1, 4, 2, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+            return run_convg16<Op16<DT>, 32, 32, 1, 1, 2, 2>(x, y, bp, bias, Di, Hi, Wi, s);
         case 5:
-            if (tile_fills_chip(Di, Hi, Wi, 2, 2, 1, 1)) return run_convg16<DT, 32, 64, 2, 2, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
-            return run_convg16<DT, 32, 64, 2, 1, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+            if (tile_fills_chip(Di, Hi, Wi, 2, 2, 1, 1)) return run_convg16<Op16<DT>, 32, 64, 2, 2, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+            return run_convg16<Op16<DT>, 32, 64, 2, 1, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
         case 6:
-            if (tile_fills_chip(Di, Hi, Wi, 1, 4, 1, 1)) return run_convg16<DT, 64, 64, 1, 4, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
-            return run_convg16<DT, 64, 64, 1, 1, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+            if (tile_fills_chip(Di, Hi, Wi, 1, 4, 1, 1)) return run_convg16<Op16<DT>, 64, 64, 1, 4, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+            return run_convg16<Op16<DT>, 64, 64, 1, 1, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
         default: return fail(MVS_ERR_BAD_SHAPE, "convg16_mfma: layer %d not covered", layer);
     }
 }
@@ -464,14 +538,9 @@ __global__ __launch_bounds__(c0z::THREADS) void conv0z16_mfma_kernel(
     const unsigned short* xs = static_cast<const unsigned short*>(x);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // Blocks are dealt round-robin over the 8 XCDs (blockIdx.x % 8 names the XCD: speed only, never correctness)
-    // and every XCD has its own L2: XCD k works through the k-th eighth of the (z chunk, row, column) sequence, so
-    // that columns sharing a y / x halo run on the same L2 at about the same time
-    int b;
-    {
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;   // XCD k runs q (+1 if k < rem) blocks
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
+    // XCD-aware order of the (z chunk, row, column) sequence: columns sharing a y / x halo run on the same L2 at about
+    // the same time
+    int b = xcd_block();
     const int bx = b % nbx; b /= nbx;
     const int by = b % nby;
     const int bz = b / nby;
@@ -648,11 +717,7 @@ __global__ __launch_bounds__(512) void convz16_mfma_kernel(
     const unsigned short* xs = static_cast<const unsigned short*>(x);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int b;
-    {   // XCD k works through the k-th eighth of the (z chunk, row, column) sequence
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
+    int b = xcd_block();   // XCD-aware order of the (z chunk, row, column) sequence
     const int bx = b % nbx; b /= nbx;
     const int by = b % nby;
     const int bz = b / nby;
@@ -871,7 +936,7 @@ void pack_conv0p16_weights(const float* wfold, int dt, unsigned short* bp) {
 }
 
 // =============================================================================================
-// deconvg16: conv7 / conv9 / conv11 (+ skip)
+// deconvg16: conv7 / conv9 / conv11 (+ skip) (16-bit storage), conv7 / conv9 (+ skip) (fp32 storage, split operands)
 // =============================================================================================
 // Deconv16Tap / deconv16_tap(ks, q): mvs_internal.h (shared with conv11_prob.hip)
 
@@ -893,48 +958,51 @@ struct DeconvG16 {
     static_assert(MT % MG == 0, "block tile must split evenly over the M-groups");
 };
 
-template <int DT, int CIN, int COUT, int BZ, int BY, int BX>
+template <class Op, int CIN, int COUT, int BZ, int BY, int BX>
 __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
-    const void* __restrict__ x, const unsigned short* __restrict__ bp, const float* __restrict__ bias,
-    const void* __restrict__ skip, void* __restrict__ y, int Di, int Hi, int Wi) {
+    const typename Op::T* __restrict__ x,     // [CIN/8][Di][Hi][Wi][8]
+    const unsigned short* __restrict__ bp,    // [Op::NPC pieces][NCH][NTT][5][64][8] 16-bit
+    const float* __restrict__ bias,           // [COUT]
+    const typename Op::T* __restrict__ skip,  // [COUT/8][2 Di][2 Hi][2 Wi][8]
+    typename Op::T* __restrict__ y, int Di, int Hi, int Wi) {
     using G = DeconvG16<CIN, COUT, BZ, BY, BX>;
-    // epilogue staging tile (fp32; deconvg_mfma's scheme, see deconvgs_mfma_kernel): one z parity of the block's output
+    // epilogue staging tile (deconvg_mfma's scheme): one z parity of the block's 2BZ x 4BY x 16BX output voxels x COUT channels,
+    // rows padded (16 floats per 8 voxels, row pitch = 16 mod 32) so that the accumulator scatter is conflict-free
     constexpr int OY = 4 * BY, OX = 16 * BX;
     constexpr int RP0 = OX * COUT + 16 * (OX / 8), RP = (RP0 % 32 == 16) ? RP0 : RP0 + 16;
     constexpr int OUT_FLOATS = BZ * OY * RP, NUNIT = BZ * OY * OX * (COUT / 8), UPT = (NUNIT + 255) / 256;
-    constexpr int LDS_BYTES = G::TILE_ELEMS * 2 > OUT_FLOATS * 4 ? G::TILE_ELEMS * 2 : OUT_FLOATS * 4;
+    constexpr int TILE_BYTES = Op::NPC * G::TILE_ELEMS * 2;
+    constexpr int LDS_BYTES = TILE_BYTES > OUT_FLOATS * 4 ? TILE_BYTES : OUT_FLOATS * 4;
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
     unsigned short* tile = reinterpret_cast<unsigned short*>(lds_raw);
     float* otile = reinterpret_cast<float*>(lds_raw);
-    const unsigned short* xs = static_cast<const unsigned short*>(x);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nt = wave % G::NTT, mg = wave / G::NTT;
     const int nbx = (Wi + 8 * BX - 1) / (8 * BX), nby = (Hi + 2 * BY - 1) / (2 * BY);
-    int b;   // XCD-aware tile order (see convgs_mfma_kernel)
-    {
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
+    int b = xcd_block();   // XCD-aware order of the (z, row, column) tile sequence: tiles sharing halo planes / rows meet in one L2
     const int bx = b % nbx; b /= nbx;
     const int by = b % nby;
     const int bz = b / nby;
     const int ix0 = bx * 8 * BX, iy0 = by * 2 * BY, iz0 = bz * BZ;
     const int Ho = 2 * Hi, Wo = 2 * Wi;
     const size_t Vin = (size_t)Di * Hi * Wi, Vout = Vin * 8;
+    constexpr size_t PANEL = (size_t)G::NCH * G::NTT * G::KS * 64;   // u32x4 fragments per piece
 
+    // staging: piece p = tid + i * 256 = one voxel (8 channels) of the halo tile
     int goff[G::PPT], loff[G::PPT];
     unsigned inside = 0;
 #pragma unroll
     for (int i = 0; i < G::PPT; ++i) {
-        const int v = tid + i * 256;
+        const int v = Op::CLAMP ? min(tid + i * 256, G::NPIECE - 1) : tid + i * 256;
         const int hx = v % G::HX, t = v / G::HX;
         const int hy = t % G::HY, hz = t / G::HY;
         const int gz = iz0 + hz, gy = iy0 + hy, gx = ix0 + hx;
-        const bool ok = v < G::NPIECE && gz < Di && gy < Hi && gx < Wi;
+        const bool live = Op::CLAMP || v < G::NPIECE;   // else: a thread past the last halo voxel (masked)
+        const bool ok = live && gz < Di && gy < Hi && gx < Wi;
         goff[i] = ok ? (int)((((size_t)gz * Hi + gy) * Wi + gx) * 8) : 0;
         inside |= ok ? (1u << i) : 0u;
-        loff[i] = (v < G::NPIECE) ? ((hz * G::HY + hy) * G::HXP + hx) * G::VS : -1;
+        loff[i] = live ? ((hz * G::HY + hy) * G::HXP + hx) * G::VS : -1;
     }
 
     const int r = lane & 15, g = lane >> 4;
@@ -958,62 +1026,54 @@ __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
     for (int c = 0; c < 4; ++c)
 #pragma unroll
         for (int i = 0; i < G::MPW; ++i) acc[c][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    u32x4 breg[G::KS];
-    u32x4 stg[G::PPT];
+    u32x4 breg[Op::NPC * G::KS];   // [piece][k-step]
+    typename Op::Stage stg[G::PPT];
 
-#define MVS_LOAD_B(C)                                                                               \
-    {                                                                                               \
-        const u32x4* bsrc =                                                                         \
-            reinterpret_cast<const u32x4*>(bp) + ((size_t)((C) * G::NTT + nt) * G::KS) * 64 + lane; \
-        _Pragma("unroll") for (int ks = 0; ks < G::KS; ++ks) breg[ks] = bsrc[ks * 64];              \
-    }
-#define MVS_LOAD_A(C)                                                                               \
-    {                                                                                               \
-        const unsigned short* plane = xs + (size_t)(C) * Vin * 8;                                   \
-        _Pragma("unroll") for (int i = 0; i < G::PPT; ++i)                                          \
-            stg[i] = *reinterpret_cast<const u32x4*>(plane + goff[i]);                              \
-    }
-#define MVS_STORE_A()                                                                               \
-    {                                                                                               \
-        _Pragma("unroll") for (int i = 0; i < G::PPT; ++i)                                          \
-            if (loff[i] >= 0)                                                                       \
-                *reinterpret_cast<u32x4*>(tile + loff[i]) =                                         \
-                    ((inside >> i) & 1u) ? stg[i] : (u32x4){0u, 0u, 0u, 0u};                        \
-    }
+    auto load_b = [&](int c) {
+        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NTT + nt) * G::KS) * 64 + lane;
+#pragma unroll
+        for (int q = 0; q < Op::NPC; ++q)
+#pragma unroll
+            for (int ks = 0; ks < G::KS; ++ks) breg[q * G::KS + ks] = bsrc[q * PANEL + ks * 64];
+    };
+    auto load_a = [&](int c) {
+        const typename Op::T* plane = x + (size_t)c * Vin * 8;
+#pragma unroll
+        for (int i = 0; i < G::PPT; ++i) stg[i].load(plane, goff[i]);
+    };
+    auto store_a = [&]() {
+#pragma unroll
+        for (int i = 0; i < G::PPT; ++i) stg[i].stage(tile, G::TILE_ELEMS, loff[i], (inside >> i) & 1u);
+    };
 
-    MVS_LOAD_B(0)
-    MVS_LOAD_A(0)
-    MVS_STORE_A()
+    load_b(0);
+    load_a(0);
+    store_a();
     __syncthreads();
 
 #pragma unroll 1
     for (int c = 0; c < G::NCH; ++c) {
-        if (c + 1 < G::NCH) MVS_LOAD_A(c + 1)
+        if (c + 1 < G::NCH) load_a(c + 1);
 #pragma unroll
         for (int ks = 0; ks < G::KS; ++ks) {
-            constexpr int dummy = 0;
-            (void)dummy;
             const int cls = deconv16_tap(ks, 0).cls;
 #pragma unroll
-            for (int i = 0; i < G::MPW; ++i) {
-                const u32x4 a = *reinterpret_cast<const u32x4*>(tile + abase[i] + koff[ks]);
-                acc[cls][i] = mfma16<DT>(a, breg[ks], acc[cls][i]);
-            }
+            for (int i = 0; i < G::MPW; ++i)
+                Op::mac(acc[cls][i], tile + abase[i] + koff[ks], G::TILE_ELEMS, breg, ks);
         }
         if (c + 1 < G::NCH) {
-            MVS_LOAD_B(c + 1)
+            load_b(c + 1);
             __syncthreads();
-            MVS_STORE_A()
+            store_a();
             __syncthreads();
         }
     }
-#undef MVS_LOAD_B
-#undef MVS_LOAD_A
-#undef MVS_STORE_A
 
-    // epilogue: ReLU(acc + bias) scattered into the LDS tile [oz][oy][ox][co] (fp32), then every thread owns whole voxels of one
-    // C8 plane (8 channels = 16 B of 16-bit storage): skip add with 16-byte loads / stores contiguous across the wave (the
-    // scalar form stored 2-byte elements).  Two passes, one per output z parity; a pass requests its skip values first.
+    // epilogue: col n -> (px, co); row m -> input voxel of the tile; class -> (pz, py).  ReLU(acc + bias) is scattered into the
+    // LDS tile [oz][oy][ox][co] (fp32); then every thread owns whole voxels of one C8 plane (8 channels) and does the skip add
+    // with 16-byte loads / stores that are contiguous across the wave (the scalar forms stored single elements, 2- or 4-byte
+    // pieces, and exposed one skip load per element).  Two passes, one per output z parity; the skip values of a pass are
+    // requested before its scatter.
     const int Do = 2 * Di;
     const int nn = 16 * nt + (lane & 15);
     const int px = nn / COUT, co = nn % COUT;
@@ -1022,7 +1082,7 @@ __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
     for (int pz = 0; pz < 2; ++pz) {
         size_t uo[UPT];
         int usrc[UPT];
-        float sk16[UPT][8];
+        typename Op::Skip sk[UPT];
 #pragma unroll
         for (int j = 0; j < UPT; ++j) {
             const int u = tid + j * 256;
@@ -1034,9 +1094,9 @@ __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
             const bool ok = u < NUNIT && gz < Do && gy < Ho && gx < Wo;
             usrc[j] = ok ? (ozl * OY + oy) * RP + ox * COUT + (ox >> 3) * 16 + pl * 8 : -1;
             uo[j] = ok ? ((size_t)pl * Vout + ((size_t)gz * Ho + gy) * Wo + gx) * 8 : 0;
-            load8_16<DT>(skip, uo[j], sk16[j]);
+            Op::load8(skip, uo[j], sk[j]);
         }
-        __syncthreads();  // input tile (pass 0) / previous pass's staging tile fully consumed
+        __syncthreads();  // input tiles (pass 0) / previous pass's staging tile fully consumed
 #pragma unroll
         for (int i = 0; i < G::MPW; ++i) {
             const int t = mg * G::MPW + i;
@@ -1058,20 +1118,21 @@ __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
             if (usrc[j] < 0) continue;
             const float* src = otile + usrc[j];
             const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
-            const float v[8] = {lo.x + sk16[j][0], lo.y + sk16[j][1], lo.z + sk16[j][2], lo.w + sk16[j][3],
-                                hi.x + sk16[j][4], hi.y + sk16[j][5], hi.z + sk16[j][6], hi.w + sk16[j][7]};
-            store8_16<DT>(y, uo[j], v);
+            Op::store8(y, uo[j], lo, hi, sk[j]);
         }
     }
 }
 
-template <int DT, int CIN, int COUT, int BZ, int BY, int BX>
+template <class Op, int CIN, int COUT, int BZ, int BY, int BX>
 static int run_deconvg16(const void* x, const void* skip, void* y, const unsigned short* bp,
                          const float* bias, int Di, int Hi, int Wi, hipStream_t s) {
+    using T = typename Op::T;
     if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
         return fail(MVS_ERR_BAD_SHAPE, "deconvg16_mfma: plane exceeds 31-bit offsets");
     const int nb = ((Wi + 8 * BX - 1) / (8 * BX)) * ((Hi + 2 * BY - 1) / (2 * BY)) * ((Di + BZ - 1) / BZ);
-    deconvg16_mfma_kernel<DT, CIN, COUT, BZ, BY, BX><<<nb, 256, 0, s>>>(x, bp, bias, skip, y, Di, Hi, Wi);
+    deconvg16_mfma_kernel<Op, CIN, COUT, BZ, BY, BX><<<nb, 256, 0, s>>>(static_cast<const T*>(x), bp, bias,
+                                                                        static_cast<const T*>(skip),
+                                                                        static_cast<T*>(y), Di, Hi, Wi);
     return check_hip(hipGetLastError(), "deconvg16_mfma launch");
 }
 
@@ -1142,12 +1203,12 @@ static int launch_layer16_dt(int layer, const void* x, const void* skip, void* y
         // the same for the transposed layers (tiles over the INPUT grid): cfg3 conv7 1x1x1 -> 2x1x1 0.0486 -> 0.0389, conv9 1x4x1
         // -> 4x2x1 0.1059 -> 0.1026; cfg5 conv9 0.0171 -> 0.0164, conv7 stays (2x1x1: 240 blocks)
         case 7:
-            if (tile_fills_chip(Di, Hi, Wi, 1, 2, 1, 1)) return run_deconvg16<DT, 64, 32, 2, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
-            return run_deconvg16<DT, 64, 32, 1, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+            if (tile_fills_chip(Di, Hi, Wi, 1, 2, 1, 1)) return run_deconvg16<Op16<DT>, 64, 32, 2, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+            return run_deconvg16<Op16<DT>, 64, 32, 1, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
         case 8:
-            if (tile_fills_chip(Di, Hi, Wi, 1, 4, 2, 1)) return run_deconvg16<DT, 32, 16, 4, 2, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
-            return run_deconvg16<DT, 32, 16, 1, 4, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
-        case 9: return run_deconvg16<DT, 16, 8, 1, 4, 2>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+            if (tile_fills_chip(Di, Hi, Wi, 1, 4, 2, 1)) return run_deconvg16<Op16<DT>, 32, 16, 4, 2, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+            return run_deconvg16<Op16<DT>, 32, 16, 1, 4, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+        case 9: return run_deconvg16<Op16<DT>, 16, 8, 1, 4, 2>(x, skip, y, bp, bias, Di, Hi, Wi, s);
         default: return fail(MVS_ERR_BAD_SHAPE, "mfma16: layer %d not covered", layer);
     }
 }
@@ -1161,405 +1222,8 @@ int launch_layer_mfma16(int layer, const void* x, const void* skip, void* y, con
 }
 
 // =============================================================================================
-// SPLIT-OPERAND kernels for fp32 volumes (round 4): the tile kernels above with every fp32 operand written as the sum
-// of three bf16 numbers (a = a1 + a2 + a3, RNE, exact residuals) and the fp32 product evaluated as the six leading
-// cross products a1 b1 + a1 b2 + a2 b1 + a2 b2 + a1 b3 + a3 b1 on v_mfma_f32_16x16x32_bf16 with fp32 accumulation: the
-// dropped terms are <= 2^-26 of the product (csrc/conv0_split.hip has the argument), the per-layer bounds of the
-// fp32-MFMA kernels hold unchanged, and six bf16 MFMAs cost 6/16 of the fp32 MFMA time they replace.  Inputs and
-// outputs are the fp32 C8-planar volumes; a staged voxel (8 channels, two 16-byte loads) is split once, on its way
-// into LDS, into three 16-byte bf16 fragments (three tiles); the weights are split on the host (three panels in the
-// layout of the 16-bit kernels: pack_split_panels).
-//   convgs   : conv2 .. conv4 (the tile scheme of convg16)
+// dispatch for the fp32 layers on the tile kernels with split operands (OpSplit)
 // =============================================================================================
-template <int CIN, int COUT, int S, int BZ, int BY, int BX>
-__global__ __launch_bounds__(256) void convgs_mfma_kernel(
-    const float* __restrict__ x,              // [CIN/8][Di][Hi][Wi][8] fp32
-    const unsigned short* __restrict__ bp,    // [3 pieces][NCH][NT][7][64][8] bf16
-    const float* __restrict__ bias,           // [COUT]
-    float* __restrict__ y,                    // [COUT/8][Do][Ho][Wo][8] fp32
-    int Di, int Hi, int Wi, int Do, int Ho, int Wo) {
-    using G = ConvG16<CIN, COUT, S, BZ, BY, BX>;
-    // epilogue staging tile (fp32): the block's BZ x 2BY x 8BX output voxels x COUT channels, rows padded (16 floats per 8
-    // voxels, row pitch = 16 mod 32 floats) so that the accumulator scatter is conflict-free
-    constexpr int OY = 2 * BY, OX = 8 * BX;
-    constexpr int RP0 = OX * COUT + 16 * (OX / 8), RP = (RP0 % 32 == 16) ? RP0 : RP0 + 16;
-    constexpr int OUT_FLOATS = BZ * OY * RP, NUNIT = BZ * OY * OX * (COUT / 8), UPT = (NUNIT + 255) / 256;
-    constexpr int LDS_BYTES = 3 * G::TILE_ELEMS * 2 > OUT_FLOATS * 4 ? 3 * G::TILE_ELEMS * 2 : OUT_FLOATS * 4;
-    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
-    unsigned short* tile = reinterpret_cast<unsigned short*>(lds_raw);
-    float* otile = reinterpret_cast<float*>(lds_raw);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nt = wave % G::NT, mg = wave / G::NT;
-    const int nbx = (Wo + 8 * BX - 1) / (8 * BX), nby = (Ho + 2 * BY - 1) / (2 * BY);
-    // blocks are dealt round-robin over the 8 XCDs (blockIdx.x % 8 names the XCD: speed only, never correctness): XCD k works
-    // through the k-th eighth of the (z, row, column) tile sequence, so that tiles sharing halo planes / rows meet in one L2
-    int b;
-    {
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
-    const int bx = b % nbx; b /= nbx;
-    const int by = b % nby;
-    const int bz = b / nby;
-    const int ox0 = bx * 8 * BX, oy0 = by * 2 * BY, oz0 = bz * BZ;
-    const int ix0 = ox0 * S - 1, iy0 = oy0 * S - 1, iz0 = oz0 * S - 1;
-    const size_t Vin = (size_t)Di * Hi * Wi, Vout = (size_t)Do * Ho * Wo;
-    constexpr size_t PANEL = (size_t)G::NCH * G::NT * G::KS * 64;   // u32x4 fragments per piece
-
-    // staging: piece p = tid + i * 256 = one voxel (8 channels) of the halo tile; threads beyond the tile shadow its
-    // last voxel (no branch in the staging code)
-    int goff[G::PPT], loff[G::PPT];
-    unsigned inside = 0;
-#pragma unroll
-    for (int i = 0; i < G::PPT; ++i) {
-        const int v = min(tid + i * 256, G::NPIECE - 1);
-        const int hx = v % G::HX, t = v / G::HX;
-        const int hy = t % G::HY, hz = t / G::HY;
-        const int gz = iz0 + hz, gy = iy0 + hy, gx = ix0 + hx;
-        const bool ok = gz >= 0 && gz < Di && gy >= 0 && gy < Hi && gx >= 0 && gx < Wi;
-        goff[i] = ok ? (int)((((size_t)gz * Hi + gy) * Wi + gx) * 8) : 0;
-        inside |= ok ? (1u << i) : 0u;
-        loff[i] = ((hz * G::HY + hy) * G::HXP + hx) * G::VS;
-    }
-
-    // A fragment: lane (r = lane&15 -> voxel (ry, rx) of the M-tile, g = lane>>4 -> tap 4ks+g)
-    const int r = lane & 15, g = lane >> 4;
-    const int ry = r >> 3, rx = r & 7;
-    int abase[G::MPW];
-#pragma unroll
-    for (int i = 0; i < G::MPW; ++i) {
-        const int t = mg * G::MPW + i;
-        const int tx = t % BX, ty = (t / BX) % BY, tz = t / (BX * BY);
-        abase[i] = (((tz * S) * G::HY + (2 * ty + ry) * S) * G::HXP + (8 * tx + rx) * S) * G::VS;
-    }
-    int koff[G::KS];
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks)
-        koff[ks] = g == 0 ? G::tap_off(4 * ks) : g == 1 ? G::tap_off(4 * ks + 1)
-                 : g == 2 ? G::tap_off(4 * ks + 2) : G::tap_off(4 * ks + 3);
-
-    f32x4 acc[G::MPW];
-#pragma unroll
-    for (int i = 0; i < G::MPW; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    u32x4 breg[3][G::KS];
-    f32x4 stg[G::PPT][2];
-
-    auto load_b = [&](int c) {
-        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NT + nt) * G::KS) * 64 + lane;
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-#pragma unroll
-            for (int ks = 0; ks < G::KS; ++ks) breg[q][ks] = bsrc[q * PANEL + ks * 64];
-    };
-    auto load_a = [&](int c) {
-        const float* plane = x + (size_t)c * Vin * 8;
-#pragma unroll
-        for (int i = 0; i < G::PPT; ++i) {
-            stg[i][0] = *reinterpret_cast<const f32x4*>(plane + goff[i]);
-            stg[i][1] = *reinterpret_cast<const f32x4*>(plane + goff[i] + 4);
-        }
-    };
-    auto store_a = [&]() {
-        const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < G::PPT; ++i) {
-            const bool in = (inside >> i) & 1u;
-            u32x4 p1, p2, p3;
-            gs_split8(in ? stg[i][0] : z4, in ? stg[i][1] : z4, p1, p2, p3);
-            *reinterpret_cast<u32x4*>(tile + loff[i]) = p1;
-            *reinterpret_cast<u32x4*>(tile + G::TILE_ELEMS + loff[i]) = p2;
-            *reinterpret_cast<u32x4*>(tile + 2 * G::TILE_ELEMS + loff[i]) = p3;
-        }
-    };
-
-    load_b(0);
-    load_a(0);
-    store_a();
-    __syncthreads();
-
-#pragma unroll 1
-    for (int c = 0; c < G::NCH; ++c) {
-        if (c + 1 < G::NCH) load_a(c + 1);
-#pragma unroll
-        for (int ks = 0; ks < G::KS; ++ks) {
-#pragma unroll
-            for (int i = 0; i < G::MPW; ++i) {
-                const unsigned short* ap = tile + abase[i] + koff[ks];
-                const u32x4 a1 = *reinterpret_cast<const u32x4*>(ap);
-                const u32x4 a2 = *reinterpret_cast<const u32x4*>(ap + G::TILE_ELEMS);
-                const u32x4 a3 = *reinterpret_cast<const u32x4*>(ap + 2 * G::TILE_ELEMS);
-                acc[i] = gs_mfma(a3, breg[0][ks], acc[i]);   // the small terms first
-                acc[i] = gs_mfma(a1, breg[2][ks], acc[i]);
-                acc[i] = gs_mfma(a2, breg[1][ks], acc[i]);
-                acc[i] = gs_mfma(a2, breg[0][ks], acc[i]);
-                acc[i] = gs_mfma(a1, breg[1][ks], acc[i]);
-                acc[i] = gs_mfma(a1, breg[0][ks], acc[i]);
-            }
-        }
-        if (c + 1 < G::NCH) {
-            load_b(c + 1);
-            __syncthreads();
-            store_a();
-            __syncthreads();
-        }
-    }
-
-    // epilogue: ReLU(acc + bias) scattered into the LDS tile [oz][oy][ox][co], then every thread owns whole voxels of one C8
-    // plane (8 channels) and stores them 16 bytes at a time, contiguous across the wave (the scalar form stored single
-    // elements: 2- or 4-byte pieces in 16- or 32-byte runs)
-    const int n = lane & 15, co = 16 * nt + n;
-    const float bv = bias[co];
-    __syncthreads();   // the input tile is fully consumed
-#pragma unroll
-    for (int i = 0; i < G::MPW; ++i) {
-        const int t = mg * G::MPW + i;
-        const int tx = t % BX, ty = (t / BX) % BY, tz = t / (BX * BY);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int m = 4 * (lane >> 4) + e;
-            const int oy = 2 * ty + (m >> 3), ox = 8 * tx + (m & 7);
-            otile[(tz * OY + oy) * RP + ox * COUT + (ox >> 3) * 16 + co] = fmaxf(acc[i][e] + bv, 0.0f);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < UPT; ++j) {
-        const int u = tid + j * 256;
-        const int ox = u % OX;
-        int t = u / OX;
-        const int oy = t % OY; t /= OY;
-        const int ozl = t % BZ, pl = t / BZ;
-        const int gz = oz0 + ozl, gy = oy0 + oy, gx = ox0 + ox;
-        if (u < NUNIT && gz < Do && gy < Ho && gx < Wo) {
-            const float* src = otile + (ozl * OY + oy) * RP + ox * COUT + (ox >> 3) * 16 + pl * 8;
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
-            const size_t uo = ((size_t)pl * Vout + ((size_t)gz * Ho + gy) * Wo + gx) * 8;
-            *reinterpret_cast<f32x4*>(y + uo) = lo;
-            *reinterpret_cast<f32x4*>(y + uo + 4) = hi;
-        }
-    }
-}
-
-template <int CIN, int COUT, int S, int BZ, int BY, int BX>
-static int run_convgs(const void* x, void* y, const unsigned short* bp, const float* bias, int Di, int Hi, int Wi,
-                      hipStream_t s) {
-    const int Do = (Di - 1) / S + 1, Ho = (Hi - 1) / S + 1, Wo = (Wi - 1) / S + 1;
-    if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
-        return fail(MVS_ERR_BAD_SHAPE, "convgs_mfma: plane exceeds 31-bit offsets");
-    const int nb = ((Wo + 8 * BX - 1) / (8 * BX)) * ((Ho + 2 * BY - 1) / (2 * BY)) * ((Do + BZ - 1) / BZ);
-    convgs_mfma_kernel<CIN, COUT, S, BZ, BY, BX><<<nb, 256, 0, s>>>(static_cast<const float*>(x), bp, bias,
-                                                                    static_cast<float*>(y), Di, Hi, Wi, Do, Ho, Wo);
-    return check_hip(hipGetLastError(), "convgs_mfma launch");
-}
-
-// deconvgs: the transposed layers conv7 / conv9 (+ skip) for fp32 volumes with split operands -- deconvg16's tile scheme
-// and tap order (deconv16_tap: 5 k-steps per 8-channel chunk, 4 (pz, py) classes, x parity folded into N), fp32 in / out,
-// three bf16 tiles, three panels (pack_split_panels), six MFMAs per k-step with the small terms first.
-template <int CIN, int COUT, int BZ, int BY, int BX>
-__global__ __launch_bounds__(256) void deconvgs_mfma_kernel(
-    const float* __restrict__ x,              // [CIN/8][Di][Hi][Wi][8] fp32
-    const unsigned short* __restrict__ bp,    // [3 pieces][NCH][NTT][5][64][8] bf16
-    const float* __restrict__ bias,           // [COUT]
-    const float* __restrict__ skip,           // [COUT/8][2 Di][2 Hi][2 Wi][8] fp32
-    float* __restrict__ y, int Di, int Hi, int Wi) {
-    using G = DeconvG16<CIN, COUT, BZ, BY, BX>;
-    // epilogue staging tile (deconvg_mfma's scheme): one z parity of the block's 2BZ x 4BY x 16BX output voxels x COUT channels,
-    // rows padded (16 floats per 8 voxels, row pitch = 16 mod 32) so that the accumulator scatter is conflict-free
-    constexpr int OY = 4 * BY, OX = 16 * BX;
-    constexpr int RP0 = OX * COUT + 16 * (OX / 8), RP = (RP0 % 32 == 16) ? RP0 : RP0 + 16;
-    constexpr int OUT_FLOATS = BZ * OY * RP, NUNIT = BZ * OY * OX * (COUT / 8), UPT = (NUNIT + 255) / 256;
-    constexpr int LDS_BYTES = 3 * G::TILE_ELEMS * 2 > OUT_FLOATS * 4 ? 3 * G::TILE_ELEMS * 2 : OUT_FLOATS * 4;
-    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
-    unsigned short* tile = reinterpret_cast<unsigned short*>(lds_raw);
-    float* otile = reinterpret_cast<float*>(lds_raw);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nt = wave % G::NTT, mg = wave / G::NTT;
-    const int nbx = (Wi + 8 * BX - 1) / (8 * BX), nby = (Hi + 2 * BY - 1) / (2 * BY);
-    // blocks are dealt round-robin over the 8 XCDs (blockIdx.x % 8 names the XCD: speed only, never correctness): XCD k works
-    // through the k-th eighth of the (z, row, column) tile sequence, so that tiles sharing halo planes / rows meet in one L2
-    int b;
-    {
-        const int k = blockIdx.x & 7, q = gridDim.x >> 3, rem = gridDim.x & 7;
-        b = k * q + min(k, rem) + (blockIdx.x >> 3);
-    }
-    const int bx = b % nbx; b /= nbx;
-    const int by = b % nby;
-    const int bz = b / nby;
-    const int ix0 = bx * 8 * BX, iy0 = by * 2 * BY, iz0 = bz * BZ;
-    const int Ho = 2 * Hi, Wo = 2 * Wi;
-    const size_t Vin = (size_t)Di * Hi * Wi, Vout = Vin * 8;
-    constexpr size_t PANEL = (size_t)G::NCH * G::NTT * G::KS * 64;   // u32x4 fragments per piece
-
-    // staging: piece p = tid + i * 256 = one voxel (8 channels) of the halo tile; threads beyond the tile shadow its
-    // last voxel (no branch in the staging code)
-    int goff[G::PPT], loff[G::PPT];
-    unsigned inside = 0;
-#pragma unroll
-    for (int i = 0; i < G::PPT; ++i) {
-        const int v = min(tid + i * 256, G::NPIECE - 1);
-        const int hx = v % G::HX, t = v / G::HX;
-        const int hy = t % G::HY, hz = t / G::HY;
-        const int gz = iz0 + hz, gy = iy0 + hy, gx = ix0 + hx;
-        const bool ok = gz < Di && gy < Hi && gx < Wi;
-        goff[i] = ok ? (int)((((size_t)gz * Hi + gy) * Wi + gx) * 8) : 0;
-        inside |= ok ? (1u << i) : 0u;
-        loff[i] = ((hz * G::HY + hy) * G::HXP + hx) * G::VS;
-    }
-
-    const int r = lane & 15, g = lane >> 4;
-    const int ry = r >> 3, rx = r & 7;
-    int abase[G::MPW];
-#pragma unroll
-    for (int i = 0; i < G::MPW; ++i) {
-        const int t = mg * G::MPW + i;
-        const int tx = t % BX, ty = (t / BX) % BY, tz = t / (BX * BY);
-        abase[i] = ((tz * G::HY + 2 * ty + ry) * G::HXP + 8 * tx + rx + (g & 1)) * G::VS;
-    }
-    int koff[G::KS];
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) {
-        const Deconv16Tap t0 = deconv16_tap(ks, 0), t1 = deconv16_tap(ks, 1);
-        koff[ks] = (g >> 1) ? (t1.dz * G::HY + t1.dy) * G::HXP * G::VS : (t0.dz * G::HY + t0.dy) * G::HXP * G::VS;
-    }
-
-    f32x4 acc[4][G::MPW];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int i = 0; i < G::MPW; ++i) acc[c][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    u32x4 breg[3][G::KS];
-    f32x4 stg[G::PPT][2];
-
-    auto load_b = [&](int c) {
-        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NTT + nt) * G::KS) * 64 + lane;
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-#pragma unroll
-            for (int ks = 0; ks < G::KS; ++ks) breg[q][ks] = bsrc[q * PANEL + ks * 64];
-    };
-    auto load_a = [&](int c) {
-        const float* plane = x + (size_t)c * Vin * 8;
-#pragma unroll
-        for (int i = 0; i < G::PPT; ++i) {
-            stg[i][0] = *reinterpret_cast<const f32x4*>(plane + goff[i]);
-            stg[i][1] = *reinterpret_cast<const f32x4*>(plane + goff[i] + 4);
-        }
-    };
-    auto store_a = [&]() {
-        const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < G::PPT; ++i) {
-            const bool in = (inside >> i) & 1u;
-            u32x4 p1, p2, p3;
-            gs_split8(in ? stg[i][0] : z4, in ? stg[i][1] : z4, p1, p2, p3);
-            *reinterpret_cast<u32x4*>(tile + loff[i]) = p1;
-            *reinterpret_cast<u32x4*>(tile + G::TILE_ELEMS + loff[i]) = p2;
-            *reinterpret_cast<u32x4*>(tile + 2 * G::TILE_ELEMS + loff[i]) = p3;
-        }
-    };
-
-    load_b(0);
-    load_a(0);
-    store_a();
-    __syncthreads();
-
-#pragma unroll 1
-    for (int c = 0; c < G::NCH; ++c) {
-        if (c + 1 < G::NCH) load_a(c + 1);
-#pragma unroll
-        for (int ks = 0; ks < G::KS; ++ks) {
-            const int cls = deconv16_tap(ks, 0).cls;
-#pragma unroll
-            for (int i = 0; i < G::MPW; ++i) {
-                const unsigned short* ap = tile + abase[i] + koff[ks];
-                const u32x4 a1 = *reinterpret_cast<const u32x4*>(ap);
-                const u32x4 a2 = *reinterpret_cast<const u32x4*>(ap + G::TILE_ELEMS);
-                const u32x4 a3 = *reinterpret_cast<const u32x4*>(ap + 2 * G::TILE_ELEMS);
-                acc[cls][i] = gs_mfma(a3, breg[0][ks], acc[cls][i]);   // the small terms first
-                acc[cls][i] = gs_mfma(a1, breg[2][ks], acc[cls][i]);
-                acc[cls][i] = gs_mfma(a2, breg[1][ks], acc[cls][i]);
-                acc[cls][i] = gs_mfma(a2, breg[0][ks], acc[cls][i]);
-                acc[cls][i] = gs_mfma(a1, breg[1][ks], acc[cls][i]);
-                acc[cls][i] = gs_mfma(a1, breg[0][ks], acc[cls][i]);
-            }
-        }
-        if (c + 1 < G::NCH) {
-            load_b(c + 1);
-            __syncthreads();
-            store_a();
-            __syncthreads();
-        }
-    }
-
-    // epilogue: col n -> (px, co); row m -> input voxel of the tile; class -> (pz, py).  ReLU(acc + bias) is scattered into the
-    // LDS tile [oz][oy][ox][co]; then every thread owns whole voxels of one C8 plane (32 B) and does the skip add with 16-byte
-    // loads / stores that are contiguous across the wave (the scalar form: 4-byte stores in 32-byte runs and one exposed skip
-    // load per element).  Two passes, one per output z parity; the skip values of a pass are requested before its scatter.
-    const int Do = 2 * Di;
-    const int nn = 16 * nt + (lane & 15);
-    const int px = nn / COUT, co = nn % COUT;
-    const float bv = bias[co];
-#pragma unroll
-    for (int pz = 0; pz < 2; ++pz) {
-        size_t uo[UPT];
-        int usrc[UPT];
-        f32x4 sk0[UPT], sk1[UPT];
-#pragma unroll
-        for (int j = 0; j < UPT; ++j) {
-            const int u = tid + j * 256;
-            const int ox = u % OX;
-            int t = u / OX;
-            const int oy = t % OY; t /= OY;
-            const int ozl = t % BZ, pl = t / BZ;
-            const int gz = 2 * (iz0 + ozl) + pz, gy = 2 * iy0 + oy, gx = 2 * ix0 + ox;
-            const bool ok = u < NUNIT && gz < Do && gy < Ho && gx < Wo;
-            usrc[j] = ok ? (ozl * OY + oy) * RP + ox * COUT + (ox >> 3) * 16 + pl * 8 : -1;
-            uo[j] = ok ? ((size_t)pl * Vout + ((size_t)gz * Ho + gy) * Wo + gx) * 8 : 0;
-            sk0[j] = *reinterpret_cast<const f32x4*>(skip + uo[j]);
-            sk1[j] = *reinterpret_cast<const f32x4*>(skip + uo[j] + 4);
-        }
-        __syncthreads();  // input tiles (pass 0) / previous pass's staging tile fully consumed
-#pragma unroll
-        for (int i = 0; i < G::MPW; ++i) {
-            const int t = mg * G::MPW + i;
-            const int tx = t % BX, ty = (t / BX) % BY, tz = t / (BX * BY);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int m = 4 * (lane >> 4) + e;
-                const int ly = 2 * ty + (m >> 3), lx = 8 * tx + (m & 7);  // input voxel inside the block tile
-                const int ox = 2 * lx + px;
-#pragma unroll
-                for (int py = 0; py < 2; ++py)
-                    otile[(tz * OY + 2 * ly + py) * RP + ox * COUT + (ox >> 3) * 16 + co] =
-                        fmaxf(acc[2 * pz + py][i][e] + bv, 0.0f);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < UPT; ++j) {
-            if (usrc[j] < 0) continue;
-            const float* src = otile + usrc[j];
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
-            *reinterpret_cast<f32x4*>(y + uo[j]) = lo + sk0[j];
-            *reinterpret_cast<f32x4*>(y + uo[j] + 4) = hi + sk1[j];
-        }
-    }
-}
-
-template <int CIN, int COUT, int BZ, int BY, int BX>
-static int run_deconvgs(const void* x, const void* skip, void* y, const unsigned short* bp, const float* bias,
-                        int Di, int Hi, int Wi, hipStream_t s) {
-    if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
-        return fail(MVS_ERR_BAD_SHAPE, "deconvgs_mfma: plane exceeds 31-bit offsets");
-    const int nb = ((Wi + 8 * BX - 1) / (8 * BX)) * ((Hi + 2 * BY - 1) / (2 * BY)) * ((Di + BZ - 1) / BZ);
-    deconvgs_mfma_kernel<CIN, COUT, BZ, BY, BX><<<nb, 256, 0, s>>>(static_cast<const float*>(x), bp, bias,
-                                                                   static_cast<const float*>(skip),
-                                                                   static_cast<float*>(y), Di, Hi, Wi);
-    return check_hip(hipGetLastError(), "deconvgs_mfma launch");
-}
-
 // fp32 volumes, split operands: conv2, conv3, conv4 (measured at cfg2 against the fp32-MFMA kernels: 0.0588 -> 0.0534,
 // 0.0310 -> 0.0276, 0.0396 -> 0.0329 ms with the 16-bit kernels' block tiles; a sweep of 8-20 tiles per layer
 // (tools/gpu/tile_sweep.sh, BZ x BY x BX M-tiles of 2 x 8 outputs): conv3 1x2x2 -> 2x2x1 0.0275 -> 0.0238, conv4 1x2x2 ->
@@ -1578,11 +1242,11 @@ int launch_layer_split(int layer, const void* x, const void* skip, void* y, cons
                        int Di, int Hi, int Wi, hipStream_t s) {
     const unsigned short* bp = static_cast<const unsigned short*>(panel);
     switch (layer) {
-        case 2: return run_convgs<16, 16, 1, 2, 4, 2>(x, y, bp, bias, Di, Hi, Wi, s);
-        case 3: return run_convgs<16, 32, 2, 2, 2, 1>(x, y, bp, bias, Di, Hi, Wi, s);
-        case 4: return run_convgs<32, 32, 1, 4, 2, 1>(x, y, bp, bias, Di, Hi, Wi, s);
-        case 7: return run_deconvgs<64, 32, 1, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
-        case 8: return run_deconvgs<32, 16, 2, 4, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+        case 2: return run_convg16<OpSplit, 16, 16, 1, 2, 4, 2>(x, y, bp, bias, Di, Hi, Wi, s);
+        case 3: return run_convg16<OpSplit, 16, 32, 2, 2, 2, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+        case 4: return run_convg16<OpSplit, 32, 32, 1, 4, 2, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+        case 7: return run_deconvg16<OpSplit, 64, 32, 1, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+        case 8: return run_deconvg16<OpSplit, 32, 16, 2, 4, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
         default: return fail(MVS_ERR_BAD_SHAPE, "split kernels: layer %d not covered", layer);
     }
 }

@@ -209,7 +209,7 @@ def test_pack_weights_folds_bn_and_relayouts():
     h9 = blob[h16_bf16_off9:h16_bf16_off9 + elems // 2].view(np.uint16)
     assert np.array_equal(h9, pcs[0])
     off += ((3 * elems) // 2 + 63) // 64 * 64
-    # ... conv9 (layer 8) and conv7 (layer 7), the transposed layers' split-operand kernels (deconvgs)
+    # ... conv9 (layer 8) and conv7 (layer 7), the transposed layers on the split-operand tile kernel (deconvg16 with OpSplit)
     for l in (8, 7):
         ci, co = _lib._LAYER_CH[l]
         elems = (ci // 8) * (2 * co // 16) * 5 * 64 * 8

@@ -1,4 +1,4 @@
-# Block-tile sweep of the split-operand tile kernels (convgs, conv3d_mfma16.hip) -- a record of the round-4 sweep, not a
+# Block-tile sweep of the split-operand tile kernels (convg16 with OpSplit, conv3d_mfma16.hip) -- a record of the round-4 sweep, not a
 # runnable harness: launch_layer_split() was built with one `case` per candidate tile (BZ x BY x BX M-tiles of 2 x 8
 # outputs) chosen by an environment variable, and every candidate was timed with
 #   python bench.py --streams 1 --steps 10 --prewarm-ms 100 --no-cpu-baseline --no-e2e --no-other-configs --no-live-traffic
