@@ -1,0 +1,300 @@
+#!/usr/bin/env python3
+"""Child-process helper: single-product probes and the dense fp64 bound (tests/probes.py) for every CostRegNet layer
+and the fused conv11_prob tail, under ONE kernel-selection environment (read once per process by options() in
+mvs_host.hip).  Usage: probe_check.py <case>; the parent (test_gpu_conv_probes.py) sets CASES[case]["env"].
+Prints one JSON line with the measured max ratios (got - want over the bound, per layer / set / storage) and exits
+non-zero after listing every violated bound.
+
+Which kernel each case reaches at the probe shapes of probes.GEOM (the dispatch in conv3d_direct.hip
+launch_conv_layer, conv3d_mfma16.hip launch_layer16_dt / launch_layer_split, conv3d_mfma.hip launch_convg_dt,
+conv11_prob.hip launch_conv11_prob); "wino" names the layers held to a Winograd bound (probes.WINO).
+  fp32 "default": conv0 conv0_w48t (split-operand F(4,3), D % 4 == 0); conv1 convg (run_convg_persist falls back to the
+      one-tile-per-block kernel below 4 tiles per block, and conv1z needs columns that fill the chip); conv2-conv4
+      convg16<OpSplit>; conv5 / conv6 convs, conv7 deconvs (split-K); conv9 deconvg16<OpSplit> (MVS_SPLIT_DECONV=2);
+      conv11 deconvg; prob prob_lds; tail conv11_prob_split.
+  MVS_CONV0_SPLIT=0: conv0_w43 (fp32 F(4,3));  MVS_CONV0_WINO=0: conv0_4x4 (direct).
+  MVS_CONV1Z=1: conv1z;  MVS_PERSIST_CUS=1 with MVS_CONV1Z=0: convg_persist on a one-CU grid (MVS_PERSIST_CUS alone
+      would also make conv1z's "columns fill the chip" test pass).
+  MVS_SPLIT_LAYERS=0: conv2 / conv4 convwz (F(2,3)), conv3 convg, conv9 deconvg;  + MVS_CONV_WINO=0: conv2 / conv4 convg.
+  MVS_SPLIT_DECONV=3: conv7 deconvg16<OpSplit>;  =0: conv9 deconvg.
+  MVS_TAIL_SPLIT=0: tail conv11_prob_priv.  MVS_FUSE_PROB=0 only splits the tail of mvs_costreg_forward into the
+      layer-9 and layer-10 launches, which every case probes on their own; it selects no other kernel.
+  MVS_FORCE_DIRECT=1: conv3d_direct / deconv3d_direct / prob for every layer (fp32 only).
+  16-bit "default16": conv0 conv0p16 (conv0z16 needs columns that fill the chip), conv1-conv3 convg16<Op16> (likewise
+      convz16), conv4-conv9 the shallow block tiles (tile_fills_chip is false at these sizes), prob prob_lds<16-bit>,
+      tail conv11_prob16.  MVS_CONV0Z16=1/0, MVS_CONVZ16=1/0, MVS_DEEP_TILES=1/0 force either side.
+"""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+import probes as P  # noqa: E402
+from oracle import oracle as orc  # noqa: E402
+from scene_3dreconstruction_mvsnet_amd import _lib, synthetic  # noqa: E402
+
+DEV = "cuda:0"
+ALL = tuple(range(11)) + ("tail",)
+F32, B16 = ("f32",), ("f16", "bf16")
+
+# case -> environment, storages, layers probed, Winograd form per layer (absent: direct / MFMA / split)
+CASES = {
+    "default": dict(env={}, storages=F32, layers=ALL, wino={0: "F43"}),
+    "conv0_split0": dict(env={"MVS_CONV0_SPLIT": "0"}, storages=F32, layers=(0,), wino={0: "F43"}),
+    "conv0_wino0": dict(env={"MVS_CONV0_WINO": "0"}, storages=F32, layers=(0,), wino={}),
+    "conv1z": dict(env={"MVS_CONV1Z": "1"}, storages=F32, layers=(1,), wino={}),
+    "persist": dict(env={"MVS_PERSIST_CUS": "1", "MVS_CONV1Z": "0"}, storages=F32, layers=(1,), wino={}),
+    "split0": dict(env={"MVS_SPLIT_LAYERS": "0"}, storages=F32, layers=(2, 3, 4, 8), wino={2: "F23", 4: "F23"}),
+    "split0_wino0": dict(env={"MVS_SPLIT_LAYERS": "0", "MVS_CONV_WINO": "0"}, storages=F32, layers=(2, 4), wino={}),
+    "split_deconv3": dict(env={"MVS_SPLIT_DECONV": "3"}, storages=F32, layers=(7, 8), wino={}),
+    "split_deconv0": dict(env={"MVS_SPLIT_DECONV": "0"}, storages=F32, layers=(7, 8), wino={}),
+    "tail_split0": dict(env={"MVS_TAIL_SPLIT": "0"}, storages=F32, layers=("tail",), wino={}),
+    "force_direct": dict(env={"MVS_FORCE_DIRECT": "1"}, storages=F32, layers=tuple(range(11)), wino={}),
+    "default16": dict(env={}, storages=B16, layers=ALL, wino={}),
+    "conv0z16_1": dict(env={"MVS_CONV0Z16": "1"}, storages=B16, layers=(0,), wino={}),
+    "conv0z16_0": dict(env={"MVS_CONV0Z16": "0"}, storages=B16, layers=(0,), wino={}),
+    "convz16_1": dict(env={"MVS_CONVZ16": "1"}, storages=B16, layers=(1, 2, 3), wino={}),
+    "convz16_0": dict(env={"MVS_CONVZ16": "0"}, storages=B16, layers=(1, 2, 3), wino={}),
+    "deep1": dict(env={"MVS_DEEP_TILES": "1"}, storages=B16, layers=(4, 5, 6, 7, 8), wino={}),
+    "deep0": dict(env={"MVS_DEEP_TILES": "0"}, storages=B16, layers=(4, 5, 6, 7, 8), wino={}),
+}
+
+# every templated launcher instantiation of the CostRegNet conv kernels (run_*<...> in csrc/conv*.hip, whitespace
+# removed) and every kernel launched directly -> the case that reaches it.  test_conv_probes_host.py parses the
+# sources: a new instantiation or kernel without an entry here fails the CPU suite.
+INSTANTIATIONS = {
+    "run_direct<32,8,8,1,false,true,false>": "force_direct",
+    "run_direct<8,16,16,2,false,true,false>": "force_direct",
+    "run_direct<16,16,16,1,false,true,false>": "force_direct",
+    "run_direct<16,32,16,2,false,true,false>": "force_direct",
+    "run_direct<32,32,8,1,false,true,false>": "force_direct",
+    "run_direct<32,64,4,2,false,true,false>": "force_direct",
+    "run_direct<64,64,4,1,false,true,false>": "force_direct",
+    "run_direct<64,32,8,2,true,true,true>": "force_direct",
+    "run_direct<32,16,16,2,true,true,true>": "force_direct",
+    "run_deconv<16,8,8>": "force_direct",
+    "run_conv0_4x4<DT>": "conv0_wino0",
+    "run_conv0_w43<DT>": "conv0_split0",
+    "run_convwz<DT,16,16,4,2>": "split0",
+    "run_convwz<DT,32,32,2,2>": "split0",
+    "run_convg_persist<DT,8,16,2,1,2,2>": "persist",
+    "run_convg<DT,16,16,1,2,4,2>": "split0_wino0",
+    "run_convg<DT,16,32,2,1,2,2>": "split0",
+    "run_convg<DT,32,32,1,1,2,2>": "split0_wino0",
+    "run_deconvg<DT,32,16,1,4,1>": "split_deconv0",
+    "run_deconvg<DT,16,8,1,4,2>": "default",
+    "run_convs<DT,32,64,2,1,2,1,4>": "default",
+    "run_convs<DT,64,64,1,1,2,1,4>": "default",
+    "run_deconvs<DT,64,32,1,2,1,4>": "default",
+    "run_convg16<OpSplit,16,16,1,2,4,2>": "default",
+    "run_convg16<OpSplit,16,32,2,2,2,1>": "default",
+    "run_convg16<OpSplit,32,32,1,4,2,1>": "default",
+    "run_deconvg16<OpSplit,64,32,1,1,1>": "split_deconv3",
+    "run_deconvg16<OpSplit,32,16,2,4,1>": "default",
+    "run_convg16<Op16<DT>,8,16,2,2,2,2>": "convz16_0",
+    "run_convg16<Op16<DT>,16,16,1,2,4,2>": "convz16_0",
+    "run_convg16<Op16<DT>,16,32,2,4,1,1>": "convz16_0",
+    "run_convg16<Op16<DT>,32,32,1,4,2,1>": "deep1",
+    "run_convg16<Op16<DT>,32,32,1,1,2,2>": "deep0",
+    "run_convg16<Op16<DT>,32,64,2,2,1,1>": "deep1",
+    "run_convg16<Op16<DT>,32,64,2,1,1,1>": "deep0",
+    "run_convg16<Op16<DT>,64,64,1,4,1,1>": "deep1",
+    "run_convg16<Op16<DT>,64,64,1,1,1,1>": "deep0",
+    "run_deconvg16<Op16<DT>,64,32,2,1,1>": "deep1",
+    "run_deconvg16<Op16<DT>,64,32,1,1,1>": "deep0",
+    "run_deconvg16<Op16<DT>,32,16,4,2,1>": "deep1",
+    "run_deconvg16<Op16<DT>,32,16,1,4,1>": "deep0",
+    "run_deconvg16<Op16<DT>,16,8,1,4,2>": "default16",
+    "run_convz16<DT,8,16,2>": "convz16_1",
+    "run_convz16<DT,16,16,1>": "convz16_1",
+    "run_convz16<DT,16,32,2>": "convz16_1",
+}
+KERNELS = {
+    "conv0_w48t_kernel": "default",
+    "conv0_w43_mfma_kernel": "conv0_split0",
+    "conv0_4x4_mfma_kernel": "conv0_wino0",
+    "conv1z_mfma_kernel": "conv1z",
+    "convg_mfma_kernel": "default",
+    "convg_persist_mfma_kernel": "persist",
+    "convwz_mfma_kernel": "split0",
+    "convs_mfma_kernel": "default",
+    "deconvs_mfma_kernel": "default",
+    "deconvg_mfma_kernel": "default",
+    "convg16_mfma_kernel": "default",
+    "deconvg16_mfma_kernel": "default",
+    "convz16_mfma_kernel": "convz16_1",
+    "conv0z16_mfma_kernel": "conv0z16_1",
+    "conv0p16_mfma_kernel": "conv0z16_0",
+    "conv3d_direct_kernel": "force_direct",
+    "deconv3d_direct_kernel": "force_direct",
+    "prob_lds_kernel": "default",
+    "conv11_prob_split_kernel": "default",
+    "conv11_prob_priv_kernel": "tail_split0",
+    "conv11_prob16_kernel": "default16",
+}
+
+
+def cu(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
+
+
+class Checker:
+    def __init__(self, case):
+        self.case = case
+        self.ratios, self.inexact, self.failures = {}, {}, []
+
+    def add(self, key, err, bound):
+        r = float((err / bound).max()) if err.size else 0.0
+        self.ratios[key] = max(self.ratios.get(key, 0.0), r)
+        if r > 1.0:
+            i = np.unravel_index(int(np.argmax(err / bound)), err.shape)
+            self.failures.append(f"{key}: {r:.3g} x bound at {tuple(int(v) for v in i)} (err {float(err[i]):.3e}, "
+                                 f"bound {float(bound[i]):.3e})")
+
+
+def run_layer(layer, x, skip, blob, storage):
+    code = _lib.dtype_code(storage)
+    tdt = _lib.TORCH_DTYPES[code]
+    xt = _lib.to_c8(cu(x)).to(tdt)
+    st = None if skip is None else _lib.to_c8(cu(skip)).to(tdt)
+    y = _lib.conv_layer(layer, xt, st, blob, dtype=code).float()
+    return (y if layer == 10 else _lib.from_c8(y)).cpu().numpy().astype(np.float64)
+
+
+def run_tail(x, skip, blob, storage):
+    code = _lib.dtype_code(storage)
+    tdt = _lib.TORCH_DTYPES[code]
+    return _lib.conv11_prob(_lib.to_c8(cu(x)).to(tdt), _lib.to_c8(cu(skip)).to(tdt), blob,
+                            dtype=code).cpu().numpy().astype(np.float64)
+
+
+def out_shape(layer):
+    ci, co, s, tr, (D, H, W) = P.GEOM[layer]
+    if tr:
+        return (co, 2 * D, 2 * H, 2 * W)
+    return (co, (D - 1) // s + 1, (H - 1) // s + 1, (W - 1) // s + 1)
+
+
+def check_single(chk, key, layer, got, x, skip, wf, sh, storage, wino):
+    want, bound = P.probe_want_bound(layer, x, skip, wf, sh, storage, wino)
+    if storage != "f32" and layer != 10:
+        chk.inexact[key] = chk.inexact.get(key, 0) + int((got != want).sum())
+    chk.add(key, np.abs(got - want), bound)
+
+
+def check_dense(chk, key, layer, got, x, skip, wf, sh, storage, wino):
+    ref, bound = P.dense_ref_bound(layer, x, skip, wf, sh, storage, wino)
+    chk.add(key, np.abs(got - ref), bound)
+
+
+def probe_layer(chk, layer, storage, sd, blobs_crafted, wino, rng):
+    ci, co, _, tr, shape = P.GEOM[layer]
+    blob = blobs_crafted["rand"]
+    wf, sh = P.folded(sd, layer)
+    oshape = out_shape(layer)
+    sp = P.spacing(layer, wino)
+    for ph in P.phases(sp):
+        x = P.lattice(ci, shape, sp, ph, rng)
+        skip = rng.standard_normal(oshape).astype(np.float32) if tr else None
+        got = run_layer(layer, x, skip, blob, storage)
+        check_single(chk, f"{layer}:lattice:{storage}", layer, got, x, skip, wf, sh, storage, wino)
+    if storage == "f32":
+        runs = 27 if layer == 10 else P.crafted_runs(layer)
+        for r in range(runs):
+            sdc, blob_c = blobs_crafted[r]
+            wfc, shc = P.folded(sdc, layer)
+            x = P.crafted((ci,) + shape, rng)
+            skip = np.zeros(oshape, np.float32) if tr else None
+            got = run_layer(layer, x, skip, blob_c, storage)
+            check_single(chk, f"{layer}:crafted:{storage}", layer, got, x, skip, wfc, shc, storage, wino)
+    vols = [rng.standard_normal((ci,) + shape).astype(np.float32)]
+    if storage == "f32":   # heavy-tailed non-negative, as a variance volume (fp16 would overflow)
+        vols.append(np.exp(3.0 * rng.standard_normal((ci,) + shape)).astype(np.float32))
+    for x in vols:
+        skip = rng.standard_normal(oshape).astype(np.float32) if tr else None
+        got = run_layer(layer, x, skip, blob, storage)
+        check_dense(chk, f"{layer}:dense:{storage}", layer, got, x, skip, wf, sh, storage, wino)
+
+
+def probe_tail(chk, storage, sd, blobs_crafted, rng):
+    """conv11_prob: prob.weight with one nonzero entry (channel, tap) swept over the 27 taps (channel 3 r % 8), the
+    input on the spacing-2 lattice of a transposed layer (phase r % 8): every logit is pw d11 + pb with d11 a single
+    product + shift + skip."""
+    q = lambda t: orc.round_storage(np.asarray(t, np.float32), storage)  # noqa: E731
+    D, H, W = P.TAIL_SHAPE
+    sshape = (8, 2 * D, 2 * H, 2 * W)
+    w9, sh9 = P.folded(sd, 9)
+    wq = w9 if storage == "f32" else q(w9)
+    sp = (2, 2, 2)
+    ph = P.phases(sp)
+    key = f"tail:lattice:{storage}"
+    for r in range(27):
+        sdr = dict(sd)
+        sdr["prob.weight"] = P.single_prob_weight((3 * r) % 8, r, np.float32(rng.standard_normal()))
+        blob = _lib.pack_weights(sdr).to(DEV)
+        x = q(P.lattice(16, (D, H, W), sp, ph[r % 8], rng))
+        skip = q(rng.standard_normal(sshape).astype(np.float32))
+        got = run_tail(x, skip, blob, storage)
+        want, S = P.tail64(x, skip, wq, sh9, sdr["prob.weight"], sdr["prob.bias"])
+        chk.add(key, np.abs(got - want), P.TAIL_ULPS * P.ulp32(S))
+    if storage == "f32":
+        for r in range(27):
+            sdc, blob_c = blobs_crafted[r]
+            w9c, sh9c = P.folded(sdc, 9)
+            x = P.crafted((16, D, H, W), rng)
+            skip = np.zeros(sshape, np.float32)
+            got = run_tail(x, skip, blob_c, storage)
+            want, S = P.tail64(x, skip, w9c, sh9c, sdc["prob.weight"], sdc["prob.bias"])
+            chk.add(f"tail:crafted:{storage}", np.abs(got - want), P.TAIL_ULPS * P.ulp32(S))
+    blob = blobs_crafted["rand"]
+    for x in (rng.standard_normal((16, D, H, W)).astype(np.float32),):
+        x = q(x)
+        skip = q(rng.standard_normal(sshape).astype(np.float32))
+        got = run_tail(x, skip, blob, storage)
+        want, S = P.tail64(x, skip, wq, sh9, sd["prob.weight"], sd["prob.bias"])
+        chk.add(f"tail:dense:{storage}", np.abs(got - want), P.DENSE_C * P.U * S)
+
+
+class CraftedBlobs(dict):
+    """run -> (crafted state, packed blob on the GPU), packed on first use; "rand" -> the random state's blob."""
+
+    def __init__(self, sd):
+        super().__init__(rand=_lib.pack_weights(sd).to(DEV))
+        self.sd = sd
+
+    def __missing__(self, r):
+        sdc = P.crafted_state(self.sd, r, np.random.default_rng(1000 + r))
+        self[r] = (sdc, _lib.pack_weights(sdc).to(DEV))
+        return self[r]
+
+
+def main():
+    name = sys.argv[1]
+    case = CASES[name]
+    for k, v in case["env"].items():
+        assert os.environ.get(k) == v, f"case {name} needs {k}={v} in the environment"
+    sd = synthetic.random_costreg_state(seed=13)
+    blobs = CraftedBlobs(sd)
+    chk = Checker(name)
+    for storage in case["storages"]:
+        rng = np.random.default_rng(17)
+        for layer in case["layers"]:
+            if layer == "tail":
+                probe_tail(chk, storage, sd, blobs, rng)
+            else:
+                probe_layer(chk, layer, storage, sd, blobs, case["wino"].get(layer), rng)
+    print(json.dumps({"case": name, "ratios": {k: round(v, 4) for k, v in chk.ratios.items()},
+                      "inexact16": chk.inexact}))
+    for f in chk.failures:
+        print("FAIL", name, f)
+    return 1 if chk.failures else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,250 @@
+"""CPU side of the conv probes (tests/probes.py, tests/probe_check.py, test_gpu_conv_probes.py): the lattice and the
+crafted weights give every output at most one product, the crafted values split as designed under an exactly
+identity BN, the Winograd matrices are the ones the bound is derived from, every kernel instantiation has a probe
+case -- and the bounds catch plausible split-operand defects, emulated in numpy, while an exact emulation of the
+six-term split with fp32 accumulation passes them."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import probes as P
+from probe_check import CASES, INSTANTIATIONS, KERNELS
+from scene_3dreconstruction_mvsnet_amd import _lib, synthetic
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scene_3dreconstruction_mvsnet_amd",
+                    "csrc")
+
+
+def _read(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# one product per output
+# ---------------------------------------------------------------------------------------------------------------
+def _count_products(layer, nz):
+    """number of nonzero products each output receives from the 0/1 occupancy nz [D,H,W] (all weights nonzero)."""
+    X = torch.from_numpy(nz.astype(np.float64))[None, None]
+    ones = torch.ones((1, 1, 3, 3, 3), dtype=torch.float64)
+    if P.GEOM[layer][3]:
+        return F.conv_transpose3d(X, ones, stride=2, padding=1, output_padding=1)[0, 0].numpy()
+    return F.conv3d(X, ones, stride=P.GEOM[layer][2], padding=1)[0, 0].numpy()
+
+
+FORMS = [(layer, None) for layer in range(11)] + [(0, "F43"), (2, "F23"), (4, "F23")]
+
+
+@pytest.mark.parametrize("layer,wino", FORMS)
+def test_lattice_gives_every_output_one_product_at_most(layer, wino):
+    ci, _, _, _, shape = P.GEOM[layer]
+    sp = P.spacing(layer, wino)
+    seen = np.zeros((ci,) + shape, np.int64)
+    rng = np.random.default_rng(0)
+    for ph in P.phases(sp):
+        x = P.lattice(ci, shape, sp, ph, rng)
+        nz = x != 0
+        assert (nz.sum(0) <= 1).all()                      # one channel per voxel
+        assert _count_products(layer, nz.any(0)).max() <= 1
+        if wino:   # every tile's m + 2 input planes (any z offset) hold one lattice plane at most
+            planes = nz.any(axis=(0, 2, 3)).astype(int)
+            win = P.wino_tile(wino)[1]
+            assert max(planes[z:z + win].sum() for z in range(shape[0])) <= 1
+        seen += nz
+    assert (seen.sum(0) >= 1).all(), "the phases together probe every voxel"
+
+
+@pytest.mark.parametrize("layer", range(11))
+def test_crafted_weights_give_every_output_one_product_and_sweep_all_taps(layer):
+    ci, co = P.GEOM[layer][:2]
+    base = synthetic.random_costreg_state(seed=1)
+    runs = 27 if layer == 10 else P.crafted_runs(layer)
+    taps = set()
+    for r in range(runs):
+        wf, sh = P.folded(P.crafted_state(base, r, np.random.default_rng(r)), layer)
+        assert (sh == 0).all()
+        nzw = wf != 0
+        assert (nzw.reshape(co, -1).sum(1) == 1).all()        # one (ci, tap) per output channel
+        taps |= {int(t) for t in np.nonzero(nzw.reshape(co, ci, 27))[2]}
+    assert taps == set(range(27))
+
+
+def test_crafted_values_split_as_designed():
+    v = P.crafted((4096,), np.random.default_rng(3)).astype(np.float32)
+    p1, p2, p3 = P.split3(v)
+    v64, e = v.astype(np.float64), np.floor(np.log2(v.astype(np.float64)))
+    assert ((p1.astype(np.float64) + p2 + p3) == v64).all()    # exact three-piece split
+    np.testing.assert_array_equal(p2, (2.0 ** -8 - 2.0 ** -15) * 2.0 ** e)
+    np.testing.assert_array_equal(p3, (2.0 ** -17 - 2.0 ** -23) * 2.0 ** e)
+    # the cross terms a split kernel must keep: a2 b2 and a1 b3 (= a3 b1 by symmetry) are >= 16 ulp of a b
+    ab = v64 * v64[::-1]
+    for term in (p2.astype(np.float64) * p2[::-1], p1.astype(np.float64) * p3[::-1]):
+        assert (term >= 16 * P.ulp32(ab)).all()
+
+
+def test_identity_bn_packs_the_crafted_weights_unscaled():
+    """The packer's folded weights equal the crafted weights bit for bit (scale exactly 1.0, shift 0): the split
+    panels (pack_split_panels) and every other panel are packed from this section."""
+    v1 = P.identity_var()
+    assert np.float32(1.0) / np.sqrt(np.float32(v1) + np.float32(1e-5)) == np.float32(1.0)
+    sd = P.crafted_state(synthetic.random_costreg_state(seed=2), 0, np.random.default_rng(0))
+    blob = _lib.pack_weights(sd).numpy().view(np.float32)
+    off = 0
+    for l in range(11):
+        ci, co = _lib._LAYER_CH[l]
+        wf, sh = P.folded(sd, l)
+        want = wf.reshape(co, ci, 27).transpose(2, 1, 0)
+        np.testing.assert_array_equal(blob[off:off + 27 * ci * co].reshape(27, ci, co), want)
+        off = (off + 27 * ci * co + 63) // 64 * 64
+        np.testing.assert_array_equal(blob[off:off + co], sh)
+        off = (off + co + 63) // 64 * 64
+        if l < 10:
+            raw = np.asarray(sd[_lib.CONV_WEIGHT_KEYS[l]], np.float32)
+            raw = raw.transpose(1, 0, 2, 3, 4) if P.GEOM[l][3] else raw
+            np.testing.assert_array_equal(wf, raw)
+            nz = wf[wf != 0]
+            p1, p2, p3 = P.split3(nz)
+            assert ((p1.astype(np.float64) + p2 + p3) == nz).all() and (p2 > 0).all() and (p3 > 0).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the Winograd matrices of the bound
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["F43", "F23"])
+def test_winograd_matrices_compute_the_z_correlation(name):
+    A, G, B = P.WINO[name]
+    m, n = P.wino_tile(name)
+    rng = np.random.default_rng(5)
+    for _ in range(20):
+        d, g = rng.standard_normal(n), rng.standard_normal(3)
+        y = A @ ((G @ g) * (B @ d))
+        np.testing.assert_allclose(y, [d[i:i + 3] @ g for i in range(m)], rtol=1e-12, atol=1e-12)
+    assert 1.0 < P.wino_gain(name) < 200.0
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# sensitivity: emulated split-operand kernels against the probe and dense bounds
+# ---------------------------------------------------------------------------------------------------------------
+TERMS = ("a1b1", "a1b2", "a2b1", "a2b2", "a1b3", "a3b1")
+SENS_LAYER, SENS_SHAPE = 2, (6, 7, 10)   # conv2's geometry (16 -> 16, stride 1) on a small ragged volume
+
+
+def emulate_split(x, wf, sh, drop=(), halo_col=None, tap_shift=None, chan_swap=False):
+    """A split-operand stride-1 conv in numpy: every product a b as the six bf16 cross terms (exact in fp32),
+    accumulated in fp32 tap by tap, then relu(acc + shift) in fp32.  Defects: `drop` leaves out cross terms;
+    `halo_col` stages the input column x == halo_col with its first piece only; `tap_shift` = tap index whose input
+    is read one voxel off in x; `chan_swap` stages input channels 0 and 1 swapped."""
+    ci, D, H, W = x.shape
+    xs = x.copy()
+    if chan_swap:
+        xs[[0, 1]] = xs[[1, 0]]
+    a = list(P.split3(xs))
+    if halo_col is not None:
+        for p in (1, 2):
+            a[p] = a[p].copy()
+            a[p][..., halo_col] = 0
+    ap = [np.pad(t, ((0, 0), (1, 1), (1, 1), (1, 2))) for t in a]
+    b = P.split3(wf)
+    acc = np.zeros((wf.shape[0], D, H, W), np.float32)
+    for tap in range(27):
+        kz, ky, kx = np.unravel_index(tap, (3, 3, 3))
+        dx = kx + (1 if tap == tap_shift else 0)
+        for term in TERMS:
+            if term in drop:
+                continue
+            ia, ib = int(term[1]) - 1, int(term[3]) - 1
+            xa = ap[ia][:, kz:kz + D, ky:ky + H, dx:dx + W]
+            prod = np.einsum("oc,czyx->oczyx", b[ib][:, :, kz, ky, kx], xa).astype(np.float32)   # exact
+            for c in range(ci):
+                acc = (acc + prod[:, c]).astype(np.float32)
+    return np.maximum((acc + sh[:, None, None, None]).astype(np.float32), 0).astype(np.float64)
+
+
+# defect -> (emulation arguments, caught by the dense bound too).  A dropped cross term errs by 2^-18 |a b| per
+# product with random sign: at random-normal data that sits inside fp32 summation noise, only the probes pin it.
+DEFECTS = {
+    "exact": ({}, True),
+    "halo column keeps piece 1 only": (dict(halo_col=SENS_SHAPE[2] - 1), True),
+    "a2b2 dropped": (dict(drop=("a2b2",)), False),
+    "a1b3 + a3b1 dropped": (dict(drop=("a1b3", "a3b1")), False),
+    "tap shifted by one voxel": (dict(tap_shift=22), True),
+    "staged channels 0 / 1 swapped": (dict(chan_swap=True), True),
+}
+
+
+def _sens_inputs():
+    ci, co = P.GEOM[SENS_LAYER][:2]
+    rng = np.random.default_rng(11)
+    base = synthetic.random_costreg_state(seed=4)
+    wf, sh = P.folded(base, SENS_LAYER)
+    probes = [(P.lattice(ci, SENS_SHAPE, (3, 3, 3), ph, rng), wf, sh) for ph in P.phases((3, 3, 3))]
+    for r in range(P.crafted_runs(SENS_LAYER)):
+        wfc, shc = P.folded(P.crafted_state(base, r, rng), SENS_LAYER)
+        probes.append((P.crafted((ci,) + SENS_SHAPE, rng), wfc, shc))
+    # dense: random normal and heavy-tailed non-negative (as a variance volume)
+    dense = [(rng.standard_normal((ci,) + SENS_SHAPE).astype(np.float32), wf, sh),
+             (np.exp(3.0 * rng.standard_normal((ci,) + SENS_SHAPE)).astype(np.float32), wf, sh)]
+    return probes, dense
+
+
+@pytest.fixture(scope="module")
+def sens_inputs():
+    return _sens_inputs()
+
+
+@pytest.mark.parametrize("defect", list(DEFECTS))
+def test_probe_and_dense_bounds_catch_emulated_split_defects(defect, sens_inputs):
+    probes, dense = sens_inputs
+    kw, dense_catches = DEFECTS[defect]
+    worst_probe = worst_dense = 0.0
+    for x, wf, sh in probes:
+        want, bound = P.probe_want_bound(SENS_LAYER, x, None, wf, sh)
+        got = emulate_split(x, wf, sh, **kw)
+        worst_probe = max(worst_probe, float((np.abs(got - want) / bound).max()))
+    for x, wf, sh in dense:
+        ref, bound = P.dense_ref_bound(SENS_LAYER, x, None, wf, sh)
+        got = emulate_split(x, wf, sh, **kw)
+        worst_dense = max(worst_dense, float((np.abs(got - ref) / bound).max()))
+    print(f"{defect}: probe {worst_probe:.3g} x bound, dense {worst_dense:.3g} x bound")
+    if defect == "exact":
+        assert worst_probe <= 1.0 and worst_dense <= 1.0, (worst_probe, worst_dense)
+    else:
+        assert worst_probe > 1.0, worst_probe
+        if dense_catches:
+            assert worst_dense > 1.0, worst_dense
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# every kernel form has a probe case
+# ---------------------------------------------------------------------------------------------------------------
+CONV_SOURCES = ("conv3d_direct.hip", "conv3d_mfma.hip", "conv3d_mfma16.hip", "conv3d_small.hip",
+                "conv_winograd.hip", "conv0_split.hip", "conv11_prob.hip")
+
+
+def test_every_conv_instantiation_and_kernel_has_a_probe_case():
+    inst, kern = set(), set()
+    for name in CONV_SOURCES:
+        src = _read(name)
+        for m in re.finditer(r"\b(run_\w+)\s*<((?:[^<>;(]|<[^<>;(]*>)*)>\s*\(", src):
+            args = re.sub(r"\s+", "", m.group(2))
+            if re.search(r"\b(CIN|COUT|S|BZ|BY|BX|KW|CPT|STRIDE|DECONV|RELU|SKIP)\b", args):
+                continue   # a launcher forwarding its own template parameters, not an instantiation
+            inst.add(f"{m.group(1)}<{args}>")
+        kern |= set(re.findall(r"\b(\w+_kernel)\s*(?:<[^<>;]*>)?\s*<<<", src))
+    assert inst, "no run_*<...> instantiation found: the parser no longer matches the sources"
+    assert not inst - set(INSTANTIATIONS), f"instantiations without a probe case: {sorted(inst - set(INSTANTIATIONS))}"
+    assert not kern - set(KERNELS), f"kernels without a probe case: {sorted(kern - set(KERNELS))}"
+    assert not set(INSTANTIATIONS) - inst, f"stale entries: {sorted(set(INSTANTIATIONS) - inst)}"
+    assert not set(KERNELS) - kern, f"stale entries: {sorted(set(KERNELS) - kern)}"
+    assert set(INSTANTIATIONS.values()) | set(KERNELS.values()) <= set(CASES)
+
+
+def test_probe_cases_set_only_switches_options_reads():
+    names = set(re.findall(r'"(MVS_\w+)"', _read("mvs_host.hip")))
+    for name, case in CASES.items():
+        assert set(case["env"]) <= names, (name, case["env"])
+        assert case["storages"] in (("f32",), ("f16", "bf16"))
