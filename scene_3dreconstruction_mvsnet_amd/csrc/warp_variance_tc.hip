@@ -177,7 +177,7 @@ __device__ __forceinline__ void gather_tap_buf(f32x4 (&t)[CPT / 4], __amdgpu_buf
 // soffset the compiler inserts the wait state itself.
 template <int DT, int CPT, int NTS>
 __device__ __forceinline__ void store_voxel_buf(__amdgpu_buffer_rsrc_t rs, unsigned voff, const f32x2 (&o)[CPT / 2]) {
-    constexpr int aux = NTS ? 2 : 0;   // nt: measured slower (0.253 vs 0.233 ms), kept as MVS_WARP_NT=1
+    constexpr int aux = NTS ? 2 : 0;   // nt: measured slower (0.253 vs 0.233 ms); every launch passes NTS = 0, no switch selects it
     if constexpr (DT == MVS_F32) {
 #pragma unroll
         for (int i = 0; i < CPT / 4; ++i)

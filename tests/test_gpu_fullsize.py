@@ -128,9 +128,10 @@ def test_cfg2_maps_match_the_reference_fixture(cfg2):
 def test_cfg2_two_maps_in_flight_are_bit_identical_to_one(cfg2, storage):
     """bench.py's `value` mode: two maps in flight on two HIP streams, each with its own workspace.  Every map must be
     the single-stream map bit for bit -- kernels of one map run BESIDE kernels of the other on the same CUs.  (Round 4:
-    a packed-fp32 instruction of the warp kernel whose destination aliased its op_sel-swizzled weight operand gave a
-    wrong 16-lane pass now and then, and only beside a bf16-MFMA kernel of the other stream; single-stream parity
-    tests cannot see that.)  Two host threads, two different problems, the bench size."""
+    a packed-fp32 instruction of the warp kernel, written as inline asm with an op_sel-swizzled weight operand, gave a
+    wrong 16-lane pass now and then, and only beside a bf16-MFMA kernel of the other stream; cause unpinned -- an
+    aliasing of destination and weight operand and a missing wait state were both ruled out, see the round-4 note in
+    csrc/warp_variance_tc.hip; single-stream parity tests cannot see that.)  Two host threads, two different problems, the bench size."""
     import threading
     code = _lib.dtype_code(storage)
     c = synthetic.CONFIGS["cfg2"]

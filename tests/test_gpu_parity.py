@@ -783,7 +783,8 @@ def test_two_ranks_gather_over_rccl_and_bench_self_launch():
     (5, 40, 56, 24, dict(yaw_deg=2.5)),                    # rotated rig: cells change often, ragged last block
 ])
 def test_tap_cache_kernel_is_bit_identical_to_the_plain_kernel(tmp_path, N, h, w, D, kw):
-    """warp_variance_tc2 (taps cached across depth, zero-weight views skipped per wave, lean projection) against the
+    """warp_variance_tc2 (taps cached across depth and re-gathered when a view's 2x2 cell changes, lean projection shared
+    by DPP across the lanes of a pixel; every view is blended at every step, none is skipped) against the
     plain gather kernel (MVS_WARP_TC=0, read once per process -> child process): same taps, same weights, same fma
     nesting, so the volumes must be EQUAL, not close."""
     import os
