@@ -37,7 +37,9 @@ extern "C" {
  * A packed blob (mvs_pack_weights / mvs_pack_feature_weights) is valid ONLY for the library version that produced it:
  * never cache one across builds -- re-pack from the state_dict (4 MB, milliseconds).
  * Added within version 2, without a bump (additive; packed blobs unchanged): mvs_depth_infer_views,
- * mvs_query_metrics_workspace, mvs_depth_metrics, mvs_warp_variance_backward, mvs_softargmin_backward. */
+ * mvs_query_metrics_workspace, mvs_depth_metrics, mvs_warp_variance_backward, mvs_softargmin_backward,
+ * mvs_query_conv3d_train_workspace, mvs_conv3d_train_forward, mvs_conv3d_train_backward_data,
+ * mvs_conv3d_train_backward_weight. */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {
@@ -280,6 +282,42 @@ int mvs_warp_variance_backward(const float* feats, const float* rt, const float*
                                float* grad_feats, int N, int C, int D, int h, int w, void* stream);
 int mvs_softargmin_backward(const float* cost, const float* depth_values, const float* grad_depth,
                             float* grad_cost, int D, int h, int w, void* stream);
+
+/* ---- Training: CostRegNet's 3x3x3 convolutions in their raw form (no BatchNorm folded in, no ReLU), fp32 in and fp32
+ * accumulate on the exact-fp32 matrix instruction (csrc/train_conv3d.hip).  Replace the nn.Conv3d of
+ * models/module.py:26-33 (ConvBnReLU3D.conv) and the nn.Conv3d / nn.ConvTranspose3d of models/mvsnet.py:36-62 (conv0 ..
+ * conv6, conv7 / conv9 / conv11 [0], prob), and their autograd backward; BatchNorm3d and ReLU stay with the caller.
+ *
+ * Volumes are CHANNELS-LAST per batch item, [D][H][W][C] fp32 (torch's channels_last_3d of a [1,C,D,H,W] tensor; a
+ * 1-channel volume is a plain [D][H][W]) and aligned to min(C, 4) floats.  Weights are the reference tensors as they
+ * live on the device, [Cout][Cin][3][3][3]; nothing is packed or cached, so a weight update needs no call.
+ * Cin, Cout, D, H, W, stride always describe the CONVOLUTION: x is [D][H][W][Cin], y is [D/stride][H/stride][W/stride][Cout].
+ * (Cin, Cout, stride) must be a CostRegNet layer: stride 1 (32,8) (16,16) (32,32) (64,64) (8,1); stride 2 (8,16)
+ * (16,32) (32,64).  D, H, W >= 1, even for stride 2, and D*H*W*max(Cin,Cout) < 2^31; anything else is
+ * MVS_ERR_BAD_SHAPE and nothing is enqueued.
+ *
+ * ConvTranspose3d(k=3, s=2, p=1, output_padding=1) with weight [Cin_T][Cout_T][3][3][3] is the adjoint of the stride-2
+ * conv with Cin = Cout_T, Cout = Cin_T and THE SAME weight tensor: its forward is mvs_conv3d_train_backward_data
+ * (gy = its input), its data gradient mvs_conv3d_train_forward (x = the gradient of its output), its weight gradient
+ * mvs_conv3d_train_backward_weight (x = the gradient of its output, gy = its input).
+ *
+ * mvs_conv3d_train_forward: y[co][o] = bias[co] + sum_{ci,tap} w[co][ci][tap] x[ci][stride*o + tap - 1], zero padding.
+ *     bias may be NULL.  flip_transpose = 1 (stride 1 only): w is [Cin][Cout][27] and is read with the taps reversed
+ *     and the channels transposed -- the data gradient of the stride-1 conv (Cout -> Cin) that owns w.
+ * mvs_conv3d_train_backward_data: gx [D][H][W][Cin] from gy [D/s][H/s][W/s][Cout]; every voxel of gx is written.
+ * mvs_conv3d_train_backward_weight: gw[co][ci][tap] = sum_o gy[co][o] x[ci][stride*o + tap - 1] in the layout of w, and,
+ *     when gbias != NULL, gbias[co] = sum_o gy[co][o].  Split-K into per-block partial sums in `workspace`
+ *     (>= mvs_query_conv3d_train_workspace bytes, 256-byte aligned, else MVS_ERR_WORKSPACE) and a second kernel that
+ *     adds them in a fixed order: no float atomics, bit-identical from run to run and stream to stream.
+ * None allocates or synchronises. */
+int mvs_query_conv3d_train_workspace(int Cin, int Cout, int D, int H, int W, int stride, size_t* bytes);
+int mvs_conv3d_train_forward(const float* x, const float* w, const float* bias, float* y, int Cin, int Cout, int D,
+                             int H, int W, int stride, int flip_transpose, void* stream);
+int mvs_conv3d_train_backward_data(const float* gy, const float* w, float* gx, int Cin, int Cout, int D, int H, int W,
+                                   int stride, void* stream);
+int mvs_conv3d_train_backward_weight(const float* x, const float* gy, float* gw, float* gbias, void* workspace,
+                                     size_t workspace_bytes, int Cin, int Cout, int D, int H, int W, int stride,
+                                     void* stream);
 
 #ifdef __cplusplus
 }

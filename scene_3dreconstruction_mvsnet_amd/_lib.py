@@ -49,6 +49,8 @@ SYMBOLS = (
     "mvs_feature_net_fmt", "mvs_forward_images_fmt", "mvs_depth_infer_views",
     "mvs_query_metrics_workspace", "mvs_depth_metrics",
     "mvs_warp_variance_backward", "mvs_softargmin_backward",
+    "mvs_query_conv3d_train_workspace", "mvs_conv3d_train_forward", "mvs_conv3d_train_backward_data",
+    "mvs_conv3d_train_backward_weight",
 )
 
 # mvs_image_format (include/mvs_abi.h)
@@ -123,6 +125,10 @@ def load():
         lib.mvs_depth_metrics.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]
         lib.mvs_warp_variance_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]
         lib.mvs_softargmin_backward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]
+        lib.mvs_query_conv3d_train_workspace.argtypes = [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_sz)]
+        lib.mvs_conv3d_train_forward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]
+        lib.mvs_conv3d_train_backward_data.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
+        lib.mvs_conv3d_train_backward_weight.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]
         for name in SYMBOLS:
             if name not in ("mvs_last_error_string",):
                 getattr(lib, name).restype = _i
@@ -326,6 +332,67 @@ def softargmin_backward(cost, depth_values, grad_depth):
     check(load().mvs_softargmin_backward(cost.data_ptr(), _dev_f32(depth_values, "depth_values").data_ptr(),
                                          grad_depth.data_ptr(), gc.data_ptr(), D, h, w, _stream(cost.device)))
     return gc
+
+
+# ---- training convolutions (csrc/train_conv3d.hip).  Volumes are channels-last [D,H,W,C] float32 tensors of one batch
+# item; Cin, Cout, D, H, W, stride describe the convolution (x [D,H,W,Cin] -> y [D/s,H/s,W/s,Cout]).
+def conv3d_train_workspace_bytes(Cin, Cout, D, H, W, stride) -> int:
+    n = _sz(0)
+    check(load().mvs_query_conv3d_train_workspace(Cin, Cout, D, H, W, stride, ctypes.byref(n)))
+    return int(n.value)
+
+
+def _cl_volume(t, name):
+    t = _dev_f32(t, name)
+    if t.dim() != 4:
+        raise RuntimeError(f"{name} must be a channels-last volume [D,H,W,C], got {tuple(t.shape)}")
+    return t
+
+
+def conv3d_train_forward(x, w, bias, stride, flip_transpose=False):
+    """x [D,H,W,Cin], w [Cout,Cin,3,3,3] ([Cin,Cout,3,3,3] with flip_transpose) -> y [D/s,H/s,W/s,Cout]."""
+    x, w = _cl_volume(x, "x"), _dev_f32(w, "weight")
+    D, H, W, Cin = x.shape
+    Cout = w.shape[1] if flip_transpose else w.shape[0]
+    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3) or (w.shape[0] if flip_transpose else w.shape[1]) != Cin:
+        raise RuntimeError(f"weight {tuple(w.shape)} does not fit a 3x3x3 convolution of {Cin} channels")
+    if bias is not None:
+        bias = _dev_f32(bias, "bias")
+    y = torch.empty((D // stride, H // stride, W // stride, Cout), dtype=torch.float32, device=x.device)
+    check(load().mvs_conv3d_train_forward(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
+                                          y.data_ptr(), Cin, Cout, D, H, W, stride, int(bool(flip_transpose)),
+                                          _stream(x.device)))
+    return y
+
+
+def conv3d_train_backward_data(gy, w, stride):
+    """gy [D/s,H/s,W/s,Cout], w [Cout,Cin,3,3,3] -> gx [D,H,W,Cin] (every voxel written)."""
+    gy, w = _cl_volume(gy, "gy"), _dev_f32(w, "weight")
+    Do, Ho, Wo, Cout = gy.shape
+    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3) or w.shape[0] != Cout:
+        raise RuntimeError(f"weight {tuple(w.shape)} does not fit a gradient of {Cout} channels")
+    Cin = w.shape[1]
+    D, H, W = Do * stride, Ho * stride, Wo * stride
+    gx = torch.empty((D, H, W, Cin), dtype=torch.float32, device=gy.device)
+    check(load().mvs_conv3d_train_backward_data(gy.data_ptr(), w.data_ptr(), gx.data_ptr(), Cin, Cout, D, H, W,
+                                                stride, _stream(gy.device)))
+    return gx
+
+
+def conv3d_train_backward_weight(x, gy, stride, with_bias=False):
+    """x [D,H,W,Cin], gy [D/s,H/s,W/s,Cout] -> gw [Cout,Cin,3,3,3] (and gbias [Cout] with with_bias)."""
+    x, gy = _cl_volume(x, "x"), _cl_volume(gy, "gy")
+    D, H, W, Cin = x.shape
+    Cout = gy.shape[3]
+    if tuple(gy.shape[:3]) != (D // stride, H // stride, W // stride):
+        raise RuntimeError(f"gy {tuple(gy.shape)} does not fit x {tuple(x.shape)} at stride {stride}")
+    ws = torch.empty(conv3d_train_workspace_bytes(Cin, Cout, D, H, W, stride), dtype=torch.uint8, device=x.device)
+    gw = torch.empty((Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    gb = torch.empty((Cout,), dtype=torch.float32, device=x.device) if with_bias else None
+    check(load().mvs_conv3d_train_backward_weight(x.data_ptr(), gy.data_ptr(), gw.data_ptr(),
+                                                  None if gb is None else gb.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                  Cin, Cout, D, H, W, stride, _stream(x.device)))
+    return (gw, gb) if with_bias else gw
 
 
 def depth_infer(feats, proj, depth_values, blob, workspace, depth_out, conf_out, dtype=MVS_F32):

@@ -1,14 +1,16 @@
 """Training path: the reference's `train.py --mode train` step on the MI355X (models/mvsnet.py:91-244, train.py:241-298).
 
 The cost volume and the soft-argmin -- the parts of a training step whose torch autograd graph is largest -- run as
-HIP kernels with hand-written adjoints (csrc/train_backward.hip); FeatureNet and CostRegNet run in torch (MIOpen)
-with autograd:
+HIP kernels with hand-written adjoints (csrc/train_backward.hip); FeatureNet runs in torch (MIOpen) with autograd,
+and so does CostRegNet unless `costreg_impl = "hip"` puts its convolutions on csrc/train_conv3d.hip:
 
   cost_volume(feats, proj_matrices, depth_values)   mvs_relative_proj + mvs_warp_variance (fp32) forward,
                                                     mvs_warp_variance_backward; saves only its inputs, rt and the
                                                     depth values (no volume)
   soft_argmin(cost, depth_values)                   mvs_softargmin_conf forward, mvs_softargmin_backward; only the
                                                     depth is differentiable (the confidence is no_grad, mvsnet.py:213)
+  conv3d(x, weight, bias, stride)                   mvs_conv3d_train_forward / _backward_data / _backward_weight: CostRegNet's
+  conv_transpose3d(x, weight)                       3x3x3 convolutions, raw (BatchNorm3d and ReLU stay in torch)
   mvsnet_loss(depth_est, depth_gt, mask)            masked-mean smooth-L1 (mvsnet.py:242-244) without boolean
                                                     indexing, so it never synchronises
   TrainableMVSNet                                   MVSNet whose train-mode forward builds an autograd graph
@@ -139,12 +141,141 @@ def mvsnet_loss(depth_est, depth_gt, mask):
     return F.smooth_l1_loss(est, gt, reduction="sum") / valid.sum().to(depth_est.dtype)
 
 
+def _channels_last(t, name):
+    """Logical [B,C,D,H,W] -> the kernels' [B,D,H,W,C] (no copy when t already is channels_last_3d)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} needs CUDA(ROCm) tensors: the training convolutions have no CPU implementation "
+                           f"(got {t.device})")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be float32 (got {t.dtype})")
+    if t.dim() != 5:
+        raise RuntimeError(f"{name} must be [B,C,D,H,W], got {tuple(t.shape)}")
+    return t.detach().permute(0, 2, 3, 4, 1).contiguous()
+
+
+def _logical(t):
+    """The kernels' [B,D,H,W,C] -> logical [B,C,D,H,W] in torch's channels_last_3d memory format (a view)."""
+    return t.permute(0, 4, 1, 2, 3)
+
+
+class _Conv3d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride):
+        with torch.cuda.device(x.device):
+            xc = _channels_last(x, "conv3d input")
+            w = _lib._dev_f32(weight.detach(), "weight")
+            b = None if bias is None else _lib._dev_f32(bias.detach(), "bias")
+            y = torch.stack([_lib.conv3d_train_forward(xc[i], w, b, stride) for i in range(xc.shape[0])])
+        ctx.save_for_backward(xc, w)
+        ctx.stride, ctx.has_bias = stride, bias is not None
+        return _logical(y)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        xc, w = ctx.saved_tensors
+        gx = gw = gb = None
+        with torch.cuda.device(xc.device):
+            g = _channels_last(grad_y, "conv3d output gradient")
+            B = xc.shape[0]
+            if ctx.needs_input_grad[0]:
+                gx = _logical(torch.stack([_lib.conv3d_train_backward_data(g[i], w, ctx.stride) for i in range(B)]))
+            if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+                for i in range(B):
+                    r = _lib.conv3d_train_backward_weight(xc[i], g[i], ctx.stride, with_bias=ctx.has_bias)
+                    gwi, gbi = r if ctx.has_bias else (r, None)
+                    gw = gwi if gw is None else gw + gwi
+                    gb = gbi if gb is None or gbi is None else gb + gbi
+        return gx, gw, gb, None
+
+
+class _ConvTranspose3d(torch.autograd.Function):
+    """ConvTranspose3d(k=3, s=2, p=1, output_padding=1, bias=False): the adjoint of the stride-2 conv that has the same
+    weight tensor, so its forward is that conv's data gradient and its data gradient that conv's forward."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        with torch.cuda.device(x.device):
+            xc = _channels_last(x, "conv_transpose3d input")
+            w = _lib._dev_f32(weight.detach(), "weight")
+            y = torch.stack([_lib.conv3d_train_backward_data(xc[i], w, 2) for i in range(xc.shape[0])])
+        ctx.save_for_backward(xc, w)
+        return _logical(y)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        xc, w = ctx.saved_tensors
+        gx = gw = None
+        with torch.cuda.device(xc.device):
+            g = _channels_last(grad_y, "conv_transpose3d output gradient")
+            B = xc.shape[0]
+            if ctx.needs_input_grad[0]:
+                gx = _logical(torch.stack([_lib.conv3d_train_forward(g[i], w, None, 2) for i in range(B)]))
+            if ctx.needs_input_grad[1]:
+                for i in range(B):
+                    gwi = _lib.conv3d_train_backward_weight(g[i], xc[i], 2)
+                    gw = gwi if gw is None else gw + gwi
+        return gx, gw
+
+
+def conv3d(x, weight, bias=None, stride=1):
+    """nn.Conv3d(kernel_size=3, padding=1, stride=stride) with autograd on the HIP training kernels
+    (csrc/train_conv3d.hip; models/module.py:26-33, models/mvsnet.py:36-62).  x [B,Cin,D,H,W] float32 CUDA, weight
+    [Cout,Cin,3,3,3], bias [Cout] or None -> [B,Cout,D/stride,H/stride,W/stride] in channels_last_3d memory format.
+    Only CostRegNet's (Cin, Cout, stride) combinations exist; anything else raises with the library's message."""
+    _channels_last_check(x, weight, "conv3d")
+    return _Conv3d.apply(x, weight, bias, int(stride))
+
+
+def conv_transpose3d(x, weight):
+    """nn.ConvTranspose3d(kernel_size=3, stride=2, padding=1, output_padding=1, bias=False) with autograd on the HIP
+    training kernels.  x [B,Cin,D,H,W], weight [Cin,Cout,3,3,3] -> [B,Cout,2D,2H,2W] (channels_last_3d)."""
+    _channels_last_check(x, weight, "conv_transpose3d")
+    return _ConvTranspose3d.apply(x, weight)
+
+
+def _channels_last_check(x, weight, who):
+    for t, name in ((x, "input"), (weight, "weight")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who} needs CUDA(ROCm) tensors: the training convolutions have no CPU implementation "
+                               f"(got {name} on {t.device})")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{who}: {name} must be float32 (got {t.dtype})")
+    if x.dim() != 5 or weight.dim() != 5:
+        raise RuntimeError(f"{who}: input {tuple(x.shape)} must be [B,C,D,H,W] and weight {tuple(weight.shape)} 5-d")
+
+
 def _conv_bn_relu(block, x):
     return F.relu(block.bn(block.conv(x)), inplace=True)   # models/module.py:32-33
 
 
-def _costreg(cr, x):
-    """CostRegNet.forward (models/mvsnet.py:64-73) in torch, through the blocks' .conv / .bn modules."""
+def _conv_bn_relu_hip(block, x):
+    return F.relu(block.bn(conv3d(x, block.conv.weight, None, block.conv.stride[0])), inplace=True)
+
+
+def _deconv_bn_relu_hip(seq, x):
+    return F.relu(seq[1](conv_transpose3d(x, seq[0].weight)), inplace=True)   # models/mvsnet.py:47-60
+
+
+def _costreg_hip(cr, x):
+    """CostRegNet.forward with every convolution on the HIP training kernels; BatchNorm3d (train-mode statistics and
+    their backward), ReLU and the skip additions stay in torch, on channels_last_3d tensors."""
+    conv0 = _conv_bn_relu_hip(cr.conv0, x)
+    conv2 = _conv_bn_relu_hip(cr.conv2, _conv_bn_relu_hip(cr.conv1, conv0))
+    conv4 = _conv_bn_relu_hip(cr.conv4, _conv_bn_relu_hip(cr.conv3, conv2))
+    x = _conv_bn_relu_hip(cr.conv6, _conv_bn_relu_hip(cr.conv5, conv4))
+    x = conv4 + _deconv_bn_relu_hip(cr.conv7, x)
+    x = conv2 + _deconv_bn_relu_hip(cr.conv9, x)
+    x = conv0 + _deconv_bn_relu_hip(cr.conv11, x)
+    return conv3d(x, cr.prob.weight, cr.prob.bias, 1)
+
+
+def _costreg(cr, x, impl="torch"):
+    """CostRegNet.forward (models/mvsnet.py:64-73): impl "torch" through the blocks' .conv / .bn modules, "hip" with
+    the convolutions on csrc/train_conv3d.hip."""
+    if impl == "hip":
+        return _costreg_hip(cr, x)
+    if impl != "torch":
+        raise RuntimeError(f"costreg_impl must be 'torch' or 'hip', got {impl!r}")
     conv0 = _conv_bn_relu(cr.conv0, x)
     conv2 = _conv_bn_relu(cr.conv2, _conv_bn_relu(cr.conv1, conv0))
     conv4 = _conv_bn_relu(cr.conv4, _conv_bn_relu(cr.conv3, conv2))
@@ -162,7 +293,13 @@ class TrainableMVSNet(MVSNet):
     FeatureNet in torch once per view (models/mvsnet.py:125: per-view BN batch statistics, running statistics
     updated N times), cost_volume, CostRegNet in torch, soft_argmin.  The HIP inference blobs are re-packed from
     the parameters after every train-mode forward (BN statistics) and whenever a parameter's `_version` changes
-    (optimizer steps, MVSNet._param_versions)."""
+    (optimizer steps, MVSNet._param_versions).
+
+    costreg_impl: "torch" (default) runs CostRegNet's convolutions on torch's backend; "hip" on the library's training
+    kernels (conv3d / conv_transpose3d above), with BatchNorm3d and ReLU still in torch.  Parameters, state_dict keys
+    and the eval path do not depend on it."""
+
+    costreg_impl = "torch"
 
     def forward(self, imgs, proj_matrices, depth_values):
         if not self.training:
@@ -176,6 +313,8 @@ class TrainableMVSNet(MVSNet):
         if _lib.dtype_code(self.storage_dtype) != _lib.MVS_F32:
             raise RuntimeError(f"training needs storage_dtype 'f32' (got {self.storage_dtype!r}): 16-bit training "
                                "is not implemented")
+        if self.costreg_impl not in ("torch", "hip"):
+            raise RuntimeError(f"costreg_impl must be 'torch' or 'hip', got {self.costreg_impl!r}")
         if not imgs.is_cuda:
             raise RuntimeError("MVSNet.forward needs CUDA(ROCm) tensors: the depth path has no CPU "
                                "implementation (got imgs on {})".format(imgs.device))
@@ -197,7 +336,7 @@ class TrainableMVSNet(MVSNet):
             dv = depth_values.to(device=device, dtype=torch.float32)
             volume = cost_volume(feats, proj, dv)
             # step 3. cost regularisation (models/mvsnet.py:180, 192)
-            cost = _costreg(self.cost_regularization, volume).squeeze(1)
+            cost = _costreg(self.cost_regularization, volume, self.costreg_impl).squeeze(1)
             # step 4. soft-argmin and photometric confidence (models/mvsnet.py:193-218)
             depth, conf = soft_argmin(cost, dv)
         return {"depth": depth, "photometric_confidence": conf}

@@ -7,9 +7,14 @@
   train_step    one whole optimisation step: training.train_sample on TrainableMVSNet against the same step with
                 every stage in torch (FeatureNet, the torch cost volume, CostRegNet, softmax + depth regression)
   soft_argmin   forward + backward of training.soft_argmin against torch softmax + depth regression
+  costreg       forward + backward of CostRegNet alone (training._costreg) at the training shape, costreg_impl "torch"
+                and "hip" alternating in the same process on the same seeded volume and upstream gradient; also
+                BatchNorm3d forward + backward on a contiguous NCDHW and on a channels_last_3d volume
+  train_step    (part of the same key) additionally times train_sample with costreg_impl = "hip"
 
 and the peak torch.cuda.max_memory_allocated of each.  Prints one JSON document (and writes it to --out).
-    python tools/time_train_step.py [--warmup 3] [--iters 10] [--only cost_volume,train_step,soft_argmin]
+    python tools/time_train_step.py [--warmup 3] [--iters 10] [--only cost_volume,train_step,soft_argmin,costreg]
+The costreg and train_step parts are also written to profiles/train_costreg_timing.json.
 """
 import argparse
 import json
@@ -99,7 +104,37 @@ def timed(fn, warmup, iters):
         b.synchronize()
         times.append(a.elapsed_time(b))
     peak = torch.cuda.max_memory_allocated(DEV) - base
-    return {"median_ms": float(np.median(times)), "min_ms": float(np.min(times)), "peak_bytes": int(peak)}
+    return {"median_ms": float(np.median(times)), "min_ms": float(np.min(times)), "max_ms": float(np.max(times)),
+            "peak_bytes": int(peak)}
+
+
+def timed_alternating(fns, warmup, iters):
+    """The same figures for several callables run in turn (a, b, a, b, ...) in this process, so that clock and
+    allocator state are shared; the peak is taken per callable in a pass of its own at the end."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(iters):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[k].append(a.elapsed_time(b))
+    out = {}
+    for k, fn in fns.items():
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats(DEV)
+        base = torch.cuda.memory_allocated(DEV)
+        fn()
+        torch.cuda.synchronize()
+        out[k] = {"median_ms": float(np.median(times[k])), "min_ms": float(np.min(times[k])),
+                  "max_ms": float(np.max(times[k])), "peak_bytes": int(torch.cuda.max_memory_allocated(DEV) - base)}
+    return out
 
 
 def make_sample():
@@ -165,6 +200,66 @@ def bench_train_step(sample, warmup, iters):
             out[name] = timed(lambda: torch_train_step(model, opt, sample), warmup, iters)
         del model, opt
         torch.cuda.empty_cache()
+    # the same step with CostRegNet's convolutions in torch and in HIP, alternating
+    steps = {}
+    for impl in ("torch", "hip"):
+        torch.manual_seed(0)
+        model = training.TrainableMVSNet(refine=False).to(DEV)
+        model.costreg_impl = impl
+        opt = torch.optim.Adam(model.parameters(), lr=1e-3, betas=(0.9, 0.999), weight_decay=0.0)
+        steps[f"costreg_{impl}"] = (lambda m=model, o=opt: training.train_sample(m, o, sample))
+    out.update(timed_alternating(steps, warmup, iters))
+    a, b = out["costreg_torch"], out["costreg_hip"]
+    out["hip_median_not_above_torch_median"] = bool(b["median_ms"] <= a["median_ms"])
+    return out
+
+
+# CostRegNet's layers as convolutions: (Cin, Cout, level of the volume the 27-tap sum runs over)
+_COSTREG_CONVS = ((32, 8, 0), (8, 16, 1), (16, 16, 1), (16, 32, 2), (32, 32, 2), (32, 64, 3), (64, 64, 3),
+                  (64, 32, 3), (32, 16, 2), (16, 8, 1), (8, 1, 0))
+
+
+def costreg_gflop():
+    """Forward + data gradient + weight gradient of the eleven 3x3x3 layers at the training shape, 2 FLOP per MAC."""
+    d, h, w = D, H // 4, W // 4
+    mac = sum(27 * ci * co * (d >> lv) * (h >> lv) * (w >> lv) for ci, co, lv in _COSTREG_CONVS)
+    return {"forward_gmac": mac / 1e9, "conv0_forward_gmac": 27 * 32 * 8 * d * h * w / 1e9,
+            "fwd_dgrad_wgrad_gflop": 3 * 2 * mac / 1e9, "ms_at_155_tflops": 3 * 2 * mac / 155e12 * 1e3}
+
+
+def bench_costreg(warmup, iters):
+    d, h, w = D, H // 4, W // 4
+    volume = torch.randn((1, 32, d, h, w), generator=torch.Generator().manual_seed(0)).to(DEV).requires_grad_(True)
+    g = torch.randn((1, 1, d, h, w), generator=torch.Generator().manual_seed(1)).to(DEV)
+    torch.manual_seed(0)
+    cr = training.TrainableMVSNet(refine=False).to(DEV).train().cost_regularization
+
+    def run(impl):
+        def step():
+            volume.grad = None
+            cr.zero_grad(set_to_none=True)
+            training._costreg(cr, volume, impl).backward(g)
+        return step
+
+    out = timed_alternating({"torch": run("torch"), "hip": run("hip")}, warmup, iters)
+    out["flop"] = costreg_gflop()
+    t, hp = out["torch"], out["hip"]
+    out["speedup_median"] = t["median_ms"] / hp["median_ms"]
+    out["hip_below_torch_and_ranges_disjoint"] = bool(hp["median_ms"] < t["median_ms"] and hp["max_ms"] < t["min_ms"])
+    # BatchNorm3d (train mode) forward + backward on conv0's output, the two memory formats
+    bn = torch.nn.BatchNorm3d(8).to(DEV).train()
+    y = torch.randn((1, 8, d, h, w), generator=torch.Generator().manual_seed(2)).to(DEV)
+    variants = {"bn_ncdhw": y.clone().requires_grad_(True),
+                "bn_channels_last_3d": y.clone(memory_format=torch.channels_last_3d).requires_grad_(True)}
+    gy = {k: torch.randn_like(v) for k, v in variants.items()}
+
+    def bn_run(k):
+        def step():
+            variants[k].grad = None
+            bn(variants[k]).backward(gy[k])
+        return step
+
+    out.update(timed_alternating({k: bn_run(k) for k in variants}, warmup, iters))
     return out
 
 
@@ -188,11 +283,17 @@ def main():
             res[part] = bench_soft_argmin(args.warmup, args.iters)
         elif part == "train_step":
             res[part] = bench_train_step(sample, args.warmup, args.iters)
+        elif part == "costreg":
+            res[part] = bench_costreg(args.warmup, args.iters)
         else:
             raise SystemExit(f"unknown part {part!r}")
     res["wall_s"] = round(time.time() - t0, 1)
     text = json.dumps(res, indent=1)
     print(text)
+    if "costreg" in res or "train_step" in res:
+        keep = {k: v for k, v in res.items() if k not in ("cost_volume", "soft_argmin")}
+        with open(os.path.join(REPO, "profiles", "train_costreg_timing.json"), "w") as f:
+            f.write(json.dumps(keep, indent=1) + "\n")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
