@@ -39,7 +39,7 @@ extern "C" {
  * Added within version 2, without a bump (additive; packed blobs unchanged): mvs_depth_infer_views,
  * mvs_query_metrics_workspace, mvs_depth_metrics, mvs_warp_variance_backward, mvs_softargmin_backward,
  * mvs_query_conv3d_train_workspace, mvs_conv3d_train_forward, mvs_conv3d_train_backward_data,
- * mvs_conv3d_train_backward_weight. */
+ * mvs_conv3d_train_backward_weight, mvs_feature_conv01_fmt. */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {
@@ -216,6 +216,12 @@ int mvs_filter_depth(const float* depth, const float* conf, const float* ref_mat
  *   FeatureNet.forward returns them); workspace of mvs_query_feature_workspace(N,H,W) bytes.
  * mvs_feature_layer: one layer (0..6 = conv0..conv6, 7 = feature) for per-layer parity tests;
  *   x = NCHW image [N][3][Hi][Wi] for layer 0, else C8-planar [Cin/8][N][Hi][Wi][8]; y C8-planar.
+ * mvs_feature_conv01_fmt: conv0 + conv1 as the ONE fused kernel that mvs_feature_net / mvs_forward_images run first
+ *   (mvs_feature_layer 0 and 1 are the two separate kernels of MVS_FEAT_SPLIT01=1), for parity tests and per-kernel
+ *   timing; imgs in any mvs_image_format -> y C8-planar [1][N][H][W][8].  Same refusals as mvs_feature_net_fmt
+ *   (NULL, format, N*H*W*8 >= 2^31, H or W < 4); nothing is enqueued on a refusal.
+ * FeatureNet promises nothing for non-finite pixels: the k5 layers' padded 26th tap multiplies a voxel by a packed
+ *   weight of exactly 0, which turns an infinite activation into NaN where the reference keeps the infinity.
  * mvs_forward_images: FeatureNet + mvs_depth_infer with the features handed over in the private
  *   C8-planar layout (no NCHW round trip); H, W multiples of 32; workspace of
  *   mvs_query_forward_workspace(N,H,W,D,dtype) bytes. */
@@ -226,6 +232,8 @@ int mvs_pack_feature_weights(const float* const* conv_weights, const float* cons
 int mvs_query_feature_workspace(int N, int H, int W, size_t* bytes);
 int mvs_feature_layer(int layer, const float* x, float* y, const void* feature_blob, int N, int Hi, int Wi,
                       void* stream);
+int mvs_feature_conv01_fmt(const void* imgs, int image_format, float* y, const void* feature_blob, int N, int H, int W,
+                           void* stream);
 int mvs_feature_net(const float* imgs, const void* feature_blob, float* feats_out, void* workspace,
                     size_t workspace_bytes, int N, int H, int W, void* stream);
 int mvs_query_forward_workspace(int N, int H, int W, int D, int dtype, size_t* bytes);

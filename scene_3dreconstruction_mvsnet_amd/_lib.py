@@ -50,7 +50,7 @@ SYMBOLS = (
     "mvs_query_metrics_workspace", "mvs_depth_metrics",
     "mvs_warp_variance_backward", "mvs_softargmin_backward",
     "mvs_query_conv3d_train_workspace", "mvs_conv3d_train_forward", "mvs_conv3d_train_backward_data",
-    "mvs_conv3d_train_backward_weight",
+    "mvs_conv3d_train_backward_weight", "mvs_feature_conv01_fmt",
 )
 
 # mvs_image_format (include/mvs_abi.h)
@@ -110,6 +110,7 @@ def load():
                                                  ctypes.c_float, _vp, _sz]
         lib.mvs_query_feature_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_sz)]
         lib.mvs_feature_layer.argtypes = [_i, _vp, _vp, _vp, _i, _i, _i, _vp]
+        lib.mvs_feature_conv01_fmt.argtypes = [_vp, _i, _vp, _vp, _i, _i, _i, _vp]
         lib.mvs_feature_net.argtypes = [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]
         lib.mvs_query_forward_workspace.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(_sz)]
         lib.mvs_forward_images.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
@@ -622,6 +623,16 @@ def _image_arg(imgs, what):
     if imgs.shape[1] != 3:
         raise RuntimeError(f"{what} wants [N,3,H,W] images, got {tuple(imgs.shape)}")
     return imgs, MVS_IMG_F32_CHW, imgs.shape[0], imgs.shape[2], imgs.shape[3]
+
+
+def feature_conv01(imgs, fblob):
+    """conv0 + conv1 of FeatureNet as the one fused kernel the net runs: imgs [N,3,H,W] fp32 (or uint8, see
+    _image_arg) -> C8-planar [1,N,H,W,8].  For parity tests and per-kernel timing."""
+    imgs, fmt, N, H, W = _image_arg(imgs, "feature_conv01")
+    y = torch.empty((1, N, H, W, 8), dtype=torch.float32, device=imgs.device)
+    check(load().mvs_feature_conv01_fmt(imgs.data_ptr(), fmt, y.data_ptr(), fblob.data_ptr(), N, H, W,
+                                        _stream(imgs.device)))
+    return y
 
 
 def feature_net(imgs, fblob, workspace=None, out=None):

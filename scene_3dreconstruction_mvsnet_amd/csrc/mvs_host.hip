@@ -467,6 +467,16 @@ int mvs_feature_layer(int layer, const float* x, float* y, const void* feature_b
                                 static_cast<hipStream_t>(stream));
 }
 
+int mvs_feature_conv01_fmt(const void* imgs, int image_format, float* y, const void* feature_blob, int N, int H, int W,
+                           void* stream) {
+    if (!imgs || !y || !feature_blob) return fail(MVS_ERR_NULL, "mvs_feature_conv01_fmt: NULL argument");
+    if (image_format < MVS_IMG_F32_CHW || image_format > MVS_IMG_U8_HWC)
+        return fail(MVS_ERR_BAD_DTYPE, "mvs_feature_conv01_fmt: unknown image format %d", image_format);
+    if (int st = check_image_dims(N, H, W)) return st;
+    return launch_feature_conv01(imgs, image_format, y, static_cast<const float*>(feature_blob), N, H, W,
+                                 static_cast<hipStream_t>(stream));
+}
+
 int mvs_feature_net(const float* imgs, const void* feature_blob, float* feats_out, void* workspace,
                     size_t workspace_bytes, int N, int H, int W, void* stream) {
     return mvs_feature_net_fmt(imgs, MVS_IMG_F32_CHW, feature_blob, feats_out, workspace, workspace_bytes, N, H, W, stream);

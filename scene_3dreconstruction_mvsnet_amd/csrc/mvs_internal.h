@@ -183,6 +183,8 @@ inline FeatWorkspace feat_workspace_layout(int N, int H, int W) {
 bool feat16_gather();
 int launch_feature_layer(int l, const float* x, float* y, const float* blob, int N, int Hi, int Wi,
                          hipStream_t s);
+// fused conv0 + conv1 (what launch_feature_net_c8 runs first): images -> C8-planar [1][N][H][W][8]
+int launch_feature_conv01(const void* imgs, int fmt, float* y, const float* blob, int N, int H, int W, hipStream_t s);
 int launch_feature_net_c8(const void* imgs, int fmt, const float* blob, float* feats_c8, float* bufA, float* bufB,
                           int N, int H, int W, hipStream_t s);   // fmt: mvs_image_format
 int launch_c8_to_nchw(const float* in, float* out, int N, int C, int h, int w, hipStream_t s);
