@@ -39,7 +39,8 @@ extern "C" {
  * Added within version 2, without a bump (additive; packed blobs unchanged): mvs_depth_infer_views,
  * mvs_query_metrics_workspace, mvs_depth_metrics, mvs_warp_variance_backward, mvs_softargmin_backward,
  * mvs_query_conv3d_train_workspace, mvs_conv3d_train_forward, mvs_conv3d_train_backward_data,
- * mvs_conv3d_train_backward_weight, mvs_feature_conv01_fmt. */
+ * mvs_conv3d_train_backward_weight, mvs_feature_conv01_fmt, mvs_query_bn3d_train_workspace, mvs_bn3d_train_forward,
+ * mvs_bn3d_train_backward, mvs_volume_relayout. */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {
@@ -326,6 +327,54 @@ int mvs_conv3d_train_backward_data(const float* gy, const float* w, float* gx, i
 int mvs_conv3d_train_backward_weight(const float* x, const float* gy, float* gw, float* gbias, void* workspace,
                                      size_t workspace_bytes, int Cin, int Cout, int D, int H, int W, int stride,
                                      void* stream);
+
+/* ---- Training: BatchNorm3d with batch statistics, fused with the ReLU and the skip addition that follow it in
+ * CostRegNet, and its backward (csrc/train_bn3d.hip).  Replace, in training mode, the nn.BatchNorm3d + F.relu of
+ * models/module.py:26-33 and models/mvsnet.py:47-60, the additions of models/mvsnet.py:66-70, and their autograd
+ * backward.  With them and the convolutions above, nothing between mvs_warp_variance and mvs_softargmin_conf is left
+ * to the caller's framework during a training step.
+ *
+ * Data is channels-last [M][C] fp32: M = B*D*H*W voxels of a contiguous [B][D][H][W][C] tensor (the statistics are
+ * pooled over the batch, as nn.BatchNorm3d pools them), 16-byte aligned.  C in {8, 16, 32, 64}, M >= 2 (torch refuses
+ * one value per channel in training mode as well) and M*C < 2^31; anything else is MVS_ERR_BAD_SHAPE and nothing is
+ * enqueued.  gamma, beta, save_mean, save_invstd, grad_gamma, grad_beta, running_* are dev fp32 [C], 16-byte aligned.
+ *
+ * mvs_bn3d_train_forward:
+ *     mean_c = sum y / M;  var_c = sum (y - mean_c)^2 / M (biased);  invstd = 1 / sqrt(var + eps)   (IEEE sqrt, divide)
+ *     r = ((y - mean) * invstd) * gamma + beta, each operation rounded once;  relu != 0: r = max(r, 0)
+ *     out = r + skip when skip != NULL: the skip is added AFTER the ReLU (conv4 + conv7(x), models/mvsnet.py:66-70)
+ *     save_mean, save_invstd are written for the backward.  running_mean / running_var (both or neither):
+ *     running <- (1 - momentum) running + momentum stat, the variance in its unbiased form var M / (M - 1);
+ *     num_batches_tracked stays with the caller.
+ *   The variance is a merge of per-thread and per-block (count, mean, M2) triples: one statistics read of y, and no
+ *   mean^2 / var term in its error (tests/bn3d_ref.py derives the bound).
+ * mvs_bn3d_train_backward: with g = grad_out where r > 0 (relu != 0; r recomputed from y, save_mean, save_invstd,
+ *   gamma, beta by the forward's instruction sequence, so the mask is the sign of the forward's output bit for bit),
+ *   else 0, and xhat = (y - mean) * invstd:
+ *     grad_beta = sum g;  grad_gamma = sum g xhat;  grad_y = gamma invstd (g - grad_beta / M - xhat grad_gamma / M)
+ *   The skip's gradient is grad_out itself: no kernel.
+ * Both: per-block partial results in `workspace` (>= mvs_query_bn3d_train_workspace bytes, 256-byte aligned, else
+ * MVS_ERR_WORKSPACE) combined by a second kernel in a fixed order: no float atomics, bit-identical from run to run and
+ * stream to stream.  Forward reads y twice and skip once and writes out once; backward reads y and grad_out twice each
+ * and writes grad_y once; nothing else of size M*C is touched.  Neither allocates or synchronises.
+ *
+ * mvs_volume_relayout: a pure copy through LDS between the layouts at the cost volume's boundary, C channels (8, 16, 32
+ * or 64) by V voxels (V a positive multiple of 4, V*C < 2^31), both 16-byte aligned:
+ *     MVS_RELAYOUT_C8_TO_CHANNELS_LAST      C8-planar [C/8][V][8] (mvs_warp_variance's output) -> channels-last [V][C]
+ *     MVS_RELAYOUT_CHANNELS_LAST_TO_PLANAR  channels-last [V][C] -> planar [C][V], the NCDHW gradient that
+ *                                           mvs_warp_variance_backward reads */
+#define MVS_RELAYOUT_C8_TO_CHANNELS_LAST 0
+#define MVS_RELAYOUT_CHANNELS_LAST_TO_PLANAR 1
+int mvs_query_bn3d_train_workspace(int C, long long M, size_t* bytes);
+int mvs_bn3d_train_forward(const float* y, const float* gamma, const float* beta, const float* skip, float* out,
+                           float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                           float momentum, float eps, int relu, int C, long long M, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int mvs_bn3d_train_backward(const float* y, const float* grad_out, const float* gamma, const float* beta,
+                            const float* save_mean, const float* save_invstd, float* grad_y, float* grad_gamma,
+                            float* grad_beta, int relu, int C, long long M, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int mvs_volume_relayout(const float* src, float* dst, int C, long long V, int direction, void* stream);
 
 #ifdef __cplusplus
 }

@@ -51,6 +51,7 @@ SYMBOLS = (
     "mvs_warp_variance_backward", "mvs_softargmin_backward",
     "mvs_query_conv3d_train_workspace", "mvs_conv3d_train_forward", "mvs_conv3d_train_backward_data",
     "mvs_conv3d_train_backward_weight", "mvs_feature_conv01_fmt",
+    "mvs_query_bn3d_train_workspace", "mvs_bn3d_train_forward", "mvs_bn3d_train_backward", "mvs_volume_relayout",
 )
 
 # mvs_image_format (include/mvs_abi.h)
@@ -130,6 +131,12 @@ def load():
         lib.mvs_conv3d_train_forward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]
         lib.mvs_conv3d_train_backward_data.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
         lib.mvs_conv3d_train_backward_weight.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]
+        _ll, _f = ctypes.c_longlong, ctypes.c_float
+        lib.mvs_query_bn3d_train_workspace.argtypes = [_i, _ll, ctypes.POINTER(_sz)]
+        lib.mvs_bn3d_train_forward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _ll, _vp,
+                                               _sz, _vp]
+        lib.mvs_bn3d_train_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _vp, _sz, _vp]
+        lib.mvs_volume_relayout.argtypes = [_vp, _vp, _i, _ll, _i, _vp]
         for name in SYMBOLS:
             if name not in ("mvs_last_error_string",):
                 getattr(lib, name).restype = _i
@@ -394,6 +401,104 @@ def conv3d_train_backward_weight(x, gy, stride, with_bias=False):
                                                   None if gb is None else gb.data_ptr(), ws.data_ptr(), ws.numel(),
                                                   Cin, Cout, D, H, W, stride, _stream(x.device)))
     return (gw, gb) if with_bias else gw
+
+
+# ---- training batch-norm (csrc/train_bn3d.hip).  Data is channels-last [M, C] float32: M voxels pooled over the batch.
+def bn3d_train_workspace_bytes(C, M) -> int:
+    n = _sz(0)
+    check(load().mvs_query_bn3d_train_workspace(C, M, ctypes.byref(n)))
+    return int(n.value)
+
+
+def _cl_rows(t, name):
+    t = _dev_f32(t, name)
+    if t.dim() != 2:
+        raise RuntimeError(f"{name} must be channels-last rows [M,C], got {tuple(t.shape)}")
+    return t
+
+
+def _channel_vector(t, C, name):
+    t = _dev_f32(t, name)
+    if tuple(t.shape) != (C,):
+        raise RuntimeError(f"{name} {tuple(t.shape)} must be [{C}]")
+    return t
+
+
+def bn3d_train_forward(y, gamma, beta, skip=None, running_mean=None, running_var=None, momentum=0.1, eps=1e-5,
+                       relu=True):
+    """y [M,C], gamma, beta [C], skip [M,C] or None -> (out [M,C], save_mean [C], save_invstd [C]); out = relu(bn(y)) +
+    skip with batch statistics.  running_mean / running_var [C] (both or neither) are updated in place."""
+    y = _cl_rows(y, "y")
+    M, C = y.shape
+    gamma, beta = _channel_vector(gamma, C, "gamma"), _channel_vector(beta, C, "beta")
+    if skip is not None:
+        skip = _cl_rows(skip, "skip")
+        if skip.shape != y.shape:
+            raise RuntimeError(f"skip {tuple(skip.shape)} must be shaped like y {tuple(y.shape)}")
+    if (running_mean is None) != (running_var is None):
+        raise RuntimeError("running_mean and running_var must both be given or both be None")
+    if running_mean is not None:
+        for t, name in ((running_mean, "running_mean"), (running_var, "running_var")):
+            if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (C,) or not t.is_contiguous():
+                raise RuntimeError(f"{name} must be a contiguous float32 CUDA tensor [{C}] (it is updated in place)")
+    ws = torch.empty(bn3d_train_workspace_bytes(C, M), dtype=torch.uint8, device=y.device)
+    out = torch.empty_like(y)
+    mean = torch.empty((C,), dtype=torch.float32, device=y.device)
+    invstd = torch.empty_like(mean)
+    check(load().mvs_bn3d_train_forward(y.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                        None if skip is None else skip.data_ptr(), out.data_ptr(), mean.data_ptr(),
+                                        invstd.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
+                                        None if running_var is None else running_var.data_ptr(), float(momentum),
+                                        float(eps), int(bool(relu)), C, M, ws.data_ptr(), ws.numel(),
+                                        _stream(y.device)))
+    return out, mean, invstd
+
+
+def bn3d_train_backward(y, grad_out, gamma, beta, save_mean, save_invstd, relu=True):
+    """y, grad_out [M,C]; gamma, beta, save_mean, save_invstd [C] -> (grad_y [M,C], grad_gamma [C], grad_beta [C]).
+    grad_out is the gradient of relu(bn(y)) (+ skip: the skip's own gradient is grad_out itself)."""
+    y, grad_out = _cl_rows(y, "y"), _cl_rows(grad_out, "grad_out")
+    M, C = y.shape
+    if grad_out.shape != y.shape:
+        raise RuntimeError(f"grad_out {tuple(grad_out.shape)} must be shaped like y {tuple(y.shape)}")
+    vec = [_channel_vector(t, C, n) for t, n in ((gamma, "gamma"), (beta, "beta"), (save_mean, "save_mean"),
+                                                 (save_invstd, "save_invstd"))]
+    ws = torch.empty(bn3d_train_workspace_bytes(C, M), dtype=torch.uint8, device=y.device)
+    gy = torch.empty_like(y)
+    gg = torch.empty((C,), dtype=torch.float32, device=y.device)
+    gb = torch.empty_like(gg)
+    check(load().mvs_bn3d_train_backward(y.data_ptr(), grad_out.data_ptr(), *[t.data_ptr() for t in vec],
+                                         gy.data_ptr(), gg.data_ptr(), gb.data_ptr(), int(bool(relu)), C, M,
+                                         ws.data_ptr(), ws.numel(), _stream(y.device)))
+    return gy, gg, gb
+
+
+RELAYOUT_C8_TO_CHANNELS_LAST, RELAYOUT_CHANNELS_LAST_TO_PLANAR = 0, 1
+
+
+def volume_relayout(src, direction, out=None):
+    """direction RELAYOUT_C8_TO_CHANNELS_LAST: C8-planar [C/8,D,h,w,8] -> channels-last [D,h,w,C];
+    RELAYOUT_CHANNELS_LAST_TO_PLANAR: channels-last [D,h,w,C] -> planar [C,D,h,w].  A pure copy (into `out` when given)."""
+    src = _dev_f32(src, "volume")
+    if direction == RELAYOUT_C8_TO_CHANNELS_LAST:
+        if src.dim() != 5 or src.shape[4] != 8:
+            raise RuntimeError(f"volume must be C8-planar [C/8,D,h,w,8], got {tuple(src.shape)}")
+        C, dims = src.shape[0] * 8, tuple(src.shape[1:4])
+        oshape = dims + (C,)
+    elif direction == RELAYOUT_CHANNELS_LAST_TO_PLANAR:
+        if src.dim() != 4:
+            raise RuntimeError(f"volume must be channels-last [D,h,w,C], got {tuple(src.shape)}")
+        C, dims = src.shape[3], tuple(src.shape[:3])
+        oshape = (C,) + dims
+    else:
+        raise RuntimeError(f"volume_relayout: direction {direction!r} (0 or 1)")
+    if out is None:
+        out = torch.empty(oshape, dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != oshape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device:
+        raise RuntimeError(f"volume_relayout: out must be a contiguous float32 tensor {oshape}")
+    check(load().mvs_volume_relayout(src.data_ptr(), out.data_ptr(), C, dims[0] * dims[1] * dims[2], direction,
+                                     _stream(src.device)))
+    return out
 
 
 def depth_infer(feats, proj, depth_values, blob, workspace, depth_out, conf_out, dtype=MVS_F32):

@@ -2,7 +2,8 @@
 
 The cost volume and the soft-argmin -- the parts of a training step whose torch autograd graph is largest -- run as
 HIP kernels with hand-written adjoints (csrc/train_backward.hip); FeatureNet runs in torch (MIOpen) with autograd,
-and so does CostRegNet unless `costreg_impl = "hip"` puts its convolutions on csrc/train_conv3d.hip:
+and so does CostRegNet unless `costreg_impl = "hip"` puts its convolutions on csrc/train_conv3d.hip
+(`"hip_fused"`: its batch-norms, ReLUs and skip additions on csrc/train_bn3d.hip as well):
 
   cost_volume(feats, proj_matrices, depth_values)   mvs_relative_proj + mvs_warp_variance (fp32) forward,
                                                     mvs_warp_variance_backward; saves only its inputs, rt and the
@@ -11,6 +12,9 @@ and so does CostRegNet unless `costreg_impl = "hip"` puts its convolutions on cs
                                                     depth is differentiable (the confidence is no_grad, mvsnet.py:213)
   conv3d(x, weight, bias, stride)                   mvs_conv3d_train_forward / _backward_data / _backward_weight: CostRegNet's
   conv_transpose3d(x, weight)                       3x3x3 convolutions, raw (BatchNorm3d and ReLU stay in torch)
+  batch_norm_relu(x, bn, relu, skip)                mvs_bn3d_train_forward / _backward: train-mode BatchNorm3d + ReLU +
+                                                    skip addition as one forward and one backward call
+                                                    (csrc/train_bn3d.hip; `costreg_impl = "hip_fused"`)
   mvsnet_loss(depth_est, depth_gt, mask)            masked-mean smooth-L1 (mvsnet.py:242-244) without boolean
                                                     indexing, so it never synchronises
   TrainableMVSNet                                   MVSNet whose train-mode forward builds an autograd graph
@@ -40,7 +44,7 @@ def _feature_workspace(N, h, w, device):
 
 class _CostVolume(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feats, proj_matrices, depth_values):
+    def forward(ctx, feats, proj_matrices, depth_values, channels_last=False):
         B, N, C, h, w = feats.shape
         D = depth_values.shape[1]
         device = feats.device
@@ -49,34 +53,49 @@ class _CostVolume(torch.autograd.Function):
             proj = _lib._dev_f32(proj_matrices.detach().to(device), "proj_matrices")
             dv = _lib._dev_f32(depth_values.detach().to(device), "depth_values")
             ws = _feature_workspace(N, h, w, device)
-            out = torch.empty((B, C, D, h, w), dtype=torch.float32, device=device)
+            oshape = (B, D, h, w, C) if channels_last else (B, C, D, h, w)
+            out = torch.empty(oshape, dtype=torch.float32, device=device)
             rts = []
             for b in range(B):
                 rt = _lib.relative_proj(proj[b])
                 var = _lib.warp_variance(feats[b], rt, dv[b], ws, _lib.MVS_F32)   # C8-planar [4,D,h,w,8]
-                out[b].view(C // 8, 8, D, h, w).copy_(var.permute(0, 4, 1, 2, 3))
+                if channels_last:
+                    _lib.volume_relayout(var, _lib.RELAYOUT_C8_TO_CHANNELS_LAST, out=out[b])
+                else:
+                    out[b].view(C // 8, 8, D, h, w).copy_(var.permute(0, 4, 1, 2, 3))
                 rts.append(rt)
         ctx.save_for_backward(feats, torch.stack(rts), dv)
-        return out
+        ctx.channels_last = channels_last
+        return _logical(out) if channels_last else out
 
     @staticmethod
     def backward(ctx, grad_var):
         feats, rts, dv = ctx.saved_tensors
         if grad_var is None or not ctx.needs_input_grad[0]:
-            return None, None, None
+            return None, None, None, None
         with torch.cuda.device(feats.device):
-            grad_var = grad_var.contiguous()
             grad = torch.empty_like(feats)
-            for b in range(feats.shape[0]):
-                _lib.warp_variance_backward(feats[b], rts[b], dv[b], grad_var[b], out=grad[b])
-        return grad, None, None
+            if ctx.channels_last:
+                g = _channels_last(grad_var, "cost volume gradient")   # no copy when it comes from conv3d's backward
+                planar = torch.empty((g.shape[4],) + tuple(g.shape[1:4]), dtype=torch.float32, device=g.device)
+                for b in range(feats.shape[0]):
+                    _lib.volume_relayout(g[b], _lib.RELAYOUT_CHANNELS_LAST_TO_PLANAR, out=planar)
+                    _lib.warp_variance_backward(feats[b], rts[b], dv[b], planar, out=grad[b])
+            else:
+                grad_var = grad_var.contiguous()
+                for b in range(feats.shape[0]):
+                    _lib.warp_variance_backward(feats[b], rts[b], dv[b], grad_var[b], out=grad[b])
+        return grad, None, None, None
 
 
-def cost_volume(feats, proj_matrices, depth_values):
+def cost_volume(feats, proj_matrices, depth_values, channels_last=False):
     """Variance cost volume with autograd (models/module.py:96-139 + models/mvsnet.py:145-177, training branch).
 
     feats [B,N,32,h,w] float32 CUDA (view 0 = reference view), proj_matrices [B,N,4,4], depth_values [B,D]
-    -> variance [B,32,D,h,w] float32, NCDHW as CostRegNet's Conv3d takes it.  Gradients flow to feats only."""
+    -> variance [B,32,D,h,w] float32, NCDHW as CostRegNet's Conv3d takes it.  Gradients flow to feats only.
+    channels_last=True: the same logical tensor in torch's channels_last_3d memory format, as conv3d above takes it
+    without a copy -- one mvs_volume_relayout of the kernel's C8-planar output instead of a permute to NCDHW and a
+    second one to channels-last, and one relayout of the incoming gradient on the way back."""
     if not feats.is_cuda:
         raise RuntimeError(f"cost_volume needs CUDA(ROCm) tensors: the depth path has no CPU implementation "
                            f"(got feats on {feats.device})")
@@ -86,7 +105,7 @@ def cost_volume(feats, proj_matrices, depth_values):
             or depth_values.shape[0] != feats.shape[0]:
         raise RuntimeError(f"cost_volume: proj_matrices {tuple(proj_matrices.shape)} must be [B,N,4,4] and "
                            f"depth_values {tuple(depth_values.shape)} [B,D] for feats {tuple(feats.shape)}")
-    return _CostVolume.apply(feats, proj_matrices, depth_values)
+    return _CostVolume.apply(feats, proj_matrices, depth_values, bool(channels_last))
 
 
 class _SoftArgmin(torch.autograd.Function):
@@ -244,6 +263,66 @@ def _channels_last_check(x, weight, who):
         raise RuntimeError(f"{who}: input {tuple(x.shape)} must be [B,C,D,H,W] and weight {tuple(weight.shape)} 5-d")
 
 
+class _BatchNormReLU(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, skip, running_mean, running_var, momentum, eps, relu):
+        with torch.cuda.device(x.device):
+            xc = _channels_last(x, "batch_norm_relu input")
+            C = xc.shape[4]
+            g, b = _lib._dev_f32(gamma.detach(), "weight"), _lib._dev_f32(beta.detach(), "bias")
+            sc = None if skip is None else _channels_last(skip, "batch_norm_relu skip").view(-1, C)
+            out, mean, invstd = _lib.bn3d_train_forward(xc.view(-1, C), g, b, sc, running_mean, running_var, momentum,
+                                                        eps, relu)
+        ctx.save_for_backward(xc, g, b, mean, invstd)
+        ctx.relu = relu
+        return _logical(out.view(xc.shape))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        xc, g, b, mean, invstd = ctx.saved_tensors
+        C = xc.shape[4]
+        with torch.cuda.device(xc.device):
+            go = _channels_last(grad_out, "batch_norm_relu output gradient")
+            gy, gg, gb = _lib.bn3d_train_backward(xc.view(-1, C), go.view(-1, C), g, b, mean, invstd, ctx.relu)
+        # the skip joins after the ReLU: its gradient is the incoming one, the same tensor
+        return (_logical(gy.view(xc.shape)), gg, gb, grad_out if ctx.needs_input_grad[3] else None,
+                None, None, None, None, None)
+
+
+def batch_norm_relu(x, bn, relu=True, skip=None):
+    """relu(bn(x)) + skip with bn (an nn.BatchNorm3d) in training mode: batch statistics pooled over [B,D,H,W], the
+    running buffers and num_batches_tracked updated as nn.BatchNorm3d updates them (models/module.py:32-33,
+    models/mvsnet.py:47-60, 66-70), with autograd, on csrc/train_bn3d.hip.  x [B,C,D,H,W] float32 CUDA in
+    channels_last_3d memory format (conv3d's output; anything else is copied), C in {8,16,32,64}, B*D*H*W >= 2;
+    skip None or shaped like x -> [B,C,D,H,W] in channels_last_3d memory format."""
+    for t, name in ((x, "input"), (skip, "skip")):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"batch_norm_relu needs CUDA(ROCm) tensors: the training batch-norm has no CPU "
+                               f"implementation (got {name} on {t.device})")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"batch_norm_relu: {name} must be float32 (got {t.dtype})")
+    if x.dim() != 5 or (skip is not None and skip.shape != x.shape):
+        raise RuntimeError(f"batch_norm_relu: input {tuple(x.shape)} must be [B,C,D,H,W] and skip "
+                           f"{None if skip is None else tuple(skip.shape)} shaped like it")
+    if not isinstance(bn, torch.nn.BatchNorm3d) or not bn.affine or bn.num_features != x.shape[1]:
+        raise RuntimeError(f"batch_norm_relu: bn must be an affine nn.BatchNorm3d of {x.shape[1]} features, got {bn!r}")
+    if not bn.training:
+        raise RuntimeError("batch_norm_relu computes batch statistics: bn must be in training mode")
+    rm = rv = None
+    momentum = 0.0
+    if bn.track_running_stats and bn.running_mean is not None:
+        rm, rv = bn.running_mean, bn.running_var
+        # momentum None is nn.BatchNorm3d's cumulative average, 1 / num_batches_tracked (one host read, as torch's own)
+        momentum = 1.0 / (float(bn.num_batches_tracked) + 1.0) if bn.momentum is None else bn.momentum
+    out = _BatchNormReLU.apply(x, bn.weight, bn.bias, skip, rm, rv, momentum, bn.eps, bool(relu))
+    if rm is not None:
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)   # after the call: a refusal leaves the module as it was
+    return out
+
+
 def _conv_bn_relu(block, x):
     return F.relu(block.bn(block.conv(x)), inplace=True)   # models/module.py:32-33
 
@@ -269,13 +348,40 @@ def _costreg_hip(cr, x):
     return conv3d(x, cr.prob.weight, cr.prob.bias, 1)
 
 
+def _conv_bn_relu_fused(block, x):
+    return batch_norm_relu(conv3d(x, block.conv.weight, None, block.conv.stride[0]), block.bn)
+
+
+def _deconv_bn_relu_fused(seq, x, skip):
+    return batch_norm_relu(conv_transpose3d(x, seq[0].weight), seq[1], skip=skip)   # models/mvsnet.py:47-60, 66-70
+
+
+def _costreg_hip_fused(cr, x):
+    """CostRegNet.forward with nothing left to torch: the convolutions as _costreg_hip runs them, and after each of
+    the ten normalised layers one batch_norm_relu (the three deconvolution layers with their skip)."""
+    conv0 = _conv_bn_relu_fused(cr.conv0, x)
+    conv2 = _conv_bn_relu_fused(cr.conv2, _conv_bn_relu_fused(cr.conv1, conv0))
+    conv4 = _conv_bn_relu_fused(cr.conv4, _conv_bn_relu_fused(cr.conv3, conv2))
+    x = _conv_bn_relu_fused(cr.conv6, _conv_bn_relu_fused(cr.conv5, conv4))
+    x = _deconv_bn_relu_fused(cr.conv7, x, conv4)
+    x = _deconv_bn_relu_fused(cr.conv9, x, conv2)
+    x = _deconv_bn_relu_fused(cr.conv11, x, conv0)
+    return conv3d(x, cr.prob.weight, cr.prob.bias, 1)
+
+
+COSTREG_IMPLS = ("torch", "hip", "hip_fused")
+
+
 def _costreg(cr, x, impl="torch"):
     """CostRegNet.forward (models/mvsnet.py:64-73): impl "torch" through the blocks' .conv / .bn modules, "hip" with
-    the convolutions on csrc/train_conv3d.hip."""
+    the convolutions on csrc/train_conv3d.hip, "hip_fused" with BatchNorm3d, ReLU and the skip additions on
+    csrc/train_bn3d.hip as well."""
     if impl == "hip":
         return _costreg_hip(cr, x)
+    if impl == "hip_fused":
+        return _costreg_hip_fused(cr, x)
     if impl != "torch":
-        raise RuntimeError(f"costreg_impl must be 'torch' or 'hip', got {impl!r}")
+        raise RuntimeError(f"costreg_impl must be 'torch', 'hip' or 'hip_fused', got {impl!r}")
     conv0 = _conv_bn_relu(cr.conv0, x)
     conv2 = _conv_bn_relu(cr.conv2, _conv_bn_relu(cr.conv1, conv0))
     conv4 = _conv_bn_relu(cr.conv4, _conv_bn_relu(cr.conv3, conv2))
@@ -296,8 +402,9 @@ class TrainableMVSNet(MVSNet):
     (optimizer steps, MVSNet._param_versions).
 
     costreg_impl: "torch" (default) runs CostRegNet's convolutions on torch's backend; "hip" on the library's training
-    kernels (conv3d / conv_transpose3d above), with BatchNorm3d and ReLU still in torch.  Parameters, state_dict keys
-    and the eval path do not depend on it."""
+    kernels (conv3d / conv_transpose3d above), with BatchNorm3d and ReLU still in torch; "hip_fused" adds
+    batch_norm_relu after every normalised layer and takes the cost volume channels-last, so that nothing between the
+    cost volume and the soft-argmin runs in torch.  Parameters, state_dict keys and the eval path do not depend on it."""
 
     costreg_impl = "torch"
 
@@ -313,8 +420,8 @@ class TrainableMVSNet(MVSNet):
         if _lib.dtype_code(self.storage_dtype) != _lib.MVS_F32:
             raise RuntimeError(f"training needs storage_dtype 'f32' (got {self.storage_dtype!r}): 16-bit training "
                                "is not implemented")
-        if self.costreg_impl not in ("torch", "hip"):
-            raise RuntimeError(f"costreg_impl must be 'torch' or 'hip', got {self.costreg_impl!r}")
+        if self.costreg_impl not in COSTREG_IMPLS:
+            raise RuntimeError(f"costreg_impl must be 'torch', 'hip' or 'hip_fused', got {self.costreg_impl!r}")
         if not imgs.is_cuda:
             raise RuntimeError("MVSNet.forward needs CUDA(ROCm) tensors: the depth path has no CPU "
                                "implementation (got imgs on {})".format(imgs.device))
@@ -334,7 +441,7 @@ class TrainableMVSNet(MVSNet):
             # step 2. cost volume (models/mvsnet.py:145-177)
             proj = proj_matrices.to(device=device, dtype=torch.float32)
             dv = depth_values.to(device=device, dtype=torch.float32)
-            volume = cost_volume(feats, proj, dv)
+            volume = cost_volume(feats, proj, dv, channels_last=self.costreg_impl == "hip_fused")
             # step 3. cost regularisation (models/mvsnet.py:180, 192)
             cost = _costreg(self.cost_regularization, volume, self.costreg_impl).squeeze(1)
             # step 4. soft-argmin and photometric confidence (models/mvsnet.py:193-218)

@@ -7,14 +7,18 @@
   train_step    one whole optimisation step: training.train_sample on TrainableMVSNet against the same step with
                 every stage in torch (FeatureNet, the torch cost volume, CostRegNet, softmax + depth regression)
   soft_argmin   forward + backward of training.soft_argmin against torch softmax + depth regression
-  costreg       forward + backward of CostRegNet alone (training._costreg) at the training shape, costreg_impl "torch"
-                and "hip" alternating in the same process on the same seeded volume and upstream gradient; also
-                BatchNorm3d forward + backward on a contiguous NCDHW and on a channels_last_3d volume
-  train_step    (part of the same key) additionally times train_sample with costreg_impl = "hip"
+  costreg       forward + backward of CostRegNet alone (training._costreg) at the training shape, costreg_impl "torch",
+                "hip" and "hip_fused" alternating in the same process on the same seeded volume and upstream gradient;
+                also BatchNorm3d forward + backward on a contiguous NCDHW and on a channels_last_3d volume
+  train_step    (part of the same key) additionally times train_sample with costreg_impl = "hip" and "hip_fused"
+  bn            per normalised CostRegNet layer at the training shape: training.batch_norm_relu forward + backward
+                against nn.BatchNorm3d + relu (+ skip addition) on the same channels-last input, alternating, with the
+                bytes the fused kernels move (3 or 4 sweeps forward, 5 backward) and the resulting TB/s
 
 and the peak torch.cuda.max_memory_allocated of each.  Prints one JSON document (and writes it to --out).
-    python tools/time_train_step.py [--warmup 3] [--iters 10] [--only cost_volume,train_step,soft_argmin,costreg]
-The costreg and train_step parts are also written to profiles/train_costreg_timing.json.
+    python tools/time_train_step.py [--warmup 3] [--iters 10] [--only cost_volume,train_step,soft_argmin,costreg,bn]
+The costreg and train_step parts are also written to profiles/train_costreg_timing.json, and with the bn part to
+profiles/train_fused_timing.json.
 """
 import argparse
 import json
@@ -202,7 +206,7 @@ def bench_train_step(sample, warmup, iters):
         torch.cuda.empty_cache()
     # the same step with CostRegNet's convolutions in torch and in HIP, alternating
     steps = {}
-    for impl in ("torch", "hip"):
+    for impl in training.COSTREG_IMPLS:
         torch.manual_seed(0)
         model = training.TrainableMVSNet(refine=False).to(DEV)
         model.costreg_impl = impl
@@ -211,6 +215,7 @@ def bench_train_step(sample, warmup, iters):
     out.update(timed_alternating(steps, warmup, iters))
     a, b = out["costreg_torch"], out["costreg_hip"]
     out["hip_median_not_above_torch_median"] = bool(b["median_ms"] <= a["median_ms"])
+    out["hip_fused_range_entirely_below_hip"] = bool(out["costreg_hip_fused"]["max_ms"] < b["min_ms"])
     return out
 
 
@@ -241,10 +246,11 @@ def bench_costreg(warmup, iters):
             training._costreg(cr, volume, impl).backward(g)
         return step
 
-    out = timed_alternating({"torch": run("torch"), "hip": run("hip")}, warmup, iters)
+    out = timed_alternating({impl: run(impl) for impl in training.COSTREG_IMPLS}, warmup, iters)
     out["flop"] = costreg_gflop()
     t, hp = out["torch"], out["hip"]
     out["speedup_median"] = t["median_ms"] / hp["median_ms"]
+    out["hip_fused_range_entirely_below_hip"] = bool(out["hip_fused"]["max_ms"] < hp["min_ms"])
     out["hip_below_torch_and_ranges_disjoint"] = bool(hp["median_ms"] < t["median_ms"] and hp["max_ms"] < t["min_ms"])
     # BatchNorm3d (train mode) forward + backward on conv0's output, the two memory formats
     bn = torch.nn.BatchNorm3d(8).to(DEV).train()
@@ -260,6 +266,42 @@ def bench_costreg(warmup, iters):
         return step
 
     out.update(timed_alternating({k: bn_run(k) for k in variants}, warmup, iters))
+    return out
+
+
+# the ten normalised layers: (name, C, level, has a skip)
+_BN_LAYERS = (("conv0", 8, 0, False), ("conv1", 16, 1, False), ("conv2", 16, 1, False), ("conv3", 32, 2, False),
+              ("conv4", 32, 2, False), ("conv5", 64, 3, False), ("conv6", 64, 3, False), ("conv7", 32, 2, True),
+              ("conv9", 16, 1, True), ("conv11", 8, 0, True))
+
+
+def bench_bn(warmup, iters):
+    out = {}
+    for name, C, lv, has_skip in _BN_LAYERS:
+        d, h, w = D >> lv, (H // 4) >> lv, (W // 4) >> lv
+        gen = torch.Generator().manual_seed(C + lv)
+        cl = lambda: torch.randn((1, d, h, w, C), generator=gen).to(DEV).permute(0, 4, 1, 2, 3)  # noqa: E731
+        x, g = cl().requires_grad_(True), cl()
+        skip = cl().requires_grad_(True) if has_skip else None
+        bn = torch.nn.BatchNorm3d(C).to(DEV).train()
+
+        def hip():
+            x.grad = None
+            training.batch_norm_relu(x, bn, relu=True, skip=skip).backward(g)
+
+        def tor():
+            x.grad = None
+            r = F.relu(bn(x), inplace=True)
+            (r if skip is None else skip + r).backward(g)
+
+        res = timed_alternating({"hip": hip, "torch": tor}, warmup, iters)
+        vol = d * h * w * C * 4
+        res["bytes_moved"] = ((4 if has_skip else 3) + 5) * vol
+        res["hip_TBps_at_median"] = res["bytes_moved"] / (res["hip"]["median_ms"] * 1e-3) / 1e12
+        res["quoted_peak_TBps"] = 8.0
+        out[name] = res
+        del x, g, skip
+        torch.cuda.empty_cache()
     return out
 
 
@@ -285,14 +327,19 @@ def main():
             res[part] = bench_train_step(sample, args.warmup, args.iters)
         elif part == "costreg":
             res[part] = bench_costreg(args.warmup, args.iters)
+        elif part == "bn":
+            res[part] = bench_bn(args.warmup, args.iters)
         else:
             raise SystemExit(f"unknown part {part!r}")
     res["wall_s"] = round(time.time() - t0, 1)
     text = json.dumps(res, indent=1)
     print(text)
+    keep = {k: v for k, v in res.items() if k not in ("cost_volume", "soft_argmin")}
     if "costreg" in res or "train_step" in res:
-        keep = {k: v for k, v in res.items() if k not in ("cost_volume", "soft_argmin")}
         with open(os.path.join(REPO, "profiles", "train_costreg_timing.json"), "w") as f:
+            f.write(json.dumps({k: v for k, v in keep.items() if k != "bn"}, indent=1) + "\n")
+    if "costreg" in res or "train_step" in res or "bn" in res:
+        with open(os.path.join(REPO, "profiles", "train_fused_timing.json"), "w") as f:
             f.write(json.dumps(keep, indent=1) + "\n")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
