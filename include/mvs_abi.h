@@ -194,7 +194,12 @@ int mvs_depth_regression(const float* p, const float* depth_values, float* depth
  *     depth_avg double [R][h][w]     (sum of agreeing reprojected depths + d_ref)/(geo_sum+1) (699)
  *     masks     uint8  [R][3][h][w]  photo, geo, final as 0/1                    (660, 702, 706)
  *     xyz_world double [R][h*w][3]   depth2pts_np(depth_avg, K_ref, E_ref)       (752, 253-265)
- *   Selecting xyz_world[final] and the colours (eval.py:753-759) stays with the caller. */
+ *   Selecting xyz_world[final] and the colours (eval.py:753-759) stays with the caller.
+ *   Index contract: mvs_filter_compose rejects a ref_idx outside [0,V) and a src_idx >= V with
+ *   MVS_ERR_BAD_SHAPE, and ref_idx / src_idx handed to mvs_filter_depth must be the arrays it
+ *   accepted.  mvs_filter_depth cannot read device memory on the host and does not validate them:
+ *   for a ref_idx[r] outside [0,V) the kernel returns without writing ANY output of row r (the
+ *   caller's buffers keep whatever they held), and a src_idx outside [0,V) is skipped like -1. */
 #define MVS_FILTER_REF_FLOATS 30
 #define MVS_FILTER_PAIR_FLOATS 42
 int mvs_filter_compose(const float* intrinsics, const float* extrinsics, const int* ref_idx,

@@ -4,14 +4,16 @@ eval.py:590-760, helpers eval.py:253-275).
 TEST INFRASTRUCTURE ONLY: imported by tests/ and tools/ timing scripts as the checker, never by
 scene_3dreconstruction_mvsnet_amd (the product).
 
-PARITY UNPINNED for the bilinear sampler: the reference samples the source depth map with
-`cv2.remap(..., INTER_LINEAR)` (eval.py:541) and OpenCV is not importable in this image (no
-`cv2`, nothing may be installed), and the reference holds no fixture for this step.  `remap_linear`
-below restates OpenCV's published algorithm for float32 maps (modules/imgproc/src/imgwarp.cpp,
-remap -> remapBilinear, OpenCV 4.x): coordinates are quantised to 1/32 pixel with round-half-even,
-weights come from the 32x32 bilinear table, taps outside the image contribute the border value 0.
-Everything else (numpy dtype promotion) follows eval.py line by line in behaviour and is exercised
-against hand-computed cases in tests/test_filter_oracle.py.
+PARITY UNPINNED for ONE call, `cv2.remap(..., INTER_LINEAR)` (eval.py:540): OpenCV is not importable
+here.  `remap_linear` below restates OpenCV's published algorithm for float32 maps
+(modules/imgproc/src/imgwarp.cpp, remap -> remapBilinear, OpenCV 4.x): coordinates are quantised to
+1/32 pixel with round-half-even, weights come from the 32x32 bilinear table, taps outside the image
+contribute the border value 0; it is pinned by hand-computed cases in tests/test_filter_oracle.py.
+Everything else is pinned to the reference's own code: tests/golden/fx_filter.npz holds what the
+reference's reproject_with_depth / check_geometric_consistency / depth2pts_np return (with this
+`remap_linear` supplied as cv2.remap) and tests/test_filter_ref_host.py holds this oracle to it
+under the derived bounds of tests/filter_ref.py (dtype promotions, which matrix goes where, the
++0.5 pixel centres, the 1.0531 factor).
 
 Operation order: the reference forms its small matrix products with `np.matmul` and its inverses
 with `np.linalg.inv`, whose rounding order belongs to whatever BLAS / LAPACK build numpy links

@@ -9,7 +9,8 @@ boolean selection of the fused points (eval.py:753-759).
 
 Differences from the reference, flagged rather than hidden:
   * cv2.remap is restated inside the kernel (1/32-pixel quantised bilinear, zero border); OpenCV is
-    not installable here, so that restatement is pinned only by the oracle's hand-computed cases.
+    not importable here, so that one call is pinned only by the oracle's hand-computed cases.  The rest
+    of the chain is pinned to the reference's own functions (tests/golden/fx_filter.npz).
   * the reference's PLY block (eval.py:789-800) raises AttributeError as written
     (`vertices_colors.dtype` on a list); `write_ply` emits what that block is evidently meant to
     produce through plyfile: binary little-endian vertices x,y,z (float) + red,green,blue (uchar).

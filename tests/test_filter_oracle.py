@@ -1,7 +1,8 @@
 """CPU checks of the filter / fusion oracle (oracle/filter_oracle.py) and of the host side of the
 filter boundary (mvs_filter_compose, PLY writer).  OpenCV is absent, so `remap_linear` is pinned by
-hand-computed values of OpenCV's published 1/32-pixel bilinear rule -- "parity unpinned" against the
-reference itself, as the oracle's header states."""
+hand-computed values of OpenCV's published 1/32-pixel bilinear rule: cv2.remap is the one call whose
+parity with the reference is unpinned, as the oracle's header states (everything around it is held
+to the reference's own functions by tests/test_filter_ref_host.py)."""
 import os
 
 import numpy as np
