@@ -113,7 +113,12 @@ int mvs_warp_variance(const float* feats, const float* rt, const float* depth_va
 /* 3D U-Net cost regularisation.  Replaces CostRegNet.forward, models/mvsnet.py:64-73.
  *   var           dev C8-planar [4][D][h][w][8] in `dtype` (from mvs_warp_variance)
  *   weights_blob  dev copy of the mvs_pack_weights blob
- *   cost_out      dev fp32 [D][h][w]  (== cost_reg.squeeze(1) of models/mvsnet.py:192) */
+ *   cost_out      dev fp32 [D][h][w]  (== cost_reg.squeeze(1) of models/mvsnet.py:192)
+ * Non-finite voxels (the warp writes NaN for non-finite sampling coordinates) are ordinary data: every layer keeps
+ *   them as F.relu and conv3d do.  A logit is non-finite wherever the reference's is (NaN where it is NaN; NaN or the
+ *   infinity where it is +-inf: the split-operand and zero-padded forms turn inf into inf - inf or inf * 0); every finite
+ *   logit keeps its bound; non-finite logits outside the reference's set stay within the kernel forms' tile geometry
+ *   (Winograd along z: the rest of the 4- or 2-plane output tile; Toeplitz-pair and transposed forms: one voxel in x). */
 int mvs_costreg_forward(const void* var, const void* weights_blob, float* cost_out,
                         void* workspace, size_t workspace_bytes, int D, int h, int w, int dtype,
                         void* stream);
@@ -123,7 +128,9 @@ int mvs_costreg_forward(const void* var, const void* weights_blob, float* cost_o
  * Replaces one ConvBnReLU3D / ConvTranspose3d+BN+ReLU(+skip) / prob conv of
  * models/mvsnet.py:36-62.
  *   x     dev [Cin/8][Di][Hi][Wi][8]    skip  dev [Cout/8][Do][Ho][Wo][8] or NULL (layers 7..9
- *   y     dev [Cout/8][Do][Ho][Wo][8]   need it)              (layer 10: y is fp32 [D][h][w]) */
+ *   y     dev [Cout/8][Do][Ho][Wo][8]   need it)              (layer 10: y is fp32 [D][h][w])
+ * NaN and infinity in x or skip: as stated at mvs_costreg_forward, per layer (the ReLU keeps NaN; a 16-bit store keeps
+ *   NaN and infinity). */
 int mvs_conv_layer(int layer, const void* x, const void* skip, void* y, const void* weights_blob,
                    int Di, int Hi, int Wi, int dtype, void* stream);
 
@@ -133,13 +140,18 @@ int mvs_conv_layer(int layer, const void* x, const void* skip, void* y, const vo
  * mvs_conv_layer, for parity tests and per-kernel timing.  x and skip in `dtype` (16-bit storage: the transposed
  * convolution runs on the 16-bit MFMA, the sum that feeds prob stays fp32); the logits are always fp32.
  *   x     dev [2][Di][Hi][Wi][8]  (output of layer 8)     skip  dev [1][2Di][2Hi][2Wi][8]  (output of layer 0)
- *   cost_out  dev fp32 [2Di][2Hi][2Wi] */
+ *   cost_out  dev fp32 [2Di][2Hi][2Wi]
+ * NaN and infinity in x or skip: as stated at mvs_costreg_forward (a non-finite skip voxel reaches its 27 logits, a
+ *   non-finite x voxel the logits of its transposed footprint and one more voxel in x). */
 int mvs_conv11_prob(const void* x, const void* skip, float* cost_out, const void* weights_blob,
                     int Di, int Hi, int Wi, int dtype, void* stream);
 
 /* softmax over D, depth expectation and photometric confidence in one pass.
  * Replaces models/mvsnet.py:192-193,204,214-218 and models/module.py:144-147.
- *   cost dev fp32 [D][h][w]; depth_out, conf_out dev fp32 [h][w] */
+ *   cost dev fp32 [D][h][w]; depth_out, conf_out dev fp32 [h][w]
+ * A pixel's depth and confidence are NaN exactly where softmax-then-sum is: a NaN or +inf logit, or -inf logits only
+ *   (the reference's trunc of the NaN expectation picks some window of an all-NaN row: NaN whichever).  A -inf logit
+ *   among finite ones is a term of exactly 0; other pixels of the block are untouched. */
 int mvs_softargmin_conf(const float* cost, const float* depth_values, float* depth_out,
                         float* conf_out, int D, int h, int w, void* stream);
 

@@ -235,7 +235,6 @@ __global__ __launch_bounds__(512) void conv0_w48t_kernel(
             f32x4 M[NT_PLANES];
 #pragma unroll
             for (int q = 0; q < NT_PLANES; ++q) M[q] = *reinterpret_cast<const f32x4*>(ex + (q * NPOS + pos) * EXS + ch * 4);
-            const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
             const f32x4 s12 = M[1] + M[2], d12 = M[1] - M[2], s34 = M[3] + M[4], d34 = M[3] - M[4];
             f32x4 o[TZ];
             o[0] = (M[0] + s12) + s34;
@@ -245,7 +244,7 @@ __global__ __launch_bounds__(512) void conv0_w48t_kernel(
             const unsigned base = (unsigned)((((size_t)z0 * H + gy) * W + gx) * 8 + ch * 4) * 4u;
 #pragma unroll
             for (int q = 0; q < TZ; ++q) {
-                const f32x4 v = __builtin_elementwise_max(o[q] + obias, zero);
+                const f32x4 v = relu(o[q] + obias);
                 const unsigned off = (ok && z0 + q < D) ? base + (unsigned)q * (unsigned)(HW8 * 4) : 0xFFFFFFF0u;
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yrs, (int)off, 0, 0);
             }

@@ -285,7 +285,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_priv_kernel(
             if (c < 2 ? !de : !dodd) continue;
             float* dst = ct + (c >> 1) * PS + (c & 1) * RS + sbase0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) dst[8 * e] = fmaxf(acc[c][e] + bv, 0.0f);
+            for (int e = 0; e < 4; ++e) dst[8 * e] = relu(acc[c][e] + bv);
         }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob16_kernel(
             if (c < 2 ? !de : !dodd) continue;
             float* dst = ct + (c >> 1) * PS + (c & 1) * RS + sbase0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) dst[8 * e] = fmaxf(acc[c][e] + bv, 0.0f);
+            for (int e = 0; e < 4; ++e) dst[8 * e] = relu(acc[c][e] + bv);
         }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -669,7 +669,7 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
             float* dst = ct + c * RS + sbase0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float v = fmaxf((c ? s1 : s0)[e], 0.0f) + sk[2 * pz + c][e];
+                const float v = relu((c ? s1 : s0)[e]) + sk[2 * pz + c][e];
                 dst[8 * e] = ((c ? vy1 : vy0) && vx[e]) ? v : 0.0f;
             }
         }

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void conv3d_direct_kernel(const float* __restr
         const int co = co0 + j;
         const size_t o = (COUT == 1) ? vi : ((size_t)(co >> 3) * nvox + vi) * 8 + (co & 7);
         float v = acc[j];
-        if (RELU) v = fmaxf(v, 0.0f);
+        if (RELU) v = relu(v);
         if (SKIP) v += skip[o];  // skip + relu(bn(deconv(x)))   (models/mvsnet.py:69-71)
         y[o] = v;
     }
@@ -195,10 +195,10 @@ __global__ __launch_bounds__(256) void deconv3d_direct_kernel(const float* __res
         const float4 s1 = *reinterpret_cast<const float4*>(skip + o + 8);
         // skip + relu(bn(deconv(x)))   (models/mvsnet.py:69-71)
         float4 r0, r1;
-        r0.x = fmaxf(acc0[j + 0], 0.f) + s0.x; r0.y = fmaxf(acc0[j + 1], 0.f) + s0.y;
-        r0.z = fmaxf(acc0[j + 2], 0.f) + s0.z; r0.w = fmaxf(acc0[j + 3], 0.f) + s0.w;
-        r1.x = fmaxf(acc1[j + 0], 0.f) + s1.x; r1.y = fmaxf(acc1[j + 1], 0.f) + s1.y;
-        r1.z = fmaxf(acc1[j + 2], 0.f) + s1.z; r1.w = fmaxf(acc1[j + 3], 0.f) + s1.w;
+        r0.x = relu(acc0[j + 0]) + s0.x; r0.y = relu(acc0[j + 1]) + s0.y;
+        r0.z = relu(acc0[j + 2]) + s0.z; r0.w = relu(acc0[j + 3]) + s0.w;
+        r1.x = relu(acc1[j + 0]) + s1.x; r1.y = relu(acc1[j + 1]) + s1.y;
+        r1.z = relu(acc1[j + 2]) + s1.z; r1.w = relu(acc1[j + 3]) + s1.w;
         *reinterpret_cast<float4*>(y + o) = r0;
         *reinterpret_cast<float4*>(y + o + 8) = r1;
     }

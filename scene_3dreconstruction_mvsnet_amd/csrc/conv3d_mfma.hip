@@ -175,7 +175,7 @@ __global__ __launch_bounds__(c0q::THREADS, 2) void conv0_4x4_mfma_kernel(
                 const size_t o = (((size_t)gz * H + gy) * W + gx) * 8;
 #pragma unroll
                 for (int n = 0; n < 2; ++n)
-                    St<DT>::store1(y, o + 4 * n + j, fmaxf(acc[m][n][i] + bias[4 * n + j], 0.0f));
+                    St<DT>::store1(y, o + 4 * n + j, relu(acc[m][n][i] + bias[4 * n + j]));
             }
         }
 }
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256) void convg_mfma_kernel(
             const int m = 4 * (lane >> 4) + e;
             const int gy = oy0 + 2 * ty + (m >> 3), gx = ox0 + 8 * tx + (m & 7);
             if (gz < Do && gy < Ho && gx < Wo)
-                St<DT>::store1(y, yplane + (((size_t)gz * Ho + gy) * Wo + gx) * 8, fmaxf(acc[i][e] + bv, 0.0f));
+                St<DT>::store1(y, yplane + (((size_t)gz * Ho + gy) * Wo + gx) * 8, relu(acc[i][e] + bv));
         }
     }
 }
@@ -568,7 +568,7 @@ __global__ __launch_bounds__(256) void convg_persist_mfma_kernel(
                 const int m = 4 * (lane >> 4) + e;
                 const int gy = cy0 + 2 * ty + (m >> 3), gx = cx0 + 8 * tx + (m & 7);
                 if (gz < Do && gy < Ho && gx < Wo)
-                    St<DT>::store1(y, yplane + (((size_t)gz * Ho + gy) * Wo + gx) * 8, fmaxf(acc[i][e] + bv, 0.0f));
+                    St<DT>::store1(y, yplane + (((size_t)gz * Ho + gy) * Wo + gx) * 8, relu(acc[i][e] + bv));
             }
         }
         if (has_next) {
@@ -752,7 +752,7 @@ __global__ __launch_bounds__(c1z::THREADS) void conv1z_mfma_kernel(
         }
         // epilogue: row m = 4 g + e of the M-tile, column n -> strip[m][n]; then one 16-byte piece per lane
 #pragma unroll
-        for (int e = 0; e < 4; ++e) strip[(4 * g + e) * 20 + n] = fmaxf(acc[e] + bv, 0.0f);
+        for (int e = 0; e < 4; ++e) strip[(4 * g + e) * 20 + n] = relu(acc[e] + bv);
         __builtin_amdgcn_wave_barrier();
         const f32x4 o = *reinterpret_cast<const f32x4*>(strip + sv * 20 + sq * 4);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4r, o), yrs,
@@ -1053,7 +1053,7 @@ __global__ __launch_bounds__(256) void deconvg_mfma_kernel(
 #pragma unroll
                 for (int py = 0; py < 2; ++py)
                     tile[(tz * G::OY + 2 * ly + py) * G::RP + ox * COUT + (ox >> 3) * 16 + co] =
-                        fmaxf(acc[2 * pz + py][i][e] + bv, 0.0f);
+                        relu(acc[2 * pz + py][i][e] + bv);
             }
         }
         __syncthreads();

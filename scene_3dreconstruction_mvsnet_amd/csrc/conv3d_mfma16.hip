@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256) void convg16_mfma_kernel(
         for (int e = 0; e < 4; ++e) {
             const int m = 4 * (lane >> 4) + e;
             const int oy = 2 * ty + (m >> 3), ox = 8 * tx + (m & 7);
-            otile[(tz * OY + oy) * RP + ox * COUT + (ox >> 3) * 16 + co] = fmaxf(acc[i][e] + bv, 0.0f);
+            otile[(tz * OY + oy) * RP + ox * COUT + (ox >> 3) * 16 + co] = relu(acc[i][e] + bv);
         }
     }
     __syncthreads();
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(256) void conv0p16_mfma_kernel(
             const int m = 4 * (lane >> 4) + e;
             const int gx = x0 + 2 * m + jj;
             if (gz < D && gy < H && gx < W)
-                St<DT>::store1(y, (((size_t)gz * H + gy) * W + gx) * 8 + co, fmaxf(acc[i][e] + bv, 0.0f));
+                St<DT>::store1(y, (((size_t)gz * H + gy) * W + gx) * 8 + co, relu(acc[i][e] + bv));
         }
     }
 }
@@ -652,7 +652,7 @@ __global__ __launch_bounds__(c0z::THREADS) void conv0z16_mfma_kernel(
         // epilogue: element e of acc = pair m = 4 g + e -> voxel x = 2 m + jj, channel co
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float v = fmaxf(acc[e] + bv, 0.0f);
+            const float v = relu(acc[e] + bv);
             unsigned short bits;
             if (DT == MVS_F16) { const _Float16 hv = (_Float16)v; bits = __builtin_bit_cast(unsigned short, hv); }
             else { const __bf16 hv = (__bf16)v; bits = __builtin_bit_cast(unsigned short, hv); }
@@ -847,7 +847,7 @@ __global__ __launch_bounds__(512) void convz16_mfma_kernel(
             for (int i = 0; i < G::MPW; ++i)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float v = fmaxf(acc[i][nt][e] + bv[nt], 0.0f);
+                    const float v = relu(acc[i][nt][e] + bv[nt]);
                     unsigned short bits;
                     if (DT == MVS_F16) { const _Float16 hv = (_Float16)v; bits = __builtin_bit_cast(unsigned short, hv); }
                     else { const __bf16 hv = (__bf16)v; bits = __builtin_bit_cast(unsigned short, hv); }
@@ -1109,7 +1109,7 @@ __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
 #pragma unroll
                 for (int py = 0; py < 2; ++py)
                     otile[(tz * OY + 2 * ly + py) * RP + ox * COUT + (ox >> 3) * 16 + co] =
-                        fmaxf(acc[2 * pz + py][i][e] + bv, 0.0f);
+                        relu(acc[2 * pz + py][i][e] + bv);
             }
         }
         __syncthreads();

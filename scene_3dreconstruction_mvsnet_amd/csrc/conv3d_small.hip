@@ -183,7 +183,7 @@ __global__ __launch_bounds__(64 * (COUT / 16) * KW) void convs_mfma_kernel(
         for (int e = 0; e < 4; ++e) {
             const int gx = ox0 + 4 * tx + e;
             if (gz < Do && gy < Ho && gx < Wo)
-                St<DT>::store1(y, yplane + (((size_t)gz * Ho + gy) * Wo + gx) * 8, fmaxf(acc[i][e] + bv, 0.0f));
+                St<DT>::store1(y, yplane + (((size_t)gz * Ho + gy) * Wo + gx) * 8, relu(acc[i][e] + bv));
         }
     }
 }
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(64 * (2 * COUT / 16) * KW) void deconvs_mfma_kernel
                 const int gx = 2 * (ix0 + 4 * tx + e) + px;
                 if (gz < Do && gy < Ho && gx < Wo) {
                     const size_t o = yplane + (((size_t)gz * Ho + gy) * Wo + gx) * 8;
-                    St<DT>::store1(y, o, fmaxf(sum[i][e] + bv, 0.0f) + St<DT>::load1(skip, o));
+                    St<DT>::store1(y, o, relu(sum[i][e] + bv) + St<DT>::load1(skip, o));
                 }
             }
         }

@@ -273,7 +273,6 @@ __global__ __launch_bounds__(256, 2) void conv0_w43_mfma_kernel(
 #pragma unroll
     for (int q = 0; q < NT_PLANES; ++q) M[q] = *reinterpret_cast<const f32x4*>(tile + (q * NPOS + pos) * EXS + ch * 4);
     const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + ch * 4);
-    const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
     const f32x4 s12 = M[1] + M[2], d12 = M[1] - M[2], s34 = M[3] + M[4], d34 = M[3] - M[4];
     f32x4 o[TZ];
     o[0] = (M[0] + s12) + s34;
@@ -283,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void conv0_w43_mfma_kernel(
 #pragma unroll
     for (int q = 0; q < TZ; ++q) {
         if (z0 + q >= D) break;
-        const f32x4 v = __builtin_elementwise_max(o[q] + bv, zero);
+        const f32x4 v = relu(o[q] + bv);
         St<DT>::store4(y, (((size_t)(z0 + q) * H + gy) * W + gx) * 8 + ch * 4, v);
     }
 }
@@ -527,7 +526,6 @@ __global__ __launch_bounds__(256) void convwz_mfma_kernel(
         }
         const f32x4 bv0 = *reinterpret_cast<const f32x4*>(bias + pl * 8);
         const f32x4 bv1 = *reinterpret_cast<const f32x4*>(bias + pl * 8 + 4);
-        const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int o = 0; o < 2; ++o) {
             if (z0 + o >= D) break;
@@ -539,8 +537,8 @@ __global__ __launch_bounds__(256) void convwz_mfma_kernel(
                 lo = (M[1][0] - M[2][0]) - M[3][0] + bv0;
                 hi = (M[1][1] - M[2][1]) - M[3][1] + bv1;
             }
-            lo = __builtin_elementwise_max(lo, zero);
-            hi = __builtin_elementwise_max(hi, zero);
+            lo = relu(lo);
+            hi = relu(hi);
             const size_t off = (size_t)pl * V8 + (((size_t)(z0 + o) * H + gy) * W + gx) * 8;
             if constexpr (DT == MVS_F32) {
                 St<DT>::store4(y, off, lo);

@@ -51,7 +51,8 @@ __global__ __launch_bounds__(256) void softargmin_conf_kernel(const float* __res
     for (int j = 0; j < MAXPER; ++j) {
         const int d = d0 + j;
         if (d < d1) {
-            const float e = expf(cbuf[j] - m);
+            // a slice of -inf logits alone has m = -inf: -inf - -inf would be NaN where the softmax term is 0
+            const float e = (cbuf[j] == -INFINITY) ? 0.0f : expf(cbuf[j] - m);
             s += e;
             sd = fmaf(e, dv[d], sd);
             si = fmaf(e, (float)d, si);
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(256) void softargmin_conf_loop_kernel(const float* 
                     s *= r; sd *= r; si *= r;
                     m = c;
                 }
-                const float e = expf(c - m);
+                const float e = (c == -INFINITY) ? 0.0f : expf(c - m);   // m is still -inf before the first finite logit
                 s += e;
                 sd = fmaf(e, dv[d], sd);
                 si = fmaf(e, (float)d, si);

@@ -15,6 +15,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
+// ReLU of the inference epilogues.  It keeps a NaN, as F.relu and both oracles do (fmaxf(NaN, 0) is 0): the IEEE 754-2019
+// maximum, one v_maximum3_f32 on gfx950 in the place of fmaxf's v_max_f32.
+__device__ __forceinline__ float relu(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+__device__ __forceinline__ f32x4 relu(f32x4 v) { return __builtin_elementwise_maximum(v, (f32x4){0.0f, 0.0f, 0.0f, 0.0f}); }
+
 template <int DT>
 struct St;
 

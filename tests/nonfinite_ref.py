@@ -1,0 +1,478 @@
+"""NaN and infinity through CostRegNet and the soft-argmin: the contract, the injection patterns, the per-form spread
+extents, the checker and the references.  Shared by tests/test_nonfinite_host.py (CPU), tests/nonfinite_check.py (the
+GPU child) and tests/test_gpu_nonfinite.py.
+
+Contract, for a kernel output `got` and the NaN-propagating reference `ref` (probes.ref64: np.maximum keeps NaN, as
+F.relu and both oracles do):
+  R1  never hide     wherever ref is non-finite got is non-finite (NaN for +-inf is accepted: a split-operand or padded
+                     form turns inf into inf - inf or inf * 0); where ref is NaN got is NaN.
+  R2  nothing moves  wherever got is finite the kernel's own bound holds against ref (probes.dense_ref_bound, its scale S
+                     taken of the input with the non-finite entries replaced by 0; softargmin_ref for the last stage).
+  R3  bounded spread got may be non-finite outside ref's non-finite set only within EXTENTS[form] output voxels of the
+                     TOUCHED set: the outputs whose pre-activation reference value is non-finite, in any channel (after
+                     the ReLU a -inf is an exact 0 in ref, where a form that cannot keep an infinity gives NaN).
+"""
+import re
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+import probes as P
+import softargmin_ref as sar
+from oracle import oracle as orc
+
+# ---------------------------------------------------------------------------------------------------------------
+# R3: how far beyond the touched set a form may turn outputs non-finite, (ez, ey, ex) in output voxels.  Keyed by the
+# kernel names of probe_check.KERNELS; a launcher instantiation of probe_check.INSTANTIATIONS resolves through
+# LAUNCHER_KERNEL.  Every entry is derived from the form's operand geometry, not from a run:
+#   * an implicit-GEMM form whose K dimension holds (tap, channel) pairs of ONE output voxel accumulates only that
+#     voxel's own taps.  Its padded 28th tap (27 -> 28) re-reads tap 26 of the same voxel against a packed zero weight:
+#     NaN * 0 lands on an output that the NaN reaches anyway.                                                  (0, 0, 0)
+#   * Winograd along z mixes the m + 2 input planes of a tile into its m output planes: an input plane that the
+#     reference spreads over 3 outputs can reach the rest of the tile's m planes, at most m - 1 planes away.
+#     F(4,3): 3, F(2,3): 1.                                                                            (m - 1, 0, 0)
+#   * a Toeplitz-pair form puts two x-adjacent outputs (x0, x0 + 1) into N and their 4 x-taps x0 - 1 .. x0 + 2 into K;
+#     the taps an output does not use meet packed zeros, so voxel x0 + 2 reaches output x0 and voxel x0 - 1 reaches
+#     output x0 + 1: one voxel beyond the 3-tap footprint.                                                     (0, 0, 1)
+#   * the transposed forms fold the output's x parity into N over the input taps (i, i + 1): the even output 2i uses
+#     input i only and meets a packed zero for i + 1, whose footprint is 2i + 1 .. 2i + 3: one voxel.          (0, 0, 1)
+#     The direct kernels skip the taps of the other parity instead of multiplying by zero.                     (0, 0, 0)
+#   * the fused tail is the transposed form followed by the 3x3x3 prob layer; the touched set is taken of the logits,
+#     and the prob layer carries conv11's one extra x voxel along unchanged.                                   (0, 0, 1)
+# ---------------------------------------------------------------------------------------------------------------
+EXTENTS = {
+    "conv3d_direct_kernel": (0, 0, 0),
+    "deconv3d_direct_kernel": (0, 0, 0),
+    "prob_lds_kernel": (0, 0, 0),
+    "conv0_4x4_mfma_kernel": (0, 0, 0),
+    "convg_mfma_kernel": (0, 0, 0),
+    "convg_persist_mfma_kernel": (0, 0, 0),
+    "conv1z_mfma_kernel": (0, 0, 0),
+    "convs_mfma_kernel": (0, 0, 0),
+    "convg16_mfma_kernel": (0, 0, 0),
+    "convz16_mfma_kernel": (0, 0, 0),
+    "conv0_w43_mfma_kernel": (3, 0, 0),        # F(4,3) along z
+    "convwz_mfma_kernel": (1, 0, 0),           # F(2,3) along z
+    "conv0_w48t_kernel": (3, 0, 1),            # F(4,3) along z on a Toeplitz-pair panel in x
+    "conv0p16_mfma_kernel": (0, 0, 1),         # Toeplitz pair in x
+    "conv0z16_mfma_kernel": (0, 0, 1),         # Toeplitz pair in x
+    "deconvg_mfma_kernel": (0, 0, 1),          # x parity folded into N
+    "deconvs_mfma_kernel": (0, 0, 1),
+    "deconvg16_mfma_kernel": (0, 0, 1),
+    "conv11_prob_split_kernel": (0, 0, 1),     # transposed form + prob
+    "conv11_prob_priv_kernel": (0, 0, 1),
+    "conv11_prob16_kernel": (0, 0, 1),
+}
+LAUNCHER_KERNEL = {
+    "run_direct": "conv3d_direct_kernel", "run_deconv": "deconv3d_direct_kernel",
+    "run_conv0_4x4": "conv0_4x4_mfma_kernel", "run_conv0_w43": "conv0_w43_mfma_kernel",
+    "run_convwz": "convwz_mfma_kernel", "run_convg_persist": "convg_persist_mfma_kernel",
+    "run_convg": "convg_mfma_kernel", "run_deconvg": "deconvg_mfma_kernel", "run_convs": "convs_mfma_kernel",
+    "run_deconvs": "deconvs_mfma_kernel", "run_convg16": "convg16_mfma_kernel",
+    "run_deconvg16": "deconvg16_mfma_kernel", "run_convz16": "convz16_mfma_kernel",
+}
+
+
+def extent_of(name):
+    """(ez, ey, ex) of a kernel name or of a launcher instantiation `run_x<...>`; KeyError when it has no entry."""
+    m = re.match(r"(run_\w+)<", name)
+    return EXTENTS[LAUNCHER_KERNEL[m.group(1)] if m else name]
+
+
+# probe_check case -> layer -> the kernels that can serve it there (probe_check's docstring; where the dispatch
+# depends on the shape both candidates are listed and the larger extent holds)
+_DIRECT = {l: ("conv3d_direct_kernel", "deconv3d_direct_kernel") if 7 <= l <= 9 else
+           ("prob_lds_kernel", "conv3d_direct_kernel") if l == 10 else ("conv3d_direct_kernel",) for l in range(11)}
+CASE_KERNELS = {
+    "default": {0: ("conv0_w48t_kernel",), 1: ("convg_mfma_kernel", "convg_persist_mfma_kernel"),
+                2: ("convg16_mfma_kernel",), 3: ("convg16_mfma_kernel",), 4: ("convg16_mfma_kernel",),
+                5: ("convs_mfma_kernel",), 6: ("convs_mfma_kernel",), 7: ("deconvs_mfma_kernel",),
+                8: ("deconvg16_mfma_kernel",), 9: ("deconvg_mfma_kernel",), 10: ("prob_lds_kernel",),
+                "tail": ("conv11_prob_split_kernel",)},
+    "conv0_split0": {0: ("conv0_w43_mfma_kernel",)},
+    "conv0_wino0": {0: ("conv0_4x4_mfma_kernel",)},
+    "conv1z": {1: ("conv1z_mfma_kernel",)},
+    "persist": {1: ("convg_persist_mfma_kernel", "convg_mfma_kernel")},
+    "split0": {2: ("convwz_mfma_kernel",), 3: ("convg_mfma_kernel",), 4: ("convwz_mfma_kernel",),
+               8: ("deconvg_mfma_kernel",)},
+    "split0_wino0": {2: ("convg_mfma_kernel",), 4: ("convg_mfma_kernel",)},
+    "split_deconv3": {7: ("deconvg16_mfma_kernel",), 8: ("deconvg16_mfma_kernel",)},
+    "split_deconv0": {7: ("deconvs_mfma_kernel", "deconvg_mfma_kernel"), 8: ("deconvg_mfma_kernel",)},
+    "tail_split0": {"tail": ("conv11_prob_priv_kernel",)},
+    "force_direct": _DIRECT,
+    "default16": {0: ("conv0p16_mfma_kernel", "conv0z16_mfma_kernel"),
+                  **{l: ("convg16_mfma_kernel", "convz16_mfma_kernel") for l in (1, 2, 3, 4, 5, 6)},
+                  **{l: ("deconvg16_mfma_kernel",) for l in (7, 8, 9)}, 10: ("prob_lds_kernel",),
+                  "tail": ("conv11_prob16_kernel",)},
+    "conv0z16_1": {0: ("conv0z16_mfma_kernel",)},
+    "conv0z16_0": {0: ("conv0p16_mfma_kernel",)},
+    "convz16_1": {l: ("convz16_mfma_kernel",) for l in (1, 2, 3)},
+    "convz16_0": {l: ("convg16_mfma_kernel",) for l in (1, 2, 3)},
+    "deep1": {**{l: ("convg16_mfma_kernel",) for l in (4, 5, 6)}, **{l: ("deconvg16_mfma_kernel",) for l in (7, 8)}},
+    "deep0": {**{l: ("convg16_mfma_kernel",) for l in (4, 5, 6)}, **{l: ("deconvg16_mfma_kernel",) for l in (7, 8)}},
+}
+
+
+def case_extent(case, layer):
+    return tuple(max(e) for e in zip(*(EXTENTS[k] for k in CASE_KERNELS[case][layer])))
+
+
+# every kernel that can serve a layer of mvs_costreg_forward, per storage class: the chain takes the largest extent
+CHAIN_KERNELS = {
+    "f32": {0: ("conv0_w48t_kernel", "conv0_w43_mfma_kernel", "conv0_4x4_mfma_kernel"),
+            **{l: ("convg_mfma_kernel", "convwz_mfma_kernel", "convg16_mfma_kernel", "convs_mfma_kernel",
+                   "conv1z_mfma_kernel", "convg_persist_mfma_kernel") for l in range(1, 7)},
+            **{l: ("deconvg_mfma_kernel", "deconvs_mfma_kernel", "deconvg16_mfma_kernel") for l in (7, 8)},
+            "tail": ("conv11_prob_split_kernel", "conv11_prob_priv_kernel")},
+    "b16": {0: ("conv0p16_mfma_kernel", "conv0z16_mfma_kernel"),
+            **{l: ("convg16_mfma_kernel", "convz16_mfma_kernel") for l in range(1, 7)},
+            **{l: ("deconvg16_mfma_kernel",) for l in (7, 8)}, "tail": ("conv11_prob16_kernel",)},
+}
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# injection patterns
+# ---------------------------------------------------------------------------------------------------------------
+def edge_pairs(n, transposed=False):
+    """Input coordinates (t - 1, t) on both sides of a tile edge of a dimension of n voxels.  Every tile of every form
+    is a power of two of at most 32 outputs per dimension (2 x 8 and 4 x 4 M-tiles in 1, 2 or 4 per block, 4 x 8 x 32
+    Winograd tiles, 8 x 16 marching columns, Winograd tiles of 4 and 2 planes), at stride 2 that many outputs are twice
+    as many inputs and a transposed layer's tile half as many: an edge of the tile size T is an edge of every smaller
+    one, so t = 8, 16, 32 (transposed: 4, 8, 16) below n cover them all; a short dimension takes its largest power of
+    two.  At stride 2, t - 1 and t are the two input parities."""
+    ts = [t for t in ((4, 8, 16) if transposed else (8, 16, 32)) if t < n]
+    if not ts:
+        ts = [max(t for t in (1, 2, 4) if t < n)]
+    return [(t - 1, t) for t in ts]
+
+
+def voxel_positions(layer, full=True):
+    """name -> (channel, z, y, x) of the one non-finite input voxel: a volume corner, an interior voxel, and both sides
+    of the tile edges in z, y and x (full=False: the largest edge per dimension only)."""
+    ci, _, _, tr, (D, H, W) = P.GEOM[layer]
+    mid = (D // 2 - 1, H // 2, W // 2 - 1)
+    out = {"interior": (5 % ci,) + mid}
+    if full:
+        out["corner"] = (ci - 1, D - 1, H - 1, W - 1)
+    for ax, n in enumerate((D, H, W)):
+        pairs = edge_pairs(n, tr)
+        for a, b in (pairs if full else pairs[-1:]):
+            for v in (a, b):
+                pos = list(mid)
+                pos[ax] = v
+                out["%s%d" % ("zyx"[ax], v)] = ((3 * v + ax) % ci,) + tuple(pos)
+    return out
+
+
+def out_shape(layer, shape=None):
+    _, co, s, tr, (D, H, W) = P.GEOM[layer]
+    if shape is not None:
+        D, H, W = shape
+    if tr:
+        return (co, 2 * D, 2 * H, 2 * W)
+    return (co, (D - 1) // s + 1, (H - 1) // s + 1, (W - 1) // s + 1)
+
+
+def background(shape, rng, storage="f32"):
+    """Dense, heavy-tailed and positive, as a variance volume (the probes' second dense volume): exp(3 randn); fp16
+    storage takes exp(1.5 randn), whose sums stay far inside fp16's range."""
+    return np.exp((1.5 if storage == "f16" else 3.0) * rng.standard_normal(shape)).astype(np.float32)
+
+
+def layer_patterns(layer, rng, storage="f32"):
+    """-> list of (name, x, skip): one NaN voxel at every position, one +inf and one -inf voxel at the interior and
+    the largest tile edges, and for the layers with a skip tensor a NaN and an inf in the skip only."""
+    ci, _, _, tr, shape = P.GEOM[layer]
+    base = background((ci,) + shape, rng, storage)
+    skip = rng.standard_normal(out_shape(layer)).astype(np.float32) if tr else None
+    out = []
+    for value, tag, full in ((np.nan, "nan", True), (np.inf, "+inf", False), (-np.inf, "-inf", False)):
+        for name, pos in voxel_positions(layer, full).items():
+            x = base.copy()
+            x[pos] = value
+            out.append(("%s@%s" % (tag, name), x, skip))
+    if tr:
+        co, D2, H2, W2 = skip.shape
+        for value, tag in ((np.nan, "nan"), (np.inf, "+inf"), (-np.inf, "-inf")):
+            for name, pos in (("interior", (3, D2 // 2, H2 // 2, W2 // 2)), ("corner", (co - 1, D2 - 1, H2 - 1, W2 - 1))):
+                s = skip.copy()
+                s[pos] = value
+                out.append(("skip %s@%s" % (tag, name), base, s))
+    return out
+
+
+def tail_patterns(rng, storage="f32"):
+    """conv11_prob: a non-finite voxel in x, and in the skip only, which is a non-finite value in prob's input."""
+    D, H, W = P.TAIL_SHAPE
+    base = background((16, D, H, W), rng, storage)
+    skip = rng.standard_normal((8, 2 * D, 2 * H, 2 * W)).astype(np.float32)
+    out = []
+    for value, tag in ((np.nan, "nan"), (np.inf, "+inf"), (-np.inf, "-inf")):
+        for name, pos in (("interior", (5, D // 2 - 1, H // 2, W // 2 - 1)), ("x3", (2, 3, 3, 3)), ("x4", (9, 3, 3, 4)),
+                          ("corner", (15, D - 1, H - 1, W - 1))):
+            x = base.copy()
+            x[pos] = value
+            out.append(("%s@%s" % (tag, name), x, skip))
+        for name, pos in (("interior", (3, D, H, W)), ("x15", (1, D, H, 15)), ("x16", (6, D, H, 16)),
+                          ("corner", (7, 2 * D - 1, 2 * H - 1, 2 * W - 1))):
+            s = skip.copy()
+            s[pos] = value
+            out.append(("skip %s@%s" % (tag, name), base, s))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the references
+# ---------------------------------------------------------------------------------------------------------------
+def _zeroed(a):
+    return None if a is None else np.where(np.isfinite(a), a, 0).astype(np.float32)
+
+
+def layer_reference(layer, x, skip, wf, sh, storage="f32", wino=None):
+    """-> (ref, bound, touched): probes.dense_ref_bound on the tensor as stored (16-bit: the matched reference), the
+    bound's scale of the input with its non-finite entries replaced by 0, and the touched voxels [D,H,W]."""
+    with np.errstate(all="ignore"):
+        ref, _ = P.dense_ref_bound(layer, x, skip, wf, sh, storage, wino)
+        _, bound = P.dense_ref_bound(layer, _zeroed(x), _zeroed(skip), wf, sh, storage, wino)
+        q = lambda t: orc.round_storage(np.asarray(t, np.float32), storage)  # noqa: E731
+        w16 = wf if (storage == "f32" or layer == 10) else q(wf)
+        pre = P._conv64(layer, q(x), w16) + np.asarray(sh, np.float64)[:, None, None, None]
+        touched = ~np.isfinite(pre)
+        if skip is not None:
+            touched |= ~np.isfinite(skip)
+    return ref, bound, touched.any(0)
+
+
+def tail_reference(x, skip, w9, sh9, pw, pb, storage="f32"):
+    """conv11_prob: probes.tail64 on the stored tensors (conv11's output + skip is never rounded) -> (ref, bound,
+    touched) of the logits [D,H,W]."""
+    q = lambda t: orc.round_storage(np.asarray(t, np.float32), storage)  # noqa: E731
+    wq = w9 if storage == "f32" else q(w9)
+    with np.errstate(all="ignore"):
+        ref, _ = P.tail64(q(x), q(skip), wq, sh9, pw, pb)
+        _, S = P.tail64(_zeroed(q(x)), _zeroed(q(skip)), wq, sh9, pw, pb)
+        d11 = P._conv64(9, q(x), wq) + np.asarray(sh9, np.float64)[:, None, None, None] + q(skip)
+        pre = P._conv64(10, np.where(np.isfinite(d11), 0.0, np.nan), np.ones_like(pw))
+    return ref, P.DENSE_C * P.U * S, ~np.isfinite(pre[0])
+
+
+def ref64_keeps_nan():
+    """The reference's ReLU keeps NaN and maps -inf to 0, +inf to +inf (F.relu: [nan, 0, inf])."""
+    wf = np.ones((8, 32, 3, 3, 3), np.float32)
+    y = []
+    for v in (np.nan, -np.inf, np.inf):
+        x = np.zeros((32, 1, 1, 1), np.float32)
+        x[0] = v
+        with np.errstate(all="ignore"):
+            y.append(P.ref64(0, x, wf, np.zeros(8, np.float32))[0, 0, 0, 0])
+    t = torch.relu(torch.tensor([np.nan, -np.inf, np.inf])).numpy()
+    return (np.isnan(y[0]) and y[1] == 0.0 and y[2] == np.inf and np.isnan(t[0]) and t[1] == 0 and t[2] == np.inf)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the checker
+# ---------------------------------------------------------------------------------------------------------------
+def dilate(mask, extent):
+    """mask [..., D, H, W] grown by (ez, ey, ex) voxels."""
+    if not any(extent):
+        return mask
+    m = torch.from_numpy(np.ascontiguousarray(mask, dtype=np.float32)).reshape((1, 1) + mask.shape[-3:])
+    k = tuple(2 * e + 1 for e in extent)
+    return F.max_pool3d(m, kernel_size=k, stride=1, padding=tuple(extent))[0, 0].numpy() > 0
+
+
+def spread(stray, touched):
+    """Largest per-axis distance of a stray voxel from the touched set's bounding box (what a run reports next to the
+    table's extent)."""
+    if not stray.any() or not touched.any():
+        return (0, 0, 0)
+    out = []
+    for ax in range(3):
+        t = np.nonzero(touched.any(tuple(a for a in range(3) if a != ax)))[0]
+        s = np.nonzero(stray.any(tuple(a for a in range(3) if a != ax)))[0]
+        out.append(int(max(t.min() - s.min(), s.max() - t.max(), 0)))
+    return tuple(out)
+
+
+class Checker:
+    """Collects R1 / R2 / R3 violations with the first offending index, the worst R2 ratio and the widest spread."""
+
+    def __init__(self):
+        self.ratios, self.spreads, self.failures = {}, {}, []
+
+    def _fail(self, key, name, rule, mask, got, ref):
+        i = tuple(int(v) for v in np.argwhere(mask)[0])
+        self.failures.append("%s [%s]: %s at %s: got %r, reference %r (%d elements)"
+                             % (key, name, rule, i, float(got[i]), float(ref[i]), int(mask.sum())))
+
+    def check(self, key, name, got, ref, bound, touched, extent):
+        """got, ref, bound [..., D, H, W] (float64); touched [D, H, W]."""
+        got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+        nf_ref, nf_got = ~np.isfinite(ref), ~np.isfinite(got)
+        hidden = nf_ref & ~nf_got
+        if hidden.any():
+            self._fail(key, name, "R1 a finite value hides a non-finite one", hidden, got, ref)
+        lost = np.isnan(ref) & ~np.isnan(got) & nf_got
+        if lost.any():
+            self._fail(key, name, "R1 NaN came back as an infinity", lost, got, ref)
+        stray = nf_got & ~nf_ref
+        stray_vox = stray.reshape((-1,) + stray.shape[-3:]).any(0) & ~touched
+        sp = spread(stray_vox, touched)
+        self.spreads[key] = tuple(max(a, b) for a, b in zip(self.spreads.get(key, (0, 0, 0)), sp))
+        outside = stray & ~dilate(touched, extent)
+        if outside.any():
+            self._fail(key, name, "R3 non-finite beyond extent %s of the touched set (spread %s)" % (extent, sp),
+                       outside, got, ref)
+        ok = ~nf_got & ~nf_ref
+        with np.errstate(all="ignore"):
+            r = np.where(ok, np.abs(got - ref) / bound, 0.0)
+        r = np.where(np.isnan(r), np.inf, r)
+        worst = float(r.max()) if r.size else 0.0
+        self.ratios[key] = max(self.ratios.get(key, 0.0), worst)
+        if worst > 1.0:
+            i = np.unravel_index(int(np.argmax(r)), r.shape)
+            self.failures.append("%s [%s]: R2 %.3g x bound at %s: got %r, reference %r (%d elements over)"
+                                 % (key, name, worst, tuple(int(v) for v in i), float(got[i]), float(ref[i]),
+                                    int((r > 1).sum())))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# soft-argmin
+# ---------------------------------------------------------------------------------------------------------------
+SOFTARGMIN_PATTERNS = ("nan_first", "nan_last", "nan_edge", "nan_ragged", "nan_all", "+inf", "-inf_first", "-inf_mid",
+                       "-inf_slice", "-inf_all")
+
+
+def softargmin_case(form, seed=0):
+    """One launch of a form-forcing shape (softargmin_ref.FORM_SHAPES) with every pattern on pixels of its own, spread
+    over the map so that each sits in a block among untouched pixels: a NaN logit in the first slice (d = 0), in the
+    last (d = D - 1), on a slice edge and in the ragged last block; a pixel of NaN logits only; one +inf logit; one
+    -inf logit at d = 0 (the first logit a slice meets) and mid-slice, a whole slice of -inf (both layouts' first
+    slice), and a pixel of -inf logits only.  -> dict(cost, dv, h, w, pixels: pattern -> pixel indices)."""
+    D, (h, w) = sar.FORM_SHAPES[form]
+    P_ = h * w
+    cost = sar.logits("gain3", D, P_, 900 + seed)
+    dv = sar.depth_axis("dtu", D)
+    per = max(-(-D // 8), -(-D // 16))
+    edge = sar.slice_boundaries(D)[len(sar.slice_boundaries(D)) // 2]
+    pixels = {}
+    for k, name in enumerate(SOFTARGMIN_PATTERNS):
+        pix = np.array([37 + 101 * k, P_ // 2 + 13 * k, P_ - 64 - 3 * k]) if name != "nan_ragged" else \
+            np.array([P_ - 1, P_ - 3])            # neither map size is a multiple of 16: the last block is ragged
+        pixels[name] = pix
+        if name == "nan_first":
+            cost[0, pix] = np.nan
+        elif name == "nan_last" or name == "nan_ragged":
+            cost[D - 1, pix] = np.nan
+        elif name == "nan_edge":
+            cost[edge - 1, pix[0]] = np.nan
+            cost[edge, pix[1:]] = np.nan
+        elif name == "nan_all":
+            cost[:, pix] = np.nan
+        elif name == "+inf":
+            cost[D // 3, pix] = np.inf
+        elif name == "-inf_first":
+            cost[0, pix] = -np.inf
+        elif name == "-inf_mid":
+            cost[D // 2 + 1, pix] = -np.inf
+        elif name == "-inf_slice":
+            cost[:per, pix] = -np.inf
+        elif name == "-inf_all":
+            cost[:, pix] = -np.inf
+    return dict(cost=cost, dv=dv, h=h, w=w, pixels=pixels)
+
+
+NAN_PATTERNS = ("nan_first", "nan_last", "nan_edge", "nan_ragged", "nan_all", "+inf", "-inf_all")
+
+
+def softmax_nan64(cost):
+    """Pixels where fp64 softmax-then-sum is NaN: np.max and the sums keep NaN, inf - inf and -inf - -inf are NaN."""
+    c = np.asarray(cost, np.float64)
+    with np.errstate(all="ignore"):
+        e = np.exp(c - c.max(0))
+        p = e / e.sum(0)
+        return np.isnan(p.sum(0))
+
+
+def check_softargmin(depth, conf, cost, dv, pixels=None):
+    """-> (worst depth ratio, worst conf ratio, problems).  `pixels`: hold only the 32-pixel blocks around these pixels
+    to the bound (the neighbours a block shares its LDS with); every pixel's NaN-ness is checked regardless.  depth and conf are NaN exactly where the fp64 softmax is
+    (the reference's trunc of a NaN expectation clamps to some index of an all-NaN probability row: NaN whichever);
+    everywhere else softargmin_ref's bound holds, a -inf logit standing as a term of exactly 0 (-1e5 in the
+    reference: exp underflows to 0 in fp64, the depth is removed and charged nothing)."""
+    depth, conf = np.asarray(depth, np.float64).ravel(), np.asarray(conf, np.float64).ravel()
+    want_nan = softmax_nan64(cost)
+    problems = []
+    for what, got in (("depth", depth), ("conf", conf)):
+        bad = np.isnan(got) != want_nan
+        if bad.any():
+            i = int(np.argwhere(bad)[0, 0])
+            problems.append("%s: NaN set differs at pixel %d: got %r, reference is %s (%d pixels)"
+                            % (what, i, float(got[i]), "NaN" if want_nan[i] else "finite", int(bad.sum())))
+    fin = ~want_nan
+    if pixels is not None:
+        near = np.zeros(fin.shape, bool)
+        for p in np.asarray(pixels).ravel():
+            near[p // 32 * 32:p // 32 * 32 + 32] = True
+        fin &= near
+    c = np.where(np.isneginf(cost[:, fin]), np.float32(-1e5), cost[:, fin])
+    ref = sar.reference(c, dv)
+    d, k = np.where(np.isfinite(depth[fin]), depth[fin], np.inf), np.where(np.isfinite(conf[fin]), conf[fin], np.inf)
+    rd, rc, pr = sar.check_forward(d, k, ref)
+    return rd, rc, problems + pr
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the chain: mvs_costreg_forward + mvs_softargmin_conf and mvs_depth_infer at D = 8, h = 8, w = 160
+# ---------------------------------------------------------------------------------------------------------------
+CHAIN_SHAPE = (8, 8, 160)
+CHAIN_VOXEL = (5, 3, 4, 2)
+MIN_FINITE_GOT, MIN_FINITE_REF_VOXEL, MIN_FINITE_REF_RIG = 0.5, 0.79, 0.6
+# test_gpu_parity's tolerances: fp32 logits |got - ref| <= 3e-4 max|ref| (the 16-bit ratio, with 2 eps |ref| of slack, is
+# reported only: parity holds a 16-bit chain to the depth alone), depth: relative L1 per storage
+CHAIN_EPS = {"f32": 0.0, "f16": 2.0 ** -11, "bf16": 2.0 ** -8}
+CHAIN_DEPTH_L1 = {"f32": 1e-5, "f16": 2e-4, "bf16": 1e-3}
+
+
+def chain_voxel_volume(seed=3):
+    D, h, w = CHAIN_SHAPE
+    var = (np.random.default_rng(seed).random((32, D, h, w)) + 0.05).astype(np.float32)
+    var[CHAIN_VOXEL] = np.nan
+    return var
+
+
+def chain_rig(w=CHAIN_SHAPE[2]):
+    """warp_ref's `behind` (z0) rig at the chain's shape: source row 2 = (1/8, 0, 1, -4) makes Z = (x/8 + 1) d - 4 an
+    exact zero at (x, d) = (0, 4), (8, 2) and (24, 1) for every row, so the warp itself writes NaN columns there."""
+    from scene_3dreconstruction_mvsnet_amd import synthetic
+    D, h, _ = CHAIN_SHAPE
+    s1, s2 = np.eye(4), np.eye(4)
+    s1[2, 0], s1[2, 3], s1[0, 3], s1[1, 3] = 0.125, -4.0, 96.0, -2.0
+    s2[0, 3], s2[1, 3], s2[2, 3] = 6.0, 2.0, 1.0
+    dv = (0.5 * np.arange(2, D + 2)).astype(np.float32)
+    return dict(feats=synthetic.random_features(3, 32, h, w, seed=25), proj=np.stack([np.eye(4), s1, s2]).astype(np.float32),
+                dv=dv)
+
+
+def chain_allowed(touched0, storage):
+    """The touched voxels of the variance volume [D,h,w] carried through the eleven layers, each level grown by the
+    largest extent of the kernels that can serve it -> the pixels [h,w] whose logits may be non-finite."""
+    kern = CHAIN_KERNELS["f32" if storage == "f32" else "b16"]
+    ext = lambda l: tuple(max(e) for e in zip(*(EXTENTS[k] for k in kern[l])))  # noqa: E731
+
+    def through(layer, m):
+        x = m[None].astype(np.float64) * np.ones((P.GEOM[layer][0], 1, 1, 1))
+        return P._conv64(layer, x, np.ones((P.GEOM[layer][1], P.GEOM[layer][0], 3, 3, 3))).any(0) != 0
+
+    c0 = dilate(through(0, touched0), ext(0))
+    c1 = dilate(through(1, c0), ext(1))
+    c2 = dilate(through(2, c1), ext(2))
+    c3 = dilate(through(3, c2), ext(3))
+    c4 = dilate(through(4, c3), ext(4))
+    c5 = dilate(through(5, c4), ext(5))
+    c6 = dilate(through(6, c5), ext(6))
+    x = dilate(through(7, c6) | c4, ext(7))
+    x = dilate(through(8, x) | c2, ext(8))
+    x = dilate(through(9, x) | c0, ext("tail"))
+    return dilate(through(10, x), (0, 0, 0)).any(0)

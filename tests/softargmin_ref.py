@@ -403,7 +403,9 @@ def _rcp(x, ulps=0):
 
 def emulate_forward(cost, dv, hw_form=None, exp_ulps=0, rcp_ulps=0, defect=None):
     """cost [D,P] fp32 -> (depth, conf) [P] fp32 as launch_softargmin's form for (D, P) computes them; hw_form
-    overrides P in the form choice (a small P standing in for a large map)."""
+    overrides P in the form choice (a small P standing in for a large map).  A -inf logit is a term of exactly 0, as
+    in the kernels; defect "minus_inf_term_nan" (not in FWD_DEFECTS: it shows on non-finite logits only,
+    test_nonfinite_host.py) computes expf(-inf - m) instead, NaN while the slice's maximum is still -inf."""
     c = np.asarray(cost, f32)
     dv = np.asarray(dv, f32)
     D, P = c.shape
@@ -426,7 +428,7 @@ def emulate_forward(cost, dv, hw_form=None, exp_ulps=0, rcp_ulps=0, defect=None)
             if maxper is not None:
                 m = c[d0:d1].max(0)
                 for d in range(d0, d1):
-                    e = ex(c[d] - m)
+                    e = ex(c[d] - m) if defect == "minus_inf_term_nan" else np.where(c[d] == -np.inf, f32(0), ex(c[d] - m))
                     s = s + e
                     sd = _fma(e, dv[d], sd)
                     si = _fma(e, f32(d), si)
@@ -437,7 +439,7 @@ def emulate_forward(cost, dv, hw_form=None, exp_ulps=0, rcp_ulps=0, defect=None)
                     r = np.where(up, ex(m - c[d]), f32(1))
                     s, sd, si = np.where(up, s * r, s), np.where(up, sd * r, sd), np.where(up, si * r, si)
                     m = np.where(up, c[d], m)
-                    e = ex(c[d] - m)
+                    e = ex(c[d] - m) if defect == "minus_inf_term_nan" else np.where(c[d] == -np.inf, f32(0), ex(c[d] - m))
                     s = s + e
                     sd = _fma(e, dv[d], sd)
                     si = _fma(e, f32(d), si)

@@ -225,7 +225,9 @@ CONV_SOURCES = ("conv3d_direct.hip", "conv3d_mfma.hip", "conv3d_mfma16.hip", "co
                 "conv_winograd.hip", "conv0_split.hip", "conv11_prob.hip")
 
 
-def test_every_conv_instantiation_and_kernel_has_a_probe_case():
+def parse_conv_sources():
+    """-> (launcher instantiations `run_x<...>`, kernel names) found in the conv sources (shared with
+    test_nonfinite_host.py)."""
     inst, kern = set(), set()
     for name in CONV_SOURCES:
         src = _read(name)
@@ -235,6 +237,11 @@ def test_every_conv_instantiation_and_kernel_has_a_probe_case():
                 continue   # a launcher forwarding its own template parameters, not an instantiation
             inst.add(f"{m.group(1)}<{args}>")
         kern |= set(re.findall(r"\b(\w+_kernel)\s*(?:<[^<>;]*>)?\s*<<<", src))
+    return inst, kern
+
+
+def test_every_conv_instantiation_and_kernel_has_a_probe_case():
+    inst, kern = parse_conv_sources()
     assert inst, "no run_*<...> instantiation found: the parser no longer matches the sources"
     assert not inst - set(INSTANTIATIONS), f"instantiations without a probe case: {sorted(inst - set(INSTANTIATIONS))}"
     assert not kern - set(KERNELS), f"kernels without a probe case: {sorted(kern - set(KERNELS))}"
