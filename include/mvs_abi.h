@@ -40,7 +40,8 @@ extern "C" {
  * mvs_query_metrics_workspace, mvs_depth_metrics, mvs_warp_variance_backward, mvs_softargmin_backward,
  * mvs_query_conv3d_train_workspace, mvs_conv3d_train_forward, mvs_conv3d_train_backward_data,
  * mvs_conv3d_train_backward_weight, mvs_feature_conv01_fmt, mvs_query_bn3d_train_workspace, mvs_bn3d_train_forward,
- * mvs_bn3d_train_backward, mvs_volume_relayout. */
+ * mvs_bn3d_train_backward, mvs_volume_relayout; and, declared in a header of their own, include/mvs_fuse_abi.h:
+ * mvs_query_fuse_workspace, mvs_fuse_points. */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {
@@ -206,7 +207,8 @@ int mvs_depth_regression(const float* p, const float* depth_values, float* depth
  *     depth_avg double [R][h][w]     (sum of agreeing reprojected depths + d_ref)/(geo_sum+1) (699)
  *     masks     uint8  [R][3][h][w]  photo, geo, final as 0/1                    (660, 702, 706)
  *     xyz_world double [R][h*w][3]   depth2pts_np(depth_avg, K_ref, E_ref)       (752, 253-265)
- *   Selecting xyz_world[final] and the colours (eval.py:753-759) stays with the caller.
+ *   Selecting xyz_world[final] and the colours (eval.py:753-759) stays with the caller (or with mvs_fuse_points,
+ *   include/mvs_fuse_abi.h).
  *   Index contract: mvs_filter_compose rejects a ref_idx outside [0,V) and a src_idx >= V with
  *   MVS_ERR_BAD_SHAPE, and ref_idx / src_idx handed to mvs_filter_depth must be the arrays it
  *   accepted.  mvs_filter_depth cannot read device memory on the host and does not validate them:

@@ -4,8 +4,10 @@
 (SURVEY.md §8 f3).
 
 All reference views of a scan go through ONE launch of `mvs_filter_depth`; the numpy / cv2.remap
-loops of the reference are not reproduced on the host.  What stays on the host is file I/O and the
-boolean selection of the fused points (eval.py:753-759).
+loops of the reference are not reproduced on the host.  In `filter_depth`, which works from the depth stage's files,
+file I/O and the boolean selection of the fused points (eval.py:753-759) stay on the host.  `fuse_views` does that
+selection on the device (mvs_fuse_points), and `reconstruct_scan` is the whole chain -- images of a scan in, its
+coloured point cloud out -- without a file in between.
 
 Differences from the reference, flagged rather than hidden:
   * cv2.remap is restated inside the kernel (1/32-pixel quantised bilinear, zero border); OpenCV is
@@ -135,6 +137,139 @@ def filter_depth(scan_out_folder: str, pair_file: str, plyfilename: str | None =
         colours.append((img[1::4, 1::4, :][final] * 255).astype(np.uint8))         # eval.py:755,759
     vertices = np.concatenate(vertices, 0)
     colours = np.concatenate(colours, 0)
+    if plyfilename:
+        write_ply(plyfilename, vertices, colours)
+    return vertices, colours
+
+
+_DECODE_THREADS = 16     # reconstruct_scan's image decoders (the eval driver's default)
+
+
+def fuse_views(filtered, images, pairs_or_ref_idx, capacity=None):
+    """The fused, coloured points of every reference view (eval.py:745-758) from what `filter_views` returned.
+
+    filtered: the dict of filter_views (masks [R,3,h,w], xyz_world [R,h*w,3], on the GPU).  images: uint8 [V,H,W,3] or
+    [V,3,H,W] (numpy or torch, host or device), index = view id; float32 [V,3,H,W] in [0,1] is converted on the
+    device with (img*255).to(uint8), the depth stage's np.uint8(img*255) (eval.py:346-350).  pairs_or_ref_idx: the
+    pair list handed to filter_views, or the image index of each reference view.  Returns (xyz float32 [P,3],
+    rgb uint8 [P,3]) on the device, in the reference's order, and the per-view counts (numpy int32 [R]).  Reading the
+    counts is the one host synchronisation.  capacity (default R*h*w, always enough) bounds the device buffers."""
+    masks, xyz_world = filtered["masks"], filtered["xyz_world"]
+    dev = xyz_world.device
+    R, _, h, w = masks.shape
+    images = torch.as_tensor(images) if not torch.is_tensor(images) else images
+    if images.dim() != 4 or images.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError(f"fuse_views: images must be uint8 [V,H,W,3] / [V,3,H,W] or float32 [V,3,H,W], got "
+                           f"{images.dtype} {tuple(images.shape)}")
+    images = images.to(dev)
+    if images.dtype == torch.float32:
+        if images.shape[1] != 3:
+            raise RuntimeError(f"fuse_views: float32 images must be [V,3,H,W], got {tuple(images.shape)}")
+        images = (images * 255).to(torch.uint8)
+    hwc = images.shape[1] != 3 and images.shape[3] == 3
+    H, W = (images.shape[1], images.shape[2]) if hwc else (images.shape[2], images.shape[3])
+    if (H, W) != (4 * h, 4 * w):
+        raise RuntimeError(f"images are {H}x{W}, depth maps {h}x{w}: incompatible depth and image dimensions.")
+    ref = [p[0] if isinstance(p, (tuple, list)) else p for p in
+           (pairs_or_ref_idx.tolist() if torch.is_tensor(pairs_or_ref_idx) else list(pairs_or_ref_idx))]
+    if len(ref) != R:
+        raise RuntimeError(f"fuse_views: {len(ref)} reference views named, the filter produced {R}")
+    ref_idx = torch.tensor([int(r) for r in ref], dtype=torch.int32).to(dev)
+    xyz, rgb, counts = _lib.fuse_points(xyz_world, masks, images, ref_idx, capacity=capacity)
+    counts = counts.cpu().numpy()
+    total = int(counts[-1])
+    if total > xyz.shape[0]:
+        raise RuntimeError(f"fuse_views: the scan has {total} fused points, capacity is {xyz.shape[0]}")
+    return xyz[:total], rgb[:total], counts[:-1]
+
+
+def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8, geomask=3, condmask_pixel=1.0,
+                     condmask_depth=0.01, plyfilename=None, batch=1, device=None):
+    """eval.py's save_depth + filter_depth for one scan of an EvalDataset, in memory: every image is decoded once (as
+    uint8), FeatureNet runs once per image, every reference view's depth and confidence map is computed from that
+    feature bank, and the maps are filtered and fused on the device.  No file is written except the optional PLY; the
+    packed points are the one device-to-host copy.  The cameras of the filter are the ones each sample carries for its
+    reference view (what the depth stage writes to cams/).  `batch` maps go through one forward_features call.
+    Returns (vertices float32 [P,3], colours uint8 [P,3]); the PLY equals `filter_depth`'s byte for byte."""
+    import copy
+    for a in ("view_plan", "decode_view", "assemble", "metas"):
+        if not hasattr(dataset, a):
+            raise ValueError("reconstruct_scan needs a dataset with metas, view_plan(), decode_view() and assemble(), "
+                             "e.g. dataset_eval.EvalDataset")
+    if not all(hasattr(model, a) for a in ("extract_features", "forward_features")):
+        raise ValueError("reconstruct_scan needs a model with extract_features / forward_features (MVSNet)")
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    scans = list(dict.fromkeys(m[0] for m in dataset.metas))
+    if scan is None:
+        if len(scans) != 1:
+            raise ValueError(f"the dataset holds {len(scans)} scans: name one of {scans}")
+        scan = scans[0]
+    indices = [i for i, m in enumerate(dataset.metas) if m[0] == scan]
+    if not indices:
+        raise ValueError(f"scan {scan!r} is not in the dataset ({scans})")
+    if getattr(dataset, "image_dtype", "uint8") != "uint8":
+        dataset = copy.copy(dataset)          # same files and caches; the pixels stay bytes
+        dataset.image_dtype = "uint8"
+    pairs = [(dataset.metas[i][1], list(dataset.metas[i][2])) for i in indices]
+    refs = [r for r, _ in pairs]
+    if len(set(refs)) != len(refs):
+        raise ValueError(f"scan {scan!r} lists a reference view twice")
+    missing = sorted({s for _, ss in pairs for s in ss[:n_view_filter]} - set(refs))
+    if missing:
+        raise ValueError(f"views {missing} are filter sources of scan {scan!r} but no reference view: they get no depth map")
+    # every image once, on a few threads (PIL's decoding releases the GIL)
+    plans, paths = [], {}
+    for i in indices:
+        _, views = dataset.view_plan(i)
+        ids = ([dataset.metas[i][1]] + list(dataset.metas[i][2]))[:len(views)]
+        plans.append((i, ids))
+        for vid, (img_path, _) in zip(ids, views):
+            paths.setdefault(vid, img_path)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=min(_DECODE_THREADS, len(paths))) as pool:
+        decoded = dict(zip(paths, pool.map(dataset.decode_view, paths.values())))
+    pixels = {v: d[0] for v, d in decoded.items()}
+    adjust = {v: d[1] for v, d in decoded.items()}
+    samples = [(ids, dataset.assemble(i, [adjust[v] for v in ids])) for i, ids in plans]
+    shapes = {tuple(np.asarray(a).shape) for a in pixels.values()}
+    if len(shapes) != 1:
+        raise ValueError(f"the views of scan {scan!r} differ in size: {sorted(shapes)}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("reconstruct_scan needs the GPU: libmvs_hip has no CPU implementation")
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    present = sorted(pixels)
+    slot = {v: k for k, v in enumerate(present)}
+    V = max(present) + 1
+    Ks = np.tile(np.eye(3, dtype=np.float32), (V, 1, 1))
+    Es = np.tile(np.eye(4, dtype=np.float32), (V, 1, 1))
+    model = model.to(device).eval()
+    with torch.cuda.device(device), torch.no_grad():
+        imgs = torch.from_numpy(np.stack([np.asarray(pixels[v]) for v in present])).to(device)
+        feats = model.extract_features(imgs)
+        h, w = feats.shape[2], feats.shape[3]
+        depths = torch.zeros((V, h, w), dtype=torch.float32, device=device)
+        confs = torch.zeros((V, h, w), dtype=torch.float32, device=device)
+        for g in range(0, len(samples), batch):
+            group = samples[g:g + batch]
+            same = all(s["proj_matrices"].shape == group[0][1]["proj_matrices"].shape and
+                       s["depth_values"].shape == group[0][1]["depth_values"].shape for _, s in group)
+            for chunk in ([group] if same else [[x] for x in group]):
+                out = model.forward_features(
+                    feats, [[slot[v] for v in ids] for ids, _ in chunk],
+                    torch.from_numpy(np.stack([np.asarray(s["proj_matrices"], np.float32) for _, s in chunk])).to(device),
+                    torch.from_numpy(np.stack([np.asarray(s["depth_values"], np.float32) for _, s in chunk])).to(device))
+                for b, (ids, s) in enumerate(chunk):
+                    depths[ids[0]] = out["depth"][b]
+                    confs[ids[0]] = out["photometric_confidence"][b]
+                    Ks[ids[0]], Es[ids[0]] = np.asarray(s["intrinsics"][0]), np.asarray(s["extrinsics"][0])
+        filtered = filter_views(depths, confs, Ks, Es, pairs, n_view_filter, photomask, geomask, condmask_pixel,
+                                condmask_depth, device)
+        xyz, rgb, _ = fuse_views(filtered, imgs, [slot[r] for r in refs])
+        P = xyz.shape[0]
+        packed = torch.cat([xyz.reshape(-1).view(torch.uint8), rgb.reshape(-1)]).cpu().numpy()   # the one copy
+    vertices = packed[:12 * P].view(np.float32).reshape(P, 3)
+    colours = packed[12 * P:].reshape(P, 3)
     if plyfilename:
         write_ply(plyfilename, vertices, colours)
     return vertices, colours

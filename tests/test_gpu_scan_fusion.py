@@ -1,0 +1,431 @@
+"""mvs_fuse_points / fusion.fuse_views / fusion.reconstruct_scan on the GPU, held to tests/fuse_ref.py bit for bit:
+no tolerance anywhere.  The scenes take their masks and points from the existing fusion.filter_views; the edge cases
+write their masks directly and code each point's (view, pixel) into its coordinates, so a point in the wrong place
+cannot compare equal."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import fuse_ref
+import guarded as G
+from conftest import load_weights
+from scene_3dreconstruction_mvsnet_amd import MVSNet, _lib, fusion
+from synthetic_scene import make_scene
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+T = _lib.FUSE_TILE
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def cu(a):
+    return torch.from_numpy(np.array(a, order="C")).to(DEV)      # a copy: the cached scenes are read-only
+
+
+def coded_xyz(R, hw):
+    """float64 [R,hw,3] = (view + 0.3, pixel + 0.7, view * hw + pixel + 0.1): distinct per point, none a float32."""
+    r = np.arange(R, dtype=np.float64)[:, None]
+    p = np.arange(hw, dtype=np.float64)[None, :]
+    return np.stack([np.broadcast_to(r + 0.3, (R, hw)), np.broadcast_to(p + 0.7, (R, hw)), r * hw + p + 0.1], -1)
+
+
+def random_images(V, h, w, seed=5, hwc=True):
+    img = np.random.default_rng(seed).integers(0, 256, size=(V, 4 * h, 4 * w, 3), dtype=np.uint8)
+    return img if hwc else np.ascontiguousarray(img.transpose(0, 3, 1, 2))
+
+
+def final_masks(R, h, w, selected):
+    """masks [R,3,h,w] uint8 with plane 2 set at the flat (view-major) indices `selected`; the photo and geo planes
+    are all ones, so a kernel that read the wrong plane would select everything."""
+    m = np.zeros((R, 3, h * w), np.uint8)
+    m[:, :2] = 1
+    sel = np.asarray(selected, dtype=np.int64)
+    m[sel // (h * w), 2, sel % (h * w)] = 1
+    return m.reshape(R, 3, h, w)
+
+
+def run(xyz, masks, images, ref_idx, capacity=None, out=None):
+    x, c, n = _lib.fuse_points(cu(xyz), cu(masks), cu(images), cu(np.asarray(ref_idx, np.int32)), capacity=capacity, out=out)
+    torch.cuda.synchronize()
+    return x.cpu().numpy(), c.cpu().numpy(), n.cpu().numpy()
+
+
+def check(xyz, masks, images, ref_idx, hwc=True):
+    """Bit-equality with fuse_ref at the default capacity -> the counts."""
+    want = fuse_ref.fuse(xyz, masks, images, ref_idx, hwc=hwc)
+    x, c, n = run(xyz, masks, images, ref_idx)
+    total = int(want[2][-1])
+    np.testing.assert_array_equal(n, want[2])
+    assert x.shape == (masks.shape[0] * masks.shape[2] * masks.shape[3], 3) and x.dtype == np.float32 and c.dtype == np.uint8
+    np.testing.assert_array_equal(x[:total], want[0])
+    np.testing.assert_array_equal(c[:total], want[1])
+    return n
+
+
+# ---------------------------------------------------------------- scenes through the existing filter
+SCENES = {"v3_5x7": dict(V=3, h=5, w=7, geomask=1),            # smaller than one wave; view 2 keeps no point
+          "v7_37x53": dict(V=7, h=37, w=53, geomask=3),        # h*w = 1961: odd, no multiple of any tile
+          "v6_64x80": dict(V=6, h=64, w=80, geomask=3),
+          "v12_128x160": dict(V=12, h=128, w=160, geomask=3)}  # cfg2's map size
+_scene_cache = {}
+
+
+def scene(name):
+    """(xyz_world, masks, pairs) of a scene as host arrays, computed once by fusion.filter_views and never changed."""
+    if name not in _scene_cache:
+        s = SCENES[name]
+        depths, confs, Ks, Es, pairs = make_scene(V=s["V"], h=s["h"], w=s["w"])
+        out = fusion.filter_views(depths, confs, Ks, Es, pairs, geomask=s["geomask"], device=DEV)
+        xyz, masks = out["xyz_world"].cpu().numpy(), out["masks"].cpu().numpy().astype(np.uint8)
+        xyz.setflags(write=False)
+        masks.setflags(write=False)
+        _scene_cache[name] = (xyz, masks, pairs)
+    return _scene_cache[name]
+
+
+@pytest.mark.parametrize("hwc", [True, False], ids=["hwc", "chw"])
+@pytest.mark.parametrize("name", list(SCENES))
+def test_scene_is_bit_equal_to_the_numpy_restatement(name, hwc):
+    """Per-view counts of the four scenes as the CPU oracle gives them: 6, 17, 0 | 180 ... 93 | 465 ... 383 |
+    2054 ... 1817 (shares 0.22, 0.09, 0.10, 0.11)."""
+    xyz, masks, pairs = scene(name)
+    s = SCENES[name]
+    share = float((masks[:, 2] != 0).mean())
+    assert 0.02 < share < 0.98, share       # a condition on the inputs: a degenerate mask is no compaction
+    images = random_images(s["V"], s["h"], s["w"], hwc=hwc)
+    counts = check(xyz, masks, images, [r for r, _ in pairs], hwc=hwc)
+    if name == "v3_5x7":
+        assert 0 in counts[:-1].tolist()    # the view without a point is in the case
+
+
+def test_bool_masks_and_fuse_views_give_the_same_points():
+    xyz, masks, pairs = scene("v7_37x53")
+    images = random_images(7, 37, 53)
+    want = fuse_ref.fuse(xyz, masks, images, [r for r, _ in pairs])
+    filtered = dict(masks=cu(masks).bool(), xyz_world=cu(xyz))
+    for imgs, where in ((images, "host uint8"), (cu(images), "device uint8"),
+                        (torch.from_numpy(images).permute(0, 3, 1, 2).contiguous(), "uint8 CHW"),
+                        # float32 [V,3,H,W] in [0,1], as the loader yields it: the writer's np.uint8(img * 255)
+                        (torch.from_numpy(images).permute(0, 3, 1, 2).to(torch.float32) / 255.0, "float32 CHW")):
+        x, c, n = fusion.fuse_views(filtered, imgs, pairs)
+        assert x.is_cuda and c.is_cuda and isinstance(n, np.ndarray), where
+        np.testing.assert_array_equal(x.cpu().numpy(), want[0], err_msg=where)
+        np.testing.assert_array_equal(c.cpu().numpy(), want[1], err_msg=where)
+        np.testing.assert_array_equal(n, want[2][:-1], err_msg=where)
+    x2, _, _ = fusion.fuse_views(filtered, images, torch.tensor([r for r, _ in pairs]))     # ref_idx instead of pairs
+    np.testing.assert_array_equal(x2.cpu().numpy(), want[0])
+
+
+# ---------------------------------------------------------------- edges, masks written directly
+def edge_case(R, h, w, selected, V=None, ref_idx=None, seed=11):
+    V = V or R
+    masks = final_masks(R, h, w, selected)
+    images = random_images(V, h, w, seed=seed)
+    return coded_xyz(R, h * w), masks, images, list(range(R)) if ref_idx is None else ref_idx
+
+
+def test_all_zero_and_all_one():
+    R, h, w = 3, 9, 13
+    n = check(*edge_case(R, h, w, []))
+    assert n.tolist() == [0, 0, 0, 0]
+    n = check(*edge_case(R, h, w, np.arange(R * h * w)))
+    assert n.tolist() == [h * w] * R + [R * h * w]
+
+
+def test_only_the_first_and_only_the_last_pixel():
+    R, h, w = 3, 37, 53
+    assert check(*edge_case(R, h, w, [0])).tolist() == [1, 0, 0, 1]
+    assert check(*edge_case(R, h, w, [R * h * w - 1])).tolist() == [0, 0, 1, 1]
+
+
+@pytest.mark.parametrize("h,w", [(32, 32), (25, 41), (33, 31), (50, 41)], ids=["tile", "tile+1", "tile-1", "2tiles+2"])
+def test_one_pixel_on_each_side_of_every_tile_wave_and_pass_boundary(h, w):
+    hw, R = h * w, 3
+    assert (hw - T) in (0, 1, -1, T + 2) and T == 1024
+    edges = sorted({0, hw - 1} | {k for b in range(0, hw + 1, 64) for k in (b - 1, b) if 0 <= k < hw and
+                                  (b % T == 0 or b % 256 == 0 or b in (64, 128))})
+    assert {T - 1, T} & set(edges) or hw < T
+    selected = [r * hw + p for r in range(R) for p in edges]
+    n = check(*edge_case(R, h, w, selected))
+    assert n.tolist() == [len(edges)] * R + [R * len(edges)]
+
+
+def test_more_tiles_than_two_passes_of_the_scan_kernel():
+    """n_tiles = 2 * R > 2 * MVS_FUSE_SCAN_WIDTH: the scan kernel runs three passes and carries the running total over
+    two pass boundaries.  h*w = tile + 1 gives every view a second tile of one pixel."""
+    W = _lib.FUSE_SCAN_WIDTH
+    h, w = 25, 41
+    R = W + 37
+    assert h * w == T + 1 and 2 * R > 2 * W and _lib.query_fuse_workspace(R, h, w) == 4 * (2 * R + 1)
+    rng = np.random.default_rng(3)
+    sel = np.flatnonzero(rng.random(R * h * w) < 0.3)
+    last = np.arange(R) * (h * w) + T                      # the lone pixel of each view's second tile, every other view
+    sel = np.union1d(np.setdiff1d(sel, last), last[::2])
+    xyz, masks, images, _ = edge_case(R, h, w, sel, V=3)
+    n = check(xyz, masks, images, [r % 3 for r in range(R)])
+    assert 0.02 < n[-1] / (R * h * w) < 0.98
+
+
+def test_out_of_range_views_contribute_nothing():
+    R, h, w, V = 5, 37, 53, 3
+    rng = np.random.default_rng(4)
+    sel = np.flatnonzero(rng.random(R * h * w) < 0.4)
+    xyz, masks, images, _ = edge_case(R, h, w, sel, V=V)
+    good = check(xyz, masks, images, [0, 1, 2, 1, 0])
+    n = check(xyz, masks, images, [0, -1, 2, V, 0])
+    assert n[1] == 0 and n[3] == 0 and n[[0, 2, 4]].tolist() == good[[0, 2, 4]].tolist()
+    assert n[-1] == good[0] + good[2] + good[4]
+
+
+def test_nan_and_infinity_come_through():
+    R, h, w = 2, 9, 13
+    xyz, masks, images, ref = edge_case(R, h, w, np.arange(0, R * h * w, 3))
+    xyz[0, 3] = [np.nan, 1.5, -np.inf]
+    xyz[1, 6] = [np.inf, np.nan, 1e300]          # 1e300 overflows float32: infinity, as numpy's assignment gives
+    xyz[1, 9] = [1e-300, -1e-46, 2.0 ** -149]    # underflow to +0 / -0 and the smallest subnormal
+    want = fuse_ref.fuse(xyz, masks, images, ref)
+    x, c, n = run(xyz, masks, images, ref)
+    total = int(n[-1])
+    np.testing.assert_array_equal(x[:total], want[0])       # NaN compares equal to NaN here
+    assert np.isnan(x[:total]).sum() == 2 and np.isinf(x[:total]).sum() == 3
+    finite = ~np.isnan(want[0])
+    assert np.array_equal(x[:total][finite].view(np.uint32), want[0][finite].view(np.uint32))   # signed zeros too
+    np.testing.assert_array_equal(c[:total], want[1])
+
+
+# ---------------------------------------------------------------- capacity
+def test_capacity_equal_to_below_and_zero():
+    R, h, w = 4, 37, 53
+    rng = np.random.default_rng(8)
+    xyz, masks, images, ref = edge_case(R, h, w, np.flatnonzero(rng.random(R * h * w) < 0.25))
+    want = fuse_ref.fuse(xyz, masks, images, ref)
+    total = int(want[2][-1])
+    assert total > T + 5 + 64                        # the cut at total - T - 5 leaves more than a wave
+    for capacity in (total, total - 1, total - T - 5, 1, 0):
+        big_x = torch.full((total + 8, 3), 777.0, dtype=torch.float32, device=DEV)
+        big_c = torch.full((total + 8, 3), 0x5A, dtype=torch.uint8, device=DEV)
+        counts = torch.full((R + 1,), -7, dtype=torch.int32, device=DEV)
+        x, c, n = run(xyz, masks, images, ref, capacity=capacity, out=(big_x[:capacity], big_c[:capacity], counts))
+        np.testing.assert_array_equal(n, want[2], err_msg=f"capacity {capacity}: the counts stay exact")
+        np.testing.assert_array_equal(x, want[0][:capacity])
+        np.testing.assert_array_equal(c, want[1][:capacity])
+        assert bool((big_x[capacity:] == 777.0).all()) and bool((big_c[capacity:] == 0x5A).all()), capacity
+    x, c, n = run(xyz, masks, images, ref, capacity=0)      # no buffers given: empty ones come back
+    assert x.shape == (0, 3) and c.shape == (0, 3)
+    np.testing.assert_array_equal(n, want[2])
+
+
+def test_fuse_views_raises_when_the_total_exceeds_the_capacity():
+    xyz, masks, pairs = scene("v7_37x53")
+    filtered = dict(masks=cu(masks), xyz_world=cu(xyz))
+    total = int((masks[:, 2] != 0).sum())
+    images = random_images(7, 37, 53)
+    assert fusion.fuse_views(filtered, images, pairs, capacity=total)[0].shape[0] == total
+    with pytest.raises(RuntimeError, match=f"{total} fused points, capacity is {total - 1}"):
+        fusion.fuse_views(filtered, images, pairs, capacity=total - 1)
+
+
+# ---------------------------------------------------------------- guarded buffers
+def fuse_device_entry_points():
+    """The same rule as test_gpu_guarded.device_entry_points, for the header of this addition: every `int mvs_*` it
+    declares that is not a mvs_query_* size query takes device buffers."""
+    with open(os.path.join(os.path.dirname(HERE), "include", "mvs_fuse_abi.h")) as f:
+        names = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", f.read(), re.M)
+    return [n for n in names if not n.startswith("mvs_query_")]
+
+
+GUARDED_ENTRIES = {"mvs_fuse_points": "test_every_buffer_between_guards_under_every_poison"}
+
+
+def test_every_device_entry_point_of_the_fuse_header_has_a_guarded_case():
+    names = fuse_device_entry_points()
+    assert names and set(names) == set(GUARDED_ENTRIES), (names, sorted(GUARDED_ENTRIES))
+    for test in GUARDED_ENTRIES.values():
+        assert callable(globals()[test])
+
+
+@pytest.mark.parametrize("hwc", [True, False], ids=["hwc", "chw"])
+def test_every_buffer_between_guards_under_every_poison(hwc):
+    xyz, masks, pairs = scene("v6_64x80")
+    images = random_images(6, 64, 80, hwc=hwc)
+    ref = np.array([r for r, _ in pairs], np.int32)
+    want = fuse_ref.fuse(xyz, masks, images, ref, hwc=hwc)
+    total = int(want[2][-1])
+    arena = G.Arena(16 << 20, DEV)
+    seen = []
+
+    def fn(a):
+        ins = [a.put(cu(t), name=n) for t, n in ((xyz, "xyz_world"), (masks, "masks"),
+                                                                        (images, "images"), (ref, "ref_idx"))]
+        with a.intercept(_lib):       # xyz, rgb, counts are carved as `out`, the workspace as `scratch`
+            x, c, n = _lib.fuse_points(*ins)
+        torch.cuda.synchronize()
+        assert int(n[-1]) == total
+        if isinstance(a, G.Arena):
+            roles = sorted(r.role for r in a.carved)
+            assert roles == ["in"] * 4 + ["out"] * 3 + ["scratch"], roles
+            ws = [r for r in a.carved if r.role == "scratch"][0]
+            assert ws.tensor.numel() == _lib.query_fuse_workspace(6, 64, 80)     # its guard starts at the next byte
+            # beyond the total nothing is written: the poison is still there
+            assert bool((G.raw_bytes(x[total:]) == a.poison).all()) and bool((G.raw_bytes(c[total:]) == a.poison).all())
+            seen.append(a.poison)
+        return x[:total], c[:total], n
+
+    guard_bytes = G.guarded_and_plain(arena, fn)
+    assert seen == list(G.POISONS) and guard_bytes >= 16 * G.MIN_GUARD
+    x, c, n = fn(G.Plain(DEV))
+    np.testing.assert_array_equal(x.cpu().numpy(), want[0])
+    np.testing.assert_array_equal(c.cpu().numpy(), want[1])
+    np.testing.assert_array_equal(n.cpu().numpy(), want[2])
+
+
+# ---------------------------------------------------------------- determinism, no synchronisation
+def test_two_runs_one_on_a_side_stream_give_identical_bytes():
+    xyz, masks, pairs = scene("v12_128x160")
+    args = [cu(xyz), cu(masks), cu(random_images(12, 128, 160)), cu(np.array([r for r, _ in pairs], np.int32))]
+    a = _lib.fuse_points(*args)
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        b = _lib.fuse_points(*args)
+    side.synchronize()
+    torch.cuda.synchronize()
+    total = int(a[2][-1])
+    assert total == int(b[2][-1]) and total > 0
+    for u, v in zip((a[0][:total], a[1][:total], a[2]), (b[0][:total], b[1][:total], b[2])):
+        assert torch.equal(G.raw_bytes(u), G.raw_bytes(v))
+
+
+def test_fuse_points_enqueues_without_a_host_synchronisation():
+    xyz, masks, pairs = scene("v6_64x80")
+    args = [cu(xyz), cu(masks), cu(random_images(6, 64, 80)), cu(np.array([r for r, _ in pairs], np.int32))]
+    _lib.fuse_points(*args)             # the library is loaded and the allocator warm
+    torch.cuda.synchronize()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.set_sync_debug_mode("error")     # torch raises on any synchronising call of its own
+    try:
+        start.record()
+        x, c, n = _lib.fuse_points(*args)
+        stop.record()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert x.is_cuda and c.is_cuda and n.is_cuda and n.dtype == torch.int32 and tuple(n.shape) == (7,)
+    stop.synchronize()
+    assert start.elapsed_time(stop) >= 0.0
+    assert int(n[-1]) == int((masks[:, 2] != 0).sum())
+
+
+# ---------------------------------------------------------------- refusals of the Python layer
+def test_fuse_views_and_fuse_points_refuse_what_does_not_fit():
+    xyz, masks, pairs = scene("v3_5x7")
+    filtered = dict(masks=cu(masks), xyz_world=cu(xyz))
+    with pytest.raises(RuntimeError, match="incompatible depth and image dimensions."):
+        fusion.fuse_views(filtered, np.zeros((3, 20, 32, 3), np.uint8), pairs)          # W != 4w
+    with pytest.raises(RuntimeError, match="incompatible depth and image dimensions."):
+        fusion.fuse_views(filtered, np.zeros((3, 3, 24, 28), np.uint8), pairs)          # H != 4h, CHW
+    with pytest.raises(RuntimeError, match="reference views named"):
+        fusion.fuse_views(filtered, np.zeros((3, 20, 28, 3), np.uint8), pairs[:2])
+    with pytest.raises(RuntimeError, match="images must be"):
+        fusion.fuse_views(filtered, np.zeros((3, 20, 28, 3), np.float64), pairs)
+    imgs, ref = cu(np.zeros((3, 20, 28, 3), np.uint8)), cu(np.arange(3, dtype=np.int32))
+    with pytest.raises(RuntimeError, match="float64"):
+        _lib.fuse_points(cu(xyz).float(), cu(masks), imgs, ref)
+    with pytest.raises(RuntimeError, match="masks"):
+        _lib.fuse_points(cu(xyz), cu(masks)[:, :2], imgs, ref)
+    with pytest.raises(RuntimeError, match="uint8"):
+        _lib.fuse_points(cu(xyz), cu(masks), imgs.float(), ref)
+    with pytest.raises(RuntimeError, match="ref_idx"):
+        _lib.fuse_points(cu(xyz), cu(masks), imgs, ref.long())
+    with pytest.raises(RuntimeError, match="negative"):
+        _lib.fuse_points(cu(xyz), cu(masks), imgs, ref, capacity=-1)
+    with pytest.raises(RuntimeError, match="out xyz"):
+        _lib.fuse_points(cu(xyz), cu(masks), imgs, ref, out=(torch.empty((4, 3), device=DEV), torch.empty((105, 3), dtype=torch.uint8, device=DEV),
+                                                             torch.empty(4, dtype=torch.int32, device=DEV)))
+
+
+# ---------------------------------------------------------------- end to end: files against memory
+def _files_under(root):
+    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs)
+
+
+def test_reconstruct_scan_writes_the_ply_of_the_file_path(tmp_path):
+    """save_depth_sharded -> fusion.filter_depth (every map, camera and image through a file) against
+    reconstruct_scan (nothing but the PLY): byte-identical clouds for both scans; scan9 has a grey-scale image."""
+    from synthetic_dataset import write_synthetic_dataset
+    from scene_3dreconstruction_mvsnet_amd import data_io
+    from scene_3dreconstruction_mvsnet_amd.dataset_eval import EvalDataset
+    from scene_3dreconstruction_mvsnet_amd.eval_driver import save_depth_sharded
+    listfile = write_synthetic_dataset(str(tmp_path))
+    datapath = os.path.join(str(tmp_path), "data")
+    ds = EvalDataset(datapath, listfile, "test", nviews=3, ndepths=16, interval_scale=1.06, img_res=(96, 128),
+                     dataset_name="dtu")
+    model = MVSNet(refine=False)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in load_weights().items()})
+    out = tmp_path / "out"
+    assert save_depth_sharded(model, ds, str(out), rank=0, world=1, device=DEV) == list(range(8))
+    mem = tmp_path / "mem"
+    mem.mkdir()
+    before = _files_under(str(tmp_path / "data"))
+    for scan in ("scan1", "scan9"):
+        conf = np.stack([data_io.read_pfm(str(out / scan / "confidence" / f"{v:08d}.pfm"))[0] for v in range(4)])
+        photomask = float(np.median(conf))
+        thresholds = dict(photomask=photomask, geomask=0)      # random weights on random images agree on no geometry
+        ply_files = str(out / f"{scan}.ply")
+        v_files, c_files = fusion.filter_depth(str(out / scan), os.path.join(datapath, "pair.txt"), ply_files, **thresholds)
+        share = len(v_files) / conf.size
+        assert 0.2 < share < 0.8, share                        # the file path's own selection is no degenerate one
+        ply_mem = str(mem / f"{scan}.ply")
+        v_mem, c_mem = fusion.reconstruct_scan(model, ds, scan, plyfilename=ply_mem, device=DEV, **thresholds)
+        assert v_mem.dtype == np.float32 and c_mem.dtype == np.uint8 and v_mem.shape == (len(v_files), 3)
+        np.testing.assert_array_equal(c_mem, c_files)
+        np.testing.assert_array_equal(v_mem, v_files.astype("<f4"))
+        with open(ply_files, "rb") as f, open(ply_mem, "rb") as g:
+            assert f.read() == g.read(), scan
+        # batch > 1 groups maps into one forward_features call: the same bytes
+        v_b, c_b = fusion.reconstruct_scan(model, ds, scan, batch=3, device=DEV, **thresholds)
+        assert np.array_equal(v_b.view(np.uint32), v_mem.view(np.uint32)) and np.array_equal(c_b, c_mem)
+    assert _files_under(str(mem)) == ["scan1.ply", "scan9.ply"]         # nothing written but the PLYs
+    assert _files_under(str(tmp_path / "data")) == before
+    assert ds.image_dtype == "float32"                                  # the caller's dataset is left as it was
+
+
+def test_reconstruct_scan_refuses_what_forward_features_refuses(tmp_path):
+    from synthetic_dataset import write_synthetic_dataset
+    from scene_3dreconstruction_mvsnet_amd.dataset_eval import EvalDataset
+    listfile = write_synthetic_dataset(str(tmp_path))
+    ds = EvalDataset(os.path.join(str(tmp_path), "data"), listfile, "test", 3, 16, 1.06, img_res=(96, 128), dataset_name="dtu")
+    with pytest.raises(NotImplementedError, match="refine"):
+        fusion.reconstruct_scan(MVSNet(refine=True), ds, "scan1", device=DEV)
+    with pytest.raises(ValueError, match="name one of"):
+        fusion.reconstruct_scan(MVSNet(refine=False), ds, device=DEV)
+    ds15 = EvalDataset(os.path.join(str(tmp_path), "data"), listfile, "test", 3, 15, 1.06, img_res=(96, 128), dataset_name="dtu")
+    with pytest.raises(_lib.MvsError):              # D = 15 is no multiple of 8: the library's own refusal
+        fusion.reconstruct_scan(MVSNet(refine=False), ds15, "scan1", device=DEV)
+
+
+def test_the_command_line_writes_one_ply_per_scan_under_eval_pys_name(tmp_path):
+    from synthetic_dataset import write_synthetic_dataset
+    from scene_3dreconstruction_mvsnet_amd import reconstruct
+    from scene_3dreconstruction_mvsnet_amd.dataset_eval import EvalDataset
+    listfile = write_synthetic_dataset(str(tmp_path))
+    datapath = os.path.join(str(tmp_path), "data")
+    state = {"module." + k: torch.from_numpy(v) for k, v in load_weights().items()}     # as nn.DataParallel saves it
+    torch.save({"model": state}, str(tmp_path / "model.ckpt"))
+    out = tmp_path / "plys"
+    written = reconstruct.main(["--testpath", datapath, "--testlist", listfile, "--loadckpt", str(tmp_path / "model.ckpt"),
+                                "--outdir", str(out), "--numdepth", "16", "--NviewGen", "3", "--img_res", "96", "128",
+                                "--geomask", "0", "--photomask", "0.0"])      # thresholds that keep every pixel
+    assert [os.path.basename(p) for p in written] == ["mvsnet001_l3.ply", "mvsnet009_l3.ply"]
+    assert _files_under(str(out)) == ["mvsnet001_l3.ply", "mvsnet009_l3.ply"]
+    ds = EvalDataset(datapath, listfile, "test", 3, 16, 1.06, img_res=(96, 128), dataset_name="dtu")
+    model = MVSNet(refine=False)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in load_weights().items()})
+    for scan, ply in zip(("scan1", "scan9"), written):
+        v, c = fusion.reconstruct_scan(model, ds, scan, geomask=0, photomask=0.0, plyfilename=str(tmp_path / "direct.ply"),
+                                       device=DEV)
+        assert len(v) == 4 * 24 * 32 and len(c) == len(v)
+        with open(ply, "rb") as f, open(str(tmp_path / "direct.ply"), "rb") as g:
+            assert f.read() == g.read(), scan

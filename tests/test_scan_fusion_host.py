@@ -1,0 +1,190 @@
+"""Host-side checks of the scan-fusion addition (include/mvs_fuse_abi.h, csrc/fuse_points.hip): none needs a GPU.
+Every refusal of mvs_fuse_points is decided before its first HIP call, so fake device pointers are never dereferenced."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import fuse_ref
+from scene_3dreconstruction_mvsnet_amd import _lib, fusion
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FUSE_HEADER = os.path.join(REPO, "include", "mvs_fuse_abi.h")
+OK, BAD_SHAPE, BAD_DTYPE, WORKSPACE, NULL = 0, 1, 2, 3, 5
+_FAKE = [ctypes.c_void_p(0x100000 * (i + 1)) for i in range(8)]   # aligned, never dereferenced
+GOOD = dict(fmt=_lib.MVS_IMG_U8_HWC, V=4, R=4, h=37, w=53, capacity=100)
+
+
+def _query(R, h, w):
+    n = ctypes.c_size_t(0)
+    return _lib.load().mvs_query_fuse_workspace(R, h, w, ctypes.byref(n)), int(n.value)
+
+
+def _fuse(null=None, ws_bytes=1 << 40, ws_ptr=None, **kw):
+    a = dict(GOOD, **kw)
+    p = list(_FAKE)   # xyz_world masks images ref_idx xyz_out rgb_out counts_out workspace
+    if null is not None:
+        p[null] = None
+    if ws_ptr is not None:
+        p[7] = ctypes.c_void_p(ws_ptr)
+    return _lib.load().mvs_fuse_points(p[0], p[1], p[2], a["fmt"], p[3], a["V"], a["R"], a["h"], a["w"], a["capacity"],
+                                       p[4], p[5], p[6], p[7], ws_bytes, None)
+
+
+def formula(R, h, w):
+    """The header's words: 4 * (R * ceil(h*w / MVS_FUSE_TILE) + 1) bytes."""
+    return 4 * (R * -(-(h * w) // _lib.FUSE_TILE) + 1)
+
+
+# ---------------------------------------------------------------- the colour identity the kernel relies on
+def test_the_reference_colour_arithmetic_is_the_identity_on_all_256_values():
+    u = np.arange(256, dtype=np.uint8)
+    assert np.array_equal(fuse_ref.colour_roundtrip(u), u)
+    # and the depth stage's image file holds the same byte: np.uint8(float32(u) / 255 * 255) (eval.py:346-350)
+    assert np.array_equal(np.uint8((u.astype(np.float32) / np.float32(255.0)) * 255), u)
+
+
+# ---------------------------------------------------------------- refusals
+@pytest.mark.parametrize("which", range(8))
+def test_a_null_pointer_is_refused(which):
+    assert _fuse(null=which) == NULL
+    assert b"NULL" in _lib.load().mvs_last_error_string()
+
+
+def test_null_outputs_pass_only_at_capacity_zero_and_then_the_next_check_decides():
+    # capacity 0 writes no point: xyz_out / rgb_out may be NULL; the call is then stopped by the workspace check
+    assert _fuse(null=4, capacity=0, ws_bytes=0) == WORKSPACE
+    assert _fuse(null=5, capacity=0, ws_bytes=0) == WORKSPACE
+    assert _fuse(null=6, capacity=0, ws_bytes=0) == NULL        # counts_out is always written
+    assert _query(4, 37, 53)[0] == OK and _lib.load().mvs_query_fuse_workspace(4, 37, 53, None) == NULL
+
+
+@pytest.mark.parametrize("bad", [dict(R=0), dict(R=-1), dict(h=0), dict(h=-3), dict(w=0), dict(w=-1), dict(V=0), dict(V=-2),
+                                 dict(capacity=-1),
+                                 dict(R=1, h=32768, w=65536), dict(R=2, h=32768, w=32768), dict(R=1 << 20, h=64, w=32),
+                                 dict(R=3, h=1 << 20, w=1 << 20)])
+def test_bad_shapes_are_refused(bad):
+    assert _fuse(**bad) == BAD_SHAPE, bad
+    assert _lib.load().mvs_last_error_string()
+    if "V" not in bad and "capacity" not in bad:
+        a = dict(GOOD, **bad)
+        assert _query(a["R"], a["h"], a["w"])[0] == BAD_SHAPE
+
+
+def test_the_largest_legal_sizes_are_accepted_by_the_query():
+    for R, h, w in [(1, 1, (1 << 31) - 1), (1, (1 << 31) - 1, 1), ((1 << 31) - 1, 1, 1), (2, 32768, 32767), (1, 1, 1)]:
+        st, n = _query(R, h, w)
+        assert st == OK and n == formula(R, h, w), (R, h, w, n)
+
+
+@pytest.mark.parametrize("fmt", [_lib.MVS_IMG_F32_CHW, 3, -1, 7])
+def test_only_the_two_uint8_image_formats_are_taken(fmt):
+    assert _fuse(fmt=fmt) == BAD_DTYPE
+    assert b"format" in _lib.load().mvs_last_error_string()
+
+
+@pytest.mark.parametrize("R,h,w", [(3, 5, 7), (7, 37, 53), (6, 64, 80), (12, 128, 160), (49, 296, 400), (2, 32, 32),
+                                   (2, 25, 41), (2, 33, 31), (1, 1, 1)])
+def test_workspace_query_agrees_with_its_formula_and_one_byte_less_is_refused(R, h, w):
+    st, n = _query(R, h, w)
+    assert st == OK and n == formula(R, h, w) == _lib.query_fuse_workspace(R, h, w), (R, h, w, n)
+    assert _fuse(R=R, h=h, w=w, ws_bytes=n - 1) == WORKSPACE        # from below
+    assert _fuse(R=R, h=h, w=w, ws_bytes=0) == WORKSPACE
+    assert _fuse(R=R, h=h, w=w, ws_bytes=n, ws_ptr=0x500002) == WORKSPACE      # exactly enough, misaligned
+    assert b"aligned" in _lib.load().mvs_last_error_string()
+    # the formula from the other side: one tile more per view than the pixels need would be 4 * R bytes more
+    assert n < 4 * (R * (-(-(h * w) // _lib.FUSE_TILE) + 1) + 1)
+
+
+# ---------------------------------------------------------------- declarations
+def test_fuse_symbols_are_the_declarations_of_the_fuse_header():
+    src = open(FUSE_HEADER).read()
+    declared = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", src, flags=re.M)
+    assert sorted(declared) == sorted(_lib.FUSE_SYMBOLS) and len(set(declared)) == len(declared)
+    assert not set(_lib.FUSE_SYMBOLS) & set(_lib.SYMBOLS)       # SYMBOLS stays mvs_abi.h alone
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name in declared:
+        assert hasattr(raw, name), name
+    assert '#include "mvs_abi.h"' in src
+    for name, value in (("MVS_FUSE_TILE", _lib.FUSE_TILE), ("MVS_FUSE_SCAN_WIDTH", _lib.FUSE_SCAN_WIDTH)):
+        assert int(re.search(rf"^#define {name} (\d+)", src, flags=re.M).group(1)) == value
+    main = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
+    assert "mvs_fuse_abi.h" in main and not re.search(r"^int\s+mvs_(query_fuse|fuse)", main, flags=re.M)
+
+
+def test_the_abi_version_is_still_2():
+    assert _lib.load().mvs_abi_version() == 2 == _lib.ABI_VERSION
+
+
+# ---------------------------------------------------------------- the yardstick itself, on a case small enough to read
+def test_fuse_ref_on_a_hand_written_case():
+    h, w = 2, 3
+    xyz = np.arange(2 * h * w * 3, dtype=np.float64).reshape(2, h * w, 3) + 0.1
+    masks = np.zeros((2, 3, h, w), np.uint8)
+    masks[0, 2, 0, 1] = masks[0, 2, 1, 2] = 1
+    masks[1, 2, 1, 0] = 255
+    masks[1, 0] = masks[1, 1] = 1          # the photo / geo planes select nothing
+    img = np.arange(2 * 8 * 12 * 3, dtype=np.uint32).reshape(2, 8, 12, 3).astype(np.uint8)
+    got = fuse_ref.fuse(xyz, masks, img, [1, 0])
+    assert got[2].tolist() == [2, 1, 3]
+    assert np.array_equal(got[0], np.array([xyz[0, 1], xyz[0, 5], xyz[1, 3]]).astype("<f4")) and got[0].dtype == np.float32
+    assert np.array_equal(got[1], np.array([img[1, 1, 5], img[1, 5, 9], img[0, 5, 1]]))
+    chw = fuse_ref.fuse(xyz, masks, np.ascontiguousarray(img.transpose(0, 3, 1, 2)), [1, 0], hwc=False)
+    assert all(np.array_equal(a, b) for a, b in zip(got, chw))
+    gone = fuse_ref.fuse(xyz, masks, img, [2, 0])
+    assert gone[2].tolist() == [0, 1, 1] and np.array_equal(gone[0], got[0][2:])
+
+
+# ---------------------------------------------------------------- the Python layer, before any GPU work
+def test_python_functions_refuse_host_tensors_and_foreign_objects():
+    import torch
+    with pytest.raises(RuntimeError, match="CUDA"):
+        _lib.fuse_points(torch.zeros(1, 4, 3, dtype=torch.float64), torch.zeros(1, 3, 2, 2, dtype=torch.uint8),
+                         torch.zeros(1, 8, 8, 3, dtype=torch.uint8), torch.zeros(1, dtype=torch.int32))
+    with pytest.raises(ValueError, match="view_plan"):
+        fusion.reconstruct_scan(object(), object())
+
+    class NoFeatures:
+        metas = [("scan1", 0, [1])]
+        view_plan = decode_view = assemble = None
+
+    with pytest.raises(ValueError, match="extract_features"):
+        fusion.reconstruct_scan(object(), NoFeatures())
+
+
+class _TwoSizes:
+    """A dataset whose second view is smaller than the first."""
+    metas = [("s", 0, [1]), ("s", 1, [0]), ("t", 0, [1])]
+    image_dtype = "uint8"
+
+    def view_plan(self, idx):
+        _, ref, src = self.metas[idx]
+        return "s/{}/%08d{}" % ref, [(f"img{v}", f"cam{v}") for v in [ref] + src]
+
+    def decode_view(self, path):
+        return np.zeros((3, 64, 96 if path == "img0" else 64), np.uint8), (1.0, 0.0, 0.0)
+
+    def assemble(self, idx, adjust):
+        n = len(adjust)
+        return {"proj_matrices": np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)), "intrinsics": [np.eye(3, dtype=np.float32)] * n,
+                "extrinsics": [np.eye(4, dtype=np.float32)] * n, "depth_values": np.arange(8, dtype=np.float32),
+                "filename": "s/{}/x{}"}
+
+
+class _Model:
+    extract_features = forward_features = None
+
+
+def test_reconstruct_scan_refuses_a_scan_it_cannot_fuse():
+    with pytest.raises(ValueError, match="differ in size"):
+        fusion.reconstruct_scan(_Model(), _TwoSizes(), scan="s")
+    with pytest.raises(ValueError, match="name one of"):
+        fusion.reconstruct_scan(_Model(), _TwoSizes())
+    with pytest.raises(ValueError, match="not in the dataset"):
+        fusion.reconstruct_scan(_Model(), _TwoSizes(), scan="nowhere")
+    with pytest.raises(ValueError, match="no reference view"):
+        fusion.reconstruct_scan(_Model(), _TwoSizes(), scan="t")      # view 1 is a filter source without a depth map
+    with pytest.raises(ValueError, match="batch"):
+        fusion.reconstruct_scan(_Model(), _TwoSizes(), scan="s", batch=0)
