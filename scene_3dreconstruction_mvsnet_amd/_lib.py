@@ -38,25 +38,6 @@ def dtype_code(dtype) -> int:
 NUM_LAYERS = 11
 ABI_VERSION = 2
 
-# every symbol include/mvs_abi.h declares
-SYMBOLS = (
-    "mvs_abi_version", "mvs_last_error_string", "mvs_query_workspace", "mvs_query_weights_blob",
-    "mvs_pack_weights", "mvs_relative_proj", "mvs_warp_variance", "mvs_costreg_forward",
-    "mvs_conv_layer", "mvs_conv11_prob", "mvs_softargmin_conf", "mvs_depth_infer", "mvs_homo_warp", "mvs_depth_regression",
-    "mvs_filter_compose", "mvs_filter_depth",
-    "mvs_query_feature_blob", "mvs_pack_feature_weights", "mvs_query_feature_workspace",
-    "mvs_feature_layer", "mvs_feature_net", "mvs_query_forward_workspace", "mvs_forward_images",
-    "mvs_feature_net_fmt", "mvs_forward_images_fmt", "mvs_depth_infer_views",
-    "mvs_query_metrics_workspace", "mvs_depth_metrics",
-    "mvs_warp_variance_backward", "mvs_softargmin_backward",
-    "mvs_query_conv3d_train_workspace", "mvs_conv3d_train_forward", "mvs_conv3d_train_backward_data",
-    "mvs_conv3d_train_backward_weight", "mvs_feature_conv01_fmt",
-    "mvs_query_bn3d_train_workspace", "mvs_bn3d_train_forward", "mvs_bn3d_train_backward", "mvs_volume_relayout",
-)
-
-# the symbols include/mvs_fuse_abi.h declares (kept apart: SYMBOLS is exactly mvs_abi.h)
-FUSE_SYMBOLS = ("mvs_query_fuse_workspace", "mvs_fuse_points")
-
 # mvs_image_format (include/mvs_abi.h)
 MVS_IMG_F32_CHW, MVS_IMG_U8_CHW, MVS_IMG_U8_HWC = 0, 1, 2
 
@@ -66,6 +47,64 @@ _lib = None
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _sz = ctypes.c_size_t
+_f, _d, _ll = ctypes.c_float, ctypes.c_double, ctypes.c_longlong
+_szp = ctypes.POINTER(_sz)      # size_t* bytes
+_vpp = ctypes.POINTER(_vp)      # const float* const*
+
+# Every entry point, declared once on this side: header -> {name: argument types}, in the headers' order.  Any other
+# pointer is a c_void_p (device and host addresses travel as integers).  load() applies the table; SYMBOLS and
+# FUSE_SYMBOLS are its keys; tests/test_host_logic.py and tests/test_scan_fusion_host.py hold every argument list to
+# its prototype.  Everything returns int except mvs_last_error_string.
+_ABI = {
+    "mvs_abi.h": {
+        "mvs_abi_version": [],
+        "mvs_last_error_string": [],
+        "mvs_query_workspace": [_i, _i, _i, _i, _i, _i, _szp],
+        "mvs_query_weights_blob": [_szp],
+        "mvs_pack_weights": [_vpp, _vpp, _vp, _f, _vp, _sz],
+        "mvs_relative_proj": [_vp, _vp, _i, _vp],
+        "mvs_warp_variance": [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
+        "mvs_costreg_forward": [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
+        "mvs_conv_layer": [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+        "mvs_conv11_prob": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+        "mvs_softargmin_conf": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+        "mvs_depth_infer": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
+        "mvs_depth_infer_views": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
+        "mvs_homo_warp": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+        "mvs_depth_regression": [_vp, _vp, _vp, _i, _i, _i, _vp],
+        "mvs_filter_compose": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+        "mvs_filter_depth": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _d, _d, _vp, _vp, _vp, _vp, _vp],
+        "mvs_query_feature_blob": [_szp],
+        "mvs_pack_feature_weights": [_vpp, _vpp, _vp, _f, _vp, _sz],
+        "mvs_query_feature_workspace": [_i, _i, _i, _szp],
+        "mvs_feature_layer": [_i, _vp, _vp, _vp, _i, _i, _i, _vp],
+        "mvs_feature_conv01_fmt": [_vp, _i, _vp, _vp, _i, _i, _i, _vp],
+        "mvs_feature_net": [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp],
+        "mvs_query_forward_workspace": [_i, _i, _i, _i, _i, _szp],
+        "mvs_forward_images": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp],
+        "mvs_feature_net_fmt": [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp],
+        "mvs_forward_images_fmt": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp],
+        "mvs_query_metrics_workspace": [_i, _i, _i, _szp],
+        "mvs_depth_metrics": [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp],
+        "mvs_warp_variance_backward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+        "mvs_softargmin_backward": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+        "mvs_query_conv3d_train_workspace": [_i, _i, _i, _i, _i, _i, _szp],
+        "mvs_conv3d_train_forward": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+        "mvs_conv3d_train_backward_data": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+        "mvs_conv3d_train_backward_weight": [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
+        "mvs_query_bn3d_train_workspace": [_i, _ll, _szp],
+        "mvs_bn3d_train_forward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _ll, _vp, _sz, _vp],
+        "mvs_bn3d_train_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _vp, _sz, _vp],
+        "mvs_volume_relayout": [_vp, _vp, _i, _ll, _i, _vp],
+    },
+    # kept apart: SYMBOLS is exactly mvs_abi.h
+    "mvs_fuse_abi.h": {
+        "mvs_query_fuse_workspace": [_i, _i, _i, _szp],
+        "mvs_fuse_points": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _vp, _sz, _vp],
+    },
+}
+SYMBOLS = tuple(_ABI["mvs_abi.h"])
+FUSE_SYMBOLS = tuple(_ABI["mvs_fuse_abi.h"])
 
 
 class MvsError(RuntimeError):
@@ -91,60 +130,11 @@ def load():
         for name in SYMBOLS + FUSE_SYMBOLS:
             if not hasattr(lib, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}")
-        lib.mvs_abi_version.restype = _i
-        lib.mvs_last_error_string.restype = ctypes.c_char_p
-        lib.mvs_query_workspace.argtypes = [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_sz)]
-        lib.mvs_query_weights_blob.argtypes = [ctypes.POINTER(_sz)]
-        lib.mvs_pack_weights.argtypes = [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
-                                         ctypes.c_float, _vp, _sz]
-        lib.mvs_relative_proj.argtypes = [_vp, _vp, _i, _vp]
-        lib.mvs_warp_variance.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]
-        lib.mvs_costreg_forward.argtypes = [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]
-        lib.mvs_conv_layer.argtypes = [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]
-        lib.mvs_conv11_prob.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]
-        lib.mvs_softargmin_conf.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]
-        lib.mvs_depth_infer.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
-                                        _i, _i, _i, _i, _i, _i, _vp]
-        lib.mvs_depth_infer_views.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
-                                              _i, _i, _i, _i, _i, _i, _vp]
-        lib.mvs_homo_warp.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]
-        lib.mvs_depth_regression.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp]
-        lib.mvs_query_feature_blob.argtypes = [ctypes.POINTER(_sz)]
-        lib.mvs_pack_feature_weights.argtypes = [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
-                                                 ctypes.c_float, _vp, _sz]
-        lib.mvs_query_feature_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_sz)]
-        lib.mvs_feature_layer.argtypes = [_i, _vp, _vp, _vp, _i, _i, _i, _vp]
-        lib.mvs_feature_conv01_fmt.argtypes = [_vp, _i, _vp, _vp, _i, _i, _i, _vp]
-        lib.mvs_feature_net.argtypes = [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]
-        lib.mvs_query_forward_workspace.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(_sz)]
-        lib.mvs_forward_images.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
-                                           _i, _i, _i, _i, _i, _vp]
-        lib.mvs_feature_net_fmt.argtypes = [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]
-        lib.mvs_forward_images_fmt.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
-                                               _i, _i, _i, _i, _i, _vp]
-        lib.mvs_filter_compose.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]
-        _d = ctypes.c_double
-        lib.mvs_filter_depth.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
-                                         _d, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]
-        lib.mvs_query_metrics_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_sz)]
-        lib.mvs_depth_metrics.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]
-        lib.mvs_warp_variance_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]
-        lib.mvs_softargmin_backward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]
-        lib.mvs_query_conv3d_train_workspace.argtypes = [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_sz)]
-        lib.mvs_conv3d_train_forward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]
-        lib.mvs_conv3d_train_backward_data.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
-        lib.mvs_conv3d_train_backward_weight.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]
-        _ll, _f = ctypes.c_longlong, ctypes.c_float
-        lib.mvs_query_bn3d_train_workspace.argtypes = [_i, _ll, ctypes.POINTER(_sz)]
-        lib.mvs_bn3d_train_forward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _ll, _vp,
-                                               _sz, _vp]
-        lib.mvs_bn3d_train_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _vp, _sz, _vp]
-        lib.mvs_volume_relayout.argtypes = [_vp, _vp, _i, _ll, _i, _vp]
-        lib.mvs_query_fuse_workspace.argtypes = [_i, _i, _i, ctypes.POINTER(_sz)]
-        lib.mvs_fuse_points.argtypes = [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _vp, _sz, _vp]
-        for name in SYMBOLS + FUSE_SYMBOLS:
-            if name not in ("mvs_last_error_string",):
-                getattr(lib, name).restype = _i
+        for prototypes in _ABI.values():
+            for name, argtypes in prototypes.items():
+                fn = getattr(lib, name)
+                fn.argtypes = argtypes
+                fn.restype = ctypes.c_char_p if name == "mvs_last_error_string" else _i
         if lib.mvs_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libmvs_hip ABI {lib.mvs_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -156,20 +146,29 @@ def check(status: int) -> None:
         raise MvsError(status, load().mvs_last_error_string().decode("utf-8", "replace"))
 
 
-def query_workspace(N, C, D, h, w, dtype=MVS_F32) -> int:
+def _query(name, *args) -> int:
+    """The byte count an mvs_query_* entry point writes through its last argument (`size_t* bytes`)."""
     n = _sz(0)
-    check(load().mvs_query_workspace(N, C, D, h, w, dtype, ctypes.byref(n)))
+    check(getattr(load(), name)(*args, ctypes.byref(n)))
     return int(n.value)
+
+
+def query_workspace(N, C, D, h, w, dtype=MVS_F32) -> int:
+    return _query("mvs_query_workspace", N, C, D, h, w, dtype)
 
 
 def query_weights_blob() -> int:
-    n = _sz(0)
-    check(load().mvs_query_weights_blob(ctypes.byref(n)))
-    return int(n.value)
+    return _query("mvs_query_weights_blob")
 
 
 def _stream(device) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _check_out(t, shape, dtype, device, who, what):
+    """The refusal of a caller's output tensor that is not contiguous, of `dtype`, shaped `shape` and on `device`."""
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device != device:
+        raise RuntimeError(f"{who} must be a contiguous {what}")
 
 
 def _dev_f32(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -189,41 +188,44 @@ _LAYER_CH = ((32, 8), (8, 16), (16, 16), (16, 32), (32, 32), (32, 64), (64, 64),
              (64, 32), (32, 16), (16, 8), (8, 1))
 
 
-def pack_weights(state: dict, eps: float = 1e-5) -> torch.Tensor:
-    """BN-fold + re-layout the CostRegNet parameters into the kernels' blob (host, uint8).
+_BN_SUFFIXES = ("weight", "bias", "running_mean", "running_var")
 
-    `state` maps names relative to `cost_regularization.` to CPU float32 tensors/arrays.
-    """
+
+def _host_f32(state, entries):
+    """Named state entries -> (array of their addresses, the arrays): entries = [(key, shape)], each taken from `state`
+    as a contiguous float32 host array of exactly that shape.  The addresses hold while the arrays are alive."""
     import numpy as np
-
-    lib = load()
-    keep = []
-
-    def arr(key, shape):
+    arrays = []
+    for key, shape in entries:
         a = state[key]
         if isinstance(a, torch.Tensor):
             a = a.detach().cpu().numpy()
         a = np.ascontiguousarray(a, dtype=np.float32)
         if tuple(a.shape) != tuple(shape):
             raise RuntimeError(f"{key}: shape {tuple(a.shape)} != expected {tuple(shape)}")
-        keep.append(a)
-        return a.ctypes.data
+        arrays.append(a)
+    return (_vp * len(arrays))(*[a.ctypes.data for a in arrays]), arrays
 
-    convs = (_vp * NUM_LAYERS)()
-    for l, key in enumerate(CONV_WEIGHT_KEYS):
-        ci, co = _LAYER_CH[l]
-        shape = (ci, co, 3, 3, 3) if 7 <= l <= 9 else (co, ci, 3, 3, 3)
-        convs[l] = arr(key, shape)
-    bns = (_vp * 40)()
-    for l, pre in enumerate(BN_PREFIXES):
-        co = _LAYER_CH[l][1]
-        for j, suffix in enumerate(("weight", "bias", "running_mean", "running_var")):
-            bns[4 * l + j] = arr(f"{pre}.{suffix}", (co,))
-    bias = arr("prob.bias", (1,))
-    nbytes = query_weights_blob()
+
+def _pack(pack, nbytes, state, convs, bns, bias, eps):
+    """One mvs_pack_* call: the conv weights, the BatchNorm parameters and the bias of `state` -> host blob (uint8)."""
+    conv_ptrs, conv_arrays = _host_f32(state, convs)      # the arrays are locals: they outlive the call below
+    bn_ptrs, bn_arrays = _host_f32(state, bns)
+    bias_ptr, bias_array = _host_f32(state, [bias])
     blob = torch.empty(nbytes, dtype=torch.uint8)
-    check(lib.mvs_pack_weights(convs, bns, bias, ctypes.c_float(eps), blob.data_ptr(), nbytes))
+    check(pack(conv_ptrs, bn_ptrs, bias_ptr[0], ctypes.c_float(eps), blob.data_ptr(), nbytes))
     return blob
+
+
+def pack_weights(state: dict, eps: float = 1e-5) -> torch.Tensor:
+    """BN-fold + re-layout the CostRegNet parameters into the kernels' blob (host, uint8).
+
+    `state` maps names relative to `cost_regularization.` to CPU float32 tensors/arrays.
+    """
+    convs = [(key, (ci, co, 3, 3, 3) if 7 <= l <= 9 else (co, ci, 3, 3, 3))
+             for l, (key, (ci, co)) in enumerate(zip(CONV_WEIGHT_KEYS, _LAYER_CH))]
+    bns = [(f"{pre}.{suffix}", (_LAYER_CH[l][1],)) for l, pre in enumerate(BN_PREFIXES) for suffix in _BN_SUFFIXES]
+    return _pack(load().mvs_pack_weights, query_weights_blob(), state, convs, bns, ("prob.bias", (1,)), eps)
 
 
 def relative_proj(proj: torch.Tensor) -> torch.Tensor:
@@ -325,9 +327,9 @@ def warp_variance_backward(feats, rt, depth_values, grad_var, out=None):
         raise RuntimeError(f"grad_var {tuple(grad_var.shape)} must be [{C},{D},{h},{w}]")
     if out is None:
         out = torch.empty_like(feats)
-    elif tuple(out.shape) != tuple(feats.shape) or out.dtype != torch.float32 or not out.is_contiguous() \
-            or out.device != feats.device:
-        raise RuntimeError("warp_variance_backward: out must be a contiguous float32 tensor shaped like feats")
+    else:
+        _check_out(out, feats.shape, torch.float32, feats.device, "warp_variance_backward: out",
+                   "float32 tensor shaped like feats")
     check(load().mvs_warp_variance_backward(feats.data_ptr(), _dev_f32(rt, "rt").data_ptr(),
                                             _dev_f32(depth_values, "depth_values").data_ptr(), grad_var.data_ptr(),
                                             out.data_ptr(), N, C, D, h, w, _stream(feats.device)))
@@ -350,9 +352,7 @@ def softargmin_backward(cost, depth_values, grad_depth):
 # ---- training convolutions (csrc/train_conv3d.hip).  Volumes are channels-last [D,H,W,C] float32 tensors of one batch
 # item; Cin, Cout, D, H, W, stride describe the convolution (x [D,H,W,Cin] -> y [D/s,H/s,W/s,Cout]).
 def conv3d_train_workspace_bytes(Cin, Cout, D, H, W, stride) -> int:
-    n = _sz(0)
-    check(load().mvs_query_conv3d_train_workspace(Cin, Cout, D, H, W, stride, ctypes.byref(n)))
-    return int(n.value)
+    return _query("mvs_query_conv3d_train_workspace", Cin, Cout, D, H, W, stride)
 
 
 def _cl_volume(t, name):
@@ -410,9 +410,7 @@ def conv3d_train_backward_weight(x, gy, stride, with_bias=False):
 
 # ---- training batch-norm (csrc/train_bn3d.hip).  Data is channels-last [M, C] float32: M voxels pooled over the batch.
 def bn3d_train_workspace_bytes(C, M) -> int:
-    n = _sz(0)
-    check(load().mvs_query_bn3d_train_workspace(C, M, ctypes.byref(n)))
-    return int(n.value)
+    return _query("mvs_query_bn3d_train_workspace", C, M)
 
 
 def _cl_rows(t, name):
@@ -499,8 +497,8 @@ def volume_relayout(src, direction, out=None):
         raise RuntimeError(f"volume_relayout: direction {direction!r} (0 or 1)")
     if out is None:
         out = torch.empty(oshape, dtype=torch.float32, device=src.device)
-    elif tuple(out.shape) != oshape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device:
-        raise RuntimeError(f"volume_relayout: out must be a contiguous float32 tensor {oshape}")
+    else:
+        _check_out(out, oshape, torch.float32, src.device, "volume_relayout: out", f"float32 tensor {oshape}")
     check(load().mvs_volume_relayout(src.data_ptr(), out.data_ptr(), C, dims[0] * dims[1] * dims[2], direction,
                                      _stream(src.device)))
     return out
@@ -641,9 +639,7 @@ FUSE_TILE, FUSE_SCAN_WIDTH = 1024, 1024     # MVS_FUSE_TILE, MVS_FUSE_SCAN_WIDTH
 
 
 def query_fuse_workspace(R, h, w) -> int:
-    n = _sz(0)
-    check(load().mvs_query_fuse_workspace(R, h, w, ctypes.byref(n)))
-    return int(n.value)
+    return _query("mvs_query_fuse_workspace", R, h, w)
 
 
 def fuse_points(xyz_world, masks, images, ref_idx, capacity=None, out=None):
@@ -689,8 +685,7 @@ def fuse_points(xyz_world, masks, images, ref_idx, capacity=None, out=None):
             xyz, rgb, counts = out
             for t, shape, dt, name in ((xyz, (capacity, 3), torch.float32, "xyz"), (rgb, (capacity, 3), torch.uint8, "rgb"),
                                        (counts, (R + 1,), torch.int32, "counts")):
-                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
-                    raise RuntimeError(f"fuse_points: out {name} must be a contiguous {dt} {shape} tensor on {dev}")
+                _check_out(t, shape, dt, dev, f"fuse_points: out {name}", f"{dt} {shape} tensor on {dev}")
         ws = torch.empty(query_fuse_workspace(R, h, w), dtype=torch.uint8, device=dev)
         check(load().mvs_fuse_points(xyz_world.data_ptr(), masks.data_ptr(), images.data_ptr(), fmt, ref_idx.data_ptr(),
                                      V, R, h, w, capacity, xyz.data_ptr() if capacity else None,
@@ -707,53 +702,23 @@ FEATURE_WEIGHT_KEYS = tuple([f"conv{i}.conv.weight" for i in range(7)] + ["featu
 
 
 def query_feature_blob() -> int:
-    n = _sz(0)
-    check(load().mvs_query_feature_blob(ctypes.byref(n)))
-    return int(n.value)
+    return _query("mvs_query_feature_blob")
 
 
 def pack_feature_weights(state: dict, eps: float = 1e-5) -> torch.Tensor:
     """BN-fold + re-layout FeatureNet's parameters into MFMA panels (host, uint8).
     `state` maps names relative to `feature.` to CPU float32 tensors/arrays."""
-    import numpy as np
-    keep = []
-
-    def arr(key, shape):
-        a = state[key]
-        if isinstance(a, torch.Tensor):
-            a = a.detach().cpu().numpy()
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if tuple(a.shape) != tuple(shape):
-            raise RuntimeError(f"{key}: shape {tuple(a.shape)} != expected {tuple(shape)}")
-        keep.append(a)
-        return a.ctypes.data
-
-    convs = (_vp * 8)()
-    for l, key in enumerate(FEATURE_WEIGHT_KEYS):
-        ci, co, k, _ = FEATURE_LAYERS[l]
-        convs[l] = arr(key, (co, ci, k, k))
-    bns = (_vp * 28)()
-    for l in range(7):
-        co = FEATURE_LAYERS[l][1]
-        for j, suffix in enumerate(("weight", "bias", "running_mean", "running_var")):
-            bns[4 * l + j] = arr(f"conv{l}.bn.{suffix}", (co,))
-    bias = arr("feature.bias", (32,))
-    nbytes = query_feature_blob()
-    blob = torch.empty(nbytes, dtype=torch.uint8)
-    check(load().mvs_pack_feature_weights(convs, bns, bias, ctypes.c_float(eps), blob.data_ptr(), nbytes))
-    return blob
+    convs = [(key, (co, ci, k, k)) for key, (ci, co, k, _) in zip(FEATURE_WEIGHT_KEYS, FEATURE_LAYERS)]
+    bns = [(f"conv{l}.bn.{suffix}", (FEATURE_LAYERS[l][1],)) for l in range(7) for suffix in _BN_SUFFIXES]
+    return _pack(load().mvs_pack_feature_weights, query_feature_blob(), state, convs, bns, ("feature.bias", (32,)), eps)
 
 
 def query_feature_workspace(N, H, W) -> int:
-    n = _sz(0)
-    check(load().mvs_query_feature_workspace(N, H, W, ctypes.byref(n)))
-    return int(n.value)
+    return _query("mvs_query_feature_workspace", N, H, W)
 
 
 def query_forward_workspace(N, H, W, D, dtype=MVS_F32) -> int:
-    n = _sz(0)
-    check(load().mvs_query_forward_workspace(N, H, W, D, dtype, ctypes.byref(n)))
-    return int(n.value)
+    return _query("mvs_query_forward_workspace", N, H, W, D, dtype)
 
 
 def feature_layer(layer, x, fblob):
@@ -818,9 +783,9 @@ def feature_net(imgs, fblob, workspace=None, out=None):
     h4, w4 = ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1
     if out is None:
         out = torch.empty((N, 32, h4, w4), dtype=torch.float32, device=imgs.device)
-    elif tuple(out.shape) != (N, 32, h4, w4) or out.dtype != torch.float32 or not out.is_contiguous() \
-            or out.device != imgs.device:
-        raise RuntimeError(f"feature_net: out must be a contiguous float32 [{N},32,{h4},{w4}] tensor on {imgs.device}")
+    else:
+        _check_out(out, (N, 32, h4, w4), torch.float32, imgs.device, "feature_net: out",
+                   f"float32 [{N},32,{h4},{w4}] tensor on {imgs.device}")
     check(load().mvs_feature_net_fmt(imgs.data_ptr(), fmt, fblob.data_ptr(), out.data_ptr(), workspace.data_ptr(),
                                      workspace.numel(), N, H, W, _stream(imgs.device)))
     return out
@@ -849,9 +814,7 @@ METRICS_MAX_THRES = 8
 
 
 def query_metrics_workspace(B, h, w) -> int:
-    n = _sz(0)
-    check(load().mvs_query_metrics_workspace(B, h, w, ctypes.byref(n)))
-    return int(n.value)
+    return _query("mvs_query_metrics_workspace", B, h, w)
 
 
 def depth_metrics(depth_est, depth_gt, mask, thresholds=(1.0, 2.0, 4.0, 8.0), sums_out=None, errmap=False,
@@ -884,9 +847,8 @@ def depth_metrics(depth_est, depth_gt, mask, thresholds=(1.0, 2.0, 4.0, 8.0), su
     dev = est.device
     if sums_out is None:
         sums_out = torch.empty((B, K), dtype=torch.float64, device=dev)
-    elif tuple(sums_out.shape) != (B, K) or sums_out.dtype != torch.float64 or not sums_out.is_contiguous() \
-            or sums_out.device != dev:
-        raise RuntimeError(f"depth_metrics: sums_out must be a contiguous float64 [{B},{K}] tensor on {dev}")
+    else:
+        _check_out(sums_out, (B, K), torch.float64, dev, "depth_metrics: sums_out", f"float64 [{B},{K}] tensor on {dev}")
     err = torch.empty((B, h, w), dtype=torch.float32, device=dev) if errmap else None
     with torch.cuda.device(dev):
         nbytes = query_metrics_workspace(B, h, w)

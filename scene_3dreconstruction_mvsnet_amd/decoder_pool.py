@@ -61,7 +61,52 @@ def _unpin(pool):
         unpin()
 
 
-class DecoderPool:
+class _SharedMemoryPool:
+    """What the two pools share: the end of their workers and of the shared-memory segment."""
+
+    _unmap_errors = ()      # what unmapping the segment may raise without failing close()
+
+    def _worker_queues(self):
+        """The task queue of every worker, one entry each: close() puts one sentinel per entry."""
+        raise NotImplementedError
+
+    def close(self):
+        for q in self._worker_queues():
+            try:
+                q.put(_SENTINEL)
+            except (OSError, ValueError):
+                pass
+        for p in self._workers:
+            p.join(timeout=5)
+            if p.is_alive():
+                p.terminate()
+        self._workers = []
+        if self._shm is not None:
+            _unpin(self)
+            try:
+                self._shm.close()
+            except self._unmap_errors:
+                pass
+            try:
+                self._shm.unlink()
+            except FileNotFoundError:
+                pass
+            self._shm = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # best effort: never leave a segment behind in /dev/shm
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class DecoderPool(_SharedMemoryPool):
     """`for sample in pool.imap(indices): ...; pool.release(sample)` -- samples in order."""
 
     def __init__(self, dataset, procs: int = 8, chunk: int = 4, slots: int | None = None,
@@ -97,37 +142,12 @@ class DecoderPool:
             self._tasks.append(q)
             self._workers.append(p)
 
+    def _worker_queues(self):
+        return self._tasks
+
     def close(self):
-        for q in self._tasks:
-            try:
-                q.put(_SENTINEL)
-            except (OSError, ValueError):
-                pass
-        for p in self._workers:
-            p.join(timeout=5)
-            if p.is_alive():
-                p.terminate()
-        self._workers, self._tasks = [], []
-        if self._shm is not None:
-            _unpin(self)
-            self._shm.close()
-            try:
-                self._shm.unlink()
-            except FileNotFoundError:
-                pass
-            self._shm = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):  # best effort: never leave a segment behind in /dev/shm
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        super().close()
+        self._tasks = []
 
     # -- iteration ---------------------------------------------------------------------------
     def release(self, sample):
@@ -206,7 +226,7 @@ def _view_worker(dataset, shm_name, slot_bytes, tasks, results):
         shm.close()
 
 
-class ViewDecoderPool:
+class ViewDecoderPool(_SharedMemoryPool):
     """Samples in dataset order with `imgs` = LIST of per-view arrays [3,H,W] living in shared memory.
 
     In an eval run every view is the reference view of one sample and a source view of several
@@ -243,40 +263,10 @@ class ViewDecoderPool:
         self._free = list(range(self.slots))
         self._pins_of = {}      # id(sample) -> [paths]
 
-    def close(self):
-        for _ in self._workers:
-            try:
-                self._tasks.put(_SENTINEL)
-            except (OSError, ValueError):
-                pass
-        for p in self._workers:
-            p.join(timeout=5)
-            if p.is_alive():
-                p.terminate()
-        self._workers = []
-        if self._shm is not None:
-            _unpin(self)
-            try:
-                self._shm.close()
-            except BufferError:      # the consumer still holds views of the cache (or page-locked it)
-                pass
-            try:
-                self._shm.unlink()
-            except FileNotFoundError:
-                pass
-            self._shm = None
+    _unmap_errors = (BufferError,)      # the consumer still holds views of the cache (or page-locked it)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+    def _worker_queues(self):
+        return [self._tasks] * len(self._workers)       # one queue that all workers read
 
     def release(self, sample):
         for path in self._pins_of.pop(id(sample), ()):

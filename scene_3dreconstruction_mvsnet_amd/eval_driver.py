@@ -286,6 +286,62 @@ def _loader(dataset, indices, device, copy_stream, q: "queue.Queue", decoders: i
     q.put(None)
 
 
+def _loaded(q: "queue.Queue", compute):
+    """Consumer half of the pipeline: the items _loader put on `q`, in order, up to its closing None; an exception it
+    forwarded is re-raised here.  Before an item is handed on, `compute` waits for the item's copies and its device
+    tensors (allocated on the copy stream) are recorded on `compute`.  Yields (index, sample, device list, plan)."""
+    while True:
+        t0 = _now()
+        item = q.get()
+        _tick("main.q_get", t0)
+        if item is None:
+            return
+        if isinstance(item, BaseException):
+            raise item
+        idx, s, dev, ready, plan = item
+        compute.wait_event(ready)
+        for t in dev:
+            if t is not None:
+                t.record_stream(compute)
+        yield idx, s, dev, plan
+
+
+def _check_reuse_features(model, dataset, first, feature_slots):
+    """reuse_features' refusals about the model and the bank's size, made before any work starts (the caller has
+    checked that the dataset has view_plan).  `first`: the indices whose view count the bank must hold."""
+    if not all(hasattr(model, a) for a in ("extract_features", "forward_features")):
+        raise ValueError("reuse_features needs a model with extract_features / forward_features (MVSNet)")
+    n_max = max((len(dataset.view_plan(i)[1]) for i in first), default=0)
+    if feature_slots < max(1, n_max):
+        raise ValueError(f"feature_slots={feature_slots} is below the {n_max} views of one sample")
+
+
+class _FeatureBank:
+    """The device side of reuse_features: FeatureNet outputs [slots, 32, h, w], allocated at the first sample."""
+
+    def __init__(self, model, slots, device):
+        self.model, self.slots, self.device = model, slots, device
+        self.bank = None
+
+    def forward(self, dev, plan):
+        """One sample's map from the bank: `dev` = [images of its new views or None, proj, depth_values] and `plan` =
+        (the new views' slots, the sample's slot ids), as _loader hands them over.  Returns forward_features' dict."""
+        # Slot reuse is safe because everything that touches the bank is enqueued here, on the one compute stream,
+        # map by map in sample order: a slot the planner gave to a new view is overwritten only after every earlier
+        # map that read its old view was enqueued.
+        new_slots, slot_ids = plan
+        if dev[0] is not None:
+            feats = self.model.extract_features(dev[0])
+            if self.bank is None:
+                self.bank = torch.empty((self.slots,) + tuple(feats.shape[1:]), dtype=feats.dtype, device=self.device)
+            elif self.bank.shape[1:] != feats.shape[1:]:
+                raise RuntimeError(f"reuse_features: image size changed within the run (features "
+                                   f"{tuple(feats.shape[1:])}, bank {tuple(self.bank.shape[1:])})")
+            for j, slot in enumerate(new_slots):
+                self.bank[slot].copy_(feats[j])
+        return self.model.forward_features(self.bank, [slot_ids], dev[1], dev[2])
+
+
 def save_depth_sharded(model, dataset, outdir: str, rank: int = 0, world: int = 1, device=None,
                        writers: int = 16, save_images: bool = True, decoders: int = 16, decoder_procs: int = 0,
                        decoder_pool=None, reuse_features: bool = False, feature_slots: int = 64):
@@ -315,11 +371,7 @@ def save_depth_sharded(model, dataset, outdir: str, rank: int = 0, world: int = 
         if not hasattr(dataset, "view_plan"):
             raise ValueError("reuse_features needs a dataset with view_plan() (image path of every view), "
                              "e.g. dataset_eval.EvalDataset")
-        if not all(hasattr(model, a) for a in ("extract_features", "forward_features")):
-            raise ValueError("reuse_features needs a model with extract_features / forward_features (MVSNet)")
-        n_max = max((len(dataset.view_plan(i)[1]) for i in mine[:1]), default=0)
-        if feature_slots < max(1, n_max):
-            raise ValueError(f"feature_slots={feature_slots} is below the {n_max} views of one sample")
+        _check_reuse_features(model, dataset, mine[:1], feature_slots)
     model = model.to(device).eval()
     from concurrent.futures import ThreadPoolExecutor
     q: "queue.Queue" = queue.Queue(maxsize=4)
@@ -338,46 +390,17 @@ def save_depth_sharded(model, dataset, outdir: str, rank: int = 0, world: int = 
         th.start()
         futures = []
         cq: "queue.Queue" = queue.Queue(maxsize=4 * max(1, writers))
-        bank = None     # reuse_features: [feature_slots, 32, h, w], allocated at the first sample
+        bank = _FeatureBank(model, feature_slots, device)    # used when reuse_features gives the items a plan
         with ThreadPoolExecutor(max_workers=max(1, writers)) as pool, torch.no_grad():
             errors: list = []
             comp = threading.Thread(target=_completer, args=(cq, pool, futures, device, errors), daemon=True)
             comp.start()
             try:
-                while True:
-                    t0 = _now()
-                    item = q.get()
-                    _tick("main.q_get", t0)
-                    if item is None:
-                        break
-                    if isinstance(item, BaseException):
-                        raise item
+                for _, s, dev, plan in _loaded(q, compute):
                     if errors:      # the completer failed: stop enqueuing forwards
                         break
-                    idx, s, dev, ready, plan = item
-                    compute.wait_event(ready)
-                    for t in dev:
-                        if t is not None:
-                            t.record_stream(compute)
                     t0 = _now()
-                    if plan is None:
-                        out = model(*dev)
-                    else:
-                        # Slot reuse is safe because everything that touches the bank is enqueued here, on
-                        # the one compute stream, in sample order: a slot the planner gave to a new view is
-                        # overwritten only after every earlier map that read its old view was enqueued.
-                        new_slots, slot_ids = plan
-                        if dev[0] is not None:
-                            feats = model.extract_features(dev[0])
-                            if bank is None:
-                                bank = torch.empty((feature_slots,) + tuple(feats.shape[1:]), dtype=feats.dtype,
-                                                   device=device)
-                            elif bank.shape[1:] != feats.shape[1:]:
-                                raise RuntimeError(f"reuse_features: image size changed within the run (features "
-                                                   f"{tuple(feats.shape[1:])}, bank {tuple(bank.shape[1:])})")
-                            for j, slot in enumerate(new_slots):
-                                bank[slot].copy_(feats[j])
-                        out = model.forward_features(bank, [slot_ids], dev[1], dev[2])
+                    out = model(*dev) if plan is None else bank.forward(dev, plan)
                     _tick("main.forward_enqueue", t0)
                     t0 = _now()
                     done = torch.cuda.Event()

@@ -23,7 +23,7 @@ import threading
 
 import torch
 
-from .eval_driver import _loader
+from .eval_driver import _check_reuse_features, _FeatureBank, _loaded, _loader
 from .metrics import DepthMetricsAccumulator
 
 
@@ -42,11 +42,7 @@ def evaluate_depth(model, dataset, batch_size=1, device=None, decoders=16, reuse
     if reuse_features:   # refused before any work starts
         if not hasattr(dataset, "view_plan"):
             raise ValueError("reuse_features needs a dataset with view_plan() (image path of every view)")
-        if not all(hasattr(model, a) for a in ("extract_features", "forward_features")):
-            raise ValueError("reuse_features needs a model with extract_features / forward_features (MVSNet)")
-        n_views = len(dataset.view_plan(0)[1])
-        if feature_slots < n_views:
-            raise ValueError(f"feature_slots={feature_slots} is below the {n_views} views of one sample")
+        _check_reuse_features(model, dataset, indices[:1], feature_slots)
     model = model.to(device).eval()
     acc = DepthMetricsAccumulator(device=device) if accumulator is None else accumulator
     q: "queue.Queue" = queue.Queue(maxsize=4)
@@ -59,7 +55,7 @@ def evaluate_depth(model, dataset, batch_size=1, device=None, decoders=16, reuse
         th.start()
         batch = []      # per item: device inputs [imgs, proj, dv] (plain) or the finished depth map (bank)
         gts = []        # per item: (GT depth [1,h,w], mask [1,h,w])
-        bank = None
+        bank = _FeatureBank(model, feature_slots, device)
 
         def flush():
             depth_gt = torch.cat([g for g, _ in gts]) if len(gts) > 1 else gts[0][0]
@@ -73,35 +69,9 @@ def evaluate_depth(model, dataset, batch_size=1, device=None, decoders=16, reuse
             batch.clear()
             gts.clear()
 
-        while True:
-            item = q.get()
-            if item is None:
-                break
-            if isinstance(item, BaseException):
-                raise item
-            _, _, dev, ready, plan = item
-            compute.wait_event(ready)
-            for t in dev:
-                if t is not None:
-                    t.record_stream(compute)
+        for _, _, dev, plan in _loaded(q, compute):
             gts.append((dev[3], dev[4]))
-            if plan is None:
-                batch.append(dev[:3])
-            else:
-                # map by map, in sample order: a slot given to a new view is overwritten only after every
-                # earlier map that read its old view was enqueued (see eval_driver.save_depth_sharded)
-                new_slots, slot_ids = plan
-                if dev[0] is not None:
-                    feats = model.extract_features(dev[0])
-                    if bank is None:
-                        bank = torch.empty((feature_slots,) + tuple(feats.shape[1:]), dtype=feats.dtype,
-                                           device=device)
-                    elif bank.shape[1:] != feats.shape[1:]:
-                        raise RuntimeError(f"reuse_features: image size changed within the run (features "
-                                           f"{tuple(feats.shape[1:])}, bank {tuple(bank.shape[1:])})")
-                    for j, slot in enumerate(new_slots):
-                        bank[slot].copy_(feats[j])
-                batch.append(model.forward_features(bank, [slot_ids], dev[1], dev[2])["depth"])
+            batch.append(dev[:3] if plan is None else bank.forward(dev, plan)["depth"])   # map by map, in sample order
             if len(gts) == batch_size:
                 flush()
         if gts:
@@ -110,17 +80,9 @@ def evaluate_depth(model, dataset, batch_size=1, device=None, decoders=16, reuse
         return acc.mean()
 
 
-def _load_checkpoint(model, path):
-    """train.py's checkpoint layout: torch.save({'model': state_dict, ...}); keys may carry the `module.` prefix of
-    nn.DataParallel."""
-    state = torch.load(path, map_location="cpu")["model"]
-    state = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
-    model.load_state_dict(state)
-
-
 def main(argv=None):
-    from . import MVSNet
     from .dataset_gt import find_dataset_def
+    from .mvsnet import MVSNet, _load_checkpoint
 
     p = argparse.ArgumentParser(description="Score a checkpoint against ground-truth depth (train.py --mode test)")
     p.add_argument("--dataset", default="dtu_yao", choices=["dtu_yao", "blender"])

@@ -74,9 +74,6 @@ class CostRegNet(nn.Module):
     def forward(self, x):  # pragma: no cover - never called on the product path
         raise RuntimeError("CostRegNet runs inside libmvs_hip (mvs_costreg_forward)")
 
-    def bn_eps(self):
-        return float(self.conv0.bn.eps)
-
 
 class RefineNet(nn.Module):
     """Parameter container only; the reference's RefineNet.forward is broken (mvsnet.py:85,238)."""
@@ -154,17 +151,24 @@ class MVSNet(nn.Module):
         mod = getattr(self._source(), which)
         return {k: v.detach().cpu() for k, v in mod.state_dict().items()}
 
-    def _feature_blob(self, device):
-        key = ("feature", device.index if device.index is not None else torch.cuda.current_device())
-        versions = self._param_versions(self._source().feature)
+    def _packed_blob(self, which, device):
+        """Device copy of the packed weights of `which` ("feature" / "cost_regularization"), packed again when a
+        parameter or buffer of the source module changed.  Cache keys: ("feature", device index) / device index."""
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        key = ("feature", index) if which == "feature" else index
+        pack = _lib.pack_feature_weights if which == "feature" else _lib.pack_weights
+        mod = getattr(self._source(), which)
+        versions = self._param_versions(mod)
         with self._cache_lock:
             hit = self._blob_cache.get(key)
             if hit is not None and hit[0] == versions:
                 return hit[1]
-            state = self._packable_state("feature")
-            blob = _lib.pack_feature_weights(state, eps=self._source().feature.conv0.bn.eps).to(device)
+            blob = pack(self._packable_state(which), eps=float(mod.conv0.bn.eps)).to(device)
             self._blob_cache[key] = (versions, blob)
             return blob
+
+    def _feature_blob(self, device):
+        return self._packed_blob("feature", device)
 
     # One workspace per (device, stream, shape): forwards enqueued on different streams (user side
     # streams, DataParallel worker threads) must not share the variance / activation volumes --
@@ -186,33 +190,35 @@ class MVSNet(nn.Module):
         return self._cached_workspace(key, lambda: _lib.query_forward_workspace(N, H, W, D, dtype), device)
 
     def _weights_blob(self, device):
-        key = device.index if device.index is not None else torch.cuda.current_device()
-        versions = self._param_versions(self._source().cost_regularization)
-        with self._cache_lock:
-            hit = self._blob_cache.get(key)
-            if hit is not None and hit[0] == versions:
-                return hit[1]
-            state = self._packable_state("cost_regularization")
-            blob = _lib.pack_weights(state, eps=self._source().cost_regularization.bn_eps()).to(device)
-            self._blob_cache[key] = (versions, blob)
-            return blob
+        return self._packed_blob("cost_regularization", device)
 
     def _workspace(self, device, N, D, h, w, dtype):
         key = (device.index, _lib._stream(device), N, D, h, w, dtype)
         return self._cached_workspace(key, lambda: _lib.query_workspace(N, 32, D, h, w, dtype), device)
 
-    def _check_inference(self, what, t):
+    def _check_inference(self, what, t, name="a tensor"):
         """The refusals forward() makes: training mode, refine=True, CPU tensors."""
         if self.training:
             raise RuntimeError("this MVSNet is the MI355X inference path; call .eval() "
                                "(training, models/mvsnet.py:167-169, is out of scope)")
         if not t.is_cuda:
             raise RuntimeError(f"MVSNet.{what} needs CUDA(ROCm) tensors: the depth path has no CPU "
-                               f"implementation (got a tensor on {t.device})")
+                               f"implementation (got {name} on {t.device})")
         if self.refine:
             raise NotImplementedError("refine=True: the reference's RefineNet path is broken "
                                       "(F.cat at models/mvsnet.py:85); every working caller passes "
                                       "refine=False (eval.py:308)")
+
+    def _prepare(self, device, proj_matrices, depth_values, B, h, w):
+        """What every forward readies before its enqueues: the projection matrices and depth values on the device,
+        CostRegNet's packed weights, the storage dtype's code and the [B,h,w] depth and confidence outputs."""
+        proj = _lib._dev_f32(proj_matrices.to(device), "proj_matrices")
+        dv = _lib._dev_f32(depth_values.to(device), "depth_values")
+        blob = self._weights_blob(device)
+        dt = _lib.dtype_code(self.storage_dtype)
+        depth = torch.empty((B, h, w), dtype=torch.float32, device=device)
+        conf = torch.empty((B, h, w), dtype=torch.float32, device=device)
+        return proj, dv, blob, dt, depth, conf
 
     # -- shared features ---------------------------------------------------------------------
     # FeatureNet workspace bytes one extract_features chunk may use (about 11 cfg2 images)
@@ -279,13 +285,8 @@ class MVSNet(nn.Module):
         h, w = feats.shape[2], feats.shape[3]
         with torch.cuda.device(device), torch.no_grad():
             feats = _lib._dev_f32(feats, "features")
-            proj = _lib._dev_f32(proj_matrices.to(device), "proj_matrices")
-            dv = _lib._dev_f32(depth_values.to(device), "depth_values")
-            blob = self._weights_blob(device)
-            dt = _lib.dtype_code(self.storage_dtype)
+            proj, dv, blob, dt, depth, conf = self._prepare(device, proj_matrices, depth_values, B, h, w)
             ws = self._workspace(device, N, D, h, w, dt)
-            depth = torch.empty((B, h, w), dtype=torch.float32, device=device)
-            conf = torch.empty((B, h, w), dtype=torch.float32, device=device)
             # one enqueue per batch item on the current stream, as forward
             for b in range(B):
                 _lib.depth_infer_views(feats, rows[b], proj[b], dv[b], blob, ws, depth[b], conf[b], dtype=dt)
@@ -295,16 +296,7 @@ class MVSNet(nn.Module):
     def forward(self, imgs, proj_matrices, depth_values):
         n_imgs, n_proj = imgs.shape[1], proj_matrices.shape[1]
         assert n_imgs == n_proj, "Different number of images and projection matrices"
-        if self.training:
-            raise RuntimeError("this MVSNet is the MI355X inference path; call .eval() "
-                               "(training, models/mvsnet.py:167-169, is out of scope)")
-        if not imgs.is_cuda:
-            raise RuntimeError("MVSNet.forward needs CUDA(ROCm) tensors: the depth path has no CPU "
-                               "implementation (got imgs on {})".format(imgs.device))
-        if self.refine:
-            raise NotImplementedError("refine=True: the reference's RefineNet path is broken "
-                                      "(F.cat at models/mvsnet.py:85); every working caller passes "
-                                      "refine=False (eval.py:308)")
+        self._check_inference("forward", imgs, "imgs")
         device = imgs.device
         # uint8 images -- [B,N,3,H,W], or [B,N,H,W,3] as a decoder yields them -- are the reference loader's pixels
         # before `np.array(img, float32) / 255.` (datasets/data_io.py:143); the HIP FeatureNet divides on the device
@@ -321,13 +313,9 @@ class MVSNet(nn.Module):
                 raise RuntimeError(f"imgs must be [B,N,3,H,W] with H, W multiples of 32, got {tuple(imgs.shape)}")
             with torch.cuda.device(device), torch.no_grad():
                 imgs_f = imgs.contiguous() if imgs.dtype == torch.uint8 else _lib._dev_f32(imgs.to(torch.float32), "imgs")
-                proj = _lib._dev_f32(proj_matrices.to(device), "proj_matrices")
-                dv = _lib._dev_f32(depth_values.to(device), "depth_values")
-                blob, fblob = self._weights_blob(device), self._feature_blob(device)
-                dt = _lib.dtype_code(self.storage_dtype)
+                proj, dv, blob, dt, depth, conf = self._prepare(device, proj_matrices, depth_values, B, H // 4, W // 4)
+                fblob = self._feature_blob(device)
                 ws = self._forward_workspace(device, N, H, W, D, dt)
-                depth = torch.empty((B, H // 4, W // 4), dtype=torch.float32, device=device)
-                conf = torch.empty((B, H // 4, W // 4), dtype=torch.float32, device=device)
                 # steps 1-4 (reference mvsnet.py:125-218): one enqueue per batch item, same stream
                 for b in range(B):
                     _lib.forward_images(imgs_f[b], proj[b], dv[b], fblob, blob, ws, depth[b], conf[b], dtype=dt)
@@ -339,14 +327,17 @@ class MVSNet(nn.Module):
             feats = self.feature(imgs.reshape(B * N, imgs.shape[2], H, W).to(torch.float32))
             C, h, w = feats.shape[1], feats.shape[2], feats.shape[3]
             feats = feats.reshape(B, N, C, h, w).contiguous()
-            proj = _lib._dev_f32(proj_matrices.to(device), "proj_matrices")
-            dv = _lib._dev_f32(depth_values.to(device), "depth_values")
-            blob = self._weights_blob(device)
-            dt = _lib.dtype_code(self.storage_dtype)
+            proj, dv, blob, dt, depth, conf = self._prepare(device, proj_matrices, depth_values, B, h, w)
             ws = self._workspace(device, N, D, h, w, dt)
-            depth = torch.empty((B, h, w), dtype=torch.float32, device=device)
-            conf = torch.empty((B, h, w), dtype=torch.float32, device=device)
             # steps 2-4 (reference mvsnet.py:145-218): one enqueue per batch item, same stream
             for b in range(B):
                 _lib.depth_infer(feats[b], proj[b], dv[b], blob, ws, depth[b], conf[b], dtype=dt)
         return {"depth": depth, "photometric_confidence": conf}
+
+
+def _load_checkpoint(model, path):
+    """train.py's checkpoint layout: torch.save({'model': state_dict, ...}); keys may carry the `module.` prefix of
+    nn.DataParallel."""
+    state = torch.load(path, map_location="cpu")["model"]
+    state = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    model.load_state_dict(state)

@@ -16,7 +16,7 @@ import argparse
 import os
 import re
 
-from .eval_gt import _load_checkpoint
+from .mvsnet import _load_checkpoint
 
 
 def main(argv=None):

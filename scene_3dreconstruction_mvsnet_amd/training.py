@@ -252,13 +252,21 @@ def conv_transpose3d(x, weight):
     return _ConvTranspose3d.apply(x, weight)
 
 
-def _channels_last_check(x, weight, who):
-    for t, name in ((x, "input"), (weight, "weight")):
+def _check_cuda_f32(who, no_cpu, tensors):
+    """`who` refuses those of `tensors` = [(tensor or None, its name)] that are not on the GPU or not float32;
+    `no_cpu` is the clause that says what has no CPU implementation."""
+    for t, name in tensors:
+        if t is None:
+            continue
         if not t.is_cuda:
-            raise RuntimeError(f"{who} needs CUDA(ROCm) tensors: the training convolutions have no CPU implementation "
+            raise RuntimeError(f"{who} needs CUDA(ROCm) tensors: {no_cpu} "
                                f"(got {name} on {t.device})")
         if t.dtype != torch.float32:
             raise RuntimeError(f"{who}: {name} must be float32 (got {t.dtype})")
+
+
+def _channels_last_check(x, weight, who):
+    _check_cuda_f32(who, "the training convolutions have no CPU implementation", ((x, "input"), (weight, "weight")))
     if x.dim() != 5 or weight.dim() != 5:
         raise RuntimeError(f"{who}: input {tuple(x.shape)} must be [B,C,D,H,W] and weight {tuple(weight.shape)} 5-d")
 
@@ -295,14 +303,8 @@ def batch_norm_relu(x, bn, relu=True, skip=None):
     models/mvsnet.py:47-60, 66-70), with autograd, on csrc/train_bn3d.hip.  x [B,C,D,H,W] float32 CUDA in
     channels_last_3d memory format (conv3d's output; anything else is copied), C in {8,16,32,64}, B*D*H*W >= 2;
     skip None or shaped like x -> [B,C,D,H,W] in channels_last_3d memory format."""
-    for t, name in ((x, "input"), (skip, "skip")):
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError(f"batch_norm_relu needs CUDA(ROCm) tensors: the training batch-norm has no CPU "
-                               f"implementation (got {name} on {t.device})")
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"batch_norm_relu: {name} must be float32 (got {t.dtype})")
+    _check_cuda_f32("batch_norm_relu", "the training batch-norm has no CPU implementation",
+                    ((x, "input"), (skip, "skip")))
     if x.dim() != 5 or (skip is not None and skip.shape != x.shape):
         raise RuntimeError(f"batch_norm_relu: input {tuple(x.shape)} must be [B,C,D,H,W] and skip "
                            f"{None if skip is None else tuple(skip.shape)} shaped like it")
@@ -327,25 +329,16 @@ def _conv_bn_relu(block, x):
     return F.relu(block.bn(block.conv(x)), inplace=True)   # models/module.py:32-33
 
 
+def _deconv_bn_relu(seq, x, skip):
+    return skip + seq(x)   # models/mvsnet.py:66-70
+
+
 def _conv_bn_relu_hip(block, x):
     return F.relu(block.bn(conv3d(x, block.conv.weight, None, block.conv.stride[0])), inplace=True)
 
 
-def _deconv_bn_relu_hip(seq, x):
-    return F.relu(seq[1](conv_transpose3d(x, seq[0].weight)), inplace=True)   # models/mvsnet.py:47-60
-
-
-def _costreg_hip(cr, x):
-    """CostRegNet.forward with every convolution on the HIP training kernels; BatchNorm3d (train-mode statistics and
-    their backward), ReLU and the skip additions stay in torch, on channels_last_3d tensors."""
-    conv0 = _conv_bn_relu_hip(cr.conv0, x)
-    conv2 = _conv_bn_relu_hip(cr.conv2, _conv_bn_relu_hip(cr.conv1, conv0))
-    conv4 = _conv_bn_relu_hip(cr.conv4, _conv_bn_relu_hip(cr.conv3, conv2))
-    x = _conv_bn_relu_hip(cr.conv6, _conv_bn_relu_hip(cr.conv5, conv4))
-    x = conv4 + _deconv_bn_relu_hip(cr.conv7, x)
-    x = conv2 + _deconv_bn_relu_hip(cr.conv9, x)
-    x = conv0 + _deconv_bn_relu_hip(cr.conv11, x)
-    return conv3d(x, cr.prob.weight, cr.prob.bias, 1)
+def _deconv_bn_relu_hip(seq, x, skip):
+    return skip + F.relu(seq[1](conv_transpose3d(x, seq[0].weight)), inplace=True)   # models/mvsnet.py:47-60
 
 
 def _conv_bn_relu_fused(block, x):
@@ -356,40 +349,41 @@ def _deconv_bn_relu_fused(seq, x, skip):
     return batch_norm_relu(conv_transpose3d(x, seq[0].weight), seq[1], skip=skip)   # models/mvsnet.py:47-60, 66-70
 
 
-def _costreg_hip_fused(cr, x):
-    """CostRegNet.forward with nothing left to torch: the convolutions as _costreg_hip runs them, and after each of
-    the ten normalised layers one batch_norm_relu (the three deconvolution layers with their skip)."""
-    conv0 = _conv_bn_relu_fused(cr.conv0, x)
-    conv2 = _conv_bn_relu_fused(cr.conv2, _conv_bn_relu_fused(cr.conv1, conv0))
-    conv4 = _conv_bn_relu_fused(cr.conv4, _conv_bn_relu_fused(cr.conv3, conv2))
-    x = _conv_bn_relu_fused(cr.conv6, _conv_bn_relu_fused(cr.conv5, conv4))
-    x = _deconv_bn_relu_fused(cr.conv7, x, conv4)
-    x = _deconv_bn_relu_fused(cr.conv9, x, conv2)
-    x = _deconv_bn_relu_fused(cr.conv11, x, conv0)
-    return conv3d(x, cr.prob.weight, cr.prob.bias, 1)
+def _prob(prob, x):
+    return prob(x)
 
 
-COSTREG_IMPLS = ("torch", "hip", "hip_fused")
+def _prob_hip(prob, x):
+    return conv3d(x, prob.weight, prob.bias, 1)
+
+
+# impl -> (ConvBnReLU3D block, deconvolution block with its skip, the prob convolution):
+#   "torch"      through the blocks' .conv / .bn modules;
+#   "hip"        every convolution on the HIP training kernels; BatchNorm3d (train-mode statistics and their backward),
+#                ReLU and the skip additions stay in torch, on channels_last_3d tensors;
+#   "hip_fused"  nothing left to torch: the convolutions as "hip" runs them, and after each of the ten normalised
+#                layers one batch_norm_relu (the three deconvolution layers with their skip).
+_COSTREG_BLOCKS = {"torch": (_conv_bn_relu, _deconv_bn_relu, _prob),
+                   "hip": (_conv_bn_relu_hip, _deconv_bn_relu_hip, _prob_hip),
+                   "hip_fused": (_conv_bn_relu_fused, _deconv_bn_relu_fused, _prob_hip)}
+COSTREG_IMPLS = tuple(_COSTREG_BLOCKS)
 
 
 def _costreg(cr, x, impl="torch"):
     """CostRegNet.forward (models/mvsnet.py:64-73): impl "torch" through the blocks' .conv / .bn modules, "hip" with
     the convolutions on csrc/train_conv3d.hip, "hip_fused" with BatchNorm3d, ReLU and the skip additions on
     csrc/train_bn3d.hip as well."""
-    if impl == "hip":
-        return _costreg_hip(cr, x)
-    if impl == "hip_fused":
-        return _costreg_hip_fused(cr, x)
-    if impl != "torch":
+    if impl not in COSTREG_IMPLS:
         raise RuntimeError(f"costreg_impl must be 'torch', 'hip' or 'hip_fused', got {impl!r}")
-    conv0 = _conv_bn_relu(cr.conv0, x)
-    conv2 = _conv_bn_relu(cr.conv2, _conv_bn_relu(cr.conv1, conv0))
-    conv4 = _conv_bn_relu(cr.conv4, _conv_bn_relu(cr.conv3, conv2))
-    x = _conv_bn_relu(cr.conv6, _conv_bn_relu(cr.conv5, conv4))
-    x = conv4 + cr.conv7(x)
-    x = conv2 + cr.conv9(x)
-    x = conv0 + cr.conv11(x)
-    return cr.prob(x)
+    conv, deconv, prob = _COSTREG_BLOCKS[impl]
+    conv0 = conv(cr.conv0, x)
+    conv2 = conv(cr.conv2, conv(cr.conv1, conv0))
+    conv4 = conv(cr.conv4, conv(cr.conv3, conv2))
+    x = conv(cr.conv6, conv(cr.conv5, conv4))
+    x = deconv(cr.conv7, x, conv4)
+    x = deconv(cr.conv9, x, conv2)
+    x = deconv(cr.conv11, x, conv0)
+    return prob(cr.prob, x)
 
 
 class TrainableMVSNet(MVSNet):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import fuse_ref
+from test_host_logic import header_argtypes
 from scene_3dreconstruction_mvsnet_amd import _lib, fusion
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -104,6 +105,11 @@ def test_fuse_symbols_are_the_declarations_of_the_fuse_header():
     declared = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", src, flags=re.M)
     assert sorted(declared) == sorted(_lib.FUSE_SYMBOLS) and len(set(declared)) == len(declared)
     assert not set(_lib.FUSE_SYMBOLS) & set(_lib.SYMBOLS)       # SYMBOLS stays mvs_abi.h alone
+    prototypes = header_argtypes(src)       # and every argument list handed to ctypes is its prototype's
+    assert sorted(prototypes) == sorted(declared)
+    for name, kinds in prototypes.items():
+        assert _lib._ABI["mvs_fuse_abi.h"][name] == kinds, name
+        assert list(getattr(_lib.load(), name).argtypes) == kinds, name
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(raw, name), name
