@@ -53,8 +53,8 @@ _vpp = ctypes.POINTER(_vp)      # const float* const*
 
 # Every entry point, declared once on this side: header -> {name: argument types}, in the headers' order.  Any other
 # pointer is a c_void_p (device and host addresses travel as integers).  load() applies the table; SYMBOLS and
-# FUSE_SYMBOLS are its keys; tests/test_host_logic.py and tests/test_scan_fusion_host.py hold every argument list to
-# its prototype.  Everything returns int except mvs_last_error_string.
+# FUSE_SYMBOLS and CLOUD_SYMBOLS are its keys; tests/test_host_logic.py, tests/test_scan_fusion_host.py and
+# tests/test_cloud_downsample_host.py hold every argument list to its prototype.  Everything returns int except mvs_last_error_string.
 _ABI = {
     "mvs_abi.h": {
         "mvs_abi_version": [],
@@ -102,9 +102,14 @@ _ABI = {
         "mvs_query_fuse_workspace": [_i, _i, _i, _szp],
         "mvs_fuse_points": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _vp, _sz, _vp],
     },
+    "mvs_cloud_abi.h": {
+        "mvs_query_cloud_workspace": [_ll, _vp, _vp, _d, _szp],
+        "mvs_cloud_downsample": [_vp, _i, _vp, _ll, _vp, _vp, _d, _d, _ll, _vp, _vp, _vp, _vp, _sz, _vp],
+    },
 }
 SYMBOLS = tuple(_ABI["mvs_abi.h"])
 FUSE_SYMBOLS = tuple(_ABI["mvs_fuse_abi.h"])
+CLOUD_SYMBOLS = tuple(_ABI["mvs_cloud_abi.h"])
 
 
 class MvsError(RuntimeError):
@@ -127,7 +132,7 @@ def load():
                 "g.build()'` (or make -C scene_3dreconstruction_mvsnet_amd/csrc). "
                 "There is no CPU/PyTorch fallback for the MVSNet depth path.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name in SYMBOLS + FUSE_SYMBOLS:
+        for name in SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS:
             if not hasattr(lib, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}")
         for prototypes in _ABI.values():
@@ -692,6 +697,80 @@ def fuse_points(xyz_world, masks, images, ref_idx, capacity=None, out=None):
                                      rgb.data_ptr() if capacity else None, counts.data_ptr(), ws.data_ptr(), ws.numel(),
                                      _stream(dev)))
     return xyz, rgb, counts
+
+
+# ---- crop + voxel downsample of a cloud (include/mvs_cloud_abi.h, csrc/cloud_downsample.hip) ----
+MVS_CLOUD_F32, MVS_CLOUD_F64 = 0, 1
+CLOUD_CHUNK, CLOUD_TILE, CLOUD_SCAN_WIDTH, CLOUD_RECORD = 1024, 1024, 1024, 64     # the header's MVS_CLOUD_* sizes
+
+
+def _box_arg(box_min, box_max, who):
+    """Two host triples -> two ctypes double[3] (the library reads them before it returns)."""
+    out = []
+    for name, b in (("box_min", box_min), ("box_max", box_max)):
+        if isinstance(b, torch.Tensor):
+            if b.device.type != "cpu":
+                raise RuntimeError(f"{who}: {name} must be host numbers (got a tensor on {b.device}): the box travels in "
+                                   "the kernel arguments, reading device memory would sync")
+            b = b.tolist()
+        b = [float(x) for x in b]
+        if len(b) != 3:
+            raise RuntimeError(f"{who}: {name} must hold 3 numbers, got {len(b)}")
+        out.append((_d * 3)(*b))
+    return out
+
+
+def query_cloud_workspace(P, box_min, box_max, voxel_size) -> int:
+    lo, hi = _box_arg(box_min, box_max, "query_cloud_workspace")
+    return _query("mvs_query_cloud_workspace", int(P), ctypes.addressof(lo), ctypes.addressof(hi), float(voxel_size))
+
+
+def cloud_downsample(xyz, rgb, box_min, box_max, voxel_size, scale=1.0, capacity=None, out=None):
+    """Crop a coloured cloud to a box and keep the mean point and colour of every occupied voxel (the reference's
+    pcd.crop / voxel_down_sample / scale, eval.py:831-840, as include/mvs_cloud_abi.h defines them), on the device.
+
+    xyz float32 or float64 [P,3] and rgb uint8 [P,3] on one device; box_min, box_max: 3 host numbers each.  Returns
+    (xyz float32 [capacity,3], rgb uint8 [capacity,3], counts int64 [2]: kept points, occupied voxels), all on the
+    device, voxels in ascending (iz, iy, ix); rows at and beyond counts[1] are not written.  capacity defaults to P,
+    which always suffices; with less, the first `capacity` voxels are written and counts stays exact.  `out` =
+    (xyz, rgb, counts) receives the results.  Enqueued on the current stream; nothing synchronises."""
+    for name, t in (("xyz", xyz), ("rgb", rgb)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"cloud_downsample: {name} must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    dev = xyz.device
+    if rgb.device != dev:
+        raise RuntimeError("cloud_downsample: xyz and rgb must be on one device")
+    if xyz.dtype not in (torch.float32, torch.float64) or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError(f"cloud_downsample: xyz must be float32 or float64 [P,3], got {xyz.dtype} {tuple(xyz.shape)}")
+    P = xyz.shape[0]
+    if rgb.dtype != torch.uint8 or tuple(rgb.shape) != (P, 3):
+        raise RuntimeError(f"cloud_downsample: rgb must be uint8 [P,3] = [{P},3], got {rgb.dtype} {tuple(rgb.shape)}")
+    lo, hi = _box_arg(box_min, box_max, "cloud_downsample")
+    capacity = P if capacity is None else int(capacity)
+    if capacity < 0:
+        raise RuntimeError(f"cloud_downsample: capacity {capacity} is negative")
+    xyz, rgb = xyz.contiguous(), rgb.contiguous()
+    nbytes = _query("mvs_query_cloud_workspace", P, ctypes.addressof(lo), ctypes.addressof(hi), float(voxel_size))
+    with torch.cuda.device(dev):
+        if out is None:
+            xyz_out = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
+            rgb_out = torch.empty((capacity, 3), dtype=torch.uint8, device=dev)
+            counts = torch.empty((2,), dtype=torch.int64, device=dev)
+        else:
+            xyz_out, rgb_out, counts = out
+            for t, shape, dt, name in ((xyz_out, (capacity, 3), torch.float32, "xyz"),
+                                       (rgb_out, (capacity, 3), torch.uint8, "rgb"), (counts, (2,), torch.int64, "counts")):
+                _check_out(t, shape, dt, dev, f"cloud_downsample: out {name}", f"{dt} {shape} tensor on {dev}")
+        if P == 0:          # an empty tensor has no address to hand over: the two zero counts of the header's P == 0
+            counts.zero_()
+            return xyz_out, rgb_out, counts
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(load().mvs_cloud_downsample(xyz.data_ptr(), MVS_CLOUD_F64 if xyz.dtype == torch.float64 else MVS_CLOUD_F32,
+                                          rgb.data_ptr(), P, ctypes.addressof(lo), ctypes.addressof(hi), float(voxel_size),
+                                          float(scale), capacity, xyz_out.data_ptr() if capacity else None,
+                                          rgb_out.data_ptr() if capacity else None, counts.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), _stream(dev)))
+    return xyz_out, rgb_out, counts
 
 
 # ---- FeatureNet (reference models/mvsnet.py:10-30) -------------------------------------------

@@ -7,7 +7,9 @@ All reference views of a scan go through ONE launch of `mvs_filter_depth`; the n
 loops of the reference are not reproduced on the host.  In `filter_depth`, which works from the depth stage's files,
 file I/O and the boolean selection of the fused points (eval.py:753-759) stay on the host.  `fuse_views` does that
 selection on the device (mvs_fuse_points), and `reconstruct_scan` is the whole chain -- images of a scan in, its
-coloured point cloud out -- without a file in between.
+coloured point cloud out -- without a file in between.  `downsample_cloud` is eval.py's last step for the bin-picking
+datasets (eval.py:831-840: crop to the bin's outer box `bin_box`, voxel_down_sample, scale), on the device
+(mvs_cloud_downsample); `reconstruct_scan(..., downsample=...)` appends it to the chain.
 
 Differences from the reference, flagged rather than hidden:
   * cv2.remap is restated inside the kernel (1/32-pixel quantised bilinear, zero border); OpenCV is
@@ -183,15 +185,61 @@ def fuse_views(filtered, images, pairs_or_ref_idx, capacity=None):
     return xyz[:total], rgb[:total], counts[:-1]
 
 
+def bin_box(dims=(0.57, 0.37, 0.22), delta=(0, 0, 0), wall=20.0, scale=1.0):
+    """The outer box of the bin, the reference's bbox2 (get_o3d_frame_bbox, eval.py:188-213), as (min, max) in mm.
+
+    dims: the bin's inner size in metres, delta: its offset in metres (both times 1000 * scale), wall: the wall
+    thickness in mm (not scaled, as in the reference).  The bin is centred on the origin in x and y and stands on z = 0;
+    the walls are added on every side but the open top.  The default is (-305, -205, -20), (305, 205, 220);
+    delta=(0.08, 0.03, 0) is the reference's "overhead02" / "overhead03" setting."""
+    size = np.asarray(dims, np.float64) * 1000 * scale
+    shift = np.asarray(delta, np.float64) * 1000 * scale
+    if size.shape != (3,) or shift.shape != (3,):
+        raise ValueError(f"bin_box: dims and delta must hold 3 numbers each, got {dims!r} and {delta!r}")
+    lo = np.array([-size[0] / 2, -size[1] / 2, 0.0]) + shift - wall
+    hi = np.array([size[0] / 2, size[1] / 2, size[2]]) + shift + np.array([wall, wall, 0.0])
+    return lo, hi
+
+
+def downsample_cloud(xyz, rgb, voxel_size=5.0, box=None, scale=0.01, capacity=None):
+    """eval.py:831-840 on the device: crop the cloud to `box` = (min, max) (default bin_box(), in the cloud's units), keep
+    the mean point and colour of every occupied voxel of size `voxel_size`, scale the coordinates.  xyz float32 or
+    float64 [P,3], rgb uint8 [P,3], on the GPU.  Returns (xyz float32 [Q,3], rgb uint8 [Q,3]) on the device, voxels in
+    ascending (iz, iy, ix).  Reading the two counts is the one host synchronisation.  capacity (default P, always
+    enough) bounds the device buffers."""
+    lo, hi = bin_box() if box is None else box
+    out_xyz, out_rgb, counts = _lib.cloud_downsample(xyz, rgb, lo, hi, voxel_size, scale=scale, capacity=capacity)
+    voxels = int(counts.cpu()[1])
+    if voxels > out_xyz.shape[0]:
+        raise RuntimeError(f"downsample_cloud: the cloud occupies {voxels} voxels, capacity is {out_xyz.shape[0]}")
+    return out_xyz[:voxels], out_rgb[:voxels]
+
+
+def _packed_to_host(xyz, rgb):
+    """Device points and colours -> host (float32 [P,3], uint8 [P,3]) in one copy."""
+    P = xyz.shape[0]
+    packed = torch.cat([xyz.reshape(-1).view(torch.uint8), rgb.reshape(-1)]).cpu().numpy()
+    return packed[:12 * P].view(np.float32).reshape(P, 3), packed[12 * P:].reshape(P, 3)
+
+
 def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8, geomask=3, condmask_pixel=1.0,
-                     condmask_depth=0.01, plyfilename=None, batch=1, device=None):
+                     condmask_depth=0.01, plyfilename=None, batch=1, device=None, downsample=None):
     """eval.py's save_depth + filter_depth for one scan of an EvalDataset, in memory: every image is decoded once (as
     uint8), FeatureNet runs once per image, every reference view's depth and confidence map is computed from that
     feature bank, and the maps are filtered and fused on the device.  No file is written except the optional PLY; the
     packed points are the one device-to-host copy.  The cameras of the filter are the ones each sample carries for its
     reference view (what the depth stage writes to cams/).  `batch` maps go through one forward_features call.
-    Returns (vertices float32 [P,3], colours uint8 [P,3]); the PLY equals `filter_depth`'s byte for byte."""
+    Returns (vertices float32 [P,3], colours uint8 [P,3]); the PLY equals `filter_depth`'s byte for byte.
+    downsample=dict(voxel_size=5.0, box=None, scale=0.01, plyfilename=None) also runs `downsample_cloud` on the fused
+    cloud while it is on the device; the return is then (vertices, colours, ds_vertices float32 [Q,3], ds_colours uint8
+    [Q,3]) and the downsampled cloud goes to its own plyfilename through write_ply."""
     import copy
+    if downsample is not None:
+        downsample = dict(downsample)
+        ds_ply = downsample.pop("plyfilename", None)
+        unknown = set(downsample) - {"voxel_size", "box", "scale"}
+        if unknown:
+            raise ValueError(f"downsample: unknown keys {sorted(unknown)} (voxel_size, box, scale, plyfilename)")
     for a in ("view_plan", "decode_view", "assemble", "metas"):
         if not hasattr(dataset, a):
             raise ValueError("reconstruct_scan needs a dataset with metas, view_plan(), decode_view() and assemble(), "
@@ -266,10 +314,13 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
         filtered = filter_views(depths, confs, Ks, Es, pairs, n_view_filter, photomask, geomask, condmask_pixel,
                                 condmask_depth, device)
         xyz, rgb, _ = fuse_views(filtered, imgs, [slot[r] for r in refs])
-        P = xyz.shape[0]
-        packed = torch.cat([xyz.reshape(-1).view(torch.uint8), rgb.reshape(-1)]).cpu().numpy()   # the one copy
-    vertices = packed[:12 * P].view(np.float32).reshape(P, 3)
-    colours = packed[12 * P:].reshape(P, 3)
+        if downsample is not None:
+            ds_vertices, ds_colours = _packed_to_host(*downsample_cloud(xyz, rgb, **downsample))
+        vertices, colours = _packed_to_host(xyz, rgb)      # the one copy of the full cloud
     if plyfilename:
         write_ply(plyfilename, vertices, colours)
-    return vertices, colours
+    if downsample is None:
+        return vertices, colours
+    if ds_ply:
+        write_ply(ds_ply, ds_vertices, ds_colours)
+    return vertices, colours, ds_vertices, ds_colours

@@ -9,6 +9,11 @@ Each scan of the list goes through fusion.reconstruct_scan and is written to OUT
 eval.py gives it (scan_id = the first number in the scan's name).  eval.py picks the camera folder, the image path
 pattern and the image size from a table keyed by --dataset_name; here they are the flags --cam_subfolder,
 --img_subfolder and --img_res, with EvalDataset's defaults.
+
+--downsample_mm V adds eval.py's last step for the bin-picking datasets (eval.py:831-840): the fused cloud is cropped to
+the bin's outer box, voxel-downsampled at V and scaled by --cloud_scale on the device, and written to
+OUT/<scan>/fused_dwnsmpld_<V>mm.ply, eval.py's name and place.  The box is --crop_box x0 y0 z0 x1 y1 z1 (in the cloud's
+units), or the bin of --bin_dims / --bin_delta (metres, fusion.bin_box).
 """
 from __future__ import annotations
 
@@ -19,10 +24,15 @@ import re
 from .mvsnet import _load_checkpoint
 
 
+def downsampled_name(voxel_mm):
+    """eval.py:836's file name: fused_dwnsmpld_5mm.ply for 5 and 5.0, fused_dwnsmpld_2.5mm.ply for 2.5."""
+    return f"fused_dwnsmpld_{voxel_mm:g}mm.ply"
+
+
 def main(argv=None):
     from . import MVSNet
     from .dataset_eval import EvalDataset
-    from .fusion import reconstruct_scan
+    from .fusion import bin_box, reconstruct_scan
 
     p = argparse.ArgumentParser(description="Reconstruct every scan of a list into a fused, coloured point cloud")
     p.add_argument("--testpath", required=True)
@@ -42,7 +52,21 @@ def main(argv=None):
     p.add_argument("--cam_subfolder", default="Cameras")
     p.add_argument("--img_subfolder", default="Rectified/{}/rect_{:0>3}_3_r5000.png")
     p.add_argument("--img_res", type=int, nargs=2, default=(512, 640), metavar=("H", "W"))
+    p.add_argument("--downsample_mm", type=float, default=None, metavar="V",
+                   help="also write OUT/<scan>/fused_dwnsmpld_<V>mm.ply: the cloud cropped to the box, one point per voxel of size V")
+    p.add_argument("--crop_box", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                   help="the box to keep, in the cloud's units (instead of --bin_dims / --bin_delta)")
+    p.add_argument("--bin_dims", type=float, nargs=3, default=(0.57, 0.37, 0.22), metavar=("DX", "DY", "DZ"),
+                   help="inner size of the bin in metres (eval.py's get_o3d_frame_bbox)")
+    p.add_argument("--bin_delta", type=float, nargs=3, default=(0.0, 0.0, 0.0), metavar=("X", "Y", "Z"),
+                   help="offset of the bin in metres (0.08 0.03 0 is eval.py's overhead02 / overhead03)")
+    p.add_argument("--cloud_scale", type=float, default=0.01, help="factor on the downsampled coordinates (eval.py:839)")
     args = p.parse_args(argv)
+    if args.downsample_mm is None and args.crop_box is not None:
+        p.error("--crop_box needs --downsample_mm")
+    box = None
+    if args.downsample_mm is not None:
+        box = (args.crop_box[:3], args.crop_box[3:]) if args.crop_box else bin_box(args.bin_dims, args.bin_delta)
     ds = EvalDataset(args.testpath, args.testlist, "test", args.NviewGen, args.numdepth, args.interval_scale,
                      pairfile=args.pairfile, cam_subfolder=args.cam_subfolder, img_subfolder=args.img_subfolder,
                      img_res=tuple(args.img_res), dataset_name=args.dataset_name, image_dtype="uint8")
@@ -53,11 +77,19 @@ def main(argv=None):
     for scan in dict.fromkeys(m[0] for m in ds.metas):
         scan_id = int(re.findall(r"\d+", scan)[0])
         ply = os.path.join(args.outdir, "mvsnet{:0>3}_l3.ply".format(scan_id))
-        vertices, _ = reconstruct_scan(model, ds, scan, n_view_filter=args.NviewFilter, photomask=args.photomask,
-                                       geomask=args.geomask, condmask_pixel=args.condmask_pixel,
-                                       condmask_depth=args.condmask_depth, plyfilename=ply)
-        print(f"{scan}: {len(vertices)} points -> {ply}")
+        downsample = None
+        if box is not None:
+            os.makedirs(os.path.join(args.outdir, scan), exist_ok=True)
+            small = os.path.join(args.outdir, scan, downsampled_name(args.downsample_mm))
+            downsample = dict(voxel_size=args.downsample_mm, box=box, scale=args.cloud_scale, plyfilename=small)
+        got = reconstruct_scan(model, ds, scan, n_view_filter=args.NviewFilter, photomask=args.photomask,
+                               geomask=args.geomask, condmask_pixel=args.condmask_pixel,
+                               condmask_depth=args.condmask_depth, plyfilename=ply, downsample=downsample)
+        print(f"{scan}: {len(got[0])} points -> {ply}")
         written.append(ply)
+        if downsample:
+            print(f"{scan}: {len(got[2])} voxels of {args.downsample_mm:g} -> {small}")
+            written.append(small)
     return written
 
 
