@@ -19,6 +19,7 @@
 // holds what differs.
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "mvs_internal.h"
 #include "storage.h"
@@ -48,8 +49,11 @@ static inline uint16_t to_bits16(float v, int dt) {
 
 // =============================================================================================
 // operand policies of the tile kernels (convg16_mfma_kernel, deconvg16_mfma_kernel): what 16-bit storage and fp32
-// storage with split operands do differently.  The tile geometry, block order, k-step scheme, chunk pipeline and
-// epilogue are the kernels' own and the same for both.
+// storage with split operands do differently.  The tile geometry, block order, k-step scheme and epilogue are the
+// kernels' own and the same for both.  STEPWISE selects the chunk pipeline and the A-fragment addressing: with split
+// operands a chunk has six times the MFMAs and three times the panel of a 16-bit one, and the next panel is re-requested
+// k-step by k-step under the MFMAs (convg16_mfma_kernel has the description); the 16-bit kernels, whose MFMA phase is too
+// short to hide anything behind (measured: -8 % .. +12 %), request it after the chunk's MFMAs.
 //   Op16<DT> : fp16 / bf16 volumes.  A staged voxel is one 16-byte piece, one panel, one 16-bit MFMA per k-step;
 //              threads past the last halo voxel are masked (loff = -1).
 //   OpSplit  : fp32 volumes (round 4).  Every fp32 operand is written as the sum of three bf16 numbers (a = a1 + a2 + a3,
@@ -61,10 +65,14 @@ static inline uint16_t to_bits16(float v, int dt) {
 //              (three tiles); the weights are split on the host (three panels in the layout of the 16-bit kernels:
 //              pack_split_panels).  Threads past the last halo voxel shadow it (no branch in the staging code).
 // =============================================================================================
+// sched_barrier mask of the point that pins a VMEM request between two k-steps: VALU (0x2), SALU (0x4) and LDS reads
+// (0x100: the A fragments of the next k-step are read ahead) may still move across it; MFMAs and VMEM may not
+constexpr int kSchedPin = 0x106;
 template <int DT>
 struct Op16 {
     using T = unsigned short;           // storage element
     static constexpr int NPC = 1;       // pieces: tiles in LDS, panels of the B operand
+    static constexpr bool STEPWISE = false;   // chunk pipeline: the next panel after the chunk's MFMAs (false) / k-step by k-step under them
     static constexpr bool CLAMP = false;   // threads past the last halo voxel: masked (false) / shadow it (true)
     struct Stage {                      // one staged voxel
         u32x4 v;
@@ -95,6 +103,7 @@ struct Op16 {
 struct OpSplit {
     using T = float;
     static constexpr int NPC = 3;
+    static constexpr bool STEPWISE = true;
     static constexpr bool CLAMP = true;
     struct Stage {
         f32x4 lo, hi;
@@ -163,10 +172,22 @@ struct ConvG16 {
         const int t = tap > 26 ? 26 : tap;
         return (((t / 9) * HY + (t / 3) % 3) * HXP + t % 3) * VS;
     }
+    // origin of M-tile t (x fastest, then y, then z) in the halo tile
+    static constexpr int mt_off(int t) {
+        return ((((t / (BX * BY)) * S) * HY + 2 * ((t / BX) % BY) * S) * HXP + 8 * (t % BX) * S) * VS;
+    }
+    // a wave's M-tiles MPW * mg + i: does counting i up never carry into a digit that depends on mg?  Then
+    // mt_off(MPW * mg + i) = mt_off(MPW * mg) + mt_off(i), and the second term is an immediate of the LDS read
+    static constexpr bool MT_SPLITS = BX % MPW == 0 || (MPW % BX == 0 && BY % (MPW / BX) == 0) || MPW % (BX * BY) == 0;
 };
 
+// waves per SIMD the register allocation must leave room for: three for conv2 / conv3 with split operands (168 VGPRs: three
+// 4-wave blocks per CU, which their LDS tiles allow; conv2 would take 172 and run two), the compiler's choice elsewhere
+template <class Op, int CIN>
+constexpr int convg16_waves() { return (Op::STEPWISE && CIN == 16) ? 3 : 1; }
+
 template <class Op, int CIN, int COUT, int S, int BZ, int BY, int BX>
-__global__ __launch_bounds__(256) void convg16_mfma_kernel(
+__global__ __launch_bounds__(256, (convg16_waves<Op, CIN>())) void convg16_mfma_kernel(
     const typename Op::T* __restrict__ x,     // [CIN/8][Di][Hi][Wi][8]
     const unsigned short* __restrict__ bp,    // [Op::NPC pieces][NCH][NT][7][64][8] 16-bit
     const float* __restrict__ bias,           // [COUT]
@@ -184,7 +205,9 @@ __global__ __launch_bounds__(256) void convg16_mfma_kernel(
     unsigned short* tile = reinterpret_cast<unsigned short*>(lds_raw);
     float* otile = reinterpret_cast<float*>(lds_raw);
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    // wave-uniform; with split operands also known to be: the panel's addresses stay scalar
+    const int wave = Op::STEPWISE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int nt = wave % G::NT, mg = wave / G::NT;
     const int nbx = (Wo + 8 * BX - 1) / (8 * BX), nby = (Ho + 2 * BY - 1) / (2 * BY);
     int b = xcd_block();   // XCD-aware order of the (z, row, column) tile sequence: tiles sharing halo planes / rows meet in one L2
@@ -213,20 +236,34 @@ __global__ __launch_bounds__(256) void convg16_mfma_kernel(
     }
 
     // A fragment: lane (r = lane&15 -> voxel (ry, rx) of the M-tile, g = lane>>4 -> tap 4ks+g)
+    // Its address is aoff[M-tile] + koff[k-step].  With split operands koff holds the wave's first M-tile, the lane's voxel
+    // and the lane's tap, and aoff the M-tile's offset from the first, an immediate of the LDS read wherever the geometry
+    // allows: seven address registers, where the compiler kept one per (k-step, M-tile) and conv2 did not fit three waves
+    // per SIMD.  16-bit storage keeps the form it had (aoff: M-tile and voxel, koff: tap).
     const int r = lane & 15, g = lane >> 4;
     const int ry = r >> 3, rx = r & 7;
-    int abase[G::MPW];
+    int aoff[G::MPW], koff[G::KS];
+    if constexpr (Op::STEPWISE) {
+        const int mt0 = G::mt_off(mg * G::MPW);
+        const int abase = mt0 + ((ry * S) * G::HXP + rx * S) * G::VS;
 #pragma unroll
-    for (int i = 0; i < G::MPW; ++i) {
-        const int t = mg * G::MPW + i;
-        const int tx = t % BX, ty = (t / BX) % BY, tz = t / (BX * BY);
-        abase[i] = (((tz * S) * G::HY + (2 * ty + ry) * S) * G::HXP + (8 * tx + rx) * S) * G::VS;
+        for (int i = 0; i < G::MPW; ++i) aoff[i] = G::MT_SPLITS ? G::mt_off(i) : G::mt_off(mg * G::MPW + i) - mt0;
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks)
+            koff[ks] = abase + (g == 0 ? G::tap_off(4 * ks) : g == 1 ? G::tap_off(4 * ks + 1)
+                              : g == 2 ? G::tap_off(4 * ks + 2) : G::tap_off(4 * ks + 3));
+    } else {
+#pragma unroll
+        for (int i = 0; i < G::MPW; ++i) {
+            const int t = mg * G::MPW + i;
+            const int tx = t % BX, ty = (t / BX) % BY, tz = t / (BX * BY);
+            aoff[i] = (((tz * S) * G::HY + (2 * ty + ry) * S) * G::HXP + (8 * tx + rx) * S) * G::VS;
+        }
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks)
+            koff[ks] = g == 0 ? G::tap_off(4 * ks) : g == 1 ? G::tap_off(4 * ks + 1)
+                     : g == 2 ? G::tap_off(4 * ks + 2) : G::tap_off(4 * ks + 3);
     }
-    int koff[G::KS];
-#pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks)
-        koff[ks] = g == 0 ? G::tap_off(4 * ks) : g == 1 ? G::tap_off(4 * ks + 1)
-                 : g == 2 ? G::tap_off(4 * ks + 2) : G::tap_off(4 * ks + 3);
 
     f32x4 acc[G::MPW];
 #pragma unroll
@@ -234,12 +271,11 @@ __global__ __launch_bounds__(256) void convg16_mfma_kernel(
     u32x4 breg[Op::NPC * G::KS];   // [piece][k-step]
     typename Op::Stage stg[G::PPT];
 
-    auto load_b = [&](int c) {
-        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NT + nt) * G::KS) * 64 + lane;
+    // the fragments of k-step ks of chunk c, all pieces
+    auto load_b_step = [&](int c, int ks) {
+        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NT + nt) * G::KS + ks) * 64 + lane;
 #pragma unroll
-        for (int q = 0; q < Op::NPC; ++q)
-#pragma unroll
-            for (int ks = 0; ks < G::KS; ++ks) breg[q * G::KS + ks] = bsrc[q * PANEL + ks * 64];
+        for (int q = 0; q < Op::NPC; ++q) breg[q * G::KS + ks] = bsrc[q * PANEL];
     };
     auto load_a = [&](int c) {
         const typename Op::T* plane = x + (size_t)c * Vin * 8;
@@ -251,24 +287,73 @@ __global__ __launch_bounds__(256) void convg16_mfma_kernel(
         for (int i = 0; i < G::PPT; ++i) stg[i].stage(tile, G::TILE_ELEMS, loff[i], (inside >> i) & 1u);
     };
 
-    load_b(0);
-    load_a(0);
-    store_a();
-    __syncthreads();
+    auto load_b = [&](int c) {   // the whole panel of chunk c
+        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NT + nt) * G::KS) * 64 + lane;
+#pragma unroll
+        for (int q = 0; q < Op::NPC; ++q)
+#pragma unroll
+            for (int ks = 0; ks < G::KS; ++ks) breg[q * G::KS + ks] = bsrc[q * PANEL + ks * 64];
+    };
+
+    // chunk pipeline, split operands.  The activations of chunk 0 are requested before the panel, so that staging them waits for them alone
+    // and the panel arrives behind the split and the barrier.  Chunk c multiplies while chunk c + 1 arrives: its activations
+    // are requested at the top, and the panel's fragments are re-requested k-step by k-step, each as soon as the last MFMA
+    // that reads it has issued (the MFMAs consume the fragments in k-step order) -- the panel's way through L2 / L1 (21 KB per
+    // wave and chunk with split operands) runs under the MFMAs instead of after them, in front of the two barriers.  The last
+    // chunk is peeled off: no VMEM instruction of the loop sits behind a branch and none is issued for nothing.
+    // 16-bit storage (else branch): the whole panel of chunk c + 1 after the MFMAs of chunk c.
+    if constexpr (Op::STEPWISE) {
+        load_a(0);
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) load_b_step(0, ks);
+        store_a();
+        __syncthreads();
+
+        auto chunk = [&](int c, auto more) {   // std::true_type: another chunk follows
+            constexpr bool MORE = decltype(more)::value;
+            if (MORE) {
+                load_a(c + 1);
+                __builtin_amdgcn_sched_barrier(kSchedPin);
+            }
+#pragma unroll
+            for (int ks = 0; ks < G::KS; ++ks) {
+#pragma unroll
+                for (int i = 0; i < G::MPW; ++i) Op::mac(acc[i], tile + aoff[i] + koff[ks], G::TILE_ELEMS, breg, ks);
+                if (MORE) {
+                    load_b_step(c + 1, ks);
+                    __builtin_amdgcn_sched_barrier(kSchedPin);
+                }
+            }
+            if (MORE) {
+                __builtin_amdgcn_sched_barrier(0);   // staging's selects and split wait for the activations: not among the MFMAs
+                __syncthreads();
+                store_a();
+                __syncthreads();
+            }
+        };
+#pragma unroll 1
+        for (int c = 0; c < G::NCH - 1; ++c) chunk(c, std::true_type{});
+        chunk(G::NCH - 1, std::false_type{});
+    } else {
+        load_b(0);
+        load_a(0);
+        store_a();
+        __syncthreads();
 
 #pragma unroll 1
-    for (int c = 0; c < G::NCH; ++c) {
-        if (c + 1 < G::NCH) load_a(c + 1);
+        for (int c = 0; c < G::NCH; ++c) {
+            if (c + 1 < G::NCH) load_a(c + 1);
 #pragma unroll
-        for (int ks = 0; ks < G::KS; ++ks) {
+            for (int ks = 0; ks < G::KS; ++ks) {
 #pragma unroll
-            for (int i = 0; i < G::MPW; ++i) Op::mac(acc[i], tile + abase[i] + koff[ks], G::TILE_ELEMS, breg, ks);
-        }
-        if (c + 1 < G::NCH) {
-            load_b(c + 1);
-            __syncthreads();
-            store_a();
-            __syncthreads();
+                for (int i = 0; i < G::MPW; ++i) Op::mac(acc[i], tile + aoff[i] + koff[ks], G::TILE_ELEMS, breg, ks);
+            }
+            if (c + 1 < G::NCH) {
+                load_b(c + 1);
+                __syncthreads();
+                store_a();
+                __syncthreads();
+            }
         }
     }
 
@@ -956,6 +1041,9 @@ struct DeconvG16 {
     static constexpr int PPT = (NPIECE + 255) / 256;
     static_assert(NTT == 1 || NTT == 2 || NTT == 4, "COUT must be 8, 16 or 32");
     static_assert(MT % MG == 0, "block tile must split evenly over the M-groups");
+    // ConvG16's: origin of M-tile t in the halo tile; whether a wave's M-tiles are its first one plus a constant
+    static constexpr int mt_off(int t) { return (((t / (BX * BY)) * HY + 2 * ((t / BX) % BY)) * HXP + 8 * (t % BX)) * VS; }
+    static constexpr bool MT_SPLITS = BX % MPW == 0 || (MPW % BX == 0 && BY % (MPW / BX) == 0) || MPW % (BX * BY) == 0;
 };
 
 template <class Op, int CIN, int COUT, int BZ, int BY, int BX>
@@ -977,7 +1065,9 @@ __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
     unsigned short* tile = reinterpret_cast<unsigned short*>(lds_raw);
     float* otile = reinterpret_cast<float*>(lds_raw);
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    // wave-uniform; with split operands also known to be: the panel's addresses stay scalar
+    const int wave = Op::STEPWISE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int nt = wave % G::NTT, mg = wave / G::NTT;
     const int nbx = (Wi + 8 * BX - 1) / (8 * BX), nby = (Hi + 2 * BY - 1) / (2 * BY);
     int b = xcd_block();   // XCD-aware order of the (z, row, column) tile sequence: tiles sharing halo planes / rows meet in one L2
@@ -1007,18 +1097,29 @@ __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
 
     const int r = lane & 15, g = lane >> 4;
     const int ry = r >> 3, rx = r & 7;
-    int abase[G::MPW];
+    int aoff[G::MPW], koff[G::KS];   // convg16_mfma_kernel's addressing: aoff[M-tile] + koff[k-step]
+    if constexpr (Op::STEPWISE) {
+        const int mt0 = G::mt_off(mg * G::MPW);
+        const int abase = mt0 + (ry * G::HXP + rx + (g & 1)) * G::VS;
 #pragma unroll
-    for (int i = 0; i < G::MPW; ++i) {
-        const int t = mg * G::MPW + i;
-        const int tx = t % BX, ty = (t / BX) % BY, tz = t / (BX * BY);
-        abase[i] = ((tz * G::HY + 2 * ty + ry) * G::HXP + 8 * tx + rx + (g & 1)) * G::VS;
-    }
-    int koff[G::KS];
+        for (int i = 0; i < G::MPW; ++i) aoff[i] = G::MT_SPLITS ? G::mt_off(i) : G::mt_off(mg * G::MPW + i) - mt0;
 #pragma unroll
-    for (int ks = 0; ks < G::KS; ++ks) {
-        const Deconv16Tap t0 = deconv16_tap(ks, 0), t1 = deconv16_tap(ks, 1);
-        koff[ks] = (g >> 1) ? (t1.dz * G::HY + t1.dy) * G::HXP * G::VS : (t0.dz * G::HY + t0.dy) * G::HXP * G::VS;
+        for (int ks = 0; ks < G::KS; ++ks) {
+            const Deconv16Tap t0 = deconv16_tap(ks, 0), t1 = deconv16_tap(ks, 1);
+            koff[ks] = abase + ((g >> 1) ? (t1.dz * G::HY + t1.dy) * G::HXP * G::VS : (t0.dz * G::HY + t0.dy) * G::HXP * G::VS);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < G::MPW; ++i) {
+            const int t = mg * G::MPW + i;
+            const int tx = t % BX, ty = (t / BX) % BY, tz = t / (BX * BY);
+            aoff[i] = ((tz * G::HY + 2 * ty + ry) * G::HXP + 8 * tx + rx + (g & 1)) * G::VS;
+        }
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) {
+            const Deconv16Tap t0 = deconv16_tap(ks, 0), t1 = deconv16_tap(ks, 1);
+            koff[ks] = (g >> 1) ? (t1.dz * G::HY + t1.dy) * G::HXP * G::VS : (t0.dz * G::HY + t0.dy) * G::HXP * G::VS;
+        }
     }
 
     f32x4 acc[4][G::MPW];
@@ -1029,12 +1130,10 @@ __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
     u32x4 breg[Op::NPC * G::KS];   // [piece][k-step]
     typename Op::Stage stg[G::PPT];
 
-    auto load_b = [&](int c) {
-        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NTT + nt) * G::KS) * 64 + lane;
+    auto load_b_step = [&](int c, int ks) {
+        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NTT + nt) * G::KS + ks) * 64 + lane;
 #pragma unroll
-        for (int q = 0; q < Op::NPC; ++q)
-#pragma unroll
-            for (int ks = 0; ks < G::KS; ++ks) breg[q * G::KS + ks] = bsrc[q * PANEL + ks * 64];
+        for (int q = 0; q < Op::NPC; ++q) breg[q * G::KS + ks] = bsrc[q * PANEL];
     };
     auto load_a = [&](int c) {
         const typename Op::T* plane = x + (size_t)c * Vin * 8;
@@ -1046,26 +1145,70 @@ __global__ __launch_bounds__(256) void deconvg16_mfma_kernel(
         for (int i = 0; i < G::PPT; ++i) stg[i].stage(tile, G::TILE_ELEMS, loff[i], (inside >> i) & 1u);
     };
 
-    load_b(0);
-    load_a(0);
-    store_a();
-    __syncthreads();
+    // chunk pipeline of convg16_mfma_kernel: activations first, the panel re-requested k-step by k-step under the MFMAs, the
+    // last chunk peeled off
+    auto load_b = [&](int c) {   // the whole panel of chunk c
+        const u32x4* bsrc = reinterpret_cast<const u32x4*>(bp) + ((size_t)(c * G::NTT + nt) * G::KS) * 64 + lane;
+#pragma unroll
+        for (int q = 0; q < Op::NPC; ++q)
+#pragma unroll
+            for (int ks = 0; ks < G::KS; ++ks) breg[q * G::KS + ks] = bsrc[q * PANEL + ks * 64];
+    };
+
+    if constexpr (Op::STEPWISE) {
+        load_a(0);
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) load_b_step(0, ks);
+        store_a();
+        __syncthreads();
+
+        auto chunk = [&](int c, auto more) {   // std::true_type: another chunk follows
+            constexpr bool MORE = decltype(more)::value;
+            if (MORE) {
+                load_a(c + 1);
+                __builtin_amdgcn_sched_barrier(kSchedPin);
+            }
+#pragma unroll
+            for (int ks = 0; ks < G::KS; ++ks) {
+                const int cls = deconv16_tap(ks, 0).cls;
+#pragma unroll
+                for (int i = 0; i < G::MPW; ++i) Op::mac(acc[cls][i], tile + aoff[i] + koff[ks], G::TILE_ELEMS, breg, ks);
+                if (MORE) {
+                    load_b_step(c + 1, ks);
+                    __builtin_amdgcn_sched_barrier(kSchedPin);
+                }
+            }
+            if (MORE) {
+                __builtin_amdgcn_sched_barrier(0);   // staging's selects and split wait for the activations: not among the MFMAs
+                __syncthreads();
+                store_a();
+                __syncthreads();
+            }
+        };
+#pragma unroll 1
+        for (int c = 0; c < G::NCH - 1; ++c) chunk(c, std::true_type{});
+        chunk(G::NCH - 1, std::false_type{});
+    } else {
+        load_b(0);
+        load_a(0);
+        store_a();
+        __syncthreads();
 
 #pragma unroll 1
-    for (int c = 0; c < G::NCH; ++c) {
-        if (c + 1 < G::NCH) load_a(c + 1);
+        for (int c = 0; c < G::NCH; ++c) {
+            if (c + 1 < G::NCH) load_a(c + 1);
 #pragma unroll
-        for (int ks = 0; ks < G::KS; ++ks) {
-            const int cls = deconv16_tap(ks, 0).cls;
+            for (int ks = 0; ks < G::KS; ++ks) {
+                const int cls = deconv16_tap(ks, 0).cls;
 #pragma unroll
-            for (int i = 0; i < G::MPW; ++i)
-                Op::mac(acc[cls][i], tile + abase[i] + koff[ks], G::TILE_ELEMS, breg, ks);
-        }
-        if (c + 1 < G::NCH) {
-            load_b(c + 1);
-            __syncthreads();
-            store_a();
-            __syncthreads();
+                for (int i = 0; i < G::MPW; ++i) Op::mac(acc[cls][i], tile + aoff[i] + koff[ks], G::TILE_ELEMS, breg, ks);
+            }
+            if (c + 1 < G::NCH) {
+                load_b(c + 1);
+                __syncthreads();
+                store_a();
+                __syncthreads();
+            }
         }
     }
 
