@@ -21,6 +21,15 @@
  *  - Volumes between stages use a PRIVATE "C8-planar" layout: a C-channel volume is C/8 planes,
  *    each a channels-last volume of 8 channels, [C/8][D][h][w][8].  Only the documented
  *    inputs/outputs below have reference layouts.
+ *  - Shape domain: every device entry point states the admitted range of each integer argument and which pointers may
+ *    be NULL.  Outside it the call returns MVS_ERR_NULL (a required pointer is NULL), MVS_ERR_BAD_SHAPE,
+ *    MVS_ERR_BAD_DTYPE or MVS_ERR_WORKSPACE, decided on the host from the arguments alone: nothing is enqueued on a
+ *    refusal and no HIP call is made.  The upper ends come from the index types of the kernel forms an entry point can
+ *    select, whichever MVS_* switch is set; they are derived, and beyond the largest shapes the tests run
+ *    (D*h*w*32 < 2^32 volumes at 512 x 640) not measured: a HIP runtime that declines a grid of that many blocks
+ *    returns MVS_ERR_HIP for such a shape, it is never served wrongly.  "The volume domain" below is the one
+ *    mvs_query_workspace checks: N in [1,64], C = 32, D, h, w positive multiples of 8, D*h*w*32 < 2^32, dtype an
+ *    mvs_dtype.
  */
 #ifndef MVS_ABI_H
 #define MVS_ABI_H
@@ -78,7 +87,9 @@ const char* mvs_last_error_string(void);
 
 /* Bytes of device workspace needed by mvs_depth_infer / mvs_warp_variance / mvs_costreg_forward
  * for a [N views, C, D, h, w] problem.  Replaces nothing in the reference (torch allocates its
- * intermediates implicitly at models/mvsnet.py:145-180). */
+ * intermediates implicitly at models/mvsnet.py:145-180).
+ * Domain: the volume domain (N in [1,64], C = 32, D,h,w positive multiples of 8, D*h*w*32 < 2^32; dtype 0..2 else
+ * MVS_ERR_BAD_DTYPE); bytes must not be NULL.  Host only: no device work. */
 int mvs_query_workspace(int N, int C, int D, int h, int w, int dtype, size_t* bytes);
 
 /* Bytes of the packed weight blob produced by mvs_pack_weights. */
@@ -92,13 +103,16 @@ int mvs_query_weights_blob(size_t* bytes);
  *   bn_params[4*l+{0,1,2,3}] = gamma, beta, running_mean, running_var of layer l (l in 0..9)
  *   prob_bias        host fp32 [1]          (cost_regularization.prob.bias)
  *   blob_out         host buffer of mvs_query_weights_blob() bytes; copy it to the device
- *                    and pass that device pointer as `weights_blob` below. */
+ *                    and pass that device pointer as `weights_blob` below.
+ * Domain: no pointer may be NULL, nor any of conv_weights[0..10] and bn_params[0..39] (MVS_ERR_NULL); blob_bytes >=
+ * mvs_query_weights_blob (MVS_ERR_WORKSPACE).  Host only. */
 int mvs_pack_weights(const float* const* conv_weights, const float* const* bn_params,
                      const float* prob_bias, float eps, void* blob_out, size_t blob_bytes);
 
 /* rt_out[(v-1)*12 .. +12] = rows 0..2 of proj[v] @ inverse(proj[0]) as rot (9, row-major) then
  * trans (3), for v = 1..N-1.   Replaces torch.inverse/matmul at models/module.py:107-109.
- *   proj   dev fp32 [N][4][4]      rt_out dev fp32 [(N-1)][12] */
+ *   proj   dev fp32 [N][4][4]      rt_out dev fp32 [(N-1)][12]
+ * Domain: N in [1,64]; neither pointer may be NULL.  N = 1 enqueues nothing and leaves rt_out untouched. */
 int mvs_relative_proj(const float* proj, float* rt_out, int N, void* stream);
 
 /* Fused homography warp + variance cost volume.
@@ -107,7 +121,9 @@ int mvs_relative_proj(const float* proj, float* rt_out, int N, void* stream);
  *   rt            dev fp32 [(N-1)][12]    (from mvs_relative_proj)
  *   depth_values  dev fp32 [D]
  *   var_out       dev, C8-planar [4][D][h][w][8] in `dtype`; must not alias the workspace
- *   workspace     dev, >= mvs_query_workspace bytes (uses the feature-transpose region only) */
+ *   workspace     dev, >= mvs_query_workspace bytes (uses the feature-transpose region only)
+ * Domain: the volume domain.  rt may be NULL when N = 1; no other pointer may.  A workspace smaller than the
+ * feature-transpose region or not 256-byte aligned is MVS_ERR_WORKSPACE.  Nothing is enqueued on a refusal. */
 int mvs_warp_variance(const float* feats, const float* rt, const float* depth_values,
                       void* var_out, void* workspace, size_t workspace_bytes, int N, int C, int D,
                       int h, int w, int dtype, void* stream);
@@ -120,7 +136,9 @@ int mvs_warp_variance(const float* feats, const float* rt, const float* depth_va
  *   them as F.relu and conv3d do.  A logit is non-finite wherever the reference's is (NaN where it is NaN; NaN or the
  *   infinity where it is +-inf: the split-operand and zero-padded forms turn inf into inf - inf or inf * 0); every finite
  *   logit keeps its bound; non-finite logits outside the reference's set stay within the kernel forms' tile geometry
- *   (Winograd along z: the rest of the 4- or 2-plane output tile; Toeplitz-pair and transposed forms: one voxel in x). */
+ *   (Winograd along z: the rest of the 4- or 2-plane output tile; Toeplitz-pair and transposed forms: one voxel in x).
+ * Domain: the volume domain with N = 1, C = 32; no pointer may be NULL; workspace >= mvs_query_workspace(1, 32, D, h, w,
+ * dtype) bytes and 256-byte aligned, else MVS_ERR_WORKSPACE.  Nothing is enqueued on a refusal. */
 int mvs_costreg_forward(const void* var, const void* weights_blob, float* cost_out,
                         void* workspace, size_t workspace_bytes, int D, int h, int w, int dtype,
                         void* stream);
@@ -132,7 +150,14 @@ int mvs_costreg_forward(const void* var, const void* weights_blob, float* cost_o
  *   x     dev [Cin/8][Di][Hi][Wi][8]    skip  dev [Cout/8][Do][Ho][Wo][8] or NULL (layers 7..9
  *   y     dev [Cout/8][Do][Ho][Wo][8]   need it)              (layer 10: y is fp32 [D][h][w])
  * NaN and infinity in x or skip: as stated at mvs_costreg_forward, per layer (the ReLU keeps NaN; a 16-bit store keeps
- *   NaN and infinity). */
+ *   NaN and infinity).
+ * Domain: layer in [0,10]; dtype 0..2 (MVS_FORCE_DIRECT=1: MVS_F32 only), else MVS_ERR_BAD_DTYPE; Di, Hi, Wi >= 1, all
+ * three even at the stride-2 layers 1, 3, 5, and Di*Hi*Wi < 2^28 (every kernel form addresses one 8-channel plane of
+ * its input with 31-bit element offsets; planes and outputs are 64-bit), at layer 10 also (5 Hi + 9) Wi + 33 < 2^28
+ * (the prob kernel holds a piece's offset from its tile's halo origin, up to 5 planes and 9 rows on, in 31 bits: it
+ * bites only below D = 5 or within a row of the first bound), else MVS_ERR_BAD_SHAPE.  Any such volume is served, down
+ * to 1 x 1 x 1: the tile forms pad.  skip may be NULL at layers 0..6 and 10 (it is not read); x, y,
+ * weights_blob and, at layers 7..9, skip may not.  Nothing is enqueued on a refusal. */
 int mvs_conv_layer(int layer, const void* x, const void* skip, void* y, const void* weights_blob,
                    int Di, int Hi, int Wi, int dtype, void* stream);
 
@@ -144,7 +169,9 @@ int mvs_conv_layer(int layer, const void* x, const void* skip, void* y, const vo
  *   x     dev [2][Di][Hi][Wi][8]  (output of layer 8)     skip  dev [1][2Di][2Hi][2Wi][8]  (output of layer 0)
  *   cost_out  dev fp32 [2Di][2Hi][2Wi]
  * NaN and infinity in x or skip: as stated at mvs_costreg_forward (a non-finite skip voxel reaches its 27 logits, a
- *   non-finite x voxel the logits of its transposed footprint and one more voxel in x). */
+ *   non-finite x voxel the logits of its transposed footprint and one more voxel in x).
+ * Domain: Di, Hi, Wi >= 1 and Di*Hi*Wi*64 < 2^31 (31-bit element offsets into the full-resolution skip plane), else
+ * MVS_ERR_BAD_SHAPE; dtype 0..2; no pointer may be NULL.  Nothing is enqueued on a refusal. */
 int mvs_conv11_prob(const void* x, const void* skip, float* cost_out, const void* weights_blob,
                     int Di, int Hi, int Wi, int dtype, void* stream);
 
@@ -153,13 +180,18 @@ int mvs_conv11_prob(const void* x, const void* skip, float* cost_out, const void
  *   cost dev fp32 [D][h][w]; depth_out, conf_out dev fp32 [h][w]
  * A pixel's depth and confidence are NaN exactly where softmax-then-sum is: a NaN or +inf logit, or -inf logits only
  *   (the reference's trunc of the NaN expectation picks some window of an all-NaN row: NaN whichever).  A -inf logit
- *   among finite ones is a term of exactly 0; other pixels of the block are untouched. */
+ *   among finite ones is a term of exactly 0; other pixels of the block are untouched.
+ * Domain: D in [1, 2^24] (the expected depth index is an fp32 sum of p_d * d: exact integers end there), h, w >= 1 and
+ * h*w <= 2^31 - 256 (the pixel index of the last, partly filled block is an int), else MVS_ERR_BAD_SHAPE; no pointer
+ * may be NULL.  D = 1 yields depth = depth_values[0] and confidence 1.  Nothing is enqueued on a refusal. */
 int mvs_softargmin_conf(const float* cost, const float* depth_values, float* depth_out,
                         float* conf_out, int D, int h, int w, void* stream);
 
 /* mvs_relative_proj -> mvs_warp_variance -> mvs_costreg_forward -> mvs_softargmin_conf for one
  * batch item.  Replaces models/mvsnet.py:145-218 after FeatureNet.
- *   proj dev fp32 [N][4][4]; other arguments as above. */
+ *   proj dev fp32 [N][4][4]; other arguments as above.
+ * Domain: the volume domain; no pointer may be NULL; workspace >= mvs_query_workspace(N, C, D, h, w, dtype) bytes and
+ * 256-byte aligned, else MVS_ERR_WORKSPACE.  Nothing is enqueued on a refusal. */
 int mvs_depth_infer(const float* feats, const float* proj, const float* depth_values,
                     const void* weights_blob, float* depth_out, float* conf_out, void* workspace,
                     size_t workspace_bytes, int N, int C, int D, int h, int w, int dtype,
@@ -175,7 +207,7 @@ int mvs_depth_infer(const float* feats, const float* proj, const float* depth_va
  *   proj      dev fp32 [N][4][4] in view_idx order; other arguments as mvs_depth_infer
  *             (workspace of mvs_query_workspace(N, ...) bytes).
  * An index outside [0, V) or V < 1 returns MVS_ERR_BAD_SHAPE, a NULL view_idx MVS_ERR_NULL; nothing
- * is enqueued then. */
+ * is enqueued then.  Otherwise the domain, pointers and workspace of mvs_depth_infer. */
 int mvs_depth_infer_views(const float* feats, int V, const int* view_idx, const float* proj,
                           const float* depth_values, const void* weights_blob, float* depth_out,
                           float* conf_out, void* workspace, size_t workspace_bytes, int N, int C,
@@ -185,7 +217,12 @@ int mvs_depth_infer_views(const float* feats, int V, const int* view_idx, const 
  * mvs_homo_warp: src_fea dev fp32 [C][h][w], rt dev fp32 [12] -> out dev fp32 [C][D][h][w]
  *   (models/module.py:96-139 for one batch item).
  * mvs_depth_regression: p dev fp32 [D][h][w] -> depth dev fp32 [h][w] = sum_d p*depth_values
- *   (models/module.py:144-147). */
+ *   (models/module.py:144-147).
+ * Domain, mvs_homo_warp: C, D >= 1; h, w >= 2 (the reference's grid normalisation divides by h - 1 and w - 1);
+ *   h*w < 2^31 (int texel offsets), D*h*w <= (2^31 - 2) * 256 (one thread per output voxel of a channel, fewer than
+ *   2^31 blocks of 256) and C*D*h*w <= 2^61 (64-bit byte offsets), else MVS_ERR_BAD_SHAPE.
+ * Domain, mvs_depth_regression: D, h, w >= 1 and h*w <= 2^31 - 256 (int pixel index), else MVS_ERR_BAD_SHAPE.
+ * Neither takes a NULL pointer; nothing is enqueued on a refusal. */
 int mvs_homo_warp(const float* src_fea, const float* rt, const float* depth_values, float* out,
                   int C, int D, int h, int w, void* stream);
 int mvs_depth_regression(const float* p, const float* depth_values, float* depth_out, int D,
@@ -245,7 +282,16 @@ int mvs_filter_depth(const float* depth, const float* conf, const float* ref_mat
  *   weight of exactly 0, which turns an infinite activation into NaN where the reference keeps the infinity.
  * mvs_forward_images: FeatureNet + mvs_depth_infer with the features handed over in the private
  *   C8-planar layout (no NCHW round trip); H, W multiples of 32; workspace of
- *   mvs_query_forward_workspace(N,H,W,D,dtype) bytes. */
+ *   mvs_query_forward_workspace(N,H,W,D,dtype) bytes.
+ * Domain of the image calls (mvs_query_feature_workspace, mvs_feature_layer, mvs_feature_conv01_fmt, mvs_feature_net,
+ *   mvs_feature_net_fmt): N in [1,65535] (the image index is a grid dimension), H, W >= 4 (Hi, Wi of mvs_feature_layer
+ *   likewise: the dims of that layer's INPUT), N*H*W*8 < 2^31 (31-bit offsets into the 8-channel full-resolution
+ *   activation), else MVS_ERR_BAD_SHAPE; feature layer in [0,7]; image_format 0..2 else MVS_ERR_BAD_DTYPE; odd H, W are
+ *   served (the stride-2 layers yield (H - 1) / 2 + 1).  mvs_query_forward_workspace, mvs_forward_images and
+ *   mvs_forward_images_fmt: both that domain and the volume domain at h = H / 4, w = W / 4, so H, W are positive
+ *   multiples of 32.  No pointer of any of them may be NULL (the packers: nor conv_weights[0..7], bn_params[0..27]);
+ *   a workspace (blob) smaller than its query or not 256-byte aligned is MVS_ERR_WORKSPACE.  Nothing is enqueued on a
+ *   refusal. */
 #define MVS_FEATURE_LAYERS 8
 int mvs_query_feature_blob(size_t* bytes);
 int mvs_pack_feature_weights(const float* const* conv_weights, const float* const* bn_params,
@@ -305,7 +351,9 @@ int mvs_depth_metrics(const float* depth_est, const float* depth_gt, const float
  * mvs_softargmin_backward: grad_cost[d][p] = grad_depth[p] * p_d * (depth_values[d] - depth[p]), with the softmax
  *   p and the depth recomputed from the logits in mvs_softargmin_conf's max-subtracted form.
  *     cost dev fp32 [D][h][w]; grad_depth dev fp32 [h][w]; grad_cost dev fp32 [D][h][w] (written, no atomics)
- *   D, h, w >= 1 and h*w < 2^31, else MVS_ERR_BAD_SHAPE.
+ *   mvs_softargmin_conf's domain: D in [1, 2^24], h, w >= 1 and h*w <= 2^31 - 256, else MVS_ERR_BAD_SHAPE (narrowed from
+ *   "any D, h*w < 2^31": the launcher's rounded-up int grid wrapped in the last 127 pixels of that range, and the
+ *   backward accepts what its forward does).
  * Neither allocates, needs a workspace or synchronises. */
 int mvs_warp_variance_backward(const float* feats, const float* rt, const float* depth_values, const float* grad_var,
                                float* grad_feats, int N, int C, int D, int h, int w, void* stream);

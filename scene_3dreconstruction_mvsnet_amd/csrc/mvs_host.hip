@@ -29,6 +29,9 @@ int check_hip(hipError_t e, const char* what) {
     return fail(MVS_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 
+// a * b * c > limit for positive ints, without the 64-bit wrap of the plain product (2^30 cubed is 0 mod 2^64)
+static bool product_exceeds(int a, int b, int c, size_t limit) { return (size_t)a * b > limit / (size_t)c; }
+
 static int check_dims(int N, int C, int D, int h, int w, int dtype) {
     if (dtype != MVS_F32 && dtype != MVS_F16 && dtype != MVS_BF16)
         return fail(MVS_ERR_BAD_DTYPE, "unknown dtype %d", dtype);
@@ -38,9 +41,8 @@ static int check_dims(int N, int C, int D, int h, int w, int dtype) {
         return fail(MVS_ERR_BAD_SHAPE,
                     "D,h,w = %d,%d,%d must be positive multiples of 8 (three stride-2 stages with "
                     "additive skips, models/mvsnet.py:38-60,69-71)", D, h, w);
-    if ((size_t)D * h * w * kC >= ((size_t)1 << 32))
-        return fail(MVS_ERR_BAD_SHAPE, "volume of %zu elements exceeds 32-bit indexing",
-                    (size_t)D * h * w * kC);
+    if (product_exceeds(D, h, w, (((size_t)1 << 32) - 1) / kC))
+        return fail(MVS_ERR_BAD_SHAPE, "volume of %d x %d x %d x %d elements exceeds 32-bit indexing", D, h, w, kC);
     return MVS_OK;
 }
 
@@ -283,6 +285,11 @@ int mvs_conv_layer(int layer, const void* x, const void* skip, void* y, const vo
     if (S.kind == kDeconv && !skip) return fail(MVS_ERR_NULL, "layer %d needs its skip tensor", layer);
     if (Di < 1 || Hi < 1 || Wi < 1 || (S.stride == 2 && S.kind == kConv && ((Di | Hi | Wi) & 1)))
         return fail(MVS_ERR_BAD_SHAPE, "layer %d: input dims %d,%d,%d unsupported", layer, Di, Hi, Wi);
+    if (product_exceeds(Di, Hi, Wi, kMaxConvInputVoxels))
+        return fail(MVS_ERR_BAD_SHAPE, "layer %d: input plane of %d,%d,%d exceeds 31-bit offsets", layer, Di, Hi, Wi);
+    if (layer == 10 && (5 * (size_t)Hi + 9) * (size_t)Wi + 33 > kMaxProbHaloVoxels)   // Hi*Wi < 2^28 here: no wrap
+        return fail(MVS_ERR_BAD_SHAPE, "layer 10: plane of %d,%d exceeds the 31-bit halo offsets of the prob kernel "
+                    "((5 Hi + 9) Wi + 33 < 2^28)", Hi, Wi);
     return launch_conv_layer(layer, x, skip, y, static_cast<const float*>(weights_blob), Di, Hi, Wi,
                              dtype, static_cast<hipStream_t>(stream));
 }
@@ -292,7 +299,8 @@ int mvs_conv11_prob(const void* x, const void* skip, float* cost_out, const void
     if (!x || !skip || !cost_out || !weights_blob) return fail(MVS_ERR_NULL, "mvs_conv11_prob: NULL argument");
     if (dtype != MVS_F32 && dtype != MVS_F16 && dtype != MVS_BF16)
         return fail(MVS_ERR_BAD_DTYPE, "mvs_conv11_prob: unknown dtype %d", dtype);
-    if (Di < 1 || Hi < 1 || Wi < 1) return fail(MVS_ERR_BAD_SHAPE, "mvs_conv11_prob: input dims %d,%d,%d", Di, Hi, Wi);
+    if (Di < 1 || Hi < 1 || Wi < 1 || product_exceeds(Di, Hi, Wi, (((size_t)1 << 31) - 1) / 64))
+        return fail(MVS_ERR_BAD_SHAPE, "mvs_conv11_prob: input dims %d,%d,%d outside Di*Hi*Wi*64 in [64, 2^31)", Di, Hi, Wi);
     return launch_conv11_prob(x, skip, cost_out, static_cast<const float*>(weights_blob), Di, Hi, Wi, dtype,
                               static_cast<hipStream_t>(stream));
 }
@@ -301,7 +309,9 @@ int mvs_softargmin_conf(const float* cost, const float* depth_values, float* dep
                         float* conf_out, int D, int h, int w, void* stream) {
     if (!cost || !depth_values || !depth_out || !conf_out)
         return fail(MVS_ERR_NULL, "mvs_softargmin_conf: NULL argument");
-    if (D < 1 || h < 1 || w < 1) return fail(MVS_ERR_BAD_SHAPE, "D,h,w = %d,%d,%d", D, h, w);
+    if (D < 1 || h < 1 || w < 1 || D > kMaxSoftargminD || (size_t)h * w > kMaxPixels)
+        return fail(MVS_ERR_BAD_SHAPE, "mvs_softargmin_conf: D,h,w = %d,%d,%d outside D in [1,2^24], h*w in [1,2^31-256]",
+                    D, h, w);
     return launch_softargmin(cost, depth_values, depth_out, conf_out, D, h, w,
                              static_cast<hipStream_t>(stream));
 }
@@ -323,8 +333,9 @@ int mvs_softargmin_backward(const float* cost, const float* depth_values, const 
                             float* grad_cost, int D, int h, int w, void* stream) {
     if (!cost || !depth_values || !grad_depth || !grad_cost)
         return fail(MVS_ERR_NULL, "mvs_softargmin_backward: NULL argument");
-    if (D < 1 || h < 1 || w < 1 || (size_t)h * w >= ((size_t)1 << 31))
-        return fail(MVS_ERR_BAD_SHAPE, "mvs_softargmin_backward: D,h,w = %d,%d,%d", D, h, w);
+    if (D < 1 || h < 1 || w < 1 || D > kMaxSoftargminD || (size_t)h * w > kMaxPixels)   // the forward's domain
+        return fail(MVS_ERR_BAD_SHAPE,
+                    "mvs_softargmin_backward: D,h,w = %d,%d,%d outside D in [1,2^24], h*w in [1,2^31-256]", D, h, w);
     return launch_softargmin_backward(cost, depth_values, grad_depth, grad_cost, D, h, w,
                                       static_cast<hipStream_t>(stream));
 }
@@ -446,8 +457,8 @@ int mvs_pack_feature_weights(const float* const* conv_weights, const float* cons
 static int check_image_dims(int N, int H, int W) {
     if (N < 1 || N > 65535) return fail(MVS_ERR_BAD_SHAPE, "number of images N=%d outside [1,65535]", N);
     if (H < 4 || W < 4) return fail(MVS_ERR_BAD_SHAPE, "image H,W = %d,%d must be >= 4", H, W);
-    if ((size_t)N * H * W * 8 >= ((size_t)1 << 31))
-        return fail(MVS_ERR_BAD_SHAPE, "N*H*W = %zu exceeds 31-bit offsets", (size_t)N * H * W);
+    if (product_exceeds(N, H, W, (((size_t)1 << 31) - 1) / 8))
+        return fail(MVS_ERR_BAD_SHAPE, "N*H*W = %d*%d*%d exceeds 31-bit offsets", N, H, W);
     return MVS_OK;
 }
 
@@ -506,7 +517,7 @@ int mvs_feature_net_fmt(const void* imgs, int image_format, const void* feature_
 
 int mvs_query_forward_workspace(int N, int H, int W, int D, int dtype, size_t* bytes) {
     if (!bytes) return fail(MVS_ERR_NULL, "bytes is NULL");
-    if (H % 4 || W % 4) return fail(MVS_ERR_BAD_SHAPE, "image H,W = %d,%d must be multiples of 32", H, W);
+    if (H % 32 || W % 32) return fail(MVS_ERR_BAD_SHAPE, "image H,W = %d,%d must be multiples of 32", H, W);
     if (int st = check_dims(N, kC, D, H / 4, W / 4, dtype)) return st;
     if (int st = check_image_dims(N, H, W)) return st;
     *bytes = workspace_layout(N, kC, D, H / 4, W / 4, dtype).total + feat_workspace_layout(N, H, W).total;
@@ -530,7 +541,7 @@ int mvs_forward_images_fmt(const void* imgs, int image_format, const float* proj
     if (!imgs || !proj || !depth_values || !feature_blob || !weights_blob || !depth_out || !conf_out ||
         !workspace)
         return fail(MVS_ERR_NULL, "mvs_forward_images: NULL argument");
-    if (H % 4 || W % 4) return fail(MVS_ERR_BAD_SHAPE, "image H,W = %d,%d must be multiples of 32", H, W);
+    if (H % 32 || W % 32) return fail(MVS_ERR_BAD_SHAPE, "image H,W = %d,%d must be multiples of 32", H, W);
     const int h = H / 4, w = W / 4;
     if (int st = check_dims(N, kC, D, h, w, dtype)) return st;
     if (int st = check_image_dims(N, H, W)) return st;
@@ -563,13 +574,20 @@ int mvs_homo_warp(const float* src_fea, const float* rt, const float* depth_valu
                   int C, int D, int h, int w, void* stream) {
     if (!src_fea || !rt || !depth_values || !out) return fail(MVS_ERR_NULL, "mvs_homo_warp: NULL argument");
     if (C < 1 || D < 1 || h < 2 || w < 2) return fail(MVS_ERR_BAD_SHAPE, "C,D,h,w = %d,%d,%d,%d", C, D, h, w);
+    // int texel offsets inside one h*w map; one thread per (d, y, x) in a grid of fewer than 2^31 blocks of 256; size_t
+    // offsets into the [C][D][h][w] output
+    const size_t hw = (size_t)h * w;
+    if (hw >= ((size_t)1 << 31) || hw * D > kMaxHomoWarpThreads || hw * D > kMaxHomoWarpOutput / C)
+        return fail(MVS_ERR_BAD_SHAPE, "mvs_homo_warp: C,D,h,w = %d,%d,%d,%d: h*w >= 2^31, D*h*w > 2^39-512 or "
+                    "C*D*h*w > 2^61", C, D, h, w);
     return launch_homo_warp(src_fea, rt, depth_values, out, C, D, h, w, static_cast<hipStream_t>(stream));
 }
 
 int mvs_depth_regression(const float* p, const float* depth_values, float* depth_out, int D,
                          int h, int w, void* stream) {
     if (!p || !depth_values || !depth_out) return fail(MVS_ERR_NULL, "mvs_depth_regression: NULL argument");
-    if (D < 1 || h < 1 || w < 1) return fail(MVS_ERR_BAD_SHAPE, "D,h,w = %d,%d,%d", D, h, w);
+    if (D < 1 || h < 1 || w < 1 || (size_t)h * w > kMaxPixels)
+        return fail(MVS_ERR_BAD_SHAPE, "mvs_depth_regression: D,h,w = %d,%d,%d outside D >= 1, h*w in [1,2^31-256]", D, h, w);
     return launch_depth_regression(p, depth_values, depth_out, D, h, w, static_cast<hipStream_t>(stream));
 }
 

@@ -220,6 +220,22 @@ __host__ __device__ constexpr Deconv16Tap deconv16_tap(int ks, int q) {
                    : (q == 0 ? Deconv16Tap{3, 0, 1, 2, 0, 1} : Deconv16Tap{3, 0, 1, 0, 1, 1});
 }
 
+// Upper ends of the shape domain (include/mvs_abi.h states them per entry point), from the kernels' index types:
+//  - the per-pixel ops (soft-argmin, depth regression, the soft-argmin backward) hold h*w and the pixel index of the
+//    last, partly filled block in an int: h*w + 255 (the largest block of the three) must not wrap
+//  - the soft-argmin's depth index travels as a float (sum_d p_d * d, then trunc): exact up to 2^24
+//  - every CostRegNet kernel form addresses one 8-channel plane of its INPUT with int offsets ("plane exceeds 31-bit
+//    offsets" in the MFMA launchers); planes are told apart and outputs addressed with size_t
+constexpr size_t kMaxPixels = ((size_t)1 << 31) - 256;
+constexpr int kMaxSoftargminD = 1 << 24;
+constexpr size_t kMaxConvInputVoxels = ((size_t)1 << 28) - 1;   // Di*Hi*Wi*8 < 2^31
+//  - prob_lds (layer 10) keeps a piece's offset from its tile's halo origin in an int: up to 5 planes, 9 rows and 33
+//    voxels on, whatever D and H are: ((5 Hi + 9) Wi + 33) * 8 + 4 < 2^31
+constexpr size_t kMaxProbHaloVoxels = ((size_t)1 << 28) - 1;
+//  - mvs_homo_warp: one thread per (d, y, x), 256 to a block, fewer than 2^31 blocks; element offsets are size_t
+constexpr size_t kMaxHomoWarpThreads = (((size_t)1 << 31) - 2) * 256;
+constexpr size_t kMaxHomoWarpOutput = (size_t)1 << 61;
+
 // thread-local error text
 int fail(int code, const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);

@@ -2,6 +2,9 @@
 """Child-process helper: single-product probes and the dense fp64 bound (tests/probes.py) for every CostRegNet layer
 and the fused conv11_prob tail, under ONE kernel-selection environment (read once per process by options() in
 mvs_host.hip).  Usage: probe_check.py <case>; the parent (test_gpu_conv_probes.py) sets CASES[case]["env"].
+After the probes, the smallest volumes the ABI admits (TINY_* below, keys "<layer>:tiny:<storage>": one figure per
+environment and layer -- at these shapes several environments fall back to the generic tile kernels (persist below four
+tiles per block, convz16 below 4 output planes, conv0z16 below D = 8), which the launchers decide, not this file).
 Prints one JSON line with the measured max ratios (got - want over the bound, per layer / set / storage) and exits
 non-zero after listing every violated bound.
 
@@ -35,6 +38,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
+import guarded as G  # noqa: E402
 import probes as P  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 from scene_3dreconstruction_mvsnet_amd import _lib, synthetic  # noqa: E402
@@ -138,6 +142,25 @@ KERNELS = {
     "conv11_prob_priv_kernel": "tail_split0",
     "conv11_prob16_kernel": "default16",
 }
+
+
+# The smallest volumes mvs_conv_layer / mvs_conv11_prob admit (include/mvs_abi.h: Di, Hi, Wi >= 1, even at the stride-2
+# layers): no tile of any form is filled in any dimension -- one voxel, one row along each axis, odd D through the
+# two-plane F(2,3) tiles, D below the z-marching pipelines' depth, D % 4 != 0 at conv0 (conv0_mfma instead of the
+# F(4,3) forms) and its smallest D % 4 == 0.  Dense standard-normal input against the dense bound of the form the
+# dispatch takes, every launch in a guarded arena under the three poisons (tests/guarded.py).
+TINY_S1 = ((1, 1, 1), (3, 1, 1), (1, 3, 1), (1, 1, 3), (5, 2, 9))
+TINY_S2 = ((2, 2, 2), (6, 2, 2), (2, 6, 2), (2, 2, 6), (4, 2, 10))
+TINY_CONV0 = ((4, 1, 1), (8, 1, 1), (5, 1, 1))
+TINY_TAIL = ((1, 1, 1), (3, 1, 1), (1, 3, 1), (1, 1, 3), (2, 3, 5))
+TINY_TAIL_CASES = ("default", "tail_split0", "default16")
+ARENA_BYTES = 32 << 20
+
+
+def tiny_shapes(layer):
+    if layer == "tail":
+        return TINY_TAIL
+    return (TINY_S2 if P.GEOM[layer][2] == 2 and not P.GEOM[layer][3] else TINY_S1) + (TINY_CONV0 if layer == 0 else ())
 
 
 def cu(a):
@@ -261,6 +284,68 @@ def probe_tail(chk, storage, sd, blobs_crafted, rng):
         chk.add(f"tail:dense:{storage}", np.abs(got - want), P.DENSE_C * P.U * S)
 
 
+def tiny_out_shape(layer, shape):
+    _, co, s, tr, _ = P.GEOM[layer]
+    return (co,) + tuple(2 * n if tr else (n - 1) // s + 1 for n in shape)
+
+
+def guarded_call(arena, fn, oshape):
+    """fn(A) -> one output tensor carved from A; the output as float64 numpy [C, D, H, W] ([D, H, W] for logits)"""
+    code_out = {}
+
+    def run(A):
+        y = fn(A)
+        code_out["dtype"], code_out["shape"] = y.dtype, tuple(y.shape)
+        return y
+    (raw,), _ = G.same_under_all_poisons(arena, run)
+    y = raw.view(code_out["dtype"]).view(code_out["shape"]).float()
+    y = _lib.from_c8(y) if y.dim() == 5 else y
+    assert tuple(y.shape) == tuple(oshape), (tuple(y.shape), oshape)
+    return y.numpy().astype(np.float64)
+
+
+def probe_tiny(chk, arena, layer, storage, sd, blob, wino, rng):
+    code = _lib.dtype_code(storage)
+    tdt = _lib.TORCH_DTYPES[code]
+    if layer == "tail":
+        q = lambda t: orc.round_storage(np.asarray(t, np.float32), storage)  # noqa: E731
+        w9, sh9 = P.folded(sd, 9)
+        wq = w9 if storage == "f32" else q(w9)
+        for D, H, W in TINY_TAIL:
+            x = q(rng.standard_normal((16, D, H, W)).astype(np.float32))
+            skip = q(rng.standard_normal((8, 2 * D, 2 * H, 2 * W)).astype(np.float32))
+
+            def run(A):
+                xt, st = A.put(_lib.to_c8(cu(x)).to(tdt), "in", "x"), A.put(_lib.to_c8(cu(skip)).to(tdt), "in", "skip")
+                b = A.put(blob, "in", "blob")
+                with A.intercept(_lib):
+                    return _lib.conv11_prob(xt, st, b, dtype=code)
+            got = guarded_call(arena, run, (2 * D, 2 * H, 2 * W))
+            want, S = P.tail64(x, skip, wq, sh9, sd["prob.weight"], sd["prob.bias"])
+            chk.add(f"tail:tiny:{storage}", np.abs(got - want), P.DENSE_C * P.U * S)
+        return
+    ci, _, _, tr, _ = P.GEOM[layer]
+    wf, sh = P.folded(sd, layer)
+    for shape in tiny_shapes(layer):
+        oshape = tiny_out_shape(layer, shape)
+        x = rng.standard_normal((ci,) + shape).astype(np.float32)
+        skip = rng.standard_normal(oshape).astype(np.float32) if tr else None
+
+        def run(A):
+            xt = A.put(_lib.to_c8(cu(x)).to(tdt), "in", "x")
+            st = None if skip is None else A.put(_lib.to_c8(cu(skip)).to(tdt), "in", "skip")
+            b = A.put(blob, "in", "blob")
+            with A.intercept(_lib):
+                return _lib.conv_layer(layer, xt, st, b, dtype=code)
+        got = guarded_call(arena, run, oshape[1:] if layer == 10 else oshape)
+        # conv0's F(4,3) forms need D % 4 == 0: any other D runs conv0_mfma and is held to the direct forms' bound
+        form = None if layer == 0 and shape[0] % 4 else wino
+        ref, bound = P.dense_ref_bound(layer, x, skip, wf, sh, storage, form)
+        if layer == 10:
+            ref, bound = ref[0], bound[0]
+        chk.add(f"{layer}:tiny:{storage}", np.abs(got - ref), bound)
+
+
 class CraftedBlobs(dict):
     """run -> (crafted state, packed blob on the GPU), packed on first use; "rand" -> the random state's blob."""
 
@@ -282,6 +367,7 @@ def main():
     sd = synthetic.random_costreg_state(seed=13)
     blobs = CraftedBlobs(sd)
     chk = Checker(name)
+    arena = G.Arena(ARENA_BYTES, DEV)
     for storage in case["storages"]:
         rng = np.random.default_rng(17)
         for layer in case["layers"]:
@@ -289,6 +375,10 @@ def main():
                 probe_tail(chk, storage, sd, blobs, rng)
             else:
                 probe_layer(chk, layer, storage, sd, blobs, case["wino"].get(layer), rng)
+        trng = np.random.default_rng(29)     # a stream of their own: the probes above keep their inputs
+        for layer in case["layers"]:
+            if layer != "tail" or name in TINY_TAIL_CASES:
+                probe_tiny(chk, arena, layer, storage, sd, blobs["rand"], case["wino"].get(layer), trng)
     print(json.dumps({"case": name, "ratios": {k: round(v, 4) for k, v in chk.ratios.items()},
                       "inexact16": chk.inexact}))
     for f in chk.failures:

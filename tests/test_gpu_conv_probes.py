@@ -1,7 +1,9 @@
 """Single-product probes and the dense fp64 bound (tests/probes.py) for every conv kernel form of CostRegNet, one
 child process per kernel-selection environment (tests/probe_check.py: the environment -> kernel map and the case
 table).  The bounds are about 1000x tighter than the per-layer oracle comparisons of test_gpu_parity.py /
-test_gpu_fullsize.py: a lost low-order bf16 piece at a tile edge or a dropped split cross term fails here."""
+test_gpu_fullsize.py: a lost low-order bf16 piece at a tile edge or a dropped split cross term fails here.  Each child also
+runs the smallest volumes mvs_conv_layer / mvs_conv11_prob admit (1 x 1 x 1 upwards; probe_check.TINY_*) against the
+dense bound, inside a guarded, poisoned arena."""
 import json
 import os
 import subprocess
