@@ -53,8 +53,8 @@ _vpp = ctypes.POINTER(_vp)      # const float* const*
 
 # Every entry point, declared once on this side: header -> {name: argument types}, in the headers' order.  Any other
 # pointer is a c_void_p (device and host addresses travel as integers).  load() applies the table; SYMBOLS and
-# FUSE_SYMBOLS and CLOUD_SYMBOLS are its keys; tests/test_host_logic.py, tests/test_scan_fusion_host.py and
-# tests/test_cloud_downsample_host.py hold every argument list to its prototype.  Everything returns int except mvs_last_error_string.
+# FUSE_SYMBOLS, CLOUD_SYMBOLS and NORMALS_SYMBOLS are its keys; tests/test_host_logic.py, tests/test_scan_fusion_host.py,
+# tests/test_cloud_downsample_host.py and tests/test_cloud_normals_host.py hold every argument list to its prototype.  Everything returns int except mvs_last_error_string.
 _ABI = {
     "mvs_abi.h": {
         "mvs_abi_version": [],
@@ -106,10 +106,17 @@ _ABI = {
         "mvs_query_cloud_workspace": [_ll, _vp, _vp, _d, _szp],
         "mvs_cloud_downsample": [_vp, _i, _vp, _ll, _vp, _vp, _d, _d, _ll, _vp, _vp, _vp, _vp, _sz, _vp],
     },
+    "mvs_normals_abi.h": {
+        "mvs_query_normals_workspace": [_ll, _vp, _vp, _d, _szp],
+        "mvs_cloud_normals": [_vp, _i, _ll, _vp, _vp, _d, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+        "mvs_query_cloud_normals_downsample_workspace": [_ll, _vp, _vp, _d, _szp],
+        "mvs_cloud_downsample_normals": [_vp, _i, _vp, _vp, _ll, _vp, _vp, _d, _d, _ll, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    },
 }
 SYMBOLS = tuple(_ABI["mvs_abi.h"])
 FUSE_SYMBOLS = tuple(_ABI["mvs_fuse_abi.h"])
 CLOUD_SYMBOLS = tuple(_ABI["mvs_cloud_abi.h"])
+NORMALS_SYMBOLS = tuple(_ABI["mvs_normals_abi.h"])
 
 
 class MvsError(RuntimeError):
@@ -132,7 +139,7 @@ def load():
                 "g.build()'` (or make -C scene_3dreconstruction_mvsnet_amd/csrc). "
                 "There is no CPU/PyTorch fallback for the MVSNet depth path.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name in SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS:
+        for name in SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS:
             if not hasattr(lib, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}")
         for prototypes in _ABI.values():
@@ -771,6 +778,124 @@ def cloud_downsample(xyz, rgb, box_min, box_max, voxel_size, scale=1.0, capacity
                                           rgb_out.data_ptr() if capacity else None, counts.data_ptr(), ws.data_ptr(),
                                           ws.numel(), _stream(dev)))
     return xyz_out, rgb_out, counts
+
+
+# ---- point normals and the downsample that carries them (include/mvs_normals_abi.h, csrc/cloud_normals.hip) ----
+NORMALS_KNN_MAX, NORMALS_TILE = 64, 1024     # MVS_NORMALS_KNN_MAX, MVS_NORMALS_TILE
+
+
+def _cloud_xyz(xyz, who):
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise RuntimeError(f"{who}: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    if xyz.dtype not in (torch.float32, torch.float64) or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError(f"{who}: xyz must be float32 or float64 [P,3], got {xyz.dtype} {tuple(xyz.shape)}")
+    return xyz.contiguous()
+
+
+def query_normals_workspace(P, box_min, box_max, cell) -> int:
+    lo, hi = _box_arg(box_min, box_max, "query_normals_workspace")
+    return _query("mvs_query_normals_workspace", int(P), ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+
+
+def query_cloud_normals_downsample_workspace(P, box_min, box_max, voxel_size) -> int:
+    lo, hi = _box_arg(box_min, box_max, "query_cloud_normals_downsample_workspace")
+    return _query("mvs_query_cloud_normals_downsample_workspace", int(P), ctypes.addressof(lo), ctypes.addressof(hi),
+                  float(voxel_size))
+
+
+def cloud_normals(xyz, box_min, box_max, cell=5.0, knn=30, view_starts=None, centres=None, neighbours=False, out=None):
+    """A normal for every point of the cloud inside the box from its `knn` nearest neighbours there (the reference's
+    pcd.estimate_normals(), eval.py:817, as include/mvs_normals_abi.h defines it), on the device.
+
+    xyz float32 or float64 [P,3]; box_min, box_max: 3 host numbers each; cell: the search grid's cell edge (it changes the
+    time, never the result).  view_starts int64 [R+1] and centres float64 [R,3], both on the device or both None: the
+    normals of points view_starts[r] .. view_starts[r+1]-1 are turned towards centres[r].  Returns (normals float32 [P,3],
+    neighbours int32 [P,knn] or None, counts int64 [3]: members, members with an estimated normal, members an outside
+    point could have served better), all on the device.  `out` = (normals, neighbours or None, counts) receives the
+    results.  Enqueued on the current stream; nothing synchronises."""
+    xyz = _cloud_xyz(xyz, "cloud_normals")
+    dev = xyz.device
+    P, knn = xyz.shape[0], int(knn)
+    lo, hi = _box_arg(box_min, box_max, "cloud_normals")
+    if (view_starts is None) != (centres is None):
+        raise RuntimeError("cloud_normals: view_starts and centres must both be given or both be None")
+    R = 0
+    if view_starts is not None:
+        R = view_starts.shape[0] - 1 if isinstance(view_starts, torch.Tensor) and view_starts.dim() == 1 else -1
+        if R < 1 or view_starts.dtype != torch.int64 or view_starts.device != dev:
+            raise RuntimeError("cloud_normals: view_starts must be an int64 [R+1] tensor, R >= 1, on xyz's device")
+        if not isinstance(centres, torch.Tensor) or centres.dtype != torch.float64 or tuple(centres.shape) != (R, 3) \
+                or centres.device != dev:
+            raise RuntimeError(f"cloud_normals: centres must be a float64 [R,3] = [{R},3] tensor on xyz's device")
+        view_starts, centres = view_starts.contiguous(), centres.contiguous()
+    nbytes = _query("mvs_query_normals_workspace", P, ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+    with torch.cuda.device(dev):
+        if out is None:
+            normals = torch.empty((P, 3), dtype=torch.float32, device=dev)
+            nbr = torch.empty((P, knn), dtype=torch.int32, device=dev) if neighbours else None
+            counts = torch.empty((3,), dtype=torch.int64, device=dev)
+        else:
+            normals, nbr, counts = out
+            _check_out(normals, (P, 3), torch.float32, dev, "cloud_normals: out normals", f"float32 {(P, 3)} tensor on {dev}")
+            _check_out(counts, (3,), torch.int64, dev, "cloud_normals: out counts", f"int64 (3,) tensor on {dev}")
+            if nbr is not None:
+                _check_out(nbr, (P, knn), torch.int32, dev, "cloud_normals: out neighbours", f"int32 {(P, knn)} tensor on {dev}")
+        if P == 0:          # an empty tensor has no address to hand over: the three zero counts of the header's P == 0
+            if not 3 <= knn <= NORMALS_KNN_MAX:
+                raise RuntimeError(f"cloud_normals: knn = {knn} (need 3 <= knn <= {NORMALS_KNN_MAX})")
+            counts.zero_()
+            return normals, nbr, counts
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(load().mvs_cloud_normals(xyz.data_ptr(), MVS_CLOUD_F64 if xyz.dtype == torch.float64 else MVS_CLOUD_F32, P,
+                                       ctypes.addressof(lo), ctypes.addressof(hi), float(cell), knn,
+                                       view_starts.data_ptr() if R else None, centres.data_ptr() if R else None, R,
+                                       normals.data_ptr(), None if nbr is None else nbr.data_ptr(), counts.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), _stream(dev)))
+    return normals, nbr, counts
+
+
+def cloud_downsample_normals(xyz, rgb, normals, box_min, box_max, voxel_size, scale=1.0, capacity=None, out=None):
+    """cloud_downsample that also carries the points' normals: returns (xyz float32 [capacity,3], rgb uint8 [capacity,3],
+    normals float32 [capacity,3]: the mean of each voxel's normals, not renormalised, counts int64 [2]).  The first, second
+    and last are byte for byte what cloud_downsample returns.  normals float32 [P,3] on xyz's device.  `out` = (xyz, rgb,
+    normals, counts).  Enqueued on the current stream; nothing synchronises."""
+    xyz = _cloud_xyz(xyz, "cloud_downsample_normals")
+    dev = xyz.device
+    P = xyz.shape[0]
+    if not isinstance(rgb, torch.Tensor) or rgb.device != dev or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (P, 3):
+        raise RuntimeError(f"cloud_downsample_normals: rgb must be uint8 [P,3] = [{P},3] on xyz's device")
+    if not isinstance(normals, torch.Tensor) or normals.device != dev or normals.dtype != torch.float32 \
+            or tuple(normals.shape) != (P, 3):
+        raise RuntimeError(f"cloud_downsample_normals: normals must be float32 [P,3] = [{P},3] on xyz's device")
+    lo, hi = _box_arg(box_min, box_max, "cloud_downsample_normals")
+    capacity = P if capacity is None else int(capacity)
+    if capacity < 0:
+        raise RuntimeError(f"cloud_downsample_normals: capacity {capacity} is negative")
+    rgb, normals = rgb.contiguous(), normals.contiguous()
+    nbytes = _query("mvs_query_cloud_normals_downsample_workspace", P, ctypes.addressof(lo), ctypes.addressof(hi),
+                    float(voxel_size))
+    with torch.cuda.device(dev):
+        if out is None:
+            xyz_out = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
+            rgb_out = torch.empty((capacity, 3), dtype=torch.uint8, device=dev)
+            normals_out = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
+            counts = torch.empty((2,), dtype=torch.int64, device=dev)
+        else:
+            xyz_out, rgb_out, normals_out, counts = out
+            for t, shape, dt, name in ((xyz_out, (capacity, 3), torch.float32, "xyz"), (rgb_out, (capacity, 3), torch.uint8, "rgb"),
+                                       (normals_out, (capacity, 3), torch.float32, "normals"),
+                                       (counts, (2,), torch.int64, "counts")):
+                _check_out(t, shape, dt, dev, f"cloud_downsample_normals: out {name}", f"{dt} {shape} tensor on {dev}")
+        if P == 0:
+            counts.zero_()
+            return xyz_out, rgb_out, normals_out, counts
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(load().mvs_cloud_downsample_normals(
+            xyz.data_ptr(), MVS_CLOUD_F64 if xyz.dtype == torch.float64 else MVS_CLOUD_F32, rgb.data_ptr(), normals.data_ptr(),
+            P, ctypes.addressof(lo), ctypes.addressof(hi), float(voxel_size), float(scale), capacity,
+            xyz_out.data_ptr() if capacity else None, rgb_out.data_ptr() if capacity else None,
+            normals_out.data_ptr() if capacity else None, counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return xyz_out, rgb_out, normals_out, counts
 
 
 # ---- FeatureNet (reference models/mvsnet.py:10-30) -------------------------------------------

@@ -14,9 +14,13 @@
 //   cloud_emit_kernel        one block per tile: lanes ranked by mbcnt, one thread per occupied voxel writes its mean
 // A floating-point minimum and integer sums do not depend on the order of their operands, no block waits for another,
 // and linear voxel order is (iz, iy, ix) order: the same inputs give the same bytes on every run and stream.
+// mvs_cloud_downsample_normals (include/mvs_normals_abi.h) is the same launches with the accumulate and emit kernels'
+// kNormals = true forms, which also keep three 64-bit fixed-point sums of the points' normals per voxel, in an array of
+// their own behind the workspace of the plain call: the record and the plain call's kernels are what they were.
 // This file is compiled with -ffp-contract=off: voxel_index and voxel_corner are the header's fp64 restatement,
 // operation for operation, and the emit pass must recompute the very corner the accumulate pass subtracted.
 #include "mvs_cloud_abi.h"
+#include "mvs_normals_abi.h"
 #include "mvs_internal.h"
 
 #include <cmath>
@@ -65,6 +69,9 @@ struct CloudParams {
     CloudRecord* grid;
     CloudPartial* partial;
     int* tiles;                    // [n_tiles + 1]
+    const float* normals;          // the three below: mvs_cloud_downsample_normals only
+    float* normals_out;
+    long long* nsum;               // [cells][3]: sums of rint(clamp(n, -1, 1) * 2^30), zeroed with the records
     double bmin[3], bmax[3];
     double v, scale;
     long long capacity;
@@ -179,7 +186,7 @@ __global__ void __launch_bounds__(kCloudScanWidth) cloud_merge_kernel(CloudParam
     }
 }
 
-template <typename T>
+template <typename T, bool kNormals>
 __global__ void __launch_bounds__(kCloudThreads) cloud_accumulate_kernel(CloudParams C) {
     const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
     double p[3];
@@ -196,13 +203,23 @@ __global__ void __launch_bounds__(kCloudThreads) cloud_accumulate_kernel(CloudPa
         // the offset lies in [0, 1) up to a rounding of the corner: signed, so that a tiny negative one adds as such
         fix[a] = __double2ll_rn(((p[a] - voxel_corner(k, vmin, C.v)) / C.v) * 4294967296.0);
     }
-    CloudRecord* r = C.grid + (((size_t)idx[2] * C.n[1] + idx[1]) * C.n[0] + idx[0]);
+    const size_t cell = ((size_t)idx[2] * C.n[1] + idx[1]) * C.n[0] + idx[0];
+    CloudRecord* r = C.grid + cell;
     const unsigned char* c = C.rgb + (size_t)i * 3;
     __hip_atomic_fetch_add(&r->count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         __hip_atomic_fetch_add(&r->rgb[a], (unsigned long long)c[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_fetch_add(&r->fix[a], fix[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if constexpr (kNormals) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            double n = (double)C.normals[(size_t)i * 3 + a];
+            n = n != n ? 0.0 : n < -1.0 ? -1.0 : n > 1.0 ? 1.0 : n;
+            __hip_atomic_fetch_add(&C.nsum[cell * 3 + a], __double2ll_rn(n * 1073741824.0), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
 }
 
@@ -260,6 +277,7 @@ __global__ void __launch_bounds__(kCloudScanWidth) cloud_scan_kernel(CloudParams
     }
 }
 
+template <bool kNormals>
 __global__ void __launch_bounds__(kCloudThreads) cloud_emit_kernel(CloudParams C) {
     __shared__ int slot_count[kCloudSlots];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -295,6 +313,12 @@ __global__ void __launch_bounds__(kCloudThreads) cloud_emit_kernel(CloudParams C
                 const double mean = corner + ((double)r.fix[a] / count) * C.v * (1.0 / 4294967296.0);
                 dst[a] = (float)(mean * C.scale);          // v_cvt_f32_f64, round-to-nearest-even
                 col[a] = (unsigned char)((2ull * r.rgb[a] + r.count) / (2ull * r.count));
+            }
+            if constexpr (kNormals) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a)
+                    C.normals_out[(size_t)o * 3 + a] =
+                        (float)(((double)C.nsum[(size_t)cell * 3 + a] / count) * (1.0 / 1073741824.0));
             }
         }
     }
@@ -333,52 +357,42 @@ static size_t cloud_workspace(long long P, long long cells) {
            8 * (size_t)((cloud_tiles(cells) + 2) / 2);
 }
 
-}  // namespace mvs
+constexpr size_t kCloudNormalSums = 3 * sizeof(long long);     // per voxel, mvs_cloud_downsample_normals only
 
-using namespace mvs;
-
-extern "C" {
-
-int mvs_query_cloud_workspace(long long P, const double box_min[3], const double box_max[3], double voxel_size,
-                              size_t* bytes) {
-    if (!bytes || !box_min || !box_max) return fail(MVS_ERR_NULL, "mvs_query_cloud_workspace: NULL argument");
+// both entry points, after their NULL checks
+static int cloud_downsample(const char* who, bool with_normals, const void* xyz, int xyz_dtype, const unsigned char* rgb,
+                            const float* normals, long long P, const double* box_min, const double* box_max,
+                            double voxel_size, double scale, long long capacity, float* xyz_out, unsigned char* rgb_out,
+                            float* normals_out, long long* counts_out, void* workspace, size_t workspace_bytes,
+                            void* stream) {
     int n[3];
     long long cells;
-    if (int rc = cloud_check("mvs_query_cloud_workspace", P, box_min, box_max, voxel_size, n, &cells)) return rc;
-    *bytes = cloud_workspace(P, cells);
-    return MVS_OK;
-}
-
-int mvs_cloud_downsample(const void* xyz, int xyz_dtype, const unsigned char* rgb, long long P, const double box_min[3],
-                         const double box_max[3], double voxel_size, double scale, long long capacity, float* xyz_out,
-                         unsigned char* rgb_out, long long* counts_out, void* workspace, size_t workspace_bytes,
-                         void* stream) {
-    if (!xyz || !rgb || !box_min || !box_max || !counts_out || !workspace || (capacity != 0 && (!xyz_out || !rgb_out)))
-        return fail(MVS_ERR_NULL, "mvs_cloud_downsample: NULL argument");
-    int n[3];
-    long long cells;
-    if (int rc = cloud_check("mvs_cloud_downsample", P, box_min, box_max, voxel_size, n, &cells)) return rc;
+    if (int rc = cloud_check(who, P, box_min, box_max, voxel_size, n, &cells)) return rc;
     if (capacity < 0 || !std::isfinite(scale))
-        return fail(MVS_ERR_BAD_SHAPE, "mvs_cloud_downsample: capacity = %lld, scale = %g (need capacity >= 0 and a finite "
-                    "scale)", capacity, scale);
+        return fail(MVS_ERR_BAD_SHAPE, "%s: capacity = %lld, scale = %g (need capacity >= 0 and a finite scale)", who, capacity,
+                    scale);
     if (xyz_dtype != MVS_CLOUD_F32 && xyz_dtype != MVS_CLOUD_F64)
-        return fail(MVS_ERR_BAD_DTYPE, "mvs_cloud_downsample: xyz dtype %d (MVS_CLOUD_F32 or MVS_CLOUD_F64)", xyz_dtype);
-    const size_t need = cloud_workspace(P, cells);
+        return fail(MVS_ERR_BAD_DTYPE, "%s: xyz dtype %d (MVS_CLOUD_F32 or MVS_CLOUD_F64)", who, xyz_dtype);
+    const size_t need = cloud_workspace(P, cells) + (with_normals ? kCloudNormalSums * (size_t)cells : 0);
     if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 8)
-        return fail(MVS_ERR_WORKSPACE, "mvs_cloud_downsample: workspace of %zu bytes at %p, need %zu (8-byte aligned)",
-                    workspace_bytes, workspace, need);
+        return fail(MVS_ERR_WORKSPACE, "%s: workspace of %zu bytes at %p, need %zu (8-byte aligned)", who, workspace_bytes,
+                    workspace, need);
     CloudParams C{};
     C.xyz = xyz;
     C.rgb = rgb;
     C.xyz_out = xyz_out;
     C.rgb_out = rgb_out;
     C.counts_out = counts_out;
+    C.normals = normals;
+    C.normals_out = normals_out;
     char* ws = static_cast<char*>(workspace);
     C.head = reinterpret_cast<CloudHead*>(ws);
     C.grid = reinterpret_cast<CloudRecord*>(ws + sizeof(CloudHead));
     C.partial = reinterpret_cast<CloudPartial*>(ws + sizeof(CloudHead) + sizeof(CloudRecord) * (size_t)cells);
     C.n_chunks = (int)cloud_chunks(P);
     C.tiles = reinterpret_cast<int*>(reinterpret_cast<char*>(C.partial) + sizeof(CloudPartial) * (size_t)C.n_chunks);
+    // behind everything the plain call lays out (the tile offsets end on an 8-byte boundary)
+    C.nsum = with_normals ? reinterpret_cast<long long*>(ws + cloud_workspace(P, cells)) : nullptr;
     for (int a = 0; a < 3; ++a) {
         C.bmin[a] = box_min[a];
         C.bmax[a] = box_max[a];
@@ -401,18 +415,77 @@ int mvs_cloud_downsample(const void* xyz, int xyz_dtype, const unsigned char* rg
     if (int rc = check_hip(hipGetLastError(), "cloud_merge_kernel")) return rc;
     if (int rc = check_hip(hipMemsetAsync(C.grid, 0, sizeof(CloudRecord) * (size_t)cells, s), "zeroing the voxel grid"))
         return rc;
+    if (with_normals)
+        if (int rc = check_hip(hipMemsetAsync(C.nsum, 0, kCloudNormalSums * (size_t)cells, s), "zeroing the normal sums"))
+            return rc;
     if (P > 0) {
         const int blocks = (int)((P + kCloudThreads - 1) / kCloudThreads);
-        if (f64) cloud_accumulate_kernel<double><<<blocks, kCloudThreads, 0, s>>>(C);
-        else cloud_accumulate_kernel<float><<<blocks, kCloudThreads, 0, s>>>(C);
+        if (with_normals) {
+            if (f64) cloud_accumulate_kernel<double, true><<<blocks, kCloudThreads, 0, s>>>(C);
+            else cloud_accumulate_kernel<float, true><<<blocks, kCloudThreads, 0, s>>>(C);
+        } else {
+            if (f64) cloud_accumulate_kernel<double, false><<<blocks, kCloudThreads, 0, s>>>(C);
+            else cloud_accumulate_kernel<float, false><<<blocks, kCloudThreads, 0, s>>>(C);
+        }
         if (int rc = check_hip(hipGetLastError(), "cloud_accumulate_kernel")) return rc;
     }
     cloud_count_kernel<<<C.n_tiles, kCloudThreads, 0, s>>>(C);
     if (int rc = check_hip(hipGetLastError(), "cloud_count_kernel")) return rc;
     cloud_scan_kernel<<<1, kCloudScanWidth, 0, s>>>(C);
     if (int rc = check_hip(hipGetLastError(), "cloud_scan_kernel")) return rc;
-    cloud_emit_kernel<<<C.n_tiles, kCloudThreads, 0, s>>>(C);
+    if (with_normals) cloud_emit_kernel<true><<<C.n_tiles, kCloudThreads, 0, s>>>(C);
+    else cloud_emit_kernel<false><<<C.n_tiles, kCloudThreads, 0, s>>>(C);
     return check_hip(hipGetLastError(), "cloud_emit_kernel");
+}
+
+}  // namespace mvs
+
+using namespace mvs;
+
+extern "C" {
+
+int mvs_query_cloud_workspace(long long P, const double box_min[3], const double box_max[3], double voxel_size,
+                              size_t* bytes) {
+    if (!bytes || !box_min || !box_max) return fail(MVS_ERR_NULL, "mvs_query_cloud_workspace: NULL argument");
+    int n[3];
+    long long cells;
+    if (int rc = cloud_check("mvs_query_cloud_workspace", P, box_min, box_max, voxel_size, n, &cells)) return rc;
+    *bytes = cloud_workspace(P, cells);
+    return MVS_OK;
+}
+
+int mvs_cloud_downsample(const void* xyz, int xyz_dtype, const unsigned char* rgb, long long P, const double box_min[3],
+                         const double box_max[3], double voxel_size, double scale, long long capacity, float* xyz_out,
+                         unsigned char* rgb_out, long long* counts_out, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    if (!xyz || !rgb || !box_min || !box_max || !counts_out || !workspace || (capacity != 0 && (!xyz_out || !rgb_out)))
+        return fail(MVS_ERR_NULL, "mvs_cloud_downsample: NULL argument");
+    return cloud_downsample("mvs_cloud_downsample", false, xyz, xyz_dtype, rgb, nullptr, P, box_min, box_max, voxel_size,
+                            scale, capacity, xyz_out, rgb_out, nullptr, counts_out, workspace, workspace_bytes, stream);
+}
+
+int mvs_query_cloud_normals_downsample_workspace(long long P, const double box_min[3], const double box_max[3],
+                                                 double voxel_size, size_t* bytes) {
+    if (!bytes || !box_min || !box_max)
+        return fail(MVS_ERR_NULL, "mvs_query_cloud_normals_downsample_workspace: NULL argument");
+    int n[3];
+    long long cells;
+    if (int rc = cloud_check("mvs_query_cloud_normals_downsample_workspace", P, box_min, box_max, voxel_size, n, &cells))
+        return rc;
+    *bytes = cloud_workspace(P, cells) + kCloudNormalSums * (size_t)cells;
+    return MVS_OK;
+}
+
+int mvs_cloud_downsample_normals(const void* xyz, int xyz_dtype, const unsigned char* rgb, const float* normals, long long P,
+                                 const double box_min[3], const double box_max[3], double voxel_size, double scale,
+                                 long long capacity, float* xyz_out, unsigned char* rgb_out, float* normals_out,
+                                 long long* counts_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!xyz || !rgb || !normals || !box_min || !box_max || !counts_out || !workspace ||
+        (capacity != 0 && (!xyz_out || !rgb_out || !normals_out)))
+        return fail(MVS_ERR_NULL, "mvs_cloud_downsample_normals: NULL argument");
+    return cloud_downsample("mvs_cloud_downsample_normals", true, xyz, xyz_dtype, rgb, normals, P, box_min, box_max,
+                            voxel_size, scale, capacity, xyz_out, rgb_out, normals_out, counts_out, workspace,
+                            workspace_bytes, stream);
 }
 
 }  // extern "C"

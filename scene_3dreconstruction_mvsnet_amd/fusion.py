@@ -9,7 +9,9 @@ file I/O and the boolean selection of the fused points (eval.py:753-759) stay on
 selection on the device (mvs_fuse_points), and `reconstruct_scan` is the whole chain -- images of a scan in, its
 coloured point cloud out -- without a file in between.  `downsample_cloud` is eval.py's last step for the bin-picking
 datasets (eval.py:831-840: crop to the bin's outer box `bin_box`, voxel_down_sample, scale), on the device
-(mvs_cloud_downsample); `reconstruct_scan(..., downsample=...)` appends it to the chain.
+(mvs_cloud_downsample); `reconstruct_scan(..., downsample=...)` appends it to the chain.  `estimate_normals` is
+eval.py:817's pcd.estimate_normals() on the device (mvs_cloud_normals, include/mvs_normals_abi.h); the reference runs it
+before the crop and the voxel filter, which carry the normals along, and so does `downsample=dict(normals=...)`.
 
 Differences from the reference, flagged rather than hidden:
   * cv2.remap is restated inside the kernel (1/32-pixel quantised bilinear, zero border); OpenCV is
@@ -18,6 +20,10 @@ Differences from the reference, flagged rather than hidden:
   * the reference's PLY block (eval.py:789-800) raises AttributeError as written
     (`vertices_colors.dtype` on a list); `write_ply` emits what that block is evidently meant to
     produce through plyfile: binary little-endian vertices x,y,z (float) + red,green,blue (uchar).
+  * normals (INTEGRATION.md has the list): the sign is specified -- towards the point's own camera -- where Open3D
+    leaves it to its eigen-solver; only points inside a box are served, and the points whose neighbourhood a point
+    outside the box could have changed are counted; the PLY's nx, ny, nz are float32 where Open3D writes doubles;
+    the covariance is centred.  Open3D is not installed here: nothing was compared against it.
 """
 from __future__ import annotations
 
@@ -85,14 +91,21 @@ def filter_views(depths, confs, intrinsics, extrinsics, pairs, n_view_filter=10,
     return dict(geo_sum=geo, depth_avg=avg, masks=masks.bool(), xyz_world=xyz)
 
 
-def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray) -> None:
-    rec = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
-                                    ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray, normals: np.ndarray | None = None) -> None:
+    """Binary little-endian vertices x, y, z (float), then nx, ny, nz (float) when `normals` [P,3] is given -- Open3D's
+    property order --, then red, green, blue (uchar).  Without normals the file is what it always was."""
+    nfields = [] if normals is None else [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    rec = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + nfields +
+                   [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if normals is not None:
+        if len(normals) != len(xyz):
+            raise ValueError(f"write_ply: {len(normals)} normals for {len(xyz)} points")
+        rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\n"
-              "property float y\nproperty float z\nproperty uchar red\nproperty uchar green\n"
-              "property uchar blue\nend_header\n" % len(rec))
+              "property float y\nproperty float z\n%sproperty uchar red\nproperty uchar green\n"
+              "property uchar blue\nend_header\n" % (len(rec), "".join(f"property float {n}\n" for n, _ in nfields)))
     with open(filename, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())
@@ -201,18 +214,69 @@ def bin_box(dims=(0.57, 0.37, 0.22), delta=(0, 0, 0), wall=20.0, scale=1.0):
     return lo, hi
 
 
-def downsample_cloud(xyz, rgb, voxel_size=5.0, box=None, scale=0.01, capacity=None):
+def estimate_normals(xyz, knn=30, box=None, cell=5.0, view_counts=None, centres=None, return_neighbours=False):
+    """eval.py:817's pcd.estimate_normals() on the device (mvs_cloud_normals): a unit normal for every point of xyz
+    (float32 or float64 [P,3], on the GPU) inside `box` = (min, max) from its `knn` nearest neighbours inside the box;
+    points outside get (0, 0, 0).  box defaults to the bounding box of the finite points, which costs the one host
+    synchronisation of this function (its six numbers travel in the kernel arguments); with a box given nothing
+    synchronises.  cell: the search grid's cell edge, in the cloud's units -- it changes the time, never the result.
+    view_counts (the per-view counts `fuse_views` returns, any integer sequence) and centres (float [R,3], the camera
+    centres) turn each normal towards the camera of its point; the prefix of the counts is built on the device.  Without
+    them the sign makes the normal's largest component positive.
+    Returns (normals float32 [P,3], counts int64 [3]) on the device -- counts: points inside the box, those with an
+    estimated normal, those whose knn-th neighbour is farther than the nearest face of the box (a point outside could
+    have been nearer: grow the box until this is 0 for the whole cloud's answer) -- and, with return_neighbours, the
+    neighbour indices int32 [P,knn] (ascending distance, then index; -1 pads) as a third item."""
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise RuntimeError("estimate_normals: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    dev = xyz.device
+    if box is None:
+        finite = xyz[torch.isfinite(xyz).all(dim=1)]
+        if finite.shape[0] == 0:
+            lo, hi = (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)
+        else:
+            both = torch.stack([finite.min(dim=0).values, finite.max(dim=0).values]).double().cpu()      # the one sync
+            lo, hi = both[0].tolist(), both[1].tolist()
+    else:
+        lo, hi = box
+    starts = ctr = None
+    if (view_counts is None) != (centres is None):
+        raise RuntimeError("estimate_normals: view_counts and centres must both be given or both be None")
+    if view_counts is not None:
+        counts = torch.as_tensor(np.asarray(view_counts.cpu() if torch.is_tensor(view_counts) else view_counts, np.int64))
+        ctr = torch.as_tensor(np.asarray(centres.cpu() if torch.is_tensor(centres) else centres, np.float64))
+        if counts.dim() != 1 or counts.shape[0] < 1 or tuple(ctr.shape) != (counts.shape[0], 3):
+            raise RuntimeError(f"estimate_normals: view_counts must be [R], R >= 1, and centres [R,3]; got "
+                               f"{tuple(counts.shape)} and {tuple(ctr.shape)}")
+        with torch.cuda.device(dev):
+            starts = torch.zeros(counts.shape[0] + 1, dtype=torch.int64, device=dev)
+            starts[1:] = torch.cumsum(counts.to(dev, non_blocking=True), 0)
+            ctr = ctr.to(dev, non_blocking=True)
+    normals, nbr, n = _lib.cloud_normals(xyz, lo, hi, cell=cell, knn=knn, view_starts=starts, centres=ctr,
+                                         neighbours=return_neighbours)
+    return (normals, n, nbr) if return_neighbours else (normals, n)
+
+
+def downsample_cloud(xyz, rgb, voxel_size=5.0, box=None, scale=0.01, capacity=None, normals=None):
     """eval.py:831-840 on the device: crop the cloud to `box` = (min, max) (default bin_box(), in the cloud's units), keep
     the mean point and colour of every occupied voxel of size `voxel_size`, scale the coordinates.  xyz float32 or
     float64 [P,3], rgb uint8 [P,3], on the GPU.  Returns (xyz float32 [Q,3], rgb uint8 [Q,3]) on the device, voxels in
     ascending (iz, iy, ix).  Reading the two counts is the one host synchronisation.  capacity (default P, always
-    enough) bounds the device buffers."""
+    enough) bounds the device buffers.  With normals (float32 [P,3] on the GPU, e.g. estimate_normals') a third tensor
+    follows: float32 [Q,3], the mean of each voxel's normals, not renormalised, as Open3D's voxel filter leaves them
+    (mvs_cloud_downsample_normals); the first two are the same bytes either way."""
     lo, hi = bin_box() if box is None else box
-    out_xyz, out_rgb, counts = _lib.cloud_downsample(xyz, rgb, lo, hi, voxel_size, scale=scale, capacity=capacity)
+    if normals is None:
+        out_xyz, out_rgb, counts = _lib.cloud_downsample(xyz, rgb, lo, hi, voxel_size, scale=scale, capacity=capacity)
+    else:
+        out_xyz, out_rgb, out_normals, counts = _lib.cloud_downsample_normals(xyz, rgb, normals, lo, hi, voxel_size,
+                                                                              scale=scale, capacity=capacity)
     voxels = int(counts.cpu()[1])
     if voxels > out_xyz.shape[0]:
         raise RuntimeError(f"downsample_cloud: the cloud occupies {voxels} voxels, capacity is {out_xyz.shape[0]}")
-    return out_xyz[:voxels], out_rgb[:voxels]
+    if normals is None:
+        return out_xyz[:voxels], out_rgb[:voxels]
+    return out_xyz[:voxels], out_rgb[:voxels], out_normals[:voxels]
 
 
 def _packed_to_host(xyz, rgb):
@@ -232,14 +296,28 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
     Returns (vertices float32 [P,3], colours uint8 [P,3]); the PLY equals `filter_depth`'s byte for byte.
     downsample=dict(voxel_size=5.0, box=None, scale=0.01, plyfilename=None) also runs `downsample_cloud` on the fused
     cloud while it is on the device; the return is then (vertices, colours, ds_vertices float32 [Q,3], ds_colours uint8
-    [Q,3]) and the downsampled cloud goes to its own plyfilename through write_ply."""
+    [Q,3]) and the downsampled cloud goes to its own plyfilename through write_ply.
+    downsample=dict(..., normals=dict(knn=30, margin=20.0, cell=5.0)) estimates the normals of the fused cloud first
+    (eval.py:817 runs before the crop, eval.py:832), inside the crop box grown by `margin` on every side, each turned
+    towards the camera of its own reference view (centre -R^T t of the extrinsics the sample carries); the downsample
+    carries them, the small PLY gets nx, ny, nz, and the return gains two items: ds_normals float32 [Q,3] and the three
+    counts of estimate_normals as a numpy array -- the last is the number of points inside the grown box that a point
+    outside it could have served better.  The default margin is a guess (the reach of 30 neighbours on a dense scan),
+    not measured on a real bin scan: watch that count."""
     import copy
+    normals_opt = None
     if downsample is not None:
         downsample = dict(downsample)
         ds_ply = downsample.pop("plyfilename", None)
+        normals_opt = downsample.pop("normals", None)
         unknown = set(downsample) - {"voxel_size", "box", "scale"}
         if unknown:
-            raise ValueError(f"downsample: unknown keys {sorted(unknown)} (voxel_size, box, scale, plyfilename)")
+            raise ValueError(f"downsample: unknown keys {sorted(unknown)} (voxel_size, box, scale, plyfilename, normals)")
+        if normals_opt is not None:
+            normals_opt = dict(dict(knn=30, margin=20.0, cell=5.0), **normals_opt)
+            unknown = set(normals_opt) - {"knn", "margin", "cell"}
+            if unknown:
+                raise ValueError(f"downsample['normals']: unknown keys {sorted(unknown)} (knn, margin, cell)")
     for a in ("view_plan", "decode_view", "assemble", "metas"):
         if not hasattr(dataset, a):
             raise ValueError("reconstruct_scan needs a dataset with metas, view_plan(), decode_view() and assemble(), "
@@ -313,14 +391,28 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
                     Ks[ids[0]], Es[ids[0]] = np.asarray(s["intrinsics"][0]), np.asarray(s["extrinsics"][0])
         filtered = filter_views(depths, confs, Ks, Es, pairs, n_view_filter, photomask, geomask, condmask_pixel,
                                 condmask_depth, device)
-        xyz, rgb, _ = fuse_views(filtered, imgs, [slot[r] for r in refs])
-        if downsample is not None:
+        xyz, rgb, view_counts = fuse_views(filtered, imgs, [slot[r] for r in refs])
+        if normals_opt is not None:
+            lo, hi = bin_box() if downsample.get("box") is None else downsample["box"]
+            grown = (np.asarray(lo, np.float64) - normals_opt["margin"], np.asarray(hi, np.float64) + normals_opt["margin"])
+            E = Es[refs].astype(np.float64)
+            centres = -np.einsum("rji,rj->ri", E[:, :3, :3], E[:, :3, 3])          # -R^T t
+            normals, normal_counts = estimate_normals(xyz, knn=normals_opt["knn"], box=grown, cell=normals_opt["cell"],
+                                                      view_counts=view_counts, centres=centres)
+            ds_xyz, ds_rgb, ds_nrm = downsample_cloud(xyz, rgb, normals=normals, **downsample)
+            ds_vertices, ds_colours = _packed_to_host(ds_xyz, ds_rgb)
+            ds_normals, normal_counts = ds_nrm.cpu().numpy(), normal_counts.cpu().numpy()
+        elif downsample is not None:
             ds_vertices, ds_colours = _packed_to_host(*downsample_cloud(xyz, rgb, **downsample))
         vertices, colours = _packed_to_host(xyz, rgb)      # the one copy of the full cloud
     if plyfilename:
         write_ply(plyfilename, vertices, colours)
     if downsample is None:
         return vertices, colours
+    if normals_opt is None:
+        if ds_ply:
+            write_ply(ds_ply, ds_vertices, ds_colours)
+        return vertices, colours, ds_vertices, ds_colours
     if ds_ply:
-        write_ply(ds_ply, ds_vertices, ds_colours)
-    return vertices, colours, ds_vertices, ds_colours
+        write_ply(ds_ply, ds_vertices, ds_colours, ds_normals)
+    return vertices, colours, ds_vertices, ds_colours, ds_normals, normal_counts

@@ -13,7 +13,9 @@ pattern and the image size from a table keyed by --dataset_name; here they are t
 --downsample_mm V adds eval.py's last step for the bin-picking datasets (eval.py:831-840): the fused cloud is cropped to
 the bin's outer box, voxel-downsampled at V and scaled by --cloud_scale on the device, and written to
 OUT/<scan>/fused_dwnsmpld_<V>mm.ply, eval.py's name and place.  The box is --crop_box x0 y0 z0 x1 y1 z1 (in the cloud's
-units), or the bin of --bin_dims / --bin_delta (metres, fusion.bin_box).
+units), or the bin of --bin_dims / --bin_delta (metres, fusion.bin_box).  --normals_knn K (with --downsample_mm) adds
+eval.py:817's estimate_normals: normals from K neighbours inside the box grown by --normals_margin_mm, turned towards each
+point's camera, carried through the voxel filter and written as nx, ny, nz.
 """
 from __future__ import annotations
 
@@ -61,9 +63,16 @@ def main(argv=None):
     p.add_argument("--bin_delta", type=float, nargs=3, default=(0.0, 0.0, 0.0), metavar=("X", "Y", "Z"),
                    help="offset of the bin in metres (0.08 0.03 0 is eval.py's overhead02 / overhead03)")
     p.add_argument("--cloud_scale", type=float, default=0.01, help="factor on the downsampled coordinates (eval.py:839)")
+    p.add_argument("--normals_knn", type=int, default=None, metavar="K",
+                   help="with --downsample_mm: estimate normals from K neighbours (eval.py:817) and write nx, ny, nz")
+    p.add_argument("--normals_margin_mm", type=float, default=20.0,
+                   help="the neighbour search covers the box grown by this much (a guess; the tool prints how many points "
+                        "a point outside could have served better)")
     args = p.parse_args(argv)
     if args.downsample_mm is None and args.crop_box is not None:
         p.error("--crop_box needs --downsample_mm")
+    if args.downsample_mm is None and args.normals_knn is not None:
+        p.error("--normals_knn needs --downsample_mm")
     box = None
     if args.downsample_mm is not None:
         box = (args.crop_box[:3], args.crop_box[3:]) if args.crop_box else bin_box(args.bin_dims, args.bin_delta)
@@ -82,6 +91,8 @@ def main(argv=None):
             os.makedirs(os.path.join(args.outdir, scan), exist_ok=True)
             small = os.path.join(args.outdir, scan, downsampled_name(args.downsample_mm))
             downsample = dict(voxel_size=args.downsample_mm, box=box, scale=args.cloud_scale, plyfilename=small)
+            if args.normals_knn is not None:
+                downsample["normals"] = dict(knn=args.normals_knn, margin=args.normals_margin_mm)
         got = reconstruct_scan(model, ds, scan, n_view_filter=args.NviewFilter, photomask=args.photomask,
                                geomask=args.geomask, condmask_pixel=args.condmask_pixel,
                                condmask_depth=args.condmask_depth, plyfilename=ply, downsample=downsample)
@@ -90,6 +101,10 @@ def main(argv=None):
         if downsample:
             print(f"{scan}: {len(got[2])} voxels of {args.downsample_mm:g} -> {small}")
             written.append(small)
+            if args.normals_knn is not None:
+                members, estimated, open_ = (int(x) for x in got[5])
+                print(f"{scan}: normals of {estimated} of {members} points in the grown box; {open_} of them could have "
+                      f"had a nearer neighbour outside it")
     return written
 
 

@@ -1,0 +1,416 @@
+"""Host-side checks of the point normals (include/mvs_normals_abi.h, csrc/cloud_normals.hip, csrc/cloud_downsample.hip):
+none needs a GPU.  Every refusal is decided before the first HIP call, so the fake device pointers are never
+dereferenced; the refusals run in a child process that sees no device (HIP_VISIBLE_DEVICES and ROCR_VISIBLE_DEVICES
+empty), where a call the library failed to refuse would come back as MVS_ERR_HIP (4) instead of reaching hardware."""
+import ctypes
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+for path in (REPO, HERE):
+    if path not in sys.path:
+        sys.path.insert(0, path)
+
+import cloud_ref  # noqa: E402
+import normals_ref  # noqa: E402
+
+HEADER = os.path.join(REPO, "include", "mvs_normals_abi.h")
+OK, BAD_SHAPE, BAD_DTYPE, WORKSPACE, HIP, NULL = 0, 1, 2, 3, 4, 5
+BIN = ((-305.0, -205.0, -20.0), (305.0, 205.0, 220.0))
+NAN, INF = float("nan"), float("inf")
+
+# ---------------------------------------------------------------- the refusal cases (shared by the child and the tests)
+# mvs_cloud_normals: pointer slots xyz box_min box_max view_starts centres normals_out nbr_out counts_out workspace
+N_GOOD = dict(dtype=0, P=5000, lo=BIN[0], hi=BIN[1], cell=5.0, knn=30, R=2)
+N_CASES = [(f"null {k}", dict(null=[k]), NULL, "NULL") for k in (0, 1, 2, 5, 7, 8)]
+N_CASES += [
+    ("nbr_out may be NULL", dict(null=[6], ws_bytes=0), WORKSPACE, "workspace"),
+    ("R == 0 with both NULL", dict(R=0, null=[3, 4], ws_bytes=0), WORKSPACE, "workspace"),
+    ("R == 0 with view_starts", dict(R=0, null=[4]), NULL, "R == 0"),
+    ("R == 0 with centres", dict(R=0, null=[3]), NULL, "R == 0"),
+    ("R == 0 with both given", dict(R=0), NULL, "R == 0"),
+    ("R > 0 without view_starts", dict(null=[3]), NULL, "R == 0"),
+    ("R > 0 without centres", dict(null=[4]), NULL, "R == 0"),
+    ("R > 0 without either", dict(null=[3, 4]), NULL, "R == 0"),
+    ("R < 0", dict(R=-1, null=[3, 4]), BAD_SHAPE, "R = -1"),
+    ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
+    ("P = 2^31", dict(P=1 << 31), BAD_SHAPE, "2^31"),
+    ("P = 2^40", dict(P=1 << 40), BAD_SHAPE, "2^31"),
+    ("knn 2", dict(knn=2), BAD_SHAPE, "knn = 2"),
+    ("knn 0", dict(knn=0), BAD_SHAPE, "knn = 0"),
+    ("knn -5", dict(knn=-5), BAD_SHAPE, "knn = -5"),
+    ("knn 65", dict(knn=65), BAD_SHAPE, "knn = 65"),
+    ("cell 0", dict(cell=0.0), BAD_SHAPE, "cell"),
+    ("cell < 0", dict(cell=-5.0), BAD_SHAPE, "cell"),
+    ("cell nan", dict(cell=NAN), BAD_SHAPE, "cell"),
+    ("cell inf", dict(cell=INF), BAD_SHAPE, "cell"),
+    ("box nan", dict(lo=(NAN, 0, 0)), BAD_SHAPE, "box axis 0"),
+    ("box -inf", dict(lo=(0, -INF, 0)), BAD_SHAPE, "box axis 1"),
+    ("box inf", dict(hi=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
+    ("min > max", dict(lo=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
+    ("1291^3 cells", dict(lo=(0, 0, 0), hi=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("one axis of 3e9", dict(lo=(0, 0, 0), hi=(3e9, 0, 0), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("the quotient overflows", dict(lo=(-1e308, 0, 0), hi=(1e308, 1, 1), cell=1e-300), BAD_SHAPE, "2^31 cells"),
+    ("denormal cell", dict(lo=(0, 0, 0), hi=(1, 1, 1), cell=5e-324), BAD_SHAPE, "2^31 cells"),
+    ("dtype 2", dict(dtype=2), BAD_DTYPE, "dtype"),
+    ("dtype -1", dict(dtype=-1), BAD_DTYPE, "dtype"),
+    ("one byte short", dict(ws_bytes="need-1"), WORKSPACE, "workspace"),
+    ("no workspace", dict(ws_bytes=0), WORKSPACE, "workspace"),
+    ("misaligned workspace", dict(ws_bytes="need", ws_ptr=0x900004), WORKSPACE, "aligned"),
+    ("everything right reaches HIP", dict(ws_bytes="need"), HIP, ""),
+    ("P == 0 reaches HIP", dict(P=0, ws_bytes="need"), HIP, ""),
+]
+# mvs_cloud_downsample_normals: xyz rgb normals box_min box_max xyz_out rgb_out normals_out counts_out workspace
+D_GOOD = dict(dtype=0, P=5000, lo=BIN[0], hi=BIN[1], v=5.0, scale=0.01, capacity=100)
+D_CASES = [(f"null {k}", dict(null=[k]), NULL, "NULL") for k in range(10)]
+D_CASES += [(f"null output {k} at capacity 0", dict(null=[k], capacity=0, ws_bytes=0), WORKSPACE, "workspace") for k in (5, 6, 7)]
+D_CASES += [
+    ("null normals at capacity 0", dict(null=[2], capacity=0), NULL, "NULL"),
+    ("null counts at capacity 0", dict(null=[8], capacity=0), NULL, "NULL"),
+    ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
+    ("P = 2^31", dict(P=1 << 31), BAD_SHAPE, "2^31"),
+    ("voxel 0", dict(v=0.0), BAD_SHAPE, "voxel_size"),
+    ("voxel nan", dict(v=NAN), BAD_SHAPE, "voxel_size"),
+    ("capacity < 0", dict(capacity=-1), BAD_SHAPE, "capacity"),
+    ("scale nan", dict(scale=NAN), BAD_SHAPE, "scale"),
+    ("scale inf", dict(scale=INF), BAD_SHAPE, "scale"),
+    ("box nan", dict(hi=(305, NAN, 220)), BAD_SHAPE, "box axis 1"),
+    ("min > max", dict(lo=(-305, -205, 220.5)), BAD_SHAPE, "box axis 2"),
+    ("1292^3 cells", dict(lo=(0, 0, 0), hi=(1290, 1290, 1290), v=1.0), BAD_SHAPE, "2^31 cells"),
+    ("dtype 7", dict(dtype=7), BAD_DTYPE, "dtype"),
+    ("one byte short", dict(ws_bytes="need-1"), WORKSPACE, "workspace"),
+    ("the plain call's size is too small", dict(ws_bytes="plain"), WORKSPACE, "workspace"),
+    ("misaligned workspace", dict(ws_bytes="need", ws_ptr=0xA00004), WORKSPACE, "aligned"),
+    ("everything right reaches HIP", dict(ws_bytes="need"), HIP, ""),
+]
+
+
+def _box(lo, hi):
+    return (ctypes.c_double * 3)(*lo), (ctypes.c_double * 3)(*hi)
+
+
+def _fake(k):
+    return ctypes.c_void_p(0x100000 * (k + 1))        # aligned, never dereferenced
+
+
+def _call_normals(lib, ov):
+    a = dict(N_GOOD, **{k: v for k, v in ov.items() if k in N_GOOD})
+    lo, hi = _box(a["lo"], a["hi"])
+    p = [_fake(k) for k in range(9)]
+    p[1], p[2] = ctypes.c_void_p(ctypes.addressof(lo)), ctypes.c_void_p(ctypes.addressof(hi))
+    for k in ov.get("null", []):
+        p[k] = None
+    if "ws_ptr" in ov:
+        p[8] = ctypes.c_void_p(ov["ws_ptr"])
+    ws = ov.get("ws_bytes", 1 << 44)
+    if isinstance(ws, str):
+        ws = normals_ref.workspace_bytes(a["P"], a["lo"], a["hi"], a["cell"]) - (ws == "need-1")
+    return lib.mvs_cloud_normals(p[0], a["dtype"], a["P"], p[1], p[2], a["cell"], a["knn"], p[3], p[4], a["R"], p[5], p[6],
+                                 p[7], p[8], ws, None)
+
+
+def _call_downsample(lib, ov):
+    a = dict(D_GOOD, **{k: v for k, v in ov.items() if k in D_GOOD})
+    lo, hi = _box(a["lo"], a["hi"])
+    p = [_fake(k) for k in range(10)]
+    p[3], p[4] = ctypes.c_void_p(ctypes.addressof(lo)), ctypes.c_void_p(ctypes.addressof(hi))
+    for k in ov.get("null", []):
+        p[k] = None
+    if "ws_ptr" in ov:
+        p[9] = ctypes.c_void_p(ov["ws_ptr"])
+    ws = ov.get("ws_bytes", 1 << 44)
+    if isinstance(ws, str):
+        plain = cloud_ref.workspace_bytes(a["P"], a["lo"], a["hi"], a["v"])
+        cells = int(np.prod(cloud_ref.grid_shape(a["lo"], a["hi"], a["v"])))
+        ws = plain if ws == "plain" else plain + 24 * cells - (ws == "need-1")
+    return lib.mvs_cloud_downsample_normals(p[0], a["dtype"], p[1], p[2], a["P"], p[3], p[4], a["v"], a["scale"],
+                                            a["capacity"], p[5], p[6], p[7], p[8], p[9], ws, None)
+
+
+def _child():
+    from scene_3dreconstruction_mvsnet_amd import _lib
+    lib = _lib.load()
+    for ep, cases, call in (("normals", N_CASES, _call_normals), ("downsample", D_CASES, _call_downsample)):
+        for label, ov, want, _ in cases:
+            # a refusal nobody else makes sets the thread's error string: a refusal without its own message shows as stale
+            assert lib.mvs_query_feature_workspace(1, 3, 2, ctypes.byref(ctypes.c_size_t(0))) == BAD_SHAPE
+            before = lib.mvs_last_error_string()
+            got = call(lib, ov)
+            err = lib.mvs_last_error_string() or b""
+            print("R " + json.dumps(dict(ep=ep, case=label, got=got, err=err.decode("utf-8", "replace"), stale=err == before)),
+                  flush=True)
+
+
+_RESULTS = {}
+
+
+def _records():
+    if not _RESULTS:
+        env = {k: v for k, v in os.environ.items() if not k.startswith("MVS_") or k == "MVS_LIB_PATH"}
+        env.update(HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--refusals"], env=env, capture_output=True, text=True,
+                           timeout=300)
+        recs = [json.loads(ln[2:]) for ln in r.stdout.splitlines() if ln.startswith("R ")]
+        _RESULTS.update(rc=r.returncode, stderr=r.stderr[-2000:], records={(x["ep"], x["case"]): x for x in recs})
+    assert _RESULTS["rc"] == 0, _RESULTS["stderr"]
+    return _RESULTS["records"]
+
+
+@pytest.mark.parametrize("ep,cases", [("normals", N_CASES), ("downsample", D_CASES)])
+def test_every_refusal_comes_with_its_status_and_its_message(ep, cases):
+    records = _records()
+    assert len({label for label, *_ in cases}) == len(cases)
+    wrong = []
+    for label, _, want, text in cases:
+        rec = records[(ep, label)]
+        if rec["got"] != want or (want != HIP and (rec["stale"] or text not in rec["err"])):
+            wrong.append((label, want, rec["got"], rec["err"]))
+    assert not wrong, wrong
+
+
+# ---------------------------------------------------------------- declarations
+from test_host_logic import header_argtypes  # noqa: E402
+from scene_3dreconstruction_mvsnet_amd import _lib, fusion, reconstruct  # noqa: E402
+
+
+def _plain_prototypes(src):
+    """Comments inside prototypes dropped and `double name[3]` written `double* name`, which is the same C parameter."""
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    return re.sub(r"(\w+)\s*\[\s*\d+\s*\]", r"* \1", src)
+
+
+def test_normals_symbols_are_the_declarations_of_the_normals_header():
+    src = open(HEADER).read()
+    declared = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", src, flags=re.M)
+    assert declared == ["mvs_query_normals_workspace", "mvs_cloud_normals", "mvs_query_cloud_normals_downsample_workspace",
+                        "mvs_cloud_downsample_normals"]
+    assert list(_lib.NORMALS_SYMBOLS) == declared == list(_lib._ABI["mvs_normals_abi.h"])
+    assert not set(declared) & (set(_lib.SYMBOLS) | set(_lib.FUSE_SYMBOLS) | set(_lib.CLOUD_SYMBOLS))
+    prototypes = header_argtypes(_plain_prototypes(src))
+    assert sorted(prototypes) == sorted(declared)
+    for name, kinds in prototypes.items():
+        assert _lib._ABI["mvs_normals_abi.h"][name] == kinds, name
+        assert list(getattr(_lib.load(), name).argtypes) == kinds, name
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name in declared:
+        assert hasattr(raw, name), name
+    assert '#include "mvs_abi.h"' in src
+    for name, value in (("MVS_NORMALS_KNN_MAX", _lib.NORMALS_KNN_MAX), ("MVS_NORMALS_TILE", _lib.NORMALS_TILE)):
+        assert int(re.search(rf"^#define {name} (\d+)", src, flags=re.M).group(1)) == value == getattr(normals_ref, name[12:])
+    # the other headers declare none of them; the main one names this header
+    main = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
+    assert "mvs_normals_abi.h" in main
+    for other in ("mvs_abi.h", "mvs_fuse_abi.h", "mvs_cloud_abi.h"):
+        text = open(os.path.join(REPO, "include", other)).read()
+        assert not re.search(r"^int\s+mvs_\w*normals", text, flags=re.M), other
+
+
+def test_the_abi_version_is_still_2():
+    assert _lib.load().mvs_abi_version() == 2 == _lib.ABI_VERSION
+    main = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
+    assert re.search(r"^#define MVS_ABI_VERSION 2$", main, flags=re.M)
+
+
+# ---------------------------------------------------------------- workspace formulas
+@pytest.mark.parametrize("P,lo,hi,cell", [(5000, BIN[0], BIN[1], 5.0), (1, BIN[0], BIN[1], 5.0), (2, BIN[0], BIN[1], 2.5),
+                                          (4097, (-300, -200, -50), (300, 200, 150), 7.3), (0, BIN[0], BIN[1], 5.0),
+                                          (3, (0, 0, 0), (0, 0, 0), 1.0), (64, (0, 0, 0), (10, 10, 10), 10.0),
+                                          ((1 << 31) - 1, (0, 0, 0), (1289, 1289, 1289), 1.0),
+                                          (7, (-1e-3, -1e-3, -1e-3), (1e-3, 1e-3, 1e-3), 1e300)])
+def test_normals_workspace_query_agrees_with_the_headers_formula(P, lo, hi, cell):
+    want = normals_ref.workspace_bytes(P, lo, hi, cell)
+    assert _lib.query_normals_workspace(P, lo, hi, cell) == want and want % 8 == 0
+    n = normals_ref.grid_shape(lo, hi, cell)
+    cells = n[0] * n[1] * n[2]
+    # every term is the smallest that holds what the header says it holds
+    tiles = -(-cells // _lib.NORMALS_TILE)
+    assert want >= 24 * P + 4 * P + 4 * cells + 4 * (tiles + 1) and want < 24 * P + 4 * P + 4 * cells + 4 * (tiles + 1) + 24
+
+
+def test_the_normals_grid_is_the_headers():
+    assert normals_ref.grid_shape(*BIN, 5.0) == [123, 83, 49]                      # floor(span / cell) + 1
+    assert normals_ref.grid_shape((0, 0, 0), (10, 10, 10), 10.0) == [2, 2, 2]       # a box-sized cell: the far faces get a cell
+    assert normals_ref.grid_shape((0, 0, 0), (0, 0, 0), 1.0) == [1, 1, 1]
+    with pytest.raises(_lib.MvsError) as e:
+        _lib.query_normals_workspace(10, (0, 0, 0), (1290, 1290, 1290), 1.0)      # 1291^3 >= 2^31
+    assert e.value.code == BAD_SHAPE
+    with pytest.raises(_lib.MvsError):
+        _lib.query_normals_workspace(10, (0, 0, 0), (1, 1, 1), 0.0)
+
+
+@pytest.mark.parametrize("P,lo,hi,v", [(5000, BIN[0], BIN[1], 5.0), (1025, BIN[0], BIN[1], 2.5), (0, BIN[0], BIN[1], 5.0),
+                                       (3, (0, 0, 0), (0, 0, 0), 1.0), (1000, (-24, -24, 0), (24, 24, 32), 0.4)])
+def test_the_downsample_with_normals_needs_24_bytes_per_voxel_more_than_the_plain_one(P, lo, hi, v):
+    cells = int(np.prod(cloud_ref.grid_shape(lo, hi, v)))
+    plain = _lib.query_cloud_workspace(P, lo, hi, v)
+    assert plain == cloud_ref.workspace_bytes(P, lo, hi, v)              # the plain formula is what it was
+    assert _lib.query_cloud_normals_downsample_workspace(P, lo, hi, v) == plain + 24 * cells
+
+
+# ---------------------------------------------------------------- write_ply
+def _old_write_ply(filename, xyz, rgb):
+    """fusion.write_ply as it was before it learnt normals, kept here as the yardstick of 'byte for byte'."""
+    rec = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\n"
+              "property float y\nproperty float z\nproperty uchar red\nproperty uchar green\n"
+              "property uchar blue\nend_header\n" % len(rec))
+    with open(filename, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def read_ply_with_normals(path):
+    with open(path, "rb") as f:
+        head, body = f.read().split(b"end_header\n", 1)
+    names = re.findall(rb"property (\w+) (\w+)", head)
+    assert names == [(b"float", b"x"), (b"float", b"y"), (b"float", b"z"), (b"float", b"nx"), (b"float", b"ny"),
+                     (b"float", b"nz"), (b"uchar", b"red"), (b"uchar", b"green"), (b"uchar", b"blue")], names
+    n = int(re.search(rb"element vertex (\d+)", head).group(1))
+    rec = np.frombuffer(body, dtype=[(k.decode(), "<f4" if t == b"float" else "u1") for t, k in names])
+    assert len(rec) == n
+    col = lambda *ks: np.column_stack([rec[k] for k in ks])      # noqa: E731
+    return col("x", "y", "z"), col("red", "green", "blue"), col("nx", "ny", "nz")
+
+
+@pytest.mark.parametrize("P", [0, 1, 257])
+def test_write_ply_is_unchanged_without_normals_and_reads_back_with_them(tmp_path, P):
+    rng = np.random.default_rng(P)
+    xyz = rng.normal(0, 100, (P, 3)).astype(np.float32)
+    rgb = rng.integers(0, 256, (P, 3), dtype=np.uint8)
+    nrm = rng.normal(0, 1, (P, 3)).astype(np.float32)
+    if P:
+        nrm[0] = [np.nan, -0.0, np.inf]
+    a, b, c = (str(tmp_path / f) for f in ("a.ply", "b.ply", "c.ply"))
+    _old_write_ply(a, xyz, rgb)
+    fusion.write_ply(b, xyz, rgb)
+    fusion.write_ply(c, xyz, rgb, None)
+    assert open(a, "rb").read() == open(b, "rb").read() == open(c, "rb").read()
+    fusion.write_ply(c, xyz, rgb, nrm)
+    x, col, n = read_ply_with_normals(c)
+    assert np.array_equal(x.view(np.uint32), xyz.view(np.uint32)) and np.array_equal(col, rgb)
+    assert np.array_equal(n.view(np.uint32), nrm.view(np.uint32))
+    assert os.path.getsize(c) - os.path.getsize(a) == 12 * P + len("property float nx\n") * 3
+    with pytest.raises(ValueError, match="normals for"):
+        fusion.write_ply(c, xyz, rgb, np.zeros((P + 1, 3), np.float32))
+
+
+# ---------------------------------------------------------------- the yardstick on cases with known answers
+def test_the_yardstick_on_axis_aligned_lattice_planes():
+    g = np.arange(8, dtype=np.float64)
+    X, Y = (a.reshape(-1) for a in np.meshgrid(g, g, indexing="ij"))
+    for axis in range(3):
+        p = np.zeros((64, 3))
+        p[:, (axis + 1) % 3], p[:, (axis + 2) % 3], p[:, axis] = X, Y, 3.0
+        r = normals_ref.estimate(p, (-1, -1, -1), (9, 9, 9), 9)
+        want = np.zeros(3)
+        want[axis] = 1.0
+        assert r["counts"][:2] == [64, 64] and np.array_equal(r["normals"], np.tile(want, (64, 1)))
+        assert (r["eig"][:, 0] == 0).all() and (r["eig"][:, 1] > 0).all() and not r["degenerate"].any()
+        # cameras on either side of the plane: the first half looks from below
+        centres = np.full((2, 3), 3.5)
+        centres[0, axis], centres[1, axis] = -50.0, 50.0
+        r = normals_ref.estimate(p, (-1, -1, -1), (9, 9, 9), 9, view_starts=[0, 32, 64], centres=centres)
+        assert np.array_equal(r["normals"][:32], np.tile(-want, (32, 1))) and np.array_equal(r["normals"][32:], np.tile(want, (32, 1)))
+    # the neighbours of the corner (0, 0) of the x-y lattice at knn 9: distance, then index
+    p = np.column_stack([X, Y, np.zeros(64)])
+    r = normals_ref.estimate(p, (-1, -1, -1), (9, 9, 9), 9)
+    # d2: 0 | 1 1 | 2 | 4 4 | 5 5 | 8; index = 8 x + y
+    assert r["nbr"][0].tolist() == [0, 1, 8, 9, 2, 16, 10, 17, 18]
+    assert r["nbr"].dtype == np.int32
+
+
+def test_the_yardstick_on_a_tilted_exact_plane():
+    """Points with small integer coordinates on x + 2 y + 2 z = 0: every difference, product and sum is exact, the
+    covariance has the exact null vector (1, 2, 2) / 3."""
+    rng = np.random.default_rng(5)
+    ab = rng.integers(-40, 41, size=(300, 2)).astype(np.float64)
+    p = ab[:, :1] * [2.0, -1.0, 0.0] + ab[:, 1:] * [0.0, 1.0, -1.0]        # two integer vectors in the plane
+    assert ((p @ [1.0, 2.0, 2.0]) == 0).all()
+    r = normals_ref.estimate(p, (-100, -100, -100), (100, 100, 100), 12)
+    n = np.array([1.0, 2.0, 2.0]) / 3.0
+    ok = ~r["degenerate"] & (r["eig"][:, 1] > 1e-9)            # not collinear
+    assert ok.sum() > 250
+    assert (normals_ref.angle_between(r["normals"][ok], n) <= r["angle_bound"][ok]).all()
+    assert (r["normals"][ok] @ n > 0).all()                     # largest component (y, the lower of the tied two) positive
+    assert (np.abs(r["eig"][ok, 0]) <= r["rayleigh_slack"][ok]).all()
+    # towards a camera on the far side
+    r = normals_ref.estimate(p, (-100, -100, -100), (100, 100, 100), 12, view_starts=[0, 300], centres=[-300.0 * n])
+    assert (r["normals"][ok] @ n < 0).all() and (r["view"] == 0).all()
+    assert r["counts"] == [300, 300, int(r["uncertified"].sum())]
+
+
+def test_the_yardstick_on_duplicates_members_and_counts():
+    base = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [5.0, 5.0, 0.5]])
+    p = np.repeat(base, 2, axis=0)                       # every point twice: 0 1 | 2 3 | 4 5 | 6 7
+    p = np.vstack([p, [[np.nan, 0, 0], [0, np.inf, 0], [50.0, 0, 0]]])      # three non-members
+    r = normals_ref.estimate(p, (-10, -10, -10), (10, 10, 10), 4)
+    assert r["member"].tolist() == [True] * 8 + [False] * 3 and r["counts"][:2] == [8, 8]
+    # a point, its twin (the lower index first), then the nearest pair: ties by index
+    assert r["nbr"][0].tolist() == [0, 1, 2, 3] and r["nbr"][1].tolist() == [0, 1, 2, 3]
+    assert r["nbr"][3].tolist() == [2, 3, 0, 1] and r["nbr"][5].tolist() == [4, 5, 0, 1]
+    assert (r["nbr"][8:] == -1).all() and (r["normals"][8:] == 0).all()
+    # two coincident pairs are collinear: lambda_0 = lambda_1 = 0, the bound says nothing, the normal is still a unit vector
+    assert np.allclose(np.linalg.norm(r["normals"][:8], axis=1), 1.0) and r["angle_bound"][0] > 1.5
+    # all coincident: C == 0 -> (0, 0, 1); fewer than three members likewise
+    same = np.tile([1.5, 2.5, 3.5], (6, 1))
+    r = normals_ref.estimate(same, (0, 0, 0), (5, 5, 5), 3)
+    assert r["degenerate"].all() and np.array_equal(r["normals"], np.tile([0.0, 0.0, 1.0], (6, 1))) and r["counts"][:2] == [6, 6]
+    r = normals_ref.estimate(base[:2], (-1, -1, -1), (2, 2, 2), 3)
+    assert r["counts"] == [2, 0, 2] and np.array_equal(r["normals"], np.tile([0.0, 0.0, 1.0], (2, 1)))
+    assert r["nbr"].tolist() == [[0, 1, -1], [1, 0, -1]]
+    r = normals_ref.estimate(base[:2], (-1, -1, -1), (2, 2, 2), 3, view_starts=[0, 2], centres=[[0.0, 0.0, -9.0]])
+    assert np.array_equal(r["normals"], np.tile([0.0, 0.0, -1.0], (2, 1)))       # the degenerate normal is signed too
+    # uncertified: the k-th neighbour against the nearest face.  Five points on a line one unit apart, knn 3
+    line = np.column_stack([np.arange(5.0), np.zeros(5), np.zeros(5)])
+    r = normals_ref.estimate(line, (-0.5, -5, -5), (10, 5, 5), 3)
+    # point 0: neighbours at 0, 1, 2 -> d2 = 4 > 0.5^2; point 1: d2 = 1 (0 and 2) <= 1.5^2; ...
+    assert r["uncertified"].tolist() == [True, False, False, False, False] and r["counts"] == [5, 5, 1]
+
+
+def test_the_voxel_mean_of_normals_on_a_hand_written_case():
+    xyz = np.array([[0.0, 0.0, 0.0], [2.0, 1.0, 1.0], [10.0, 10.0, 10.0], [11.0, 0.0, 0.0], [3.0, 0.0, 0.0]])
+    nrm = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.5, 2.0, np.nan], [9.0, 9.0, 9.0], [0.0, 0.0, -1.0]], np.float32)
+    got = normals_ref.voxel_mean_normals(xyz, nrm, (0, 0, 0), (10, 10, 10), 5.0)
+    # voxels (0,0,0): points 0, 1; (1,0,0): point 4; (2,2,2): point 2, clamped to 1 and NaN as 0; point 3 is outside
+    assert got.tolist() == [[0.5, 0.5, 0.0], [0.0, 0.0, -1.0], [0.5, 1.0, 0.0]]
+
+
+# ---------------------------------------------------------------- the Python layer, before any GPU work
+def test_python_functions_refuse_host_tensors_and_bad_options():
+    import torch
+    xyz = torch.zeros(4, 3)
+    with pytest.raises(RuntimeError, match="xyz must be a CUDA"):
+        _lib.cloud_normals(xyz, *BIN)
+    with pytest.raises(RuntimeError, match="xyz must be a CUDA"):
+        _lib.cloud_downsample_normals(xyz, torch.zeros(4, 3, dtype=torch.uint8), torch.zeros(4, 3), *BIN, 5.0)
+    with pytest.raises(RuntimeError, match="CUDA"):
+        fusion.estimate_normals(xyz)
+    with pytest.raises(RuntimeError, match="CUDA"):
+        fusion.downsample_cloud(xyz, torch.zeros(4, 3, dtype=torch.uint8), normals=torch.zeros(4, 3))
+    with pytest.raises(SystemExit):         # normals without a voxel size are refused while the arguments are parsed
+        reconstruct.main(["--testpath", "x", "--testlist", "y", "--loadckpt", "z", "--normals_knn", "30"])
+
+    class Stop(Exception):
+        pass
+
+    class NoDataset:
+        def __getattr__(self, name):
+            raise Stop(name)
+    with pytest.raises(ValueError, match=r"downsample\['normals'\]: unknown keys \['k'\]"):
+        fusion.reconstruct_scan(None, NoDataset(), downsample=dict(voxel_size=5.0, normals=dict(k=8)))
+    with pytest.raises(ValueError, match="unknown keys"):
+        fusion.reconstruct_scan(None, NoDataset(), downsample=dict(voxel_size=5.0, normal=dict(knn=8)))
+
+
+if __name__ == "__main__":
+    assert sys.argv[1] == "--refusals"
+    _child()
