@@ -279,8 +279,19 @@ int mvs_filter_depth(const float* depth, const float* conf, const float* ref_mat
  *   (mvs_feature_layer 0 and 1 are the two separate kernels of MVS_FEAT_SPLIT01=1), for parity tests and per-kernel
  *   timing; imgs in any mvs_image_format -> y C8-planar [1][N][H][W][8].  Same refusals as mvs_feature_net_fmt
  *   (NULL, format, N*H*W*8 >= 2^31, H or W < 4); nothing is enqueued on a refusal.
- * FeatureNet promises nothing for non-finite pixels: the k5 layers' padded 26th tap multiplies a voxel by a packed
- *   weight of exactly 0, which turns an infinite activation into NaN where the reference keeps the infinity.
+ * NaN and infinity (mvs_feature_layer, mvs_feature_conv01_fmt, mvs_feature_net[_fmt], mvs_forward_images[_fmt]): a
+ *   non-finite pixel, activation, weight or BatchNorm parameter is ordinary data and is never hidden.  Every ReLU keeps
+ *   a NaN, as F.relu does.  An output is non-finite wherever the reference's is: NaN where it is NaN; NaN or the
+ *   infinity where it is +-inf (the layers' padded last tap multiplies the pixel under the last real tap by a packed
+ *   weight of exactly 0, and inf * 0 is NaN; that pixel belongs to the same output, so nothing spreads).  Outside the
+ *   reference's own footprint of the damaged pixels -- k x k per layer, every output channel; 5 x 5 for the fused
+ *   conv0 + conv1 kernel, which computes conv0 on conv1's halo and selects 0 outside the image; 41 x 41 image pixels
+ *   per feature pixel for the whole net -- the output bytes are those of the same call on the same input with the
+ *   damaged values replaced by finite ones, other views included.  A NaN in a weight or a BatchNorm parameter is
+ *   folded into the blob by mvs_pack_feature_weights and makes that channel, hence every feature, depth and
+ *   confidence, NaN.  mvs_feature_net's last step moves layer 7's bits to NCHW; the 16-bit copy of the features
+ *   (MVS_FEAT16=1) keeps NaN and +-inf and turns a finite value beyond the format's range into the infinity of its
+ *   sign.
  * mvs_forward_images: FeatureNet + mvs_depth_infer with the features handed over in the private
  *   C8-planar layout (no NCHW round trip); H, W multiples of 32; workspace of
  *   mvs_query_forward_workspace(N,H,W,D,dtype) bytes.
@@ -355,6 +366,10 @@ int mvs_depth_metrics(const float* depth_est, const float* depth_gt, const float
  *   mvs_softargmin_conf's domain: D in [1, 2^24], h, w >= 1 and h*w <= 2^31 - 256, else MVS_ERR_BAD_SHAPE (narrowed from
  *   "any D, h*w < 2^31": the launcher's rounded-up int grid wrapped in the last 127 pixels of that range, and the
  *   backward accepts what its forward does).
+ *   NaN and infinity: a thread owns a pixel.  A NaN or +inf logit at pixel p, logits that are all -inf at p, or a
+ *   non-finite grad_depth[p] make grad_cost[:, p] non-finite (NaN, or the infinity the formula gives for an infinite
+ *   grad_depth); a single -inf logit among finite ones is a term of exactly 0 with gradient 0, and the other depths
+ *   of that pixel keep their bound.  The bytes of every other pixel are those of the call on finite input.
  * Neither allocates, needs a workspace or synchronises. */
 int mvs_warp_variance_backward(const float* feats, const float* rt, const float* depth_values, const float* grad_var,
                                float* grad_feats, int N, int C, int D, int h, int w, void* stream);
@@ -387,6 +402,13 @@ int mvs_softargmin_backward(const float* cost, const float* depth_values, const 
  *     when gbias != NULL, gbias[co] = sum_o gy[co][o].  Split-K into per-block partial sums in `workspace`
  *     (>= mvs_query_conv3d_train_workspace bytes, 256-byte aligned, else MVS_ERR_WORKSPACE) and a second kernel that
  *     adds them in a fixed order: no float atomics, bit-identical from run to run and stream to stream.
+ * NaN and infinity in x or gy are ordinary data and never hidden; they reach exactly what the formulas above say and
+ *   the bytes of every other output are those of the call on finite input.  Forward and data gradient: the 3 x 3 x 3
+ *   (adjoint) footprint of the damaged voxel, every output channel (lanes, rows and taps outside the volume are selected
+ *   to 0 or skipped, never multiplied).  Weight gradient: a non-finite x[ci] at voxel v reaches gw[:, ci, tap] for the
+ *   taps through which an in-range output reads v; a non-finite gy[co] reaches gbias[co] and all of gw[co, :, :], also
+ *   the taps that are out of range at that output (NaN * 0 is NaN; fp64 conv3d autograd gives the same set).  A
+ *   non-finite weight is never hidden either; how far it reaches is not stated.
  * None allocates or synchronises. */
 int mvs_query_conv3d_train_workspace(int Cin, int Cout, int D, int H, int W, int stride, size_t* bytes);
 int mvs_conv3d_train_forward(const float* x, const float* w, const float* bias, float* y, int Cin, int Cout, int D,
@@ -417,11 +439,19 @@ int mvs_conv3d_train_backward_weight(const float* x, const float* gy, float* gw,
  *     num_batches_tracked stays with the caller.
  *   The variance is a merge of per-thread and per-block (count, mean, M2) triples: one statistics read of y, and no
  *   mean^2 / var term in its error (tests/bn3d_ref.py derives the bound).
- * mvs_bn3d_train_backward: with g = grad_out where r > 0 (relu != 0; r recomputed from y, save_mean, save_invstd,
- *   gamma, beta by the forward's instruction sequence, so the mask is the sign of the forward's output bit for bit),
- *   else 0, and xhat = (y - mean) * invstd:
+ * mvs_bn3d_train_backward: with g = 0 where r <= 0, else grad_out (relu != 0; r recomputed from y, save_mean,
+ *   save_invstd, gamma, beta by the forward's instruction sequence, so the mask is the sign of the forward's output bit
+ *   for bit; a NaN r passes grad_out, as the forward's ReLU passes the NaN and as torch's threshold_backward does),
+ *   and xhat = (y - mean) * invstd:
  *     grad_beta = sum g;  grad_gamma = sum g xhat;  grad_y = gamma invstd (g - grad_beta / M - xhat grad_gamma / M)
  *   The skip's gradient is grad_out itself: no kernel.
+ * NaN and infinity: a channel is the unit.  A non-finite y[:, c] makes all of out[:, c], save_mean[c], save_invstd[c],
+ *   running_mean[c] and running_var[c] non-finite (the merge of the (count, mean, M2) triples turns an infinite mean
+ *   into inf - inf: NaN where the reference holds an infinity, or 0 for the invstd of an infinite variance); a
+ *   non-finite skip element reaches its own output element only.  Backward: a non-finite grad_out[:, c] (where the ReLU
+ *   is open) or y[:, c] reaches grad_y[:, c], grad_gamma[c] and grad_beta[c]; in a channel whose statistics are NaN
+ *   every element passes the ReLU, so grad_beta[c] is the plain sum of grad_out[:, c].  The bytes of every other
+ *   channel, through the block tree and the second kernel, are those of the call on finite input.
  * Both: per-block partial results in `workspace` (>= mvs_query_bn3d_train_workspace bytes, 256-byte aligned, else
  * MVS_ERR_WORKSPACE) combined by a second kernel in a fixed order: no float atomics, bit-identical from run to run and
  * stream to stream.  Forward reads y twice and skip once and writes out once; backward reads y and grad_out twice each
@@ -431,7 +461,8 @@ int mvs_conv3d_train_backward_weight(const float* x, const float* gy, float* gw,
  * or 64) by V voxels (V a positive multiple of 4, V*C < 2^31), both 16-byte aligned:
  *     MVS_RELAYOUT_C8_TO_CHANNELS_LAST      C8-planar [C/8][V][8] (mvs_warp_variance's output) -> channels-last [V][C]
  *     MVS_RELAYOUT_CHANNELS_LAST_TO_PLANAR  channels-last [V][C] -> planar [C][V], the NCDHW gradient that
- *                                           mvs_warp_variance_backward reads */
+ *                                           mvs_warp_variance_backward reads
+ *   Every 32-bit pattern is moved as it is, NaN payloads and signed zeros included. */
 #define MVS_RELAYOUT_C8_TO_CHANNELS_LAST 0
 #define MVS_RELAYOUT_CHANNELS_LAST_TO_PLANAR 1
 int mvs_query_bn3d_train_workspace(int C, long long M, size_t* bytes);

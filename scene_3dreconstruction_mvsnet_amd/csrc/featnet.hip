@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void fconv_mfma_kernel(
             const int m = 4 * (lane >> 4) + e;
             const int oy = 2 * ty + (m >> 3), ox = 8 * tx + (m & 7);
             const float v = acc[i][e] + bv;
-            tile[oy * RP + ox * CP + (ox >> 3) * 16 + co] = RELU ? fmaxf(v, 0.0f) : v;
+            tile[oy * RP + ox * CP + (ox >> 3) * 16 + co] = RELU ? relu(v) : v;
         }
     }
     __syncthreads();
@@ -317,18 +317,18 @@ __global__ __launch_bounds__(256) void fconv01_fused_kernel(
         const bool in0 = (oy0 - 1 + hy0) >= 0 && (oy0 - 1 + hy0) < H && (ox0 - 1 + hx0) >= 0 && (ox0 - 1 + hx0) < W;
         const bool in1 = (oy0 - 1 + hy1) >= 0 && (oy0 - 1 + hy1) < H && (ox0 - 1 + hx1) >= 0 && (ox0 - 1 + hx1) < W;
         f32x4 lo, hi;
-        lo.x = in0 ? fmaxf(a0[0][0], 0.f) : 0.f; lo.y = in0 ? fmaxf(a0[0][1], 0.f) : 0.f;
-        lo.z = in0 ? fmaxf(a0[1][0], 0.f) : 0.f; lo.w = in0 ? fmaxf(a0[1][1], 0.f) : 0.f;
-        hi.x = in0 ? fmaxf(a0[2][0], 0.f) : 0.f; hi.y = in0 ? fmaxf(a0[2][1], 0.f) : 0.f;
-        hi.z = in0 ? fmaxf(a0[3][0], 0.f) : 0.f; hi.w = in0 ? fmaxf(a0[3][1], 0.f) : 0.f;
+        lo.x = in0 ? relu(a0[0][0]) : 0.f; lo.y = in0 ? relu(a0[0][1]) : 0.f;
+        lo.z = in0 ? relu(a0[1][0]) : 0.f; lo.w = in0 ? relu(a0[1][1]) : 0.f;
+        hi.x = in0 ? relu(a0[2][0]) : 0.f; hi.y = in0 ? relu(a0[2][1]) : 0.f;
+        hi.z = in0 ? relu(a0[3][0]) : 0.f; hi.w = in0 ? relu(a0[3][1]) : 0.f;
         float* dst = tile + (hy0 * G::HXP + hx0) * G::VS;
         *reinterpret_cast<f32x4*>(dst) = lo;
         *reinterpret_cast<f32x4*>(dst + 4) = hi;
         if (tid + 256 < G::NVOX) {
-            lo.x = in1 ? fmaxf(a1[0][0], 0.f) : 0.f; lo.y = in1 ? fmaxf(a1[0][1], 0.f) : 0.f;
-            lo.z = in1 ? fmaxf(a1[1][0], 0.f) : 0.f; lo.w = in1 ? fmaxf(a1[1][1], 0.f) : 0.f;
-            hi.x = in1 ? fmaxf(a1[2][0], 0.f) : 0.f; hi.y = in1 ? fmaxf(a1[2][1], 0.f) : 0.f;
-            hi.z = in1 ? fmaxf(a1[3][0], 0.f) : 0.f; hi.w = in1 ? fmaxf(a1[3][1], 0.f) : 0.f;
+            lo.x = in1 ? relu(a1[0][0]) : 0.f; lo.y = in1 ? relu(a1[0][1]) : 0.f;
+            lo.z = in1 ? relu(a1[1][0]) : 0.f; lo.w = in1 ? relu(a1[1][1]) : 0.f;
+            hi.x = in1 ? relu(a1[2][0]) : 0.f; hi.y = in1 ? relu(a1[2][1]) : 0.f;
+            hi.z = in1 ? relu(a1[3][0]) : 0.f; hi.w = in1 ? relu(a1[3][1]) : 0.f;
             dst = tile + (hy1 * G::HXP + hx1) * G::VS;
             *reinterpret_cast<f32x4*>(dst) = lo;
             *reinterpret_cast<f32x4*>(dst + 4) = hi;
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256) void fconv01_fused_kernel(
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int m = 4 * (lane >> 4) + e;
-                tile[(2 * ty + (m >> 3)) * ORP + (8 * tx + (m & 7)) * 8 + col] = fmaxf(acc[i][e] + bv, 0.0f);
+                tile[(2 * ty + (m >> 3)) * ORP + (8 * tx + (m & 7)) * 8 + col] = relu(acc[i][e] + bv);
             }
         }
     }

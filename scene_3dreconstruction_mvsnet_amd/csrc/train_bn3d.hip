@@ -6,6 +6,7 @@
 // autograd backward.  Data is channels-last [M][C] fp32, M = B*D*H*W voxels (statistics pooled over the batch), C in
 // {8, 16, 32, 64}.  This file is compiled with -ffp-contract=off: bn_pre() below is ONE instruction sequence (sub, mul,
 // mul, add) wherever it is inlined, so the backward's ReLU mask agrees bit for bit with the sign of the forward's output.
+// Forward and backward close the ReLU on !(pre <= 0): a NaN pre-activation passes, value and gradient, as in torch.
 //
 // Geometry (all five sweep kernels).  A block of 256 threads owns 8 * R consecutive rows, R = 256 / (C / 4); a thread
 // owns one float4 (4 channels, group cg = tid % (C/4)) of the rows k = j * R + q, j < 8, q = tid / (C/4): a wave's
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_sums_kernel(const float* __rest
 #pragma unroll
         for (int j = 0; j < kRows; ++j) {
             float gm = d[j].v[c];
-            if (RELU) gm = bn_pre(v[j].v[c], mu.v[c], is.v[c], ga.v[c], be.v[c]) > 0.f ? gm : 0.f;
+            if (RELU) gm = !(bn_pre(v[j].v[c], mu.v[c], is.v[c], ga.v[c], be.v[c]) <= 0.f) ? gm : 0.f;   // NaN passes, as torch's
             tg[j] = gm;
             tx[j] = gm * bn_xhat(v[j].v[c], mu.v[c], is.v[c]);
         }
@@ -315,7 +316,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(const float* __res
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float gm = d[j].v[c];
-            if (RELU) gm = bn_pre(v[j].v[c], mu.v[c], is.v[c], ga.v[c], be.v[c]) > 0.f ? gm : 0.f;
+            if (RELU) gm = !(bn_pre(v[j].v[c], mu.v[c], is.v[c], ga.v[c], be.v[c]) <= 0.f) ? gm : 0.f;   // NaN passes, as torch's
             const float xh = bn_xhat(v[j].v[c], mu.v[c], is.v[c]);
             r.v[c] = kk[c] * ((gm - mb[c]) - xh * mg[c]);
         }

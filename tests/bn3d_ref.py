@@ -321,7 +321,9 @@ def _final(parts, counts, geo, merge):
 
 def emulate_forward(y, gamma, beta, skip=None, rm=None, rv=None, momentum=0.1, eps=1e-5, relu=True, defects=()):
     """-> dict(mean, invstd, var, out, pre, rm, rv) in fp32, computed as bn_stats_kernel, bn_stats_final_kernel and
-    bn_apply_kernel compute them."""
+    bn_apply_kernel compute them.  Defect "nan_channel_leaks" (not in DEFECTS: it shows on non-finite input only,
+    tests/test_nonfinite_train_host.py): the last merge also reads the partial of the neighbouring channel group,
+    behind a weight of 0."""
     M, C = y.shape
     geo = geometry(C, M)
     y, gamma, beta = y.astype(F), gamma.astype(F), beta.astype(F)
@@ -341,6 +343,8 @@ def emulate_forward(y, gamma, beta, skip=None, rm=None, rv=None, momentum=0.1, e
 
     pm, pq = _tree_q((mean_t, m2_t), geo, nrows, merge)
     mean, m2 = _final((pm, pq), nrows, geo, merge)
+    if "nan_channel_leaks" in defects:
+        mean, m2 = mean + F(0) * np.roll(mean, 4), m2 + F(0) * np.roll(m2, 4)
     var = m2 / F(M)
     if "naive_variance" in defects:                                     # E[y^2] - E[y]^2 from fp32 sums
         mean = np.sum(y, 0, dtype=F) / F(M)
@@ -366,13 +370,14 @@ def emulate_forward(y, gamma, beta, skip=None, rm=None, rv=None, momentum=0.1, e
 
 
 def emulate_mask(y, gamma, beta, mean, invstd, defects=(), out=None):
-    """the backward's ReLU mask."""
+    """the backward's ReLU mask: closed where pre <= 0, so that a NaN pre-activation passes (as the forward's ReLU
+    and torch's threshold_backward)."""
     if "mask_from_out" in defects:                  # defect: the stored output, which includes the skip
         return out > 0
     if "folded_backward" in defects:                # defect: pre recomputed as a y + b
         a = gamma * invstd
-        return a * y + (beta - mean * a) > 0
-    return ((y - mean) * invstd) * gamma + beta > 0
+        return ~(a * y + (beta - mean * a) <= 0)
+    return ~(((y - mean) * invstd) * gamma + beta <= 0)
 
 
 def emulate_backward(y, go, gamma, beta, mean, invstd, relu=True, defects=(), out=None):

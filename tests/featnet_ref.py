@@ -380,7 +380,10 @@ def emulate_layer(st, layer, x, mutation=None, prepadded=False):
     """fconv_mfma_kernel in fp32 numpy: acc += a b serially over (chunk, k-step, j4, lane group g), the padded tap read
     from the clamped LDS offset, then + shift (and ReLU).  `prepadded`: x already carries conv's zero ring (the fused
     kernel's conv1 half).  mutation: ("drop_tap", tap) zeroes that tap's packed weights, "swap_halves" reads the other
-    channel half, ("residue", v) leaves v in the padded panel slots."""
+    channel half, ("residue", v) leaves v in the padded panel slots.  Two more show on non-finite input only
+    (tests/test_nonfinite_train_host.py): ("relu_drops_nan",) is the ReLU as fmaxf(v, 0), whose NaN is 0;
+    ("mask_by_multiply",) fills the out-of-image halo with the clamped load of the view's first pixel times 0 instead
+    of a selected 0."""
     ci_n, co_n, k, s = LAYERS[layer]
     wf, sh, _ = fold32(st, layer)
     bp = pack_panels(wf)
@@ -403,6 +406,9 @@ def emulate_layer(st, layer, x, mutation=None, prepadded=False):
     else:
         H, W = x.shape[2:]
         xp = np.zeros((N, 8 * nch, H + 2 * p, W + 2 * p), np.float32)
+        if mutation == ("mask_by_multiply",):
+            with np.errstate(invalid="ignore"):
+                xp[:, :ci_n] = x[:, :, :1, :1] * np.float32(0)
         xp[:, :ci_n, p:p + H, p:p + W] = x
     Ho, Wo = out_size(H, s), out_size(W, s)
     acc = np.zeros((N, 16 * nt, Ho, Wo), np.float32)
@@ -414,13 +420,13 @@ def emulate_layer(st, layer, x, mutation=None, prepadded=False):
         b = bp[c, :, ks, 16 * g:16 * g + 16, j4].reshape(-1)
         acc = _fma32(a[:, None], b[None, :, None, None], acc)
     y = (acc[:, :co_n] + sh[None, :, None, None]).astype(np.float32)
-    return y if layer == 7 else np.maximum(y, np.float32(0))
+    return y if layer == 7 else (np.fmax if mutation == ("relu_drops_nan",) else np.maximum)(y, np.float32(0))
 
 
 def emulate_fused(st, img32, mutation=None):
     """fconv01_fused_kernel: conv0 as 27 serial fp32 FMAs from the shift on conv1's halo (the image grown by one pixel),
     ReLU, the halo pixels outside the image set to 0 -- mutation "ring": left as computed, i.e. ReLU(shift0) -- then
-    conv1 in the MFMA order."""
+    conv1 in the MFMA order.  ("relu_drops_nan",): both ReLUs as fmaxf(v, 0)."""
     w0, s0, _ = fold32(st, 0)
     img32 = np.asarray(img32, np.float32)
     N, _, H, W = img32.shape
@@ -429,12 +435,12 @@ def emulate_fused(st, img32, mutation=None):
     a = np.broadcast_to(s0[None, :, None, None], (N, 8, H + 2, W + 2)).astype(np.float32)
     for c, ky, kx in itertools.product(range(3), range(3), range(3)):
         a = _fma32(ip[:, c, None, ky:ky + H + 2, kx:kx + W + 2], w0[None, :, c, ky, kx, None, None], a)
-    a = np.maximum(a, np.float32(0))
+    a = (np.fmax if mutation == ("relu_drops_nan",) else np.maximum)(a, np.float32(0))
     if mutation != ("ring",):
         inside = np.zeros((H + 2, W + 2), bool)
         inside[1:1 + H, 1:1 + W] = True
         a = np.where(inside[None, None], a, np.float32(0))
-    return emulate_layer(st, 1, a, prepadded=True)
+    return emulate_layer(st, 1, a, mutation=mutation if mutation == ("relu_drops_nan",) else None, prepadded=True)
 
 
 # ---- shapes ----------------------------------------------------------------------------------------------------------

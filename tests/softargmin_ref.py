@@ -485,12 +485,17 @@ def emulate_forward(cost, dv, hw_form=None, exp_ulps=0, rcp_ulps=0, defect=None)
 
 
 def emulate_backward(cost, dv, gd, exp_ulps=0, rcp_ulps=0, defect=None):
+    """softargmin_bwd_kernel in fp32 numpy.  Defect "minus_inf_term_nan" (not in BWD_DEFECTS: it shows on non-finite
+    logits only, tests/test_nonfinite_train_host.py): the maximum is found on the way, as the forward's loop form does,
+    and a -inf logit met while the running maximum is still -inf is expf(-inf - -inf), NaN, instead of a term of 0."""
     c, dv, gd = np.asarray(cost, f32), np.asarray(dv, f32), np.asarray(gd, f32)
     D, P = c.shape
     with np.errstate(all="ignore"):
         M = c.max(0)
         S, SD, SI = np.zeros(P, f32), np.zeros(P, f32), np.zeros(P, f32)
         e = _expf(c - M[None], exp_ulps)
+        if defect == "minus_inf_term_nan":
+            e = np.where(np.isnan(_expf(c - np.maximum.accumulate(c, 0))), f32(np.nan), e)
         for d in range(D):
             S = S + e[d]
             SD = _fma(e[d], dv[d], SD)

@@ -1,5 +1,5 @@
 """Per-layer and whole-net timing of FeatureNet in HIP (featnet.hip) at a config's image size, with
-PyTorch-ROCm (MIOpen) timed beside it.  Usage: python tools/time_featnet.py [cfg2]"""
+PyTorch-ROCm (MIOpen) timed beside it.  Usage: python tools/time_featnet.py [cfg2 [iterations per timed window]]"""
 import json
 import os
 import sys
@@ -22,7 +22,11 @@ fblob = model._feature_blob(dev)
 imgs = torch.rand(N, 3, H, W, device=dev)
 
 
-def timed(fn, iters=30):
+ITERS = int(sys.argv[2]) if len(sys.argv) > 2 else 30
+
+
+def timed(fn, iters=None):
+    iters = iters or ITERS
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
@@ -48,6 +52,8 @@ for l, (ci, co, k, s) in enumerate(_lib.FEATURE_LAYERS):
     flops_total += fl
     res[f"L{l}"] = {"ms": round(ms, 4), "TF": round(fl / ms / 1e9, 1), "GBps": round(by / ms / 1e6, 0)}
     x, hh, ww = y, ho, wo
+# conv0 + conv1 as the one fused kernel the whole net runs in the place of L0 and L1
+res["fused01"] = {"ms": round(timed(lambda: _lib.feature_conv01(imgs, fblob)), 4)}
 ws = torch.empty(_lib.query_feature_workspace(N, H, W), dtype=torch.uint8, device=dev)
 res["hip_total_ms"] = round(timed(lambda: _lib.feature_net(imgs, fblob, ws)), 4)
 with torch.no_grad():
