@@ -52,7 +52,8 @@ extern "C" {
  * mvs_bn3d_train_backward, mvs_volume_relayout; and, declared in a header of their own, include/mvs_fuse_abi.h:
  * mvs_query_fuse_workspace, mvs_fuse_points.
  * Likewise include/mvs_cloud_abi.h: mvs_query_cloud_workspace, mvs_cloud_downsample.
- * Likewise include/mvs_normals_abi.h: point normals of a cloud, and the downsample that carries them. */
+ * Likewise include/mvs_normals_abi.h: point normals of a cloud, and the downsample that carries them.
+ * Likewise include/mvs_outliers_abi.h: statistical outlier removal among the points of a cloud inside a box. */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {

@@ -53,8 +53,9 @@ _vpp = ctypes.POINTER(_vp)      # const float* const*
 
 # Every entry point, declared once on this side: header -> {name: argument types}, in the headers' order.  Any other
 # pointer is a c_void_p (device and host addresses travel as integers).  load() applies the table; SYMBOLS and
-# FUSE_SYMBOLS, CLOUD_SYMBOLS and NORMALS_SYMBOLS are its keys; tests/test_host_logic.py, tests/test_scan_fusion_host.py,
-# tests/test_cloud_downsample_host.py and tests/test_cloud_normals_host.py hold every argument list to its prototype.  Everything returns int except mvs_last_error_string.
+# FUSE_SYMBOLS, CLOUD_SYMBOLS, NORMALS_SYMBOLS and OUTLIERS_SYMBOLS are its keys; tests/test_host_logic.py,
+# tests/test_scan_fusion_host.py, tests/test_cloud_downsample_host.py, tests/test_cloud_normals_host.py and
+# tests/test_cloud_outliers_host.py hold every argument list to its prototype.  Everything returns int except mvs_last_error_string.
 _ABI = {
     "mvs_abi.h": {
         "mvs_abi_version": [],
@@ -112,11 +113,16 @@ _ABI = {
         "mvs_query_cloud_normals_downsample_workspace": [_ll, _vp, _vp, _d, _szp],
         "mvs_cloud_downsample_normals": [_vp, _i, _vp, _vp, _ll, _vp, _vp, _d, _d, _ll, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     },
+    "mvs_outliers_abi.h": {
+        "mvs_query_outliers_workspace": [_ll, _vp, _vp, _d, _szp],
+        "mvs_cloud_outliers": [_vp, _i, _ll, _vp, _vp, _d, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    },
 }
 SYMBOLS = tuple(_ABI["mvs_abi.h"])
 FUSE_SYMBOLS = tuple(_ABI["mvs_fuse_abi.h"])
 CLOUD_SYMBOLS = tuple(_ABI["mvs_cloud_abi.h"])
 NORMALS_SYMBOLS = tuple(_ABI["mvs_normals_abi.h"])
+OUTLIERS_SYMBOLS = tuple(_ABI["mvs_outliers_abi.h"])
 
 
 class MvsError(RuntimeError):
@@ -139,7 +145,7 @@ def load():
                 "g.build()'` (or make -C scene_3dreconstruction_mvsnet_amd/csrc). "
                 "There is no CPU/PyTorch fallback for the MVSNet depth path.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name in SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS:
+        for name in SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS + OUTLIERS_SYMBOLS:
             if not hasattr(lib, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}")
         for prototypes in _ABI.values():
@@ -896,6 +902,63 @@ def cloud_downsample_normals(xyz, rgb, normals, box_min, box_max, voxel_size, sc
             xyz_out.data_ptr() if capacity else None, rgb_out.data_ptr() if capacity else None,
             normals_out.data_ptr() if capacity else None, counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
     return xyz_out, rgb_out, normals_out, counts
+
+
+# ---- statistical outlier removal (include/mvs_outliers_abi.h, csrc/cloud_outliers.hip) ----
+OUTLIERS_BLOCK, OUTLIERS_SCALARS = 1024, 64     # MVS_OUTLIERS_BLOCK, MVS_OUTLIERS_SCALARS
+
+
+def query_outliers_workspace(P, box_min, box_max, cell) -> int:
+    lo, hi = _box_arg(box_min, box_max, "query_outliers_workspace")
+    return _query("mvs_query_outliers_workspace", int(P), ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+
+
+def cloud_outliers(xyz, box_min, box_max, cell=5.0, nb_neighbors=20, std_ratio=2.0, masked=False, out=None):
+    """Statistical outlier removal among the points of the cloud inside the box (the reference's
+    pcd.remove_statistical_outlier(), eval.py:495, as include/mvs_outliers_abi.h defines it), on the device.
+
+    xyz float32 or float64 [P,3]; box_min, box_max: 3 host numbers each; cell: the search grid's cell edge (it changes the
+    time, never the result).  Returns (dist float64 [P]: the mean distance to the nb_neighbors nearest points inside the box,
+    -1 outside it, keep bool [P]: True where dist is positive and below mean + std_ratio * std, xyz_masked of xyz's dtype
+    [P,3] or None: the kept points, NaN elsewhere, counts int64 [3]: points inside the box, valid ones, kept ones, stats
+    float64 [3]: mean, std, threshold), all on the device.  `out` = (dist, keep, xyz_masked or None, counts, stats)
+    receives the results.  Enqueued on the current stream; nothing synchronises."""
+    xyz = _cloud_xyz(xyz, "cloud_outliers")
+    dev = xyz.device
+    P, nb, ratio = xyz.shape[0], int(nb_neighbors), float(std_ratio)
+    lo, hi = _box_arg(box_min, box_max, "cloud_outliers")
+    nbytes = _query("mvs_query_outliers_workspace", P, ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+    with torch.cuda.device(dev):
+        if out is None:
+            dist = torch.empty((P,), dtype=torch.float64, device=dev)
+            keep = torch.empty((P,), dtype=torch.bool, device=dev)      # the library writes bytes 0 and 1
+            xyz_masked = torch.empty((P, 3), dtype=xyz.dtype, device=dev) if masked else None
+            counts = torch.empty((3,), dtype=torch.int64, device=dev)
+            stats = torch.empty((3,), dtype=torch.float64, device=dev)
+        else:
+            dist, keep, xyz_masked, counts, stats = out
+            for t, shape, dt, name in ((dist, (P,), torch.float64, "dist"), (keep, (P,), torch.bool, "keep"),
+                                       (counts, (3,), torch.int64, "counts"), (stats, (3,), torch.float64, "stats")):
+                _check_out(t, shape, dt, dev, f"cloud_outliers: out {name}", f"{dt} {shape} tensor on {dev}")
+            if xyz_masked is not None:
+                _check_out(xyz_masked, (P, 3), xyz.dtype, dev, "cloud_outliers: out xyz_masked",
+                           f"{xyz.dtype} {(P, 3)} tensor on {dev}")
+                if P and xyz_masked.data_ptr() == xyz.data_ptr():
+                    raise RuntimeError("cloud_outliers: out xyz_masked must not alias xyz")
+        if P == 0:          # an empty tensor has no address to hand over: the zeros of the header's P == 0
+            if not 2 <= nb <= NORMALS_KNN_MAX:
+                raise RuntimeError(f"cloud_outliers: nb_neighbors = {nb} (need 2 <= nb_neighbors <= {NORMALS_KNN_MAX})")
+            if not (0.0 < ratio < float("inf")):
+                raise RuntimeError(f"cloud_outliers: std_ratio = {ratio} (need a finite ratio > 0)")
+            counts.zero_()
+            stats.zero_()
+            return dist, keep, xyz_masked, counts, stats
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(load().mvs_cloud_outliers(xyz.data_ptr(), MVS_CLOUD_F64 if xyz.dtype == torch.float64 else MVS_CLOUD_F32, P,
+                                        ctypes.addressof(lo), ctypes.addressof(hi), float(cell), nb, ratio, dist.data_ptr(),
+                                        keep.data_ptr(), None if xyz_masked is None else xyz_masked.data_ptr(),
+                                        counts.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return dist, keep, xyz_masked, counts, stats
 
 
 # ---- FeatureNet (reference models/mvsnet.py:10-30) -------------------------------------------

@@ -1,0 +1,415 @@
+// cloud_knn.h -- the exact k-nearest-neighbour search among the points of a cloud inside a box, shared by
+// cloud_normals.hip (mvs_cloud_normals) and cloud_outliers.hip (mvs_cloud_outliers): the cell grid and the ring search, as
+// include/mvs_normals_abi.h describes them.  Each user adds its own classify kernel (what a non-member gets) around
+// knn_classify and its own search kernel (what is done with the neighbours) around knn_search.
+//
+// The box bounds a dense grid of `cell`-sized cells.  Launches, ordered by the stream alone:
+//   hipMemsetAsync          the cell counters (knn_build_begin)
+//   the user's classify     one thread per point: knn_classify adds a member to its cell and to the count of members
+//   knn_tile_sum_kernel, knn_tile_scan_kernel <<<1>>>, knn_cell_scan_kernel
+//                           the cell counts become exclusive offsets, in place
+//   knn_scatter_kernel      one thread per member: claims the next slot of its cell (which turns the cell's offset into its
+//                           END) and writes its index and its point, as doubles, there (all four: knn_build_finish)
+//   the user's search       one WAVE per member, kKnnPerWave members in turn: knn_search, see below
+// The order of the points inside a cell is whatever the atomics gave.  It cannot reach the output: the neighbours are the
+// first min(knn, M) of a TOTAL order, (d2, index), every candidate that could be among them is examined, and the users' sums
+// run over them in that order.
+//
+// The search keeps the 64 best candidates so far sorted over the 64 lanes of the wave, lane j holding the j-th: no array a
+// thread would index dynamically, no LDS, no scratch.  A batch of 64 candidates is loaded one per lane; the lanes whose
+// candidate beats the current knn-th are found with a ballot, and each of those is inserted in turn: its rank is the
+// population count of a ballot, the lanes behind it shift up by one.  Rings of cells are taken in Chebyshev order around
+// the member's cell; the (z, y) rows of a ring are looked up 64 at a time, one per lane, so the latency of the offset
+// loads is paid once per 64 rows and empty rows cost nothing more.  After ring r the examined cells form a block; whatever
+// lies outside it is at least as far as the block's nearest face that is not also the grid's, less a slack of
+// kKnnSlack cells + 2^-48 of the box's largest coordinate: the index of a point is the floor of a quotient that is off
+// by at most 2^-52 of itself, i.e. by less than 2^-21 cells on a grid of fewer than 2^31, and a face bmin + k * cell is
+// computed to 2^-52 of the box's largest coordinate, so the slack is conservative many times over.  The search ends when
+// the knn-th candidate is strictly nearer than that, or when no face is left.
+// Both users are compiled with -ffp-contract=off: d2 and the cell index are the header's fp64 restatement.
+// The kernels here are static: each of the two translation units carries its own copy.
+#pragma once
+
+#include "mvs_normals_abi.h"
+#include "mvs_internal.h"
+
+#include <climits>
+#include <cmath>
+
+namespace mvs {
+
+constexpr int kKnnThreads = 256;
+constexpr int kKnnWaves = kKnnThreads / 64;
+constexpr int kKnnPerWave = 8;                    // members one wave of a search kernel serves
+constexpr int kKnnTile = MVS_NORMALS_TILE;        // cells per block of the two tile kernels: 4 per thread
+constexpr int kKnnScanWidth = 1024;
+constexpr double kKnnSlack = 1e-3;                // of a cell, see above
+static_assert(MVS_NORMALS_KNN_MAX == 64, "one candidate per lane");
+static_assert(kKnnTile == 4 * kKnnThreads, "four cells per thread");
+
+struct KnnGrid {
+    const void* xyz;
+    double* sxyz;                  // [P][3]: the members' points, cell by cell
+    int* sidx;                     // [P]: their indices
+    int* cells_end;                // [cells]: counts, then exclusive offsets, then (after the scatter) each cell's end
+    int* tiles;                    // [n_tiles + 1]
+    double bmin[3], bmax[3];
+    double cell;
+    double slack;                  // what a face of the examined block is pulled in by: kKnnSlack cells + 2^-48 of the box
+    int P, knn;
+    int n[3];
+    int cells, n_tiles;
+};
+
+template <typename T>
+__device__ __forceinline__ bool knn_load(const KnnGrid& G, int i, double p[3]) {
+    const T* src = static_cast<const T*>(G.xyz) + (size_t)i * 3;
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        p[a] = (double)src[a];
+        in = in && G.bmin[a] <= p[a] && p[a] <= G.bmax[a];      // false for NaN
+    }
+    return in;
+}
+
+// the header's cell of a member; at most n - 1 by the header's argument, the clamp only keeps an access inside the grid
+__device__ __forceinline__ void knn_cell(const KnnGrid& G, const double p[3], int c[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double k = floor((p[a] - G.bmin[a]) / G.cell);
+        c[a] = k >= (double)(G.n[a] - 1) ? G.n[a] - 1 : k > 0.0 ? (int)k : 0;
+    }
+}
+__device__ __forceinline__ int knn_linear(const KnnGrid& G, int x, int y, int z) {
+    return (z * G.n[1] + y) * G.n[0] + x;      // < cells < 2^31
+}
+
+// the body of a classify kernel of kKnnThreads threads, one per point, called by every thread of the block: is point i a
+// member?  A member is counted into its cell, and the members of each wave into *members, with integer atomics.
+template <typename T>
+__device__ __forceinline__ bool knn_classify(const KnnGrid& G, long long i, long long* members) {
+    double p[3];
+    const bool member = i < G.P && knn_load<T>(G, (int)i, p);
+    if (member) {
+        int c[3];
+        knn_cell(G, p, c);
+        __hip_atomic_fetch_add(&G.cells_end[knn_linear(G, c[0], c[1], c[2])], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const int count = __popcll(__ballot(member));
+    if ((threadIdx.x & 63) == 0 && count)
+        __hip_atomic_fetch_add(members, (long long)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return member;
+}
+
+__device__ __forceinline__ int knn_count(const KnnGrid& G, long long cell) {
+    return cell < G.cells ? G.cells_end[cell] : 0;
+}
+
+static __global__ void __launch_bounds__(kKnnThreads) knn_tile_sum_kernel(KnnGrid G) {
+    __shared__ int wave_sum[kKnnWaves];
+    const long long base = (long long)blockIdx.x * kKnnTile + 4 * threadIdx.x;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += knn_count(G, base + k);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+#pragma unroll
+        for (int wv = 0; wv < kKnnWaves; ++wv) t += wave_sum[wv];
+        G.tiles[blockIdx.x] = t;
+    }
+}
+
+// exclusive scan of the tile sums with a running carry (the pattern of cloud_scan_kernel); tiles[n_tiles] = M
+static __global__ void __launch_bounds__(kKnnScanWidth) knn_tile_scan_kernel(KnnGrid G) {
+    __shared__ int wave_total[kKnnScanWidth / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int carry = 0;
+    for (long long base = 0; base < G.n_tiles; base += kKnnScanWidth) {
+        const long long i = base + tid;
+        const int v = i < G.n_tiles ? G.tiles[i] : 0;
+        int incl = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(incl, off);
+            if (lane >= off) incl += up;
+        }
+        if (lane == 63) wave_total[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int wv = 0; wv < kKnnScanWidth / 64; ++wv) {
+            const int c = wave_total[wv];
+            before += wv < wave ? c : 0;
+            total += c;
+        }
+        if (i < G.n_tiles) G.tiles[i] = carry + before + incl - v;
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) G.tiles[G.n_tiles] = carry;
+}
+
+static __global__ void __launch_bounds__(kKnnThreads) knn_cell_scan_kernel(KnnGrid G) {
+    __shared__ int wave_total[kKnnWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long base = (long long)blockIdx.x * kKnnTile + 4 * threadIdx.x;
+    int v[4], mine = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        v[k] = knn_count(G, base + k);
+        mine += v[k];
+    }
+    int incl = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(incl, off);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    int run = G.tiles[blockIdx.x] + incl - mine;
+#pragma unroll
+    for (int wv = 0; wv < kKnnWaves; ++wv) run += wv < wave ? wave_total[wv] : 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (base + k < G.cells) G.cells_end[base + k] = run;
+        run += v[k];
+    }
+}
+
+template <typename T>
+static __global__ void __launch_bounds__(kKnnThreads) knn_scatter_kernel(KnnGrid G) {
+    const long long i = (long long)blockIdx.x * kKnnThreads + threadIdx.x;
+    double p[3];
+    if (i >= G.P || !knn_load<T>(G, (int)i, p)) return;
+    int c[3];
+    knn_cell(G, p, c);
+    const int slot = __hip_atomic_fetch_add(&G.cells_end[knn_linear(G, c[0], c[1], c[2])], 1, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+    if (slot < 0 || slot >= G.P) return;       // cannot happen: the classify pass counted this very point into this very cell
+    G.sidx[slot] = (int)i;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) G.sxyz[(size_t)slot * 3 + a] = p[a];
+}
+
+// ---- wave-level helpers: values that are the same in every lane are read with readlane, `lane` wave-uniform
+__device__ __forceinline__ int lane_int(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+__device__ __forceinline__ double lane_double(double v, int lane) {
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)b >> 32), lane);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ bool key_less(double d2a, int ia, double d2b, int ib) {
+    return d2a < d2b || (d2a == d2b && ia < ib);
+}
+
+// the sorted list of the 64 best: lane j holds the j-th smallest (d2, idx); (inf, INT_MAX) where nothing is yet
+struct KnnList {
+    double d2;
+    int idx;
+    double kth_d2;     // the knn-th entry, the same in every lane
+    int kth_idx;
+};
+
+// the candidates [a, b) of the sorted arrays against the list.  The clamps and the index test cannot bite (the offsets
+// are a scan of the very counts the scatter fills); they keep every access inside the buffers whatever the offsets hold.
+__device__ __forceinline__ void knn_take(const KnnGrid& G, KnnList& L, const double p[3], int a, int b) {
+    const int lane = threadIdx.x & 63;
+    a = a < 0 ? 0 : a;
+    b = b > G.P ? G.P : b;
+    for (int base = a; base < b; base += 64) {
+        const int j = base + lane;
+        double d2 = INFINITY;
+        int idx = INT_MAX;
+        if (j < b) {
+            const double* q = G.sxyz + (size_t)j * 3;
+            const double dx = q[0] - p[0], dy = q[1] - p[1], dz = q[2] - p[2];
+            d2 = (dx * dx + dy * dy) + dz * dz;
+            idx = G.sidx[j];
+        }
+        const bool real = j < b && idx >= 0 && idx < G.P;
+        unsigned long long better = __ballot(real && key_less(d2, idx, L.kth_d2, L.kth_idx));
+        while (better) {
+            const int src = __builtin_ctzll(better);
+            better &= better - 1;
+            const double cd = lane_double(d2, src);
+            const int ci = lane_int(idx, src);
+            if (!key_less(cd, ci, L.kth_d2, L.kth_idx)) continue;      // the list has moved on since the ballot
+            const int pos = __popcll(__ballot(key_less(L.d2, L.idx, cd, ci)));
+            const double up_d2 = __shfl_up(L.d2, 1);
+            const int up_idx = __shfl_up(L.idx, 1);
+            if (lane > pos) {
+                L.d2 = up_d2;
+                L.idx = up_idx;
+            } else if (lane == pos) {
+                L.d2 = cd;
+                L.idx = ci;
+            }
+            L.kth_d2 = lane_double(L.d2, G.knn - 1);
+            L.kth_idx = lane_int(L.idx, G.knn - 1);
+        }
+    }
+}
+
+// first slot of cell `lin` after the scatter: the end of the cell before it
+__device__ __forceinline__ int knn_begin(const KnnGrid& G, int lin) { return lin > 0 ? G.cells_end[lin - 1] : 0; }
+
+// M as the tile scan left it, never more than P
+__device__ __forceinline__ int knn_members(const KnnGrid& G) { return G.tiles[G.n_tiles] < G.P ? G.tiles[G.n_tiles] : G.P; }
+
+// The ring search for the member at p, called by a whole wave with p wave-uniform.  On return lane j of L holds the j-th
+// smallest (d2, idx) over ALL members for j < min(knn, M); the lanes behind hold whatever else was seen, or (inf, INT_MAX).
+__device__ __forceinline__ void knn_search(const KnnGrid& G, const double p[3], KnnList& L) {
+    const int lane = threadIdx.x & 63;
+    int c[3];
+    knn_cell(G, p, c);
+    L = KnnList{INFINITY, INT_MAX, INFINITY, INT_MAX};
+    for (int r = 0;; ++r) {
+        // the ring's block of cells, clipped to the grid.  r stays below the longest axis (the loop ends once the block
+        // covers the grid) and every test is written so that no sum of two of c, r and n is formed unless it fits
+        const int x0 = c[0] - r > 0 ? c[0] - r : 0, x1 = r < G.n[0] - 1 - c[0] ? c[0] + r : G.n[0] - 1;
+        const int y0 = c[1] - r > 0 ? c[1] - r : 0, y1 = r < G.n[1] - 1 - c[1] ? c[1] + r : G.n[1] - 1;
+        const int z0 = c[2] - r > 0 ? c[2] - r : 0, z1 = r < G.n[2] - 1 - c[2] ? c[2] + r : G.n[2] - 1;
+        const int hy = y1 - y0 + 1, rows = (z1 - z0 + 1) * hy;       // <= cells
+        for (int row = 0; row < rows; row = rows - row > 64 ? row + 64 : rows) {
+            // lane -> one (z, y) row of the block: the whole x span on the ring's z and y faces, its two end cells else
+            const int q = lane < rows - row ? row + lane : row;       // never past rows: it may be close to 2^31
+            const int z = z0 + q / hy, y = y0 + q % hy;
+            const int dz = z - c[2], dy = y - c[1];
+            int a0 = 0, b0 = 0, a1 = 0, b1 = 0;
+            if (lane < rows - row) {
+                const int line = knn_linear(G, 0, y, z);
+                if (dz == -r || dz == r || dy == -r || dy == r) {
+                    a0 = knn_begin(G, line + x0);
+                    b0 = G.cells_end[line + x1];
+                } else {
+                    if (c[0] - r >= 0) {
+                        a0 = knn_begin(G, line + c[0] - r);
+                        b0 = G.cells_end[line + c[0] - r];
+                    }
+                    if (r < G.n[0] - c[0]) {
+                        a1 = knn_begin(G, line + c[0] + r);
+                        b1 = G.cells_end[line + c[0] + r];
+                    }
+                }
+            }
+            unsigned long long busy = __ballot(b0 > a0);
+            while (busy) {
+                const int src = __builtin_ctzll(busy);
+                busy &= busy - 1;
+                knn_take(G, L, p, lane_int(a0, src), lane_int(b0, src));
+            }
+            busy = __ballot(b1 > a1);
+            while (busy) {
+                const int src = __builtin_ctzll(busy);
+                busy &= busy - 1;
+                knn_take(G, L, p, lane_int(a1, src), lane_int(b1, src));
+            }
+        }
+        // the nearest face of the examined block that has cells behind it
+        double face = INFINITY;
+        bool open = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            if (c[a] - r > 0) {
+                const double d = p[a] - (G.bmin[a] + (double)(c[a] - r) * G.cell);
+                face = d < face ? d : face;
+                open = true;
+            }
+            if (r < G.n[a] - 1 - c[a]) {
+                const double d = (G.bmin[a] + (double)(c[a] + r + 1) * G.cell) - p[a];      // c + r + 1 <= n - 1
+                face = d < face ? d : face;
+                open = true;
+            }
+        }
+        if (!open) break;
+        const double safe = face - G.slack;
+        if (safe > 0.0 && L.kth_d2 < safe * safe) break;
+    }
+}
+
+// ---- host side
+// n[a] and their product; BAD_SHAPE for anything the header refuses about P, the box and the cell
+static int knn_check(const char* who, long long P, const double* bmin, const double* bmax, double cell, int n[3],
+                     long long* cells) {
+    if (P < 0 || P >= (1LL << 31)) return fail(MVS_ERR_BAD_SHAPE, "%s: P = %lld (need 0 <= P < 2^31)", who, P);
+    if (!std::isfinite(cell) || cell <= 0.0)
+        return fail(MVS_ERR_BAD_SHAPE, "%s: cell = %g (need a finite size > 0)", who, cell);
+    long long c = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(bmin[a]) || !std::isfinite(bmax[a]) || bmin[a] > bmax[a])
+            return fail(MVS_ERR_BAD_SHAPE, "%s: box axis %d is [%g, %g] (need finite bounds, min <= max)", who, a, bmin[a],
+                        bmax[a]);
+        const double na = std::floor((bmax[a] - bmin[a]) / cell) + 1.0;
+        if (!(na < 2147483648.0))          // also an infinite quotient
+            return fail(MVS_ERR_BAD_SHAPE, "%s: axis %d needs %g cells (the grid must have fewer than 2^31 cells)", who, a, na);
+        n[a] = (int)na;
+        c *= n[a];                         // < 2^31 before this factor, so < 2^62 after it
+        if (c >= (1LL << 31))
+            return fail(MVS_ERR_BAD_SHAPE, "%s: the grid of the box at cell %g has 2^31 cells or more", who, cell);
+    }
+    *cells = c;
+    return MVS_OK;
+}
+
+static long long knn_tiles(long long cells) { return (cells + kKnnTile - 1) / kKnnTile; }
+// mvs_query_normals_workspace: the sorted points and indices, the cells, the tiles
+static size_t knn_workspace(long long P, long long cells) {
+    return 24 * (size_t)P + 8 * (size_t)((P + 1) / 2) + 8 * (size_t)((cells + 1) / 2) + 8 * (size_t)((knn_tiles(cells) + 2) / 2);
+}
+
+// G over a workspace of knn_workspace(P, cells) bytes, for a box and a cell that passed knn_check
+static void knn_bind(KnnGrid& G, const void* xyz, long long P, const double* box_min, const double* box_max, double cell,
+                     int knn, const int n[3], long long cells, void* workspace) {
+    G.xyz = xyz;
+    char* ws = static_cast<char*>(workspace);
+    G.sxyz = reinterpret_cast<double*>(ws);
+    G.sidx = reinterpret_cast<int*>(ws + 24 * (size_t)P);
+    G.cells_end = reinterpret_cast<int*>(ws + 24 * (size_t)P + 8 * (size_t)((P + 1) / 2));
+    G.tiles = reinterpret_cast<int*>(reinterpret_cast<char*>(G.cells_end) + 8 * (size_t)((cells + 1) / 2));
+    for (int a = 0; a < 3; ++a) {
+        G.bmin[a] = box_min[a];
+        G.bmax[a] = box_max[a];
+        G.n[a] = n[a];
+    }
+    G.cell = cell;
+    double far = 0.0;
+    for (int a = 0; a < 3; ++a) far = std::fmax(far, std::fmax(std::fabs(box_min[a]), std::fabs(box_max[a])));
+    G.slack = kKnnSlack * cell + far * 0x1p-48;
+    G.P = (int)P;
+    G.knn = knn;
+    G.cells = (int)cells;
+    G.n_tiles = (int)knn_tiles(cells);
+}
+
+static int knn_point_blocks(const KnnGrid& G) { return (int)(((long long)G.P + kKnnThreads - 1) / kKnnThreads); }
+static int knn_search_blocks(const KnnGrid& G) {
+    const int per_block = kKnnWaves * kKnnPerWave;
+    return (int)(((long long)G.P + per_block - 1) / per_block);
+}
+
+// before the user's classify kernel (P > 0)
+static int knn_build_begin(const KnnGrid& G, hipStream_t s) {
+    return check_hip(hipMemsetAsync(G.cells_end, 0, sizeof(int) * (size_t)G.cells, s), "zeroing the cell counts");
+}
+
+// after it: offsets, then the scatter
+static int knn_build_finish(const KnnGrid& G, bool f64, hipStream_t s) {
+    knn_tile_sum_kernel<<<G.n_tiles, kKnnThreads, 0, s>>>(G);
+    if (int rc = check_hip(hipGetLastError(), "knn_tile_sum_kernel")) return rc;
+    knn_tile_scan_kernel<<<1, kKnnScanWidth, 0, s>>>(G);
+    if (int rc = check_hip(hipGetLastError(), "knn_tile_scan_kernel")) return rc;
+    knn_cell_scan_kernel<<<G.n_tiles, kKnnThreads, 0, s>>>(G);
+    if (int rc = check_hip(hipGetLastError(), "knn_cell_scan_kernel")) return rc;
+    if (f64) knn_scatter_kernel<double><<<knn_point_blocks(G), kKnnThreads, 0, s>>>(G);
+    else knn_scatter_kernel<float><<<knn_point_blocks(G), kKnnThreads, 0, s>>>(G);
+    return check_hip(hipGetLastError(), "knn_scatter_kernel");
+}
+
+}  // namespace mvs

@@ -12,6 +12,8 @@ datasets (eval.py:831-840: crop to the bin's outer box `bin_box`, voxel_down_sam
 (mvs_cloud_downsample); `reconstruct_scan(..., downsample=...)` appends it to the chain.  `estimate_normals` is
 eval.py:817's pcd.estimate_normals() on the device (mvs_cloud_normals, include/mvs_normals_abi.h); the reference runs it
 before the crop and the voxel filter, which carry the normals along, and so does `downsample=dict(normals=...)`.
+`remove_outliers` is eval.py:495's pcd.remove_statistical_outlier() on the device (mvs_cloud_outliers,
+include/mvs_outliers_abi.h), between the crop and the voxel filter: `downsample=dict(outliers=...)`, off by default.
 
 Differences from the reference, flagged rather than hidden:
   * cv2.remap is restated inside the kernel (1/32-pixel quantised bilinear, zero border); OpenCV is
@@ -24,6 +26,9 @@ Differences from the reference, flagged rather than hidden:
     leaves it to its eigen-solver; only points inside a box are served, and the points whose neighbourhood a point
     outside the box could have changed are counted; the PLY's nx, ny, nz are float32 where Open3D writes doubles;
     the covariance is centred.  Open3D is not installed here: nothing was compared against it.
+  * outliers: the reference drops the result of remove_statistical_outlier, so its cloud is unfiltered; here the step,
+    when asked for, filters.  Ties, the order of every sum and the cases of fewer than two valid points are specified
+    (INTEGRATION.md §6.4).
 """
 from __future__ import annotations
 
@@ -257,6 +262,25 @@ def estimate_normals(xyz, knn=30, box=None, cell=5.0, view_counts=None, centres=
     return (normals, n, nbr) if return_neighbours else (normals, n)
 
 
+def remove_outliers(xyz, nb_neighbors=20, std_ratio=2.0, box=None, cell=5.0, masked=False):
+    """eval.py:495's pcd.remove_statistical_outlier() on the device (mvs_cloud_outliers), among the points of xyz (float32
+    or float64 [P,3], on the GPU) inside `box` = (min, max), default bin_box(): the reference crops first.  A point is kept
+    iff it lies inside the box, its mean distance to its `nb_neighbors` nearest points there (itself among them) is positive,
+    and that distance is below mean + std_ratio * std of those distances over the box.  cell: the search grid's cell edge,
+    in the cloud's units -- it changes the time, never the result.
+    Returns (keep bool [P], dist float64 [P]: the mean distances, -1 outside the box, counts int64 [3]: points inside the
+    box, those with a positive distance, those kept, stats float64 [3]: mean, std, threshold), all on the device; nothing
+    synchronises.  With masked=True a fifth item follows: xyz_masked, xyz with NaN in the rows that are not kept, which
+    `downsample_cloud` and `estimate_normals` take in place of xyz (NaN points fall out of both) with colours and normals
+    as they are; `xyz[keep]` is the compacted cloud."""
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise RuntimeError("remove_outliers: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    lo, hi = bin_box() if box is None else box
+    dist, keep, xyz_masked, counts, stats = _lib.cloud_outliers(xyz, lo, hi, cell=cell, nb_neighbors=nb_neighbors,
+                                                                std_ratio=std_ratio, masked=masked)
+    return (keep, dist, counts, stats, xyz_masked) if masked else (keep, dist, counts, stats)
+
+
 def downsample_cloud(xyz, rgb, voxel_size=5.0, box=None, scale=0.01, capacity=None, normals=None):
     """eval.py:831-840 on the device: crop the cloud to `box` = (min, max) (default bin_box(), in the cloud's units), keep
     the mean point and colour of every occupied voxel of size `voxel_size`, scale the coordinates.  xyz float32 or
@@ -303,21 +327,32 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
     carries them, the small PLY gets nx, ny, nz, and the return gains two items: ds_normals float32 [Q,3] and the three
     counts of estimate_normals as a numpy array -- the last is the number of points inside the grown box that a point
     outside it could have served better.  The default margin is a guess (the reach of 30 neighbours on a dense scan),
-    not measured on a real bin scan: watch that count."""
+    not measured on a real bin scan: watch that count.
+    downsample=dict(..., outliers=dict(nb_neighbors=20, std_ratio=2.0, cell=5.0)) runs `remove_outliers` among the points
+    inside the crop box between the normals (of the whole fused cloud, if asked for) and the voxel downsample, eval.py's
+    order (817, 494-496); the downsample takes the masked cloud and the normals as they are.  The return gains one last
+    item: dict(counts int64 [3], stats float64 [3], keep bool [P]) as numpy arrays, keep over the fused cloud."""
     import copy
-    normals_opt = None
+    normals_opt = outliers_opt = None
     if downsample is not None:
         downsample = dict(downsample)
         ds_ply = downsample.pop("plyfilename", None)
         normals_opt = downsample.pop("normals", None)
+        outliers_opt = downsample.pop("outliers", None)
         unknown = set(downsample) - {"voxel_size", "box", "scale"}
         if unknown:
-            raise ValueError(f"downsample: unknown keys {sorted(unknown)} (voxel_size, box, scale, plyfilename, normals)")
+            raise ValueError(f"downsample: unknown keys {sorted(unknown)} (voxel_size, box, scale, plyfilename, normals, "
+                             "outliers)")
         if normals_opt is not None:
             normals_opt = dict(dict(knn=30, margin=20.0, cell=5.0), **normals_opt)
             unknown = set(normals_opt) - {"knn", "margin", "cell"}
             if unknown:
                 raise ValueError(f"downsample['normals']: unknown keys {sorted(unknown)} (knn, margin, cell)")
+        if outliers_opt is not None:
+            outliers_opt = dict(dict(nb_neighbors=20, std_ratio=2.0, cell=5.0), **outliers_opt)
+            unknown = set(outliers_opt) - {"nb_neighbors", "std_ratio", "cell"}
+            if unknown:
+                raise ValueError(f"downsample['outliers']: unknown keys {sorted(unknown)} (nb_neighbors, std_ratio, cell)")
     for a in ("view_plan", "decode_view", "assemble", "metas"):
         if not hasattr(dataset, a):
             raise ValueError("reconstruct_scan needs a dataset with metas, view_plan(), decode_view() and assemble(), "
@@ -392,6 +427,7 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
         filtered = filter_views(depths, confs, Ks, Es, pairs, n_view_filter, photomask, geomask, condmask_pixel,
                                 condmask_depth, device)
         xyz, rgb, view_counts = fuse_views(filtered, imgs, [slot[r] for r in refs])
+        normals = None
         if normals_opt is not None:
             lo, hi = bin_box() if downsample.get("box") is None else downsample["box"]
             grown = (np.asarray(lo, np.float64) - normals_opt["margin"], np.asarray(hi, np.float64) + normals_opt["margin"])
@@ -399,20 +435,28 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
             centres = -np.einsum("rji,rj->ri", E[:, :3, :3], E[:, :3, 3])          # -R^T t
             normals, normal_counts = estimate_normals(xyz, knn=normals_opt["knn"], box=grown, cell=normals_opt["cell"],
                                                       view_counts=view_counts, centres=centres)
-            ds_xyz, ds_rgb, ds_nrm = downsample_cloud(xyz, rgb, normals=normals, **downsample)
+        ds_in = xyz
+        if outliers_opt is not None:
+            keep, _, out_counts, out_stats, ds_in = remove_outliers(xyz, box=downsample.get("box"), masked=True,
+                                                                    **outliers_opt)
+        if normals_opt is not None:
+            ds_xyz, ds_rgb, ds_nrm = downsample_cloud(ds_in, rgb, normals=normals, **downsample)
             ds_vertices, ds_colours = _packed_to_host(ds_xyz, ds_rgb)
             ds_normals, normal_counts = ds_nrm.cpu().numpy(), normal_counts.cpu().numpy()
         elif downsample is not None:
-            ds_vertices, ds_colours = _packed_to_host(*downsample_cloud(xyz, rgb, **downsample))
+            ds_vertices, ds_colours = _packed_to_host(*downsample_cloud(ds_in, rgb, **downsample))
+        if outliers_opt is not None:
+            outliers = dict(counts=out_counts.cpu().numpy(), stats=out_stats.cpu().numpy(), keep=keep.cpu().numpy())
         vertices, colours = _packed_to_host(xyz, rgb)      # the one copy of the full cloud
     if plyfilename:
         write_ply(plyfilename, vertices, colours)
     if downsample is None:
         return vertices, colours
+    tail = () if outliers_opt is None else (outliers,)
     if normals_opt is None:
         if ds_ply:
             write_ply(ds_ply, ds_vertices, ds_colours)
-        return vertices, colours, ds_vertices, ds_colours
+        return (vertices, colours, ds_vertices, ds_colours) + tail
     if ds_ply:
         write_ply(ds_ply, ds_vertices, ds_colours, ds_normals)
-    return vertices, colours, ds_vertices, ds_colours, ds_normals, normal_counts
+    return (vertices, colours, ds_vertices, ds_colours, ds_normals, normal_counts) + tail

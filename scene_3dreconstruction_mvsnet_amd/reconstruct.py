@@ -15,7 +15,9 @@ the bin's outer box, voxel-downsampled at V and scaled by --cloud_scale on the d
 OUT/<scan>/fused_dwnsmpld_<V>mm.ply, eval.py's name and place.  The box is --crop_box x0 y0 z0 x1 y1 z1 (in the cloud's
 units), or the bin of --bin_dims / --bin_delta (metres, fusion.bin_box).  --normals_knn K (with --downsample_mm) adds
 eval.py:817's estimate_normals: normals from K neighbours inside the box grown by --normals_margin_mm, turned towards each
-point's camera, carried through the voxel filter and written as nx, ny, nz.
+point's camera, carried through the voxel filter and written as nx, ny, nz.  --outlier_knn K (with --downsample_mm) adds
+eval.py:495's remove_statistical_outlier between the crop and the voxel filter: a point of the box whose mean distance to
+its K nearest neighbours there is not below mean + --outlier_std standard deviations of those distances is dropped.
 """
 from __future__ import annotations
 
@@ -68,11 +70,17 @@ def main(argv=None):
     p.add_argument("--normals_margin_mm", type=float, default=20.0,
                    help="the neighbour search covers the box grown by this much (a guess; the tool prints how many points "
                         "a point outside could have served better)")
+    p.add_argument("--outlier_knn", type=int, default=None, metavar="K",
+                   help="with --downsample_mm: drop statistical outliers from K neighbours (eval.py:495) before the voxel filter")
+    p.add_argument("--outlier_std", type=float, default=2.0, metavar="S",
+                   help="a point is kept while its mean neighbour distance is below mean + S standard deviations")
     args = p.parse_args(argv)
     if args.downsample_mm is None and args.crop_box is not None:
         p.error("--crop_box needs --downsample_mm")
     if args.downsample_mm is None and args.normals_knn is not None:
         p.error("--normals_knn needs --downsample_mm")
+    if args.downsample_mm is None and args.outlier_knn is not None:
+        p.error("--outlier_knn needs --downsample_mm")
     box = None
     if args.downsample_mm is not None:
         box = (args.crop_box[:3], args.crop_box[3:]) if args.crop_box else bin_box(args.bin_dims, args.bin_delta)
@@ -93,6 +101,8 @@ def main(argv=None):
             downsample = dict(voxel_size=args.downsample_mm, box=box, scale=args.cloud_scale, plyfilename=small)
             if args.normals_knn is not None:
                 downsample["normals"] = dict(knn=args.normals_knn, margin=args.normals_margin_mm)
+            if args.outlier_knn is not None:
+                downsample["outliers"] = dict(nb_neighbors=args.outlier_knn, std_ratio=args.outlier_std)
         got = reconstruct_scan(model, ds, scan, n_view_filter=args.NviewFilter, photomask=args.photomask,
                                geomask=args.geomask, condmask_pixel=args.condmask_pixel,
                                condmask_depth=args.condmask_depth, plyfilename=ply, downsample=downsample)
@@ -105,6 +115,10 @@ def main(argv=None):
                 members, estimated, open_ = (int(x) for x in got[5])
                 print(f"{scan}: normals of {estimated} of {members} points in the grown box; {open_} of them could have "
                       f"had a nearer neighbour outside it")
+            if args.outlier_knn is not None:
+                members, valid, kept = (int(x) for x in got[-1]["counts"])
+                print(f"{scan}: {kept} of {members} points in the box kept ({valid} with a neighbour elsewhere; mean distance "
+                      f"below {got[-1]['stats'][2]:g})")
     return written
 
 
