@@ -53,7 +53,8 @@ extern "C" {
  * mvs_query_fuse_workspace, mvs_fuse_points.
  * Likewise include/mvs_cloud_abi.h: mvs_query_cloud_workspace, mvs_cloud_downsample.
  * Likewise include/mvs_normals_abi.h: point normals of a cloud, and the downsample that carries them.
- * Likewise include/mvs_outliers_abi.h: statistical outlier removal among the points of a cloud inside a box. */
+ * Likewise include/mvs_outliers_abi.h: statistical outlier removal among the points of a cloud inside a box.
+ * Likewise include/mvs_distance_abi.h: the distance from every point of one cloud to the nearest point of another. */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {

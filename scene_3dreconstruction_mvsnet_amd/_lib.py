@@ -53,9 +53,10 @@ _vpp = ctypes.POINTER(_vp)      # const float* const*
 
 # Every entry point, declared once on this side: header -> {name: argument types}, in the headers' order.  Any other
 # pointer is a c_void_p (device and host addresses travel as integers).  load() applies the table; SYMBOLS and
-# FUSE_SYMBOLS, CLOUD_SYMBOLS, NORMALS_SYMBOLS and OUTLIERS_SYMBOLS are its keys; tests/test_host_logic.py,
-# tests/test_scan_fusion_host.py, tests/test_cloud_downsample_host.py, tests/test_cloud_normals_host.py and
-# tests/test_cloud_outliers_host.py hold every argument list to its prototype.  Everything returns int except mvs_last_error_string.
+# FUSE_SYMBOLS, CLOUD_SYMBOLS, NORMALS_SYMBOLS, OUTLIERS_SYMBOLS and DISTANCE_SYMBOLS are its keys; tests/test_host_logic.py,
+# tests/test_scan_fusion_host.py, tests/test_cloud_downsample_host.py, tests/test_cloud_normals_host.py,
+# tests/test_cloud_outliers_host.py and tests/test_cloud_distance_host.py hold every argument list to its prototype.
+# Everything returns int except mvs_last_error_string.
 _ABI = {
     "mvs_abi.h": {
         "mvs_abi_version": [],
@@ -117,12 +118,17 @@ _ABI = {
         "mvs_query_outliers_workspace": [_ll, _vp, _vp, _d, _szp],
         "mvs_cloud_outliers": [_vp, _i, _ll, _vp, _vp, _d, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     },
+    "mvs_distance_abi.h": {
+        "mvs_query_distance_workspace": [_ll, _ll, _vp, _vp, _d, _szp],
+        "mvs_cloud_distance": [_vp, _i, _ll, _vp, _i, _ll, _vp, _vp, _d, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    },
 }
 SYMBOLS = tuple(_ABI["mvs_abi.h"])
 FUSE_SYMBOLS = tuple(_ABI["mvs_fuse_abi.h"])
 CLOUD_SYMBOLS = tuple(_ABI["mvs_cloud_abi.h"])
 NORMALS_SYMBOLS = tuple(_ABI["mvs_normals_abi.h"])
 OUTLIERS_SYMBOLS = tuple(_ABI["mvs_outliers_abi.h"])
+DISTANCE_SYMBOLS = tuple(_ABI["mvs_distance_abi.h"])
 
 
 class MvsError(RuntimeError):
@@ -145,7 +151,7 @@ def load():
                 "g.build()'` (or make -C scene_3dreconstruction_mvsnet_amd/csrc). "
                 "There is no CPU/PyTorch fallback for the MVSNet depth path.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name in SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS + OUTLIERS_SYMBOLS:
+        for name in SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS + OUTLIERS_SYMBOLS + DISTANCE_SYMBOLS:
             if not hasattr(lib, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}")
         for prototypes in _ABI.values():
@@ -959,6 +965,71 @@ def cloud_outliers(xyz, box_min, box_max, cell=5.0, nb_neighbors=20, std_ratio=2
                                         keep.data_ptr(), None if xyz_masked is None else xyz_masked.data_ptr(),
                                         counts.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
     return dist, keep, xyz_masked, counts, stats
+
+
+# ---- cloud-to-cloud distance (include/mvs_distance_abi.h, csrc/cloud_distance.hip) ----
+DISTANCE_THRESHOLDS_MAX, DISTANCE_SCALARS = 8, 64     # MVS_DISTANCE_THRESHOLDS_MAX, MVS_DISTANCE_SCALARS
+
+
+def query_distance_workspace(P, N, box_min, box_max, cell) -> int:
+    lo, hi = _box_arg(box_min, box_max, "query_distance_workspace")
+    return _query("mvs_query_distance_workspace", int(P), int(N), ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+
+
+def cloud_distance(ref, query, box_min, box_max, cell, max_dist, thresholds, indices=False, out=None):
+    """The distance from every point of `query` to the nearest point of `ref` inside the box, its counts and its mean
+    (one direction of accuracy / completeness, as include/mvs_distance_abi.h defines it), on the device.
+
+    ref float32 or float64 [P,3] and query float32 or float64 [N,3] on one device (they may be the same tensor); box_min,
+    box_max: 3 host numbers each, the box of `ref`; cell: the search grid's cell edge (it changes the time, never the
+    result); max_dist >= 0, +inf allowed; thresholds: up to 8 finite host numbers >= 0.  Returns (dist float64 [N]: the
+    distance, +inf where no point of `ref` in the box lies within max_dist, -1 for a query with a non-finite coordinate,
+    idx int32 [N] or None: the nearest point's row in `ref`, -1 where there is none, counts int64 [2 + T]: queries with
+    finite coordinates, those within max_dist, those below each threshold, stats float64 [2]: the sum of the distances
+    within max_dist and their mean), all on the device.  `out` = (dist, idx or None, counts, stats) receives the results.
+    Enqueued on the current stream; nothing synchronises."""
+    import numpy as np
+    ref, query = _cloud_xyz(ref, "cloud_distance"), _cloud_xyz(query, "cloud_distance")
+    dev = ref.device
+    if query.device != dev:
+        raise RuntimeError("cloud_distance: ref and query must be on one device")
+    P, N, cap = ref.shape[0], query.shape[0], float(max_dist)
+    th = np.ascontiguousarray([float(t) for t in thresholds], dtype=np.float64)
+    T = int(th.size)
+    if T > DISTANCE_THRESHOLDS_MAX:
+        raise RuntimeError(f"cloud_distance: {T} thresholds (at most {DISTANCE_THRESHOLDS_MAX})")
+    if not cap >= 0.0:
+        raise RuntimeError(f"cloud_distance: max_dist = {cap} (need max_dist >= 0; +inf is allowed)")
+    if T and not (np.isfinite(th).all() and (th >= 0).all()):
+        raise RuntimeError(f"cloud_distance: thresholds {th.tolist()} (need finite thresholds >= 0)")
+    lo, hi = _box_arg(box_min, box_max, "cloud_distance")
+    nbytes = _query("mvs_query_distance_workspace", P, N, ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+    with torch.cuda.device(dev):
+        if out is None:
+            dist = torch.empty((N,), dtype=torch.float64, device=dev)
+            idx = torch.empty((N,), dtype=torch.int32, device=dev) if indices else None
+            counts = torch.empty((2 + T,), dtype=torch.int64, device=dev)
+            stats = torch.empty((2,), dtype=torch.float64, device=dev)
+        else:
+            dist, idx, counts, stats = out
+            for t, shape, dt, name in ((dist, (N,), torch.float64, "dist"), (counts, (2 + T,), torch.int64, "counts"),
+                                       (stats, (2,), torch.float64, "stats")):
+                _check_out(t, shape, dt, dev, f"cloud_distance: out {name}", f"{dt} {shape} tensor on {dev}")
+            if idx is not None:
+                _check_out(idx, (N,), torch.int32, dev, "cloud_distance: out idx", f"int32 {(N,)} tensor on {dev}")
+        if N == 0:          # an empty tensor has no address to hand over: the zeros of the header's N == 0
+            counts.zero_()
+            stats.zero_()
+            return dist, idx, counts, stats
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        codes = [MVS_CLOUD_F64 if t.dtype == torch.float64 else MVS_CLOUD_F32 for t in (ref, query)]
+        # P == 0: the library does not read ref; it gets the workspace's address in place of an empty tensor's
+        check(load().mvs_cloud_distance(ref.data_ptr() if P else ws.data_ptr(), codes[0], P, query.data_ptr(), codes[1], N,
+                                        ctypes.addressof(lo), ctypes.addressof(hi), float(cell), cap,
+                                        th.ctypes.data if T else None, T, dist.data_ptr(),
+                                        None if idx is None else idx.data_ptr(), counts.data_ptr(), stats.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream(dev)))
+    return dist, idx, counts, stats
 
 
 # ---- FeatureNet (reference models/mvsnet.py:10-30) -------------------------------------------

@@ -1,7 +1,9 @@
 // cloud_knn.h -- the exact k-nearest-neighbour search among the points of a cloud inside a box, shared by
-// cloud_normals.hip (mvs_cloud_normals) and cloud_outliers.hip (mvs_cloud_outliers): the cell grid and the ring search, as
-// include/mvs_normals_abi.h describes them.  Each user adds its own classify kernel (what a non-member gets) around
-// knn_classify and its own search kernel (what is done with the neighbours) around knn_search.
+// cloud_normals.hip (mvs_cloud_normals), cloud_outliers.hip (mvs_cloud_outliers) and cloud_distance.hip
+// (mvs_cloud_distance): the cell grid and the ring search, as include/mvs_normals_abi.h describes them.  Each user adds its
+// own classify kernel (what a non-member gets) around knn_classify and its own search kernel (what is done with the
+// neighbours) around knn_search -- the knn nearest members of a member -- or knn_nearest -- the one nearest member of a
+// point anywhere in space, which is no member of the grid (include/mvs_distance_abi.h).
 //
 // The box bounds a dense grid of `cell`-sized cells.  Launches, ordered by the stream alone:
 //   hipMemsetAsync          the cell counters (knn_build_begin)
@@ -26,8 +28,10 @@
 // by at most 2^-52 of itself, i.e. by less than 2^-21 cells on a grid of fewer than 2^31, and a face bmin + k * cell is
 // computed to 2^-52 of the box's largest coordinate, so the slack is conservative many times over.  The search ends when
 // the knn-th candidate is strictly nearer than that, or when no face is left.
-// Both users are compiled with -ffp-contract=off: d2 and the cell index are the header's fp64 restatement.
-// The kernels here are static: each of the two translation units carries its own copy.
+// All users are compiled with -ffp-contract=off: d2 and the cell index are the header's fp64 restatement.
+// knn_nearest keeps no list: each lane holds the best (d2, index) of the candidates it loaded; a ballot closes every ring
+// and one minimum over the wave the search.  Both searches walk the same rings (knn_walk).
+// The kernels here are static: each translation unit carries its own copy.
 #pragma once
 
 #include "mvs_normals_abi.h"
@@ -44,6 +48,7 @@ constexpr int kKnnPerWave = 8;                    // members one wave of a searc
 constexpr int kKnnTile = MVS_NORMALS_TILE;        // cells per block of the two tile kernels: 4 per thread
 constexpr int kKnnScanWidth = 1024;
 constexpr double kKnnSlack = 1e-3;                // of a cell, see above
+constexpr int kKnnGroup = 16;                     // lanes that share one span in knn_nearest
 static_assert(MVS_NORMALS_KNN_MAX == 64, "one candidate per lane");
 static_assert(kKnnTile == 4 * kKnnThreads, "four cells per thread");
 
@@ -263,13 +268,26 @@ __device__ __forceinline__ int knn_begin(const KnnGrid& G, int lin) { return lin
 // M as the tile scan left it, never more than P
 __device__ __forceinline__ int knn_members(const KnnGrid& G) { return G.tiles[G.n_tiles] < G.P ? G.tiles[G.n_tiles] : G.P; }
 
-// The ring search for the member at p, called by a whole wave with p wave-uniform.  On return lane j of L holds the j-th
-// smallest (d2, idx) over ALL members for j < min(knn, M); the lanes behind hold whatever else was seen, or (inf, INT_MAX).
-__device__ __forceinline__ void knn_search(const KnnGrid& G, const double p[3], KnnList& L) {
+// The rings of cells around the cell of p, in Chebyshev order, called by a whole wave with p wave-uniform.  p may lie
+// anywhere: knn_cell clamps, so a point outside the box starts at the cell nearest to it.  take(a, b) is called by the
+// whole wave with one span [a, b) of the sorted arrays PER LANE (empty where b <= a): the spans that up to 64 rows of ring
+// r add; how the lanes share the work is the user's.  done(safe) closes ring r: every member not yet handed to take() is
+// at least `safe` away from p on one axis (+inf once the block covers the grid), and a true return ends the walk.  `slack` is what a face is pulled in by: G.slack for a point of the box, see knn_nearest
+// for any other.
+//
+// Why `safe` is a lower bound wherever p lies.  After ring r the examined block is [c - r, c + r] per axis, clipped to
+// the grid.  A side of an axis is OPEN when cells lie beyond it.  Low side, open iff c - r > 0: a member beyond it has
+// a cell index below c - r, so its coordinate is below F = bmin + (c - r) * cell (give or take the slack), and p[a] - F
+// bounds its offset from below provided p[a] >= F.  That holds for p inside the box (c is p's own cell) and for p above
+// the box (c = n - 1 and p[a] > bmax >= F); for p below the box c = 0, so the side is never open.  High side, open iff
+// c + r < n - 1, F = bmin + (c + r + 1) * cell: the mirror image, p above the box has c = n - 1 and the side closed, p
+// below the box has p[a] < bmin <= F.  So a clamped axis has its near side closed and its far side farther than the
+// true offset of every member behind it, and the smallest open face remains a lower bound of the distance.
+template <typename Take, typename Done>
+__device__ __forceinline__ void knn_walk(const KnnGrid& G, const double p[3], double slack, Take take, Done done) {
     const int lane = threadIdx.x & 63;
     int c[3];
     knn_cell(G, p, c);
-    L = KnnList{INFINITY, INT_MAX, INFINITY, INT_MAX};
     for (int r = 0;; ++r) {
         // the ring's block of cells, clipped to the grid.  r stays below the longest axis (the loop ends once the block
         // covers the grid) and every test is written so that no sum of two of c, r and n is formed unless it fits
@@ -299,18 +317,8 @@ __device__ __forceinline__ void knn_search(const KnnGrid& G, const double p[3], 
                     }
                 }
             }
-            unsigned long long busy = __ballot(b0 > a0);
-            while (busy) {
-                const int src = __builtin_ctzll(busy);
-                busy &= busy - 1;
-                knn_take(G, L, p, lane_int(a0, src), lane_int(b0, src));
-            }
-            busy = __ballot(b1 > a1);
-            while (busy) {
-                const int src = __builtin_ctzll(busy);
-                busy &= busy - 1;
-                knn_take(G, L, p, lane_int(a1, src), lane_int(b1, src));
-            }
+            take(a0, b0);
+            take(a1, b1);
         }
         // the nearest face of the examined block that has cells behind it
         double face = INFINITY;
@@ -328,9 +336,114 @@ __device__ __forceinline__ void knn_search(const KnnGrid& G, const double p[3], 
                 open = true;
             }
         }
-        if (!open) break;
-        const double safe = face - G.slack;
-        if (safe > 0.0 && L.kth_d2 < safe * safe) break;
+        if (done(face - slack) || !open) break;
+    }
+}
+
+// The ring search for the member at p, called by a whole wave with p wave-uniform.  On return lane j of L holds the j-th
+// smallest (d2, idx) over ALL members for j < min(knn, M); the lanes behind hold whatever else was seen, or (inf, INT_MAX).
+__device__ __forceinline__ void knn_search(const KnnGrid& G, const double p[3], KnnList& L) {
+    L = KnnList{INFINITY, INT_MAX, INFINITY, INT_MAX};
+    knn_walk(G, p, G.slack,
+             [&](int a, int b) {       // one span at a time, the whole wave on it: the list is the wave's
+                 unsigned long long busy = __ballot(b > a);
+                 while (busy) {
+                     const int src = __builtin_ctzll(busy);
+                     busy &= busy - 1;
+                     knn_take(G, L, p, lane_int(a, src), lane_int(b, src));
+                 }
+             },
+             [&](double safe) { return safe > 0.0 && L.kth_d2 < safe * safe; });
+}
+
+// d2 of the box's nearest point to q, in the operation order of a member's d2.  No member is nearer, not even in the
+// rounded arithmetic: for q[a] < bmin[a] <= r[a] the exact r[a] - q[a] is at least bmin[a] - q[a], rounding is monotone, so
+// is the square of a non-negative value, so is each of the two sums; likewise above the box.
+__device__ __forceinline__ double knn_box_d2(const KnnGrid& G, const double q[3]) {
+    double e[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) e[a] = q[a] < G.bmin[a] ? G.bmin[a] - q[a] : q[a] > G.bmax[a] ? q[a] - G.bmax[a] : 0.0;
+    return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+}
+
+// the smallest (d2, idx) of every lane's pair, in every lane: an xor butterfly over the wave
+__device__ __forceinline__ void knn_wave_min(double& d2, int& idx) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double od = __shfl_xor(d2, off);
+        const int oi = __shfl_xor(idx, off);
+        if (key_less(od, oi, d2, idx)) {
+            d2 = od;
+            idx = oi;
+        }
+    }
+}
+
+// The nearest member to a point q anywhere in space (finite coordinates), called by a whole wave with q wave-uniform:
+// the smallest (d2, idx) over ALL members whose d2 is finite, if that d2 <= max_d2; else (inf, INT_MAX).  The k = 1 form
+// of the search: no sorted list, each lane keeps the best of the candidates it loaded.  The walk ends after ring r when
+// the best d2 is strictly below safe^2, or max_d2 is, or no face is left; safe^2 is the larger of the face bound
+// (knn_walk) and knn_box_d2.  "The best d2 of the wave is below safe^2" is "some lane's best is": one ballot closes a
+// ring, and the one minimum over the wave on (d2, idx) closes the search.  A q farther than max_d2 from the box is
+// answered before the first cell is read.
+// The slack: q is not bounded by the box, so the rounding of a face distance p[a] - F, 2^-53 of |p[a]| + |F|, is covered by
+// 2^-48 of q's largest coordinate on top of G.slack (which covers F and the cell index, see the head of this file).
+__device__ __forceinline__ void knn_nearest(const KnnGrid& G, const double q[3], double max_d2, double& best_d2,
+                                            int& best_idx) {
+    const int lane = threadIdx.x & 63;
+    best_d2 = INFINITY;
+    best_idx = INT_MAX;
+    const double box_d2 = knn_box_d2(G, q);
+    if (max_d2 < box_d2) return;
+    const double reach = fmax(fabs(q[0]), fmax(fabs(q[1]), fabs(q[2])));
+    knn_walk(G, q, G.slack + reach * 0x1p-48,
+             [&](int a, int b) {
+                 // a lane's candidate j against its own best.  The index test cannot bite, see knn_take
+                 auto candidate = [&](int j) {
+                     const double* r = G.sxyz + (size_t)j * 3;
+                     const double dx = r[0] - q[0], dy = r[1] - q[1], dz = r[2] - q[2];
+                     const double d2 = (dx * dx + dy * dy) + dz * dz;
+                     const int idx = G.sidx[j];
+                     if (idx >= 0 && idx < G.P && d2 < INFINITY && key_less(d2, idx, best_d2, best_idx)) {
+                         best_d2 = d2;
+                         best_idx = idx;
+                     }
+                 };
+                 unsigned long long busy = __ballot(b > a);
+                 if (__popcll(busy) == 1) {          // one span (ring 0, or a grid of few cells): the whole wave on it
+                     const int src = __builtin_ctzll(busy);
+                     const int ga = lane_int(a, src), gb = lane_int(b, src);
+                     for (int j = (ga > 0 ? ga : 0) + lane; j < (gb < G.P ? gb : G.P); j += 64) candidate(j);
+                     return;
+                 }
+                 // the spans of a ring are short where the cloud is a surface, and each costs a round trip to memory: four
+                 // at a time, one per group of kKnnGroup lanes.  No lane talks to another in here
+                 while (busy) {
+                     int sa = 0, sb = 0;
+#pragma unroll
+                     for (int g = 0; g < 64 / kKnnGroup; ++g) {
+                         if (busy) {
+                             const int src = __builtin_ctzll(busy);
+                             busy &= busy - 1;
+                             const int ga = lane_int(a, src), gb = lane_int(b, src);
+                             if (lane / kKnnGroup == g) {
+                                 sa = ga > 0 ? ga : 0;
+                                 sb = gb < G.P ? gb : G.P;
+                             }
+                         }
+                     }
+                     for (int j = sa + lane % kKnnGroup; j < sb; j += kKnnGroup) candidate(j);
+                 }
+             },
+             [&](double safe) {
+                 const double face2 = safe > 0.0 ? safe * safe : 0.0;
+                 const double safe2 = face2 > box_d2 ? face2 : box_d2;
+                 return __ballot(best_d2 < safe2) != 0 || max_d2 < safe2;
+             });
+    knn_wave_min(best_d2, best_idx);
+    if (best_d2 > max_d2) {
+        best_d2 = INFINITY;
+        best_idx = INT_MAX;
     }
 }
 

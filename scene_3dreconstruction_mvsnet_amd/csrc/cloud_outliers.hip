@@ -7,27 +7,19 @@
 //   the grid's three scans and its scatter (knn_build_finish)
 //   outliers_search_kernel    one WAVE per member: the ring search, then the sum of the m square roots in neighbour order
 //                             over readlane, one division, and the count of valid points
-//   outliers_sum_kernel<0>    S(x): each block sums kOutliersBlock consecutive elements in the header's pairing -- an xor
-//                             butterfly inside a wave, bit 0 first, then the same pairing over the 16 wave sums through
-//                             LDS -- and is relaunched on the partial sums (<2>) until one is left
+//   cloud_sum_tree            S(x), cloud_sum.h's pairwise tree (shared with cloud_distance.hip): blocks of
+//                             MVS_OUTLIERS_BLOCK consecutive elements, relaunched on the partial sums until one is left
 //   outliers_mean_kernel      one thread: the mean, into the scalar block
-//   outliers_sum_kernel<1>    S(y), the deviations formed on load, then <2> as above
+//   cloud_sum_tree            S(y), the deviations formed on load
 //   outliers_stats_kernel     one thread: std and threshold; writes stats_out and the threshold into the scalar block
 //   outliers_mark_kernel      one thread per point: keep_out, xyz_masked_out; `kept` by a ballot and one atomic per wave
 // No floating-point atomics: a block's sum has one owner, and the tree's shape depends on P alone.
 // Compiled with -ffp-contract=off: every sum, the deviations and the threshold are the header's fp64 restatement.
 #include "mvs_outliers_abi.h"
 #include "cloud_knn.h"
+#include "cloud_sum.h"
 
 namespace mvs {
-
-constexpr int kOutliersBlock = MVS_OUTLIERS_BLOCK;
-constexpr int kOutliersWaves = kOutliersBlock / 64;
-static_assert(kOutliersWaves == 16, "the second butterfly runs over 16 lanes");
-static_assert(MVS_OUTLIERS_SCALARS >= 3 * sizeof(double), "mean, threshold, the total of a single point");
-
-// the scalar block: doubles
-constexpr int kScalarMean = 0, kScalarThreshold = 1, kScalarTotal = 2;
 
 struct OutliersParams {
     KnnGrid G;
@@ -91,40 +83,6 @@ __global__ void __launch_bounds__(kKnnThreads) outliers_search_kernel(OutliersPa
         __hip_atomic_fetch_add(&O.counts_out[1], valid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// out[block] = the header's S over in[block * kOutliersBlock ..], +0.0 past n.
-// MODE 0: in is dist, summed is x; MODE 1: in is dist, summed is y about the mean; MODE 2: in is summed as it is
-template <int MODE>
-__global__ void __launch_bounds__(kOutliersBlock) outliers_sum_kernel(const double* in, long long n, const double* scalars,
-                                                                      double* out) {
-    __shared__ double wave_sum[kOutliersWaves];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long i = (long long)blockIdx.x * kOutliersBlock + threadIdx.x;
-    double v = 0.0;
-    if (i < n) {
-        const double d = in[i];
-        if (MODE == 2) {
-            v = d;
-        } else if (d > 0.0) {                   // valid: a member (not -1.0) with a neighbour elsewhere (not 0.0)
-            if (MODE == 0) {
-                v = d;
-            } else {
-                const double e = d - scalars[kScalarMean];
-                v = e * e;
-            }
-        }
-    }
-#pragma unroll
-    for (int bit = 1; bit < 64; bit <<= 1) v = v + __shfl_xor(v, bit);
-    if (lane == 0) wave_sum[wave] = v;
-    __syncthreads();
-    if (wave == 0) {
-        double w = lane < kOutliersWaves ? wave_sum[lane] : 0.0;
-#pragma unroll
-        for (int bit = 1; bit < kOutliersWaves; bit <<= 1) w = w + __shfl_xor(w, bit);
-        if (lane == 0) out[blockIdx.x] = w;
-    }
-}
-
 __global__ void outliers_mean_kernel(const double* total, const long long* counts, double* scalars) {
     const long long n_valid = counts[1];
     scalars[kScalarMean] = n_valid > 0 ? *total / (double)n_valid : 0.0;
@@ -165,42 +123,8 @@ __global__ void __launch_bounds__(kKnnThreads) outliers_mark_kernel(OutliersPara
         __hip_atomic_fetch_add(&O.counts_out[2], (long long)kept, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// the header's L_1 + L_2 + ...
-static long long outliers_partials(long long P) {
-    long long total = 0;
-    for (long long L = P; L > 1;) {
-        L = (L + kOutliersBlock - 1) / kOutliersBlock;
-        total += L;
-    }
-    return total;
-}
-
 static size_t outliers_workspace(long long P, long long cells) {
-    return knn_workspace(P, cells) + 8 * (size_t)outliers_partials(P) + MVS_OUTLIERS_SCALARS;
-}
-
-// S over dist (first_mode 0 or 1), level by level; *total is where the one value left lies
-static int outliers_tree(int first_mode, const double* dist, long long P, double* partials, double* scalars, hipStream_t s,
-                         const double** total) {
-    const double* in = dist;
-    long long n = P;
-    double* out = P > 1 ? partials : scalars + kScalarTotal;      // a single point has no level of partial sums
-    int mode = first_mode;
-    for (;;) {
-        const long long blocks = (n + kOutliersBlock - 1) / kOutliersBlock;
-        if (mode == 0) outliers_sum_kernel<0><<<(int)blocks, kOutliersBlock, 0, s>>>(in, n, scalars, out);
-        else if (mode == 1) outliers_sum_kernel<1><<<(int)blocks, kOutliersBlock, 0, s>>>(in, n, scalars, out);
-        else outliers_sum_kernel<2><<<(int)blocks, kOutliersBlock, 0, s>>>(in, n, scalars, out);
-        if (int rc = check_hip(hipGetLastError(), "outliers_sum_kernel")) return rc;
-        if (blocks == 1) {
-            *total = out;
-            return MVS_OK;
-        }
-        in = out;
-        out += blocks;
-        n = blocks;
-        mode = 2;
-    }
+    return knn_workspace(P, cells) + 8 * (size_t)cloud_sum_partials(P) + MVS_OUTLIERS_SCALARS;
 }
 
 }  // namespace mvs
@@ -245,7 +169,7 @@ int mvs_cloud_outliers(const void* xyz, int xyz_dtype, long long P, const double
     O.masked_out = xyz_masked_out;
     O.counts_out = counts_out;
     double* partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + knn_workspace(P, cells));
-    double* scalars = partials + outliers_partials(P);
+    double* scalars = partials + cloud_sum_partials(P);
     const bool f64 = xyz_dtype == MVS_CLOUD_F64;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = check_hip(hipMemsetAsync(counts_out, 0, 3 * sizeof(long long), s), "zeroing the counts")) return rc;
@@ -259,10 +183,10 @@ int mvs_cloud_outliers(const void* xyz, int xyz_dtype, long long P, const double
     outliers_search_kernel<<<knn_search_blocks(O.G), kKnnThreads, 0, s>>>(O);
     if (int rc = check_hip(hipGetLastError(), "outliers_search_kernel")) return rc;
     const double* total = nullptr;
-    if (int rc = outliers_tree(0, dist_out, P, partials, scalars, s, &total)) return rc;
+    if (int rc = cloud_sum_tree(kSumPositive, dist_out, P, partials, scalars, s, &total)) return rc;
     outliers_mean_kernel<<<1, 1, 0, s>>>(total, counts_out, scalars);
     if (int rc = check_hip(hipGetLastError(), "outliers_mean_kernel")) return rc;
-    if (int rc = outliers_tree(1, dist_out, P, partials, scalars, s, &total)) return rc;
+    if (int rc = cloud_sum_tree(kSumDeviation, dist_out, P, partials, scalars, s, &total)) return rc;
     outliers_stats_kernel<<<1, 1, 0, s>>>(total, counts_out, std_ratio, scalars, stats_out);
     if (int rc = check_hip(hipGetLastError(), "outliers_stats_kernel")) return rc;
     if (f64) outliers_mark_kernel<double><<<blocks, kKnnThreads, 0, s>>>(O, scalars);

@@ -14,6 +14,9 @@ eval.py:817's pcd.estimate_normals() on the device (mvs_cloud_normals, include/m
 before the crop and the voxel filter, which carry the normals along, and so does `downsample=dict(normals=...)`.
 `remove_outliers` is eval.py:495's pcd.remove_statistical_outlier() on the device (mvs_cloud_outliers,
 include/mvs_outliers_abi.h), between the crop and the voxel filter: `downsample=dict(outliers=...)`, off by default.
+`cloud_distance` and `evaluate_cloud` score a cloud against a ground-truth cloud on the device (mvs_cloud_distance,
+include/mvs_distance_abi.h): accuracy, completeness, their mean, precision / recall / F-score.  The reference leaves this
+to DTU's MATLAB code; `read_ply` reads the clouds back.
 
 Differences from the reference, flagged rather than hidden:
   * cv2.remap is restated inside the kernel (1/32-pixel quantised bilinear, zero border); OpenCV is
@@ -114,6 +117,74 @@ def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray, normals: np.ndarr
     with open(filename, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply(filename: str):
+    """The counterpart of write_ply: (xyz [P,3] of the file's coordinate type, rgb uint8 [P,3] or None, normals [P,3] of
+    their type or None) from a PLY in format binary_little_endian or ascii whose first element is `vertex` with scalar
+    properties, x, y, z among them; red, green, blue (uchar) and nx, ny, nz are read when all three are there, every other
+    property and every later element (faces) is ignored.  Anything else -- another format, a list property of the
+    vertices, a short file -- raises ValueError.  read_ply(write_ply(...)) returns the arrays bit for bit."""
+    with open(filename, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    stop = data.find(b"\n", end)
+    if not data.startswith(b"ply") or end < 0 or stop < 0:
+        raise ValueError(f"read_ply: {filename} has no PLY header")
+    lines = [ln.split() for ln in data[:end].decode("ascii", "replace").splitlines()]
+    lines = [ln for ln in lines[1:] if ln and ln[0] not in ("comment", "obj_info")]
+    if not lines or lines[0][0] != "format" or len(lines[0]) < 2 or lines[0][1] not in ("binary_little_endian", "ascii"):
+        raise ValueError(f"read_ply: {filename}: format {' '.join(lines[0][1:2]) if lines else '?'!r} "
+                         "(binary_little_endian or ascii)")
+    binary = lines[0][1] == "binary_little_endian"
+    if len(lines) < 2 or lines[1][:2] != ["element", "vertex"] or len(lines[1]) != 3 or not lines[1][2].isdigit():
+        raise ValueError(f"read_ply: {filename}: the first element must be `element vertex <count>`")
+    count = int(lines[1][2])
+    fields = []
+    for ln in lines[2:]:
+        if ln[0] == "element":
+            break
+        if ln[0] != "property" or len(ln) != 3 or ln[1] not in _PLY_TYPES:
+            raise ValueError(f"read_ply: {filename}: vertex property {' '.join(ln)!r} (scalar properties only)")
+        if ln[2] in (n for n, _ in fields):
+            raise ValueError(f"read_ply: {filename}: vertex property {ln[2]!r} is declared twice")
+        fields.append((ln[2], "<" + _PLY_TYPES[ln[1]]))
+    kinds = dict(fields)
+    if not all(a in kinds for a in "xyz") or len({kinds[a] for a in "xyz"}) != 1 or kinds["x"][1] != "f":
+        raise ValueError(f"read_ply: {filename}: the vertices need x, y, z of one floating-point type")
+    body = data[stop + 1:]
+    if binary:
+        dtype = np.dtype(fields)
+        if len(body) < count * dtype.itemsize:
+            raise ValueError(f"read_ply: {filename}: {len(body)} bytes after the header, {count} vertices need "
+                             f"{count * dtype.itemsize}")
+        rec = np.frombuffer(body, dtype=dtype, count=count)
+        column = {n: rec[n] for n in kinds}
+    else:
+        rows = [ln.split() for ln in body.decode("ascii", "replace").splitlines()[:count]]
+        if len(rows) < count or any(len(r) != len(fields) for r in rows):
+            raise ValueError(f"read_ply: {filename}: {count} vertex lines of {len(fields)} values each expected")
+        column = {n: np.array([r[k] for r in rows], dtype=np.float64 if t[1] == "f" else np.int64).astype(t[1:])
+                  for k, (n, t) in enumerate(fields)}
+
+    def triple(names, what):
+        if not any(n in kinds for n in names):
+            return None
+        if not all(n in kinds for n in names) or len({kinds[n] for n in names}) != 1:
+            raise ValueError(f"read_ply: {filename}: {what} need {', '.join(names)} of one type")
+        return np.stack([column[n] for n in names], axis=1)
+    rgb = triple(("red", "green", "blue"), "colours")
+    if rgb is not None and rgb.dtype != np.uint8:
+        raise ValueError(f"read_ply: {filename}: red, green, blue must be uchar")
+    normals = triple(("nx", "ny", "nz"), "normals")
+    if normals is not None and normals.dtype.kind != "f":
+        raise ValueError(f"read_ply: {filename}: nx, ny, nz must be floating-point")
+    return triple(("x", "y", "z"), "points"), rgb, normals
 
 
 def filter_depth(scan_out_folder: str, pair_file: str, plyfilename: str | None = None,
@@ -235,15 +306,7 @@ def estimate_normals(xyz, knn=30, box=None, cell=5.0, view_counts=None, centres=
     if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
         raise RuntimeError("estimate_normals: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
     dev = xyz.device
-    if box is None:
-        finite = xyz[torch.isfinite(xyz).all(dim=1)]
-        if finite.shape[0] == 0:
-            lo, hi = (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)
-        else:
-            both = torch.stack([finite.min(dim=0).values, finite.max(dim=0).values]).double().cpu()      # the one sync
-            lo, hi = both[0].tolist(), both[1].tolist()
-    else:
-        lo, hi = box
+    lo, hi = _finite_box(xyz) if box is None else box
     starts = ctr = None
     if (view_counts is None) != (centres is None):
         raise RuntimeError("estimate_normals: view_counts and centres must both be given or both be None")
@@ -279,6 +342,101 @@ def remove_outliers(xyz, nb_neighbors=20, std_ratio=2.0, box=None, cell=5.0, mas
     dist, keep, xyz_masked, counts, stats = _lib.cloud_outliers(xyz, lo, hi, cell=cell, nb_neighbors=nb_neighbors,
                                                                 std_ratio=std_ratio, masked=masked)
     return (keep, dist, counts, stats, xyz_masked) if masked else (keep, dist, counts, stats)
+
+
+DISTANCE_CELL_BUDGET = 1 << 24      # the most cells `cell=None` lets the search grid of cloud_distance have (64 MiB of counters)
+
+
+def _finite_box(xyz):
+    """The bounding box of the finite points, as host numbers: one synchronisation (estimate_normals' default)."""
+    finite = xyz[torch.isfinite(xyz).all(dim=1)]
+    if finite.shape[0] == 0:
+        return (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)
+    both = torch.stack([finite.min(dim=0).values, finite.max(dim=0).values]).double().cpu()      # the one sync
+    return both[0].tolist(), both[1].tolist()
+
+
+def distance_cell(box, P):
+    """The cell edge cloud_distance picks for a box and P reference points: the edge at which the box holds about one
+    cell per two points -- over the axes along which the box has an extent; 1.0 if it has none -- grown by a quarter at a
+    time until the grid has at most DISTANCE_CELL_BUDGET cells.  Host arithmetic on host numbers."""
+    ext = [float(h) - float(l) for l, h in zip(*box)]
+    pos = [e for e in ext if e > 0.0]
+    if not pos or not all(np.isfinite(pos)):
+        return 1.0
+    target = min(max(int(P) // 2, 1), DISTANCE_CELL_BUDGET // 4)
+    cell = float(np.prod(pos) / target) ** (1.0 / len(pos))
+    cell = max(cell, max(pos) * 2.0 ** -20)             # a sliver of a box: never more than 2^20 cells along an axis
+    while np.prod([np.floor(e / cell) + 1.0 for e in ext]) > DISTANCE_CELL_BUDGET:
+        cell *= 1.25
+    return cell
+
+
+def cloud_distance(query, ref, max_dist=float("inf"), thresholds=(), box=None, cell=None, return_indices=False):
+    """For every point of `query` the distance to the nearest point of `ref` (both float32 or float64 [.,3] on the GPU,
+    possibly the same tensor), on the device (mvs_cloud_distance, include/mvs_distance_abi.h): one direction of accuracy /
+    completeness.  Only the points of `ref` inside `box` = (min, max) are searched; box defaults to the bounding box of
+    ref's finite points, which costs the one host synchronisation of this function (with a box given nothing
+    synchronises).  A query may lie anywhere.  cell: the search grid's cell edge, default distance_cell(box, P) -- it
+    changes the time, never the result.
+    Returns (dist float64 [N]: the distance; +inf where no point of ref in the box lies within max_dist; -1 for a query
+    with a non-finite coordinate, counts int64 [2 + T]: the queries with finite coordinates, those within max_dist, those
+    strictly below each of `thresholds` (at most 8), stats float64 [2]: the sum of the distances within max_dist, in a
+    fixed order, and their mean), all on the device, and with return_indices a fourth item: idx int32 [N], the row of the
+    nearest point in ref, the smallest on a tie, -1 where there is none."""
+    for name, t in (("query", query), ("ref", ref)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"cloud_distance: {name} must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    lo, hi = _finite_box(ref) if box is None else box
+    if cell is None:
+        cell = distance_cell((lo, hi), ref.shape[0])
+    dist, idx, counts, stats = _lib.cloud_distance(ref, query, lo, hi, cell, max_dist, thresholds, indices=return_indices)
+    return (dist, counts, stats, idx) if return_indices else (dist, counts, stats)
+
+
+def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), box=None, cell=None):
+    """The measure a reconstruction is judged by, both directions of `cloud_distance` on the device:
+        accuracy      from every point of pred_xyz to the nearest point of gt_xyz
+        completeness  from every point of gt_xyz to the nearest point of pred_xyz
+    each as dict(mean, median, n, n_within, below): `n` points with finite coordinates, `n_within` of them with a
+    neighbour within max_dist, mean and median (the lower one, the ((n_within + 1) // 2)-th smallest; NaN for none) over
+    those, `below[t]` of them strictly nearer than thresholds[t]; and
+        overall       (accuracy.mean + completeness.mean) / 2
+        precision[t]  accuracy.below[t] / accuracy.n            recall[t]  completeness.below[t] / completeness.n
+        fscore[t]     2 p r / (p + r), 0 when p + r == 0
+    with max_dist and thresholds repeated, all plain Python numbers after one device-to-host copy.  A point farther than
+    max_dist from the other cloud counts in n, in no mean and below no threshold.  `box` = (min, max) limits the points
+    that are SEARCHED in either direction (default: each cloud's own bounding box, one host synchronisation per
+    direction); the points that are scored are always all of the other cloud.  cell as in cloud_distance.
+
+    What this is not: DTU's evaluation.  There is no observability mask, no ground-plane filter and no point reduction
+    (reducePts), so clouds of different density or extent are scored as they are and the numbers are not those of the
+    MATLAB tables; it reproduces the definition of the distances, nothing more.  `downsample_cloud` and a box are the
+    tools to equalise density and region before the call."""
+    thresholds = [float(t) for t in thresholds]
+    T = len(thresholds)
+    parts = []
+    for query, ref in ((pred_xyz, gt_xyz), (gt_xyz, pred_xyz)):
+        dist, counts, stats = cloud_distance(query, ref, max_dist=max_dist, thresholds=thresholds, box=box, cell=cell)
+        if dist.shape[0]:
+            within = (dist >= 0) & torch.isfinite(dist)
+            ordered = torch.sort(torch.where(within, dist, torch.full_like(dist, float("inf")))).values
+            k = torch.clamp((counts[1] + 1) // 2 - 1, min=0)
+            median = torch.where(counts[1] > 0, ordered[k], torch.full_like(stats[0], float("nan")))
+        else:
+            median = torch.full_like(stats[0], float("nan"))
+        parts += [counts.double(), stats, median.reshape(1)]
+    host = torch.cat(parts).cpu().tolist()                # the one copy; every count is below 2^31, exact as a double
+    out = {}
+    for name, v in (("accuracy", host[:T + 5]), ("completeness", host[T + 5:])):
+        out[name] = dict(mean=v[T + 3], median=v[T + 4], n=int(v[0]), n_within=int(v[1]), below=[int(b) for b in v[2:2 + T]])
+    acc, comp = out["accuracy"], out["completeness"]
+    out["overall"] = (acc["mean"] + comp["mean"]) / 2
+    out["precision"] = [b / acc["n"] if acc["n"] else 0.0 for b in acc["below"]]
+    out["recall"] = [b / comp["n"] if comp["n"] else 0.0 for b in comp["below"]]
+    out["fscore"] = [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(out["precision"], out["recall"])]
+    out["max_dist"], out["thresholds"] = float(max_dist), thresholds
+    return out
 
 
 def downsample_cloud(xyz, rgb, voxel_size=5.0, box=None, scale=0.01, capacity=None, normals=None):

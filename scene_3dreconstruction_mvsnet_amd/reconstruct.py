@@ -18,10 +18,15 @@ eval.py:817's estimate_normals: normals from K neighbours inside the box grown b
 point's camera, carried through the voxel filter and written as nx, ny, nz.  --outlier_knn K (with --downsample_mm) adds
 eval.py:495's remove_statistical_outlier between the crop and the voxel filter: a point of the box whose mean distance to
 its K nearest neighbours there is not below mean + --outlier_std standard deviations of those distances is dropped.
+
+--gt_ply PATH scores every scan's fused cloud (the full one, as it is written) against the ground-truth cloud of PATH on
+the GPU and prints the result as `<scan>: score {json}`; --max_dist, --thresholds, --box, --cell and --json are eval_cloud's
+(--json receives {scan: result}).  PATH may hold `{scan}`.  Nothing else about the run changes.
 """
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import re
 
@@ -36,6 +41,7 @@ def downsampled_name(voxel_mm):
 def main(argv=None):
     from . import MVSNet
     from .dataset_eval import EvalDataset
+    from .eval_cloud import add_score_arguments, score
     from .fusion import bin_box, reconstruct_scan
 
     p = argparse.ArgumentParser(description="Reconstruct every scan of a list into a fused, coloured point cloud")
@@ -74,7 +80,14 @@ def main(argv=None):
                    help="with --downsample_mm: drop statistical outliers from K neighbours (eval.py:495) before the voxel filter")
     p.add_argument("--outlier_std", type=float, default=2.0, metavar="S",
                    help="a point is kept while its mean neighbour distance is below mean + S standard deviations")
+    p.add_argument("--gt_ply", default=None, metavar="PATH",
+                   help="score each scan's fused cloud against this ground-truth PLY ({scan} is replaced by the scan's name)")
+    add_score_arguments(p)
     args = p.parse_args(argv)
+    if args.gt_ply is None and (args.box is not None or args.json is not None):
+        p.error("--box and --json need --gt_ply")
+    if len(args.thresholds) > 8:
+        p.error("at most 8 --thresholds")
     if args.downsample_mm is None and args.crop_box is not None:
         p.error("--crop_box needs --downsample_mm")
     if args.downsample_mm is None and args.normals_knn is not None:
@@ -90,7 +103,7 @@ def main(argv=None):
     model = MVSNet(refine=False)
     _load_checkpoint(model, args.loadckpt)
     os.makedirs(args.outdir, exist_ok=True)
-    written = []
+    written, scores = [], {}
     for scan in dict.fromkeys(m[0] for m in ds.metas):
         scan_id = int(re.findall(r"\d+", scan)[0])
         ply = os.path.join(args.outdir, "mvsnet{:0>3}_l3.ply".format(scan_id))
@@ -119,6 +132,13 @@ def main(argv=None):
                 members, valid, kept = (int(x) for x in got[-1]["counts"])
                 print(f"{scan}: {kept} of {members} points in the box kept ({valid} with a neighbour elsewhere; mean distance "
                       f"below {got[-1]['stats'][2]:g})")
+        if args.gt_ply is not None:
+            from .fusion import read_ply
+            scores[scan] = score(got[0], read_ply(args.gt_ply.replace("{scan}", scan))[0], args)
+            print(f"{scan}: score {json.dumps(scores[scan], sort_keys=True)}")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(scores, f, indent=1, sort_keys=True)
     return written
 
 
