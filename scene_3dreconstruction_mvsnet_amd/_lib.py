@@ -658,6 +658,71 @@ def filter_depth(depth, conf, ref_mats, pair_mats, ref_idx, src_idx, photomask=0
     return geo, avg, masks, xyz
 
 
+# ---- the cloud path: what its wrappers share ---------------------------------------------------
+MVS_CLOUD_F32, MVS_CLOUD_F64 = 0, 1
+
+
+def _outputs(who, dev, specs, out):
+    """The tensors a wrapper's results go to, one per entry of `specs` = [(name, shape, dtype, wanted)], in the order of
+    its `out` tuple.  Without `out` they are allocated here (None where not wanted); otherwise `out` is unpacked and each
+    tensor that is present is checked against its entry.  Called inside `with torch.cuda.device(dev)`, before the
+    workspace is allocated."""
+    if out is None:
+        return [torch.empty(shape, dtype=dtype, device=dev) if wanted else None for _, shape, dtype, wanted in specs]
+    out = list(out)
+    if len(out) != len(specs):
+        raise ValueError(f"{who}: out must hold ({', '.join(s[0] for s in specs)}), got {len(out)} entries")
+    for t, (name, shape, dtype, _) in zip(out, specs):
+        if t is not None:
+            _check_out(t, shape, dtype, dev, f"{who}: out {name}", f"{dtype} {shape} tensor on {dev}")
+    return out
+
+
+def _cloud_xyz(xyz, who):
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise RuntimeError(f"{who}: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    if xyz.dtype not in (torch.float32, torch.float64) or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError(f"{who}: xyz must be float32 or float64 [P,3], got {xyz.dtype} {tuple(xyz.shape)}")
+    return xyz.contiguous()
+
+
+def _cloud_rows(t, name, dtype, P, dev, who):
+    """What travels with xyz, one row per point (rgb, normals): a `dtype` [P,3] tensor on xyz's device."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{who}: {name} must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    if t.device != dev:
+        raise RuntimeError(f"{who}: xyz and {name} must be on one device")
+    if t.dtype != dtype or tuple(t.shape) != (P, 3):
+        raise RuntimeError(f"{who}: {name} must be {str(dtype)[6:]} [P,3] = [{P},3], got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _xyz_code(t):
+    return MVS_CLOUD_F64 if t.dtype == torch.float64 else MVS_CLOUD_F32
+
+
+def _box_arg(box_min, box_max, who):
+    """Two host triples -> two ctypes double[3] (the library reads them before it returns)."""
+    out = []
+    for name, b in (("box_min", box_min), ("box_max", box_max)):
+        if isinstance(b, torch.Tensor):
+            if b.device.type != "cpu":
+                raise RuntimeError(f"{who}: {name} must be host numbers (got a tensor on {b.device}): the box travels in "
+                                   "the kernel arguments, reading device memory would sync")
+            b = b.tolist()
+        b = [float(x) for x in b]
+        if len(b) != 3:
+            raise RuntimeError(f"{who}: {name} must hold 3 numbers, got {len(b)}")
+        out.append((_d * 3)(*b))
+    return out
+
+
+def _box_query(symbol, who, *counts, box_min, box_max, edge) -> int:
+    """The bytes `symbol` asks for: a workspace query over the grid of a box, after its point counts."""
+    lo, hi = _box_arg(box_min, box_max, who)
+    return _query(symbol, *(int(c) for c in counts), lo, hi, float(edge))
+
+
 # ---- fused point cloud (include/mvs_fuse_abi.h, csrc/fuse_points.hip) -------------------------
 FUSE_TILE, FUSE_SCAN_WIDTH = 1024, 1024     # MVS_FUSE_TILE, MVS_FUSE_SCAN_WIDTH
 
@@ -701,15 +766,9 @@ def fuse_points(xyz_world, masks, images, ref_idx, capacity=None, out=None):
         raise RuntimeError(f"fuse_points: capacity {capacity} is negative")
     xyz_world, masks, ref_idx = xyz_world.contiguous(), masks.contiguous(), ref_idx.contiguous()
     with torch.cuda.device(dev):
-        if out is None:
-            xyz = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
-            rgb = torch.empty((capacity, 3), dtype=torch.uint8, device=dev)
-            counts = torch.empty((R + 1,), dtype=torch.int32, device=dev)
-        else:
-            xyz, rgb, counts = out
-            for t, shape, dt, name in ((xyz, (capacity, 3), torch.float32, "xyz"), (rgb, (capacity, 3), torch.uint8, "rgb"),
-                                       (counts, (R + 1,), torch.int32, "counts")):
-                _check_out(t, shape, dt, dev, f"fuse_points: out {name}", f"{dt} {shape} tensor on {dev}")
+        xyz, rgb, counts = _outputs("fuse_points", dev, [("xyz", (capacity, 3), torch.float32, True),
+                                                         ("rgb", (capacity, 3), torch.uint8, True),
+                                                         ("counts", (R + 1,), torch.int32, True)], out)
         ws = torch.empty(query_fuse_workspace(R, h, w), dtype=torch.uint8, device=dev)
         check(load().mvs_fuse_points(xyz_world.data_ptr(), masks.data_ptr(), images.data_ptr(), fmt, ref_idx.data_ptr(),
                                      V, R, h, w, capacity, xyz.data_ptr() if capacity else None,
@@ -718,30 +777,48 @@ def fuse_points(xyz_world, masks, images, ref_idx, capacity=None, out=None):
     return xyz, rgb, counts
 
 
-# ---- crop + voxel downsample of a cloud (include/mvs_cloud_abi.h, csrc/cloud_downsample.hip) ----
-MVS_CLOUD_F32, MVS_CLOUD_F64 = 0, 1
+# ---- crop + voxel downsample of a cloud (include/mvs_cloud_abi.h, csrc/cloud_downsample.hip), and the one that also
+# ---- carries the points' normals (include/mvs_normals_abi.h) ----
 CLOUD_CHUNK, CLOUD_TILE, CLOUD_SCAN_WIDTH, CLOUD_RECORD = 1024, 1024, 1024, 64     # the header's MVS_CLOUD_* sizes
 
 
-def _box_arg(box_min, box_max, who):
-    """Two host triples -> two ctypes double[3] (the library reads them before it returns)."""
-    out = []
-    for name, b in (("box_min", box_min), ("box_max", box_max)):
-        if isinstance(b, torch.Tensor):
-            if b.device.type != "cpu":
-                raise RuntimeError(f"{who}: {name} must be host numbers (got a tensor on {b.device}): the box travels in "
-                                   "the kernel arguments, reading device memory would sync")
-            b = b.tolist()
-        b = [float(x) for x in b]
-        if len(b) != 3:
-            raise RuntimeError(f"{who}: {name} must hold 3 numbers, got {len(b)}")
-        out.append((_d * 3)(*b))
-    return out
-
-
 def query_cloud_workspace(P, box_min, box_max, voxel_size) -> int:
-    lo, hi = _box_arg(box_min, box_max, "query_cloud_workspace")
-    return _query("mvs_query_cloud_workspace", int(P), ctypes.addressof(lo), ctypes.addressof(hi), float(voxel_size))
+    return _box_query("mvs_query_cloud_workspace", "query_cloud_workspace", P, box_min=box_min, box_max=box_max,
+                      edge=voxel_size)
+
+
+def query_cloud_normals_downsample_workspace(P, box_min, box_max, voxel_size) -> int:
+    return _box_query("mvs_query_cloud_normals_downsample_workspace", "query_cloud_normals_downsample_workspace", P,
+                      box_min=box_min, box_max=box_max, edge=voxel_size)
+
+
+def _downsample(who, xyz, rgb, normals, box_min, box_max, voxel_size, scale, capacity, out):
+    """Both downsamples: `normals` is None for the plain one, whose entry point, `out` and result lack the normals."""
+    xyz = _cloud_xyz(xyz, who)
+    dev, P = xyz.device, xyz.shape[0]
+    carried = [_cloud_rows(rgb, "rgb", torch.uint8, P, dev, who)]
+    if normals is not None:
+        carried.append(_cloud_rows(normals, "normals", torch.float32, P, dev, who))
+    lo, hi = _box_arg(box_min, box_max, who)
+    capacity = P if capacity is None else int(capacity)
+    if capacity < 0:
+        raise RuntimeError(f"{who}: capacity {capacity} is negative")
+    symbol = "mvs_cloud_downsample" if normals is None else "mvs_cloud_downsample_normals"
+    nbytes = _box_query("mvs_query_cloud_workspace" if normals is None else "mvs_query_cloud_normals_downsample_workspace",
+                        who, P, box_min=lo, box_max=hi, edge=voxel_size)
+    with torch.cuda.device(dev):
+        specs = [("xyz", (capacity, 3), torch.float32, True), ("rgb", (capacity, 3), torch.uint8, True),
+                 ("normals", (capacity, 3), torch.float32, True)][:1 + len(carried)]
+        *means, counts = _outputs(who, dev, specs + [("counts", (2,), torch.int64, True)], out)
+        if P == 0:          # an empty tensor has no address to hand over: the two zero counts of the header's P == 0
+            counts.zero_()
+            return (*means, counts)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(getattr(load(), symbol)(xyz.data_ptr(), _xyz_code(xyz), *(t.data_ptr() for t in carried), P, lo, hi,
+                                      float(voxel_size), float(scale), capacity,
+                                      *(t.data_ptr() if capacity else None for t in means), counts.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), _stream(dev)))
+    return (*means, counts)
 
 
 def cloud_downsample(xyz, rgb, box_min, box_max, voxel_size, scale=1.0, capacity=None, out=None):
@@ -753,66 +830,25 @@ def cloud_downsample(xyz, rgb, box_min, box_max, voxel_size, scale=1.0, capacity
     device, voxels in ascending (iz, iy, ix); rows at and beyond counts[1] are not written.  capacity defaults to P,
     which always suffices; with less, the first `capacity` voxels are written and counts stays exact.  `out` =
     (xyz, rgb, counts) receives the results.  Enqueued on the current stream; nothing synchronises."""
-    for name, t in (("xyz", xyz), ("rgb", rgb)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError(f"cloud_downsample: {name} must be a CUDA(ROCm) tensor; there is no CPU implementation")
-    dev = xyz.device
-    if rgb.device != dev:
-        raise RuntimeError("cloud_downsample: xyz and rgb must be on one device")
-    if xyz.dtype not in (torch.float32, torch.float64) or xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise RuntimeError(f"cloud_downsample: xyz must be float32 or float64 [P,3], got {xyz.dtype} {tuple(xyz.shape)}")
-    P = xyz.shape[0]
-    if rgb.dtype != torch.uint8 or tuple(rgb.shape) != (P, 3):
-        raise RuntimeError(f"cloud_downsample: rgb must be uint8 [P,3] = [{P},3], got {rgb.dtype} {tuple(rgb.shape)}")
-    lo, hi = _box_arg(box_min, box_max, "cloud_downsample")
-    capacity = P if capacity is None else int(capacity)
-    if capacity < 0:
-        raise RuntimeError(f"cloud_downsample: capacity {capacity} is negative")
-    xyz, rgb = xyz.contiguous(), rgb.contiguous()
-    nbytes = _query("mvs_query_cloud_workspace", P, ctypes.addressof(lo), ctypes.addressof(hi), float(voxel_size))
-    with torch.cuda.device(dev):
-        if out is None:
-            xyz_out = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
-            rgb_out = torch.empty((capacity, 3), dtype=torch.uint8, device=dev)
-            counts = torch.empty((2,), dtype=torch.int64, device=dev)
-        else:
-            xyz_out, rgb_out, counts = out
-            for t, shape, dt, name in ((xyz_out, (capacity, 3), torch.float32, "xyz"),
-                                       (rgb_out, (capacity, 3), torch.uint8, "rgb"), (counts, (2,), torch.int64, "counts")):
-                _check_out(t, shape, dt, dev, f"cloud_downsample: out {name}", f"{dt} {shape} tensor on {dev}")
-        if P == 0:          # an empty tensor has no address to hand over: the two zero counts of the header's P == 0
-            counts.zero_()
-            return xyz_out, rgb_out, counts
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(load().mvs_cloud_downsample(xyz.data_ptr(), MVS_CLOUD_F64 if xyz.dtype == torch.float64 else MVS_CLOUD_F32,
-                                          rgb.data_ptr(), P, ctypes.addressof(lo), ctypes.addressof(hi), float(voxel_size),
-                                          float(scale), capacity, xyz_out.data_ptr() if capacity else None,
-                                          rgb_out.data_ptr() if capacity else None, counts.data_ptr(), ws.data_ptr(),
-                                          ws.numel(), _stream(dev)))
-    return xyz_out, rgb_out, counts
+    return _downsample("cloud_downsample", xyz, rgb, None, box_min, box_max, voxel_size, scale, capacity, out)
 
 
-# ---- point normals and the downsample that carries them (include/mvs_normals_abi.h, csrc/cloud_normals.hip) ----
+def cloud_downsample_normals(xyz, rgb, normals, box_min, box_max, voxel_size, scale=1.0, capacity=None, out=None):
+    """cloud_downsample that also carries the points' normals: returns (xyz float32 [capacity,3], rgb uint8 [capacity,3],
+    normals float32 [capacity,3]: the mean of each voxel's normals, not renormalised, counts int64 [2]).  The first, second
+    and last are byte for byte what cloud_downsample returns.  normals float32 [P,3] on xyz's device.  `out` = (xyz, rgb,
+    normals, counts).  Enqueued on the current stream; nothing synchronises."""
+    if normals is None:
+        raise RuntimeError("cloud_downsample_normals: normals must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    return _downsample("cloud_downsample_normals", xyz, rgb, normals, box_min, box_max, voxel_size, scale, capacity, out)
+
+
+# ---- point normals (include/mvs_normals_abi.h, csrc/cloud_normals.hip) ----
 NORMALS_KNN_MAX, NORMALS_TILE = 64, 1024     # MVS_NORMALS_KNN_MAX, MVS_NORMALS_TILE
 
 
-def _cloud_xyz(xyz, who):
-    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
-        raise RuntimeError(f"{who}: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
-    if xyz.dtype not in (torch.float32, torch.float64) or xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise RuntimeError(f"{who}: xyz must be float32 or float64 [P,3], got {xyz.dtype} {tuple(xyz.shape)}")
-    return xyz.contiguous()
-
-
 def query_normals_workspace(P, box_min, box_max, cell) -> int:
-    lo, hi = _box_arg(box_min, box_max, "query_normals_workspace")
-    return _query("mvs_query_normals_workspace", int(P), ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
-
-
-def query_cloud_normals_downsample_workspace(P, box_min, box_max, voxel_size) -> int:
-    lo, hi = _box_arg(box_min, box_max, "query_cloud_normals_downsample_workspace")
-    return _query("mvs_query_cloud_normals_downsample_workspace", int(P), ctypes.addressof(lo), ctypes.addressof(hi),
-                  float(voxel_size))
+    return _box_query("mvs_query_normals_workspace", "query_normals_workspace", P, box_min=box_min, box_max=box_max, edge=cell)
 
 
 def cloud_normals(xyz, box_min, box_max, cell=5.0, knn=30, view_starts=None, centres=None, neighbours=False, out=None):
@@ -840,74 +876,22 @@ def cloud_normals(xyz, box_min, box_max, cell=5.0, knn=30, view_starts=None, cen
                 or centres.device != dev:
             raise RuntimeError(f"cloud_normals: centres must be a float64 [R,3] = [{R},3] tensor on xyz's device")
         view_starts, centres = view_starts.contiguous(), centres.contiguous()
-    nbytes = _query("mvs_query_normals_workspace", P, ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+    nbytes = _box_query("mvs_query_normals_workspace", "cloud_normals", P, box_min=lo, box_max=hi, edge=cell)
     with torch.cuda.device(dev):
-        if out is None:
-            normals = torch.empty((P, 3), dtype=torch.float32, device=dev)
-            nbr = torch.empty((P, knn), dtype=torch.int32, device=dev) if neighbours else None
-            counts = torch.empty((3,), dtype=torch.int64, device=dev)
-        else:
-            normals, nbr, counts = out
-            _check_out(normals, (P, 3), torch.float32, dev, "cloud_normals: out normals", f"float32 {(P, 3)} tensor on {dev}")
-            _check_out(counts, (3,), torch.int64, dev, "cloud_normals: out counts", f"int64 (3,) tensor on {dev}")
-            if nbr is not None:
-                _check_out(nbr, (P, knn), torch.int32, dev, "cloud_normals: out neighbours", f"int32 {(P, knn)} tensor on {dev}")
+        normals, nbr, counts = _outputs("cloud_normals", dev, [("normals", (P, 3), torch.float32, True),
+                                                               ("neighbours", (P, knn), torch.int32, neighbours),
+                                                               ("counts", (3,), torch.int64, True)], out)
         if P == 0:          # an empty tensor has no address to hand over: the three zero counts of the header's P == 0
             if not 3 <= knn <= NORMALS_KNN_MAX:
                 raise RuntimeError(f"cloud_normals: knn = {knn} (need 3 <= knn <= {NORMALS_KNN_MAX})")
             counts.zero_()
             return normals, nbr, counts
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(load().mvs_cloud_normals(xyz.data_ptr(), MVS_CLOUD_F64 if xyz.dtype == torch.float64 else MVS_CLOUD_F32, P,
-                                       ctypes.addressof(lo), ctypes.addressof(hi), float(cell), knn,
+        check(load().mvs_cloud_normals(xyz.data_ptr(), _xyz_code(xyz), P, lo, hi, float(cell), knn,
                                        view_starts.data_ptr() if R else None, centres.data_ptr() if R else None, R,
                                        normals.data_ptr(), None if nbr is None else nbr.data_ptr(), counts.data_ptr(),
                                        ws.data_ptr(), ws.numel(), _stream(dev)))
     return normals, nbr, counts
-
-
-def cloud_downsample_normals(xyz, rgb, normals, box_min, box_max, voxel_size, scale=1.0, capacity=None, out=None):
-    """cloud_downsample that also carries the points' normals: returns (xyz float32 [capacity,3], rgb uint8 [capacity,3],
-    normals float32 [capacity,3]: the mean of each voxel's normals, not renormalised, counts int64 [2]).  The first, second
-    and last are byte for byte what cloud_downsample returns.  normals float32 [P,3] on xyz's device.  `out` = (xyz, rgb,
-    normals, counts).  Enqueued on the current stream; nothing synchronises."""
-    xyz = _cloud_xyz(xyz, "cloud_downsample_normals")
-    dev = xyz.device
-    P = xyz.shape[0]
-    if not isinstance(rgb, torch.Tensor) or rgb.device != dev or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (P, 3):
-        raise RuntimeError(f"cloud_downsample_normals: rgb must be uint8 [P,3] = [{P},3] on xyz's device")
-    if not isinstance(normals, torch.Tensor) or normals.device != dev or normals.dtype != torch.float32 \
-            or tuple(normals.shape) != (P, 3):
-        raise RuntimeError(f"cloud_downsample_normals: normals must be float32 [P,3] = [{P},3] on xyz's device")
-    lo, hi = _box_arg(box_min, box_max, "cloud_downsample_normals")
-    capacity = P if capacity is None else int(capacity)
-    if capacity < 0:
-        raise RuntimeError(f"cloud_downsample_normals: capacity {capacity} is negative")
-    rgb, normals = rgb.contiguous(), normals.contiguous()
-    nbytes = _query("mvs_query_cloud_normals_downsample_workspace", P, ctypes.addressof(lo), ctypes.addressof(hi),
-                    float(voxel_size))
-    with torch.cuda.device(dev):
-        if out is None:
-            xyz_out = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
-            rgb_out = torch.empty((capacity, 3), dtype=torch.uint8, device=dev)
-            normals_out = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
-            counts = torch.empty((2,), dtype=torch.int64, device=dev)
-        else:
-            xyz_out, rgb_out, normals_out, counts = out
-            for t, shape, dt, name in ((xyz_out, (capacity, 3), torch.float32, "xyz"), (rgb_out, (capacity, 3), torch.uint8, "rgb"),
-                                       (normals_out, (capacity, 3), torch.float32, "normals"),
-                                       (counts, (2,), torch.int64, "counts")):
-                _check_out(t, shape, dt, dev, f"cloud_downsample_normals: out {name}", f"{dt} {shape} tensor on {dev}")
-        if P == 0:
-            counts.zero_()
-            return xyz_out, rgb_out, normals_out, counts
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(load().mvs_cloud_downsample_normals(
-            xyz.data_ptr(), MVS_CLOUD_F64 if xyz.dtype == torch.float64 else MVS_CLOUD_F32, rgb.data_ptr(), normals.data_ptr(),
-            P, ctypes.addressof(lo), ctypes.addressof(hi), float(voxel_size), float(scale), capacity,
-            xyz_out.data_ptr() if capacity else None, rgb_out.data_ptr() if capacity else None,
-            normals_out.data_ptr() if capacity else None, counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
-    return xyz_out, rgb_out, normals_out, counts
 
 
 # ---- statistical outlier removal (include/mvs_outliers_abi.h, csrc/cloud_outliers.hip) ----
@@ -915,8 +899,8 @@ OUTLIERS_BLOCK, OUTLIERS_SCALARS = 1024, 64     # MVS_OUTLIERS_BLOCK, MVS_OUTLIE
 
 
 def query_outliers_workspace(P, box_min, box_max, cell) -> int:
-    lo, hi = _box_arg(box_min, box_max, "query_outliers_workspace")
-    return _query("mvs_query_outliers_workspace", int(P), ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+    return _box_query("mvs_query_outliers_workspace", "query_outliers_workspace", P, box_min=box_min, box_max=box_max,
+                      edge=cell)
 
 
 def cloud_outliers(xyz, box_min, box_max, cell=5.0, nb_neighbors=20, std_ratio=2.0, masked=False, out=None):
@@ -933,24 +917,14 @@ def cloud_outliers(xyz, box_min, box_max, cell=5.0, nb_neighbors=20, std_ratio=2
     dev = xyz.device
     P, nb, ratio = xyz.shape[0], int(nb_neighbors), float(std_ratio)
     lo, hi = _box_arg(box_min, box_max, "cloud_outliers")
-    nbytes = _query("mvs_query_outliers_workspace", P, ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+    nbytes = _box_query("mvs_query_outliers_workspace", "cloud_outliers", P, box_min=lo, box_max=hi, edge=cell)
     with torch.cuda.device(dev):
-        if out is None:
-            dist = torch.empty((P,), dtype=torch.float64, device=dev)
-            keep = torch.empty((P,), dtype=torch.bool, device=dev)      # the library writes bytes 0 and 1
-            xyz_masked = torch.empty((P, 3), dtype=xyz.dtype, device=dev) if masked else None
-            counts = torch.empty((3,), dtype=torch.int64, device=dev)
-            stats = torch.empty((3,), dtype=torch.float64, device=dev)
-        else:
-            dist, keep, xyz_masked, counts, stats = out
-            for t, shape, dt, name in ((dist, (P,), torch.float64, "dist"), (keep, (P,), torch.bool, "keep"),
-                                       (counts, (3,), torch.int64, "counts"), (stats, (3,), torch.float64, "stats")):
-                _check_out(t, shape, dt, dev, f"cloud_outliers: out {name}", f"{dt} {shape} tensor on {dev}")
-            if xyz_masked is not None:
-                _check_out(xyz_masked, (P, 3), xyz.dtype, dev, "cloud_outliers: out xyz_masked",
-                           f"{xyz.dtype} {(P, 3)} tensor on {dev}")
-                if P and xyz_masked.data_ptr() == xyz.data_ptr():
-                    raise RuntimeError("cloud_outliers: out xyz_masked must not alias xyz")
+        dist, keep, xyz_masked, counts, stats = _outputs("cloud_outliers", dev, [
+            ("dist", (P,), torch.float64, True), ("keep", (P,), torch.bool, True),      # the library writes bytes 0 and 1
+            ("xyz_masked", (P, 3), xyz.dtype, masked), ("counts", (3,), torch.int64, True),
+            ("stats", (3,), torch.float64, True)], out)
+        if out is not None and xyz_masked is not None and P and xyz_masked.data_ptr() == xyz.data_ptr():
+            raise RuntimeError("cloud_outliers: out xyz_masked must not alias xyz")
         if P == 0:          # an empty tensor has no address to hand over: the zeros of the header's P == 0
             if not 2 <= nb <= NORMALS_KNN_MAX:
                 raise RuntimeError(f"cloud_outliers: nb_neighbors = {nb} (need 2 <= nb_neighbors <= {NORMALS_KNN_MAX})")
@@ -960,8 +934,7 @@ def cloud_outliers(xyz, box_min, box_max, cell=5.0, nb_neighbors=20, std_ratio=2
             stats.zero_()
             return dist, keep, xyz_masked, counts, stats
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(load().mvs_cloud_outliers(xyz.data_ptr(), MVS_CLOUD_F64 if xyz.dtype == torch.float64 else MVS_CLOUD_F32, P,
-                                        ctypes.addressof(lo), ctypes.addressof(hi), float(cell), nb, ratio, dist.data_ptr(),
+        check(load().mvs_cloud_outliers(xyz.data_ptr(), _xyz_code(xyz), P, lo, hi, float(cell), nb, ratio, dist.data_ptr(),
                                         keep.data_ptr(), None if xyz_masked is None else xyz_masked.data_ptr(),
                                         counts.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
     return dist, keep, xyz_masked, counts, stats
@@ -972,8 +945,8 @@ DISTANCE_THRESHOLDS_MAX, DISTANCE_SCALARS = 8, 64     # MVS_DISTANCE_THRESHOLDS_
 
 
 def query_distance_workspace(P, N, box_min, box_max, cell) -> int:
-    lo, hi = _box_arg(box_min, box_max, "query_distance_workspace")
-    return _query("mvs_query_distance_workspace", int(P), int(N), ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+    return _box_query("mvs_query_distance_workspace", "query_distance_workspace", P, N, box_min=box_min, box_max=box_max,
+                      edge=cell)
 
 
 def cloud_distance(ref, query, box_min, box_max, cell, max_dist, thresholds, indices=False, out=None):
@@ -1003,32 +976,21 @@ def cloud_distance(ref, query, box_min, box_max, cell, max_dist, thresholds, ind
     if T and not (np.isfinite(th).all() and (th >= 0).all()):
         raise RuntimeError(f"cloud_distance: thresholds {th.tolist()} (need finite thresholds >= 0)")
     lo, hi = _box_arg(box_min, box_max, "cloud_distance")
-    nbytes = _query("mvs_query_distance_workspace", P, N, ctypes.addressof(lo), ctypes.addressof(hi), float(cell))
+    nbytes = _box_query("mvs_query_distance_workspace", "cloud_distance", P, N, box_min=lo, box_max=hi, edge=cell)
     with torch.cuda.device(dev):
-        if out is None:
-            dist = torch.empty((N,), dtype=torch.float64, device=dev)
-            idx = torch.empty((N,), dtype=torch.int32, device=dev) if indices else None
-            counts = torch.empty((2 + T,), dtype=torch.int64, device=dev)
-            stats = torch.empty((2,), dtype=torch.float64, device=dev)
-        else:
-            dist, idx, counts, stats = out
-            for t, shape, dt, name in ((dist, (N,), torch.float64, "dist"), (counts, (2 + T,), torch.int64, "counts"),
-                                       (stats, (2,), torch.float64, "stats")):
-                _check_out(t, shape, dt, dev, f"cloud_distance: out {name}", f"{dt} {shape} tensor on {dev}")
-            if idx is not None:
-                _check_out(idx, (N,), torch.int32, dev, "cloud_distance: out idx", f"int32 {(N,)} tensor on {dev}")
+        dist, idx, counts, stats = _outputs("cloud_distance", dev, [
+            ("dist", (N,), torch.float64, True), ("idx", (N,), torch.int32, indices),
+            ("counts", (2 + T,), torch.int64, True), ("stats", (2,), torch.float64, True)], out)
         if N == 0:          # an empty tensor has no address to hand over: the zeros of the header's N == 0
             counts.zero_()
             stats.zero_()
             return dist, idx, counts, stats
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        codes = [MVS_CLOUD_F64 if t.dtype == torch.float64 else MVS_CLOUD_F32 for t in (ref, query)]
         # P == 0: the library does not read ref; it gets the workspace's address in place of an empty tensor's
-        check(load().mvs_cloud_distance(ref.data_ptr() if P else ws.data_ptr(), codes[0], P, query.data_ptr(), codes[1], N,
-                                        ctypes.addressof(lo), ctypes.addressof(hi), float(cell), cap,
-                                        th.ctypes.data if T else None, T, dist.data_ptr(),
-                                        None if idx is None else idx.data_ptr(), counts.data_ptr(), stats.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), _stream(dev)))
+        check(load().mvs_cloud_distance(ref.data_ptr() if P else ws.data_ptr(), _xyz_code(ref), P, query.data_ptr(),
+                                        _xyz_code(query), N, lo, hi, float(cell), cap, th.ctypes.data if T else None, T,
+                                        dist.data_ptr(), None if idx is None else idx.data_ptr(), counts.data_ptr(),
+                                        stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
     return dist, idx, counts, stats
 
 

@@ -35,18 +35,18 @@ struct DistanceParams {
 };
 
 template <typename T>
-__global__ void __launch_bounds__(kKnnThreads) distance_classify_kernel(KnnGrid G, long long* members) {
-    knn_classify<T>(G, (long long)blockIdx.x * kKnnThreads + threadIdx.x, members);
+__global__ void __launch_bounds__(kCloudThreads) distance_classify_kernel(KnnGrid G, long long* members) {
+    knn_classify<T>(G, (long long)blockIdx.x * kCloudThreads + threadIdx.x, members);
 }
 
 template <typename T>
-__global__ void __launch_bounds__(kKnnThreads) distance_search_kernel(DistanceParams O) {
+__global__ void __launch_bounds__(kCloudThreads) distance_search_kernel(DistanceParams O) {
     const KnnGrid& G = O.G;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int M = G.P > 0 ? knn_members(G) : 0;
     for (int t = 0; t < kKnnPerWave; ++t) {
-        const long long i = ((long long)blockIdx.x * kKnnWaves + wave) * kKnnPerWave + t;
+        const long long i = ((long long)blockIdx.x * kCloudWaves + wave) * kKnnPerWave + t;
         if (i >= O.N) break;
         const T* src = static_cast<const T*>(O.query) + (size_t)i * 3;
         double q[3];
@@ -73,8 +73,8 @@ __global__ void __launch_bounds__(kKnnThreads) distance_search_kernel(DistancePa
     }
 }
 
-__global__ void __launch_bounds__(kKnnThreads) distance_count_kernel(DistanceParams O) {
-    const long long i = (long long)blockIdx.x * kKnnThreads + threadIdx.x;
+__global__ void __launch_bounds__(kCloudThreads) distance_count_kernel(DistanceParams O) {
+    const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
     const double d = i < O.N ? O.dist_out[i] : -1.0;
     const bool counted = d >= 0.0, within = counted && d < INFINITY;
     const bool first = (threadIdx.x & 63) == 0;
@@ -95,9 +95,8 @@ __global__ void distance_stats_kernel(const double* total, const long long* coun
     stats_out[1] = n_within > 0 ? *total / (double)n_within : 0.0;
 }
 
-static size_t distance_workspace(long long P, long long N, long long cells) {
-    return knn_workspace(P, cells) + 8 * (size_t)cloud_sum_partials(N) + MVS_DISTANCE_SCALARS;
-}
+// behind the grid's knn_workspace(P, cells): the sum tree's partials and the scalar block
+static size_t distance_tail(long long N) { return 8 * (size_t)cloud_sum_partials(N) + MVS_DISTANCE_SCALARS; }
 
 static int distance_check_n(const char* who, long long N) {
     if (N < 0 || N >= (1LL << 31)) return fail(MVS_ERR_BAD_SHAPE, "%s: N = %lld (need 0 <= N < 2^31)", who, N);
@@ -112,12 +111,12 @@ extern "C" {
 
 int mvs_query_distance_workspace(long long P, long long N, const double box_min[3], const double box_max[3], double cell,
                                  size_t* bytes) {
-    if (!bytes || !box_min || !box_max) return fail(MVS_ERR_NULL, "mvs_query_distance_workspace: NULL argument");
-    int n[3];
-    long long cells;
-    if (int rc = knn_check("mvs_query_distance_workspace", P, box_min, box_max, cell, n, &cells)) return rc;
+    size_t grid = 0;       // *bytes is written only once N has passed too
+    if (int rc = grid_query("mvs_query_distance_workspace", kCellGrid, P, box_min, box_max, cell, bytes ? &grid : nullptr,
+                            knn_workspace))
+        return rc;
     if (int rc = distance_check_n("mvs_query_distance_workspace", N)) return rc;
-    *bytes = distance_workspace(P, N, cells);
+    *bytes = grid + distance_tail(N);
     return MVS_OK;
 }
 
@@ -129,7 +128,7 @@ int mvs_cloud_distance(const void* ref_xyz, int ref_dtype, long long P, const vo
         return fail(MVS_ERR_NULL, "mvs_cloud_distance: NULL argument");
     int n[3];
     long long cells;
-    if (int rc = knn_check("mvs_cloud_distance", P, box_min, box_max, cell, n, &cells)) return rc;
+    if (int rc = grid_check("mvs_cloud_distance", kCellGrid, P, box_min, box_max, cell, n, &cells)) return rc;
     if (int rc = distance_check_n("mvs_cloud_distance", N)) return rc;
     if (T < 0 || T > MVS_DISTANCE_THRESHOLDS_MAX)
         return fail(MVS_ERR_BAD_SHAPE, "mvs_cloud_distance: T = %d (need 0 <= T <= %d)", T, MVS_DISTANCE_THRESHOLDS_MAX);
@@ -141,12 +140,9 @@ int mvs_cloud_distance(const void* ref_xyz, int ref_dtype, long long P, const vo
             return fail(MVS_ERR_BAD_SHAPE, "mvs_cloud_distance: thresholds[%d] = %g (need a finite threshold >= 0)", t,
                         thresholds[t]);
     for (int dtype : {ref_dtype, query_dtype})
-        if (dtype != MVS_CLOUD_F32 && dtype != MVS_CLOUD_F64)
-            return fail(MVS_ERR_BAD_DTYPE, "mvs_cloud_distance: xyz dtype %d (MVS_CLOUD_F32 or MVS_CLOUD_F64)", dtype);
-    const size_t need = distance_workspace(P, N, cells);
-    if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 8)
-        return fail(MVS_ERR_WORKSPACE, "mvs_cloud_distance: workspace of %zu bytes at %p, need %zu (8-byte aligned)",
-                    workspace_bytes, workspace, need);
+        if (int rc = check_xyz_dtype("mvs_cloud_distance", dtype)) return rc;
+    const size_t need = knn_workspace(P, cells) + distance_tail(N);
+    if (int rc = check_workspace8("mvs_cloud_distance", workspace, workspace_bytes, need)) return rc;
     DistanceParams O{};
     knn_bind(O.G, ref_xyz, P, box_min, box_max, cell, 1, n, cells, workspace);
     O.query = query_xyz;
@@ -167,17 +163,17 @@ int mvs_cloud_distance(const void* ref_xyz, int ref_dtype, long long P, const vo
         long long* members = reinterpret_cast<long long*>(scalars) + kScalarMembers;
         if (int rc = check_hip(hipMemsetAsync(members, 0, sizeof(long long), s), "zeroing the member count")) return rc;
         if (int rc = knn_build_begin(O.G, s)) return rc;
-        if (f64) distance_classify_kernel<double><<<knn_point_blocks(O.G), kKnnThreads, 0, s>>>(O.G, members);
-        else distance_classify_kernel<float><<<knn_point_blocks(O.G), kKnnThreads, 0, s>>>(O.G, members);
+        if (f64) distance_classify_kernel<double><<<knn_point_blocks(O.G), kCloudThreads, 0, s>>>(O.G, members);
+        else distance_classify_kernel<float><<<knn_point_blocks(O.G), kCloudThreads, 0, s>>>(O.G, members);
         if (int rc = check_hip(hipGetLastError(), "distance_classify_kernel")) return rc;
         if (int rc = knn_build_finish(O.G, f64, s)) return rc;
     }
-    const int per_block = kKnnWaves * kKnnPerWave;
+    const int per_block = kCloudWaves * kKnnPerWave;
     const int search_blocks = (int)((N + per_block - 1) / per_block);
-    if (query_dtype == MVS_CLOUD_F64) distance_search_kernel<double><<<search_blocks, kKnnThreads, 0, s>>>(O);
-    else distance_search_kernel<float><<<search_blocks, kKnnThreads, 0, s>>>(O);
+    if (query_dtype == MVS_CLOUD_F64) distance_search_kernel<double><<<search_blocks, kCloudThreads, 0, s>>>(O);
+    else distance_search_kernel<float><<<search_blocks, kCloudThreads, 0, s>>>(O);
     if (int rc = check_hip(hipGetLastError(), "distance_search_kernel")) return rc;
-    distance_count_kernel<<<(int)((N + kKnnThreads - 1) / kKnnThreads), kKnnThreads, 0, s>>>(O);
+    distance_count_kernel<<<(int)((N + kCloudThreads - 1) / kCloudThreads), kCloudThreads, 0, s>>>(O);
     if (int rc = check_hip(hipGetLastError(), "distance_count_kernel")) return rc;
     const double* total = nullptr;
     if (int rc = cloud_sum_tree(kSumFinite, dist_out, N, partials, scalars, s, &total)) return rc;

@@ -12,6 +12,8 @@
 //   cloud_count_kernel       one block per tile of kCloudTile voxels: ballot + popcount of count != 0 -> tiles[T]
 //   cloud_scan_kernel        one block: exclusive scan of the tile counts with a running carry; counts_out[1]
 //   cloud_emit_kernel        one block per tile: lanes ranked by mbcnt, one thread per occupied voxel writes its mean
+// The last three are cloud_common.h's tile_count, tile_scan_exclusive and tile_ranks around this file's flag (count != 0)
+// and its write per voxel; the in-box load and the host's checks of the box, the dtype and the workspace are there too.
 // A floating-point minimum and integer sums do not depend on the order of their operands, no block waits for another,
 // and linear voxel order is (iz, iy, ix) order: the same inputs give the same bytes on every run and stream.
 // mvs_cloud_downsample_normals (include/mvs_normals_abi.h) is the same launches with the accumulate and emit kernels'
@@ -19,24 +21,13 @@
 // their own behind the workspace of the plain call: the record and the plain call's kernels are what they were.
 // This file is compiled with -ffp-contract=off: voxel_index and voxel_corner are the header's fp64 restatement,
 // operation for operation, and the emit pass must recompute the very corner the accumulate pass subtracted.
-#include "mvs_cloud_abi.h"
-#include "mvs_normals_abi.h"
-#include "mvs_internal.h"
-
-#include <cmath>
+#include "cloud_common.h"
 
 namespace mvs {
 
 constexpr int kCloudChunk = MVS_CLOUD_CHUNK;
-constexpr int kCloudTile = MVS_CLOUD_TILE;
-constexpr int kCloudScanWidth = MVS_CLOUD_SCAN_WIDTH;
 constexpr int kCloudRecord = MVS_CLOUD_RECORD;
-constexpr int kCloudThreads = 256;
-constexpr int kCloudWaves = kCloudThreads / 64;
-constexpr int kCloudPasses = kCloudTile / kCloudThreads;
-constexpr int kCloudSlots = kCloudPasses * kCloudWaves;     // (pass, wave) groups of 64 voxels in a tile
-static_assert(kCloudChunk % kCloudThreads == 0 && kCloudTile % kCloudThreads == 0 && kCloudScanWidth % 64 == 0,
-              "whole waves");
+static_assert(kCloudChunk % kCloudThreads == 0, "whole waves");
 
 // one voxel: 64 bytes, zeroed before the accumulate pass
 struct CloudRecord {
@@ -80,18 +71,6 @@ struct CloudParams {
     int cells, n_tiles;
 };
 
-template <typename T>
-__device__ __forceinline__ bool cloud_load(const CloudParams& C, int i, double p[3]) {
-    const T* src = static_cast<const T*>(C.xyz) + (size_t)i * 3;
-    bool in = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        p[a] = (double)src[a];
-        in = in && C.bmin[a] <= p[a] && p[a] <= C.bmax[a];      // false for NaN
-    }
-    return in;
-}
-
 // the header's restatement: idx = floor((p - vmin) / v), corner = vmin + idx * v
 __device__ __forceinline__ double voxel_index(double p, double vmin, double v) { return floor((p - vmin) / v); }
 __device__ __forceinline__ double voxel_corner(double idx, double vmin, double v) { return vmin + idx * v; }
@@ -107,7 +86,7 @@ __global__ void __launch_bounds__(kCloudThreads) cloud_crop_min_kernel(CloudPara
     for (int k = 0; k < kCloudChunk / kCloudThreads; ++k) {
         const long long i = (long long)blockIdx.x * kCloudChunk + k * kCloudThreads + threadIdx.x;
         double p[3];
-        if (i < C.P && cloud_load<T>(C, (int)i, p)) {
+        if (i < C.P && box_load<T>(C.xyz, C.bmin, C.bmax, (int)i, p)) {
             ++kept;
 #pragma unroll
             for (int a = 0; a < 3; ++a) m[a] = p[a] < m[a] ? p[a] : m[a];
@@ -190,7 +169,7 @@ template <typename T, bool kNormals>
 __global__ void __launch_bounds__(kCloudThreads) cloud_accumulate_kernel(CloudParams C) {
     const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
     double p[3];
-    if (i >= C.P || !cloud_load<T>(C, (int)i, p)) return;
+    if (i >= C.P || !box_load<T>(C.xyz, C.bmin, C.bmax, (int)i, p)) return;
     long long fix[3];
     int idx[3];
 #pragma unroll
@@ -231,47 +210,13 @@ __device__ __forceinline__ unsigned cloud_cell(int pass) {
 }
 
 __global__ void __launch_bounds__(kCloudThreads) cloud_count_kernel(CloudParams C) {
-    __shared__ int wave_count[kCloudWaves];
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < kCloudPasses; ++i) n += __popcll(__ballot(cloud_flag(C, cloud_cell(i))));
-    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int wv = 0; wv < kCloudWaves; ++wv) s += wave_count[wv];
-        C.tiles[blockIdx.x] = s;
-    }
+    const int s = tile_count<kCloudPasses, kCloudThreads>([&](int i) { return cloud_flag(C, cloud_cell(i)); });
+    if (threadIdx.x == 0) C.tiles[blockIdx.x] = s;
 }
 
 __global__ void __launch_bounds__(kCloudScanWidth) cloud_scan_kernel(CloudParams C) {
-    __shared__ int wave_total[kCloudScanWidth / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int carry = 0;           // voxels before this pass; every thread holds the same value
-    for (long long base = 0; base < C.n_tiles; base += kCloudScanWidth) {
-        const long long i = base + tid;
-        const int v = i < C.n_tiles ? C.tiles[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int up = __shfl_up(incl, off);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_total[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int wv = 0; wv < kCloudScanWidth / 64; ++wv) {
-            const int c = wave_total[wv];
-            before += wv < wave ? c : 0;
-            total += c;
-        }
-        if (i < C.n_tiles) C.tiles[i] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();     // wave_total is rewritten by the next pass
-    }
-    if (tid == 0) {
+    const int carry = tile_scan_exclusive<kCloudScanWidth>(C.tiles, C.n_tiles);       // the occupied voxels
+    if (threadIdx.x == 0) {
         C.tiles[C.n_tiles] = carry;
         C.counts_out[1] = carry;
     }
@@ -279,25 +224,12 @@ __global__ void __launch_bounds__(kCloudScanWidth) cloud_scan_kernel(CloudParams
 
 template <bool kNormals>
 __global__ void __launch_bounds__(kCloudThreads) cloud_emit_kernel(CloudParams C) {
-    __shared__ int slot_count[kCloudSlots];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long ballots[kCloudPasses];
-#pragma unroll
-    for (int i = 0; i < kCloudPasses; ++i) {
-        ballots[i] = __ballot(cloud_flag(C, cloud_cell(i)));
-        if (lane == 0) slot_count[i * kCloudWaves + wave] = __popcll(ballots[i]);
-    }
-    __syncthreads();
     const long long tile_base = C.tiles[blockIdx.x];
-#pragma unroll
-    for (int i = 0; i < kCloudPasses; ++i) {
-        int before = 0;      // voxels of this tile in the (pass, wave) slots before this one
-#pragma unroll
-        for (int j = 0; j < kCloudSlots; ++j) before += j < i * kCloudWaves + wave ? slot_count[j] : 0;
-        const unsigned long long b = ballots[i];
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        const long long o = tile_base + before + rank;
-        if (((b >> lane) & 1ull) && o < C.capacity) {
+    tile_ranks<kCloudPasses, kCloudThreads>(
+        [&](int i) { return cloud_flag(C, cloud_cell(i)); },
+        [&](int i, int rank, bool set) {
+            const long long o = tile_base + rank;
+            if (!set || o >= C.capacity) return;
             const int cell = (int)cloud_cell(i);           // occupied, so below cells
             const CloudRecord r = C.grid[cell];
             const int plane = C.n[0] * C.n[1];
@@ -320,33 +252,7 @@ __global__ void __launch_bounds__(kCloudThreads) cloud_emit_kernel(CloudParams C
                     C.normals_out[(size_t)o * 3 + a] =
                         (float)(((double)C.nsum[(size_t)cell * 3 + a] / count) * (1.0 / 1073741824.0));
             }
-        }
-    }
-}
-
-// n[a] and their product; BAD_SHAPE for anything the header refuses about P, the box and the voxel size
-static int cloud_check(const char* who, long long P, const double* bmin, const double* bmax, double v, int n[3],
-                       long long* cells) {
-    if (P < 0 || P >= (1LL << 31))
-        return fail(MVS_ERR_BAD_SHAPE, "%s: P = %lld (need 0 <= P < 2^31)", who, P);
-    if (!std::isfinite(v) || v <= 0.0)
-        return fail(MVS_ERR_BAD_SHAPE, "%s: voxel_size = %g (need a finite size > 0)", who, v);
-    long long c = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(bmin[a]) || !std::isfinite(bmax[a]) || bmin[a] > bmax[a])
-            return fail(MVS_ERR_BAD_SHAPE, "%s: box axis %d is [%g, %g] (need finite bounds, min <= max)", who, a, bmin[a],
-                        bmax[a]);
-        const double na = std::floor((bmax[a] - bmin[a]) / v + 0.5) + 2.0;
-        if (!(na < 2147483648.0))          // also an infinite quotient
-            return fail(MVS_ERR_BAD_SHAPE, "%s: axis %d needs %g voxels (the grid must have fewer than 2^31 cells)", who, a,
-                        na);
-        n[a] = (int)na;
-        c *= n[a];                         // < 2^31 before this factor, so < 2^62 after it
-        if (c >= (1LL << 31))
-            return fail(MVS_ERR_BAD_SHAPE, "%s: the grid of the box at voxel_size %g has 2^31 cells or more", who, v);
-    }
-    *cells = c;
-    return MVS_OK;
+        });
 }
 
 static long long cloud_chunks(long long P) { return (P + kCloudChunk - 1) / kCloudChunk; }
@@ -358,6 +264,9 @@ static size_t cloud_workspace(long long P, long long cells) {
 }
 
 constexpr size_t kCloudNormalSums = 3 * sizeof(long long);     // per voxel, mvs_cloud_downsample_normals only
+static size_t cloud_normals_workspace(long long P, long long cells) {
+    return cloud_workspace(P, cells) + kCloudNormalSums * (size_t)cells;
+}
 
 // both entry points, after their NULL checks
 static int cloud_downsample(const char* who, bool with_normals, const void* xyz, int xyz_dtype, const unsigned char* rgb,
@@ -367,16 +276,13 @@ static int cloud_downsample(const char* who, bool with_normals, const void* xyz,
                             void* stream) {
     int n[3];
     long long cells;
-    if (int rc = cloud_check(who, P, box_min, box_max, voxel_size, n, &cells)) return rc;
+    if (int rc = grid_check(who, kVoxelGrid, P, box_min, box_max, voxel_size, n, &cells)) return rc;
     if (capacity < 0 || !std::isfinite(scale))
         return fail(MVS_ERR_BAD_SHAPE, "%s: capacity = %lld, scale = %g (need capacity >= 0 and a finite scale)", who, capacity,
                     scale);
-    if (xyz_dtype != MVS_CLOUD_F32 && xyz_dtype != MVS_CLOUD_F64)
-        return fail(MVS_ERR_BAD_DTYPE, "%s: xyz dtype %d (MVS_CLOUD_F32 or MVS_CLOUD_F64)", who, xyz_dtype);
-    const size_t need = cloud_workspace(P, cells) + (with_normals ? kCloudNormalSums * (size_t)cells : 0);
-    if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 8)
-        return fail(MVS_ERR_WORKSPACE, "%s: workspace of %zu bytes at %p, need %zu (8-byte aligned)", who, workspace_bytes,
-                    workspace, need);
+    if (int rc = check_xyz_dtype(who, xyz_dtype)) return rc;
+    const size_t need = with_normals ? cloud_normals_workspace(P, cells) : cloud_workspace(P, cells);
+    if (int rc = check_workspace8(who, workspace, workspace_bytes, need)) return rc;
     CloudParams C{};
     C.xyz = xyz;
     C.rgb = rgb;
@@ -446,12 +352,7 @@ extern "C" {
 
 int mvs_query_cloud_workspace(long long P, const double box_min[3], const double box_max[3], double voxel_size,
                               size_t* bytes) {
-    if (!bytes || !box_min || !box_max) return fail(MVS_ERR_NULL, "mvs_query_cloud_workspace: NULL argument");
-    int n[3];
-    long long cells;
-    if (int rc = cloud_check("mvs_query_cloud_workspace", P, box_min, box_max, voxel_size, n, &cells)) return rc;
-    *bytes = cloud_workspace(P, cells);
-    return MVS_OK;
+    return grid_query("mvs_query_cloud_workspace", kVoxelGrid, P, box_min, box_max, voxel_size, bytes, cloud_workspace);
 }
 
 int mvs_cloud_downsample(const void* xyz, int xyz_dtype, const unsigned char* rgb, long long P, const double box_min[3],
@@ -466,14 +367,8 @@ int mvs_cloud_downsample(const void* xyz, int xyz_dtype, const unsigned char* rg
 
 int mvs_query_cloud_normals_downsample_workspace(long long P, const double box_min[3], const double box_max[3],
                                                  double voxel_size, size_t* bytes) {
-    if (!bytes || !box_min || !box_max)
-        return fail(MVS_ERR_NULL, "mvs_query_cloud_normals_downsample_workspace: NULL argument");
-    int n[3];
-    long long cells;
-    if (int rc = cloud_check("mvs_query_cloud_normals_downsample_workspace", P, box_min, box_max, voxel_size, n, &cells))
-        return rc;
-    *bytes = cloud_workspace(P, cells) + kCloudNormalSums * (size_t)cells;
-    return MVS_OK;
+    return grid_query("mvs_query_cloud_normals_downsample_workspace", kVoxelGrid, P, box_min, box_max, voxel_size, bytes,
+                      cloud_normals_workspace);
 }
 
 int mvs_cloud_downsample_normals(const void* xyz, int xyz_dtype, const unsigned char* rgb, const float* normals, long long P,

@@ -31,26 +31,21 @@
 // All users are compiled with -ffp-contract=off: d2 and the cell index are the header's fp64 restatement.
 // knn_nearest keeps no list: each lane holds the best (d2, index) of the candidates it loaded; a ballot closes every ring
 // and one minimum over the wave the search.  Both searches walk the same rings (knn_walk).
-// The kernels here are static: each translation unit carries its own copy.
+// The kernels here are static: each translation unit that includes this header carries its own copy of them.  The tile
+// scan's loop, the in-box load, the grid check and the refusals are cloud_common.h's, shared with the fuse and the downsample.
 #pragma once
 
-#include "mvs_normals_abi.h"
-#include "mvs_internal.h"
+#include "cloud_common.h"
 
 #include <climits>
-#include <cmath>
 
 namespace mvs {
 
-constexpr int kKnnThreads = 256;
-constexpr int kKnnWaves = kKnnThreads / 64;
 constexpr int kKnnPerWave = 8;                    // members one wave of a search kernel serves
-constexpr int kKnnTile = MVS_NORMALS_TILE;        // cells per block of the two tile kernels: 4 per thread
-constexpr int kKnnScanWidth = 1024;
 constexpr double kKnnSlack = 1e-3;                // of a cell, see above
 constexpr int kKnnGroup = 16;                     // lanes that share one span in knn_nearest
 static_assert(MVS_NORMALS_KNN_MAX == 64, "one candidate per lane");
-static_assert(kKnnTile == 4 * kKnnThreads, "four cells per thread");
+static_assert(kCloudTile == 4 * kCloudThreads, "four cells per thread");
 
 struct KnnGrid {
     const void* xyz;
@@ -66,18 +61,6 @@ struct KnnGrid {
     int cells, n_tiles;
 };
 
-template <typename T>
-__device__ __forceinline__ bool knn_load(const KnnGrid& G, int i, double p[3]) {
-    const T* src = static_cast<const T*>(G.xyz) + (size_t)i * 3;
-    bool in = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        p[a] = (double)src[a];
-        in = in && G.bmin[a] <= p[a] && p[a] <= G.bmax[a];      // false for NaN
-    }
-    return in;
-}
-
 // the header's cell of a member; at most n - 1 by the header's argument, the clamp only keeps an access inside the grid
 __device__ __forceinline__ void knn_cell(const KnnGrid& G, const double p[3], int c[3]) {
 #pragma unroll
@@ -90,12 +73,12 @@ __device__ __forceinline__ int knn_linear(const KnnGrid& G, int x, int y, int z)
     return (z * G.n[1] + y) * G.n[0] + x;      // < cells < 2^31
 }
 
-// the body of a classify kernel of kKnnThreads threads, one per point, called by every thread of the block: is point i a
+// the body of a classify kernel of kCloudThreads threads, one per point, called by every thread of the block: is point i a
 // member?  A member is counted into its cell, and the members of each wave into *members, with integer atomics.
 template <typename T>
 __device__ __forceinline__ bool knn_classify(const KnnGrid& G, long long i, long long* members) {
     double p[3];
-    const bool member = i < G.P && knn_load<T>(G, (int)i, p);
+    const bool member = i < G.P && box_load<T>(G.xyz, G.bmin, G.bmax, (int)i, p);
     if (member) {
         int c[3];
         knn_cell(G, p, c);
@@ -111,9 +94,9 @@ __device__ __forceinline__ int knn_count(const KnnGrid& G, long long cell) {
     return cell < G.cells ? G.cells_end[cell] : 0;
 }
 
-static __global__ void __launch_bounds__(kKnnThreads) knn_tile_sum_kernel(KnnGrid G) {
-    __shared__ int wave_sum[kKnnWaves];
-    const long long base = (long long)blockIdx.x * kKnnTile + 4 * threadIdx.x;
+static __global__ void __launch_bounds__(kCloudThreads) knn_tile_sum_kernel(KnnGrid G) {
+    __shared__ int wave_sum[kCloudWaves];
+    const long long base = (long long)blockIdx.x * kCloudTile + 4 * threadIdx.x;
     int s = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) s += knn_count(G, base + k);
@@ -124,45 +107,21 @@ static __global__ void __launch_bounds__(kKnnThreads) knn_tile_sum_kernel(KnnGri
     if (threadIdx.x == 0) {
         int t = 0;
 #pragma unroll
-        for (int wv = 0; wv < kKnnWaves; ++wv) t += wave_sum[wv];
+        for (int wv = 0; wv < kCloudWaves; ++wv) t += wave_sum[wv];
         G.tiles[blockIdx.x] = t;
     }
 }
 
-// exclusive scan of the tile sums with a running carry (the pattern of cloud_scan_kernel); tiles[n_tiles] = M
-static __global__ void __launch_bounds__(kKnnScanWidth) knn_tile_scan_kernel(KnnGrid G) {
-    __shared__ int wave_total[kKnnScanWidth / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int carry = 0;
-    for (long long base = 0; base < G.n_tiles; base += kKnnScanWidth) {
-        const long long i = base + tid;
-        const int v = i < G.n_tiles ? G.tiles[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int up = __shfl_up(incl, off);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_total[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int wv = 0; wv < kKnnScanWidth / 64; ++wv) {
-            const int c = wave_total[wv];
-            before += wv < wave ? c : 0;
-            total += c;
-        }
-        if (i < G.n_tiles) G.tiles[i] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) G.tiles[G.n_tiles] = carry;
+// exclusive scan of the tile sums; tiles[n_tiles] = M
+static __global__ void __launch_bounds__(kCloudScanWidth) knn_tile_scan_kernel(KnnGrid G) {
+    const int carry = tile_scan_exclusive<kCloudScanWidth>(G.tiles, G.n_tiles);
+    if (threadIdx.x == 0) G.tiles[G.n_tiles] = carry;
 }
 
-static __global__ void __launch_bounds__(kKnnThreads) knn_cell_scan_kernel(KnnGrid G) {
-    __shared__ int wave_total[kKnnWaves];
+static __global__ void __launch_bounds__(kCloudThreads) knn_cell_scan_kernel(KnnGrid G) {
+    __shared__ int wave_total[kCloudWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long base = (long long)blockIdx.x * kKnnTile + 4 * threadIdx.x;
+    const long long base = (long long)blockIdx.x * kCloudTile + 4 * threadIdx.x;
     int v[4], mine = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -179,7 +138,7 @@ static __global__ void __launch_bounds__(kKnnThreads) knn_cell_scan_kernel(KnnGr
     __syncthreads();
     int run = G.tiles[blockIdx.x] + incl - mine;
 #pragma unroll
-    for (int wv = 0; wv < kKnnWaves; ++wv) run += wv < wave ? wave_total[wv] : 0;
+    for (int wv = 0; wv < kCloudWaves; ++wv) run += wv < wave ? wave_total[wv] : 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (base + k < G.cells) G.cells_end[base + k] = run;
@@ -188,10 +147,10 @@ static __global__ void __launch_bounds__(kKnnThreads) knn_cell_scan_kernel(KnnGr
 }
 
 template <typename T>
-static __global__ void __launch_bounds__(kKnnThreads) knn_scatter_kernel(KnnGrid G) {
-    const long long i = (long long)blockIdx.x * kKnnThreads + threadIdx.x;
+static __global__ void __launch_bounds__(kCloudThreads) knn_scatter_kernel(KnnGrid G) {
+    const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
     double p[3];
-    if (i >= G.P || !knn_load<T>(G, (int)i, p)) return;
+    if (i >= G.P || !box_load<T>(G.xyz, G.bmin, G.bmax, (int)i, p)) return;
     int c[3];
     knn_cell(G, p, c);
     const int slot = __hip_atomic_fetch_add(&G.cells_end[knn_linear(G, c[0], c[1], c[2])], 1, __ATOMIC_RELAXED,
@@ -448,36 +407,13 @@ __device__ __forceinline__ void knn_nearest(const KnnGrid& G, const double q[3],
 }
 
 // ---- host side
-// n[a] and their product; BAD_SHAPE for anything the header refuses about P, the box and the cell
-static int knn_check(const char* who, long long P, const double* bmin, const double* bmax, double cell, int n[3],
-                     long long* cells) {
-    if (P < 0 || P >= (1LL << 31)) return fail(MVS_ERR_BAD_SHAPE, "%s: P = %lld (need 0 <= P < 2^31)", who, P);
-    if (!std::isfinite(cell) || cell <= 0.0)
-        return fail(MVS_ERR_BAD_SHAPE, "%s: cell = %g (need a finite size > 0)", who, cell);
-    long long c = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(bmin[a]) || !std::isfinite(bmax[a]) || bmin[a] > bmax[a])
-            return fail(MVS_ERR_BAD_SHAPE, "%s: box axis %d is [%g, %g] (need finite bounds, min <= max)", who, a, bmin[a],
-                        bmax[a]);
-        const double na = std::floor((bmax[a] - bmin[a]) / cell) + 1.0;
-        if (!(na < 2147483648.0))          // also an infinite quotient
-            return fail(MVS_ERR_BAD_SHAPE, "%s: axis %d needs %g cells (the grid must have fewer than 2^31 cells)", who, a, na);
-        n[a] = (int)na;
-        c *= n[a];                         // < 2^31 before this factor, so < 2^62 after it
-        if (c >= (1LL << 31))
-            return fail(MVS_ERR_BAD_SHAPE, "%s: the grid of the box at cell %g has 2^31 cells or more", who, cell);
-    }
-    *cells = c;
-    return MVS_OK;
-}
-
-static long long knn_tiles(long long cells) { return (cells + kKnnTile - 1) / kKnnTile; }
+static long long knn_tiles(long long cells) { return (cells + kCloudTile - 1) / kCloudTile; }
 // mvs_query_normals_workspace: the sorted points and indices, the cells, the tiles
 static size_t knn_workspace(long long P, long long cells) {
     return 24 * (size_t)P + 8 * (size_t)((P + 1) / 2) + 8 * (size_t)((cells + 1) / 2) + 8 * (size_t)((knn_tiles(cells) + 2) / 2);
 }
 
-// G over a workspace of knn_workspace(P, cells) bytes, for a box and a cell that passed knn_check
+// G over a workspace of knn_workspace(P, cells) bytes, for a box and a cell that passed grid_check
 static void knn_bind(KnnGrid& G, const void* xyz, long long P, const double* box_min, const double* box_max, double cell,
                      int knn, const int n[3], long long cells, void* workspace) {
     G.xyz = xyz;
@@ -501,9 +437,9 @@ static void knn_bind(KnnGrid& G, const void* xyz, long long P, const double* box
     G.n_tiles = (int)knn_tiles(cells);
 }
 
-static int knn_point_blocks(const KnnGrid& G) { return (int)(((long long)G.P + kKnnThreads - 1) / kKnnThreads); }
+static int knn_point_blocks(const KnnGrid& G) { return (int)(((long long)G.P + kCloudThreads - 1) / kCloudThreads); }
 static int knn_search_blocks(const KnnGrid& G) {
-    const int per_block = kKnnWaves * kKnnPerWave;
+    const int per_block = kCloudWaves * kKnnPerWave;
     return (int)(((long long)G.P + per_block - 1) / per_block);
 }
 
@@ -514,14 +450,14 @@ static int knn_build_begin(const KnnGrid& G, hipStream_t s) {
 
 // after it: offsets, then the scatter
 static int knn_build_finish(const KnnGrid& G, bool f64, hipStream_t s) {
-    knn_tile_sum_kernel<<<G.n_tiles, kKnnThreads, 0, s>>>(G);
+    knn_tile_sum_kernel<<<G.n_tiles, kCloudThreads, 0, s>>>(G);
     if (int rc = check_hip(hipGetLastError(), "knn_tile_sum_kernel")) return rc;
-    knn_tile_scan_kernel<<<1, kKnnScanWidth, 0, s>>>(G);
+    knn_tile_scan_kernel<<<1, kCloudScanWidth, 0, s>>>(G);
     if (int rc = check_hip(hipGetLastError(), "knn_tile_scan_kernel")) return rc;
-    knn_cell_scan_kernel<<<G.n_tiles, kKnnThreads, 0, s>>>(G);
+    knn_cell_scan_kernel<<<G.n_tiles, kCloudThreads, 0, s>>>(G);
     if (int rc = check_hip(hipGetLastError(), "knn_cell_scan_kernel")) return rc;
-    if (f64) knn_scatter_kernel<double><<<knn_point_blocks(G), kKnnThreads, 0, s>>>(G);
-    else knn_scatter_kernel<float><<<knn_point_blocks(G), kKnnThreads, 0, s>>>(G);
+    if (f64) knn_scatter_kernel<double><<<knn_point_blocks(G), kCloudThreads, 0, s>>>(G);
+    else knn_scatter_kernel<float><<<knn_point_blocks(G), kCloudThreads, 0, s>>>(G);
     return check_hip(hipGetLastError(), "knn_scatter_kernel");
 }
 

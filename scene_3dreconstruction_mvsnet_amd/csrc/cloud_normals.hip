@@ -22,8 +22,8 @@ struct NormalsParams {
 };
 
 template <typename T>
-__global__ void __launch_bounds__(kKnnThreads) normals_classify_kernel(NormalsParams N) {
-    const long long i = (long long)blockIdx.x * kKnnThreads + threadIdx.x;
+__global__ void __launch_bounds__(kCloudThreads) normals_classify_kernel(NormalsParams N) {
+    const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
     const bool member = knn_classify<T>(N.G, i, &N.counts_out[0]);
     if (!member && i < N.G.P) {
 #pragma unroll
@@ -56,7 +56,7 @@ __device__ __forceinline__ void jacobi_rotate(double A[3][3], double V[3][3]) {
 }
 
 template <typename T>
-__global__ void __launch_bounds__(kKnnThreads) normals_search_kernel(NormalsParams N) {
+__global__ void __launch_bounds__(kCloudThreads) normals_search_kernel(NormalsParams N) {
     const KnnGrid& G = N.G;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(kKnnThreads) normals_search_kernel(NormalsPara
     const int m = M < G.knn ? M : G.knn;        // neighbours of every member
     long long estimated = 0, uncertified = 0;
     for (int t = 0; t < kKnnPerWave; ++t) {
-        const long long s = ((long long)blockIdx.x * kKnnWaves + wave) * kKnnPerWave + t;
+        const long long s = ((long long)blockIdx.x * kCloudWaves + wave) * kKnnPerWave + t;
         if (s >= M) break;
         const int i = G.sidx[s];
         if (i < 0 || i >= G.P) continue;        // cannot happen: the scatter filled every slot below M
@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(kKnnThreads) normals_search_kernel(NormalsPara
         double q[3] = {0.0, 0.0, 0.0};
         if (lane < m && L.idx != INT_MAX) {
             double tmp[3];
-            knn_load<T>(G, L.idx, tmp);
+            box_load<T>(G.xyz, G.bmin, G.bmax, L.idx, tmp);
 #pragma unroll
             for (int a = 0; a < 3; ++a) q[a] = tmp[a];
         }
@@ -181,12 +181,7 @@ using namespace mvs;
 extern "C" {
 
 int mvs_query_normals_workspace(long long P, const double box_min[3], const double box_max[3], double cell, size_t* bytes) {
-    if (!bytes || !box_min || !box_max) return fail(MVS_ERR_NULL, "mvs_query_normals_workspace: NULL argument");
-    int n[3];
-    long long cells;
-    if (int rc = knn_check("mvs_query_normals_workspace", P, box_min, box_max, cell, n, &cells)) return rc;
-    *bytes = knn_workspace(P, cells);
-    return MVS_OK;
+    return grid_query("mvs_query_normals_workspace", kCellGrid, P, box_min, box_max, cell, bytes, knn_workspace);
 }
 
 int mvs_cloud_normals(const void* xyz, int xyz_dtype, long long P, const double box_min[3], const double box_max[3],
@@ -200,15 +195,11 @@ int mvs_cloud_normals(const void* xyz, int xyz_dtype, long long P, const double 
                     R);
     int n[3];
     long long cells;
-    if (int rc = knn_check("mvs_cloud_normals", P, box_min, box_max, cell, n, &cells)) return rc;
+    if (int rc = grid_check("mvs_cloud_normals", kCellGrid, P, box_min, box_max, cell, n, &cells)) return rc;
     if (knn < 3 || knn > MVS_NORMALS_KNN_MAX)
         return fail(MVS_ERR_BAD_SHAPE, "mvs_cloud_normals: knn = %d (need 3 <= knn <= %d)", knn, MVS_NORMALS_KNN_MAX);
-    if (xyz_dtype != MVS_CLOUD_F32 && xyz_dtype != MVS_CLOUD_F64)
-        return fail(MVS_ERR_BAD_DTYPE, "mvs_cloud_normals: xyz dtype %d (MVS_CLOUD_F32 or MVS_CLOUD_F64)", xyz_dtype);
-    const size_t need = knn_workspace(P, cells);
-    if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 8)
-        return fail(MVS_ERR_WORKSPACE, "mvs_cloud_normals: workspace of %zu bytes at %p, need %zu (8-byte aligned)",
-                    workspace_bytes, workspace, need);
+    if (int rc = check_xyz_dtype("mvs_cloud_normals", xyz_dtype)) return rc;
+    if (int rc = check_workspace8("mvs_cloud_normals", workspace, workspace_bytes, knn_workspace(P, cells))) return rc;
     NormalsParams N{};
     knn_bind(N.G, xyz, P, box_min, box_max, cell, knn, n, cells, workspace);
     N.view_starts = view_starts;
@@ -222,13 +213,13 @@ int mvs_cloud_normals(const void* xyz, int xyz_dtype, long long P, const double 
     if (int rc = check_hip(hipMemsetAsync(counts_out, 0, 3 * sizeof(long long), s), "zeroing the counts")) return rc;
     if (P == 0) return MVS_OK;
     if (int rc = knn_build_begin(N.G, s)) return rc;
-    if (f64) normals_classify_kernel<double><<<knn_point_blocks(N.G), kKnnThreads, 0, s>>>(N);
-    else normals_classify_kernel<float><<<knn_point_blocks(N.G), kKnnThreads, 0, s>>>(N);
+    if (f64) normals_classify_kernel<double><<<knn_point_blocks(N.G), kCloudThreads, 0, s>>>(N);
+    else normals_classify_kernel<float><<<knn_point_blocks(N.G), kCloudThreads, 0, s>>>(N);
     if (int rc = check_hip(hipGetLastError(), "normals_classify_kernel")) return rc;
     if (int rc = knn_build_finish(N.G, f64, s)) return rc;
     const int search_blocks = knn_search_blocks(N.G);
-    if (f64) normals_search_kernel<double><<<search_blocks, kKnnThreads, 0, s>>>(N);
-    else normals_search_kernel<float><<<search_blocks, kKnnThreads, 0, s>>>(N);
+    if (f64) normals_search_kernel<double><<<search_blocks, kCloudThreads, 0, s>>>(N);
+    else normals_search_kernel<float><<<search_blocks, kCloudThreads, 0, s>>>(N);
     return check_hip(hipGetLastError(), "normals_search_kernel");
 }
 

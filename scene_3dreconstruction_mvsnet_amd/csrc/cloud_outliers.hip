@@ -40,9 +40,9 @@ template <> struct OutliersBits<double> {
 };
 
 template <typename T>
-__global__ void __launch_bounds__(kKnnThreads) outliers_classify_kernel(OutliersParams O) {
+__global__ void __launch_bounds__(kCloudThreads) outliers_classify_kernel(OutliersParams O) {
     using U = typename OutliersBits<T>::type;
-    const long long i = (long long)blockIdx.x * kKnnThreads + threadIdx.x;
+    const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
     const bool member = knn_classify<T>(O.G, i, &O.counts_out[0]);
     if (!member && i < O.G.P) {
         O.dist_out[i] = -1.0;
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(kKnnThreads) outliers_classify_kernel(Outliers
     }
 }
 
-__global__ void __launch_bounds__(kKnnThreads) outliers_search_kernel(OutliersParams O) {
+__global__ void __launch_bounds__(kCloudThreads) outliers_search_kernel(OutliersParams O) {
     const KnnGrid& G = O.G;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(kKnnThreads) outliers_search_kernel(OutliersPa
     const int m = M < G.knn ? M : G.knn;        // neighbours of every member
     long long valid = 0;
     for (int t = 0; t < kKnnPerWave; ++t) {
-        const long long s = ((long long)blockIdx.x * kKnnWaves + wave) * kKnnPerWave + t;
+        const long long s = ((long long)blockIdx.x * kCloudWaves + wave) * kKnnPerWave + t;
         if (s >= M) break;
         const int i = G.sidx[s];
         if (i < 0 || i >= G.P) continue;        // cannot happen: the scatter filled every slot below M
@@ -103,9 +103,9 @@ __global__ void outliers_stats_kernel(const double* total, const long long* coun
 
 // members only: the classify pass wrote the non-members
 template <typename T>
-__global__ void __launch_bounds__(kKnnThreads) outliers_mark_kernel(OutliersParams O, const double* scalars) {
+__global__ void __launch_bounds__(kCloudThreads) outliers_mark_kernel(OutliersParams O, const double* scalars) {
     using U = typename OutliersBits<T>::type;
-    const long long i = (long long)blockIdx.x * kKnnThreads + threadIdx.x;
+    const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
     const double d = i < O.G.P ? O.dist_out[i] : -1.0;
     const bool member = d >= 0.0;
     const bool keep = d > 0.0 && d < scalars[kScalarThreshold];
@@ -134,12 +134,7 @@ using namespace mvs;
 extern "C" {
 
 int mvs_query_outliers_workspace(long long P, const double box_min[3], const double box_max[3], double cell, size_t* bytes) {
-    if (!bytes || !box_min || !box_max) return fail(MVS_ERR_NULL, "mvs_query_outliers_workspace: NULL argument");
-    int n[3];
-    long long cells;
-    if (int rc = knn_check("mvs_query_outliers_workspace", P, box_min, box_max, cell, n, &cells)) return rc;
-    *bytes = outliers_workspace(P, cells);
-    return MVS_OK;
+    return grid_query("mvs_query_outliers_workspace", kCellGrid, P, box_min, box_max, cell, bytes, outliers_workspace);
 }
 
 int mvs_cloud_outliers(const void* xyz, int xyz_dtype, long long P, const double box_min[3], const double box_max[3],
@@ -150,18 +145,14 @@ int mvs_cloud_outliers(const void* xyz, int xyz_dtype, long long P, const double
         return fail(MVS_ERR_NULL, "mvs_cloud_outliers: NULL argument");
     int n[3];
     long long cells;
-    if (int rc = knn_check("mvs_cloud_outliers", P, box_min, box_max, cell, n, &cells)) return rc;
+    if (int rc = grid_check("mvs_cloud_outliers", kCellGrid, P, box_min, box_max, cell, n, &cells)) return rc;
     if (nb_neighbors < 2 || nb_neighbors > MVS_NORMALS_KNN_MAX)
         return fail(MVS_ERR_BAD_SHAPE, "mvs_cloud_outliers: nb_neighbors = %d (need 2 <= nb_neighbors <= %d)", nb_neighbors,
                     MVS_NORMALS_KNN_MAX);
     if (!std::isfinite(std_ratio) || std_ratio <= 0.0)
         return fail(MVS_ERR_BAD_SHAPE, "mvs_cloud_outliers: std_ratio = %g (need a finite ratio > 0)", std_ratio);
-    if (xyz_dtype != MVS_CLOUD_F32 && xyz_dtype != MVS_CLOUD_F64)
-        return fail(MVS_ERR_BAD_DTYPE, "mvs_cloud_outliers: xyz dtype %d (MVS_CLOUD_F32 or MVS_CLOUD_F64)", xyz_dtype);
-    const size_t need = outliers_workspace(P, cells);
-    if (workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 8)
-        return fail(MVS_ERR_WORKSPACE, "mvs_cloud_outliers: workspace of %zu bytes at %p, need %zu (8-byte aligned)",
-                    workspace_bytes, workspace, need);
+    if (int rc = check_xyz_dtype("mvs_cloud_outliers", xyz_dtype)) return rc;
+    if (int rc = check_workspace8("mvs_cloud_outliers", workspace, workspace_bytes, outliers_workspace(P, cells))) return rc;
     OutliersParams O{};
     knn_bind(O.G, xyz, P, box_min, box_max, cell, nb_neighbors, n, cells, workspace);
     O.dist_out = dist_out;
@@ -176,11 +167,11 @@ int mvs_cloud_outliers(const void* xyz, int xyz_dtype, long long P, const double
     if (P == 0) return check_hip(hipMemsetAsync(stats_out, 0, 3 * sizeof(double), s), "zeroing the statistics");
     if (int rc = knn_build_begin(O.G, s)) return rc;
     const int blocks = knn_point_blocks(O.G);
-    if (f64) outliers_classify_kernel<double><<<blocks, kKnnThreads, 0, s>>>(O);
-    else outliers_classify_kernel<float><<<blocks, kKnnThreads, 0, s>>>(O);
+    if (f64) outliers_classify_kernel<double><<<blocks, kCloudThreads, 0, s>>>(O);
+    else outliers_classify_kernel<float><<<blocks, kCloudThreads, 0, s>>>(O);
     if (int rc = check_hip(hipGetLastError(), "outliers_classify_kernel")) return rc;
     if (int rc = knn_build_finish(O.G, f64, s)) return rc;
-    outliers_search_kernel<<<knn_search_blocks(O.G), kKnnThreads, 0, s>>>(O);
+    outliers_search_kernel<<<knn_search_blocks(O.G), kCloudThreads, 0, s>>>(O);
     if (int rc = check_hip(hipGetLastError(), "outliers_search_kernel")) return rc;
     const double* total = nullptr;
     if (int rc = cloud_sum_tree(kSumPositive, dist_out, P, partials, scalars, s, &total)) return rc;
@@ -189,8 +180,8 @@ int mvs_cloud_outliers(const void* xyz, int xyz_dtype, long long P, const double
     if (int rc = cloud_sum_tree(kSumDeviation, dist_out, P, partials, scalars, s, &total)) return rc;
     outliers_stats_kernel<<<1, 1, 0, s>>>(total, counts_out, std_ratio, scalars, stats_out);
     if (int rc = check_hip(hipGetLastError(), "outliers_stats_kernel")) return rc;
-    if (f64) outliers_mark_kernel<double><<<blocks, kKnnThreads, 0, s>>>(O, scalars);
-    else outliers_mark_kernel<float><<<blocks, kKnnThreads, 0, s>>>(O, scalars);
+    if (f64) outliers_mark_kernel<double><<<blocks, kCloudThreads, 0, s>>>(O, scalars);
+    else outliers_mark_kernel<float><<<blocks, kCloudThreads, 0, s>>>(O, scalars);
     return check_hip(hipGetLastError(), "outliers_mark_kernel");
 }
 

@@ -1,30 +1,24 @@
 // fuse_points.hip -- ordered compaction of a scan's filtered depth maps into one coloured point cloud
 // (reference eval.py:745-758: xyz_world[final], img[1::4, 1::4][final], np.concatenate over the views).
 //
-// A tile is kFuseTile consecutive pixels of ONE view; tile T = r * tiles_per_view + t, so tile order is the output
+// A tile is kCloudTile consecutive pixels of ONE view; tile T = r * tiles_per_view + t, so tile order is the output
 // order.  Three launches, ordered by the stream alone:
 //   fuse_count_kernel    one block per tile: ballot + popcount of the final mask per wave, waves added through LDS
 //                        -> workspace[T]
-//   fuse_scan_kernel     one block: exclusive scan of workspace[0 .. tiles) in place, kFuseScanWidth tiles per pass
+//   fuse_scan_kernel     one block: exclusive scan of workspace[0 .. tiles) in place, kCloudScanWidth tiles per pass
 //                        with a running carry; workspace[tiles] = total; counts_out from the view boundaries
 //   fuse_scatter_kernel  one block per tile: the same ballots again, lanes ranked by mbcnt, points written at
 //                        workspace[T] + rank while rank < capacity
+// The count, the scan loop and the ranks are cloud_common.h's tile_count, tile_scan_exclusive and tile_ranks (shared with
+// cloud_downsample.hip and cloud_knn.h); this file supplies the flag of a pixel and what is written per selected point.
 // No block waits for another block and nothing is atomic: the output is the same bytes on every run and stream.
 // Within a tile, pass i of a block covers pixels [i * 256, (i + 1) * 256): wave wv its 64 lanes in order, so
 // (pass, wave, lane) is the pixel order.  Mask bytes are read twice (1 B per pixel each); only selected pixels read
 // their 24 B of xyz_world and 3 colour bytes.
 #include "mvs_fuse_abi.h"
-#include "mvs_internal.h"
+#include "cloud_common.h"
 
 namespace mvs {
-
-constexpr int kFuseTile = MVS_FUSE_TILE;
-constexpr int kFuseThreads = 256;
-constexpr int kFuseWaves = kFuseThreads / 64;
-constexpr int kFusePasses = kFuseTile / kFuseThreads;
-constexpr int kFuseSlots = kFusePasses * kFuseWaves;      // (pass, wave) groups of 64 pixels in a tile
-constexpr int kFuseScanWidth = MVS_FUSE_SCAN_WIDTH;
-static_assert(kFuseTile % kFuseThreads == 0 && kFuseThreads % 64 == 0 && kFuseScanWidth % 64 == 0, "whole waves");
 
 struct FuseParams {
     const double* xyz;
@@ -47,88 +41,40 @@ __device__ __forceinline__ bool fuse_flag(const FuseParams& P, bool view_ok, int
     return view_ok && p < (unsigned)P.hw && P.masks[((size_t)r * 3 + 2) * P.hw + p] != 0;
 }
 __device__ __forceinline__ unsigned fuse_pixel(int t, int pass) {
-    return (unsigned)t * kFuseTile + pass * kFuseThreads + threadIdx.x;
+    return (unsigned)t * kCloudTile + pass * kCloudThreads + threadIdx.x;
 }
 
-__global__ void __launch_bounds__(kFuseThreads) fuse_count_kernel(FuseParams P) {
-    __shared__ int wave_count[kFuseWaves];
+__global__ void __launch_bounds__(kCloudThreads) fuse_count_kernel(FuseParams P) {
     const int T = blockIdx.x;
     const int r = T / P.tiles_per_view, t = T - r * P.tiles_per_view;
     const int ref = P.ref_idx[r];
     const bool view_ok = ref >= 0 && ref < P.V;
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < kFusePasses; ++i) {
-        n += __popcll(__ballot(fuse_flag(P, view_ok, r, fuse_pixel(t, i))));
-    }
-    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int wv = 0; wv < kFuseWaves; ++wv) s += wave_count[wv];
-        P.tiles[T] = s;
-    }
+    const int s = tile_count<kCloudPasses, kCloudThreads>([&P, view_ok, r, t](int i) { return fuse_flag(P, view_ok, r, fuse_pixel(t, i)); });
+    if (threadIdx.x == 0) P.tiles[T] = s;
 }
 
-__global__ void __launch_bounds__(kFuseScanWidth) fuse_scan_kernel(FuseParams P) {
-    __shared__ int wave_total[kFuseScanWidth / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int carry = 0;           // points before this pass; every thread holds the same value
-    for (long long base = 0; base < P.n_tiles; base += kFuseScanWidth) {
-        const long long i = base + tid;
-        const int v = i < P.n_tiles ? P.tiles[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int up = __shfl_up(incl, off);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_total[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int wv = 0; wv < kFuseScanWidth / 64; ++wv) {
-            const int c = wave_total[wv];
-            before += wv < wave ? c : 0;
-            total += c;
-        }
-        if (i < P.n_tiles) P.tiles[i] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();     // wave_total is rewritten by the next pass
-    }
+__global__ void __launch_bounds__(kCloudScanWidth) fuse_scan_kernel(FuseParams P) {
+    const int tid = threadIdx.x;
+    const int carry = tile_scan_exclusive<kCloudScanWidth>(P.tiles, P.n_tiles);       // the points of the scan
     if (tid == 0) P.tiles[P.n_tiles] = carry;
     __syncthreads();         // the offsets this block wrote are read back below
-    for (int r = tid; r < P.R; r += kFuseScanWidth)
+    for (int r = tid; r < P.R; r += kCloudScanWidth)
         P.counts_out[r] = P.tiles[(r + 1) * P.tiles_per_view] - P.tiles[r * P.tiles_per_view];
     if (tid == 0) P.counts_out[P.R] = carry;
 }
 
-__global__ void __launch_bounds__(kFuseThreads) fuse_scatter_kernel(FuseParams P) {
-    __shared__ int slot_count[kFuseSlots];
+__global__ void __launch_bounds__(kCloudThreads) fuse_scatter_kernel(FuseParams P) {
     const int T = blockIdx.x;
     const int r = T / P.tiles_per_view, t = T - r * P.tiles_per_view;
     const int ref = P.ref_idx[r];
     const bool view_ok = ref >= 0 && ref < P.V;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long ballots[kFusePasses];
-#pragma unroll
-    for (int i = 0; i < kFusePasses; ++i) {
-        ballots[i] = __ballot(fuse_flag(P, view_ok, r, fuse_pixel(t, i)));
-        if (lane == 0) slot_count[i * kFuseWaves + wave] = __popcll(ballots[i]);
-    }
-    __syncthreads();
     const long long tile_base = P.tiles[T];
     const size_t H = (size_t)4 * P.h, W = (size_t)4 * P.w;   // image rows and columns
-#pragma unroll
-    for (int i = 0; i < kFusePasses; ++i) {
-        int before = 0;      // points of this tile in the (pass, wave) slots before this one
-#pragma unroll
-        for (int j = 0; j < kFuseSlots; ++j) before += j < i * kFuseWaves + wave ? slot_count[j] : 0;
-        const unsigned long long b = ballots[i];
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        const long long o = tile_base + before + rank;
-        if (((b >> lane) & 1ull) && o < P.capacity) {
+    tile_ranks<kCloudPasses, kCloudThreads>(
+        [&P, view_ok, r, t](int i) { return fuse_flag(P, view_ok, r, fuse_pixel(t, i)); },
+        [=, &P](int i, int rank, bool set) {
+            const long long o = tile_base + rank;
+            if (!set || o >= P.capacity) return;
             const int p = (int)fuse_pixel(t, i);       // selected, so below h*w
             const double* src = P.xyz + ((size_t)r * P.hw + p) * 3;
             float* dst = P.xyz_out + (size_t)o * 3;
@@ -150,8 +96,7 @@ __global__ void __launch_bounds__(kFuseThreads) fuse_scatter_kernel(FuseParams P
                 c[1] = s[plane];
                 c[2] = s[2 * plane];
             }
-        }
-    }
+        });
 }
 
 static int fuse_check(int R, int h, int w) {
@@ -160,7 +105,7 @@ static int fuse_check(int R, int h, int w) {
     return MVS_OK;
 }
 
-static int fuse_tiles_per_view(int h, int w) { return (int)(((long long)h * w + kFuseTile - 1) / kFuseTile); }
+static int fuse_tiles_per_view(int h, int w) { return (int)(((long long)h * w + kCloudTile - 1) / kCloudTile); }
 
 static size_t fuse_workspace(int R, int h, int w) {
     return sizeof(int) * ((size_t)R * fuse_tiles_per_view(h, w) + 1);
@@ -215,11 +160,11 @@ int mvs_fuse_points(const double* xyz_world, const unsigned char* masks, const v
     P.n_tiles = R * P.tiles_per_view;      // <= R*h*w < 2^31
     P.hwc = image_format == MVS_IMG_U8_HWC;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    fuse_count_kernel<<<P.n_tiles, kFuseThreads, 0, s>>>(P);
+    fuse_count_kernel<<<P.n_tiles, kCloudThreads, 0, s>>>(P);
     if (int rc = check_hip(hipGetLastError(), "fuse_count_kernel")) return rc;
-    fuse_scan_kernel<<<1, kFuseScanWidth, 0, s>>>(P);
+    fuse_scan_kernel<<<1, kCloudScanWidth, 0, s>>>(P);
     if (int rc = check_hip(hipGetLastError(), "fuse_scan_kernel")) return rc;
-    fuse_scatter_kernel<<<P.n_tiles, kFuseThreads, 0, s>>>(P);
+    fuse_scatter_kernel<<<P.n_tiles, kCloudThreads, 0, s>>>(P);
     return check_hip(hipGetLastError(), "fuse_scatter_kernel");
 }
 

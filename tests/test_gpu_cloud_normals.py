@@ -4,7 +4,6 @@ bound normals_ref derives (eigenvector perturbation over the gap + float32 round
 rule for every member without exception.  The buffers of the two entry points lie between guards and are poisoned."""
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,20 +11,14 @@ import torch
 
 import cloud_ref
 import guarded as G
+from cloud_testing import DEV, assert_guarded_coverage, cu, dataset, read_ply
 import normals_ref as NR
 from conftest import load_weights
-from test_cloud_normals_host import read_ply_with_normals
-from scene_3dreconstruction_mvsnet_amd import MVSNet, _lib, fusion
+from scene_3dreconstruction_mvsnet_amd import _lib, fusion
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-HERE = os.path.dirname(os.path.abspath(__file__))
 BOX = ((-290.0, -190.0, -60.0), (290.0, 190.0, 160.0))        # inside the 600 x 400 scene: some points fall out
 DTYPES = {"f32": np.float32, "f64": np.float64}
-
-
-def cu(a):
-    return torch.from_numpy(np.array(a, order="C")).to(DEV)
 
 
 @functools.lru_cache(maxsize=None)
@@ -150,6 +143,43 @@ def test_f64_points_that_are_no_float32():
     got = run(xyz, BOX, 30)
     assert_exact(got, want, "f64")
     assert_normals(got[0], want, xyz, "f64")
+
+
+TWO_PASS_BOX, TWO_PASS_CELL = ((0.0, 0.0, 0.0), (48.0, 48.0, 32.0)), 0.375      # 0.375 is exact in binary
+
+
+@functools.lru_cache(maxsize=None)
+def two_pass_scene():
+    """Two clusters of 200 points, each strictly inside a 3-unit cube of TWO_PASS_BOX: one at the low corner, one with z in
+    [28, 31]; each two tilted sheets of 10 x 10 jittered lattice points one unit apart, so that five neighbours determine a
+    normal -> (xyz float32 [400,3] (read-only), linear cell index int64 [400], the yardstick at knn = 5)."""
+    rng = np.random.default_rng(6)
+    i, j, k = (g.reshape(-1).astype(np.float64) for g in np.meshgrid(np.arange(10), np.arange(10), np.arange(4), indexing="ij"))
+    sheet = np.column_stack([0.2 + 0.28 * i, 0.2 + 0.28 * j, 0.8 + (k % 2)]) + rng.normal(0.0, [0.03, 0.03, 0.01], (400, 3))
+    sheet[:, 2] += 0.3 * (sheet[:, 0] - 1.5)
+    corners = np.where((k < 2)[:, None], [0.0, 0.0, 0.0], [40.0, 40.0, 28.0])     # sheets 0, 1 low, sheets 2, 3 high
+    assert (sheet > 0.04).all() and (sheet < 2.96).all()
+    xyz = (corners + sheet)[rng.permutation(400)].astype(np.float32)
+    xyz.setflags(write=False)
+    n = NR.grid_shape(*TWO_PASS_BOX, TWO_PASS_CELL)
+    c = np.floor((xyz.astype(np.float64) - np.asarray(TWO_PASS_BOX[0])) / TWO_PASS_CELL).astype(np.int64)
+    return xyz, (c[:, 2] * n[1] + c[:, 1]) * n[0] + c[:, 0], NR.estimate(xyz, *TWO_PASS_BOX, 5)
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+def test_a_knn_grid_of_more_tiles_than_one_pass_of_the_tile_scan(dtype):
+    """1,398 tiles of cell counts: the tile scan's second pass starts from the carry of its first, and every member of the
+    upper cluster takes its offset from there."""
+    xyz, linear, want = two_pass_scene()
+    n = NR.grid_shape(*TWO_PASS_BOX, TWO_PASS_CELL)
+    assert n == [129, 129, 86]
+    tiles = -(-(n[0] * n[1] * n[2]) // _lib.NORMALS_TILE)
+    assert n[0] * n[1] * n[2] == 1431126 and tiles == 1398 > _lib.CLOUD_SCAN_WIDTH      # the scan width is one for all grids
+    first_pass = _lib.CLOUD_SCAN_WIDTH * _lib.NORMALS_TILE                               # cells the first pass covers
+    assert want["member"].all() and (linear < first_pass).sum() >= 100 and (linear >= first_pass).sum() >= 100
+    got = run(xyz.astype(DTYPES[dtype]), TWO_PASS_BOX, 5, cell=TWO_PASS_CELL)
+    assert_exact(got, want, f"two passes {dtype}")
+    assert_normals(got[0], want, xyz, f"two passes {dtype}")
 
 
 @pytest.mark.parametrize("dtype", list(DTYPES))
@@ -297,21 +327,12 @@ def test_cloud_normals_enqueues_without_a_host_synchronisation():
 
 
 # ---------------------------------------------------------------- guarded buffers
-def normals_device_entry_points():
-    with open(os.path.join(os.path.dirname(HERE), "include", "mvs_normals_abi.h")) as f:
-        names = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", f.read(), re.M)
-    return [n for n in names if not n.startswith("mvs_query_")]
-
-
 GUARDED_ENTRIES = {"mvs_cloud_normals": "test_normals_buffers_between_guards_under_every_poison",
                    "mvs_cloud_downsample_normals": "test_downsample_normals_buffers_between_guards_under_every_poison"}
 
 
 def test_every_device_entry_point_of_the_normals_header_has_a_guarded_case():
-    names = normals_device_entry_points()
-    assert names and set(names) == set(GUARDED_ENTRIES), (names, sorted(GUARDED_ENTRIES))
-    for test in GUARDED_ENTRIES.values():
-        assert callable(globals()[test])
+    assert_guarded_coverage("mvs_normals_abi.h", GUARDED_ENTRIES, globals())
 
 
 @pytest.mark.parametrize("dtype", list(DTYPES))
@@ -471,19 +492,8 @@ def test_estimate_normals_defaults_to_the_bounding_box_of_the_finite_points():
 
 
 # ---------------------------------------------------------------- the chain
-def _dataset(tmp_path):
-    from synthetic_dataset import write_synthetic_dataset
-    from scene_3dreconstruction_mvsnet_amd.dataset_eval import EvalDataset
-    listfile = write_synthetic_dataset(str(tmp_path))
-    ds = EvalDataset(os.path.join(str(tmp_path), "data"), listfile, "test", nviews=3, ndepths=16, interval_scale=1.06,
-                     img_res=(96, 128), dataset_name="dtu")
-    model = MVSNet(refine=False)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in load_weights().items()})
-    return ds, model, listfile
-
-
 def test_reconstruct_scan_with_normals_equals_the_steps_by_hand(tmp_path):
-    ds, model, _ = _dataset(tmp_path)
+    ds, model, _ = dataset(tmp_path)
     thr = dict(geomask=0, photomask=0.0, device=DEV)        # thresholds that keep every pixel
     plain = fusion.reconstruct_scan(model, ds, "scan1", **thr)
     finite = plain[0][np.isfinite(plain[0]).all(axis=1)].astype(np.float64)
@@ -519,7 +529,7 @@ def test_reconstruct_scan_with_normals_equals_the_steps_by_hand(tmp_path):
     assert cnt.tolist() == want["counts"]
     assert_normals(nrm.cpu().numpy(), want, plain[0], "chain", list(np.arange(len(refs) + 1) * per_view), centres)
     # the PLY holds the returned arrays bit for bit; the file without normals is today's
-    px, pc, pn = read_ply_with_normals(small_n)
+    px, pc, pn = read_ply(small_n, normals=True)
     assert px.tobytes() == got[2].tobytes() and pc.tobytes() == got[3].tobytes() and pn.tobytes() == got[4].tobytes()
     body = lambda path: open(path, "rb").read()      # noqa: E731
     assert b"property float nx" not in body(small) and len(body(small_n)) > len(body(small))
@@ -527,7 +537,7 @@ def test_reconstruct_scan_with_normals_equals_the_steps_by_hand(tmp_path):
 
 def test_the_command_line_flag_writes_the_same_file(tmp_path):
     from scene_3dreconstruction_mvsnet_amd import reconstruct
-    ds, model, listfile = _dataset(tmp_path)
+    ds, model, listfile = dataset(tmp_path)
     torch.save({"model": {k: torch.from_numpy(v) for k, v in load_weights().items()}}, str(tmp_path / "model.ckpt"))
     out = tmp_path / "plys"
     common = ["--testpath", os.path.join(str(tmp_path), "data"), "--testlist", listfile, "--loadckpt",
@@ -547,6 +557,6 @@ def test_the_command_line_flag_writes_the_same_file(tmp_path):
     got = fusion.reconstruct_scan(model, ds, "scan1", geomask=0, photomask=0.0, device=DEV,
                                   downsample=dict(voxel_size=v, box=(box[:3], box[3:]), scale=1.0,
                                                   normals=dict(knn=8, margin=2 * v)))
-    px, pc, pn = read_ply_with_normals(written[1])
+    px, pc, pn = read_ply(written[1], normals=True)
     assert len(px) == len(got[2]) > 20 and np.isfinite(pn).all() and (np.linalg.norm(pn, axis=1) <= 1 + 1e-6).all()
     assert px.tobytes() == got[2].tobytes() and pc.tobytes() == got[3].tobytes() and pn.tobytes() == got[4].tobytes()

@@ -14,7 +14,6 @@ For every case 0 < kept < n_valid <= M < P; for nb = 2 the duplicates give dist 
 rounding (2^-52 of the threshold, times a handful) of the threshold."""
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -22,20 +21,15 @@ import torch
 
 import guarded as G
 import normals_ref as NR
+from cloud_testing import DEV, assert_guarded_coverage, cu, dataset, read_ply
 import outliers_ref as OR
 from conftest import load_weights
-from scene_3dreconstruction_mvsnet_amd import MVSNet, _lib, fusion
+from scene_3dreconstruction_mvsnet_amd import _lib, fusion
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-HERE = os.path.dirname(os.path.abspath(__file__))
 BOX = ((-290.0, -190.0, -60.0), (290.0, 190.0, 160.0))        # the box of the normals tests
 DTYPES = {"f32": np.float32, "f64": np.float64}
 CASES = [(4000, 20, 2.0), (1500, 8, 1.0), (4097, 64, 2.0), (4000, 2, 2.0)]
-
-
-def cu(a):
-    return torch.from_numpy(np.array(a, order="C")).to(DEV)
 
 
 @functools.lru_cache(maxsize=None)
@@ -251,20 +245,11 @@ def test_cloud_outliers_enqueues_without_a_host_synchronisation():
 
 
 # ---------------------------------------------------------------- guarded buffers
-def outliers_device_entry_points():
-    with open(os.path.join(os.path.dirname(HERE), "include", "mvs_outliers_abi.h")) as f:
-        names = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", f.read(), re.M)
-    return [n for n in names if not n.startswith("mvs_query_")]
-
-
 GUARDED_ENTRIES = {"mvs_cloud_outliers": "test_outliers_buffers_between_guards_under_every_poison"}
 
 
 def test_every_device_entry_point_of_the_outliers_header_has_a_guarded_case():
-    names = outliers_device_entry_points()
-    assert names and set(names) == set(GUARDED_ENTRIES), (names, sorted(GUARDED_ENTRIES))
-    for test in GUARDED_ENTRIES.values():
-        assert callable(globals()[test])
+    assert_guarded_coverage("mvs_outliers_abi.h", GUARDED_ENTRIES, globals())
 
 
 @pytest.mark.parametrize("masked", [True, False])
@@ -299,17 +284,6 @@ def test_outliers_buffers_between_guards_under_every_poison(dtype, masked):
 
 
 # ---------------------------------------------------------------- the chain
-def _dataset(tmp_path):
-    from synthetic_dataset import write_synthetic_dataset
-    from scene_3dreconstruction_mvsnet_amd.dataset_eval import EvalDataset
-    listfile = write_synthetic_dataset(str(tmp_path))
-    ds = EvalDataset(os.path.join(str(tmp_path), "data"), listfile, "test", nviews=3, ndepths=16, interval_scale=1.06,
-                     img_res=(96, 128), dataset_name="dtu")
-    model = MVSNet(refine=False)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in load_weights().items()})
-    return ds, model, listfile
-
-
 PLANTED = 5
 
 
@@ -338,15 +312,8 @@ def _chain_box(model, ds):
     return lo, hi, v
 
 
-def _read_ply(path, normals):
-    with open(path, "rb") as f:
-        head, body = f.read().split(b"end_header\n", 1)
-    assert (b"property float nx" in head) == normals
-    return int(re.search(rb"element vertex (\d+)", head).group(1)), body
-
-
 def test_reconstruct_scan_with_outliers_equals_the_steps_by_hand(tmp_path, monkeypatch):
-    ds, model, _ = _dataset(tmp_path)
+    ds, model, _ = dataset(tmp_path)
     thr = dict(geomask=0, photomask=0.0, device=DEV)        # thresholds that keep every pixel
     lo, hi, v = _chain_box(model, ds)
     rows = _plant(monkeypatch, lo, hi)
@@ -403,12 +370,12 @@ def test_reconstruct_scan_with_outliers_equals_the_steps_by_hand(tmp_path, monke
     fusion.write_ply(str(tmp_path / "d.ply"), got_n[2], got_n[3], got_n[4])
     for path, other in ((small, "a.ply"), (small_n, "b.ply"), (small_o, "c.ply"), (small_on, "d.ply")):
         assert open(path, "rb").read() == open(str(tmp_path / other), "rb").read(), path
-    assert _read_ply(small_o, False)[0] == len(got[2]) and _read_ply(small_on, True)[0] == len(got[2])
+    assert len(read_ply(small_o)[0]) == len(got[2]) and len(read_ply(small_on, normals=True)[0]) == len(got[2])
 
 
 def test_the_command_line_flags_write_the_same_file(tmp_path, monkeypatch):
     from scene_3dreconstruction_mvsnet_amd import reconstruct
-    ds, model, listfile = _dataset(tmp_path)
+    ds, model, listfile = dataset(tmp_path)
     torch.save({"model": {k: torch.from_numpy(v) for k, v in load_weights().items()}}, str(tmp_path / "model.ckpt"))
     out = tmp_path / "plys"
     common = ["--testpath", os.path.join(str(tmp_path), "data"), "--testlist", listfile, "--loadckpt",
@@ -427,7 +394,7 @@ def test_the_command_line_flags_write_the_same_file(tmp_path, monkeypatch):
     got = fusion.reconstruct_scan(model, ds, "scan1", geomask=0, photomask=0.0, device=DEV,
                                   downsample=dict(voxel_size=v, box=(box[:3], box[3:]), scale=1.0,
                                                   outliers=dict(nb_neighbors=8, std_ratio=1.5)))
-    n, body = _read_ply(written[1], False)
+    n = len(read_ply(written[1])[0])
     assert 20 < n == len(got[2]) and 0 < got[4]["counts"][2] < got[4]["counts"][1]
     fusion.write_ply(str(tmp_path / "want.ply"), got[2], got[3])
     assert open(written[1], "rb").read() == open(str(tmp_path / "want.ply"), "rb").read() != before[1]

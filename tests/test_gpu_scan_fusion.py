@@ -3,7 +3,6 @@ no tolerance anywhere.  The scenes take their masks and points from the existing
 write their masks directly and code each point's (view, pixel) into its coordinates, so a point in the wrong place
 cannot compare equal."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -11,18 +10,13 @@ import torch
 
 import fuse_ref
 import guarded as G
+from cloud_testing import DEV, assert_guarded_coverage, cu
 from conftest import load_weights
 from scene_3dreconstruction_mvsnet_amd import MVSNet, _lib, fusion
 from synthetic_scene import make_scene
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 T = _lib.FUSE_TILE
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def cu(a):
-    return torch.from_numpy(np.array(a, order="C")).to(DEV)      # a copy: the cached scenes are read-only
 
 
 def coded_xyz(R, hw):
@@ -229,22 +223,11 @@ def test_fuse_views_raises_when_the_total_exceeds_the_capacity():
 
 
 # ---------------------------------------------------------------- guarded buffers
-def fuse_device_entry_points():
-    """The same rule as test_gpu_guarded.device_entry_points, for the header of this addition: every `int mvs_*` it
-    declares that is not a mvs_query_* size query takes device buffers."""
-    with open(os.path.join(os.path.dirname(HERE), "include", "mvs_fuse_abi.h")) as f:
-        names = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", f.read(), re.M)
-    return [n for n in names if not n.startswith("mvs_query_")]
-
-
 GUARDED_ENTRIES = {"mvs_fuse_points": "test_every_buffer_between_guards_under_every_poison"}
 
 
 def test_every_device_entry_point_of_the_fuse_header_has_a_guarded_case():
-    names = fuse_device_entry_points()
-    assert names and set(names) == set(GUARDED_ENTRIES), (names, sorted(GUARDED_ENTRIES))
-    for test in GUARDED_ENTRIES.values():
-        assert callable(globals()[test])
+    assert_guarded_coverage("mvs_fuse_abi.h", GUARDED_ENTRIES, globals())
 
 
 @pytest.mark.parametrize("hwc", [True, False], ids=["hwc", "chw"])
