@@ -13,12 +13,13 @@ import ctypes
 import json
 import os
 import re
-import subprocess
 import sys
 import threading
 
 import numpy as np
 import pytest
+
+import gpu_child
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -353,30 +354,17 @@ def _sweep(part):
 # (force_direct, part): "main" is every case but the ones whose plain size_t product wraps (D = h = w = 2^30), which
 # run in a child of their own ("wrap"): a library that divides by the wrapped zero dies there and nowhere else
 CHILDREN = {"default": (False, "main"), "MVS_FORCE_DIRECT=1": (True, "main"), "default/wrap": (False, "wrap")}
-_RESULTS = {}
-
-
 def sweep(child):
-    if child not in _RESULTS:
-        force_direct, part = CHILDREN[child]
-        env = {k: v for k, v in os.environ.items() if not k.startswith("MVS_") or k == "MVS_LIB_PATH"}
-        env.update(HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
-        if force_direct:
-            env["MVS_FORCE_DIRECT"] = "1"
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--sweep", part], env=env, capture_output=True,
-                           text=True, timeout=300)
-        lines = r.stdout.splitlines()
-        records = {}
-        for ln in lines:
-            if ln.startswith("R "):
-                rec = json.loads(ln[2:])
-                records[(rec["ep"], rec["case"])] = rec       # the line after the call replaces the one before it
-        tail = [json.loads(ln[2:]) for ln in lines if ln.startswith("T ")]
-        _RESULTS[child] = dict(records=list(records.values()), rc=r.returncode, stderr=r.stderr[-2000:],
-                               threads=tail[-1]["threads"] if tail else None)
-        if tail:
-            assert tail[-1]["force_direct"] == ("1" if force_direct else "")
-    return _RESULTS[child]
+    force_direct, part = CHILDREN[child]
+    r = gpu_child.run_once((__file__, child), [os.path.abspath(__file__), "--sweep", part], timeout=300, gpu=False,
+                           env={"MVS_FORCE_DIRECT": "1"} if force_direct else None)
+    # the line after the call replaces the one before it
+    records = {(rec["ep"], rec["case"]): rec for rec in r.records("R ")}
+    tail = r.records("T ")
+    if tail:
+        assert tail[-1]["force_direct"] == ("1" if force_direct else "")
+    return dict(records=list(records.values()), rc=r.returncode, stderr=r.stderr[-2000:],
+                threads=tail[-1]["threads"] if tail else None)
 
 
 @pytest.mark.parametrize("child", list(CHILDREN))

@@ -7,7 +7,6 @@ import ctypes
 import json
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -20,6 +19,7 @@ for path in (REPO, HERE):
         sys.path.insert(0, path)
 
 import distance_ref  # noqa: E402
+import gpu_child  # noqa: E402
 import normals_ref  # noqa: E402
 import outliers_ref  # noqa: E402
 
@@ -139,24 +139,9 @@ def _child():
                   flush=True)
 
 
-_RESULTS = {}
-
-
-def _records():
-    if not _RESULTS:
-        env = {k: v for k, v in os.environ.items() if not k.startswith("MVS_") or k == "MVS_LIB_PATH"}
-        env.update(HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--refusals"], env=env, capture_output=True, text=True,
-                           timeout=300)
-        recs = [json.loads(ln[2:]) for ln in r.stdout.splitlines() if ln.startswith("R ")]
-        _RESULTS.update(rc=r.returncode, stderr=r.stderr[-2000:], records={(x["ep"], x["case"]): x for x in recs})
-    assert _RESULTS["rc"] == 0, _RESULTS["stderr"]
-    return _RESULTS["records"]
-
-
 @pytest.mark.parametrize("ep,cases", [("distance", CASES), ("query", Q_CASES)])
 def test_every_refusal_comes_with_its_status_and_its_message(ep, cases):
-    records = _records()
+    records = gpu_child.refusal_records(os.path.abspath(__file__))
     assert len({label for label, *_ in cases}) == len(cases)
     wrong = []
     for label, _, want, text in cases:

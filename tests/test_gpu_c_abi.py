@@ -6,6 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import gpu_child
 from conftest import REPO, rel_l1
 from oracle import oracle as orc
 from scene_3dreconstruction_mvsnet_amd import _lib, synthetic
@@ -33,7 +34,7 @@ def test_plain_c_host_runs_depth_infer(tmp_path):
             for suffix in ("weight", "bias", "running_mean", "running_var"):
                 f.write(np.ascontiguousarray(sd[f"{pre}.{suffix}"], np.float32).tobytes())
         f.write(np.ascontiguousarray(sd["prob.bias"], np.float32).tobytes())
-    r = subprocess.run([demo, _lib.LIB_PATH, fin, fout], capture_output=True, text=True, timeout=120)
+    r = gpu_child.run([demo, _lib.LIB_PATH, fin, fout], timeout=120, python=False)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "must be positive multiples of 8" in r.stdout      # the bad-shape message came back as text
     out = np.fromfile(fout, np.float32).reshape(2, h, w)
@@ -59,6 +60,5 @@ def test_rccl_backend_initialises_and_gathers_on_this_box(tmp_path):
         "t = torch.tensor([1.5], dtype=torch.float64, device=dev); dist.all_reduce(t, op=dist.ReduceOp.MAX)\n"
         "assert float(t.item()) == 1.5\n"
         "dist.destroy_process_group(); print('rccl ok')\n")
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run(["python", "-c", code], capture_output=True, text=True, timeout=240, env=env)
+    r = gpu_child.run(["-c", code], env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"}, timeout=240)
     assert r.returncode == 0 and "rccl ok" in r.stdout, r.stdout + r.stderr

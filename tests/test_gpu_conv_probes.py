@@ -4,15 +4,14 @@ table).  The bounds are about 1000x tighter than the per-layer oracle comparison
 test_gpu_fullsize.py: a lost low-order bf16 piece at a tile edge or a dropped split cross term fails here.  Each child also
 runs the smallest volumes mvs_conv_layer / mvs_conv11_prob admit (1 x 1 x 1 upwards; probe_check.TINY_*) against the
 dense bound, inside a guarded, poisoned arena."""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import gpu_child  # noqa: E402
 from probe_check import CASES  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -20,12 +19,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_conv_probes(case):
-    env = {k: v for k, v in os.environ.items() if not k.startswith("MVS_")}
-    env.update(CASES[case]["env"])
-    r = subprocess.run([sys.executable, os.path.join(HERE, "probe_check.py"), case], env=env,
-                       capture_output=True, text=True, timeout=300)
-    print(r.stdout[-6000:])
-    print(r.stderr[-3000:])
+    r = gpu_child.run(["probe_check.py", case], env=CASES[case]["env"], timeout=300)
     assert r.returncode == 0, f"probe_check {case}: rc {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-3000:]}"
-    ratios = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["ratios"]
+    ratios = r.json()["ratios"]
     assert ratios and max(ratios.values()) <= 1.0, ratios

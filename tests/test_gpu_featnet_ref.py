@@ -1,14 +1,12 @@
 """FeatureNet's kernels (csrc/featnet.hip: fconv_mfma_kernel in eight instantiations, fconv01_fused_kernel in three,
 c8_to_nchw_kernel, narrow_kernel for f16 / bf16) against the fp64 reference, the single-product probes and the derived
 bounds of tests/featnet_ref.py.  One child process per kernel-selection environment (tests/featnet_check.py), started
-with a time limit and never retried; and the 31-bit size guard of check_image_dims, just inside and at it.
+with a time limit and never retried (tests/gpu_child.py); and the 31-bit size guard of check_image_dims, just inside and at it.
 
 The size-guard cases print their wall time (MEASURED_WALL records it); over two minutes, keep one inside case only.
 """
 import ctypes
-import json
 import os
-import subprocess
 import sys
 import time
 
@@ -19,6 +17,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import featnet_ref as R  # noqa: E402
+import gpu_child  # noqa: E402
 from conftest import load_weights  # noqa: E402
 from featnet_check import ENVS, INSTANTIATIONS, KEYS  # noqa: E402
 from scene_3dreconstruction_mvsnet_amd import _lib  # noqa: E402
@@ -28,31 +27,11 @@ DEV = torch.device("cuda", 0)
 GIB = float(1 << 30)
 
 
-@pytest.fixture(scope="module")
-def runs():
-    done = {}
-
-    def run(envname):
-        if envname not in done:
-            env = {k: v for k, v in os.environ.items() if not k.startswith("MVS_")}
-            env.update(ENVS[envname])
-            try:
-                r = subprocess.run([sys.executable, os.path.join(HERE, "featnet_check.py"), envname], env=env,
-                                   capture_output=True, text=True, timeout=900)
-                done[envname] = (r.returncode, r.stdout, r.stderr)
-            except subprocess.TimeoutExpired as e:
-                done[envname] = (-1, str(e.stdout), "timeout: " + str(e.stderr))
-        return done[envname]
-    return run
-
-
 @pytest.mark.parametrize("envname", list(ENVS))
-def test_featnet_kernels_lie_within_the_fp64_bound(runs, envname):
-    rc, out, err = runs(envname)
-    print(out[-8000:])
-    print(err[-3000:])
-    assert rc == 0, f"featnet_check {envname}: rc {rc}\n{out[-4000:]}\n{err[-3000:]}"
-    res = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+def test_featnet_kernels_lie_within_the_fp64_bound(envname):
+    r = gpu_child.run_once(("featnet", envname), ["featnet_check.py", envname], env=ENVS[envname], timeout=900)
+    assert r.returncode == 0, f"featnet_check {envname}: rc {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-3000:]}"
+    res = r.json()
     assert set(KEYS[envname]) <= set(res["ratios"]), set(KEYS[envname]) - set(res["ratios"])
     assert not res["failures"] and res["worst"] <= 1.0, res
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_child
 from conftest import assert_conf_close, load_fixture, rel_l1
 from oracle import oracle as orc
 from scene_3dreconstruction_mvsnet_amd import _lib, synthetic
@@ -219,12 +220,7 @@ def test_cfg2_conv0_kernel_variants_match_oracle(split):
     """conv0's other kernel at FULL size with the per-layer bounds of test_cfg2_every_layer_matches_oracle[0]: the
     fp32-MFMA Winograd kernel (MVS_CONV0_SPLIT=0; the default until round 4).  Selection is read once per process ->
     child process (tests/conv0_check.py)."""
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, os.path.join(here, "conv0_check.py")], env=dict(os.environ, MVS_CONV0_SPLIT=split),
-                       capture_output=True, text=True, timeout=900)
+    r = gpu_child.run(["conv0_check.py"], env={"MVS_CONV0_SPLIT": split}, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
 
 

@@ -8,18 +8,15 @@ environment of probe_check.CASES (CostRegNet's layers in every kernel form, at t
 every environment of warp_ref_check.ENVS (warp + variance), the environments of the run-time z-chunk splits
 (test_gpu_zchunks.FORMS, one shape per category of zchunks.cheapest_cases at this device's CU count), and the default
 environment for everything else.  Each child has its own time limit, writes its verdicts to a JSON file and runs at
-most once; after a child that died from a signal, ran into its time limit or met a HIP error the run ends, so that
-nothing more is started on the GPU.
+most once; what ends the run after a child is the suite's one rule, in tests/gpu_child.py.
 """
 import json
 import os
 import re
-import subprocess
-import sys
-import time
 
 import pytest
 
+import gpu_child
 import guard_check
 import probe_check
 import test_gpu_zchunks as Z
@@ -53,42 +50,26 @@ def _env_key(env):
 def results(tmp_path_factory):
     """Runs each environment's cases in one child, on first use: {env key: {case id: verdict}}."""
     tmp = tmp_path_factory.mktemp("guarded")
-    done = {}
+    keys = sorted({_env_key(c["env"]) for c in CASES.values()})
+    for i, key in enumerate(keys):
+        with open(tmp / f"env{i}.cases.json", "w") as f:
+            json.dump([c for c in CASES.values() if _env_key(c["env"]) == key], f)
 
     def get(case):
         key = _env_key(case["env"])
-        if key not in done:
-            mine = [c for c in CASES.values() if _env_key(c["env"]) == key]
-            stem = tmp / f"env{len(done)}"
-            with open(f"{stem}.cases.json", "w") as f:
-                json.dump(mine, f)
-            child_env = {k: v for k, v in os.environ.items() if not k.startswith("MVS_")}
-            child_env.update(case["env"])
-            t0 = time.perf_counter()
-            try:
-                r = subprocess.run([sys.executable, os.path.join(HERE, "guard_check.py"), f"{stem}.cases.json",
-                                    f"{stem}.out.json"], env=child_env, capture_output=True, text=True,
-                                   timeout=CHILD_TIMEOUT)
-            except subprocess.TimeoutExpired as e:      # a hang: no further GPU work in this run
-                tail = e.stdout if isinstance(e.stdout, str) else (e.stdout or b"").decode("utf-8", "replace")
-                pytest.exit(f"guard_check {dict(key)} did not end within {CHILD_TIMEOUT} s:\n{tail[-4000:]}", returncode=3)
-            print(r.stdout.strip())
-            print(f"[guarded] child {dict(key)}: {len(mine)} cases, {time.perf_counter() - t0:.1f} s, status {r.returncode}")
-            if r.returncode < 0 or r.returncode in (134, 139):   # killed by a signal: no further GPU work in this run
-                pytest.exit(f"guard_check {dict(key)} died with status {r.returncode}:\n{r.stderr[-4000:]}", returncode=3)
-            try:
-                with open(f"{stem}.out.json") as f:
-                    verdicts = json.load(f)
-            except (OSError, ValueError):
-                verdicts = {}
-            if r.returncode == 2:      # the child stopped at a HIP error, a GPU fault: no further GPU work in this run
-                bad = "; ".join(f"{k}: {v['msg'].strip()}" for k, v in verdicts.items() if not v["ok"])
-                pytest.exit(f"guard_check {dict(key)} met a HIP error:\n{bad[-4000:]}\n{r.stderr[-2000:]}", returncode=3)
-            if r.returncode != 0:      # the child never runs twice: the cases without a verdict fail with its output
-                verdicts[CHILD_FAILED] = f"guard_check ended with status {r.returncode}:\n" + \
-                    r.stdout[-2000:] + r.stderr[-4000:]
-            done[key] = verdicts
-        return done[key]
+        stem = tmp / f"env{keys.index(key)}"
+        # guard_check.py ends with status 2 after a HIP error: like a signal or a time limit, that ends the run
+        r = gpu_child.run_once(("guarded", key), ["guard_check.py", f"{stem}.cases.json", f"{stem}.out.json"],
+                               env=case["env"], timeout=CHILD_TIMEOUT, hip_error_status=2)
+        try:
+            with open(f"{stem}.out.json") as f:
+                verdicts = json.load(f)
+        except (OSError, ValueError):
+            verdicts = {}
+        if r.returncode != 0:      # the child never runs twice: the cases without a verdict fail with its output
+            verdicts[CHILD_FAILED] = f"guard_check ended with status {r.returncode}:\n" + \
+                r.stdout[-2000:] + r.stderr[-4000:]
+        return verdicts
 
     return get
 

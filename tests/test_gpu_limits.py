@@ -14,7 +14,6 @@ import gc
 import hashlib
 import os
 import resource
-import subprocess
 import sys
 import time
 
@@ -22,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_child
 from conftest import assert_conf_close, rel_l1
 from oracle import oracle as orc
 from scene_3dreconstruction_mvsnet_amd import _lib, synthetic
@@ -215,10 +215,7 @@ def conv0_self_test(var, c0):
 
 def conv0_digest_child(N, D, seed, env):
     """conv0's output digest from a child process (kernel selection is read once per process)."""
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "conv0-digest", str(N), str(D), str(seed)],
-                       env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-    if r.returncode < 0 or r.returncode in (134, 139):   # killed by a signal: no further GPU work in this run
-        pytest.exit(f"conv0-digest child died with status {r.returncode}:\n{r.stderr[-4000:]}", returncode=3)
+    r = gpu_child.run([os.path.abspath(__file__), "conv0-digest", N, D, seed], env=env, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     return r.stdout.strip().splitlines()[-1]
 

@@ -8,9 +8,7 @@ as a NaN outside the spread set.  The whole net and the inference chain run in c
 environment (tests/nonfinite_train_check.py); the chain cases hold R1 only and are exempt from the coverage condition,
 which tests/test_nonfinite_train_host.py asserts for every kernel-level case.
 """
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -20,6 +18,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import featnet_ref as FR  # noqa: E402
+import gpu_child  # noqa: E402
 import guarded  # noqa: E402
 import nonfinite_ref as NR  # noqa: E402
 import nonfinite_train_ref as T  # noqa: E402
@@ -87,14 +86,9 @@ def test_featnet_kernel_keeps_and_confines_nonfinite_pixels(arena, feat_state, k
 @pytest.mark.parametrize("envname", ["default", "split01", "feat16"])
 def test_whole_net_and_inference_chain(envname):
     """one child per environment; the NaN-weight and NaN-statistic cases fail on the parent commit's library"""
-    env = {k: v for k, v in os.environ.items() if not k.startswith("MVS_")}
-    env.update(ENVS[envname])
-    r = subprocess.run([sys.executable, os.path.join(HERE, "nonfinite_train_check.py"), envname], env=env,
-                       capture_output=True, text=True, timeout=300)
-    print(r.stdout[-6000:])
-    print(r.stderr[-3000:])
+    r = gpu_child.run(["nonfinite_train_check.py", envname], env=ENVS[envname], timeout=300)
     assert r.returncode == 0, f"nonfinite_train_check {envname}: rc {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-3000:]}"
-    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    res = r.json()
     assert not res["failures"], res["failures"]
     if envname == "feat16":
         assert len(res["report"]) == 12 and all(k.startswith("narrow/") for k in res["report"])

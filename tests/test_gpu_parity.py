@@ -4,10 +4,13 @@
 stage by stage and end to end.  Tolerances are fp32 summation-order noise; the north_star
 bound (1e-3 relative L1 on depth) is asserted end to end with orders of magnitude to spare.
 """
+import os
+
 import numpy as np
 import pytest
 import torch
 
+import gpu_child
 from conftest import assert_conf_close, load_fixture, load_weights, rel_l1
 from oracle import oracle as orc
 from scene_3dreconstruction_mvsnet_amd import MVSNet, _lib, synthetic
@@ -326,13 +329,7 @@ def test_nonfinite_coordinates_give_nan_like_torch():
 def test_optin_kernel_variants(env):
     """The non-default kernels stay parity-green (selection is read once per process, so each
     variant runs tests/variant_check.py in a child process; sequential, one GPU user at a time)."""
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    child_env = dict(os.environ, **env)
-    r = subprocess.run([sys.executable, os.path.join(here, "variant_check.py")], env=child_env,
-                       capture_output=True, text=True, timeout=600)
+    r = gpu_child.run(["variant_check.py"], env=env, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
@@ -340,9 +337,6 @@ def test_optin_kernel_variants(env):
 def test_16bit_storage_16bit_feature_copy_variant(storage):
     """MVS_FEAT16=1: the 16-bit modes gather from a feature copy narrowed to the storage type (the default of rounds
     2-3; since round 4 the gather reads the fp32 copy); against the oracle with the same rounding point."""
-    import os
-    import subprocess
-    import sys
     code = (
         "import sys, numpy as np, torch; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
         "from conftest import load_fixture, load_weights, rel_l1\n"
@@ -358,17 +352,13 @@ def test_16bit_storage_16bit_feature_copy_variant(storage):
         "want, _ = orc.depth_infer(f, p, d, sd, storage=st, feat16=True)\n"
         "r = rel_l1(depth.cpu().numpy(), want); print(r); sys.exit(0 if r < (2e-4 if st == 'f16' else 1e-3) else 1)\n"
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), storage)
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MVS_FEAT16="1"),
-                       capture_output=True, text=True, timeout=600)
+    r = gpu_child.run(["-c", code], env={"MVS_FEAT16": "1"}, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
 @pytest.mark.parametrize("storage", ["f16", "bf16"])
 def test_16bit_storage_fp32_arithmetic_variant(storage):
     """MVS_MFMA16=0: fp32 MFMA on the narrowed operands, against the oracle that rounds storage only."""
-    import os
-    import subprocess
-    import sys
     code = (
         "import sys, numpy as np, torch; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
         "from conftest import load_fixture, load_weights, rel_l1\n"
@@ -384,8 +374,7 @@ def test_16bit_storage_fp32_arithmetic_variant(storage):
         "want, _ = orc.depth_infer(f, p, d, sd, storage=st, arith16=False)\n"
         "r = rel_l1(depth.cpu().numpy(), want); print(r); sys.exit(0 if r < (2e-4 if st == 'f16' else 1e-3) else 1)\n"
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), storage)
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MVS_MFMA16="0"),
-                       capture_output=True, text=True, timeout=600)
+    r = gpu_child.run(["-c", code], env={"MVS_MFMA16": "0"}, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
@@ -423,12 +412,7 @@ def test_16bit_storage_fp32_arithmetic_variant(storage):
 def test_full_size_only_code_paths_at_small_shapes(env, shape):
     """Kernels / launch orders that the default selection reaches only at full size, forced at a
     small shape in a child process and compared per layer with the oracle (tests/layer_check.py)."""
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, os.path.join(here, "layer_check.py"), *shape],
-                       env=dict(os.environ, **env), capture_output=True, text=True, timeout=900)
+    r = gpu_child.run(["layer_check.py", *shape], env=env, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
@@ -762,17 +746,10 @@ def test_two_ranks_gather_over_rccl_and_bench_self_launch():
     """On a multi-GPU box: `python bench.py --gpus 2` launches its own ranks (one per GPU, RCCL all-gather
     of the results inside the timed region) and prints one line for the whole job.  Skipped -- and so
     UNMEASURED -- on the one-GPU box these tests normally run on."""
-    import json
-    import os
-    import subprocess
-    import sys
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-e2e", "--staged-steps", "0"], env=env, capture_output=True,
-                       text=True, timeout=900)
+    r = gpu_child.run([os.path.join("..", "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--no-cpu-baseline",
+                       "--no-e2e", "--staged-steps", "0"], timeout=900, drop=("WORLD_SIZE", "RANK", "LOCAL_RANK"))
     assert r.returncode == 0, r.stdout + r.stderr
-    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    line = r.json()
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["scaling"] == "weak"
 
 
@@ -787,9 +764,6 @@ def test_tap_cache_kernel_is_bit_identical_to_the_plain_kernel(tmp_path, N, h, w
     by DPP across the lanes of a pixel; every view is blended at every step, none is skipped) against the
     plain gather kernel (MVS_WARP_TC=0, read once per process -> child process): same taps, same weights, same fma
     nesting, so the volumes must be EQUAL, not close."""
-    import os
-    import subprocess
-    import sys
     here = os.path.dirname(os.path.abspath(__file__))
     feats = synthetic.random_features(N, 32, h, w, seed=11)
     proj = synthetic.cameras(N, h, w, **kw)
@@ -803,8 +777,7 @@ def test_tap_cache_kernel_is_bit_identical_to_the_plain_kernel(tmp_path, N, h, w
         "ws = _lib.alloc_workspace(N, C, z['dv'].shape[0], h, w, dev)\n"
         "v = _lib.warp_variance(cu(z['feats']), _lib.relative_proj(cu(z['proj'])), cu(z['dv']), ws)\n"
         "np.save(sys.argv[2], v.cpu().numpy())\n") % os.path.dirname(here)
-    r = subprocess.run([sys.executable, "-c", code, str(tmp_path / "in.npz"), str(tmp_path / "plain.npy")],
-                       env=dict(os.environ, MVS_WARP_TC="0"), capture_output=True, text=True, timeout=600)
+    r = gpu_child.run(["-c", code, tmp_path / "in.npz", tmp_path / "plain.npy"], env={"MVS_WARP_TC": "0"}, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     ws = _lib.alloc_workspace(N, 32, D, h, w, DEV)
     got = _lib.warp_variance(cu(feats), _lib.relative_proj(cu(proj)), cu(dv), ws).cpu().numpy()

@@ -3,11 +3,9 @@ with 16-bit features, homo_warp_kernel, relative_proj_kernel) against the fp64 r
 tests/warp_ref.py -- about 50 times tighter than the atol = 5e-4 of test_gpu_parity.py / test_gpu_fullsize.py, on rigs
 those never try (fast epipolar motion, roll, all borders and corners, points behind a source camera with NaN voxels).
 One child process per kernel-selection environment (tests/warp_ref_check.py: the environment -> kernel map); a failed
-child fails its environment and nothing is retried.  The tap-cache forms must equal the plain forms bit for bit on
+child fails its environment and nothing is retried (tests/gpu_child.py).  The tap-cache forms must equal the plain forms bit for bit on
 every case, NaN positions included."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +13,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import gpu_child  # noqa: E402
 import warp_ref as W  # noqa: E402
 from warp_ref_check import ENVS, IDENTICAL  # noqa: E402
 
@@ -23,30 +22,21 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
+    """envname -> (the environment's child, run on first use, and the directory of its volumes)"""
     work = str(tmp_path_factory.mktemp("warp_ref"))
-    done = {}
 
     def run(envname):
-        if envname not in done:
-            env = {k: v for k, v in os.environ.items() if not k.startswith("MVS_")}
-            env.update(ENVS[envname]["env"])
-            try:
-                r = subprocess.run([sys.executable, os.path.join(HERE, "warp_ref_check.py"), envname, work], env=env,
-                                   capture_output=True, text=True, timeout=300)
-                done[envname] = (r.returncode, r.stdout, r.stderr)
-            except subprocess.TimeoutExpired as e:
-                done[envname] = (-1, str(e.stdout), "timeout: " + str(e.stderr))
-        return done[envname] + (os.path.join(work, envname),)
+        r = gpu_child.run_once(("warp_ref", envname), ["warp_ref_check.py", envname, work], env=ENVS[envname]["env"],
+                               timeout=300)
+        return r, os.path.join(work, envname)
     return run
 
 
 @pytest.mark.parametrize("envname", list(ENVS))
 def test_warp_kernels_lie_within_the_fp64_bound(runs, envname):
-    rc, out, err, _ = runs(envname)
-    print(out[-8000:])
-    print(err[-3000:])
-    assert rc == 0, f"warp_ref_check {envname}: rc {rc}\n{out[-4000:]}\n{err[-3000:]}"
-    res = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+    r, _ = runs(envname)
+    assert r.returncode == 0, f"warp_ref_check {envname}: rc {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-3000:]}"
+    res = r.json()
     want = {f"{c}/{s}" for c in W.CASES for s in ENVS[envname]["storages"]}
     assert want <= set(res["ratios"]), want - set(res["ratios"])
     assert not res["failures"] and res["worst"] <= 1.0, res
@@ -56,9 +46,10 @@ def test_warp_kernels_lie_within_the_fp64_bound(runs, envname):
 def test_tap_cache_volumes_equal_the_plain_kernels_bit_for_bit(runs, tc):
     """same taps, same weights, same fma nesting: EQUAL on every case and storage type, NaN positions included"""
     plain = IDENTICAL[tc]
-    rc_a, _, err_a, dir_a = runs(tc)
-    rc_b, _, err_b, dir_b = runs(plain)
-    assert rc_a in (0, 1) and rc_b in (0, 1), (err_a[-2000:], err_b[-2000:])    # 1: a bound failed, the volumes exist
+    ra, dir_a = runs(tc)
+    rb, dir_b = runs(plain)
+    # 1: a bound failed, the volumes exist
+    assert ra.returncode in (0, 1) and rb.returncode in (0, 1), (ra.stderr[-2000:], rb.stderr[-2000:])
     differ = []
     for name in W.CASES:
         for s in ENVS[tc]["storages"]:

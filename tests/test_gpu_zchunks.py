@@ -17,13 +17,12 @@ test reaches.  Those run in both block orders against the oracle; the fp32 volum
 """
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_child
 import zchunks
 
 pytestmark = pytest.mark.gpu
@@ -109,29 +108,20 @@ assert len(ALL_CASES) == len(CHUNK_CASES) + len(WARP_CASES)
 def results(tmp_path_factory):
     """Runs each environment's cases in one child, on first use: {env key: {case id: verdict}}."""
     tmp = tmp_path_factory.mktemp("zchunks")
-    done = {}
+    keys = sorted({_env_key(c["env"]) for c in ALL_CASES.values()})
+    for i, key in enumerate(keys):
+        with open(tmp / f"env{i}.cases.json", "w") as f:
+            json.dump([dict(c, save=str(tmp / f"{c['id']}.npy")) for c in ALL_CASES.values()
+                       if _env_key(c["env"]) == key], f)
 
     def get(case):
         key = _env_key(case["env"])
-        if key not in done:
-            mine = [dict(c, save=str(tmp / f"{c['id']}.npy")) for c in ALL_CASES.values()
-                    if _env_key(c["env"]) == key]
-            stem = tmp / f"env{len(done)}"
-            with open(f"{stem}.cases.json", "w") as f:
-                json.dump(mine, f)
-            child_env = {k: v for k, v in os.environ.items() if not k.startswith("MVS_")}
-            child_env.update(case["env"])
-            r = subprocess.run([sys.executable, os.path.join(HERE, "zchunk_check.py"), f"{stem}.cases.json",
-                                f"{stem}.out.json"], env=child_env, capture_output=True, text=True, timeout=900)
-            if r.returncode < 0 or r.returncode in (134, 139):   # killed by a signal: no further GPU work in this run
-                pytest.exit(f"zchunk_check {dict(key)} died with status {r.returncode}:\n{r.stderr[-4000:]}",
-                            returncode=3)
-            assert r.returncode == 0, r.stdout + r.stderr
-            print(r.stdout.strip())
-            with open(f"{stem}.out.json") as f:
-                done[key] = json.load(f)
-        verdict = done[key][case["id"]]
-        return verdict, tmp / f"{case['id']}.npy"
+        stem = tmp / f"env{keys.index(key)}"
+        r = gpu_child.run_once(("zchunks", key), ["zchunk_check.py", f"{stem}.cases.json", f"{stem}.out.json"],
+                               env=case["env"], timeout=900)
+        assert r.returncode == 0, r.stdout + r.stderr
+        with open(f"{stem}.out.json") as f:
+            return json.load(f)[case["id"]], tmp / f"{case['id']}.npy"
 
     return get
 

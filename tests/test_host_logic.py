@@ -493,8 +493,7 @@ def test_bench_path_totals_equal_survey_d3():
 def test_bench_parent_of_a_multi_gpu_run_never_loads_torch(tmp_path):
     """`python bench.py --gpus 2` without torchrun: the parent only relays; it must not initialise
     HIP (it must not even import torch) before starting the ranks."""
-    import subprocess
-    import sys
+    import gpu_child
     fake = tmp_path / "fake_torchrun.py"
     fake.write_text("import json, sys\nprint('noise line')\n"
                     "print(json.dumps({'metric': 'm', 'n_gpus': 2, 'argv': sys.argv[1:]}))\n")
@@ -508,8 +507,7 @@ def test_bench_parent_of_a_multi_gpu_run_never_loads_torch(tmp_path):
         "try:\n    b.main()\nexcept SystemExit as e:\n    rc = e.code\n"
         "assert 'torch' not in sys.modules, 'parent imported torch'\n"
         "sys.exit(rc)\n")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=120)
+    r = gpu_child.run(["-c", code], timeout=120, gpu=False, drop=("WORLD_SIZE", "RANK", "LOCAL_RANK"))
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout              # exactly ONE JSON line on stdout
