@@ -76,7 +76,8 @@ typedef enum mvs_image_format {
     MVS_IMG_U8_HWC = 2       /* uint8 [N][H][W][3], as PIL / np.array(img) yields it (datasets/data_io.py:143) */
 } mvs_image_format;
 
-/* storage dtype of the private volumes (accumulation is always fp32) */
+/* storage dtype of the private volumes (accumulation is always fp32; a stored value is the round-to-nearest-even cast of
+ * the fp32 one, ties to even, fp16 subnormals kept on both sides, +inf from 65520 on) */
 typedef enum mvs_dtype { MVS_F32 = 0, MVS_F16 = 1, MVS_BF16 = 2 } mvs_dtype;
 
 /* Number of conv layers in CostRegNet (models/mvsnet.py:35-62):

@@ -3,7 +3,9 @@
 // Arithmetic is always fp32 (fp32 MFMA, fp32 accumulators); only what is written to / read from
 // HBM between stages is narrowed: mvs_dtype MVS_F32 / MVS_F16 / MVS_BF16 (BASELINE.json configs
 // 2 and 4 name bf16 / fp16 volumes).  Conversions are round-to-nearest-even casts (hipcc emits
-// v_cvt_f16_f32 / v_cvt_pk_bf16_f32, which keep NaNs NaN).
+// v_cvt_f16_f32 / v_cvt_pk_bf16_f32, which keep NaNs NaN).  Nothing is flushed: fp16 subnormals survive as results of
+// the cast and as operands, of St<>::load4 and of v_mfma_f32_16x16x32_f16 alike (measured on the MI355X with exact
+// single products, tests/probes.py "ends"); a value from 65520 on is +inf, below it 65504.
 #pragma once
 #include <hip/hip_runtime.h>
 

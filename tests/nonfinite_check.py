@@ -48,7 +48,8 @@ def check_layers(name):
             wino = case["wino"].get(layer)
             for pname, x, skip in N.layer_patterns(layer, rng, storage):
                 got = run_layer(layer, x, skip, blob, storage)
-                ref, bound, touched = N.layer_reference(layer, x, skip, wf, sh, storage, wino)
+                ref, bound, touched = N.layer_reference(layer, x, skip, wf, sh, storage, wino,
+                                                        case.get("arith", "mfma16"))
                 if layer == 10:
                     ref, bound = ref[0], bound[0]
                 chk.check(key, pname, got, ref, bound, touched, extent)

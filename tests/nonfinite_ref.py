@@ -111,6 +111,14 @@ CASE_KERNELS = {
     "convz16_0": {l: ("convg16_mfma_kernel",) for l in (1, 2, 3)},
     "deep1": {**{l: ("convg16_mfma_kernel",) for l in (4, 5, 6)}, **{l: ("deconvg16_mfma_kernel",) for l in (7, 8)}},
     "deep0": {**{l: ("convg16_mfma_kernel",) for l in (4, 5, 6)}, **{l: ("deconvg16_mfma_kernel",) for l in (7, 8)}},
+    # MVS_MFMA16=0: the 16-bit instantiations of the fp32-MFMA kernels (probe_check's docstring)
+    "fp32arith16": {0: ("conv0_w43_mfma_kernel",), 1: ("convg_mfma_kernel", "convg_persist_mfma_kernel"),
+                    2: ("convwz_mfma_kernel",), 3: ("convg_mfma_kernel",), 4: ("convwz_mfma_kernel",),
+                    5: ("convs_mfma_kernel",), 6: ("convs_mfma_kernel",), 7: ("deconvs_mfma_kernel",),
+                    8: ("deconvg_mfma_kernel",), 9: ("deconvg_mfma_kernel",), 10: ("prob_lds_kernel",)},
+    "fp32arith16_conv0_wino0": {0: ("conv0_4x4_mfma_kernel",)},
+    "fp32arith16_wino0": {2: ("convg_mfma_kernel",), 4: ("convg_mfma_kernel",)},
+    "fp32arith16_persist": {1: ("convg_persist_mfma_kernel", "convg_mfma_kernel")},
 }
 
 
@@ -229,14 +237,15 @@ def _zeroed(a):
     return None if a is None else np.where(np.isfinite(a), a, 0).astype(np.float32)
 
 
-def layer_reference(layer, x, skip, wf, sh, storage="f32", wino=None):
-    """-> (ref, bound, touched): probes.dense_ref_bound on the tensor as stored (16-bit: the matched reference), the
-    bound's scale of the input with its non-finite entries replaced by 0, and the touched voxels [D,H,W]."""
+def layer_reference(layer, x, skip, wf, sh, storage="f32", wino=None, arith="mfma16"):
+    """-> (ref, bound, touched): probes.dense_ref_bound on the tensor as stored (16-bit: the matched reference; arith
+    "fp32" = MVS_MFMA16=0, whose weights stay fp32), the bound's scale of the input with its non-finite entries replaced
+    by 0, and the touched voxels [D,H,W]."""
     with np.errstate(all="ignore"):
-        ref, _ = P.dense_ref_bound(layer, x, skip, wf, sh, storage, wino)
-        _, bound = P.dense_ref_bound(layer, _zeroed(x), _zeroed(skip), wf, sh, storage, wino)
+        ref, _ = P.dense_ref_bound(layer, x, skip, wf, sh, storage, wino, arith)
+        _, bound = P.dense_ref_bound(layer, _zeroed(x), _zeroed(skip), wf, sh, storage, wino, arith)
         q = lambda t: orc.round_storage(np.asarray(t, np.float32), storage)  # noqa: E731
-        w16 = wf if (storage == "f32" or layer == 10) else q(wf)
+        w16 = wf if (storage == "f32" or layer == 10 or arith == "fp32") else q(wf)
         pre = P._conv64(layer, q(x), w16) + np.asarray(sh, np.float64)[:, None, None, None]
         touched = ~np.isfinite(pre)
         if skip is not None:

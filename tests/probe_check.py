@@ -26,10 +26,27 @@ conv11_prob.hip launch_conv11_prob); "wino" names the layers held to a Winograd 
   16-bit "default16": conv0 conv0p16 (conv0z16 needs columns that fill the chip), conv1-conv3 convg16<Op16> (likewise
       convz16), conv4-conv9 the shallow block tiles (tile_fills_chip is false at these sizes), prob prob_lds<16-bit>,
       tail conv11_prob16.  MVS_CONV0Z16=1/0, MVS_CONVZ16=1/0, MVS_DEEP_TILES=1/0 force either side.
+  16-bit "fp32arith16" (MVS_MFMA16=0: launch_conv_layer skips launch_layer_mfma16, and launch_layer_split and
+      launch_conv0_wino43_split ask for dtype == MVS_F32): the DT = F16 / BF16 instantiations of the fp32-MFMA kernels --
+      conv0 conv0_w43<DT> (F(4,3)), conv1 convg<DT> (convg_persist's fall-back; conv1z is `if constexpr (DT == MVS_F32)`),
+      conv2 / conv4 convwz<DT> (F(2,3)), conv3 convg<DT>, conv5 / conv6 convs<DT>, conv7 deconvs<DT>, conv8 / conv9
+      deconvg<DT>, prob prob_lds<16-bit>; conv11_prob_enabled() is false, so the tail is the layer-9 and layer-10 launches.
+      + MVS_CONV0_WINO=0: conv0_4x4<DT>;  + MVS_CONV_WINO=0: conv2 / conv4 convg<DT>;  + MVS_PERSIST_CUS=1:
+      convg_persist<DT>.  MVS_SPLIT_DECONV and MVS_CONV1Z change nothing for 16-bit storage (both are read behind a
+      dtype == MVS_F32 test) and MVS_FORCE_DIRECT=1 refuses it: UNREACHABLE16 quotes the lines.
+
+16-bit storage, layers 0..9 (probes.py: bound_st, err_st): every check is against the UNROUNDED fp64 value of the
+operands as the kernel holds them, within e_max + half a storage ulp; on the lattice an output may differ from
+rne_st(ref64) only where ref64 is within e_max of a rounding boundary ("inexact16": [differing, boundary cases] per key,
+"unexplained16" must be empty); the rounding-boundary probes and fp16's range ends ("<layer>:boundary:", "<layer>:ends:")
+are bit-equal to rne_st of the one exact product, except on a Winograd form, whose transforms are not exact: those keep
+the Winograd e_max.  "e_ratios": worst (|got - ref64| - half ulp) / (2^-24 S) of the dense launches, the figure
+probes.DENSE_C's rule is applied to.
 """
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -67,6 +84,14 @@ CASES = {
     "convz16_0": dict(env={"MVS_CONVZ16": "0"}, storages=B16, layers=(1, 2, 3), wino={}),
     "deep1": dict(env={"MVS_DEEP_TILES": "1"}, storages=B16, layers=(4, 5, 6, 7, 8), wino={}),
     "deep0": dict(env={"MVS_DEEP_TILES": "0"}, storages=B16, layers=(4, 5, 6, 7, 8), wino={}),
+    "fp32arith16": dict(env={"MVS_MFMA16": "0"}, storages=B16, layers=tuple(range(11)), arith="fp32",
+                        wino={0: "F43", 2: "F23", 4: "F23"}),
+    "fp32arith16_conv0_wino0": dict(env={"MVS_MFMA16": "0", "MVS_CONV0_WINO": "0"}, storages=B16, layers=(0,),
+                                    arith="fp32", wino={}),
+    "fp32arith16_wino0": dict(env={"MVS_MFMA16": "0", "MVS_CONV_WINO": "0"}, storages=B16, layers=(2, 4), arith="fp32",
+                              wino={}),
+    "fp32arith16_persist": dict(env={"MVS_MFMA16": "0", "MVS_PERSIST_CUS": "1"}, storages=B16, layers=(1,),
+                                arith="fp32", wino={}),
 }
 
 # every templated launcher instantiation of the CostRegNet conv kernels (run_*<...> in csrc/conv*.hip, whitespace
@@ -119,6 +144,53 @@ INSTANTIATIONS = {
     "run_convz16<DT,16,16,1>": "convz16_1",
     "run_convz16<DT,16,32,2>": "convz16_1",
 }
+# every launcher templated on the storage type DT -> the case that runs it with 16-BIT storage (its F32 case in the table
+# above does not count: St<DT>::load4 / store4 are other loads, stores and casts).  test_conv_probes_host.py requires
+# an entry for every instantiation whose arguments name DT.
+INSTANTIATIONS16 = {
+    "run_conv0_4x4<DT>": "fp32arith16_conv0_wino0",
+    "run_conv0_w43<DT>": "fp32arith16",
+    "run_convwz<DT,16,16,4,2>": "fp32arith16",
+    "run_convwz<DT,32,32,2,2>": "fp32arith16",
+    "run_convg_persist<DT,8,16,2,1,2,2>": "fp32arith16_persist",
+    "run_convg<DT,16,16,1,2,4,2>": "fp32arith16_wino0",
+    "run_convg<DT,16,32,2,1,2,2>": "fp32arith16",
+    "run_convg<DT,32,32,1,1,2,2>": "fp32arith16_wino0",
+    "run_deconvg<DT,32,16,1,4,1>": "fp32arith16",
+    "run_deconvg<DT,16,8,1,4,2>": "fp32arith16",
+    "run_convs<DT,32,64,2,1,2,1,4>": "fp32arith16",
+    "run_convs<DT,64,64,1,1,2,1,4>": "fp32arith16",
+    "run_deconvs<DT,64,32,1,2,1,4>": "fp32arith16",
+    "run_convg16<Op16<DT>,8,16,2,2,2,2>": "convz16_0",
+    "run_convg16<Op16<DT>,16,16,1,2,4,2>": "convz16_0",
+    "run_convg16<Op16<DT>,16,32,2,4,1,1>": "convz16_0",
+    "run_convg16<Op16<DT>,32,32,1,4,2,1>": "deep1",
+    "run_convg16<Op16<DT>,32,32,1,1,2,2>": "deep0",
+    "run_convg16<Op16<DT>,32,64,2,2,1,1>": "deep1",
+    "run_convg16<Op16<DT>,32,64,2,1,1,1>": "deep0",
+    "run_convg16<Op16<DT>,64,64,1,4,1,1>": "deep1",
+    "run_convg16<Op16<DT>,64,64,1,1,1,1>": "deep0",
+    "run_deconvg16<Op16<DT>,64,32,2,1,1>": "deep1",
+    "run_deconvg16<Op16<DT>,64,32,1,1,1>": "deep0",
+    "run_deconvg16<Op16<DT>,32,16,4,2,1>": "deep1",
+    "run_deconvg16<Op16<DT>,32,16,1,4,1>": "deep0",
+    "run_deconvg16<Op16<DT>,16,8,1,4,2>": "default16",
+    "run_convz16<DT,8,16,2>": "convz16_1",
+    "run_convz16<DT,16,16,1>": "convz16_1",
+    "run_convz16<DT,16,32,2>": "convz16_1",
+}
+# what 16-bit storage cannot reach, and the line of the dispatch that excludes it (file, line as written)
+UNREACHABLE16 = {
+    "conv1z_mfma_kernel (run_conv1z)": ("conv3d_mfma.hip", "if constexpr (DT == MVS_F32) {"),
+    "conv3d_direct_kernel / deconv3d_direct_kernel (MVS_FORCE_DIRECT=1)": (
+        "conv3d_direct.hip",
+        'return fail(MVS_ERR_BAD_DTYPE, "MVS_FORCE_DIRECT kernels are fp32-storage only (dtype %d)", dtype);'),
+    "the split-operand tile kernels run_convg16<OpSplit,...> / run_deconvg16<OpSplit,...> (MVS_SPLIT_DECONV)": (
+        "conv3d_direct.hip", "if (opt.split_layers && dtype == MVS_F32 && split_layer_covers(layer))"),
+    "conv0_w48t_kernel (launch_conv0_wino43_split)": ("conv3d_direct.hip", "if (opt.conv0_split && dtype == MVS_F32)"),
+    "the fused 16-bit tail conv11_prob16_kernel under MVS_MFMA16=0": (
+        "conv11_prob.hip", "return options().fuse_prob && (dtype == MVS_F32 || mfma16_enabled());"),
+}
 KERNELS = {
     "conv0_w48t_kernel": "default",
     "conv0_w43_mfma_kernel": "conv0_split0",
@@ -170,7 +242,7 @@ def cu(a):
 class Checker:
     def __init__(self, case):
         self.case = case
-        self.ratios, self.inexact, self.failures = {}, {}, []
+        self.ratios, self.inexact, self.unexplained, self.eratios, self.failures = {}, {}, {}, {}, []
 
     def add(self, key, err, bound):
         r = float((err / bound).max()) if err.size else 0.0
@@ -204,19 +276,58 @@ def out_shape(layer):
     return (co, (D - 1) // s + 1, (H - 1) // s + 1, (W - 1) // s + 1)
 
 
-def check_single(chk, key, layer, got, x, skip, wf, sh, storage, wino):
-    want, bound = P.probe_want_bound(layer, x, skip, wf, sh, storage, wino)
-    if storage != "f32" and layer != 10:
-        chk.inexact[key] = chk.inexact.get(key, 0) + int((got != want).sum())
-    chk.add(key, np.abs(got - want), bound)
+def narrowed(layer, storage):
+    return storage != "f32" and layer != 10
 
 
-def check_dense(chk, key, layer, got, x, skip, wf, sh, storage, wino):
-    ref, bound = P.dense_ref_bound(layer, x, skip, wf, sh, storage, wino)
-    chk.add(key, np.abs(got - ref), bound)
+def check_single(chk, key, layer, got, x, skip, wf, sh, storage, wino, arith="mfma16"):
+    if not narrowed(layer, storage):
+        want, bound = P.probe_want_bound(layer, x, skip, wf, sh, storage, wino, arith)
+        chk.add(key, np.abs(got - want), bound)
+        return
+    ref, emax = P.ref_emax(layer, x, skip, wf, sh, storage, wino, arith)
+    diff = got != P.rne_st(ref, storage)
+    near = P.near_boundary_st(ref, emax, storage)
+    d, n = chk.inexact.get(key, (0, 0))
+    chk.inexact[key] = (d + int(diff.sum()), n + int(near.sum()))
+    bad = diff & ~near
+    if bad.any():
+        chk.unexplained[key] = chk.unexplained.get(key, 0) + int(bad.sum())
+        i = tuple(int(v) for v in np.argwhere(bad)[0])
+        chk.failures.append(f"{key}: {int(bad.sum())} outputs differ from RNE(ref64) away from every rounding boundary, "
+                            f"first at {i}: got {float(got[i])!r}, ref64 {float(ref[i])!r}, e_max {float(emax[i]):.3e}")
+    chk.add(key, *P.err_st(got, ref, emax, storage))
 
 
-def probe_layer(chk, layer, storage, sd, blobs_crafted, wino, rng):
+def check_exact(chk, key, layer, got, x, skip, wf, sh, storage, wino, arith):
+    """One exact product per output: bit-equal to rne_st(product).  A Winograd form's transforms are not exact (the
+    1/6 and 1/24 of G, sums of neighbouring planes): it is held to err_st with its own e_max."""
+    ref, emax = P.ref_emax(layer, x, skip, wf, sh, storage, wino, arith)
+    if wino:
+        chk.add(key, *P.err_st(got, ref, emax, storage))
+        return
+    bad = got != P.rne_st(ref, storage)
+    chk.ratios[key] = max(chk.ratios.get(key, 0.0), 2.0 * int(bad.sum()))
+    if bad.any():
+        i = tuple(int(v) for v in np.argwhere(bad)[0])
+        chk.failures.append(f"{key}: {int(bad.sum())} of {bad.size} outputs are not RNE of their one product, first at "
+                            f"{i}: got {float(got[i])!r}, product {float(ref[i])!r}")
+
+
+def check_dense(chk, key, layer, got, x, skip, wf, sh, storage, wino, arith="mfma16"):
+    if not narrowed(layer, storage):
+        ref, bound = P.dense_ref_bound(layer, x, skip, wf, sh, storage, wino, arith)
+        chk.add(key, np.abs(got - ref), bound)
+        return
+    ref, emax = P.ref_emax(layer, x, skip, wf, sh, storage, wino, arith, dense=True)
+    err, bound = P.err_st(got, ref, emax, storage)
+    chk.add(key, err, bound)
+    if not wino:     # e / (u S): what is left of the error once the half ulp of the cast is taken off
+        e = np.where(np.isfinite(err), err - (bound - emax), 0.0) / (emax / P.DENSE_C)
+        chk.eratios[key] = max(chk.eratios.get(key, 0.0), float(e.max()))
+
+
+def probe_layer(chk, layer, storage, sd, blobs_crafted, wino, rng, arith="mfma16"):
     ci, co, _, tr, shape = P.GEOM[layer]
     blob = blobs_crafted["rand"]
     wf, sh = P.folded(sd, layer)
@@ -226,7 +337,9 @@ def probe_layer(chk, layer, storage, sd, blobs_crafted, wino, rng):
         x = P.lattice(ci, shape, sp, ph, rng)
         skip = rng.standard_normal(oshape).astype(np.float32) if tr else None
         got = run_layer(layer, x, skip, blob, storage)
-        check_single(chk, f"{layer}:lattice:{storage}", layer, got, x, skip, wf, sh, storage, wino)
+        check_single(chk, f"{layer}:lattice:{storage}", layer, got, x, skip, wf, sh, storage, wino, arith)
+    if narrowed(layer, storage):
+        probe_boundaries(chk, layer, storage, blobs_crafted, wino, arith)
     if storage == "f32":
         runs = 27 if layer == 10 else P.crafted_runs(layer)
         for r in range(runs):
@@ -242,7 +355,31 @@ def probe_layer(chk, layer, storage, sd, blobs_crafted, wino, rng):
     for x in vols:
         skip = rng.standard_normal(oshape).astype(np.float32) if tr else None
         got = run_layer(layer, x, skip, blob, storage)
-        check_dense(chk, f"{layer}:dense:{storage}", layer, got, x, skip, wf, sh, storage, wino)
+        check_dense(chk, f"{layer}:dense:{storage}", layer, got, x, skip, wf, sh, storage, wino, arith)
+    if narrowed(layer, storage):   # heavy-tailed, non-negative; fp16 in the largest octave that keeps the output finite
+        x, skip = P.heavy_launch(layer, storage, wf, sh, arith)
+        got = run_layer(layer, x, skip, blob, storage)
+        check_dense(chk, f"{layer}:heavy:{storage}", layer, got, x, skip, wf, sh, storage, wino, arith)
+
+
+def probe_boundaries(chk, layer, storage, blobs, wino, arith):
+    """The rounding-boundary probes of probes.py (every run, every exponent set) and, for fp16, the ends of its range."""
+    ci, _, _, tr, shape = P.GEOM[layer]
+    skip = np.zeros(out_shape(layer), np.float32) if tr else None
+    brng = np.random.default_rng(41 + layer)
+    for r in range(P.boundary_runs(layer)):
+        sdb, blob_b = blobs[("boundary", storage, r)]
+        wfb, shb = P.folded(sdb, layer)
+        for exps in P.BOUNDARY_EXPS[storage]:
+            x = P.boundary_inputs((ci,) + shape, storage, exps, brng)
+            got = run_layer(layer, x, skip, blob_b, storage)
+            check_exact(chk, f"{layer}:boundary:{storage}", layer, got, x, skip, wfb, shb, storage, wino, arith)
+    if storage == "f16":
+        sde, blob_e = blobs[("ends",)]
+        wfe, she = P.folded(sde, layer)
+        x = P.ends_inputs(ci, shape, brng)
+        got = run_layer(layer, x, skip, blob_e, storage)
+        check_exact(chk, f"{layer}:ends:{storage}", layer, got, x, skip, wfe, she, storage, wino, arith)
 
 
 def probe_tail(chk, storage, sd, blobs_crafted, rng):
@@ -304,7 +441,7 @@ def guarded_call(arena, fn, oshape):
     return y.numpy().astype(np.float64)
 
 
-def probe_tiny(chk, arena, layer, storage, sd, blob, wino, rng):
+def probe_tiny(chk, arena, layer, storage, sd, blob, wino, rng, arith="mfma16"):
     code = _lib.dtype_code(storage)
     tdt = _lib.TORCH_DTYPES[code]
     if layer == "tail":
@@ -340,7 +477,11 @@ def probe_tiny(chk, arena, layer, storage, sd, blob, wino, rng):
         got = guarded_call(arena, run, oshape[1:] if layer == 10 else oshape)
         # conv0's F(4,3) forms need D % 4 == 0: any other D runs conv0_mfma and is held to the direct forms' bound
         form = None if layer == 0 and shape[0] % 4 else wino
-        ref, bound = P.dense_ref_bound(layer, x, skip, wf, sh, storage, form)
+        if narrowed(layer, storage):
+            ref, emax = P.ref_emax(layer, x, skip, wf, sh, storage, form, arith, dense=True)
+            chk.add(f"{layer}:tiny:{storage}", *P.err_st(got, ref, emax, storage))
+            continue
+        ref, bound = P.dense_ref_bound(layer, x, skip, wf, sh, storage, form, arith)
         if layer == 10:
             ref, bound = ref[0], bound[0]
         chk.add(f"{layer}:tiny:{storage}", np.abs(got - ref), bound)
@@ -354,14 +495,20 @@ class CraftedBlobs(dict):
         self.sd = sd
 
     def __missing__(self, r):
+        if isinstance(r, tuple):     # ("boundary", storage, run) / ("ends",): the 16-bit rounding probes
+            sdc = P.ends_state(self.sd) if r[0] == "ends" else P.boundary_state(self.sd, r[2], r[1])
+            self[r] = (sdc, _lib.pack_weights(sdc).to(DEV))
+            return self[r]
         sdc = P.crafted_state(self.sd, r, np.random.default_rng(1000 + r))
         self[r] = (sdc, _lib.pack_weights(sdc).to(DEV))
         return self[r]
 
 
 def main():
+    t0 = time.perf_counter()
     name = sys.argv[1]
     case = CASES[name]
+    arith = case.get("arith", "mfma16")
     for k, v in case["env"].items():
         assert os.environ.get(k) == v, f"case {name} needs {k}={v} in the environment"
     sd = synthetic.random_costreg_state(seed=13)
@@ -374,13 +521,15 @@ def main():
             if layer == "tail":
                 probe_tail(chk, storage, sd, blobs, rng)
             else:
-                probe_layer(chk, layer, storage, sd, blobs, case["wino"].get(layer), rng)
+                probe_layer(chk, layer, storage, sd, blobs, case["wino"].get(layer), rng, arith)
         trng = np.random.default_rng(29)     # a stream of their own: the probes above keep their inputs
         for layer in case["layers"]:
             if layer != "tail" or name in TINY_TAIL_CASES:
-                probe_tiny(chk, arena, layer, storage, sd, blobs["rand"], case["wino"].get(layer), trng)
+                probe_tiny(chk, arena, layer, storage, sd, blobs["rand"], case["wino"].get(layer), trng, arith)
     print(json.dumps({"case": name, "ratios": {k: round(v, 4) for k, v in chk.ratios.items()},
-                      "inexact16": chk.inexact}))
+                      "inexact16": chk.inexact, "unexplained16": chk.unexplained,
+                      "e_ratios": {k: round(v, 3) for k, v in chk.eratios.items()},
+                      "seconds": round(time.perf_counter() - t0, 1)}))
     for f in chk.failures:
         print("FAIL", name, f)
     return 1 if chk.failures else 0

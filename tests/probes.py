@@ -10,6 +10,12 @@ is known (fp64 of fp32 operands) and no summation-order tolerance is needed.  Tw
              exact identity BN (scale 1.0, shift 0); every value has its 2nd and 3rd bf16 pieces near their largest
              magnitude, so a split-operand kernel that drops a2b2, a1b3 or a3b1 is off by >= 16 ulp in one direction.
 Dense bound: |got - ref64| <= c 2^-24 S with S = conv(|x|, |w_fold|) + |shift| (+ |skip|), all in fp64.
+
+16-bit storage (layers 0..9; csrc/storage.h: fp32 arithmetic, one round-to-nearest-even cast on the way to HBM): with e_max
+the bound above of the same launch, |got - ref64| <= e_max + ulp_st(|ref64| + e_max) / 2 against the UNROUNDED fp64 value
+of the narrowed operands (bound_st; err_st adds the rule around the largest finite value), and two more single-product
+sets, bit-equal to rne_st(product): the rounding-boundary probes (midpoints and their two sides, ties up and ties down)
+and the ends of fp16's range (subnormal outputs and operands, 65504 and 65520).
 """
 import itertools
 
@@ -27,6 +33,14 @@ TAIL_ULPS = 4           # fused conv11 + prob: two chained single products
 # products in fp32 (x 6 cross terms in the split forms), serially in the direct and fp32-MFMA kernels; on the
 # heavy-tailed volume that measured 39 x 2^-24 S (convg conv4) and 44 x (direct conv6) on the GPU, 29 x in the exact
 # numpy emulation of the split (test_conv_probes_host.py).
+# Rule (as featnet_ref.DENSE_C): kept while the worst measured e / (u S) is under half of it, otherwise twice the measured
+# worst, never above the layer's number of summed products.  16-bit storage, e = |got - ref64| minus the half storage ulp
+# of bound_st, worst over the dense launches (standard normal, heavy-tailed) and cases, MI355X, layers 0..9
+# (profiles/conv16_rounding_ratios.json) -- all far under 32, so 64 stays:
+#   16-bit MFMA forms  f16   1.62 0.73 2.70 0.90 2.72 0.83 1.95 1.53 1.26 1.20
+#                      bf16  1.12 0.44 0.76 0.30 0.82 0.00 1.21 0.27 0.23 0.10
+#   MVS_MFMA16=0       f16   9.28 2.65 7.68 6.31 7.23 4.59 4.91 2.35 3.32 2.88   (conv0 / conv2 / conv4: the direct forms,
+#                      bf16  5.45 1.21 1.70 1.23 3.06 0.61 1.56 2.28 2.41 0.80    MVS_CONV0_WINO=0 / MVS_CONV_WINO=0)
 DENSE_C = 64
 WINO_C = 4              # Winograd probes: |got - want| <= 4 * 2^-24 * (K |x| max|w_co| + |shift|)
 WINO_DENSE_C = 4.2      # Winograd dense: 4.2 * 2^-24 (= 2.5e-7, test_gpu_conv0_tile) * local max|x| * weight mass
@@ -167,6 +181,158 @@ def crafted_state(base, run, rng):
     return sd
 
 
+def one_weight_state(base, run, value):
+    """crafted_state's layout -- identity BN, per layer 0..9 and output channel ONE nonzero weight at
+    (ci, tap) = ((5 co + run) % Cin, (co + run Cout) % 27) -- with the weight value(ci) (fp32)."""
+    sd = {k: np.array(v, np.float32, copy=True) for k, v in base.items()}
+    v1 = identity_var()
+    for l in range(10):
+        ci_n, co_n, _, tr, _ = GEOM[l]
+        key = _lib.CONV_WEIGHT_KEYS[l]
+        w = np.zeros_like(sd[key])
+        for co in range(co_n):
+            ci, tap = (5 * co + run) % ci_n, (co + run * co_n) % 27
+            idx = (ci, co) if tr else (co, ci)
+            w[idx + np.unravel_index(tap, (3, 3, 3))] = value(ci)
+        sd[key] = w
+        pre = _lib.BN_PREFIXES[l]
+        sd[pre + ".weight"] = np.ones(co_n, np.float32)
+        sd[pre + ".bias"] = np.zeros(co_n, np.float32)
+        sd[pre + ".running_mean"] = np.zeros(co_n, np.float32)
+        sd[pre + ".running_var"] = np.full(co_n, v1, np.float32)
+    sd["prob.weight"] = single_prob_weight(run % 8, run % 27, np.float32(1.0))
+    sd["prob.bias"] = np.zeros(1, np.float32)
+    return sd
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# rounding-boundary probes of the 16-bit storage types: every output ONE exact product x w, expected rne_st(x w),
+# no tolerance.  f = FRAC_ST[storage] fraction bits.
+#
+# Weight 1 + j / 2^f, j odd, the same in every output channel of a run; input (1 + k / 2^f) 2^s, k per voxel.  In units
+# of 2^(s - 2f) the product is P = (2^f + j)(2^f + k) = 2^f (2^f + j + k) + j k, and below 2^(2f+1) (product in [1, 2) 2^s)
+# a midpoint between two storage values is P = 2^(f-1) (mod 2^f), i.e. j k = 2^(f-1) (mod 2^f): as j is odd, k = 2^(f-1)
+# is the ONLY solution (x = 1.5 2^s), and in [2, 4) 2^s there is none at all (it would need k = 0).  So
+#   midpoint  k = 2^(f-1)      P = 2^f n + 2^(f-1) with n = 2^f + j + 2^(f-1) + (j-1)/2: n is odd for j = 1 (mod 4) and
+#                              even for j = 3 (mod 4) -- the tie goes UP for j = 1 and DOWN for j = 3;
+#   below     k = 2^(f-1) - 1  P is j units below the next midpoint down  (rounds down; a truncation agrees)
+#   above     k = 2^(f-1) + 1  P is j units above the next midpoint up    (rounds up; a truncation does not)
+# with j = 1 in even runs and j = 3 in odd ones: one / three units of the product's last place, 2^-f / 3 2^-f of a
+# storage ulp, from the midpoint; 3/2 (1 + 3 / 2^f) < 2 keeps every product in [1, 2) 2^s.  As the tie's direction is a
+# property of the weight, a layer needs two runs at least: boundary_runs is crafted_runs, but never one.
+# bf16 also runs s = -20 and s = -100 (launches of their own: a Winograd tile must not mix them with s ~ 0), where the
+# old floor of 2^-14 hid everything; fp32-subnormal magnitudes (below 2^-126) are out of scope.
+# ---------------------------------------------------------------------------------------------------------------
+BOUNDARY_EXPS = {"f16": ((-2, -1, 0, 1, 2),), "bf16": ((-2, -1, 0, 1, 2), (-20,), (-100,))}
+
+
+def boundary_runs(layer):
+    return max(2, crafted_runs(layer))
+
+
+def boundary_weight(storage, run):
+    return np.float32(1.0 + (1 if run % 2 == 0 else 3) / 2.0 ** FRAC_ST[storage])
+
+
+def boundary_state(base, run, storage):
+    return one_weight_state(base, run, lambda ci: boundary_weight(storage, run))
+
+
+def boundary_inputs(shape, storage, exps, rng):
+    """[*shape] 16-bit values (1 + k / 2^f) 2^s: a third each midpoint / below / above, s drawn from exps."""
+    f = FRAC_ST[storage]
+    k = 2 ** (f - 1) + rng.integers(-1, 2, shape)
+    s = np.asarray(exps)[rng.integers(0, len(exps), shape)]
+    return ((1 + k / 2.0 ** f) * 2.0 ** s).astype(np.float32)
+
+
+def classify_boundary(p, storage):
+    """exact products p (fp64) -> (midpoint, below, above, lower neighbour's last bit): `below` / `above` = within 3
+    units of the product's last place (2^-2f relative) of a midpoint, on that side."""
+    q = ulp_st(p, storage)
+    t = p / q
+    n = np.floor(t)
+    d = (t - n - 0.5) * 2.0 ** FRAC_ST[storage]       # offset from the midpoint in product units (exact)
+    return d == 0, (d < 0) & (d >= -3), (d > 0) & (d <= 3), n.astype(np.int64) & 1
+
+
+# The ends of fp16's range, same construction (one weight per output channel, identity BN, every output one exact
+# product), with the weight a function of the input channel ci % 8 so that ONE run holds all eight pairs:
+#   0  w = 2^-12, x = (2n + 1) 2^-13 and its two fp16 neighbours: SUBNORMAL OUTPUTS (both operands normal), midpoints
+#      (n + 1/2) 2^-24 between subnormals; n = 0 is 2^-25, the midpoint between 0 and 2^-24 -> 0, its upper neighbour
+#      2^-25 (1 + 2^-10) -> 2^-24
+#   1  w = 2^12, x = m 2^-24, m < 1024: SUBNORMAL INPUT, normal product m 2^-12 (exact in fp16)
+#   2  w = 683 2^-24 (subnormal once narrowed), x = (1 + k/1024) 2^s, s = 10 .. 13: SUBNORMAL WEIGHT, normal product
+#   3-7  w = mw / 1024, x = 32 (mx + d), d = -1, 0, 1; for d = 0 the product mw mx / 32 is
+#      65519.875 (-> 65504), 65520.03125 (-> inf), 65520 (the tie to the value that no longer exists -> inf),
+#      65488.0625 (-> 65504), 65487.96875 (-> 65472): both sides of 65504's lower midpoint and of 65520.
+END_W = (2.0 ** -12, 2.0 ** 12, 683 * 2.0 ** -24, 1993 / 1024, 1123 / 1024, 1040 / 1024, 1267 / 1024, 1415 / 1024)
+END_MX = (1052, 1867, 2016, 1654, 1481)
+
+
+def ends_state(base):
+    return one_weight_state(base, 0, lambda ci: np.float32(END_W[ci % 8]))
+
+
+def ends_inputs(cin, shape, rng):
+    x = np.zeros((cin,) + tuple(shape), np.float32)
+    for ci in range(cin):
+        p = ci % 8
+        if p == 0:
+            n = np.where(rng.random(shape) < 0.125, 0, rng.integers(0, 1024, shape))
+            v = ((2 * n + 1) * 2.0 ** -13).astype(np.float16)
+            d = rng.integers(-1, 2, shape)
+            v = np.where(d == 0, v, np.nextafter(v, np.where(d > 0, np.float16(1), np.float16(0)).astype(np.float16)))
+        elif p == 1:
+            v = rng.integers(1, 1024, shape) * 2.0 ** -24
+        elif p == 2:
+            v = (1 + rng.integers(0, 1024, shape) / 1024.0) * 2.0 ** rng.integers(10, 14, shape)
+        else:
+            v = 32.0 * (END_MX[p - 3] + rng.integers(-1, 2, shape))
+        x[ci] = v.astype(np.float32)
+    assert (x.astype(np.float16).astype(np.float32) == x).all()
+    return x
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# dense heavy-tailed volumes for 16-bit storage: exp(3 N(0,1)) as the fp32 cases have it; fp16 scaled by 2^p
+# ---------------------------------------------------------------------------------------------------------------
+def heavy(cin, shape, rng):
+    return np.exp(3.0 * rng.standard_normal((cin,) + tuple(shape))).astype(np.float32)
+
+
+def f16_top(layer, x, skip, wf, sh, arith, p):
+    """Largest |fp64 reference| of the layer on fp16(x 2^p); inf once an input no longer fits fp16."""
+    xs = (np.asarray(x, np.float64) * 2.0 ** p).astype(np.float32)
+    if np.abs(xs).max() >= OVERFLOW_ST["f16"]:
+        return np.inf
+    return float(np.abs(ref_emax(layer, xs, skip, wf, sh, "f16", None, arith)[0]).max())
+
+
+def f16_scale(layer, x, skip, wf, sh, arith="mfma16"):
+    """The largest p for which the fp64 reference of the layer on fp16(x 2^p) stays below 65504 everywhere.  On the
+    heavy-tailed volume it is the INPUT that binds: its largest value must stay finite in fp16, and the outputs then
+    reach a few thousand; fp16's top octave of outputs is the business of the range-end probes."""
+    p = int(np.floor(np.log2(OVERFLOW_ST["f16"] / np.abs(x).max())))
+    while f16_top(layer, x, skip, wf, sh, arith, p) >= FMAX_ST["f16"]:
+        p -= 1
+    while f16_top(layer, x, skip, wf, sh, arith, p + 1) < FMAX_ST["f16"]:
+        p += 1
+    return p
+
+
+def heavy_launch(layer, storage, wf, sh, arith="mfma16"):
+    """(x, skip) of the heavy-tailed dense launch of a layer at GEOM's shape: bf16 as drawn; fp16 times 2^p with
+    p = f16_scale, so that the layer's largest reference output lies in fp16's top octave [32752, 65504)."""
+    ci, co, s, tr, shape = GEOM[layer]
+    rng = np.random.default_rng(53 + layer)
+    x = heavy(ci, shape, rng)
+    skip = rng.standard_normal((co,) + tuple(2 * n for n in shape)).astype(np.float32) if tr else None
+    if storage == "f16":
+        x = (x.astype(np.float64) * 2.0 ** f16_scale(layer, x, skip, wf, sh, arith)).astype(np.float32)
+    return x, skip
+
+
 def single_prob_weight(c, tap, value):
     w = np.zeros((1, 8, 3, 3, 3), np.float32)
     w[(0, c) + np.unravel_index(tap, (3, 3, 3))] = value
@@ -215,7 +381,68 @@ def ulp32(s):
     return np.spacing(np.maximum(np.abs(s), 2.0 ** -126).astype(np.float32)).astype(np.float64)
 
 
+# 16-bit storage types: fraction bits, exponent of the smallest normal number, largest finite value.  The first fp64
+# value that RNE takes to infinity is OVERFLOW_ST = FMAX_ST + half the last spacing (fp16: 65520, the tie whose even
+# neighbour 65536 no longer exists).
+FRAC_ST = {"f16": 10, "bf16": 7}
+EMIN_ST = {"f16": -14, "bf16": -126}
+FMAX_ST = {s: (2.0 - 2.0 ** -FRAC_ST[s]) * 2.0 ** e for s, e in (("f16", 15), ("bf16", 127))}
+OVERFLOW_ST = {s: (2.0 - 2.0 ** -(FRAC_ST[s] + 1)) * 2.0 ** e for s, e in (("f16", 15), ("bf16", 127))}
+
+
+def ulp_st(v, storage):
+    """Spacing of the storage type at |v| (fp64 in, fp64 out): 2^(e - f) with e = floor(log2 |v|), not below the type's
+    own smallest exponent -- fp16: 2^-24 through the subnormals, bf16: 2^-133.  fp32-subnormal magnitudes (|v| <
+    2^-126) are out of scope: the kernels' fp32 arithmetic is not exact there."""
+    a = np.abs(np.asarray(v, np.float64))
+    with np.errstate(invalid="ignore"):
+        e = np.where(a > 0, np.frexp(a)[1] - 1, EMIN_ST[storage])      # frexp(0) has exponent 0
+    return np.ldexp(1.0, np.clip(e, EMIN_ST[storage], 1023) - FRAC_ST[storage])
+
+
+def rne_st(v, storage):
+    """Round-to-nearest-even of fp64 values straight to the storage type (no rounding to fp32 in between), as fp64;
+    +-inf from OVERFLOW_ST on.  test_conv_probes_host.py holds it to numpy's float16 and to oracle.round_storage."""
+    v = np.asarray(v, np.float64)
+    q = ulp_st(v, storage)
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = np.round(v / q) * q     # v / q is exact (q a power of two); np.round rounds halves to even
+        r = np.where(np.abs(r) > FMAX_ST[storage], np.copysign(np.inf, v), r)
+    return np.where(np.isfinite(v), r, v)
+
+
+def bound_st(ref, emax, storage):
+    """The contract of csrc/storage.h for a kernel that holds v32 with |v32 - ref| <= emax before its RNE cast:
+    |got - ref| <= emax + ulp_st(|ref| + emax) / 2."""
+    return emax + 0.5 * ulp_st(np.abs(ref) + emax, storage)
+
+
+def err_st(got, ref, emax, storage):
+    """-> (err, bound) of a 16-bit output against its UNROUNDED fp64 reference.  Finite got: |got - ref| against
+    bound_st.  Around the largest finite value: got must be +inf where RNE of every value in [ref - emax, ref + emax] is
+    +inf, finite where every such rounding is finite, and is free in between (-inf likewise); a breach is err = inf."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    T = OVERFLOW_ST[storage]
+    lo, hi = ref - emax, ref + emax
+    bound = bound_st(ref, emax, storage)
+    with np.errstate(invalid="ignore"):
+        err = np.abs(got - ref)
+    pos, neg = got == np.inf, got == -np.inf
+    err = np.where(pos, np.where(hi >= T, 0.0, np.inf), err)
+    err = np.where(neg, np.where(lo <= -T, 0.0, np.inf), err)
+    err = np.where(np.isfinite(got) & ((lo >= T) | (hi <= -T)), np.inf, err)
+    return np.where(np.isnan(err), np.inf, err), bound
+
+
+def near_boundary_st(ref, emax, storage):
+    """True where ref lies within emax of a rounding boundary of the storage type (a midpoint between two neighbours,
+    or the overflow threshold): only there may a kernel that keeps the contract differ from rne_st(ref)."""
+    return rne_st(ref - emax, storage) != rne_st(ref + emax, storage)
+
+
 def ulp16(v, storage):
+    """The storage spacing as the 16-bit bounds took it before bound_st: floored at 2^-14 for both types.  Kept for
+    test_conv_probes_host.py, which shows what the old bounds let through and that the new ones are nowhere wider."""
     a = np.maximum(np.abs(v), 2.0 ** -14)
     return 2.0 ** (np.floor(np.log2(a)) - (10 if storage == "f16" else 7))
 
@@ -226,39 +453,60 @@ def local_max(x, mz):
     return F.max_pool3d(m, kernel_size=(mz, 3, 3), stride=1, padding=(mz // 2, 1, 1))[0, 0].numpy().astype(np.float64)
 
 
-def probe_want_bound(layer, x, skip, wf, sh, storage="f32", wino=None):
+def operands_st(x, skip, wf, storage, arith="mfma16", layer=0):
+    """The operands as a kernel of 16-bit storage holds them.  arith "mfma16" (conv3d_mfma16.hip, the default dispatch):
+    q(x), q(w_fold), q(skip); arith "fp32" (MVS_MFMA16=0, the fp32-MFMA kernels on narrowed volumes): q(x), fp32 w_fold,
+    q(skip) -- the oracle "that rounds storage only".  Layer 10 (prob) has fp32 weights and fp32 logits in both."""
+    if storage == "f32":
+        return x, skip, wf
+    q = lambda t: orc.round_storage(np.asarray(t, np.float32), storage)  # noqa: E731
+    w = q(wf) if (arith == "mfma16" and layer != 10) else np.asarray(wf, np.float32)
+    return q(x), None if skip is None else q(skip), w
+
+
+def _emax(layer, x, skip, wf, sh, wino, dense):
+    """The bound of the fp32 form on these operands: probes PROBE_ULPS ulp32(S) (Winograd: WINO_C 2^-24 (K |x|_local
+    max|w_co| + |shift|)), dense DENSE_C 2^-24 S (Winograd: WINO_DENSE_C 2^-24 (|x|_local weight mass + |shift|))."""
+    if wino:
+        m = wino_tile(wino)[0]
+        w2 = np.abs(wf).reshape(wf.shape[0], -1)
+        wterm = (w2.sum(1) if dense else wino_gain(wino) * w2.max(1))[:, None, None, None]
+        return (WINO_DENSE_C if dense else WINO_C) * U * (local_max(x, 2 * m + 1)[None] * wterm
+                                                          + np.abs(sh)[:, None, None, None])
+    S = scale64(layer, x, wf, sh, skip)
+    return DENSE_C * U * S if dense else PROBE_ULPS * ulp32(S)
+
+
+def ref_emax(layer, x, skip, wf, sh, storage="f32", wino=None, arith="mfma16", dense=False):
+    """(ref64, e_max) of one launch on the operands of operands_st: the fp64 value BEFORE any rounding to storage and
+    the bound of the fp32 value the kernel holds before its cast."""
+    x, skip, wf = operands_st(x, skip, wf, storage, arith, layer)
+    return ref64(layer, x, wf, sh, skip), _emax(layer, x, skip, wf, sh, wino, dense)
+
+
+def _narrowed(layer, storage):
+    return storage != "f32" and layer != 10
+
+
+def _ref_bound(layer, x, skip, wf, sh, storage, wino, arith, dense):
+    ref, emax = ref_emax(layer, x, skip, wf, sh, storage, wino, arith, dense)
+    if not _narrowed(layer, storage):
+        return ref, emax
+    with np.errstate(invalid="ignore"):     # beyond the largest finite value the reference is +-inf
+        over = np.abs(ref) >= OVERFLOW_ST[storage]
+    return np.where(over, np.copysign(np.inf, ref), ref), bound_st(ref, emax, storage)
+
+
+def probe_want_bound(layer, x, skip, wf, sh, storage="f32", wino=None, arith="mfma16"):
     """(want, bound) of one probe launch of layer 0..10 (every output one product at most).
     fp32: the fp64 value of the fp32 operands; bound PROBE_ULPS ulp32(S), or for a Winograd form
-    WINO_C 2^-24 (K |x|_local max|w_co| + |shift|).  16-bit layers 0..9: round16 of the exact value of round16
-    operands, within one storage ulp.  16-bit layer 10: 16-bit input, fp32 weights and logits."""
-    q = lambda t: orc.round_storage(np.asarray(t, np.float32), storage)  # noqa: E731
-    if storage == "f32":
-        want = ref64(layer, x, wf, sh, skip)
-        if wino:
-            m = wino_tile(wino)[0]
-            wmax = np.abs(wf).reshape(wf.shape[0], -1).max(1)[:, None, None, None]
-            return want, WINO_C * U * (wino_gain(wino) * local_max(x, 2 * m + 1)[None] * wmax
-                                       + np.abs(sh)[:, None, None, None])
-        return want, PROBE_ULPS * ulp32(scale64(layer, x, wf, sh, skip))
-    if layer == 10:
-        return ref64(10, q(x), wf, sh), PROBE_ULPS * ulp32(scale64(10, q(x), wf, sh))
-    want = q(ref64(layer, q(x), q(wf), sh, None if skip is None else q(skip))).astype(np.float64)
-    return want, ulp16(want, storage)
+    WINO_C 2^-24 (K |x|_local max|w_co| + |shift|).  16-bit layers 0..9: the UNROUNDED fp64 value of the operands of
+    operands_st, within bound_st = that same e_max + half a storage ulp (err_st adds the rule around the largest
+    finite value).  16-bit layer 10: 16-bit input, fp32 weights and logits."""
+    return _ref_bound(layer, x, skip, wf, sh, storage, wino, arith, False)
 
 
-def dense_ref_bound(layer, x, skip, wf, sh, storage="f32", wino=None):
+def dense_ref_bound(layer, x, skip, wf, sh, storage="f32", wino=None, arith="mfma16"):
     """(ref, bound) of a dense launch: |got - ref64| <= DENSE_C 2^-24 S (Winograd forms: WINO_DENSE_C 2^-24
-    (|x|_local weight mass + |shift|)); 16-bit layers 0..9 additionally one storage ulp of the matched value."""
-    q = lambda t: orc.round_storage(np.asarray(t, np.float32), storage)  # noqa: E731
-    if storage == "f32":
-        ref = ref64(layer, x, wf, sh, skip)
-        if wino:
-            m = wino_tile(wino)[0]
-            wmass = np.abs(wf).reshape(wf.shape[0], -1).sum(1)[:, None, None, None]
-            return ref, WINO_DENSE_C * U * (local_max(x, 2 * m + 1)[None] * wmass + np.abs(sh)[:, None, None, None])
-        return ref, DENSE_C * U * scale64(layer, x, wf, sh, skip)
-    if layer == 10:
-        return ref64(10, q(x), wf, sh), DENSE_C * U * scale64(10, q(x), wf, sh)
-    qs = None if skip is None else q(skip)
-    ref = q(ref64(layer, q(x), q(wf), sh, qs)).astype(np.float64)
-    return ref, ulp16(ref, storage) + DENSE_C * U * scale64(layer, q(x), q(wf), sh, qs)
+    (|x|_local weight mass + |shift|)); 16-bit layers 0..9: bound_st of that e_max around the unrounded reference."""
+    return _ref_bound(layer, x, skip, wf, sh, storage, wino, arith, True)
