@@ -41,10 +41,11 @@
 namespace mvs {
 
 namespace cp {
-constexpr int BY = 4, BX = 2;                      // MFMA M-tiles (2 rows x 8 columns of input voxels) per block
+constexpr int BY = plan::kCpBY, BX = plan::kCpBX;  // MFMA M-tiles (2 rows x 8 columns of input voxels) per block
 constexpr int IY = 2 * BY, IX = 8 * BX;            // input tile: 8 x 16 voxels
 constexpr int OY = 2 * IY, OX = 2 * IX;            // conv11 tile: 16 x 32 voxels
 constexpr int PY = OY - 2, PX = OX - 2;            // logits per tile: 14 x 30
+static_assert(PY == plan::kCpPY && PX == plan::kCpPX, "the planner counts tiles of PY x PX logits");
 
 // conv11 tile in LDS: [plane 2][row OY + 2][half 2][x XP][4 channels], a zero border of one voxel all around;
 // x-adjacent lanes read adjacent 16-byte pieces of one half-row: conflict-free ds_read_b128
@@ -770,49 +771,22 @@ __global__ __launch_bounds__(512, 4) void conv11_prob_split_kernel(
     emit(Do - 1, A, zb == Di);   // the volume's last plane has no successor to complete it
 }
 
-bool conv11_prob_enabled(int dtype) {   // MVS_FUSE_PROB=0: conv11 and prob as two launches (A/B runs)
-    // 16-bit storage: the fused kernel runs the transposed convolution on the 16-bit matrix cores, so it stands in
-    // for the 16-bit MFMA layer kernels only (MVS_MFMA16=0 = fp32 arithmetic on the narrowed operands: two launches)
-    return options().fuse_prob && (dtype == MVS_F32 || mfma16_enabled());
-}
-
+// kernel form, tiles and z chunks: plan::plan_conv11_prob (launch_plan.h)
 int launch_conv11_prob(const void* x, const void* skip, float* cost, const float* blob, int Di, int Hi, int Wi,
                        int dtype, hipStream_t s) {
-    using namespace cp;
     if (dtype != MVS_F32 && dtype != MVS_F16 && dtype != MVS_BF16)
         return fail(MVS_ERR_BAD_DTYPE, "conv11_prob: unknown dtype %d", dtype);
     if ((size_t)Di * Hi * Wi * 64 >= ((size_t)1 << 31))
         return fail(MVS_ERR_BAD_SHAPE, "conv11_prob: plane exceeds 31-bit offsets");
     const BlobLayout L = blob_layout();
-    const int Ho = 2 * Hi, Wo = 2 * Wi;
-    const int nbx = (Wo - 2 + PX - 1) / PX > 0 ? (Wo - 2 + PX - 1) / PX : 1;
-    const int nby = (Ho - 2 + PY - 1) / PY > 0 ? (Ho - 2 + PY - 1) / PY : 1;
-    const int cus = device_cus();
-    // z chunks of >= 4 input planes (every chunk recomputes one input plane and pays a prologue of about half a step):
-    // the split that fills the last round of two-blocks-per-CU best.  (Round 2 took the largest split that keeps all
-    // blocks resident at once: fine at cfg2 (60 tiles x 8 chunks = 480 blocks for 512 slots), 57 % at cfg3 (294 tiles,
-    // ONE chunk of 128 planes each).)
-    const int ntile = nbx * nby, slots = 2 * cus;
-    int best = 1;
-    double best_eff = 0.0;
-    for (int nz = 1; nz <= (Di + 3) / 4; ++nz) {
-        const int zc = (Di + nz - 1) / nz, nzc_ = (Di + zc - 1) / zc;
-        const long nb = (long)ntile * nzc_;
-        const double eff = (double)nb / (double)(((nb + slots - 1) / slots) * slots) * zc / (zc + 1.5);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best = nz; }
-    }
-    int ZC = (Di + best - 1) / best;
-    if (ZC < 4) ZC = 4;
-    if (ZC > Di) ZC = Di;
-    const int nzc = (Di + ZC - 1) / ZC;
-    const dim3 grid(nbx * nby * nzc);
-    // the split-operand kernel addresses the skip tensor through a buffer descriptor (32-bit byte offsets);
-    // MVS_TAIL_SPLIT=0: the fp32-MFMA form of the fused tail (conv11_prob_priv_kernel)
-    if (dtype == MVS_F32 && options().tail_split && (size_t)Di * Hi * Wi * 256 < ((size_t)1 << 32)) {
+    const plan::Plan p = plan::plan_conv11_prob(Di, Hi, Wi, dtype, options(), device_cus());
+    const dim3 grid((unsigned)p.z.grid);
+    const int ZC = p.z.zc, nbx = p.nbx, nby = p.nby;
+    if (p.form == plan::kTailSplit) {
         conv11_prob_split_kernel<<<grid, 512, 0, s>>>(
             static_cast<const float*>(x), reinterpret_cast<const unsigned short*>(blob + L.s16_off[9]), blob + L.b_off[9],
             static_cast<const float*>(skip), blob + L.w_off[10], blob + L.b_off[10], cost, Di, Hi, Wi, ZC, nbx, nby);
-    } else if (dtype == MVS_F32) {
+    } else if (p.form == plan::kTailPriv) {
         conv11_prob_priv_kernel<MVS_F32><<<grid, 512, 0, s>>>(x, blob + L.gp_off[9], blob + L.b_off[9], skip,
                                                                blob + L.w_off[10], blob + L.b_off[10], cost, Di, Hi, Wi,
                                                                ZC, nbx, nby);

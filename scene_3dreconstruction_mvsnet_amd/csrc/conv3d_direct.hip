@@ -405,64 +405,35 @@ int launch_conv_layer_direct(int layer, const void* x, const void* skip, void* y
     }
 }
 
-// MVS_MFMA16=0: fp32 MFMA arithmetic on the 16-bit stored operands instead of the 16-bit matrix cores
-bool mfma16_enabled() { return options().mfma16; }
-
+// One switch over the form plan::plan_layer (launch_plan.h) picks: the selection, its measurements and its switches are
+// there; a refusal stays with the launcher of the form.
 int launch_conv_layer(int layer, const void* x, const void* skip, void* y, const float* blob,
                       int Di, int Hi, int Wi, int dtype, hipStream_t s) {
     const BlobLayout L = blob_layout();
-    const Options& opt = options();
-    // MVS_FORCE_DIRECT=1 routes every layer through the direct kernels (A/B checks in tests)
-    if (opt.force_direct) {
-        if (dtype != MVS_F32)
-            return fail(MVS_ERR_BAD_DTYPE, "MVS_FORCE_DIRECT kernels are fp32-storage only (dtype %d)", dtype);
-        return launch_conv_layer_direct(layer, x, skip, y, blob + L.w_off[layer], blob + L.b_off[layer],
-                                        Di, Hi, Wi, dtype, s);
+    const plan::Plan p = plan::plan_layer(layer, Di, Hi, Wi, dtype, options(), device_cus());
+    const float* bias = p.form == plan::kNone ? nullptr : blob + L.b_off[layer];
+    switch (p.form) {
+        case plan::kDirect:
+            if (dtype != MVS_F32)
+                return fail(MVS_ERR_BAD_DTYPE, "MVS_FORCE_DIRECT kernels are fp32-storage only (dtype %d)", dtype);
+            return launch_conv_layer_direct(layer, x, skip, y, blob + L.w_off[layer], bias, Di, Hi, Wi, dtype, s);
+        case plan::kConv0Z16: case plan::kConv0Tile16: case plan::kConvZ16: case plan::kConvG16: case plan::kDeconvG16:
+            return launch_layer_mfma16(layer, x, skip, y, blob + L.h16_off[dtype == MVS_F16 ? 0 : 1][layer], bias, Di, Hi, Wi,
+                                       dtype, p, s);
+        case plan::kConv0WinoSplit: return launch_conv0_wino43_split(x, y, blob + L.c0w43s_off, bias, Di, Hi, Wi, dtype, s);
+        case plan::kConv0Wino: return launch_conv0_wino43(x, y, blob + L.c0w43_off, bias, Di, Hi, Wi, dtype, s);
+        case plan::kConv0Mfma: return launch_conv0_mfma(x, y, blob + L.c0q_off, bias, Di, Hi, Wi, dtype, s);
+        case plan::kConvGSplit: case plan::kDeconvGSplit:
+            return launch_layer_split(layer, x, skip, y, blob + L.s16_off[layer], bias, Di, Hi, Wi, s);
+        case plan::kConvWz: return launch_convwz_mfma(layer, x, y, blob + L.wz_off[layer], bias, Di, Hi, Wi, dtype, s);
+        case plan::kConvS: return launch_convs_mfma(layer, x, y, blob + L.gp_off[layer], bias, Di, Hi, Wi, dtype, s);
+        case plan::kDeconvS: return launch_deconvs_mfma(layer, x, skip, y, blob + L.gp_off[layer], bias, Di, Hi, Wi, dtype, s);
+        case plan::kConv1Z: case plan::kConvGPersist: case plan::kConvG:
+            return launch_convg_mfma(layer, x, y, blob + L.gp_off[layer], bias, Di, Hi, Wi, dtype, p, s);
+        case plan::kDeconvG: return launch_deconvg_mfma(layer, x, skip, y, blob + L.gp_off[layer], bias, Di, Hi, Wi, dtype, s);
+        case plan::kProbLds: return run_prob(x, y, blob + L.w_off[10], bias, Di, Hi, Wi, dtype, s);
+        default: return fail(MVS_ERR_BAD_SHAPE, "unknown CostRegNet layer %d", layer);
     }
-    // 16-bit storage: 16-bit MFMA arithmetic (conv3d_mfma16.hip) unless MVS_MFMA16=0 asks for fp32
-    // arithmetic on the narrowed operands
-    if (opt.mfma16 && (dtype == MVS_F16 || dtype == MVS_BF16) && layer <= 9)
-        return launch_layer_mfma16(layer, x, skip, y, blob + L.h16_off[dtype == MVS_F16 ? 0 : 1][layer],
-                                   blob + L.b_off[layer], Di, Hi, Wi, dtype, s);
-    if (layer == 0) {
-        // conv0: Winograd F(4,3) along z on the 4x4x1 MFMA (1/2 of the direct form's MFMAs; conv_winograd.hip)
-        // unless MVS_CONV0_WINO=0 asks for the direct form (cross-check) or the volume needs 64-bit offsets
-        // fp32 volumes: the same F(4,3) scheme with every operand split into three bf16 pieces, six cross products per
-        // fp32 product on the bf16 matrix cores, fp32 accumulation (conv0_split.hip: fp32-equivalent arithmetic -- the
-        // per-layer bounds of the fp32 kernel hold unchanged -- at 0.28 instead of 0.36 ms).  MVS_CONV0_SPLIT=0: the
-        // fp32-MFMA kernel below
-        if (opt.conv0_wino && Di % 4 == 0 && (size_t)Di * Hi * Wi * 32 < ((size_t)1 << 31)) {
-            if (opt.conv0_split && dtype == MVS_F32)
-                return launch_conv0_wino43_split(x, y, blob + L.c0w43s_off, blob + L.b_off[0], Di, Hi, Wi, dtype, s);
-            return launch_conv0_wino43(x, y, blob + L.c0w43_off, blob + L.b_off[0], Di, Hi, Wi, dtype, s);
-        }
-        return launch_conv0_mfma(x, y, blob + L.c0q_off, blob + L.b_off[0], Di, Hi, Wi, dtype, s);
-    }
-    // fp32 volumes: the level-1 .. 3 layers on the bf16 matrix cores with split operands (conv3d_mfma16.hip, round 4)
-    // unless MVS_SPLIT_LAYERS=0 keeps the fp32-MFMA kernels below
-    if (opt.split_layers && dtype == MVS_F32 && split_layer_covers(layer))
-        return launch_layer_split(layer, x, skip, y, blob + L.s16_off[layer], blob + L.b_off[layer], Di, Hi, Wi, s);
-    if (layer == 2 || layer == 4) {
-        // stride-1 layers conv2 / conv4: Winograd F(2,3) along z (conv_winograd.hip) unless
-        // MVS_CONV_WINO=0.  conv6 (64 -> 64 on 7,680 voxels) stays direct: with two-plane tiles it has
-        // only 240 blocks for 256 CUs and measured 0.035 vs 0.033 ms.
-        if (opt.conv_wino) return launch_convwz_mfma(layer, x, y, blob + L.wz_off[layer], blob + L.b_off[layer], Di, Hi, Wi, dtype, s);
-    }
-    // the 1/8-resolution layers conv5 / conv6 / conv7: all-K-resident split-K kernels (conv3d_small.hip)
-    if (convs_covers(layer)) {
-        if (kLayers[layer].kind == kConv)
-            return launch_convs_mfma(layer, x, y, blob + L.gp_off[layer], blob + L.b_off[layer], Di, Hi, Wi, dtype, s);
-        return launch_deconvs_mfma(layer, x, skip, y, blob + L.gp_off[layer], blob + L.b_off[layer], Di, Hi, Wi, dtype, s);
-    }
-    if (layer >= 1 && layer <= 6)
-        return launch_convg_mfma(layer, x, y, blob + L.gp_off[layer], blob + L.b_off[layer], Di, Hi, Wi,
-                                 dtype, s);
-    if (layer >= 7 && layer <= 9)
-        return launch_deconvg_mfma(layer, x, skip, y, blob + L.gp_off[layer], blob + L.b_off[layer], Di,
-                                   Hi, Wi, dtype, s);
-    if (layer == 10)
-        return run_prob(x, y, blob + L.w_off[10], blob + L.b_off[10], Di, Hi, Wi, dtype, s);
-    return fail(MVS_ERR_BAD_SHAPE, "unknown CostRegNet layer %d", layer);
 }
 
 }  // namespace mvs

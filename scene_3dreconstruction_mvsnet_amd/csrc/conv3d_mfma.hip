@@ -208,12 +208,6 @@ int launch_conv0_mfma(const void* x, void* y, const float* bq, const float* bias
     MVS_DISPATCH_DTYPE(dtype, (run_conv0_4x4<DT>(x, y, bq, bias, D, H, W, nbq, s)))
 }
 
-// number of CUs of the current device (persistent grids are sized from it); MVS_PERSIST_CUS overrides
-static int persistent_blocks_per_cu_scale() {
-    const int v = options().persist_cus;
-    return v > 0 ? v : device_cus();
-}
-
 // =============================================================================================
 // Generic fp32-MFMA implicit-GEMM 3x3x3 convolution (stride 1 or 2), Cout a multiple of 16:
 // conv1..conv6 of CostRegNet (models/mvsnet.py:38-45; ConvBnReLU3D of models/module.py:26-33).
@@ -584,22 +578,16 @@ __global__ __launch_bounds__(256) void convg_persist_mfma_kernel(
 #undef MVS_STORE_A
 }
 
+// nb persistent blocks -- plan::plan_conv1 sizes the grid (as many blocks per CU as the LDS tile allows) -- or, nb == 0 (it
+// found fewer than four tiles per block), the one-tile-per-block kernel
 template <int DT, int CIN, int COUT, int S, int BZ, int BY, int BX>
-static int run_convg_persist(const void* x, void* y, const float* bp, const float* bias, int Di, int Hi, int Wi,
-                     hipStream_t s) {
-    using G = ConvG<CIN, COUT, S, BZ, BY, BX>;
+static int run_convg_persist(const void* x, void* y, const float* bp, const float* bias, int Di, int Hi, int Wi, int nb,
+                             hipStream_t s) {
+    static_assert(ConvG<CIN, COUT, S, BZ, BY, BX>::TILE_FLOATS == plan::kConv1TileFloats, "the planner sizes the grid from this tile");
+    if (nb == 0) return run_convg<DT, CIN, COUT, S, BZ, BY, BX>(x, y, bp, bias, Di, Hi, Wi, s);
     const int Do = (Di - 1) / S + 1, Ho = (Hi - 1) / S + 1, Wo = (Wi - 1) / S + 1;
     if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
         return fail(MVS_ERR_BAD_SHAPE, "convg_mfma: plane exceeds 31-bit offsets");
-    const int ntiles = ((Wo + 8 * BX - 1) / (8 * BX)) * ((Ho + 2 * BY - 1) / (2 * BY)) * ((Do + BZ - 1) / BZ);
-    // persistent blocks: as many per CU as the LDS tile allows (at most 4)
-    int per_cu = (int)((160 * 1024) / (sizeof(float) * G::TILE_FLOATS + 512));
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const int nblocks = persistent_blocks_per_cu_scale() * per_cu;
-    // only when every block gets several tiles; otherwise the one-tile-per-block kernel balances
-    // better and is leaner (conv3: 1,152 tiles measured 0.037 vs 0.032 ms)
-    if (ntiles < 4 * nblocks) return run_convg<DT, CIN, COUT, S, BZ, BY, BX>(x, y, bp, bias, Di, Hi, Wi, s);
-    const int nb = nblocks;
     convg_persist_mfma_kernel<DT, CIN, COUT, S, BZ, BY, BX><<<nb, 256, 0, s>>>(x, bp, bias, y, Di, Hi, Wi, Do,
                                                                        Ho, Wo);
     return check_hip(hipGetLastError(), "convg_mfma launch");
@@ -623,7 +611,7 @@ static int run_convg_persist(const void* x, void* y, const float* bp, const floa
 // convg_mfma_kernel: identical results.
 // =============================================================================================
 namespace c1z {
-constexpr int TYO = 8, TXO = 16;                 // output tile: 4 x 2 M-tiles of 2 x 8
+constexpr int TYO = plan::kC1zTYO, TXO = plan::kC1zTXO;   // output tile: 4 x 2 M-tiles of 2 x 8
 constexpr int HY = 2 * TYO + 1, HX = 2 * TXO + 1;
 constexpr int PITCH = 73 * 4;                    // floats per row: 73 sixteen-byte slots (66 used)
 constexpr int SLOT = HY * PITCH;                 // one input plane (8 channels): 19.9 KB
@@ -775,44 +763,21 @@ __global__ __launch_bounds__(c1z::THREADS) void conv1z_mfma_kernel(
     }
 }
 
-static int run_conv1z(const void* x, void* y, const float* bp, const float* bias, int Di, int Hi, int Wi, int Do, int Ho,
-                      int Wo, hipStream_t s) {
-    using namespace c1z;
-    const int nbx = (Wo + TXO - 1) / TXO, nby = (Ho + TYO - 1) / TYO, ncol = nbx * nby;
-    int cus = persistent_blocks_per_cu_scale();
-    // z chunks (>= 4 output planes; each chunk re-reads one input plane and pays a prologue of about two steps): the
-    // split that fills the last round of one-block-per-CU best
-    int best = 1;
-    double best_eff = 0.0;
-    for (int nz = 1; nz <= (Do + 3) / 4; ++nz) {
-        const int zc = (Do + nz - 1) / nz, nzc = (Do + zc - 1) / zc;
-        const long nb = (long)ncol * nzc;
-        const double eff = (double)nb / (double)(((nb + cus - 1) / cus) * cus) * zc / (zc + 2.5);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best = nz; }
-    }
-    const int ZC = (Do + best - 1) / best, nzc = (Do + ZC - 1) / ZC;
-    conv1z_mfma_kernel<<<ncol * nzc, THREADS, 0, s>>>(static_cast<const float*>(x), bp, bias, static_cast<float*>(y), Di, Hi,
-                                                      Wi, Do, Ho, Wo, ZC, nbx, nby);
+static int run_conv1z(const void* x, void* y, const float* bp, const float* bias, int Di, int Hi, int Wi,
+                      const plan::Plan& p, hipStream_t s) {
+    const int Do = (Di - 1) / 2 + 1, Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
+    conv1z_mfma_kernel<<<(unsigned)p.z.grid, c1z::THREADS, 0, s>>>(static_cast<const float*>(x), bp, bias, static_cast<float*>(y),
+                                                                  Di, Hi, Wi, Do, Ho, Wo, p.z.zc, p.nbx, p.nby);
     return check_hip(hipGetLastError(), "conv1z_mfma launch");
 }
 
 template <int DT>
 static int launch_convg_dt(int layer, const void* x, void* y, const float* bp, const float* bias, int Di,
-                           int Hi, int Wi, hipStream_t s) {
+                           int Hi, int Wi, const plan::Plan& p, hipStream_t s) {
     switch (layer) {
-        case 1: {
-            // fp32 storage, a volume whose (y, x) columns fill the chip: the z-marching kernel (MVS_CONV1Z=0/1 = never /
-            // always); else the persistent tile kernel
-            if constexpr (DT == MVS_F32) {
-                const int zm = options().conv1z;
-                const int Do = (Di - 1) / 2 + 1, Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
-                const long ncol = (long)((Wo + c1z::TXO - 1) / c1z::TXO) * ((Ho + c1z::TYO - 1) / c1z::TYO);
-                if (zm != 0 && (size_t)Do * Ho * Wo * 16 * 4 < ((size_t)1 << 32) - 64 && (size_t)Di * Hi * Wi * 8 < ((size_t)1 << 31) &&
-                    (zm == 1 || ncol * ((Do + 3) / 4) >= persistent_blocks_per_cu_scale() / 2))
-                    return run_conv1z(x, y, bp, bias, Di, Hi, Wi, Do, Ho, Wo, s);
-            }
-            return run_convg_persist<DT, 8, 16, 2, 1, 2, 2>(x, y, bp, bias, Di, Hi, Wi, s);
-        }
+        case 1:   // z-marching (fp32 storage), persistent or one tile per block: plan::plan_conv1
+            if (p.form == plan::kConv1Z) return run_conv1z(x, y, bp, bias, Di, Hi, Wi, p, s);
+            return run_convg_persist<DT, 8, 16, 2, 1, 2, 2>(x, y, bp, bias, Di, Hi, Wi, p.form == plan::kConvGPersist ? (int)p.z.grid : 0, s);
         case 2: return run_convg<DT, 16, 16, 1, 2, 4, 2>(x, y, bp, bias, Di, Hi, Wi, s);
         case 3: return run_convg<DT, 16, 32, 2, 1, 2, 2>(x, y, bp, bias, Di, Hi, Wi, s);
         case 4: return run_convg<DT, 32, 32, 1, 1, 2, 2>(x, y, bp, bias, Di, Hi, Wi, s);
@@ -822,8 +787,8 @@ static int launch_convg_dt(int layer, const void* x, void* y, const float* bp, c
 
 // layers 1..4 (conv1..conv4; conv5 / conv6: conv3d_small.hip)
 int launch_convg_mfma(int layer, const void* x, void* y, const float* bp, const float* bias, int Di,
-                      int Hi, int Wi, int dtype, hipStream_t s) {
-    MVS_DISPATCH_DTYPE(dtype, (launch_convg_dt<DT>(layer, x, y, bp, bias, Di, Hi, Wi, s)))
+                      int Hi, int Wi, int dtype, const plan::Plan& p, hipStream_t s) {
+    MVS_DISPATCH_DTYPE(dtype, (launch_convg_dt<DT>(layer, x, y, bp, bias, Di, Hi, Wi, p, s)))
 }
 
 // Host-side packing for convg: wfold [27][cin][cout] -> bp [cin/8][cout/16][14][64][4]

@@ -395,6 +395,7 @@ template <class Op, int CIN, int COUT, int S, int BZ, int BY, int BX>
 static int run_convg16(const void* x, void* y, const unsigned short* bp, const float* bias, int Di, int Hi,
                        int Wi, hipStream_t s) {
     using T = typename Op::T;
+    static_assert(plan::tile_is_planned(CIN, COUT, kConv, BZ, BY, BX), "launch_plan.h's tile tables do not name this tile");
     const int Do = (Di - 1) / S + 1, Ho = (Hi - 1) / S + 1, Wo = (Wi - 1) / S + 1;
     if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
         return fail(MVS_ERR_BAD_SHAPE, "convg16_mfma: plane exceeds 31-bit offsets");
@@ -404,36 +405,22 @@ static int run_convg16(const void* x, void* y, const unsigned short* bp, const f
     return check_hip(hipGetLastError(), "convg16_mfma launch");
 }
 
-// does a grid of BZ x BY x BX M-tiles (2 x 8 outputs each) over the OUTPUT of a stride-S layer (S = 1 with the input
-// dims for the transposed layers) still give every CU a block and a half?
-static bool tile_fills_chip(int Di, int Hi, int Wi, int S, int BZ, int BY, int BX) {
-    const int force = options().deep_tiles;   // MVS_DEEP_TILES=1 / 0: always / never (tests, A/B runs)
-    if (force >= 0) return force != 0;
-    const int cus = device_cus();
-    const int Do = (Di - 1) / S + 1, Ho = (Hi - 1) / S + 1, Wo = (Wi - 1) / S + 1;
-    const long nb = (long)((Wo + 8 * BX - 1) / (8 * BX)) * ((Ho + 2 * BY - 1) / (2 * BY)) * ((Do + BZ - 1) / BZ);
-    return 2 * nb >= 3 * (long)cus;
-}
-
+// the block tiles are plan::kTiles16's (run_convg16 asserts it); `deep`: plan_layer16 chose the z-deep one of a pair
 template <int DT>
 static int launch_convg16_dt(int layer, const void* x, void* y, const unsigned short* bp, const float* bias,
-                             int Di, int Hi, int Wi, hipStream_t s) {
+                             int Di, int Hi, int Wi, bool deep, hipStream_t s) {
     switch (layer) {
         case 1: return run_convg16<Op16<DT>, 8, 16, 2, 2, 2, 2>(x, y, bp, bias, Di, Hi, Wi, s);
         case 2: return run_convg16<Op16<DT>, 16, 16, 1, 2, 4, 2>(x, y, bp, bias, Di, Hi, Wi, s);
-        case 3: return run_convg16<Op16<DT>, 16, 32, 2, 4, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);   // cfg5 sweep: 1x2x2 0.0115, 4x1x1 0.0107 ms
-        // conv4 .. conv6: z-deep block tiles (halo planes re-used) wherever they still give every CU a block and a half --
-        // round-4 sweep, cfg3 bf16 (1600x1184x256): conv4 1x2x2 -> 4x2x1 0.0574 -> 0.0456 ms, conv5 1x1x1 -> 2x1x1 0.0296 -> 0.0236,
-        // conv6 1x1x1 -> 4x1x1 0.0479 -> 0.0243; cfg5 fp16 (640x512x192): conv4 0.0133 -> 0.0118, conv5 / conv6 keep 1x1x1
-        // (2x1x1 / 4x1x1 would leave 240 / 120 blocks for 256 CUs: 0.0104 / 0.0145 against 0.0106 / 0.0134)
+        case 3: return run_convg16<Op16<DT>, 16, 32, 2, 4, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
         case 4:
-            if (tile_fills_chip(Di, Hi, Wi, 1, 4, 2, 1)) return run_convg16<Op16<DT>, 32, 32, 1, 4, 2, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+            if (deep) return run_convg16<Op16<DT>, 32, 32, 1, 4, 2, 1>(x, y, bp, bias, Di, Hi, Wi, s);
             return run_convg16<Op16<DT>, 32, 32, 1, 1, 2, 2>(x, y, bp, bias, Di, Hi, Wi, s);
         case 5:
-            if (tile_fills_chip(Di, Hi, Wi, 2, 2, 1, 1)) return run_convg16<Op16<DT>, 32, 64, 2, 2, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+            if (deep) return run_convg16<Op16<DT>, 32, 64, 2, 2, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
             return run_convg16<Op16<DT>, 32, 64, 2, 1, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
         case 6:
-            if (tile_fills_chip(Di, Hi, Wi, 1, 4, 1, 1)) return run_convg16<Op16<DT>, 64, 64, 1, 4, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
+            if (deep) return run_convg16<Op16<DT>, 64, 64, 1, 4, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
             return run_convg16<Op16<DT>, 64, 64, 1, 1, 1, 1>(x, y, bp, bias, Di, Hi, Wi, s);
         default: return fail(MVS_ERR_BAD_SHAPE, "convg16_mfma: layer %d not covered", layer);
     }
@@ -591,16 +578,11 @@ __global__ __launch_bounds__(256) void conv0p16_mfma_kernel(
 //     LDS operations execute in order) and leaves as 16-byte stores, one voxel per lane.
 // Same panel and same k order as conv0p16 (chunk-major, then kz, ky): identical results.
 // =============================================================================================
-// C0Z_TY = rows (= waves) per block: 8 -> one block per CU (default); 4 -> two independent 4-wave blocks per CU
-// (-DC0Z_TY=4) measured slower: 0.632 vs 0.590 ms at cfg3, 0.0876 vs 0.0818 at cfg5 (halo 1.5x instead of 1.25x in y)
-#ifndef C0Z_TY
-#define C0Z_TY 8
-#endif
 #ifndef C0Z_CACHE_C
 #define C0Z_CACHE_C 4
 #endif
 namespace c0z {
-constexpr int TY = C0Z_TY, TX = 32, HY = TY + 2, HX = TX + 2;
+constexpr int TY = plan::kC0zTY, TX = plan::kC0zTX, HY = TY + 2, HX = TX + 2;   // rows (= waves) x columns of a block
 constexpr int CH = HY * HX * 8;                  // 16-bit elements of one chunk of one plane
 constexpr int SLOT = 4 * CH;                     // one plane: [chunk][hy][hx][8]
 constexpr int RING = 4;
@@ -773,7 +755,7 @@ __global__ __launch_bounds__(c0z::THREADS) void conv0z16_mfma_kernel(
 // =============================================================================================
 template <int CIN, int COUT, int S>
 struct ConvZ16 {
-    static constexpr int TY = 8, TX = (S == 1) ? 32 : 16;      // output column
+    static constexpr int TY = plan::kConvZ16TY, TX = plan::convz16_tx(S);      // output column
     static constexpr int NCH = CIN / 8, NT = COUT / 16;
     static constexpr int MPW = (TY / 2) * (TX / 8) / 8;          // M-tiles (2 x 8 outputs) per wave: 2 / 1
     static constexpr int HY = (TY - 1) * S + 3, HX = (TX - 1) * S + 3;
@@ -960,49 +942,12 @@ __global__ __launch_bounds__(512) void convz16_mfma_kernel(
 
 template <int DT, int CIN, int COUT, int S>
 static int run_convz16(const void* x, void* y, const unsigned short* bp, const float* bias, int Di, int Hi, int Wi,
-                       int Do, int Ho, int Wo, int cus, hipStream_t s) {
+                       const plan::Plan& p, hipStream_t s) {
     using G = ConvZ16<CIN, COUT, S>;
-    const int nbx = (Wo + G::TX - 1) / G::TX, nby = (Ho + G::TY - 1) / G::TY, ncol = nbx * nby;
-    int best = 1;
-    double best_eff = 0.0;
-    for (int nz = 1; nz <= (Do + 3) / 4; ++nz) {   // z chunks of >= 4 output planes: best fill of the last round
-        const int zc = (Do + nz - 1) / nz, nzc = (Do + zc - 1) / zc;
-        const long nb = (long)ncol * nzc;
-        const double eff = (double)nb / (double)(((nb + cus - 1) / cus) * cus) * zc / (zc + 2.5);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best = nz; }
-    }
-    const int ZC = (Do + best - 1) / best, nzc = (Do + ZC - 1) / ZC;
-    convz16_mfma_kernel<DT, CIN, COUT, S><<<ncol * nzc, G::THREADS, 0, s>>>(x, bp, bias, y, Di, Hi, Wi, Do, Ho, Wo, ZC, nbx, nby);
-    return check_hip(hipGetLastError(), "convz16_mfma launch");
-}
-
-// layers 1..3 through the z-marching kernel when their columns fill the chip (MVS_CONVZ16=0/1 = never / always)
-template <int DT>
-static int try_convz16(int layer, const void* x, void* y, const unsigned short* bp, const float* bias, int Di, int Hi,
-                       int Wi, hipStream_t s, bool* taken) {
-    *taken = false;
-    const int zm = options().convz16;
-    if (zm == 0 || layer < 1 || layer > 3) return MVS_OK;
-    const int S = layer == 2 ? 1 : 2, cout = layer == 3 ? 32 : 16;
     const int Do = (Di - 1) / S + 1, Ho = (Hi - 1) / S + 1, Wo = (Wi - 1) / S + 1;
-    const int cus = device_cus();
-    const int tx = S == 1 ? 32 : 16;
-    const long ncol = (long)((Wo + tx - 1) / tx) * ((Ho + 7) / 8);
-    if ((size_t)Do * Ho * Wo * cout * 2 >= ((size_t)1 << 32) - 64 || Do < 4) return MVS_OK;
-    // enough columns x 8-plane chunks to fill the chip (cfg5's conv3 -- 12 columns of 48 planes -- measured 0.016 vs
-    // 0.012 ms for the tile kernel: short chunks pay the two-step prologue too often)
-    if (zm != 1 && ncol * (Do / 8) * 4 < (long)cus * 3) return MVS_OK;
-    // round 4, after the tile kernels got z-deep tiles, the XCD-aware order and staged epilogues: conv3 is faster on the tile
-    // kernel at every bench size (cfg3 0.0433-0.0448 against 0.0456-0.0463 ms, cfg5 0.0108 against 0.0154), conv2 on it at cfg5's
-    // size (0.0178 against 0.0204-0.0214) but not at cfg3's (0.106 against 0.087); conv1 stays here (cfg5 0.0215 / 0.0256, cfg3
-    // 0.113 / 0.148)
-    if (zm != 1 && (layer == 3 || (layer == 2 && ncol * (Do / 8) < (long)cus * 3))) return MVS_OK;
-    *taken = true;
-    switch (layer) {
-        case 1: return run_convz16<DT, 8, 16, 2>(x, y, bp, bias, Di, Hi, Wi, Do, Ho, Wo, cus, s);
-        case 2: return run_convz16<DT, 16, 16, 1>(x, y, bp, bias, Di, Hi, Wi, Do, Ho, Wo, cus, s);
-        default: return run_convz16<DT, 16, 32, 2>(x, y, bp, bias, Di, Hi, Wi, Do, Ho, Wo, cus, s);
-    }
+    convz16_mfma_kernel<DT, CIN, COUT, S><<<(unsigned)p.z.grid, G::THREADS, 0, s>>>(x, bp, bias, y, Di, Hi, Wi, Do, Ho, Wo, p.z.zc,
+                                                                                   p.nbx, p.nby);
+    return check_hip(hipGetLastError(), "convz16_mfma launch");
 }
 
 // wfold [27][32][8] -> bp [4][9][64][8] (16-bit): k = (g = kx', j = ci of the chunk), n = (jj, co)
@@ -1270,6 +1215,7 @@ template <class Op, int CIN, int COUT, int BZ, int BY, int BX>
 static int run_deconvg16(const void* x, const void* skip, void* y, const unsigned short* bp,
                          const float* bias, int Di, int Hi, int Wi, hipStream_t s) {
     using T = typename Op::T;
+    static_assert(plan::tile_is_planned(CIN, COUT, kDeconv, BZ, BY, BX), "launch_plan.h's tile tables do not name this tile");
     if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
         return fail(MVS_ERR_BAD_SHAPE, "deconvg16_mfma: plane exceeds 31-bit offsets");
     const int nb = ((Wi + 8 * BX - 1) / (8 * BX)) * ((Hi + 2 * BY - 1) / (2 * BY)) * ((Di + BZ - 1) / BZ);
@@ -1304,83 +1250,55 @@ void pack_deconvg16_weights(const float* wfold, int cin, int cout, int dt, unsig
 // =============================================================================================
 template <int DT>
 static int launch_layer16_dt(int layer, const void* x, const void* skip, void* y, const unsigned short* bp,
-                             const float* bias, int Di, int Hi, int Wi, hipStream_t s) {
-    if (layer == 0) {
-        using namespace c16;
-        if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
-            return fail(MVS_ERR_BAD_SHAPE, "conv0p16_mfma: plane exceeds 31-bit offsets");
-        // z-marching kernel once its (y, x) columns can fill the chip; MVS_CONV0Z16=0 keeps the tile kernel (A/B runs)
-        const int zmarch = options().conv0z16;   // 1 = also at small shapes (tests), 0 = never
-        const int ncol = ((Wi + c0z::TX - 1) / c0z::TX) * ((Hi + c0z::TY - 1) / c0z::TY);
-        const int cus = device_cus();
-        if (zmarch != 0 && Di >= 8 && (size_t)Di * Hi * Wi * 16 < ((size_t)1 << 32) - 64 &&
-            (zmarch == 1 || (size_t)ncol * (Di / 8) >= (size_t)cus / 2)) {
-            // z chunks (>= 8 planes each; every chunk re-reads 2 planes): the split that fills the last round of
-            // one-block-per-CU best
-            int best = 1;
-            double best_eff = 0.0;
-            for (int nz = 1; nz <= Di / 8; ++nz) {
-                const int zc = (Di + nz - 1) / nz, nzc = (Di + zc - 1) / zc;
-                const long nb = (long)ncol * nzc;
-                const long slots = (long)cus * (8 / c0z::TY);   // blocks resident at once
-                const double eff = (double)nb / (double)(((nb + slots - 1) / slots) * slots) * zc / (zc + 2.0);
-                if (eff > best_eff + 1e-9) { best_eff = eff; best = nz; }
+                             const float* bias, int Di, int Hi, int Wi, const plan::Plan& p, hipStream_t s) {
+    const bool deep = p.bz > 1;   // of the two tiles plan_layer16 chooses between for conv4 .. conv9, the z-deep one
+    switch (p.form) {
+        case plan::kConv0Z16:
+        case plan::kConv0Tile16: {
+            using namespace c16;
+            if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31))
+                return fail(MVS_ERR_BAD_SHAPE, "conv0p16_mfma: plane exceeds 31-bit offsets");
+            if (p.form == plan::kConv0Z16) {
+                conv0z16_mfma_kernel<DT><<<(unsigned)p.z.grid, c0z::THREADS, 0, s>>>(x, bp, bias, y, Di, Hi, Wi, p.z.zc, p.nbx, p.nby);
+                return check_hip(hipGetLastError(), "conv0z16_mfma launch");
             }
-            const int ZC = (Di + best - 1) / best, nzc = (Di + ZC - 1) / ZC;
-            conv0z16_mfma_kernel<DT><<<ncol * nzc, c0z::THREADS, 0, s>>>(x, bp, bias, y, Di, Hi, Wi, ZC,
-                                                                          (Wi + c0z::TX - 1) / c0z::TX,
-                                                                          (Hi + c0z::TY - 1) / c0z::TY);
-            return check_hip(hipGetLastError(), "conv0z16_mfma launch");
+            const int nb = ((Wi + TX - 1) / TX) * ((Hi + TY - 1) / TY) * ((Di + TZ - 1) / TZ);
+            conv0p16_mfma_kernel<DT><<<nb, 256, 0, s>>>(x, bp, bias, y, Di, Hi, Wi);
+            return check_hip(hipGetLastError(), "conv0p16_mfma launch");
         }
-        const int nb = ((Wi + TX - 1) / TX) * ((Hi + TY - 1) / TY) * ((Di + TZ - 1) / TZ);
-        conv0p16_mfma_kernel<DT><<<nb, 256, 0, s>>>(x, bp, bias, y, Di, Hi, Wi);
-        return check_hip(hipGetLastError(), "conv0p16_mfma launch");
-    }
-    if (layer <= 3) {
-        bool taken = false;
-        const int st = try_convz16<DT>(layer, x, y, bp, bias, Di, Hi, Wi, s, &taken);
-        if (taken) return st;
-    }
-    if (layer <= 6) return launch_convg16_dt<DT>(layer, x, y, bp, bias, Di, Hi, Wi, s);
-    switch (layer) {
-        // the same for the transposed layers (tiles over the INPUT grid): cfg3 conv7 1x1x1 -> 2x1x1 0.0486 -> 0.0389, conv9 1x4x1
-        // -> 4x2x1 0.1059 -> 0.1026; cfg5 conv9 0.0171 -> 0.0164, conv7 stays (2x1x1: 240 blocks)
-        case 7:
-            if (tile_fills_chip(Di, Hi, Wi, 1, 2, 1, 1)) return run_deconvg16<Op16<DT>, 64, 32, 2, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
-            return run_deconvg16<Op16<DT>, 64, 32, 1, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
-        case 8:
-            if (tile_fills_chip(Di, Hi, Wi, 1, 4, 2, 1)) return run_deconvg16<Op16<DT>, 32, 16, 4, 2, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
-            return run_deconvg16<Op16<DT>, 32, 16, 1, 4, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
-        case 9: return run_deconvg16<Op16<DT>, 16, 8, 1, 4, 2>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+        case plan::kConvZ16:
+            switch (layer) {
+                case 1: return run_convz16<DT, 8, 16, 2>(x, y, bp, bias, Di, Hi, Wi, p, s);
+                case 2: return run_convz16<DT, 16, 16, 1>(x, y, bp, bias, Di, Hi, Wi, p, s);
+                default: return run_convz16<DT, 16, 32, 2>(x, y, bp, bias, Di, Hi, Wi, p, s);
+            }
+        case plan::kConvG16: return launch_convg16_dt<DT>(layer, x, y, bp, bias, Di, Hi, Wi, deep, s);
+        case plan::kDeconvG16:
+            switch (layer) {
+                case 7:
+                    if (deep) return run_deconvg16<Op16<DT>, 64, 32, 2, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+                    return run_deconvg16<Op16<DT>, 64, 32, 1, 1, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+                case 8:
+                    if (deep) return run_deconvg16<Op16<DT>, 32, 16, 4, 2, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+                    return run_deconvg16<Op16<DT>, 32, 16, 1, 4, 1>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+                default: return run_deconvg16<Op16<DT>, 16, 8, 1, 4, 2>(x, skip, y, bp, bias, Di, Hi, Wi, s);
+            }
         default: return fail(MVS_ERR_BAD_SHAPE, "mfma16: layer %d not covered", layer);
     }
 }
 
 int launch_layer_mfma16(int layer, const void* x, const void* skip, void* y, const void* panel,
-                        const float* bias, int Di, int Hi, int Wi, int dtype, hipStream_t s) {
+                        const float* bias, int Di, int Hi, int Wi, int dtype, const plan::Plan& p, hipStream_t s) {
     const unsigned short* bp = static_cast<const unsigned short*>(panel);
-    if (dtype == MVS_F16) return launch_layer16_dt<MVS_F16>(layer, x, skip, y, bp, bias, Di, Hi, Wi, s);
-    if (dtype == MVS_BF16) return launch_layer16_dt<MVS_BF16>(layer, x, skip, y, bp, bias, Di, Hi, Wi, s);
+    if (dtype == MVS_F16) return launch_layer16_dt<MVS_F16>(layer, x, skip, y, bp, bias, Di, Hi, Wi, p, s);
+    if (dtype == MVS_BF16) return launch_layer16_dt<MVS_BF16>(layer, x, skip, y, bp, bias, Di, Hi, Wi, p, s);
     return fail(MVS_ERR_BAD_DTYPE, "mfma16 kernels need fp16 or bf16 storage (dtype %d)", dtype);
 }
 
 // =============================================================================================
 // dispatch for the fp32 layers on the tile kernels with split operands (OpSplit)
 // =============================================================================================
-// fp32 volumes, split operands: conv2, conv3, conv4 (measured at cfg2 against the fp32-MFMA kernels: 0.0588 -> 0.0534,
-// 0.0310 -> 0.0276, 0.0396 -> 0.0329 ms with the 16-bit kernels' block tiles; a sweep of 8-20 tiles per layer
-// (tools/gpu/tile_sweep.sh, BZ x BY x BX M-tiles of 2 x 8 outputs): conv3 1x2x2 -> 2x2x1 0.0275 -> 0.0238, conv4 1x2x2 ->
-// 4x2x1 0.0325 -> 0.0254 -- z-deep, x-narrow tiles re-use the halo planes --, conv2 stays at 2x4x2).  Measured and NOT selected: conv5 / conv6 on this tile kernel (0.0182 / 0.0289
-// against 0.0176 / 0.0242 ms for the all-K-resident split-K fp32 kernels: on 7,680 voxels the chunk pipeline is the cost,
-// not the matrix pipe), conv1 on it (0.083 ms) and as a z-marching kernel with three bf16 rings (csrc/attic/conv1_split_zmarch.hip in commit c2f08ac:
-// 0.054 against 0.046 ms for the fp32-MFMA z-marching kernel)
-// conv9 likewise (deconvgs<32, 16, 2, 4, 1>: 0.0354 -> 0.0266 ms at cfg2; tiles of 1x4x1 / 2x2x1 / 1x2x2 / 1x2x1 M-tiles per
-// block: 0.0278 / 0.0277 / 0.0301 / 0.0316); conv7 on the same kernel measured 0.0248 against 0.0234 ms for the split-K
-// fp32 kernel and is not selected.
-bool split_layer_covers(int layer) {
-    const int deconv = options().split_deconv;   // MVS_SPLIT_DECONV: bit 0 = conv7, bit 1 = conv9; default 2
-    return (layer >= 2 && layer <= 4) || (layer == 7 && (deconv & 1)) || (layer == 8 && (deconv & 2));
-}
+// which layers run here and why: plan::plan_layer (launch_plan.h); the tiles are plan::kTilesSplit's (asserted by the run_*)
 int launch_layer_split(int layer, const void* x, const void* skip, void* y, const void* panel, const float* bias,
                        int Di, int Hi, int Wi, hipStream_t s) {
     const unsigned short* bp = static_cast<const unsigned short*>(panel);

@@ -420,12 +420,7 @@ int launch_deconvs_dt(int layer, const void* x, const void* skip, void* y, const
 
 }  // namespace
 
-// conv5, conv6 (launch_convs_mfma) and conv7 (launch_deconvs_mfma).  The 1/4-resolution layers measured SLOWER in
-// this scheme at cfg2 (3,840 M-tiles = 3.75 rounds of blocks; conv3 0.034 vs 0.031 ms, conv4 direct 0.045 vs 0.039
-// Winograd, conv9 0.041 vs 0.035): with several rounds per CU the chunk pipeline of co-resident blocks overlaps
-// well enough, and the wider blocks only lose occupancy.
-bool convs_covers(int layer) { return layer >= 5 && layer <= 7; }
-
+// conv5, conv6 (launch_convs_mfma) and conv7 (launch_deconvs_mfma): plan::plan_layer says why these and not the others
 int launch_convs_mfma(int layer, const void* x, void* y, const float* bp, const float* bias, int Di, int Hi, int Wi,
                       int dtype, hipStream_t s) {
     if ((size_t)Di * Hi * Wi * 8 >= ((size_t)1 << 31)) return fail(MVS_ERR_BAD_SHAPE, "convs_mfma: plane exceeds 31-bit offsets");

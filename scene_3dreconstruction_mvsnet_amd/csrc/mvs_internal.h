@@ -7,31 +7,12 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "launch_plan.h"   // LayerSpec, kLayers, Options and the launch planner (HIP-free)
 #include "mvs_abi.h"
 
 namespace mvs {
 
 constexpr int kC = 32;  // feature channels (FeatureNet output, models/mvsnet.py:24)
-
-// CostRegNet layer table (models/mvsnet.py:35-62).
-enum LayerKind { kConv = 0, kDeconv = 1 };
-struct LayerSpec {
-    int cin, cout, stride, kind;
-    int level_in, level_out;  // resolution level: voxel dims = (D,h,w) >> level
-};
-constexpr LayerSpec kLayers[MVS_NUM_LAYERS] = {
-    {32, 8, 1, kConv, 0, 0},     // 0 conv0
-    {8, 16, 2, kConv, 0, 1},     // 1 conv1
-    {16, 16, 1, kConv, 1, 1},    // 2 conv2
-    {16, 32, 2, kConv, 1, 2},    // 3 conv3
-    {32, 32, 1, kConv, 2, 2},    // 4 conv4
-    {32, 64, 2, kConv, 2, 3},    // 5 conv5
-    {64, 64, 1, kConv, 3, 3},    // 6 conv6
-    {64, 32, 2, kDeconv, 3, 2},  // 7 conv7  (+conv4)
-    {32, 16, 2, kDeconv, 2, 1},  // 8 conv9  (+conv2)
-    {16, 8, 2, kDeconv, 1, 0},   // 9 conv11 (+conv0)
-    {8, 1, 1, kConv, 0, 0},      // 10 prob (bias, no BN / ReLU)
-};
 
 // Packed weight blob: for every layer l, fp32 weights [27 taps][cin][cout] with BN folded in,
 // followed by fp32 bias[cout]; each section starts 256-byte aligned.  Tap index = kd*9+kh*3+kw
@@ -220,52 +201,13 @@ __host__ __device__ constexpr Deconv16Tap deconv16_tap(int ks, int q) {
                    : (q == 0 ? Deconv16Tap{3, 0, 1, 2, 0, 1} : Deconv16Tap{3, 0, 1, 0, 1, 1});
 }
 
-// Upper ends of the shape domain (include/mvs_abi.h states them per entry point), from the kernels' index types:
-//  - the per-pixel ops (soft-argmin, depth regression, the soft-argmin backward) hold h*w and the pixel index of the
-//    last, partly filled block in an int: h*w + 255 (the largest block of the three) must not wrap
-//  - the soft-argmin's depth index travels as a float (sum_d p_d * d, then trunc): exact up to 2^24
-//  - every CostRegNet kernel form addresses one 8-channel plane of its INPUT with int offsets ("plane exceeds 31-bit
-//    offsets" in the MFMA launchers); planes are told apart and outputs addressed with size_t
-constexpr size_t kMaxPixels = ((size_t)1 << 31) - 256;
-constexpr int kMaxSoftargminD = 1 << 24;
-constexpr size_t kMaxConvInputVoxels = ((size_t)1 << 28) - 1;   // Di*Hi*Wi*8 < 2^31
-//  - prob_lds (layer 10) keeps a piece's offset from its tile's halo origin in an int: up to 5 planes, 9 rows and 33
-//    voxels on, whatever D and H are: ((5 Hi + 9) Wi + 33) * 8 + 4 < 2^31
-constexpr size_t kMaxProbHaloVoxels = ((size_t)1 << 28) - 1;
-//  - mvs_homo_warp: one thread per (d, y, x), 256 to a block, fewer than 2^31 blocks; element offsets are size_t
-constexpr size_t kMaxHomoWarpThreads = (((size_t)1 << 31) - 2) * 256;
-constexpr size_t kMaxHomoWarpOutput = (size_t)1 << 61;
+// (the upper ends of the shape domain, kMaxPixels .. kMaxHomoWarpOutput: launch_plan.h)
 
 // thread-local error text
 int fail(int code, const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);
 
-// Kernel-selection switches (environment variables MVS_*), read once on first use (DESIGN.md lists why each exists).
-// Unless noted, a bool switch is on by default and "0" (first character) turns it off.
-struct Options {
-    bool conv0_wino;              // MVS_CONV0_WINO: conv0 as Winograd F(4,3) along z; off = the direct 4x4x1 MFMA form
-    bool conv_wino;               // MVS_CONV_WINO: conv2 / conv4 as Winograd F(2,3) along z (fp32 MFMA path)
-    bool conv0_split;             // MVS_CONV0_SPLIT: conv0 of fp32 volumes with split bf16 operands; off = fp32 MFMA
-    bool split_layers;            // MVS_SPLIT_LAYERS: conv2 .. conv4 (+ MVS_SPLIT_DECONV) of fp32 volumes, split operands
-    bool mfma16;                  // MVS_MFMA16: 16-bit storage on the 16-bit matrix cores; off = fp32 MFMA arithmetic
-    bool fuse_prob;               // MVS_FUSE_PROB: conv11 + prob as one kernel; off = two launches
-    bool tail_split;              // MVS_TAIL_SPLIT: the fused tail of fp32 volumes with split operands; off = fp32 MFMA
-    bool warp_tc;                 // MVS_WARP_TC: the tap-cache warp + variance kernel (fp32 features); off = plain gather
-    bool warp_tc16;               // MVS_WARP_TC16: the same for 16-bit features
-    bool force_direct;            // MVS_FORCE_DIRECT, "1" = on (default off): VALU direct kernels for every layer
-    bool feat16;                  // MVS_FEAT16, "1" = on (default off): the 16-bit modes gather from a narrowed feature copy
-    bool feat_split01;            // MVS_FEAT_SPLIT01, "1" = on (default off): FeatureNet conv0 and conv1 as two kernels
-    int conv1z;                   // MVS_CONV1Z: fp32 conv1 z-marching kernel never (0) / always (1); -1 (unset) = by size
-    int convz16;                  // MVS_CONVZ16: the same for the 16-bit conv1 .. conv3
-    int conv0z16;                 // MVS_CONV0Z16: the same for the 16-bit conv0
-    int deep_tiles;               // MVS_DEEP_TILES: z-deep 16-bit block tiles never (0) / always (1); -1 (unset) = by size
-    int split_deconv;             // MVS_SPLIT_DECONV: split-operand transposed layers, bit 0 = conv7, bit 1 = conv9; default 2
-    int persist_cus;              // MVS_PERSIST_CUS: > 0 replaces the CU count in conv3d_mfma.hip's persistent grid sizing
-    // MVS_WARP_DEPTH_FASTEST, parsed two ways: the plain kernel forces the depth-slab-fastest order on "1" (default by
-    // size); the tap-cache kernel takes its integer value, 1 / 0 = always / never, -1 (unset) = by size
-    bool warp_depth_fastest;
-    int warp_depth_fastest_tc;
-};
+// the switches of launch_plan.h's Options, read from the environment once on first use
 const Options& options();
 int device_cus();   // CU count of the current device, cached per device id (256 if the query fails)
 
@@ -290,11 +232,11 @@ int launch_warp_variance16(const void* feats16, const float* rt, const float* dv
 int launch_relative_proj(const float* proj, float* rt, int N, hipStream_t s);
 int launch_warp_variance(const float* feats_t, const float* rt, const float* dv, void* var, int N,
                          int D, int h, int w, int dtype, hipStream_t s);
-bool warp_tc_fits(int N, int D, int h, int w, int fes, int ves);   // the tap-cache kernel's range
+// the tap-cache kernels take the slab, the block order and the grid from `p` (plan::plan_warp, form kWarpTc)
 int launch_warp_variance_tc(const float* feats_p, const float* rt, const float* dv, void* var, int N, int D,
-                            int h, int w, int dtype, hipStream_t s);
+                            int h, int w, int dtype, const plan::Plan& p, hipStream_t s);
 int launch_warp_variance_tc16(const void* feats16, const float* rt, const float* dv, void* var, int N, int D,
-                              int h, int w, int dtype, hipStream_t s);
+                              int h, int w, int dtype, const plan::Plan& p, hipStream_t s);
 int launch_homo_warp(const float* fea, const float* rt, const float* dv, float* out, int C, int D,
                      int h, int w, hipStream_t s);
 int launch_conv_layer(int layer, const void* x, const void* skip, void* y, const float* blob,
@@ -315,13 +257,12 @@ int launch_conv0_mfma(const void* x, void* y, const float* bq, const float* bias
                       int dtype, hipStream_t s);
 void pack_conv0_4x4_weights(const float* wfold, float* bq);
 int launch_convg_mfma(int layer, const void* x, void* y, const float* bp, const float* bias, int Di,
-                      int Hi, int Wi, int dtype, hipStream_t s);
+                      int Hi, int Wi, int dtype, const plan::Plan& p, hipStream_t s);
 void pack_convg_weights(const float* wfold, int cin, int cout, float* bp);
 int launch_deconvg_mfma(int layer, const void* x, const void* skip, void* y, const float* bp,
                         const float* bias, int Di, int Hi, int Wi, int dtype, hipStream_t s);
 void pack_deconvg_weights(const float* wfold, int cin, int cout, float* bp);
 // all-K-resident split-K kernels for the small levels (conv3d_small.hip); same panels as convg / deconvg
-bool convs_covers(int layer);
 int launch_convs_mfma(int layer, const void* x, void* y, const float* bp, const float* bias, int Di, int Hi, int Wi,
                       int dtype, hipStream_t s);
 int launch_deconvs_mfma(int layer, const void* x, const void* skip, void* y, const float* bp, const float* bias, int Di,
@@ -329,13 +270,10 @@ int launch_deconvs_mfma(int layer, const void* x, const void* skip, void* y, con
 // conv11 (+ conv0 skip) and prob in one kernel (conv11_prob.hip): fp32 storage, or 16-bit storage on the 16-bit MFMA
 int launch_conv11_prob(const void* x, const void* skip, float* cost, const float* blob, int Di, int Hi,
                        int Wi, int dtype, hipStream_t s);
-bool conv11_prob_enabled(int dtype);
-bool mfma16_enabled();   // MVS_MFMA16 != 0
 int launch_layer_mfma16(int layer, const void* x, const void* skip, void* y, const void* panel,
-                        const float* bias, int Di, int Hi, int Wi, int dtype, hipStream_t s);
+                        const float* bias, int Di, int Hi, int Wi, int dtype, const plan::Plan& p, hipStream_t s);
 void pack_mfma16_panel(int layer, const float* wfold, int dt, void* out);
 // fp32 volumes with split bf16 operands (three pieces, six cross products): the tile kernels of conv3d_mfma16.hip
-bool split_layer_covers(int layer);
 int launch_layer_split(int layer, const void* x, const void* skip, void* y, const void* panel, const float* bias,
                        int Di, int Hi, int Wi, hipStream_t s);
 void pack_split_panels(int layer, const float* wfold, void* out);

@@ -298,21 +298,15 @@ __global__ __launch_bounds__(256) void warp_variance16_kernel(const void* __rest
     }
 }
 
-// MVS_WARP_DEPTH_FASTEST=1 forces the depth-slab-fastest block order (default: only when the feature
-// maps exceed the L2s), so tests can reach it at small shapes
-static bool force_depth_fastest() { return options().warp_depth_fastest; }
-
+// Tap-cache or plain kernel and the block order: plan::plan_warp (launch_plan.h), asked with the feature copy's element size
 int launch_warp_variance16(const void* feats16, const float* rt, const float* dv, void* var, int N, int D,
                            int h, int w, int dtype, hipStream_t s) {
     if (h < 2 || w < 2) return fail(MVS_ERR_BAD_SHAPE, "warp_variance: h,w must be >= 2");
-    // The tap-cache kernel (second form, warp_variance_tc.hip) is the default here too: cfg5 0.20 ->
-    // 0.15 ms, cfg3 1.84 -> 1.39 ms against the plain kernel below (MVS_WARP_TC16=0 selects it; the
-    // FIRST form of the tap-cache kernel had been slower than the plain kernel with 16-bit features).
-    if (options().warp_tc16 && warp_tc_fits(N, D, h, w, 2, 2))
-        return launch_warp_variance_tc16(feats16, rt, dv, var, N, D, h, w, dtype, s);
+    const plan::Plan p = plan::plan_warp(N, D, h, w, dtype, 2, options());
+    if (p.form == plan::kWarpTc) return launch_warp_variance_tc16(feats16, rt, dv, var, N, D, h, w, dtype, p, s);
     const unsigned nd = (D + kWarpDepthSlab - 1) / kWarpDepthSlab;
     const unsigned np = (h * w + kWarpPixPerBlock - 1) / kWarpPixPerBlock;
-    const bool depth_fastest = force_depth_fastest() || (size_t)N * h * w * 64 > ((size_t)24 << 20);
+    const bool depth_fastest = p.depth_fastest != 0;
     const dim3 grid = depth_fastest ? dim3(nd, np) : dim3(np, nd);
     if (dtype == MVS_F16) {
         if (depth_fastest) warp_variance16_kernel<MVS_F16, true><<<grid, 256, 0, s>>>(feats16, rt, dv, var, N, D, h, w);
@@ -329,15 +323,12 @@ int launch_warp_variance16(const void* feats16, const float* rt, const float* dv
 int launch_warp_variance(const float* feats_p, const float* rt, const float* dv, void* var, int N,
                          int D, int h, int w, int dtype, hipStream_t s) {
     if (h < 2 || w < 2) return fail(MVS_ERR_BAD_SHAPE, "warp_variance: h,w must be >= 2");
-    // Tap-cache kernel (warp_variance_tc.hip) for 2..5 views; MVS_WARP_TC=0 keeps the plain gather
-    if (options().warp_tc && warp_tc_fits(N, D, h, w, 4, dtype == MVS_F32 ? 4 : 2))
-        return launch_warp_variance_tc(feats_p, rt, dv, var, N, D, h, w, dtype, s);
+    const plan::Plan p = plan::plan_warp(N, D, h, w, dtype, 4, options());
+    if (p.form == plan::kWarpTc) return launch_warp_variance_tc(feats_p, rt, dv, var, N, D, h, w, dtype, p, s);
     const unsigned nd = (D + kWarpDepthSlab - 1) / kWarpDepthSlab;
     const unsigned np = (h * w + kWarpPixPerBlock - 1) / kWarpPixPerBlock;
     float* v = static_cast<float*>(var);
-    // all views' features (N x 32 channels x fp32) against the 32 MB of aggregate L2
-    const bool depth_fastest = force_depth_fastest() || (size_t)N * h * w * 128 > ((size_t)24 << 20);
-    if (depth_fastest) {
+    if (p.depth_fastest) {
         dim3 grid(nd, np);
         if (dtype == MVS_F32) warp_variance_kernel<MVS_F32, true><<<grid, 256, 0, s>>>(feats_p, rt, dv, v, N, D, h, w);
         else if (dtype == MVS_F16) warp_variance_kernel<MVS_F16, true><<<grid, 256, 0, s>>>(feats_p, rt, dv, v, N, D, h, w);

@@ -210,8 +210,8 @@ __device__ __forceinline__ void store_voxel_buf(__amdgpu_buffer_rsrc_t rs, unsig
 // volume kMaxSlab + 4 planes clear of that range.  The PAIR loop steps four depths at a time with guards for a last pair or
 // step cut short; D is a multiple of 8 (check_dims), so with slabs that are multiples of 4 every slab, the ragged last
 // one included, runs whole iterations only -- the guarded partial steps never run, and no test covers them.
-constexpr int kTcSlabs[] = {40, 44, 36, 32, 28, 24};
-constexpr int kMaxSlab = 44;
+using plan::kMaxSlab;
+using plan::kTcSlabs;   // launch_plan.h
 constexpr bool tc_slabs_ok() {
     for (const int s : kTcSlabs)
         if (s > kMaxSlab || s % 4 != 0) return false;
@@ -424,28 +424,14 @@ __global__ __launch_bounds__(256, 4) void warp_variance_tc2_kernel(const void* _
     }
 }
 
+// slab, block order and grid: plan::plan_warp (launch_plan.h), with the sweeps behind them
 template <int DT, int FDT>
 int launch_tc2_dt(const void* feats_p, const float* rt, const float* dv, void* var, int N, int D, int h, int w,
-                  hipStream_t s) {
+                  const plan::Plan& p, hipStream_t s) {
     constexpr int CPT = 4;                 // 8 lanes per pixel, 16 waves per CU (CPT = 8: 0.166 vs 0.157 ms at cfg2)
-    // depths a thread marches through (cfg2, kernel + transpose: 8 / 12 / 16 / 24 / 32 / 48 / 64 = 0.183 / 0.172 / 0.168 /
-    // 0.161 / 0.160 / 0.160 / 0.159 ms in round 3)
-    // Round 4 sweep (bench per-kernel pass, cfg2 / cfg5 / cfg3): 12: 0.168 / 0.129 / 1.63; 20: 0.160 / 0.122 / 1.48; 24: 0.157
-    // / 0.122 / 1.46; 28: 0.157 / 0.122 / 1.52; 40: 0.155 / 0.120 / 1.44; 52: 0.156 / 0.121 / 1.44; 88: 0.163 / 0.131 / 1.44
-    // -- and a slab count that is a multiple of 8 is a trap in the depth-slab-fastest order (cfg3, D = 256: slab 16 /
-    // 32 / 64 = 1.95 / 1.86 / 1.78 ms): the linear block id then sends slab s of EVERY pixel block to XCD s % 8, so every
-    // XCD's L2 streams the whole feature set
-    int slab = 40;
-    for (const int cand : kTcSlabs) {   // the first whose slab count is not a multiple of 8 (D = 320: 36)
-        slab = cand;
-        if (((D + cand - 1) / cand) % 8 != 0) break;
-    }
-    constexpr int pix = 256 / (32 / CPT);
-    constexpr size_t fes = FDT == MVS_F32 ? 4 : 2;
-    // all views' features against the 32 MB of aggregate L2 (MVS_WARP_DEPTH_FASTEST=1 / 0: always / never)
-    const int force_df = options().warp_depth_fastest_tc;
-    const int df = force_df >= 0 ? force_df : ((size_t)N * h * w * 32 * fes > ((size_t)24 << 20) ? 1 : 0);
-    const unsigned npb = (h * w + pix - 1) / pix, nsl = (D + slab - 1) / slab;
+    static_assert(256 / (32 / CPT) == plan::kTcPix, "the planner counts pixel blocks of kTcPix pixels");
+    const int slab = p.z.zc, df = p.depth_fastest;
+    const unsigned npb = p.nbx, nsl = p.z.n;
     const dim3 grid = df ? dim3(nsl, npb) : dim3(npb, nsl);
     // PAIR = 1: one projection pass per two depth steps (quad q of a pixel evaluates depth d + q)
 #define MVS_TC2(NV) warp_variance_tc2_kernel<DT, FDT, NV, CPT, 0, 1><<<grid, 256, 0, s>>>(feats_p, rt, dv, var, N, D, h, w, slab, df);
@@ -462,38 +448,27 @@ int launch_tc2_dt(const void* feats_p, const float* rt, const float* dv, void* v
 
 }  // namespace
 
-// the kernel needs 32-bit byte offsets into the feature copy and the volume, and o00 << 2 in an int; 2 <= N <= 5
-// (16 VGPRs of cached taps per source view).  Other problems run the plain kernel (warp_variance.hip).
-bool warp_tc_fits(int N, int D, int h, int w, int fes, int ves) {
-    const size_t hw = (size_t)h * w;
-    // (+ kMaxSlab + 4 = 48 depth planes of one channel plane: the parking range of the last block's out-of-image lanes)
-    constexpr size_t park = kMaxSlab + 4;
-    static_assert(park == 48, "tests/test_gpu_limits.py's tc_fits restates the 48-plane margin");
-    return N >= 2 && N <= 5 && 4 * (size_t)N * hw * 8 * fes < ((size_t)1 << 31) &&
-           4 * (size_t)D * hw * 8 * ves + park * hw * 8 * ves < ((size_t)1 << 32) - 64 && hw < ((size_t)1 << 29);
-}
-
 // fp32 features [4][N][h][w][8], volume in `dtype`
 int launch_warp_variance_tc(const float* feats_p, const float* rt, const float* dv, void* var, int N, int D,
-                            int h, int w, int dtype, hipStream_t s) {
-    if (!warp_tc_fits(N, D, h, w, 4, dtype == MVS_F32 ? 4 : 2))
+                            int h, int w, int dtype, const plan::Plan& p, hipStream_t s) {
+    if (!plan::warp_tc_fits(N, D, h, w, 4, dtype == MVS_F32 ? 4 : 2))
         return fail(MVS_ERR_BAD_SHAPE, "warp_variance_tc: N,D,h,w = %d,%d,%d,%d outside the kernel's range", N, D, h, w);
     switch (dtype) {
-        case MVS_F32: return launch_tc2_dt<MVS_F32, MVS_F32>(feats_p, rt, dv, var, N, D, h, w, s);
-        case MVS_F16: return launch_tc2_dt<MVS_F16, MVS_F32>(feats_p, rt, dv, var, N, D, h, w, s);
-        case MVS_BF16: return launch_tc2_dt<MVS_BF16, MVS_F32>(feats_p, rt, dv, var, N, D, h, w, s);
+        case MVS_F32: return launch_tc2_dt<MVS_F32, MVS_F32>(feats_p, rt, dv, var, N, D, h, w, p, s);
+        case MVS_F16: return launch_tc2_dt<MVS_F16, MVS_F32>(feats_p, rt, dv, var, N, D, h, w, p, s);
+        case MVS_BF16: return launch_tc2_dt<MVS_BF16, MVS_F32>(feats_p, rt, dv, var, N, D, h, w, p, s);
         default: return fail(MVS_ERR_BAD_DTYPE, "warp_variance_tc: unknown dtype %d", dtype);
     }
 }
 
 // 16-bit features (same dtype as the volume): half the gather bytes
 int launch_warp_variance_tc16(const void* feats16, const float* rt, const float* dv, void* var, int N, int D,
-                              int h, int w, int dtype, hipStream_t s) {
-    if (!warp_tc_fits(N, D, h, w, 2, 2))
+                              int h, int w, int dtype, const plan::Plan& p, hipStream_t s) {
+    if (!plan::warp_tc_fits(N, D, h, w, 2, 2))
         return fail(MVS_ERR_BAD_SHAPE, "warp_variance_tc16: N,D,h,w = %d,%d,%d,%d outside the kernel's range", N, D, h, w);
     switch (dtype) {
-        case MVS_F16: return launch_tc2_dt<MVS_F16, MVS_F16>(feats16, rt, dv, var, N, D, h, w, s);
-        case MVS_BF16: return launch_tc2_dt<MVS_BF16, MVS_BF16>(feats16, rt, dv, var, N, D, h, w, s);
+        case MVS_F16: return launch_tc2_dt<MVS_F16, MVS_F16>(feats16, rt, dv, var, N, D, h, w, p, s);
+        case MVS_BF16: return launch_tc2_dt<MVS_BF16, MVS_BF16>(feats16, rt, dv, var, N, D, h, w, p, s);
         default: return fail(MVS_ERR_BAD_DTYPE, "warp_variance_tc16 needs fp16 or bf16 (dtype %d)", dtype);
     }
 }

@@ -8,8 +8,8 @@ tiles per block, convz16 below 4 output planes, conv0z16 below D = 8), which the
 Prints one JSON line with the measured max ratios (got - want over the bound, per layer / set / storage) and exits
 non-zero after listing every violated bound.
 
-Which kernel each case reaches at the probe shapes of probes.GEOM (the dispatch in conv3d_direct.hip
-launch_conv_layer, conv3d_mfma16.hip launch_layer16_dt / launch_layer_split, conv3d_mfma.hip launch_convg_dt,
+Which kernel each case reaches at the probe shapes of probes.GEOM (the planner in launch_plan.h, the dispatch in
+conv3d_direct.hip launch_conv_layer, conv3d_mfma16.hip launch_layer16_dt / launch_layer_split, conv3d_mfma.hip launch_convg_dt,
 conv11_prob.hip launch_conv11_prob); "wino" names the layers held to a Winograd bound (probes.WINO).
   fp32 "default": conv0 conv0_w48t (split-operand F(4,3), D % 4 == 0); conv1 convg (run_convg_persist falls back to the
       one-tile-per-block kernel below 4 tiles per block, and conv1z needs columns that fill the chip); conv2-conv4
@@ -181,15 +181,17 @@ INSTANTIATIONS16 = {
 }
 # what 16-bit storage cannot reach, and the line of the dispatch that excludes it (file, line as written)
 UNREACHABLE16 = {
-    "conv1z_mfma_kernel (run_conv1z)": ("conv3d_mfma.hip", "if constexpr (DT == MVS_F32) {"),
+    "conv1z_mfma_kernel (run_conv1z)": ("launch_plan.h", "if (dtype == MVS_F32 && opt.conv1z != 0 &&"),
     "conv3d_direct_kernel / deconv3d_direct_kernel (MVS_FORCE_DIRECT=1)": (
         "conv3d_direct.hip",
         'return fail(MVS_ERR_BAD_DTYPE, "MVS_FORCE_DIRECT kernels are fp32-storage only (dtype %d)", dtype);'),
     "the split-operand tile kernels run_convg16<OpSplit,...> / run_deconvg16<OpSplit,...> (MVS_SPLIT_DECONV)": (
-        "conv3d_direct.hip", "if (opt.split_layers && dtype == MVS_F32 && split_layer_covers(layer))"),
-    "conv0_w48t_kernel (launch_conv0_wino43_split)": ("conv3d_direct.hip", "if (opt.conv0_split && dtype == MVS_F32)"),
+        "launch_plan.h", "if (opt.split_layers && dtype == MVS_F32) {"),
+    "conv0_w48t_kernel (launch_conv0_wino43_split)": (
+        "launch_plan.h", "return formed(opt.conv0_split && dtype == MVS_F32 ? kConv0WinoSplit : kConv0Wino);"),
     "the fused 16-bit tail conv11_prob16_kernel under MVS_MFMA16=0": (
-        "conv11_prob.hip", "return options().fuse_prob && (dtype == MVS_F32 || mfma16_enabled());"),
+        "launch_plan.h",
+        "inline bool tail_fused(int dtype, const Options& opt) { return opt.fuse_prob && (dtype == MVS_F32 || opt.mfma16); }"),
 }
 KERNELS = {
     "conv0_w48t_kernel": "default",

@@ -260,24 +260,40 @@ def _function_body(src, signature):
 
 def test_every_storage_templated_launcher_has_a_16bit_case():
     """A launcher templated on the storage type DT compiles other loads, stores and casts for F16 / BF16 (St<DT>):
-    its F32 probe case does not cover them.  Reachability is read from the dispatch: launch_conv_layer sends 16-bit
-    storage to conv3d_mfma16.hip unless MVS_MFMA16=0, and past that gate every `dtype`-taking launcher it calls goes
-    through MVS_DISPATCH_DTYPE, which instantiates all three storage types."""
+    its F32 probe case does not cover them.  Reachability is read from the dispatch: plan_layer (launch_plan.h) sends
+    16-bit storage to conv3d_mfma16.hip's forms unless MVS_MFMA16=0, and every `dtype`-taking launcher that
+    launch_conv_layer calls for a form planned past that gate goes through MVS_DISPATCH_DTYPE, which instantiates all three storage types."""
     inst, _ = parse_conv_sources()
     templated = {k for k in inst if re.search(r"\bDT\b", k)}
     assert templated and templated == set(INSTANTIATIONS16), sorted(templated ^ set(INSTANTIATIONS16))
     for key, case in INSTANTIATIONS16.items():
         assert CASES[case]["storages"] == ("f16", "bf16"), (key, case)
-    # the gate, and what lies behind it
+    # the gate (csrc/launch_plan.h plans the form, launch_conv_layer switches over it), and what lies behind it
+    header = _read("launch_plan.h")
+    planner = _function_body(header, "inline Plan plan_layer(")
+    gate = "if (opt.mfma16 && (dtype == MVS_F16 || dtype == MVS_BF16) && layer <= 9) return plan_layer16("
+    assert gate in planner
+    behind = planner[planner.index(gate) + len(gate):]
+    assert "return plan_conv1(" in behind
+    all_forms = set(re.findall(r"^\s+(k\w+)(?: = 0)?,", re.search(r"enum Form \{(.*?)\n\};", header, re.S).group(1), re.M))
+    forms = set(re.findall(r"\bk[A-Z]\w+", behind + _function_body(header, "inline Plan plan_conv1("))) & all_forms
+    f32_forms = {"kConv0WinoSplit", "kConvGSplit", "kDeconvGSplit"}      # each behind a dtype == MVS_F32 test
+    assert f32_forms < forms
+    call = behind[:behind.index("kConv0WinoSplit")]
+    assert "dtype == MVS_F32" in call[call.rindex("if ("):]
+    split_block = behind[behind.index("if (opt.split_layers && dtype == MVS_F32) {"):]
+    split_block = split_block[:split_block.index("\n    }\n")]
+    assert all(behind.count(f) == split_block.count(f) > 0 for f in ("kConvGSplit", "kDeconvGSplit"))
     body = _function_body(_read("conv3d_direct.hip"), "int launch_conv_layer(")
-    gate = "if (opt.mfma16 && (dtype == MVS_F16 || dtype == MVS_BF16) && layer <= 9)"
-    assert gate in body
-    behind = body[body.index(gate):]
-    called = set(re.findall(r"return (launch_\w+)\(", behind)) - {"launch_layer_mfma16"}
-    f32_only = {"launch_layer_split", "launch_conv0_wino43_split"}      # both behind a dtype == MVS_F32 test
-    for name in f32_only:
-        call = behind[:behind.index("return " + name)]
-        assert "dtype == MVS_F32" in call[call.rindex("if ("):], name
+    launcher_of = {}
+    for labels, arm in re.findall(r"((?:case plan::k\w+:\s*)+)(.*?)(?=case plan::|default:)", body, re.S):
+        for form in re.findall(r"plan::(k\w+)", labels):
+            launcher_of[form] = set(re.findall(r"return (launch_\w+)\(", arm))
+    assert forms - {"kProbLds"} <= set(launcher_of) and set(launcher_of) | {"kProbLds", "kNone"} <= all_forms
+    called = set().union(*(launcher_of[f] for f in forms - {"kProbLds"}))
+    f32_only = {"launch_layer_split", "launch_conv0_wino43_split"}
+    assert set().union(*(launcher_of[f] for f in f32_forms)) == f32_only
+    assert len(called - f32_only) >= 7
     macro = _read("storage.h")
     assert all(f"case {t}: {{ constexpr int DT = {t};" in macro for t in ("MVS_F32", "MVS_F16", "MVS_BF16"))
     srcs = {n: _read(n) for n in CONV_SOURCES}

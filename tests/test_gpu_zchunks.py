@@ -1,6 +1,6 @@
 """The z-chunk and depth-slab splits the launchers pick at run time, at the cheapest shape of every case category.
 
-tests/zchunks.py restates each launcher's search; here the CU count of the device under test chooses, per launcher,
+tests/zchunks.py asks the library's planner for each launcher's split; here the CU count of the device under test chooses, per launcher,
 the cheapest volume (D, h, w) of every category its kernel treats differently (one chunk, ragged last chunks of 0, 1
 or 2 planes mod 3 after chunks of 0, 1 or 2 mod 3, for conv11_prob odd chunks and a one-plane last chunk), and each
 case runs against the CPU oracle.  The split of every case is in its test id: <launcher>-<form>-<categories>-

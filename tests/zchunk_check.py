@@ -8,6 +8,7 @@ Every case is {"id", "op": "conv11_prob" | "layer" | "warp", "storage", "layer",
 results file maps each id to {"ok", "msg"} and is rewritten after every case, so the cases that ran before a crash
 keep their verdicts.  "warp" cases also save the raw volume to `save` for the parent's bit-equality checks.
 """
+import functools
 import json
 import os
 import sys
@@ -20,6 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
+import gpu_child  # noqa: E402
 from conftest import assert_conf_close, rel_l1  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 from scene_3dreconstruction_mvsnet_amd import _lib, synthetic  # noqa: E402
@@ -29,7 +31,11 @@ LAYER_ATOL = 2e-4   # x max|want|: fp32 layers, as test_gpu_fullsize / test_gpu_
 EPS = {"f32": 0.0, "f16": 2.0 ** -10, "bf16": 2.0 ** -7}
 WARP_N, WARP_H, WARP_W = 5, 16, 24   # 384 pixels: 12 pixel blocks
 SD = synthetic.random_costreg_state(seed=31)
-BLOB = _lib.pack_weights(SD).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def blob():
+    return _lib.pack_weights(SD).to(DEV)
 
 
 def cu(a):
@@ -53,7 +59,7 @@ def run_layer(layer, storage, D, h, w, rng):
     x = q(rng.standard_normal((ci, D >> lvl, h >> lvl, w >> lvl)).astype(np.float32))
     key, bn = _lib.CONV_WEIGHT_KEYS[layer], _lib.BN_PREFIXES[layer]
     stride = 2 if layer in (1, 3) else 1
-    got = _lib.from_c8(_lib.conv_layer(layer, _lib.to_c8(cu(x)).to(_lib.TORCH_DTYPES[code]), None, BLOB,
+    got = _lib.from_c8(_lib.conv_layer(layer, _lib.to_c8(cu(x)).to(_lib.TORCH_DTYPES[code]), None, blob(),
                                        dtype=code).float()).cpu().numpy()
     if storage == "f32":
         check_fp32(got, orc.conv3d(x, SD[key], bn=orc._bn(SD, bn), stride=stride), f"layer {layer}")
@@ -73,7 +79,7 @@ def run_conv11_prob(storage, D, h, w, rng):
     q = lambda t: orc.round_storage(t, storage)  # noqa: E731
     x = q(np.abs(rng.standard_normal((16, D // 2, h // 2, w // 2))).astype(np.float32))
     skip = q(np.abs(rng.standard_normal((8, D, h, w))).astype(np.float32))
-    got = _lib.conv11_prob(_lib.to_c8(cu(x)).to(tdt), _lib.to_c8(cu(skip)).to(tdt), BLOB, dtype=code).cpu().numpy()
+    got = _lib.conv11_prob(_lib.to_c8(cu(x)).to(tdt), _lib.to_c8(cu(skip)).to(tdt), blob(), dtype=code).cpu().numpy()
     assert np.isfinite(got).all()
     if storage == "f32":
         d11 = skip + orc.deconv3d(x, SD["conv11.0.weight"], bn=orc._bn(SD, "conv11.1"))
@@ -135,6 +141,8 @@ def main():
                 run_warp(case["storage"], D, case["save"])
             results[case["id"]] = {"ok": True, "msg": ""}
         except (AssertionError, RuntimeError) as e:   # RuntimeError: a status the library returned
+            if any(t in str(e) for t in gpu_child.HIP_ERROR_TEXTS):
+                raise   # a HIP error is no verdict: the child ends with it on stderr, which gpu_child's stop rule reads
             results[case["id"]] = {"ok": False, "msg": "".join(traceback.format_exception_only(type(e), e))[-4000:]}
         with open(out_path, "w") as f:
             json.dump(results, f)

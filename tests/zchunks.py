@@ -1,21 +1,35 @@
-"""The launch geometry the z-marching launchers and the tap-cache warp pick at run time, restated in Python.
+"""The launch plans of the depth path, asked of the library, and the test shapes chosen from them.
 
-Five launchers choose how a volume is cut along z from its shape and, for four of them, from the device's CU count.
-Each function below restates one of those searches line for line (the source lines are quoted in its docstring) and
-returns a `Split`: the chunk (or slab) size, the chunk count, the last chunk's size and the grid the kernel launches.
-`cheapest_cases` then picks, for a launcher and a CU count, the cheapest volume (D, h, w) of every case category the
-kernels treat differently: one chunk, the ragged last chunks after a loop unrolled by 3, odd chunks, a one-plane last
-chunk.  tests/test_zchunks_host.py pins the restatements on known values; tests/test_gpu_zchunks.py runs the chosen
-shapes on the GPU.
+csrc/launch_plan.h plans every launch: the kernel form of a layer, of the fused tail and of the warp, its tile, and how
+the z-marching launchers and the tap-cache warp cut the volume.  `plan` asks it through the library's test hook
+(mvs_test_launch_plan: no GPU, no environment); the form names and the switches with their defaults are read from the
+header.  The launcher functions below ask for one launcher's split under the switch that forces its z-marching form, as
+the GPU tests run it, and return a `Split`: the chunk (or slab) size, the chunk count, the last chunk's size and the
+grid.  `cheapest_cases` then picks, for a launcher and a CU count, the cheapest volume (D, h, w) of every case category
+the kernels treat differently: one chunk, the ragged last chunks after a loop unrolled by 3, odd chunks, a one-plane
+last chunk.  tests/test_zchunks_host.py pins the plans on known values; tests/test_gpu_zchunks.py runs the chosen shapes
+on the GPU.
 
 A shape is always the full-resolution cost volume (D, h, w) of the network; each launcher sees its own layer's input:
 conv0 (D, h, w), conv1 (D, h, w) -> (D/2, h/2, w/2), conv2 at D/2, conv3 (D/2) -> (D/4), conv11_prob's input d9 at
 (D/2, h/2, w/2).
 """
+import ctypes
 import functools
+import os
+import re
+import sys
 from typing import NamedTuple
 
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:      # a test file run as a child script has only tests/ on its path
+    sys.path.insert(0, REPO)
+
+from scene_3dreconstruction_mvsnet_amd import _lib  # noqa: E402
+
 MAX_VOXELS = 1 << 21    # largest D * h * w a test case may use (about 2 M voxels)
+HEADER = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc", "launch_plan.h")
+LAYER, TAIL, WARP = 0, 1, 2     # kQueryLayer, kQueryTail, kQueryWarp
 
 
 class Split(NamedTuple):
@@ -25,68 +39,78 @@ class Split(NamedTuple):
     grid: int   # blocks launched
 
 
-def _cdiv(a, b):
-    return (a + b - 1) // b
-
-
-def _best_split(dz, nb_per_chunk, slots, nz_max, prologue):
-    """The search every z-marching launcher shares: the chunk count nz in 1..nz_max with the best fill of the last
-    round of `slots` resident blocks, discounted by a per-chunk prologue of `prologue` steps; the first best wins."""
-    best, best_eff = 1, 0.0
-    for nz in range(1, nz_max + 1):
-        zc = _cdiv(dz, nz)
-        nzc = _cdiv(dz, zc)
-        nb = nb_per_chunk * nzc
-        eff = nb / (_cdiv(nb, slots) * slots) * zc / (zc + prologue)
-        if eff > best_eff + 1e-9:
-            best_eff, best = eff, nz
-    return best
-
-
-def _split(dz, zc, ncol):
-    n = _cdiv(dz, zc)
-    return Split(zc, n, dz - (n - 1) * zc, ncol * n)
+class Plan(NamedTuple):
+    form: str               # launch_plan.h's Form without its "k": "ConvZ16", "TailSplit", "WarpTc", ...
+    tile: tuple             # (bz, by, bx) M-tiles per block of the 16-bit tile kernels, else (0, 0, 0)
+    split: Split            # all zero where the form does not cut along z
+    depth_fastest: int      # the warps' block order
+    cuts_z: bool
 
 
 @functools.lru_cache(maxsize=None)
-def _conv11_prob_z(Di, ntile, cus):
-    best = _best_split(Di, ntile, 2 * cus, (Di + 3) // 4, 1.5)
-    ZC = min(max(_cdiv(Di, best), 4), Di)
-    return _split(Di, ZC, ntile)
+def _header():
+    """(form names in enum order, switch names in Options' order, their defaults) from launch_plan.h."""
+    with open(HEADER) as f:
+        src = f.read()
+    forms = re.findall(r"^\s+k(\w+)(?: = 0)?,", re.search(r"enum Form \{(.*?)\n\};", src, re.S).group(1), re.M)
+    names = re.findall(r"^\s+(?:bool|int) (\w+);", re.search(r"struct Options \{(.*?)\n\};", src, re.S).group(1), re.M)
+    values = re.search(r"return Options\{(.*?)\};", src).group(1).split(",")
+    defaults = [{"true": 1, "false": 0}.get(v.strip(), v) for v in values]
+    defaults = [int(v) for v in defaults]
+    assert len(names) == len(defaults) == 20 and forms[0] == "None", (forms, names, defaults)
+    return forms, names, defaults
+
+
+@functools.lru_cache(maxsize=None)
+def _hook():
+    fn = ctypes.CDLL(_lib.LIB_PATH).mvs_test_launch_plan
+    fn.restype = ctypes.c_int
+    return fn, (ctypes.c_int * 29)(), (ctypes.c_longlong * 10)()
+
+
+def _ask(query):
+    fn, q, a = _hook()
+    q[:] = query
+    st = fn(q, a)
+    assert st == 0, (st, query)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def _switch_values(switches):
+    """Options' 20 values: the defaults but for `switches`, a tuple of (field name, value)."""
+    _, names, defaults = _header()
+    assert {n for n, _ in switches} <= set(names), switches
+    return [int(dict(switches).get(n, d)) for n, d in zip(names, defaults)]
+
+
+def plan(which, D, h, w, cus, *, layer=0, N=1, storage="f32", fes=4, **switches):
+    """The plan of one launch on an input of D x h x w (the launch's own input dims), at `cus` CUs, under the default
+    switches but for `switches` (Options' field names)."""
+    a = _ask([which, layer, N, D, h, w, _lib.DTYPE_CODES[storage], fes, cus] + _switch_values(tuple(sorted(switches.items()))))
+    return Plan(_header()[0][a[0]], (a[1], a[2], a[3]), Split(a[4], a[5], a[6], a[7]), a[8], bool(a[9]))
+
+
+def switch_names():
+    return _header()[1]
+
+
+# ---------------------------------------------------------------- one launcher's split, its z-marching form forced
+def _forced(form, which, layer, storage, D, h, w, cus, *switch):
+    """The split of a launch if its plan has `form` (the launcher's z-marching form), else None."""
+    a = _ask([which, layer, 1, D, h, w, _lib.DTYPE_CODES[storage], 4, cus] + _switch_values(switch))
+    return Split(a[4], a[5], a[6], a[7]) if _header()[0][a[0]] == form else None
 
 
 def conv11_prob(D, h, w, cus):
-    """launch_conv11_prob (csrc/conv11_prob.hip), on d9 = (D/2, h/2, w/2); ZC counts INPUT planes:
-
-        const int nbx = (Wo - 2 + PX - 1) / PX > 0 ? (Wo - 2 + PX - 1) / PX : 1;      // PX = 30, PY = 14
-        const int ntile = nbx * nby, slots = 2 * cus;
-        for (int nz = 1; nz <= (Di + 3) / 4; ++nz) { ... zc / (zc + 1.5) ... }
-        int ZC = (Di + best - 1) / best;  if (ZC < 4) ZC = 4;  if (ZC > Di) ZC = Di;
-        const dim3 grid(nbx * nby * nzc);
-    """
-    Di, Hi, Wi = D // 2, h // 2, w // 2
-    nbx = max((2 * Wi - 2 + 29) // 30, 1)
-    nby = max((2 * Hi - 2 + 13) // 14, 1)
-    return _conv11_prob_z(Di, nbx * nby, cus)
-
-
-@functools.lru_cache(maxsize=None)
-def _conv1z_z(Do, ncol, cus):
-    best = _best_split(Do, ncol, cus, (Do + 3) // 4, 2.5)
-    return _split(Do, _cdiv(Do, best), ncol)
+    """launch_conv11_prob on d9 = (D/2, h/2, w/2); the chunks count INPUT planes."""
+    return _forced("TailSplit", TAIL, 9, "f32", D // 2, h // 2, w // 2, cus)
 
 
 def conv1z(D, h, w, cus):
-    """run_conv1z (csrc/conv3d_mfma.hip), fp32 conv1 on (D, h, w); ZC counts OUTPUT planes, and `cus` is
-    persistent_blocks_per_cu_scale(): MVS_PERSIST_CUS if set, else device_cus():
-
-        const int nbx = (Wo + TXO - 1) / TXO, nby = (Ho + TYO - 1) / TYO, ncol = nbx * nby;   // TXO = 16, TYO = 8
-        for (int nz = 1; nz <= (Do + 3) / 4; ++nz) { ... zc / (zc + 2.5) ... }
-        const int ZC = (Do + best - 1) / best, nzc = (Do + ZC - 1) / ZC;
-        conv1z_mfma_kernel<<<ncol * nzc, THREADS, 0, s>>>
-    """
-    Do, Ho, Wo = (D - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    return _conv1z_z(Do, _cdiv(Wo, 16) * _cdiv(Ho, 8), cus)
+    """fp32 conv1 on (D, h, w) under MVS_CONV1Z=1; the chunks count OUTPUT planes, and `cus` stands for MVS_PERSIST_CUS
+    where the test sets it."""
+    return _forced("Conv1Z", LAYER, 1, "f32", D, h, w, cus, ("conv1z", 1))
 
 
 def convz16_dims(layer, D, h, w):
@@ -99,63 +123,22 @@ def convz16_dims(layer, D, h, w):
 
 
 def convz16(layer, D, h, w, cus):
-    """run_convz16 (csrc/conv3d_mfma16.hip), 16-bit conv1 / conv2 / conv3 (MVS_CONVZ16=1); ZC counts OUTPUT planes and
-    `cus` is device_cus() (try_convz16); None where try_convz16 leaves the layer to the tile kernel:
-
-        static constexpr int TY = 8, TX = (S == 1) ? 32 : 16;      // ConvZ16
-        const int nbx = (Wo + G::TX - 1) / G::TX, nby = (Ho + G::TY - 1) / G::TY, ncol = nbx * nby;
-        for (int nz = 1; nz <= (Do + 3) / 4; ++nz) { ... zc / (zc + 2.5) ... }
-        const int ZC = (Do + best - 1) / best, nzc = (Do + ZC - 1) / ZC;
-        convz16_mfma_kernel<DT, CIN, COUT, S><<<ncol * nzc, G::THREADS, 0, s>>>
-    """
-    Di, Hi, Wi, S = convz16_dims(layer, D, h, w)
-    Do, Ho, Wo = (Di - 1) // S + 1, (Hi - 1) // S + 1, (Wi - 1) // S + 1
-    if Do < 4:   # try_convz16: `|| Do < 4) return MVS_OK;` -- the tile kernel runs instead
-        return None
-    tx = 32 if S == 1 else 16
-    return _conv1z_z(Do, _cdiv(Wo, tx) * _cdiv(Ho, 8), cus)   # the same search as run_conv1z
-
-
-C0Z_TY = 8   # c0z::TY (C0Z_TY in conv3d_mfma16.hip): rows and waves per block
-
-
-@functools.lru_cache(maxsize=None)
-def _conv0z16_z(Di, ncol, cus):
-    best = _best_split(Di, ncol, cus * (8 // C0Z_TY), Di // 8, 2.0)
-    return _split(Di, _cdiv(Di, best), ncol)
+    """16-bit conv1 / conv2 / conv3 under MVS_CONVZ16=1; the chunks count OUTPUT planes; None where the tile kernel runs
+    instead (fewer than 4 output planes)."""
+    Di, Hi, Wi, _ = convz16_dims(layer, D, h, w)
+    return _forced("ConvZ16", LAYER, layer, "bf16", Di, Hi, Wi, cus, ("convz16", 1))
 
 
 def conv0z16(D, h, w, cus):
-    """The conv0z16 branch of launch_layer16_dt (csrc/conv3d_mfma16.hip), 16-bit conv0 (MVS_CONV0Z16=1); None where
-    the branch is not taken:
-
-        const int ncol = ((Wi + c0z::TX - 1) / c0z::TX) * ((Hi + c0z::TY - 1) / c0z::TY);     // TX = 32, TY = 8
-        for (int nz = 1; nz <= Di / 8; ++nz) { ... slots = (long)cus * (8 / c0z::TY); ... zc / (zc + 2.0) ... }
-        const int ZC = (Di + best - 1) / best, nzc = (Di + ZC - 1) / ZC;
-        conv0z16_mfma_kernel<DT><<<ncol * nzc, c0z::THREADS, 0, s>>>
-    """
-    if D < 8:   # `zmarch != 0 && Di >= 8 && ...`: the tile kernel runs instead
-        return None
-    return _conv0z16_z(D, _cdiv(w, 32) * _cdiv(h, C0Z_TY), cus)
-
-
-TC_SLABS = (40, 44, 36, 32, 28, 24)
-TC_PIX = 32   # pixels per block: 256 threads / 8 lanes per pixel (CPT = 4)
+    """16-bit conv0 under MVS_CONV0Z16=1; None where the tile kernel runs instead (D < 8)."""
+    return _forced("Conv0Z16", LAYER, 0, "bf16", D, h, w, cus, ("conv0z16", 1))
 
 
 def tc_slab(D, h, w):
-    """launch_tc2_dt (csrc/warp_variance_tc.hip): the depth slab and the grid (npb pixel blocks x nsl slabs, in
-    either block order); no CU count enters:
-
-        for (const int cand : {40, 44, 36, 32, 28, 24}) { slab = cand; if (((D + cand - 1) / cand) % 8 != 0) break; }
-        const unsigned npb = (h * w + pix - 1) / pix, nsl = (D + slab - 1) / slab;
-    """
-    slab = TC_SLABS[0]
-    for cand in TC_SLABS:
-        slab = cand
-        if _cdiv(D, cand) % 8 != 0:
-            break
-    return _split(D, slab, _cdiv(h * w, TC_PIX))
+    """The tap-cache warp's depth slab and grid (pixel blocks x slabs, in either block order); no CU count enters."""
+    p = plan(WARP, D, h, w, 256, N=5)
+    assert p.form == "WarpTc", p
+    return p.split
 
 
 # ---------------------------------------------------------------- the launchers and their case categories
