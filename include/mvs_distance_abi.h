@@ -8,7 +8,9 @@
  * the ground truth as the reference it gives the accuracy, the other way round the completeness; precision, recall and
  * the F-score at a threshold follow from the counts.  The reference project leaves this to DTU's MATLAB code; the
  * definition below is that code's nearest-neighbour distance alone.  DTU's observability mask, its ground-plane filter
- * and its point reduction (reducePts) are not part of it, and nothing here was compared against the MATLAB code.
+ * and its point reduction (reducePts) are not part of it: they are mvs_cloud_select and mvs_cloud_reduce
+ * (mvs_reduce_abi.h), which turn the filtered-out queries into the NaN rows this entry point leaves uncounted;
+ * nothing here was compared against the MATLAB code or real DTU files.
  *
  * Inputs:
  *     ref_xyz       DEVICE, [P][3], float (MVS_CLOUD_F32) or double (MVS_CLOUD_F64): the cloud that is searched

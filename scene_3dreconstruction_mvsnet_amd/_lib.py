@@ -47,15 +47,16 @@ _lib = None
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _sz = ctypes.c_size_t
-_f, _d, _ll = ctypes.c_float, ctypes.c_double, ctypes.c_longlong
+_f, _d, _ll, _ull = ctypes.c_float, ctypes.c_double, ctypes.c_longlong, ctypes.c_ulonglong
 _szp = ctypes.POINTER(_sz)      # size_t* bytes
 _vpp = ctypes.POINTER(_vp)      # const float* const*
 
 # Every entry point, declared once on this side: header -> {name: argument types}, in the headers' order.  Any other
 # pointer is a c_void_p (device and host addresses travel as integers).  load() applies the table; SYMBOLS and
-# FUSE_SYMBOLS, CLOUD_SYMBOLS, NORMALS_SYMBOLS, OUTLIERS_SYMBOLS and DISTANCE_SYMBOLS are its keys; tests/test_host_logic.py,
-# tests/test_scan_fusion_host.py, tests/test_cloud_downsample_host.py, tests/test_cloud_normals_host.py,
-# tests/test_cloud_outliers_host.py and tests/test_cloud_distance_host.py hold every argument list to its prototype.
+# FUSE_SYMBOLS, CLOUD_SYMBOLS, NORMALS_SYMBOLS, OUTLIERS_SYMBOLS, DISTANCE_SYMBOLS and REDUCE_SYMBOLS are its keys;
+# tests/test_host_logic.py, tests/test_scan_fusion_host.py, tests/test_cloud_downsample_host.py,
+# tests/test_cloud_normals_host.py, tests/test_cloud_outliers_host.py, tests/test_cloud_distance_host.py and
+# tests/test_cloud_reduce_host.py hold every argument list to its prototype.
 # Everything returns int except mvs_last_error_string.
 _ABI = {
     "mvs_abi.h": {
@@ -122,6 +123,11 @@ _ABI = {
         "mvs_query_distance_workspace": [_ll, _ll, _vp, _vp, _d, _szp],
         "mvs_cloud_distance": [_vp, _i, _ll, _vp, _i, _ll, _vp, _vp, _d, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     },
+    "mvs_reduce_abi.h": {
+        "mvs_query_reduce_workspace": [_ll, _vp, _vp, _d, _szp],
+        "mvs_cloud_reduce": [_vp, _i, _ll, _vp, _vp, _d, _d, _ull, _i, _vp, _vp, _vp, _sz, _vp],
+        "mvs_cloud_select": [_vp, _i, _ll, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp],
+    },
 }
 SYMBOLS = tuple(_ABI["mvs_abi.h"])
 FUSE_SYMBOLS = tuple(_ABI["mvs_fuse_abi.h"])
@@ -129,6 +135,7 @@ CLOUD_SYMBOLS = tuple(_ABI["mvs_cloud_abi.h"])
 NORMALS_SYMBOLS = tuple(_ABI["mvs_normals_abi.h"])
 OUTLIERS_SYMBOLS = tuple(_ABI["mvs_outliers_abi.h"])
 DISTANCE_SYMBOLS = tuple(_ABI["mvs_distance_abi.h"])
+REDUCE_SYMBOLS = tuple(_ABI["mvs_reduce_abi.h"])
 
 
 class MvsError(RuntimeError):
@@ -151,7 +158,8 @@ def load():
                 "g.build()'` (or make -C scene_3dreconstruction_mvsnet_amd/csrc). "
                 "There is no CPU/PyTorch fallback for the MVSNet depth path.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name in SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS + OUTLIERS_SYMBOLS + DISTANCE_SYMBOLS:
+        for name in (SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS + OUTLIERS_SYMBOLS + DISTANCE_SYMBOLS
+                     + REDUCE_SYMBOLS):
             if not hasattr(lib, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}")
         for prototypes in _ABI.values():
@@ -992,6 +1000,88 @@ def cloud_distance(ref, query, box_min, box_max, cell, max_dist, thresholds, ind
                                         dist.data_ptr(), None if idx is None else idx.data_ptr(), counts.data_ptr(),
                                         stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
     return dist, idx, counts, stats
+
+
+# ---- DTU's point reduction, observability mask and plane (include/mvs_reduce_abi.h, csrc/cloud_reduce.hip) ----
+REDUCE_ROUNDS_MAX = 256     # MVS_REDUCE_ROUNDS_MAX
+
+
+def query_reduce_workspace(P, box_min, box_max, cell) -> int:
+    return _box_query("mvs_query_reduce_workspace", "query_reduce_workspace", P, box_min=box_min, box_max=box_max, edge=cell)
+
+
+def cloud_reduce(xyz, box_min, box_max, cell, min_dist, seed=0, max_rounds=64, out=None):
+    """Thin the points of the cloud inside the box so that no two kept points lie within min_dist of each other: the
+    greedy pass of DTU's reducePts in the order of a hash of (seed, index), as include/mvs_reduce_abi.h defines it, on the
+    device.
+
+    xyz float32 or float64 [P,3]; box_min, box_max: 3 host numbers each; cell: the search grid's cell edge (it changes the
+    time, never the result); min_dist finite and >= 0; seed an integer modulo 2^64; max_rounds in [1, 256].  Returns
+    (keep bool [P], counts int64 [4]: members, kept, undecided after max_rounds, rounds), both on the device; the mask is
+    the greedy result iff undecided == 0.  `out` = (keep, counts) receives the results.  Enqueued on the current stream;
+    nothing synchronises."""
+    xyz = _cloud_xyz(xyz, "cloud_reduce")
+    dev = xyz.device
+    P, dist, rounds = xyz.shape[0], float(min_dist), int(max_rounds)
+    if not (0.0 <= dist < float("inf")):
+        raise RuntimeError(f"cloud_reduce: min_dist = {dist} (need a finite min_dist >= 0)")
+    if not 1 <= rounds <= REDUCE_ROUNDS_MAX:
+        raise RuntimeError(f"cloud_reduce: max_rounds = {rounds} (need 1 <= max_rounds <= {REDUCE_ROUNDS_MAX})")
+    lo, hi = _box_arg(box_min, box_max, "cloud_reduce")
+    nbytes = _box_query("mvs_query_reduce_workspace", "cloud_reduce", P, box_min=lo, box_max=hi, edge=cell)
+    with torch.cuda.device(dev):
+        keep, counts = _outputs("cloud_reduce", dev, [("keep", (P,), torch.bool, True),      # the library writes bytes 0 and 1
+                                                      ("counts", (4,), torch.int64, True)], out)
+        if P == 0:          # an empty tensor has no address to hand over: the four zero counts of the header's P == 0
+            counts.zero_()
+            return keep, counts
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(load().mvs_cloud_reduce(xyz.data_ptr(), _xyz_code(xyz), P, lo, hi, float(cell), dist,
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, rounds, keep.data_ptr(), counts.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), _stream(dev)))
+    return keep, counts
+
+
+def cloud_select(xyz, mask=None, origin=None, res=1.0, plane=None, out=None):
+    """DTU's two per-point filters (include/mvs_reduce_abi.h), on the device: is the voxel of the point -- the one whose
+    centre origin + g * res is nearest, halves away from zero -- set in `mask` (uint8 or bool [n0,n1,n2] on xyz's device,
+    or None: no test), and is ((plane[0] x + plane[1] y) + plane[2] z) + plane[3] > 0 (4 host numbers, or None: no test).
+
+    Returns (keep bool [P]: the conjunction of the tests asked for, False for a non-finite point, counts int64 [3]: finite
+    points, observed ones, kept ones), both on the device.  `out` = (keep, counts).  Enqueued on the current stream;
+    nothing synchronises."""
+    xyz = _cloud_xyz(xyz, "cloud_select")
+    dev, P = xyz.device, xyz.shape[0]
+    n = org = pl = None
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.device != dev or mask.dim() != 3 \
+                or mask.dtype not in (torch.uint8, torch.bool):
+            raise RuntimeError("cloud_select: mask must be a uint8 or bool [n0,n1,n2] tensor on xyz's device")
+        if origin is None or len(origin) != 3:
+            raise RuntimeError("cloud_select: a mask needs origin, 3 host numbers")
+        mask = mask.contiguous()
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)      # one byte each, 0 / 1
+        if mask.numel() == 0:
+            raise RuntimeError(f"cloud_select: the mask is empty: {tuple(mask.shape)}")
+        n = (_i * 3)(*mask.shape)
+        org = (_d * 3)(*(float(v) for v in origin))
+    if plane is not None:
+        if len(plane) != 4:
+            raise RuntimeError(f"cloud_select: plane must hold 4 numbers, got {len(plane)}")
+        pl = (_d * 4)(*(float(v) for v in plane))
+    with torch.cuda.device(dev):
+        keep, counts = _outputs("cloud_select", dev, [("keep", (P,), torch.bool, True),      # the library writes bytes 0 and 1
+                                                      ("counts", (3,), torch.int64, True)], out)
+        if P == 0:          # an empty tensor has no address to hand over: the three zero counts of the header's P == 0
+            counts.zero_()
+            return keep, counts
+        check(load().mvs_cloud_select(xyz.data_ptr(), _xyz_code(xyz), P, None if mask is None else mask.data_ptr(),
+                                      None if n is None else ctypes.addressof(n),
+                                      None if org is None else ctypes.addressof(org), float(res),
+                                      None if pl is None else ctypes.addressof(pl), keep.data_ptr(), counts.data_ptr(),
+                                      _stream(dev)))
+    return keep, counts
 
 
 # ---- FeatureNet (reference models/mvsnet.py:10-30) -------------------------------------------

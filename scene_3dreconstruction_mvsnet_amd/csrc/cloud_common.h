@@ -1,5 +1,5 @@
 // cloud_common.h -- what the cloud path's translation units share: fuse_points.hip, cloud_downsample.hip and, through
-// cloud_knn.h, cloud_normals.hip, cloud_outliers.hip and cloud_distance.hip.
+// cloud_knn.h, cloud_normals.hip, cloud_outliers.hip, cloud_distance.hip and cloud_reduce.hip.
 //
 // Device side, all inlined into the kernels that call them (the kernels keep their names and their launch order):
 //   tile_scan_exclusive   the single-block exclusive scan with a running carry over tiles[0 .. n_tiles)

@@ -1,6 +1,7 @@
 // cloud_knn.h -- the exact k-nearest-neighbour search among the points of a cloud inside a box, shared by
 // cloud_normals.hip (mvs_cloud_normals), cloud_outliers.hip (mvs_cloud_outliers) and cloud_distance.hip
-// (mvs_cloud_distance): the cell grid and the ring search, as include/mvs_normals_abi.h describes them.  Each user adds its
+// (mvs_cloud_distance): the cell grid and the ring search, as include/mvs_normals_abi.h describes them.  cloud_reduce.hip
+// (mvs_cloud_reduce) uses the grid alone and walks the cells within a fixed reach itself.  Each user adds its
 // own classify kernel (what a non-member gets) around knn_classify and its own search kernel (what is done with the
 // neighbours) around knn_search -- the knn nearest members of a member -- or knn_nearest -- the one nearest member of a
 // point anywhere in space, which is no member of the grid (include/mvs_distance_abi.h).

@@ -2,11 +2,14 @@
 precision / recall / F-score at thresholds (fusion.evaluate_cloud, include/mvs_distance_abi.h).
 
     python -m scene_3dreconstruction_mvsnet_amd.eval_cloud --pred A.ply --gt B.ply [--max_dist 20 --thresholds 1 2 5
-        --box x0 y0 z0 x1 y1 z1 --cell C --json OUT]
+        --box x0 y0 z0 x1 y1 z1 --cell C --json OUT
+        --reduce_dist 0.2 [--reduce_seed 0] [--reduce_gt] --obs_mask FILE --plane FILE]
 
 Both files are read with fusion.read_ply (binary little-endian or ascii vertices).  The dict is printed as one JSON line
-and, with --json, written to OUT.  This is the definition of the distances alone: DTU's observability mask, ground-plane
-filter and point reduction are not applied (see fusion.evaluate_cloud); units are those of the files.
+and, with --json, written to OUT.  Without the last line of options this is the definition of the distances alone; with
+them DTU's point reduction, observability mask (ObsMask/ObsMaskN_10.mat or an .npz) and ground-plane filter
+(ObsMask/PlaneN.mat or an .npz) are applied in DTU's order (see fusion.evaluate_cloud, which also says what is still
+not DTU's); units are those of the files.
 reconstruct.py takes the same options with --gt_ply.
 """
 from __future__ import annotations
@@ -16,7 +19,7 @@ import json
 
 
 def add_score_arguments(p):
-    """--max_dist, --thresholds, --box, --cell and --json, shared with reconstruct.py."""
+    """--max_dist, --thresholds, --box, --cell, --json and the DTU options, shared with reconstruct.py."""
     p.add_argument("--max_dist", type=float, default=20.0,
                    help="a point farther than this from the other cloud enters no mean and lies below no threshold")
     p.add_argument("--thresholds", type=float, nargs="*", default=(1.0, 2.0, 5.0), metavar="T",
@@ -25,9 +28,30 @@ def add_score_arguments(p):
                    help="only points inside this box are searched, in either direction (default: each cloud's bounding box)")
     p.add_argument("--cell", type=float, default=None, help="cell edge of the search grid (it changes the time, never the result)")
     p.add_argument("--json", default=None, metavar="OUT", help="also write the result to this file")
+    p.add_argument("--reduce_dist", type=float, default=None, metavar="D",
+                   help="DTU's point reduction of the reconstruction first: no two kept points within D (DTU: 0.2)")
+    p.add_argument("--reduce_seed", type=int, default=0, help="seed of the reduction's order (needs --reduce_dist)")
+    p.add_argument("--reduce_gt", action="store_true", help="also reduce the ground truth (needs --reduce_dist)")
+    p.add_argument("--obs_mask", default=None, metavar="FILE",
+                   help="DTU's observability mask (.mat or .npz with ObsMask, BB, Res): accuracy over the observed points")
+    p.add_argument("--plane", default=None, metavar="FILE",
+                   help="DTU's ground plane (.mat or .npz with P): completeness over the ground truth above it")
 
 
-def score(pred_xyz, gt_xyz, args, device=None):
+def dtu_options(args, scan=None):
+    """The reduce, obs_mask and plane keywords of fusion.evaluate_cloud from the options of add_score_arguments; `{scan}`
+    in the two file names is replaced by `scan` where one is given."""
+    from . import fusion
+    name = lambda path: path if scan is None else path.replace("{scan}", scan)      # noqa: E731
+    if args.reduce_dist is None and (args.reduce_gt or args.reduce_seed != 0):
+        raise SystemExit("--reduce_seed and --reduce_gt need --reduce_dist")
+    return dict(reduce=None if args.reduce_dist is None else dict(min_dist=args.reduce_dist, seed=args.reduce_seed,
+                                                                  gt=args.reduce_gt),
+                obs_mask=None if args.obs_mask is None else fusion.read_obs_mask(name(args.obs_mask)),
+                plane=None if args.plane is None else fusion.read_plane(name(args.plane)))
+
+
+def score(pred_xyz, gt_xyz, args, device=None, scan=None):
     """fusion.evaluate_cloud of two host arrays [.,3] with the options of add_score_arguments."""
     import numpy as np
     import torch
@@ -38,7 +62,8 @@ def score(pred_xyz, gt_xyz, args, device=None):
     device = device or torch.device("cuda", torch.cuda.current_device())
     box = None if args.box is None else (args.box[:3], args.box[3:])
     pred, gt = (torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (pred_xyz, gt_xyz))
-    return fusion.evaluate_cloud(pred, gt, max_dist=args.max_dist, thresholds=tuple(args.thresholds), box=box, cell=args.cell)
+    return fusion.evaluate_cloud(pred, gt, max_dist=args.max_dist, thresholds=tuple(args.thresholds), box=box, cell=args.cell,
+                                 **dtu_options(args, scan))
 
 
 def main(argv=None):

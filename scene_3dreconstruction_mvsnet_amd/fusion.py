@@ -394,7 +394,109 @@ def cloud_distance(query, ref, max_dist=float("inf"), thresholds=(), box=None, c
     return (dist, counts, stats, idx) if return_indices else (dist, counts, stats)
 
 
-def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), box=None, cell=None):
+def reduce_cell(box, P, min_dist):
+    """The cell edge reduce_cloud picks: min_dist, so that a member's candidates are the 27 cells around it, but never
+    below distance_cell(box, P), which keeps the grid inside DISTANCE_CELL_BUDGET however small min_dist is against the
+    scene.  Host arithmetic on host numbers."""
+    return max(float(min_dist), distance_cell(box, P))
+
+
+def reduce_cloud(xyz, min_dist=0.2, seed=0, box=None, cell=None, max_rounds=64, masked=False):
+    """DTU's point reduction (reducePts) on the device (mvs_cloud_reduce, include/mvs_reduce_abi.h): among the points of
+    xyz (float32 or float64 [P,3], on the GPU) inside `box` = (min, max), visit the points in the order of a hash of
+    (seed, index) and keep a point iff no point kept before it lies within min_dist, the bound included.  It is MATLAB's
+    greedy pass with randperm replaced by the hash: the same distribution, not the same points as any MATLAB run.  box
+    defaults to the bounding box of the finite points (one host synchronisation); cell, the search grid's cell edge,
+    to reduce_cell(box, P, min_dist) -- it changes the time, never a byte.
+    Returns (keep bool [P], counts int64 [4]: points inside the box, kept, undecided, rounds) on the device.  The counts
+    are read once: if a point is still undecided after max_rounds (at most 256) rounds this raises, with the count in the
+    message, and the caller raises max_rounds; about ten rounds serve a scan.  With masked=True a third item follows:
+    xyz with NaN in the rows that are not kept, as `remove_outliers` gives it, so the cloud goes on without compaction."""
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise RuntimeError("reduce_cloud: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    lo, hi = _finite_box(xyz) if box is None else box
+    if cell is None:
+        cell = reduce_cell((lo, hi), xyz.shape[0], min_dist)
+    keep, counts = _lib.cloud_reduce(xyz, lo, hi, cell, min_dist, seed=seed, max_rounds=max_rounds)
+    undecided = int(counts.cpu()[2])
+    if undecided:
+        raise RuntimeError(f"reduce_cloud: {undecided} points are still undecided after max_rounds = {max_rounds} rounds; "
+                           "raise max_rounds (at most 256)")
+    if not masked:
+        return keep, counts
+    return keep, counts, torch.where(keep[:, None], xyz, torch.full_like(xyz, float("nan")))
+
+
+def select_cloud(xyz, obs_mask=None, plane=None):
+    """DTU's observability mask and ground-plane filter on the device (mvs_cloud_select, include/mvs_reduce_abi.h).
+    obs_mask = dict(mask=uint8 or bool [n0,n1,n2] (a tensor on xyz's device, or a numpy array), origin=(3,), res=float),
+    e.g. read_obs_mask's: a point is observed iff the voxel round((p - origin) / res), halves away from zero, lies in the
+    array and is set.  plane: 4 numbers, e.g. read_plane's: a point is above iff P . (x, y, z, 1) > 0.  Returns (keep bool
+    [P]: every test that was asked for holds; False for a non-finite point, counts int64 [3]: finite points, observed
+    ones, kept ones) on the device; nothing synchronises."""
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise RuntimeError("select_cloud: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    mask = origin = None
+    res = 1.0
+    if obs_mask is not None:
+        unknown = set(obs_mask) - {"mask", "origin", "res"}
+        if unknown or not {"mask", "origin", "res"} <= set(obs_mask):
+            raise ValueError(f"select_cloud: obs_mask must hold mask, origin and res, got {sorted(obs_mask)}")
+        mask, res = obs_mask["mask"], float(obs_mask["res"])
+        if not torch.is_tensor(mask):
+            mask = torch.from_numpy(np.ascontiguousarray(mask))
+        mask = mask.to(xyz.device)
+        origin = [float(v) for v in np.asarray(obs_mask["origin"], np.float64).reshape(-1)]
+    if plane is not None:
+        plane = [float(v) for v in np.asarray(plane, np.float64).reshape(-1)]
+    return _lib.cloud_select(xyz, mask=mask, origin=origin, res=res, plane=plane)
+
+
+def _read_arrays(path, names, who):
+    """The named arrays of an .npz or a MATLAB .mat file."""
+    if str(path).endswith(".npz"):
+        with np.load(path) as f:
+            missing = [k for k in names if k not in f.files]
+            if missing:
+                raise ValueError(f"{who}: {path} holds {sorted(f.files)}, not {missing}")
+            return [np.asarray(f[k]) for k in names]
+    if str(path).endswith(".mat"):
+        try:
+            from scipy.io import loadmat
+        except ImportError as e:
+            raise RuntimeError(f"{who}: reading {path} needs scipy (scipy.io.loadmat), which is not installed; "
+                               "convert the file to .npz") from e
+        f = loadmat(path)
+        missing = [k for k in names if k not in f]
+        if missing:
+            raise ValueError(f"{who}: {path} holds {sorted(k for k in f if not k.startswith('__'))}, not {missing}")
+        return [np.asarray(f[k]) for k in names]
+    raise ValueError(f"{who}: {path} is neither .npz nor .mat")
+
+
+def read_obs_mask(path):
+    """DTU's ObsMask/ObsMaskN_10.mat, or an .npz with the same arrays ObsMask [n0,n1,n2], BB [2,3] and Res ->
+    dict(mask=uint8 [n0,n1,n2], C-contiguous in that index order, origin=float64 (3,) = BB[0], res=float), what
+    select_cloud and evaluate_cloud take.  A .mat file is read with scipy.io.loadmat."""
+    mask, bb, res = _read_arrays(path, ("ObsMask", "BB", "Res"), "read_obs_mask")
+    bb = np.asarray(bb, np.float64)
+    if mask.ndim != 3 or bb.shape != (2, 3) or np.size(res) != 1:
+        raise ValueError(f"read_obs_mask: {path}: ObsMask {mask.shape}, BB {bb.shape}, Res {np.shape(res)} "
+                         "(need [n0,n1,n2], [2,3] and one number)")
+    return dict(mask=np.ascontiguousarray(mask != 0).view(np.uint8), origin=bb[0].copy(), res=float(np.reshape(res, -1)[0]))
+
+
+def read_plane(path):
+    """DTU's ObsMask/PlaneN.mat, or an .npz with the same array P -> float64 (4,): the ground plane of select_cloud."""
+    (plane,) = _read_arrays(path, ("P",), "read_plane")
+    plane = np.asarray(plane, np.float64).reshape(-1)
+    if plane.shape != (4,):
+        raise ValueError(f"read_plane: {path}: P has {plane.size} numbers (need 4)")
+    return plane
+
+
+def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), box=None, cell=None, reduce=None,
+                   obs_mask=None, plane=None):
     """The measure a reconstruction is judged by, both directions of `cloud_distance` on the device:
         accuracy      from every point of pred_xyz to the nearest point of gt_xyz
         completeness  from every point of gt_xyz to the nearest point of pred_xyz
@@ -409,14 +511,43 @@ def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), 
     that are SEARCHED in either direction (default: each cloud's own bounding box, one host synchronisation per
     direction); the points that are scored are always all of the other cloud.  cell as in cloud_distance.
 
-    What this is not: DTU's evaluation.  There is no observability mask, no ground-plane filter and no point reduction
-    (reducePts), so clouds of different density or extent are scored as they are and the numbers are not those of the
-    MATLAB tables; it reproduces the definition of the distances, nothing more.  `downsample_cloud` and a box are the
-    tools to equalise density and region before the call."""
+    With reduce, obs_mask and plane all None that is the whole of it: the definition of the distances, with clouds of
+    different density or extent scored as they are.  The three options are the steps of DTU's evaluation, in its order:
+        reduce    dict(min_dist=0.2, seed=0, gt=False, max_rounds=64): the reconstruction goes through `reduce_cloud`
+                  first, with gt=True the ground truth too
+        obs_mask  read_obs_mask's dict: accuracy is measured from the reduced reconstruction's OBSERVED points to the
+                  whole ground truth
+        plane     read_plane's four numbers: completeness is measured from the ground-truth points ABOVE the plane to the
+                  whole reduced reconstruction (the observability mask does not thin the cloud that is searched)
+    A filtered-out point is a NaN row of the query, which cloud_distance leaves uncounted.  The dict then gains
+    `reduction`: the four counts of reduce_cloud per reduced cloud ("pred", "gt"), and `selection`: the three counts of
+    select_cloud per direction ("accuracy", "completeness").
+    What this still is not: DTU's tables.  MATLAB's randperm is replaced by a stated hash, so the kept points differ from
+    those of any MATLAB run while their distribution is the same; nothing was compared against the MATLAB code or real
+    DTU files; the per-scan tables are not built."""
     thresholds = [float(t) for t in thresholds]
     T = len(thresholds)
+    pairs =((pred_xyz, gt_xyz), (gt_xyz, pred_xyz))
+    dtu = reduce is not None or obs_mask is not None or plane is not None
+    if dtu:
+        reduction, selected = {}, []
+        if reduce is not None:
+            opt = dict(dict(min_dist=0.2, seed=0, gt=False, max_rounds=64), **reduce)
+            unknown = set(opt) - {"min_dist", "seed", "gt", "max_rounds"}
+            if unknown:
+                raise ValueError(f"evaluate_cloud: reduce: unknown keys {sorted(unknown)} (min_dist, seed, gt, max_rounds)")
+            also_gt = opt.pop("gt")
+            _, reduction["pred"], pred_xyz = reduce_cloud(pred_xyz, masked=True, **opt)
+            if also_gt:
+                _, reduction["gt"], gt_xyz = reduce_cloud(gt_xyz, masked=True, **opt)
+        queries = []
+        for xyz, tests in ((pred_xyz, dict(obs_mask=obs_mask)), (gt_xyz, dict(plane=plane))):
+            keep, counts = select_cloud(xyz, **tests)
+            selected.append(counts)
+            queries.append(torch.where(keep[:, None], xyz, torch.full_like(xyz, float("nan"))))
+        pairs = ((queries[0], gt_xyz), (queries[1], pred_xyz))
     parts = []
-    for query, ref in ((pred_xyz, gt_xyz), (gt_xyz, pred_xyz)):
+    for query, ref in pairs:
         dist, counts, stats = cloud_distance(query, ref, max_dist=max_dist, thresholds=thresholds, box=box, cell=cell)
         if dist.shape[0]:
             within = (dist >= 0) & torch.isfinite(dist)
@@ -426,6 +557,8 @@ def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), 
         else:
             median = torch.full_like(stats[0], float("nan"))
         parts += [counts.double(), stats, median.reshape(1)]
+    if dtu:
+        parts += [c.double() for c in selected] + [c.double() for c in reduction.values()]
     host = torch.cat(parts).cpu().tolist()                # the one copy; every count is below 2^31, exact as a double
     out = {}
     for name, v in (("accuracy", host[:T + 5]), ("completeness", host[T + 5:])):
@@ -436,6 +569,10 @@ def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), 
     out["recall"] = [b / comp["n"] if comp["n"] else 0.0 for b in comp["below"]]
     out["fscore"] = [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(out["precision"], out["recall"])]
     out["max_dist"], out["thresholds"] = float(max_dist), thresholds
+    if dtu:
+        tail = [int(v) for v in host[2 * (T + 5):]]
+        out["selection"] = dict(accuracy=tail[0:3], completeness=tail[3:6])
+        out["reduction"] = {name: tail[6 + 4 * k:10 + 4 * k] for k, name in enumerate(reduction)}
     return out
 
 

@@ -21,7 +21,8 @@ its K nearest neighbours there is not below mean + --outlier_std standard deviat
 
 --gt_ply PATH scores every scan's fused cloud (the full one, as it is written) against the ground-truth cloud of PATH on
 the GPU and prints the result as `<scan>: score {json}`; --max_dist, --thresholds, --box, --cell and --json are eval_cloud's
-(--json receives {scan: result}).  PATH may hold `{scan}`.  Nothing else about the run changes.
+(--json receives {scan: result}), and so are DTU's steps: --reduce_dist, --reduce_seed, --reduce_gt, --obs_mask FILE and
+--plane FILE.  PATH and the two FILEs may hold `{scan}`.  Nothing else about the run changes.
 """
 from __future__ import annotations
 
@@ -86,6 +87,10 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.gt_ply is None and (args.box is not None or args.json is not None):
         p.error("--box and --json need --gt_ply")
+    if args.gt_ply is None and (args.reduce_dist is not None or args.obs_mask is not None or args.plane is not None):
+        p.error("--reduce_dist, --obs_mask and --plane need --gt_ply")
+    if args.reduce_dist is None and (args.reduce_gt or args.reduce_seed != 0):
+        p.error("--reduce_seed and --reduce_gt need --reduce_dist")
     if len(args.thresholds) > 8:
         p.error("at most 8 --thresholds")
     if args.downsample_mm is None and args.crop_box is not None:
@@ -134,7 +139,7 @@ def main(argv=None):
                       f"below {got[-1]['stats'][2]:g})")
         if args.gt_ply is not None:
             from .fusion import read_ply
-            scores[scan] = score(got[0], read_ply(args.gt_ply.replace("{scan}", scan))[0], args)
+            scores[scan] = score(got[0], read_ply(args.gt_ply.replace("{scan}", scan))[0], args, scan=scan)
             print(f"{scan}: score {json.dumps(scores[scan], sort_keys=True)}")
     if args.json:
         with open(args.json, "w") as f:
