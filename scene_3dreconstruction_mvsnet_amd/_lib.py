@@ -53,10 +53,10 @@ _vpp = ctypes.POINTER(_vp)      # const float* const*
 
 # Every entry point, declared once on this side: header -> {name: argument types}, in the headers' order.  Any other
 # pointer is a c_void_p (device and host addresses travel as integers).  load() applies the table; SYMBOLS and
-# FUSE_SYMBOLS, CLOUD_SYMBOLS, NORMALS_SYMBOLS, OUTLIERS_SYMBOLS, DISTANCE_SYMBOLS and REDUCE_SYMBOLS are its keys;
-# tests/test_host_logic.py, tests/test_scan_fusion_host.py, tests/test_cloud_downsample_host.py,
-# tests/test_cloud_normals_host.py, tests/test_cloud_outliers_host.py, tests/test_cloud_distance_host.py and
-# tests/test_cloud_reduce_host.py hold every argument list to its prototype.
+# FUSE_SYMBOLS, CLOUD_SYMBOLS, NORMALS_SYMBOLS, OUTLIERS_SYMBOLS, DISTANCE_SYMBOLS, REDUCE_SYMBOLS and CLUSTER_SYMBOLS are its
+# keys; tests/test_host_logic.py, tests/test_scan_fusion_host.py, tests/test_cloud_downsample_host.py,
+# tests/test_cloud_normals_host.py, tests/test_cloud_outliers_host.py, tests/test_cloud_distance_host.py,
+# tests/test_cloud_reduce_host.py and tests/test_cloud_cluster_host.py hold every argument list to its prototype.
 # Everything returns int except mvs_last_error_string.
 _ABI = {
     "mvs_abi.h": {
@@ -128,6 +128,10 @@ _ABI = {
         "mvs_cloud_reduce": [_vp, _i, _ll, _vp, _vp, _d, _d, _ull, _i, _vp, _vp, _vp, _sz, _vp],
         "mvs_cloud_select": [_vp, _i, _ll, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp],
     },
+    "mvs_cluster_abi.h": {
+        "mvs_query_cluster_workspace": [_ll, _vp, _vp, _d, _szp],
+        "mvs_cloud_cluster": [_vp, _i, _ll, _vp, _vp, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    },
 }
 SYMBOLS = tuple(_ABI["mvs_abi.h"])
 FUSE_SYMBOLS = tuple(_ABI["mvs_fuse_abi.h"])
@@ -136,6 +140,7 @@ NORMALS_SYMBOLS = tuple(_ABI["mvs_normals_abi.h"])
 OUTLIERS_SYMBOLS = tuple(_ABI["mvs_outliers_abi.h"])
 DISTANCE_SYMBOLS = tuple(_ABI["mvs_distance_abi.h"])
 REDUCE_SYMBOLS = tuple(_ABI["mvs_reduce_abi.h"])
+CLUSTER_SYMBOLS = tuple(_ABI["mvs_cluster_abi.h"])
 
 
 class MvsError(RuntimeError):
@@ -159,7 +164,7 @@ def load():
                 "There is no CPU/PyTorch fallback for the MVSNet depth path.")
         lib = ctypes.CDLL(LIB_PATH)
         for name in (SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS + OUTLIERS_SYMBOLS + DISTANCE_SYMBOLS
-                     + REDUCE_SYMBOLS):
+                     + REDUCE_SYMBOLS + CLUSTER_SYMBOLS):
             if not hasattr(lib, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}")
         for prototypes in _ABI.values():
@@ -1082,6 +1087,47 @@ def cloud_select(xyz, mask=None, origin=None, res=1.0, plane=None, out=None):
                                       None if pl is None else ctypes.addressof(pl), keep.data_ptr(), counts.data_ptr(),
                                       _stream(dev)))
     return keep, counts
+
+
+# ---- density-connected components (include/mvs_cluster_abi.h, csrc/cloud_cluster.hip) ----
+def query_cluster_workspace(P, box_min, box_max, cell) -> int:
+    return _box_query("mvs_query_cluster_workspace", "query_cluster_workspace", P, box_min=box_min, box_max=box_max, edge=cell)
+
+
+def cloud_cluster(xyz, box_min, box_max, cell, eps, min_points=10, min_size=1, out=None):
+    """The density-connected components (DBSCAN) of the points of the cloud inside the box, numbered as the libraries'
+    traversal in index order numbers them, and the mask of the clusters of at least min_size points, as
+    include/mvs_cluster_abi.h defines them, on the device.
+
+    xyz float32 or float64 [P,3]; box_min, box_max: 3 host numbers each; cell: the search grid's cell edge (it changes the
+    time, never the result); eps finite and >= 0; min_points >= 1: the neighbours within eps, itself counted, of a core
+    point; min_size >= 1.  Returns (labels int32 [P]: the cluster number, -1 noise, -2 outside the box, keep bool [P],
+    counts int64 [7]: points inside the box, core, border, noise, clusters, kept points, size of the largest cluster), all
+    on the device.  `out` = (labels, keep, counts) receives the results.  Enqueued on the current stream; nothing
+    synchronises."""
+    xyz = _cloud_xyz(xyz, "cloud_cluster")
+    dev = xyz.device
+    P, radius, min_points, min_size = xyz.shape[0], float(eps), int(min_points), int(min_size)
+    if not (0.0 <= radius < float("inf")):
+        raise RuntimeError(f"cloud_cluster: eps = {radius} (need a finite eps >= 0)")
+    if not 1 <= min_points < 1 << 31:
+        raise RuntimeError(f"cloud_cluster: min_points = {min_points} (need 1 <= min_points < 2^31)")
+    if not 1 <= min_size < 1 << 31:
+        raise RuntimeError(f"cloud_cluster: min_size = {min_size} (need 1 <= min_size < 2^31)")
+    lo, hi = _box_arg(box_min, box_max, "cloud_cluster")
+    nbytes = _box_query("mvs_query_cluster_workspace", "cloud_cluster", P, box_min=lo, box_max=hi, edge=cell)
+    with torch.cuda.device(dev):
+        labels, keep, counts = _outputs("cloud_cluster", dev, [
+            ("labels", (P,), torch.int32, True), ("keep", (P,), torch.bool, True),      # the library writes bytes 0 and 1
+            ("counts", (7,), torch.int64, True)], out)
+        if P == 0:          # an empty tensor has no address to hand over: the seven zero counts of the header's P == 0
+            counts.zero_()
+            return labels, keep, counts
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(load().mvs_cloud_cluster(xyz.data_ptr(), _xyz_code(xyz), P, lo, hi, float(cell), radius, min_points, min_size,
+                                       labels.data_ptr(), keep.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream(dev)))
+    return labels, keep, counts
 
 
 # ---- FeatureNet (reference models/mvsnet.py:10-30) -------------------------------------------

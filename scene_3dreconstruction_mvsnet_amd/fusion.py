@@ -17,6 +17,10 @@ include/mvs_outliers_abi.h), between the crop and the voxel filter: `downsample=
 `cloud_distance` and `evaluate_cloud` score a cloud against a ground-truth cloud on the device (mvs_cloud_distance,
 include/mvs_distance_abi.h): accuracy, completeness, their mean, precision / recall / F-score.  The reference leaves this
 to DTU's MATLAB code; `read_ply` reads the clouds back.
+`cluster_cloud` labels the density-connected components of a cloud (DBSCAN with scikit-learn's and Open3D's labels) and
+marks the clusters above a size, on the device (mvs_cloud_cluster, include/mvs_cluster_abi.h): the step the reference
+leaves to the user of the cloud, and the remedy for small dense blobs of wrong depth; `downsample=dict(clusters=...)`,
+off by default.
 
 Differences from the reference, flagged rather than hidden:
   * cv2.remap is restated inside the kernel (1/32-pixel quantised bilinear, zero border); OpenCV is
@@ -427,6 +431,30 @@ def reduce_cloud(xyz, min_dist=0.2, seed=0, box=None, cell=None, max_rounds=64, 
     return keep, counts, torch.where(keep[:, None], xyz, torch.full_like(xyz, float("nan")))
 
 
+def cluster_cloud(xyz, eps, min_points=10, min_size=1, box=None, cell=None, masked=False):
+    """DBSCAN on the device (mvs_cloud_cluster, include/mvs_cluster_abi.h): the density-connected components of the points
+    of xyz (float32 or float64 [P,3], on the GPU) inside `box` = (min, max), with the labels scikit-learn's DBSCAN and
+    Open3D's cluster_dbscan give: two points are neighbours within eps, the bound included; a core point has at least
+    min_points neighbours, itself counted; clusters are numbered in the order of their first core point; a border point
+    takes the smallest number among its core neighbours; -1 is noise, -2 a point outside the box.  keep marks the points
+    of the clusters of at least min_size points (core and border counted): min_size drops the small dense blobs that
+    `remove_outliers` cannot see.  box defaults to the bounding box of the finite points (one host synchronisation; with
+    a box given nothing synchronises); cell, the search grid's cell edge, to max(eps, distance_cell(box, P)) -- it changes
+    the time, never a byte.
+    Returns (labels int32 [P], keep bool [P], counts int64 [7]: points inside the box, core, border, noise, clusters,
+    kept points, size of the largest cluster) on the device.  With masked=True a fourth item follows: xyz with NaN in the
+    rows that are not kept, as `remove_outliers` gives it, so the cloud goes on without compaction."""
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise RuntimeError("cluster_cloud: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    lo, hi = _finite_box(xyz) if box is None else box
+    if cell is None:
+        cell = max(float(eps), distance_cell((lo, hi), xyz.shape[0]))
+    labels, keep, counts = _lib.cloud_cluster(xyz, lo, hi, cell, eps, min_points=min_points, min_size=min_size)
+    if not masked:
+        return labels, keep, counts
+    return labels, keep, counts, torch.where(keep[:, None], xyz, torch.full_like(xyz, float("nan")))
+
+
 def select_cloud(xyz, obs_mask=None, plane=None):
     """DTU's observability mask and ground-plane filter on the device (mvs_cloud_select, include/mvs_reduce_abi.h).
     obs_mask = dict(mask=uint8 or bool [n0,n1,n2] (a tensor on xyz's device, or a numpy array), origin=(3,), res=float),
@@ -626,18 +654,24 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
     downsample=dict(..., outliers=dict(nb_neighbors=20, std_ratio=2.0, cell=5.0)) runs `remove_outliers` among the points
     inside the crop box between the normals (of the whole fused cloud, if asked for) and the voxel downsample, eval.py's
     order (817, 494-496); the downsample takes the masked cloud and the normals as they are.  The return gains one last
-    item: dict(counts int64 [3], stats float64 [3], keep bool [P]) as numpy arrays, keep over the fused cloud."""
+    item: dict(counts int64 [3], stats float64 [3], keep bool [P]) as numpy arrays, keep over the fused cloud.
+    downsample=dict(..., clusters=dict(eps=E, min_points=10, min_size=1, cell=None)) runs `cluster_cloud` among the points
+    inside the crop box after the outlier stage (on its masked cloud, if asked for) and before the voxel downsample, which
+    takes the cloud with the noise and the clusters below min_size masked out too.  eps is in the cloud's units and has no
+    default.  The return gains one last item, after the outliers' when both are asked for: dict(counts int64 [7], keep
+    bool [P], labels int32 [P]) as numpy arrays over the fused cloud."""
     import copy
-    normals_opt = outliers_opt = None
+    normals_opt = outliers_opt = clusters_opt = None
     if downsample is not None:
         downsample = dict(downsample)
         ds_ply = downsample.pop("plyfilename", None)
         normals_opt = downsample.pop("normals", None)
         outliers_opt = downsample.pop("outliers", None)
+        clusters_opt = downsample.pop("clusters", None)
         unknown = set(downsample) - {"voxel_size", "box", "scale"}
         if unknown:
             raise ValueError(f"downsample: unknown keys {sorted(unknown)} (voxel_size, box, scale, plyfilename, normals, "
-                             "outliers)")
+                             "outliers, clusters)")
         if normals_opt is not None:
             normals_opt = dict(dict(knn=30, margin=20.0, cell=5.0), **normals_opt)
             unknown = set(normals_opt) - {"knn", "margin", "cell"}
@@ -648,6 +682,13 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
             unknown = set(outliers_opt) - {"nb_neighbors", "std_ratio", "cell"}
             if unknown:
                 raise ValueError(f"downsample['outliers']: unknown keys {sorted(unknown)} (nb_neighbors, std_ratio, cell)")
+        if clusters_opt is not None:
+            clusters_opt = dict(dict(min_points=10, min_size=1, cell=None), **clusters_opt)
+            unknown = set(clusters_opt) - {"eps", "min_points", "min_size", "cell"}
+            if unknown:
+                raise ValueError(f"downsample['clusters']: unknown keys {sorted(unknown)} (eps, min_points, min_size, cell)")
+            if "eps" not in clusters_opt:
+                raise ValueError("downsample['clusters'] needs eps, the neighbourhood radius in the cloud's units")
     for a in ("view_plan", "decode_view", "assemble", "metas"):
         if not hasattr(dataset, a):
             raise ValueError("reconstruct_scan needs a dataset with metas, view_plan(), decode_view() and assemble(), "
@@ -734,6 +775,9 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
         if outliers_opt is not None:
             keep, _, out_counts, out_stats, ds_in = remove_outliers(xyz, box=downsample.get("box"), masked=True,
                                                                     **outliers_opt)
+        if clusters_opt is not None:
+            crop = bin_box() if downsample.get("box") is None else downsample["box"]
+            cl_labels, cl_keep, cl_counts, ds_in = cluster_cloud(ds_in, box=crop, masked=True, **clusters_opt)
         if normals_opt is not None:
             ds_xyz, ds_rgb, ds_nrm = downsample_cloud(ds_in, rgb, normals=normals, **downsample)
             ds_vertices, ds_colours = _packed_to_host(ds_xyz, ds_rgb)
@@ -742,12 +786,14 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
             ds_vertices, ds_colours = _packed_to_host(*downsample_cloud(ds_in, rgb, **downsample))
         if outliers_opt is not None:
             outliers = dict(counts=out_counts.cpu().numpy(), stats=out_stats.cpu().numpy(), keep=keep.cpu().numpy())
+        if clusters_opt is not None:
+            clusters = dict(counts=cl_counts.cpu().numpy(), keep=cl_keep.cpu().numpy(), labels=cl_labels.cpu().numpy())
         vertices, colours = _packed_to_host(xyz, rgb)      # the one copy of the full cloud
     if plyfilename:
         write_ply(plyfilename, vertices, colours)
     if downsample is None:
         return vertices, colours
-    tail = () if outliers_opt is None else (outliers,)
+    tail = (() if outliers_opt is None else (outliers,)) + (() if clusters_opt is None else (clusters,))
     if normals_opt is None:
         if ds_ply:
             write_ply(ds_ply, ds_vertices, ds_colours)

@@ -18,6 +18,9 @@ eval.py:817's estimate_normals: normals from K neighbours inside the box grown b
 point's camera, carried through the voxel filter and written as nx, ny, nz.  --outlier_knn K (with --downsample_mm) adds
 eval.py:495's remove_statistical_outlier between the crop and the voxel filter: a point of the box whose mean distance to
 its K nearest neighbours there is not below mean + --outlier_std standard deviations of those distances is dropped.
+--cluster_eps E (with --downsample_mm) adds fusion.cluster_cloud after that and before the voxel filter: DBSCAN among the
+points of the box with radius E (the cloud's units) and --cluster_min_points neighbours for a core point; the noise and the
+clusters of fewer than --cluster_min_size points are dropped.
 
 --gt_ply PATH scores every scan's fused cloud (the full one, as it is written) against the ground-truth cloud of PATH on
 the GPU and prints the result as `<scan>: score {json}`; --max_dist, --thresholds, --box, --cell and --json are eval_cloud's
@@ -81,6 +84,13 @@ def main(argv=None):
                    help="with --downsample_mm: drop statistical outliers from K neighbours (eval.py:495) before the voxel filter")
     p.add_argument("--outlier_std", type=float, default=2.0, metavar="S",
                    help="a point is kept while its mean neighbour distance is below mean + S standard deviations")
+    p.add_argument("--cluster_eps", type=float, default=None, metavar="E",
+                   help="with --downsample_mm: label the density-connected clusters of the box (DBSCAN, radius E in the "
+                        "cloud's units) and drop the noise and the small clusters before the voxel filter")
+    p.add_argument("--cluster_min_points", type=int, default=10, metavar="M",
+                   help="a core point has at least M points within E, itself counted")
+    p.add_argument("--cluster_min_size", type=int, default=1, metavar="S",
+                   help="a cluster is kept while it has at least S points (1 drops the noise only)")
     p.add_argument("--gt_ply", default=None, metavar="PATH",
                    help="score each scan's fused cloud against this ground-truth PLY ({scan} is replaced by the scan's name)")
     add_score_arguments(p)
@@ -99,6 +109,10 @@ def main(argv=None):
         p.error("--normals_knn needs --downsample_mm")
     if args.downsample_mm is None and args.outlier_knn is not None:
         p.error("--outlier_knn needs --downsample_mm")
+    if args.downsample_mm is None and args.cluster_eps is not None:
+        p.error("--cluster_eps needs --downsample_mm")
+    if args.cluster_eps is None and (args.cluster_min_points != 10 or args.cluster_min_size != 1):
+        p.error("--cluster_min_points and --cluster_min_size need --cluster_eps")
     box = None
     if args.downsample_mm is not None:
         box = (args.crop_box[:3], args.crop_box[3:]) if args.crop_box else bin_box(args.bin_dims, args.bin_delta)
@@ -121,6 +135,9 @@ def main(argv=None):
                 downsample["normals"] = dict(knn=args.normals_knn, margin=args.normals_margin_mm)
             if args.outlier_knn is not None:
                 downsample["outliers"] = dict(nb_neighbors=args.outlier_knn, std_ratio=args.outlier_std)
+            if args.cluster_eps is not None:
+                downsample["clusters"] = dict(eps=args.cluster_eps, min_points=args.cluster_min_points,
+                                              min_size=args.cluster_min_size)
         got = reconstruct_scan(model, ds, scan, n_view_filter=args.NviewFilter, photomask=args.photomask,
                                geomask=args.geomask, condmask_pixel=args.condmask_pixel,
                                condmask_depth=args.condmask_depth, plyfilename=ply, downsample=downsample)
@@ -134,9 +151,14 @@ def main(argv=None):
                 print(f"{scan}: normals of {estimated} of {members} points in the grown box; {open_} of them could have "
                       f"had a nearer neighbour outside it")
             if args.outlier_knn is not None:
-                members, valid, kept = (int(x) for x in got[-1]["counts"])
+                outliers = got[-2] if args.cluster_eps is not None else got[-1]
+                members, valid, kept = (int(x) for x in outliers["counts"])
                 print(f"{scan}: {kept} of {members} points in the box kept ({valid} with a neighbour elsewhere; mean distance "
-                      f"below {got[-1]['stats'][2]:g})")
+                      f"below {outliers['stats'][2]:g})")
+            if args.cluster_eps is not None:
+                members, core, border, noise, clusters, kept, largest = (int(x) for x in got[-1]["counts"])
+                print(f"{scan}: {clusters} clusters among {members} points in the box ({core} core, {border} border, {noise} "
+                      f"noise; the largest has {largest}); {kept} points kept")
         if args.gt_ply is not None:
             from .fusion import read_ply
             scores[scan] = score(got[0], read_ply(args.gt_ply.replace("{scan}", scan))[0], args, scan=scan)
