@@ -55,7 +55,8 @@
  *     and the reference cloud; one wave per query walks the rings of cells around the query's cell -- the cell nearest to
  *     it when it lies outside the box -- each lane keeping the best of the candidates it loads, one ballot per ring and one
  *     minimum over the wave at the end, until no unexamined cell can hold a nearer member or one within max_dist; a query
- *     farther than max_dist from the box is answered without reading a cell; one thread per query counts, with one ballot
+ *     farther than max_dist from the box is answered without reading a cell (the grid of this launch is capped at 2^24 - 1
+ *     blocks of 32 queries, a HIP launch having fewer than 2^32 threads, and the kernel loops over the rest); one thread per query counts, with one ballot
  *     and one integer atomic per wave and count; S(x) as in mvs_cloud_outliers; a one-thread kernel forms the mean.
  *
  * Workspace: mvs_query_distance_workspace = mvs_query_normals_workspace(P, box_min, box_max, cell)

@@ -39,7 +39,9 @@
  * MVS_FUSE_TILE consecutive pixels of one view (wave ballot + popcount); (2) one block of MVS_FUSE_SCAN_WIDTH
  * threads turns the tile counts into exclusive offsets, MVS_FUSE_SCAN_WIDTH tiles per pass with a running carry, and
  * writes counts_out; (3) every block ranks the selected pixels of its tile and writes them.  No block waits for
- * another and there are no atomics: the same inputs give the same bytes on every run and every stream.
+ * another and there are no atomics: the same inputs give the same bytes on every run and every stream.  The grids of (1)
+ * and (3) are capped at 2^24 - 1 blocks (a HIP launch has fewer than 2^32 threads) and a block takes every 2^24 - 1-th
+ * tile, so any R*h*w < 2^31 launches; below 2^24 tiles that is one tile per block.
  *
  * Workspace: mvs_query_fuse_workspace(R, h, w) = 4 * (R * ceil(h*w / MVS_FUSE_TILE) + 1) bytes, 4-byte aligned.
  *

@@ -61,7 +61,9 @@
  *     the atomics gave and does not matter; (5) one wave per member searches Chebyshev rings of cells around the member's
  *     own, keeping the best 64 candidates sorted by (d2, j) one per lane, until the knn-th is nearer than the nearest
  *     face of the examined block of cells less cell / 1000 (which covers the rounding of the cell index many times over),
- *     or the grid is exhausted; then mean, covariance, eigenvector, sign and counts.
+ *     or the grid is exhausted; then mean, covariance, eigenvector, sign and counts.  The grid of (5) is capped at 2^24 - 1
+ *     blocks of 32 members (a HIP launch has fewer than 2^32 threads) and the kernel loops over the rest, so every
+ *     P < 2^31 launches.
  *
  * Workspace, with cells = n[0] * n[1] * n[2]:
  *     mvs_query_normals_workspace = 24 * P + 8 * ceil(P / 2) + 8 * ceil(cells / 2)

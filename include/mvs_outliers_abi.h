@@ -58,7 +58,8 @@
  *
  * Launches, ordered by the stream alone (no block waits for another): the search grid of mvs_cloud_normals over the box,
  *     its classify pass writing -1.0, 0 and the NaNs for non-members; one wave per member runs the same ring search and
- *     sums the m square roots in order; S(x) by blocks of MVS_OUTLIERS_BLOCK consecutive elements, the kernel relaunched on
+ *     sums the m square roots in order (that grid is capped at 2^24 - 1 blocks and the kernel loops, as in
+ *     mvs_cloud_normals); S(x) by blocks of MVS_OUTLIERS_BLOCK consecutive elements, the kernel relaunched on
  *     the partial sums until one is left (at most four launches below 2^31 points); a one-thread kernel forms the mean;
  *     S(y) likewise, y formed on load; a one-thread kernel forms std and threshold and writes stats_out; one thread per
  *     point marks.

@@ -58,7 +58,9 @@
  *     cell-sorted order with one 32-bit state word per member (0 = undecided, else round << 1 | kept; a word written in
  *     round k reads as undecided in round k), each adding its still-undecided count into its own counter and returning at
  *     once when the previous counter is zero; one launch that writes keep_out and the counts.  The candidates of a member
- *     are the cells that [p - min_dist, p + min_dist] touches, pulled out by the slack of the grid.
+ *     are the cells that [p - min_dist, p + min_dist] touches, pulled out by the slack of the grid.  A round launch with
+ *     16 lanes per member (the test hook's form) is capped at 2^24 - 1 blocks, a HIP launch having fewer than 2^32
+ *     threads, and loops over the rest; with one lane per member it never needs more than 2^23.
  *
  * Workspace: mvs_query_reduce_workspace = mvs_query_normals_workspace(P, box_min, box_max, cell)
  *                                         + 8 * ceil(P / 2)                     the state words

@@ -250,7 +250,7 @@ __global__ void __launch_bounds__(kCloudThreads) cluster_finish_kernel(ClusterPa
 }
 
 // behind the grid's knn_workspace(P, cells): four words per point, the root tiles, the counters
-static long long cluster_tiles(long long P) { return (P + kCloudTile - 1) / kCloudTile; }
+static long long cluster_tiles(long long P) { return cloud_blocks(kLaunchRowTile, P); }      // P / 1024 <= 2^21: never capped
 static size_t cluster_words(long long P) { return 8 * (size_t)((P + 1) / 2); }      // one 32-bit word per point, 8-byte aligned
 static size_t cluster_tail(long long P) {
     return 4 * cluster_words(P) + 8 * (size_t)((cluster_tiles(P) + 2) / 2) + 8 * (size_t)kClusterCounters;

@@ -6,18 +6,21 @@
 //   tile_count            the count half of the ballot compaction: how many flags of a block's tile are set
 //   tile_ranks            the emit half: the output rank of every set flag, in (pass, wave, lane) order
 //   box_load              a point as doubles, and whether it lies inside a box
-// Host side: the one check of P, the box and the grid's edge (grid_check), the xyz dtype and workspace refusals, and the
-// body of a workspace query over such a grid.
+// Host side: the block count of every launch (cloud_blocks, capped at HIP's limit; the capped kernels loop), the one check
+// of P, the box and the grid's edge (grid_check), the xyz dtype and workspace refusals, and the body of a workspace query
+// over such a grid.
 // Everything is integer bookkeeping except box_load, which converts and compares: nothing here rounds.
 #pragma once
 
 #include "mvs_cloud_abi.h"
 #include "mvs_fuse_abi.h"
-#include "mvs_internal.h"
 #include "mvs_normals_abi.h"
+#include "mvs_outliers_abi.h"
 
-#include <cmath>
+#include <atomic>
 
+// ---- the launch geometry: plain C++, no HIP.  tests/cloud_launch_sweep.cpp defines MVS_CLOUD_GEOMETRY_ONLY and includes
+// this part alone, with the host compiler, and asks it about every launch below at the ends of the ABI's domain.
 namespace mvs {
 
 // one block of a tile kernel: kCloudThreads threads cover a tile of kCloudTile elements in kCloudPasses passes, element
@@ -27,10 +30,97 @@ constexpr int kCloudWaves = kCloudThreads / 64;
 constexpr int kCloudTile = 1024;
 constexpr int kCloudPasses = kCloudTile / kCloudThreads;
 constexpr int kCloudScanWidth = 1024;
+constexpr int kCloudChunk = MVS_CLOUD_CHUNK;      // points one block of the downsample's crop pass covers
+constexpr int kSumBlock = MVS_OUTLIERS_BLOCK;     // elements, and threads, of one block of cloud_sum.h's tree
+constexpr int kKnnPerWave = 8;                    // members one wave of a search kernel serves in turn
+constexpr int kKnnGroup = 16;                     // lanes that share one span in knn_nearest and in the wide reduce round
 static_assert(MVS_FUSE_TILE == kCloudTile && MVS_CLOUD_TILE == kCloudTile && MVS_NORMALS_TILE == kCloudTile,
               "one tile size for fuse, downsample and the k-NN grid");
 static_assert(MVS_FUSE_SCAN_WIDTH == kCloudScanWidth && MVS_CLOUD_SCAN_WIDTH == kCloudScanWidth, "one scan width");
 static_assert(kCloudThreads % 64 == 0 && kCloudTile % kCloudThreads == 0 && kCloudScanWidth % 64 == 0, "whole waves");
+
+// HIP launches no grid of 2^32 threads or more (gridDim.x * blockDim.x, the note at hipModuleLaunchKernel in
+// hip_runtime_api.h), so a launch of kCloudThreads-thread blocks has at most this many of them
+constexpr long long kCloudMaxBlocks = (1LL << 32) / kCloudThreads - 1;
+static_assert(kCloudMaxBlocks == (1 << 24) - 1 && (kCloudMaxBlocks + 1) * kCloudThreads == (1LL << 32),
+              "the cap is the last block count below 2^32 threads of kCloudThreads per block");
+
+// THE block count of a cloud-path launch: `work` items, `per_block` of them per block and trip
+inline int cloud_blocks(long long work, int per_block) {
+    const long long needed = (work + per_block - 1) / per_block;
+    return (int)(needed < kCloudMaxBlocks ? needed : kCloudMaxBlocks);
+}
+
+// Every launch of the cloud path whose grid grows with the problem (the single-block scans and scalar kernels are <<<1>>>).
+// A launch with loops = true can be capped inside the ABI's domain (P, N, cells, R*h*w < 2^31): its kernel takes group
+// blockIdx.x of its work, then every gridDim.x-th, which below the cap is one trip.  One with loops = false stays below
+// the cap for every legal size, by the bound written next to it, and its kernel is one trip by construction.
+enum CloudWork { kWorkRows, kWorkCells, kWorkFuseTiles };      // rows: the P points of a cloud or the N queries
+struct CloudLaunch {
+    const char* kernels;
+    CloudWork work;
+    int per_block;     // items one block takes per trip
+    int threads;       // of a block
+    bool loops;
+};
+// one thread per row: P / 256 <= 2^23.  The classify, scatter, mark, count, finish, select, accumulate, core, union and
+// label kernels, and the reduce round with one lane per member
+constexpr CloudLaunch kLaunchRow{"one thread per point or query", kWorkRows, kCloudThreads, kCloudThreads, false};
+// one block per tile of cells or voxels: cells / 1024 <= 2^21.  knn_tile_sum, knn_cell_scan, cloud_count, cloud_emit
+constexpr CloudLaunch kLaunchCellTile{"one block per tile of cells", kWorkCells, kCloudTile, kCloudThreads, false};
+// one block per tile of point indices: P / 1024 <= 2^21.  cluster_flatten, cluster_number
+constexpr CloudLaunch kLaunchRowTile{"one block per tile of points", kWorkRows, kCloudTile, kCloudThreads, false};
+// cloud_crop_min: P / 1024 <= 2^21
+constexpr CloudLaunch kLaunchChunk{"cloud_crop_min_kernel", kWorkRows, kCloudChunk, kCloudThreads, false};
+// cloud_sum_kernel, every level of cloud_sum_tree: blocks of kSumBlock = 1024 threads, n / 1024 <= 2^21 < 2^22 - 1
+constexpr CloudLaunch kLaunchSum{"cloud_sum_kernel", kWorkRows, kSumBlock, kSumBlock, false};
+// one wave per member, kKnnPerWave in turn (cloud_knn.h's knn_search_blocks): capped above 32 * (2^24 - 1) points
+constexpr CloudLaunch kLaunchSearch{"normals_search_kernel, outliers_search_kernel", kWorkRows, kCloudWaves * kKnnPerWave,
+                                    kCloudThreads, true};
+// the same shape over the N queries of mvs_cloud_distance
+constexpr CloudLaunch kLaunchQuerySearch{"distance_search_kernel", kWorkRows, kCloudWaves * kKnnPerWave, kCloudThreads,
+                                         true};
+// reduce_round_kernel with kKnnGroup lanes per member (the test hook's form): capped from P = 2^28 - 15 on
+constexpr CloudLaunch kLaunchRoundWide{"reduce_round_kernel, 16 lanes per member", kWorkRows, kCloudThreads / kKnnGroup,
+                                       kCloudThreads, true};
+// one block per tile of one view: R * ceil(h*w / 1024) tiles, capped from 2^24 tiles on (h = w = 1, R = 2^24)
+constexpr CloudLaunch kLaunchFuseTile{"fuse_count_kernel, fuse_scatter_kernel", kWorkFuseTiles, 1, kCloudThreads, true};
+constexpr CloudLaunch kCloudLaunches[] = {kLaunchRow, kLaunchCellTile, kLaunchRowTile,     kLaunchChunk,     kLaunchSum,
+                                          kLaunchSearch, kLaunchQuerySearch, kLaunchRoundWide, kLaunchFuseTile};
+
+// The hook of the tests, not part of the ABI (mvs_test_cloud_max_blocks, fuse_points.hip): a lower cap for the launches
+// that loop, so that clouds of ordinary size go round those loops several times.  One variable for the whole library
+inline std::atomic<long long> g_cloud_loop_cap{kCloudMaxBlocks};
+
+inline long long cloud_groups(const CloudLaunch& L, long long work) { return (work + L.per_block - 1) / L.per_block; }
+inline int cloud_blocks(const CloudLaunch& L, long long work) {
+    const int blocks = cloud_blocks(work, L.per_block);
+    const long long cap = L.loops ? g_cloud_loop_cap.load(std::memory_order_relaxed) : kCloudMaxBlocks;
+    return blocks < cap ? blocks : (int)cap;
+}
+// Is the grid of launch L short of its work?  Then the launch takes the kernel's looping form; else the one-trip form,
+// which is the kernel as it was before there was a cap
+inline bool cloud_capped(const CloudLaunch& L, long long work) { return cloud_blocks(L, work) < cloud_groups(L, work); }
+// how often the kernel of launch L goes round its block-stride loop at most
+inline long long cloud_trips(const CloudLaunch& L, long long work) {
+    if (!L.loops) return 1;
+    const long long groups = cloud_groups(L, work), blocks = cloud_blocks(L, work);
+    return blocks ? (groups + blocks - 1) / blocks : 0;
+}
+
+// the fuse's tiles: those of one view, and of the scan (R*h*w < 2^31, so neither wraps)
+inline int cloud_fuse_tiles_per_view(int h, int w) { return (int)(((long long)h * w + kCloudTile - 1) / kCloudTile); }
+inline long long cloud_fuse_tiles(int R, int h, int w) { return (long long)R * cloud_fuse_tiles_per_view(h, w); }
+
+}  // namespace mvs
+
+#ifndef MVS_CLOUD_GEOMETRY_ONLY
+
+#include "mvs_internal.h"
+
+#include <cmath>
+
+namespace mvs {
 
 // In-place exclusive scan of tiles[0 .. n_tiles), kWidth of them per pass with a running carry.  Called by all kWidth
 // threads of a single block; returns the total in every thread.  tiles[n_tiles] is the caller's to write.  The last
@@ -184,3 +274,5 @@ static int grid_query(const char* who, const GridKind& kind, long long P, const 
 }
 
 }  // namespace mvs
+
+#endif  // MVS_CLOUD_GEOMETRY_ONLY

@@ -39,14 +39,18 @@ __global__ void __launch_bounds__(kCloudThreads) distance_classify_kernel(KnnGri
     knn_classify<T>(G, (long long)blockIdx.x * kCloudThreads + threadIdx.x, members);
 }
 
-template <typename T>
+// kCapped: the grid is short of the queries (kLaunchQuerySearch) and a block takes every gridDim.x-th group of
+// kCloudWaves * kKnnPerWave of them; else one group per block, the kernel without a loop
+template <typename T, bool kCapped>
 __global__ void __launch_bounds__(kCloudThreads) distance_search_kernel(DistanceParams O) {
     const KnnGrid& G = O.G;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int M = G.P > 0 ? knn_members(G) : 0;
+    long long block = blockIdx.x;
+    do
     for (int t = 0; t < kKnnPerWave; ++t) {
-        const long long i = ((long long)blockIdx.x * kCloudWaves + wave) * kKnnPerWave + t;
+        const long long i = (block * kCloudWaves + wave) * kKnnPerWave + t;
         if (i >= O.N) break;
         const T* src = static_cast<const T*>(O.query) + (size_t)i * 3;
         double q[3];
@@ -71,6 +75,7 @@ __global__ void __launch_bounds__(kCloudThreads) distance_search_kernel(Distance
             if (O.idx_out) O.idx_out[i] = idx;
         }
     }
+    while (kCapped && (block += gridDim.x) * (kCloudWaves * kKnnPerWave) < O.N);
 }
 
 __global__ void __launch_bounds__(kCloudThreads) distance_count_kernel(DistanceParams O) {
@@ -168,12 +173,16 @@ int mvs_cloud_distance(const void* ref_xyz, int ref_dtype, long long P, const vo
         if (int rc = check_hip(hipGetLastError(), "distance_classify_kernel")) return rc;
         if (int rc = knn_build_finish(O.G, f64, s)) return rc;
     }
-    const int per_block = kCloudWaves * kKnnPerWave;
-    const int search_blocks = (int)((N + per_block - 1) / per_block);
-    if (query_dtype == MVS_CLOUD_F64) distance_search_kernel<double><<<search_blocks, kCloudThreads, 0, s>>>(O);
-    else distance_search_kernel<float><<<search_blocks, kCloudThreads, 0, s>>>(O);
+    const int search_blocks = cloud_blocks(kLaunchQuerySearch, N);       // capped: the kernel loops
+    if (cloud_capped(kLaunchQuerySearch, N)) {
+        if (query_dtype == MVS_CLOUD_F64) distance_search_kernel<double, true><<<search_blocks, kCloudThreads, 0, s>>>(O);
+        else distance_search_kernel<float, true><<<search_blocks, kCloudThreads, 0, s>>>(O);
+    } else {
+        if (query_dtype == MVS_CLOUD_F64) distance_search_kernel<double, false><<<search_blocks, kCloudThreads, 0, s>>>(O);
+        else distance_search_kernel<float, false><<<search_blocks, kCloudThreads, 0, s>>>(O);
+    }
     if (int rc = check_hip(hipGetLastError(), "distance_search_kernel")) return rc;
-    distance_count_kernel<<<(int)((N + kCloudThreads - 1) / kCloudThreads), kCloudThreads, 0, s>>>(O);
+    distance_count_kernel<<<cloud_blocks(kLaunchRow, N), kCloudThreads, 0, s>>>(O);
     if (int rc = check_hip(hipGetLastError(), "distance_count_kernel")) return rc;
     const double* total = nullptr;
     if (int rc = cloud_sum_tree(kSumFinite, dist_out, N, partials, scalars, s, &total)) return rc;

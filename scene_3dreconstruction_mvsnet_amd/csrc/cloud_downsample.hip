@@ -25,7 +25,6 @@
 
 namespace mvs {
 
-constexpr int kCloudChunk = MVS_CLOUD_CHUNK;
 constexpr int kCloudRecord = MVS_CLOUD_RECORD;
 static_assert(kCloudChunk % kCloudThreads == 0, "whole waves");
 
@@ -255,8 +254,9 @@ __global__ void __launch_bounds__(kCloudThreads) cloud_emit_kernel(CloudParams C
         });
 }
 
-static long long cloud_chunks(long long P) { return (P + kCloudChunk - 1) / kCloudChunk; }
-static long long cloud_tiles(long long cells) { return (cells + kCloudTile - 1) / kCloudTile; }
+// neither is ever capped: P / 1024 and cells / 1024 are at most 2^21 (cloud_common.h)
+static long long cloud_chunks(long long P) { return cloud_blocks(kLaunchChunk, P); }
+static long long cloud_tiles(long long cells) { return cloud_blocks(kLaunchCellTile, cells); }
 
 static size_t cloud_workspace(long long P, long long cells) {
     return sizeof(CloudHead) + sizeof(CloudRecord) * (size_t)cells + sizeof(CloudPartial) * (size_t)cloud_chunks(P) +
@@ -325,7 +325,7 @@ static int cloud_downsample(const char* who, bool with_normals, const void* xyz,
         if (int rc = check_hip(hipMemsetAsync(C.nsum, 0, kCloudNormalSums * (size_t)cells, s), "zeroing the normal sums"))
             return rc;
     if (P > 0) {
-        const int blocks = (int)((P + kCloudThreads - 1) / kCloudThreads);
+        const int blocks = cloud_blocks(kLaunchRow, P);
         if (with_normals) {
             if (f64) cloud_accumulate_kernel<double, true><<<blocks, kCloudThreads, 0, s>>>(C);
             else cloud_accumulate_kernel<float, true><<<blocks, kCloudThreads, 0, s>>>(C);

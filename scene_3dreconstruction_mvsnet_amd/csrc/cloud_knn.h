@@ -13,7 +13,9 @@
 //                           the cell counts become exclusive offsets, in place
 //   knn_scatter_kernel      one thread per member: claims the next slot of its cell (which turns the cell's offset into its
 //                           END) and writes its index and its point, as doubles, there (all four: knn_build_finish)
-//   the user's search       one WAVE per member, kKnnPerWave members in turn: knn_search, see below
+//   the user's search       one WAVE per member, kKnnPerWave members in turn: knn_search, see below.  Its grid is capped
+//                           (cloud_common.h's kLaunchSearch): a block takes group blockIdx.x of kCloudWaves * kKnnPerWave
+//                           members, then every gridDim.x-th, which is one trip below 32 * (2^24 - 1) points
 // The order of the points inside a cell is whatever the atomics gave.  It cannot reach the output: the neighbours are the
 // first min(knn, M) of a TOTAL order, (d2, index), every candidate that could be among them is examined, and the users' sums
 // run over them in that order.
@@ -42,9 +44,7 @@
 
 namespace mvs {
 
-constexpr int kKnnPerWave = 8;                    // members one wave of a search kernel serves
-constexpr double kKnnSlack = 1e-3;                // of a cell, see above
-constexpr int kKnnGroup = 16;                     // lanes that share one span in knn_nearest
+constexpr double kKnnSlack = 1e-3;                // of a cell, see above (kKnnPerWave, kKnnGroup: cloud_common.h)
 static_assert(MVS_NORMALS_KNN_MAX == 64, "one candidate per lane");
 static_assert(kCloudTile == 4 * kCloudThreads, "four cells per thread");
 
@@ -408,7 +408,7 @@ __device__ __forceinline__ void knn_nearest(const KnnGrid& G, const double q[3],
 }
 
 // ---- host side
-static long long knn_tiles(long long cells) { return (cells + kCloudTile - 1) / kCloudTile; }
+static long long knn_tiles(long long cells) { return cloud_blocks(kLaunchCellTile, cells); }      // cells / 1024 <= 2^21: never capped
 // mvs_query_normals_workspace: the sorted points and indices, the cells, the tiles
 static size_t knn_workspace(long long P, long long cells) {
     return 24 * (size_t)P + 8 * (size_t)((P + 1) / 2) + 8 * (size_t)((cells + 1) / 2) + 8 * (size_t)((knn_tiles(cells) + 2) / 2);
@@ -438,11 +438,9 @@ static void knn_bind(KnnGrid& G, const void* xyz, long long P, const double* box
     G.n_tiles = (int)knn_tiles(cells);
 }
 
-static int knn_point_blocks(const KnnGrid& G) { return (int)(((long long)G.P + kCloudThreads - 1) / kCloudThreads); }
-static int knn_search_blocks(const KnnGrid& G) {
-    const int per_block = kCloudWaves * kKnnPerWave;
-    return (int)(((long long)G.P + per_block - 1) / per_block);
-}
+static int knn_point_blocks(const KnnGrid& G) { return cloud_blocks(kLaunchRow, G.P); }
+static int knn_tile_blocks(const KnnGrid& G) { return cloud_blocks(kLaunchCellTile, G.cells); }      // = G.n_tiles
+static int knn_search_blocks(const KnnGrid& G) { return cloud_blocks(kLaunchSearch, G.P); }          // capped: the kernel loops
 
 // before the user's classify kernel (P > 0)
 static int knn_build_begin(const KnnGrid& G, hipStream_t s) {
@@ -451,11 +449,11 @@ static int knn_build_begin(const KnnGrid& G, hipStream_t s) {
 
 // after it: offsets, then the scatter
 static int knn_build_finish(const KnnGrid& G, bool f64, hipStream_t s) {
-    knn_tile_sum_kernel<<<G.n_tiles, kCloudThreads, 0, s>>>(G);
+    knn_tile_sum_kernel<<<knn_tile_blocks(G), kCloudThreads, 0, s>>>(G);
     if (int rc = check_hip(hipGetLastError(), "knn_tile_sum_kernel")) return rc;
     knn_tile_scan_kernel<<<1, kCloudScanWidth, 0, s>>>(G);
     if (int rc = check_hip(hipGetLastError(), "knn_tile_scan_kernel")) return rc;
-    knn_cell_scan_kernel<<<G.n_tiles, kCloudThreads, 0, s>>>(G);
+    knn_cell_scan_kernel<<<knn_tile_blocks(G), kCloudThreads, 0, s>>>(G);
     if (int rc = check_hip(hipGetLastError(), "knn_cell_scan_kernel")) return rc;
     if (f64) knn_scatter_kernel<double><<<knn_point_blocks(G), kCloudThreads, 0, s>>>(G);
     else knn_scatter_kernel<float><<<knn_point_blocks(G), kCloudThreads, 0, s>>>(G);

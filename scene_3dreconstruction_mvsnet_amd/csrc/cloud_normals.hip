@@ -55,7 +55,9 @@ __device__ __forceinline__ void jacobi_rotate(double A[3][3], double V[3][3]) {
     }
 }
 
-template <typename T>
+// kCapped: the grid is short of the members (kLaunchSearch) and a block takes every gridDim.x-th group of
+// kCloudWaves * kKnnPerWave of them; else one group per block, the kernel without a loop
+template <typename T, bool kCapped>
 __global__ void __launch_bounds__(kCloudThreads) normals_search_kernel(NormalsParams N) {
     const KnnGrid& G = N.G;
     const int lane = threadIdx.x & 63;
@@ -63,8 +65,10 @@ __global__ void __launch_bounds__(kCloudThreads) normals_search_kernel(NormalsPa
     const int M = knn_members(G);
     const int m = M < G.knn ? M : G.knn;        // neighbours of every member
     long long estimated = 0, uncertified = 0;
+    long long block = blockIdx.x;
+    do
     for (int t = 0; t < kKnnPerWave; ++t) {
-        const long long s = ((long long)blockIdx.x * kCloudWaves + wave) * kKnnPerWave + t;
+        const long long s = (block * kCloudWaves + wave) * kKnnPerWave + t;
         if (s >= M) break;
         const int i = G.sidx[s];
         if (i < 0 || i >= G.P) continue;        // cannot happen: the scatter filled every slot below M
@@ -166,6 +170,7 @@ __global__ void __launch_bounds__(kCloudThreads) normals_search_kernel(NormalsPa
         const double last = lane_double(L.d2, m - 1);     // m >= 1: this member itself
         if (m < G.knn || last > f * f) ++uncertified;
     }
+    while (kCapped && (block += gridDim.x) * (kCloudWaves * kKnnPerWave) < M);
     if (lane == 0) {
         if (estimated)
             __hip_atomic_fetch_add(&N.counts_out[1], estimated, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -218,8 +223,13 @@ int mvs_cloud_normals(const void* xyz, int xyz_dtype, long long P, const double 
     if (int rc = check_hip(hipGetLastError(), "normals_classify_kernel")) return rc;
     if (int rc = knn_build_finish(N.G, f64, s)) return rc;
     const int search_blocks = knn_search_blocks(N.G);
-    if (f64) normals_search_kernel<double><<<search_blocks, kCloudThreads, 0, s>>>(N);
-    else normals_search_kernel<float><<<search_blocks, kCloudThreads, 0, s>>>(N);
+    if (cloud_capped(kLaunchSearch, P)) {
+        if (f64) normals_search_kernel<double, true><<<search_blocks, kCloudThreads, 0, s>>>(N);
+        else normals_search_kernel<float, true><<<search_blocks, kCloudThreads, 0, s>>>(N);
+    } else {
+        if (f64) normals_search_kernel<double, false><<<search_blocks, kCloudThreads, 0, s>>>(N);
+        else normals_search_kernel<float, false><<<search_blocks, kCloudThreads, 0, s>>>(N);
+    }
     return check_hip(hipGetLastError(), "normals_search_kernel");
 }
 

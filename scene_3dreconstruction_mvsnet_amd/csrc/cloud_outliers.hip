@@ -54,6 +54,8 @@ __global__ void __launch_bounds__(kCloudThreads) outliers_classify_kernel(Outlie
     }
 }
 
+// kCapped: as in normals_search_kernel
+template <bool kCapped>
 __global__ void __launch_bounds__(kCloudThreads) outliers_search_kernel(OutliersParams O) {
     const KnnGrid& G = O.G;
     const int lane = threadIdx.x & 63;
@@ -61,8 +63,10 @@ __global__ void __launch_bounds__(kCloudThreads) outliers_search_kernel(Outliers
     const int M = knn_members(G);
     const int m = M < G.knn ? M : G.knn;        // neighbours of every member
     long long valid = 0;
+    long long block = blockIdx.x;
+    do
     for (int t = 0; t < kKnnPerWave; ++t) {
-        const long long s = ((long long)blockIdx.x * kCloudWaves + wave) * kKnnPerWave + t;
+        const long long s = (block * kCloudWaves + wave) * kKnnPerWave + t;
         if (s >= M) break;
         const int i = G.sidx[s];
         if (i < 0 || i >= G.P) continue;        // cannot happen: the scatter filled every slot below M
@@ -79,6 +83,7 @@ __global__ void __launch_bounds__(kCloudThreads) outliers_search_kernel(Outliers
         if (lane == 0) O.dist_out[i] = dist;
         if (dist > 0.0) ++valid;
     }
+    while (kCapped && (block += gridDim.x) * (kCloudWaves * kKnnPerWave) < M);
     if (lane == 0 && valid)
         __hip_atomic_fetch_add(&O.counts_out[1], valid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -171,7 +176,8 @@ int mvs_cloud_outliers(const void* xyz, int xyz_dtype, long long P, const double
     else outliers_classify_kernel<float><<<blocks, kCloudThreads, 0, s>>>(O);
     if (int rc = check_hip(hipGetLastError(), "outliers_classify_kernel")) return rc;
     if (int rc = knn_build_finish(O.G, f64, s)) return rc;
-    outliers_search_kernel<<<knn_search_blocks(O.G), kCloudThreads, 0, s>>>(O);
+    if (cloud_capped(kLaunchSearch, P)) outliers_search_kernel<true><<<knn_search_blocks(O.G), kCloudThreads, 0, s>>>(O);
+    else outliers_search_kernel<false><<<knn_search_blocks(O.G), kCloudThreads, 0, s>>>(O);
     if (int rc = check_hip(hipGetLastError(), "outliers_search_kernel")) return rc;
     const double* total = nullptr;
     if (int rc = cloud_sum_tree(kSumPositive, dist_out, P, partials, scalars, s, &total)) return rc;

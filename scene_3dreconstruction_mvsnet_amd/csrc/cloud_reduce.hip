@@ -62,74 +62,81 @@ __global__ void __launch_bounds__(kCloudThreads) reduce_classify_kernel(ReducePa
 // so fl(p[a] - reach) <= p[j][a] <= fl(p[a] + reach) as real numbers.  knn_cell is a monotone function of the coordinate
 // (a difference, a quotient and a floor, each monotone), so j's cell lies between the cells of those two bounds on every
 // axis, whatever the cell size.  The clamps of the spans cannot bite, see knn_take.
-template <int kLanes>
+// kCapped: the grid is short of the members' lanes (kLaunchRoundWide under its cap) and a block goes on to every
+// gridDim.x-th group; else one group per block, the kernel without a loop
+template <int kLanes, bool kCapped>
 __global__ void __launch_bounds__(kCloudThreads) reduce_round_kernel(ReduceParams R, int k) {
     if (R.counters[k - 1] == 0) return;       // nobody was undecided after the round before: the same in every thread
     const KnnGrid& G = R.G;
     const int M = knn_members(G);
-    const long long t = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
-    const long long s = t / kLanes;
-    const int sub = (int)(t % kLanes);
-    bool active = s < M;
-    if (active) active = __hip_atomic_load(&R.state[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
-    bool removed = false, waiting = false;
-    if (active) {
-        double p[3], lo[3], hi[3];
+    // group `block` of kCloudThreads / kLanes members, block-stride: with kKnnGroup lanes per member the grid is capped
+    // (kLaunchRoundWide).  A round reads only what earlier rounds decided, so the order of its members is free
+    long long block = blockIdx.x;
+    do {
+        const long long t = block * kCloudThreads + threadIdx.x;
+        const long long s = t / kLanes;
+        const int sub = (int)(t % kLanes);
+        bool active = s < M;
+        if (active) active = __hip_atomic_load(&R.state[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
+        bool removed = false, waiting = false;
+        if (active) {
+            double p[3], lo[3], hi[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            p[a] = G.sxyz[(size_t)s * 3 + a];
-            lo[a] = p[a] - R.reach;
-            hi[a] = p[a] + R.reach;
-        }
-        const int i = G.sidx[s];
-        const unsigned long long hi_key = reduce_key(R.seed, i);
-        int c0[3], c1[3];
-        knn_cell(G, lo, c0);
-        knn_cell(G, hi, c1);
-        for (int z = c0[2]; z <= c1[2] && !(kLanes == 1 && removed); ++z) {
-            for (int y = c0[1]; y <= c1[1] && !(kLanes == 1 && removed); ++y) {
-                const int line = knn_linear(G, 0, y, z);
-                int a = knn_begin(G, line + c0[0]), b = G.cells_end[line + c1[0]];
-                a = a < 0 ? 0 : a;
-                b = b > G.P ? G.P : b;
-                for (int j = a + sub; j < b; j += kLanes) {
-                    if (j == s) continue;
-                    const double* q = G.sxyz + (size_t)j * 3;
-                    const double dx = q[0] - p[0], dy = q[1] - p[1], dz = q[2] - p[2];
-                    const double d2 = (dx * dx + dy * dy) + dz * dz;
-                    if (!(d2 <= R.md2)) continue;
-                    const int ij = G.sidx[j];
-                    const unsigned long long hj = reduce_key(R.seed, ij);
-                    if (!(hj < hi_key || (hj == hi_key && ij < i))) continue;
-                    const unsigned w = __hip_atomic_load(&R.state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (w == 0u || (int)(w >> 1) >= k) {
-                        waiting = true;             // no earlier round decided j
-                    } else if (w & 1u) {
-                        removed = true;             // an earlier round kept j
-                        if (kLanes == 1) break;
+            for (int a = 0; a < 3; ++a) {
+                p[a] = G.sxyz[(size_t)s * 3 + a];
+                lo[a] = p[a] - R.reach;
+                hi[a] = p[a] + R.reach;
+            }
+            const int i = G.sidx[s];
+            const unsigned long long hi_key = reduce_key(R.seed, i);
+            int c0[3], c1[3];
+            knn_cell(G, lo, c0);
+            knn_cell(G, hi, c1);
+            for (int z = c0[2]; z <= c1[2] && !(kLanes == 1 && removed); ++z) {
+                for (int y = c0[1]; y <= c1[1] && !(kLanes == 1 && removed); ++y) {
+                    const int line = knn_linear(G, 0, y, z);
+                    int a = knn_begin(G, line + c0[0]), b = G.cells_end[line + c1[0]];
+                    a = a < 0 ? 0 : a;
+                    b = b > G.P ? G.P : b;
+                    for (int j = a + sub; j < b; j += kLanes) {
+                        if (j == s) continue;
+                        const double* q = G.sxyz + (size_t)j * 3;
+                        const double dx = q[0] - p[0], dy = q[1] - p[1], dz = q[2] - p[2];
+                        const double d2 = (dx * dx + dy * dy) + dz * dz;
+                        if (!(d2 <= R.md2)) continue;
+                        const int ij = G.sidx[j];
+                        const unsigned long long hj = reduce_key(R.seed, ij);
+                        if (!(hj < hi_key || (hj == hi_key && ij < i))) continue;
+                        const unsigned w = __hip_atomic_load(&R.state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (w == 0u || (int)(w >> 1) >= k) {
+                            waiting = true;             // no earlier round decided j
+                        } else if (w & 1u) {
+                            removed = true;             // an earlier round kept j
+                            if (kLanes == 1) break;
+                        }
                     }
                 }
             }
         }
-    }
-    if (kLanes > 1) {      // the lanes of a member put their findings together; every lane of the wave is here
-        const int shift = (threadIdx.x & 63) / kLanes * kLanes;
-        const unsigned long long group = (kLanes >= 64 ? ~0ull : (1ull << kLanes) - 1ull) << shift;
-        removed = (__ballot(removed) & group) != 0;
-        waiting = (__ballot(waiting) & group) != 0;
-    }
-    bool still = false;
-    if (active && sub == 0) {
-        if (removed)
-            __hip_atomic_store(&R.state[s], (unsigned)k << 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else if (!waiting)
-            __hip_atomic_store(&R.state[s], ((unsigned)k << 1) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else
-            still = true;
-    }
-    const int count = __popcll(__ballot(still));
-    if ((threadIdx.x & 63) == 0 && count)
-        __hip_atomic_fetch_add(&R.counters[k], (long long)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (kLanes > 1) {      // the lanes of a member put their findings together; every lane of the wave is here
+            const int shift = (threadIdx.x & 63) / kLanes * kLanes;
+            const unsigned long long group = (kLanes >= 64 ? ~0ull : (1ull << kLanes) - 1ull) << shift;
+            removed = (__ballot(removed) & group) != 0;
+            waiting = (__ballot(waiting) & group) != 0;
+        }
+        bool still = false;
+        if (active && sub == 0) {
+            if (removed)
+                __hip_atomic_store(&R.state[s], (unsigned)k << 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else if (!waiting)
+                __hip_atomic_store(&R.state[s], ((unsigned)k << 1) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else
+                still = true;
+        }
+        const int count = __popcll(__ballot(still));
+        if ((threadIdx.x & 63) == 0 && count)
+            __hip_atomic_fetch_add(&R.counters[k], (long long)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } while (kCapped && (block += gridDim.x) * kCloudThreads < (long long)M * kLanes);
 }
 
 __global__ void __launch_bounds__(kCloudThreads) reduce_finish_kernel(ReduceParams R) {
@@ -275,10 +282,14 @@ int mvs_cloud_reduce(const void* xyz, int dtype, long long P, const double box_m
     if (int rc = check_hip(hipGetLastError(), "reduce_classify_kernel")) return rc;
     if (int rc = knn_build_finish(R.G, f64, s)) return rc;
     const int lanes = g_reduce_lanes.load(std::memory_order_relaxed);
-    const int round_blocks = (int)((P * lanes + kCloudThreads - 1) / kCloudThreads);       // P * 16 < 2^35, blocks < 2^27
+    // one lane per member is a per-point launch; kKnnGroup lanes would need up to 2^27 blocks, eight times what HIP
+    // launches, so that grid is capped and the kernel loops
+    const int round_blocks = cloud_blocks(lanes == 1 ? kLaunchRow : kLaunchRoundWide, P);
+    const bool capped = lanes != 1 && cloud_capped(kLaunchRoundWide, P);
     for (int k = 1; k <= max_rounds; ++k) {
-        if (lanes == 1) reduce_round_kernel<1><<<round_blocks, kCloudThreads, 0, s>>>(R, k);
-        else reduce_round_kernel<kKnnGroup><<<round_blocks, kCloudThreads, 0, s>>>(R, k);
+        if (lanes == 1) reduce_round_kernel<1, false><<<round_blocks, kCloudThreads, 0, s>>>(R, k);
+        else if (capped) reduce_round_kernel<kKnnGroup, true><<<round_blocks, kCloudThreads, 0, s>>>(R, k);
+        else reduce_round_kernel<kKnnGroup, false><<<round_blocks, kCloudThreads, 0, s>>>(R, k);
         if (int rc = check_hip(hipGetLastError(), "reduce_round_kernel")) return rc;
     }
     reduce_finish_kernel<<<knn_point_blocks(R.G), kCloudThreads, 0, s>>>(R);
@@ -327,7 +338,7 @@ int mvs_cloud_select(const void* xyz, int dtype, long long P, const unsigned cha
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = check_hip(hipMemsetAsync(counts_out, 0, 3 * sizeof(long long), s), "zeroing the counts")) return rc;
     if (P == 0) return MVS_OK;
-    const int blocks = (int)((P + kCloudThreads - 1) / kCloudThreads);
+    const int blocks = cloud_blocks(kLaunchRow, P);
     if (dtype == MVS_CLOUD_F64) select_kernel<double><<<blocks, kCloudThreads, 0, s>>>(S);
     else select_kernel<float><<<blocks, kCloudThreads, 0, s>>>(S);
     return check_hip(hipGetLastError(), "select_kernel");

@@ -10,13 +10,12 @@
 #pragma once
 
 #include "mvs_outliers_abi.h"
-#include "mvs_internal.h"
+#include "cloud_common.h"      // kSumBlock, cloud_blocks
 
 #include <cmath>
 
 namespace mvs {
 
-constexpr int kSumBlock = MVS_OUTLIERS_BLOCK;
 constexpr int kSumWaves = kSumBlock / 64;
 static_assert(kSumWaves == 16, "the second butterfly runs over 16 lanes");
 static_assert(MVS_OUTLIERS_SCALARS >= 3 * sizeof(double), "mean, threshold, the total of a single element");
@@ -81,7 +80,7 @@ static int cloud_sum_tree(int first_mode, const double* in, long long n, double*
     double* out = n > 1 ? partials : scalars + kScalarTotal;      // a single element has no level of partial sums
     int mode = first_mode;
     for (;;) {
-        const long long blocks = (n + kSumBlock - 1) / kSumBlock;
+        const long long blocks = cloud_blocks(kLaunchSum, n);      // n / 1024 <= 2^21: never capped
         if (mode == kSumPositive) cloud_sum_kernel<kSumPositive><<<(int)blocks, kSumBlock, 0, s>>>(in, n, scalars, out);
         else if (mode == kSumDeviation) cloud_sum_kernel<kSumDeviation><<<(int)blocks, kSumBlock, 0, s>>>(in, n, scalars, out);
         else if (mode == kSumFinite) cloud_sum_kernel<kSumFinite><<<(int)blocks, kSumBlock, 0, s>>>(in, n, scalars, out);

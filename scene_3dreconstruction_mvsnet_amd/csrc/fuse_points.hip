@@ -44,13 +44,26 @@ __device__ __forceinline__ unsigned fuse_pixel(int t, int pass) {
     return (unsigned)t * kCloudTile + pass * kCloudThreads + threadIdx.x;
 }
 
+// Both tile kernels take tile blockIdx.x, then every gridDim.x-th: the grid is capped (cloud_common.h's kLaunchFuseTile),
+// and below 2^24 tiles that is one trip.  tile_count and tile_ranks keep their partial counts in LDS, so a block that goes
+// round again synchronises first.
+// the tile after T of this block, n_tiles when there is none: 32-bit like T itself (n_tiles < 2^31, gridDim.x < 2^24), and
+// the sum is formed only where it fits
+__device__ __forceinline__ int fuse_next_tile(const FuseParams& P, int T) {
+    return P.n_tiles - T > (int)gridDim.x ? T + (int)gridDim.x : P.n_tiles;
+}
+// kCapped: the grid is short of the tiles; else one tile per block, the kernel without a loop
+template <bool kCapped>
 __global__ void __launch_bounds__(kCloudThreads) fuse_count_kernel(FuseParams P) {
-    const int T = blockIdx.x;
-    const int r = T / P.tiles_per_view, t = T - r * P.tiles_per_view;
-    const int ref = P.ref_idx[r];
-    const bool view_ok = ref >= 0 && ref < P.V;
-    const int s = tile_count<kCloudPasses, kCloudThreads>([&P, view_ok, r, t](int i) { return fuse_flag(P, view_ok, r, fuse_pixel(t, i)); });
-    if (threadIdx.x == 0) P.tiles[T] = s;
+    int T = blockIdx.x;
+    do {
+        const int r = T / P.tiles_per_view, t = T - r * P.tiles_per_view;
+        const int ref = P.ref_idx[r];
+        const bool view_ok = ref >= 0 && ref < P.V;
+        const int s = tile_count<kCloudPasses, kCloudThreads>([&P, view_ok, r, t](int i) { return fuse_flag(P, view_ok, r, fuse_pixel(t, i)); });
+        if (threadIdx.x == 0) P.tiles[T] = s;
+        if (kCapped && fuse_next_tile(P, T) < P.n_tiles) __syncthreads();      // the same in every thread of the block
+    } while (kCapped && (T = fuse_next_tile(P, T)) < P.n_tiles);
 }
 
 __global__ void __launch_bounds__(kCloudScanWidth) fuse_scan_kernel(FuseParams P) {
@@ -63,40 +76,44 @@ __global__ void __launch_bounds__(kCloudScanWidth) fuse_scan_kernel(FuseParams P
     if (tid == 0) P.counts_out[P.R] = carry;
 }
 
+template <bool kCapped>
 __global__ void __launch_bounds__(kCloudThreads) fuse_scatter_kernel(FuseParams P) {
-    const int T = blockIdx.x;
-    const int r = T / P.tiles_per_view, t = T - r * P.tiles_per_view;
-    const int ref = P.ref_idx[r];
-    const bool view_ok = ref >= 0 && ref < P.V;
-    const long long tile_base = P.tiles[T];
     const size_t H = (size_t)4 * P.h, W = (size_t)4 * P.w;   // image rows and columns
-    tile_ranks<kCloudPasses, kCloudThreads>(
-        [&P, view_ok, r, t](int i) { return fuse_flag(P, view_ok, r, fuse_pixel(t, i)); },
-        [=, &P](int i, int rank, bool set) {
-            const long long o = tile_base + rank;
-            if (!set || o >= P.capacity) return;
-            const int p = (int)fuse_pixel(t, i);       // selected, so below h*w
-            const double* src = P.xyz + ((size_t)r * P.hw + p) * 3;
-            float* dst = P.xyz_out + (size_t)o * 3;
-            dst[0] = (float)src[0];      // v_cvt_f32_f64, round-to-nearest-even
-            dst[1] = (float)src[1];
-            dst[2] = (float)src[2];
-            const int y = p / P.w, x = p - y * P.w;
-            const size_t py = (size_t)4 * y + 1, px = (size_t)4 * x + 1;
-            unsigned char* c = P.rgb_out + (size_t)o * 3;
-            if (P.hwc) {
-                const unsigned char* s = P.images + (((size_t)ref * H + py) * W + px) * 3;
-                c[0] = s[0];
-                c[1] = s[1];
-                c[2] = s[2];
-            } else {
-                const size_t plane = H * W;
-                const unsigned char* s = P.images + (size_t)ref * 3 * plane + py * W + px;
-                c[0] = s[0];
-                c[1] = s[plane];
-                c[2] = s[2 * plane];
-            }
-        });
+    int T = blockIdx.x;
+    do {
+        const int r = T / P.tiles_per_view, t = T - r * P.tiles_per_view;
+        const int ref = P.ref_idx[r];
+        const bool view_ok = ref >= 0 && ref < P.V;
+        const long long tile_base = P.tiles[T];
+        tile_ranks<kCloudPasses, kCloudThreads>(
+            [&P, view_ok, r, t](int i) { return fuse_flag(P, view_ok, r, fuse_pixel(t, i)); },
+            [=, &P](int i, int rank, bool set) {
+                const long long o = tile_base + rank;
+                if (!set || o >= P.capacity) return;
+                const int p = (int)fuse_pixel(t, i);       // selected, so below h*w
+                const double* src = P.xyz + ((size_t)r * P.hw + p) * 3;
+                float* dst = P.xyz_out + (size_t)o * 3;
+                dst[0] = (float)src[0];      // v_cvt_f32_f64, round-to-nearest-even
+                dst[1] = (float)src[1];
+                dst[2] = (float)src[2];
+                const int y = p / P.w, x = p - y * P.w;
+                const size_t py = (size_t)4 * y + 1, px = (size_t)4 * x + 1;
+                unsigned char* c = P.rgb_out + (size_t)o * 3;
+                if (P.hwc) {
+                    const unsigned char* s = P.images + (((size_t)ref * H + py) * W + px) * 3;
+                    c[0] = s[0];
+                    c[1] = s[1];
+                    c[2] = s[2];
+                } else {
+                    const size_t plane = H * W;
+                    const unsigned char* s = P.images + (size_t)ref * 3 * plane + py * W + px;
+                    c[0] = s[0];
+                    c[1] = s[plane];
+                    c[2] = s[2 * plane];
+                }
+            });
+        if (kCapped && fuse_next_tile(P, T) < P.n_tiles) __syncthreads();      // the same in every thread of the block
+    } while (kCapped && (T = fuse_next_tile(P, T)) < P.n_tiles);
 }
 
 static int fuse_check(int R, int h, int w) {
@@ -105,10 +122,8 @@ static int fuse_check(int R, int h, int w) {
     return MVS_OK;
 }
 
-static int fuse_tiles_per_view(int h, int w) { return (int)(((long long)h * w + kCloudTile - 1) / kCloudTile); }
-
 static size_t fuse_workspace(int R, int h, int w) {
-    return sizeof(int) * ((size_t)R * fuse_tiles_per_view(h, w) + 1);
+    return sizeof(int) * ((size_t)cloud_fuse_tiles(R, h, w) + 1);
 }
 
 }  // namespace mvs
@@ -116,6 +131,13 @@ static size_t fuse_workspace(int R, int h, int w) {
 using namespace mvs;
 
 extern "C" {
+
+// The hook of the tests, not part of the ABI: the cap on the blocks of the cloud path's looping launches (1 .. 2^24 - 1)
+// in later calls of this process.  Returns the value it replaces; any other argument only reads it.
+long long mvs_test_cloud_max_blocks(long long blocks) {
+    if (blocks >= 1 && blocks <= kCloudMaxBlocks) return g_cloud_loop_cap.exchange(blocks, std::memory_order_relaxed);
+    return g_cloud_loop_cap.load(std::memory_order_relaxed);
+}
 
 int mvs_query_fuse_workspace(int R, int h, int w, size_t* bytes) {
     if (!bytes) return fail(MVS_ERR_NULL, "mvs_query_fuse_workspace: NULL bytes");
@@ -156,15 +178,19 @@ int mvs_fuse_points(const double* xyz_world, const unsigned char* masks, const v
     P.h = h;
     P.w = w;
     P.hw = h * w;
-    P.tiles_per_view = fuse_tiles_per_view(h, w);
-    P.n_tiles = R * P.tiles_per_view;      // <= R*h*w < 2^31
+    P.tiles_per_view = cloud_fuse_tiles_per_view(h, w);
+    P.n_tiles = (int)cloud_fuse_tiles(R, h, w);      // <= R*h*w < 2^31
+    const int tile_blocks = cloud_blocks(kLaunchFuseTile, P.n_tiles);      // capped: the kernels loop
     P.hwc = image_format == MVS_IMG_U8_HWC;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    fuse_count_kernel<<<P.n_tiles, kCloudThreads, 0, s>>>(P);
+    const bool capped = cloud_capped(kLaunchFuseTile, P.n_tiles);
+    if (capped) fuse_count_kernel<true><<<tile_blocks, kCloudThreads, 0, s>>>(P);
+    else fuse_count_kernel<false><<<tile_blocks, kCloudThreads, 0, s>>>(P);
     if (int rc = check_hip(hipGetLastError(), "fuse_count_kernel")) return rc;
     fuse_scan_kernel<<<1, kCloudScanWidth, 0, s>>>(P);
     if (int rc = check_hip(hipGetLastError(), "fuse_scan_kernel")) return rc;
-    fuse_scatter_kernel<<<P.n_tiles, kCloudThreads, 0, s>>>(P);
+    if (capped) fuse_scatter_kernel<true><<<tile_blocks, kCloudThreads, 0, s>>>(P);
+    else fuse_scatter_kernel<false><<<tile_blocks, kCloudThreads, 0, s>>>(P);
     return check_hip(hipGetLastError(), "fuse_scatter_kernel");
 }
 

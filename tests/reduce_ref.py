@@ -27,25 +27,29 @@ def workspace_bytes(P, box_min, box_max, cell):
     return normals_ref.workspace_bytes(P, box_min, box_max, cell) + 8 * -(-P // 2) + 8 * (ROUNDS_MAX + 2)
 
 
-def keys(P, seed=0):
-    """h(i) for i = 0 .. P-1 -> uint64 [P]."""
+def keys(P, seed=0, rows=None):
+    """h(i) for i = 0 .. P-1 -> uint64 [P]; with `rows` (int [P]) for i = rows[0] .. rows[P-1]: the points are rows of a
+    larger cloud."""
+    i = np.arange(P, dtype=np.uint64) if rows is None else np.asarray(rows).astype(np.uint64)
+    assert len(i) == P
     with np.errstate(over="ignore"):
-        z = np.uint64(seed & 0xFFFFFFFFFFFFFFFF) + (np.arange(P, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+        z = np.uint64(seed & 0xFFFFFFFFFFFFFFFF) + (i + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
         z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
         z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
         return z ^ (z >> np.uint64(31))
 
 
-def earlier_near(xyz, box_min, box_max, min_dist, seed=0, chunk=256):
+def earlier_near(xyz, box_min, box_max, min_dist, seed=0, chunk=256, rows=None):
     """-> (ids int64 [M]: the members' rows, rank int64 [M]: each member's place in key order, src, dst int64 [E]: the
-    pairs (a, b) of positions in `ids` with b in E(a): near a, with a smaller key)."""
+    pairs (a, b) of positions in `ids` with b in E(a): near a, with a smaller key).  `rows` (increasing): the index each
+    point has in the cloud it was taken from, which is what its key hashes."""
     p = np.asarray(xyz).astype(np.float64).reshape(-1, 3)
     min_dist = np.float64(min_dist)
     assert np.isfinite(min_dist) and min_dist >= 0
     ids = np.flatnonzero(normals_ref.members_of(p, box_min, box_max))
     m = p[ids]
     M = len(ids)
-    h = keys(len(p), seed)[ids]
+    h = keys(len(p), seed, rows)[ids]
     rank = np.empty(M, np.int64)
     rank[np.lexsort((ids, h))] = np.arange(M)
     md2 = min_dist * min_dist
@@ -94,10 +98,10 @@ def reduce_sequential(xyz, box_min, box_max, min_dist, seed=0):
     return mask, int(kept.sum())
 
 
-def reduce_rounds(xyz, box_min, box_max, min_dist, seed=0, max_rounds=64):
+def reduce_rounds(xyz, box_min, box_max, min_dist, seed=0, max_rounds=64, rows=None):
     """The header's synchronous rule -> (mask bool [P], counts [members, kept, undecided, rounds])."""
     assert 1 <= max_rounds <= ROUNDS_MAX
-    ids, _, src, dst = earlier_near(xyz, box_min, box_max, min_dist, seed)
+    ids, _, src, dst = earlier_near(xyz, box_min, box_max, min_dist, seed, rows=rows)
     M = len(ids)
     decided, kept = np.zeros(M, bool), np.zeros(M, bool)
     rounds = 0
