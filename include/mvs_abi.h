@@ -30,6 +30,19 @@
  *    returns MVS_ERR_HIP for such a shape, it is never served wrongly.  "The volume domain" below is the one
  *    mvs_query_workspace checks: N in [1,64], C = 32, D, h, w positive multiples of 8, D*h*w*32 < 2^32, dtype an
  *    mvs_dtype.
+ *  - Alignment.  Read from the gfx950 code of the kernels each entry point can select.  Where a public tensor is read or
+ *    written wider than an element (float4 / f32x4 / dwordx4 loads and stores, 16-byte LDS-staged epilogues), or read
+ *    as consecutive wave-uniform values (rt, depth_values, proj: scalar loads the compiler merges into multi-dword
+ *    ones), the pointer must be 16-byte aligned, else MVS_ERR_BAD_SHAPE; the blobs are read with uniform and 16-byte
+ *    loads and must be 16-byte aligned, else MVS_ERR_WORKSPACE; a workspace 256 bytes, else MVS_ERR_WORKSPACE.  Decided
+ *    on the host before anything is enqueued; a NULL that is allowed passes.  Whether the hardware would serve such an
+ *    access at a 4-byte aligned address is not measured and no test tries.  A pointer stated "per element" below is
+ *    touched by single-dword vector accesses only and needs a float's alignment: tests/test_gpu_wrapper_contract.py runs
+ *    each of them one element into a larger allocation.  torch's allocations are 256-byte aligned; a row of a batch is
+ *    16-byte aligned when a row is a multiple of 4 floats.  The entry points with a rule of their own state it:
+ *    mvs_conv3d_train_* (min(C, 4) floats), mvs_bn3d_train_*, mvs_volume_relayout (16 bytes), mvs_depth_metrics
+ *    (element-aligned tensors are served by a scalar or shifted path; workspace 8 bytes).  mvs_filter_depth states none
+ *    and is outside this rule.
  */
 #ifndef MVS_ABI_H
 #define MVS_ABI_H
@@ -64,7 +77,7 @@ typedef enum mvs_status {
     MVS_ERR_BAD_SHAPE = 1,   /* dims not supported (C != 32, D/h/w not multiples of 8, N < 1 ...);
                                 the reference raises a torch shape error here (mvsnet.py:69-71) */
     MVS_ERR_BAD_DTYPE = 2,   /* storage dtype not implemented */
-    MVS_ERR_WORKSPACE = 3,   /* workspace / blob too small or misaligned */
+    MVS_ERR_WORKSPACE = 3,   /* workspace / blob too small or misaligned (workspace: 256 bytes; blob: 16 bytes) */
     MVS_ERR_HIP = 4,         /* a HIP runtime call failed (launch error ...) */
     MVS_ERR_NULL = 5         /* required pointer is NULL */
 } mvs_status;
@@ -118,7 +131,9 @@ int mvs_pack_weights(const float* const* conv_weights, const float* const* bn_pa
 /* rt_out[(v-1)*12 .. +12] = rows 0..2 of proj[v] @ inverse(proj[0]) as rot (9, row-major) then
  * trans (3), for v = 1..N-1.   Replaces torch.inverse/matmul at models/module.py:107-109.
  *   proj   dev fp32 [N][4][4]      rt_out dev fp32 [(N-1)][12]
- * Domain: N in [1,64]; neither pointer may be NULL.  N = 1 enqueues nothing and leaves rt_out untouched. */
+ * Domain: N in [1,64]; neither pointer may be NULL.  N = 1 enqueues nothing and leaves rt_out untouched.
+ * Alignment: proj and rt_out 16-byte aligned, else MVS_ERR_BAD_SHAPE (the kernel reads proj with dwordx4 and 16-dword
+ *   uniform loads and writes rt_out with dwordx4 stores). */
 int mvs_relative_proj(const float* proj, float* rt_out, int N, void* stream);
 
 /* Fused homography warp + variance cost volume.
@@ -129,7 +144,9 @@ int mvs_relative_proj(const float* proj, float* rt_out, int N, void* stream);
  *   var_out       dev, C8-planar [4][D][h][w][8] in `dtype`; must not alias the workspace
  *   workspace     dev, >= mvs_query_workspace bytes (uses the feature-transpose region only)
  * Domain: the volume domain.  rt may be NULL when N = 1; no other pointer may.  A workspace smaller than the
- * feature-transpose region or not 256-byte aligned is MVS_ERR_WORKSPACE.  Nothing is enqueued on a refusal. */
+ * feature-transpose region or not 256-byte aligned is MVS_ERR_WORKSPACE.  Nothing is enqueued on a refusal.
+ * Alignment: feats per element (the transpose reads single floats).  var_out (f32x4 / 16-byte stores), rt and
+ *   depth_values (consecutive uniform reads) 16-byte aligned, else MVS_ERR_BAD_SHAPE. */
 int mvs_warp_variance(const float* feats, const float* rt, const float* depth_values,
                       void* var_out, void* workspace, size_t workspace_bytes, int N, int C, int D,
                       int h, int w, int dtype, void* stream);
@@ -144,7 +161,9 @@ int mvs_warp_variance(const float* feats, const float* rt, const float* depth_va
  *   logit keeps its bound; non-finite logits outside the reference's set stay within the kernel forms' tile geometry
  *   (Winograd along z: the rest of the 4- or 2-plane output tile; Toeplitz-pair and transposed forms: one voxel in x).
  * Domain: the volume domain with N = 1, C = 32; no pointer may be NULL; workspace >= mvs_query_workspace(1, 32, D, h, w,
- * dtype) bytes and 256-byte aligned, else MVS_ERR_WORKSPACE.  Nothing is enqueued on a refusal. */
+ * dtype) bytes and 256-byte aligned, else MVS_ERR_WORKSPACE.  Nothing is enqueued on a refusal.
+ * Alignment: every data pointer 16-byte aligned, else MVS_ERR_BAD_SHAPE (the conv kernels load and store activations and
+ *   logits 16 bytes at a time); weights_blob 16-byte aligned, else MVS_ERR_WORKSPACE. */
 int mvs_costreg_forward(const void* var, const void* weights_blob, float* cost_out,
                         void* workspace, size_t workspace_bytes, int D, int h, int w, int dtype,
                         void* stream);
@@ -163,7 +182,9 @@ int mvs_costreg_forward(const void* var, const void* weights_blob, float* cost_o
  * (the prob kernel holds a piece's offset from its tile's halo origin, up to 5 planes and 9 rows on, in 31 bits: it
  * bites only below D = 5 or within a row of the first bound), else MVS_ERR_BAD_SHAPE.  Any such volume is served, down
  * to 1 x 1 x 1: the tile forms pad.  skip may be NULL at layers 0..6 and 10 (it is not read); x, y,
- * weights_blob and, at layers 7..9, skip may not.  Nothing is enqueued on a refusal. */
+ * weights_blob and, at layers 7..9, skip may not.  Nothing is enqueued on a refusal.
+ * Alignment: every data pointer 16-byte aligned, else MVS_ERR_BAD_SHAPE (the conv kernels load and store activations and
+ *   logits 16 bytes at a time); weights_blob 16-byte aligned, else MVS_ERR_WORKSPACE. */
 int mvs_conv_layer(int layer, const void* x, const void* skip, void* y, const void* weights_blob,
                    int Di, int Hi, int Wi, int dtype, void* stream);
 
@@ -177,7 +198,9 @@ int mvs_conv_layer(int layer, const void* x, const void* skip, void* y, const vo
  * NaN and infinity in x or skip: as stated at mvs_costreg_forward (a non-finite skip voxel reaches its 27 logits, a
  *   non-finite x voxel the logits of its transposed footprint and one more voxel in x).
  * Domain: Di, Hi, Wi >= 1 and Di*Hi*Wi*64 < 2^31 (31-bit element offsets into the full-resolution skip plane), else
- * MVS_ERR_BAD_SHAPE; dtype 0..2; no pointer may be NULL.  Nothing is enqueued on a refusal. */
+ * MVS_ERR_BAD_SHAPE; dtype 0..2; no pointer may be NULL.  Nothing is enqueued on a refusal.
+ * Alignment: every data pointer 16-byte aligned, else MVS_ERR_BAD_SHAPE (the conv kernels load and store activations and
+ *   logits 16 bytes at a time); weights_blob 16-byte aligned, else MVS_ERR_WORKSPACE. */
 int mvs_conv11_prob(const void* x, const void* skip, float* cost_out, const void* weights_blob,
                     int Di, int Hi, int Wi, int dtype, void* stream);
 
@@ -189,7 +212,10 @@ int mvs_conv11_prob(const void* x, const void* skip, float* cost_out, const void
  *   among finite ones is a term of exactly 0; other pixels of the block are untouched.
  * Domain: D in [1, 2^24] (the expected depth index is an fp32 sum of p_d * d: exact integers end there), h, w >= 1 and
  * h*w <= 2^31 - 256 (the pixel index of the last, partly filled block is an int), else MVS_ERR_BAD_SHAPE; no pointer
- * may be NULL.  D = 1 yields depth = depth_values[0] and confidence 1.  Nothing is enqueued on a refusal. */
+ * may be NULL.  D = 1 yields depth = depth_values[0] and confidence 1.  Nothing is enqueued on a refusal.
+ * Alignment: cost, depth_out and conf_out per element.  depth_values is read uniformly (the unrolled forms may merge
+ *   its loads); nothing is asked of it: tests/test_gpu_softargmin_ref.py has always run rows of a batch that are only
+ *   4-byte aligned. */
 int mvs_softargmin_conf(const float* cost, const float* depth_values, float* depth_out,
                         float* conf_out, int D, int h, int w, void* stream);
 
@@ -197,7 +223,10 @@ int mvs_softargmin_conf(const float* cost, const float* depth_values, float* dep
  * batch item.  Replaces models/mvsnet.py:145-218 after FeatureNet.
  *   proj dev fp32 [N][4][4]; other arguments as above.
  * Domain: the volume domain; no pointer may be NULL; workspace >= mvs_query_workspace(N, C, D, h, w, dtype) bytes and
- * 256-byte aligned, else MVS_ERR_WORKSPACE.  Nothing is enqueued on a refusal. */
+ * 256-byte aligned, else MVS_ERR_WORKSPACE.  Nothing is enqueued on a refusal.
+ * Alignment: feats, depth_out and conf_out per element (the transpose reads, the soft-argmin kernel writes, single
+ *   floats).  proj (mvs_relative_proj's dwordx4 reads) and depth_values (consecutive uniform reads) 16-byte aligned,
+ *   else MVS_ERR_BAD_SHAPE; weights_blob 16-byte aligned, else MVS_ERR_WORKSPACE. */
 int mvs_depth_infer(const float* feats, const float* proj, const float* depth_values,
                     const void* weights_blob, float* depth_out, float* conf_out, void* workspace,
                     size_t workspace_bytes, int N, int C, int D, int h, int w, int dtype,
@@ -213,7 +242,8 @@ int mvs_depth_infer(const float* feats, const float* proj, const float* depth_va
  *   proj      dev fp32 [N][4][4] in view_idx order; other arguments as mvs_depth_infer
  *             (workspace of mvs_query_workspace(N, ...) bytes).
  * An index outside [0, V) or V < 1 returns MVS_ERR_BAD_SHAPE, a NULL view_idx MVS_ERR_NULL; nothing
- * is enqueued then.  Otherwise the domain, pointers and workspace of mvs_depth_infer. */
+ * is enqueued then.  Otherwise the domain, pointers, workspace and alignment of mvs_depth_infer (view_idx is a host
+ * array: any alignment of an int). */
 int mvs_depth_infer_views(const float* feats, int V, const int* view_idx, const float* proj,
                           const float* depth_values, const void* weights_blob, float* depth_out,
                           float* conf_out, void* workspace, size_t workspace_bytes, int N, int C,
@@ -228,7 +258,10 @@ int mvs_depth_infer_views(const float* feats, int V, const int* view_idx, const 
  *   h*w < 2^31 (int texel offsets), D*h*w <= (2^31 - 2) * 256 (one thread per output voxel of a channel, fewer than
  *   2^31 blocks of 256) and C*D*h*w <= 2^61 (64-bit byte offsets), else MVS_ERR_BAD_SHAPE.
  * Domain, mvs_depth_regression: D, h, w >= 1 and h*w <= 2^31 - 256 (int pixel index), else MVS_ERR_BAD_SHAPE.
- * Neither takes a NULL pointer; nothing is enqueued on a refusal. */
+ * Neither takes a NULL pointer; nothing is enqueued on a refusal.
+ * Alignment, mvs_homo_warp: src_fea, depth_values and out per element (one thread, one float, gathered or stored singly);
+ *   rt 16-byte aligned, else MVS_ERR_BAD_SHAPE (12 consecutive uniform reads).  mvs_depth_regression: p and depth_out
+ *   per element; depth_values is read uniformly and nothing is asked of it. */
 int mvs_homo_warp(const float* src_fea, const float* rt, const float* depth_values, float* out,
                   int C, int D, int h, int w, void* stream);
 int mvs_depth_regression(const float* p, const float* depth_values, float* depth_out, int D,
@@ -308,7 +341,12 @@ int mvs_filter_depth(const float* depth, const float* conf, const float* ref_mat
  *   mvs_forward_images_fmt: both that domain and the volume domain at h = H / 4, w = W / 4, so H, W are positive
  *   multiples of 32.  No pointer of any of them may be NULL (the packers: nor conv_weights[0..7], bn_params[0..27]);
  *   a workspace (blob) smaller than its query or not 256-byte aligned is MVS_ERR_WORKSPACE.  Nothing is enqueued on a
- *   refusal. */
+ *   refusal.
+ * Alignment, mvs_feature_layer, mvs_feature_conv01_fmt, mvs_feature_net[_fmt], mvs_forward_images[_fmt] alike: imgs (the
+ *   uint8 forms too), x, y and feats_out 16-byte aligned, else MVS_ERR_BAD_SHAPE (csrc/featnet.hip stages and stores
+ *   activations 16 bytes at a time; its image reads and the NCHW store were not settled and stay with them);
+ *   feature_blob and weights_blob 16-byte aligned, else MVS_ERR_WORKSPACE.  mvs_forward_images[_fmt]: proj and
+ *   depth_values as mvs_depth_infer; depth_out and conf_out per element. */
 #define MVS_FEATURE_LAYERS 8
 int mvs_query_feature_blob(size_t* bytes);
 int mvs_pack_feature_weights(const float* const* conv_weights, const float* const* bn_params,
@@ -375,6 +413,11 @@ int mvs_depth_metrics(const float* depth_est, const float* depth_gt, const float
  *   non-finite grad_depth[p] make grad_cost[:, p] non-finite (NaN, or the infinity the formula gives for an infinite
  *   grad_depth); a single -inf logit among finite ones is a term of exactly 0 with gradient 0, and the other depths
  *   of that pixel keep their bound.  The bytes of every other pixel are those of the call on finite input.
+ * Alignment: mvs_warp_variance_backward holds every pointer to 16 bytes, else MVS_ERR_BAD_SHAPE (rt and depth_values are
+ *   consecutive uniform reads; feats, grad_var and grad_feats were not read from the compiled code and stay with them).
+ *   mvs_softargmin_backward asks for none: its kernel is compiled with 8-byte (dwordx2) accesses, and
+ *   tests/test_gpu_train_autograd.py has always run it on rows of a batch that are only 4-byte aligned; no test of
+ *   the alignment rule adds to that.
  * Neither allocates, needs a workspace or synchronises. */
 int mvs_warp_variance_backward(const float* feats, const float* rt, const float* depth_values, const float* grad_var,
                                float* grad_feats, int N, int C, int D, int h, int w, void* stream);

@@ -208,13 +208,70 @@ def _check_out(t, shape, dtype, device, who, what):
         raise RuntimeError(f"{who} must be a contiguous {what}")
 
 
-def _dev_f32(t: torch.Tensor, name: str) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must live on the GPU (got {t.device}); the MVSNet depth path "
-                           "has no CPU implementation")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32 (got {t.dtype})")
+def _dev_in(t, name, dtype=torch.float32, shape=None, device=None):
+    """The refusal of a device input that is on the host, not of `dtype`, empty, or (where given) not shaped `shape` or
+    not on `device`; otherwise the tensor, contiguous (a non-contiguous view is copied)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must live on the GPU (got {t.device if isinstance(t, torch.Tensor) else type(t).__name__}); "
+                           "the MVSNet depth path has no CPU implementation")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{name} must be {str(dtype)[6:]} (got {t.dtype})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+    if device is not None and t.device != device:
+        raise RuntimeError(f"{name} is on {t.device}, not on {device}: the tensors of one call must be on one device")
+    if t.numel() == 0:
+        raise RuntimeError(f"{name} is empty: {list(t.shape)}")
     return t.contiguous()
+
+
+def _dev_f32(t: torch.Tensor, name: str) -> torch.Tensor:
+    return _dev_in(t, name)
+
+
+def _aligned16(who, **tensors):
+    """The library's alignment rule (include/mvs_abi.h), before the call: the pointers its kernels touch wider than an
+    element, and the blobs, are refused unless 16-byte aligned, which a contiguous view at an offset of a larger tensor
+    need not be.  The tensors the header states are per element are not passed here."""
+    for name, t in tensors.items():
+        if t is not None and t.data_ptr() & 15:
+            raise RuntimeError(f"{who}: {name} starts at 0x{t.data_ptr():x}: the library reads and writes 16 bytes at a time "
+                               "and refuses an address that is not 16-byte aligned (a view at an offset of a larger tensor)")
+
+
+_BLOB_QUERY = {"weights": "mvs_query_weights_blob", "feature": "mvs_query_feature_blob"}
+_blob_bytes = {}
+
+
+def _check_blob(blob, which, device, who):
+    """The refusal of a packed blob ("weights": pack_weights, "feature": pack_feature_weights) that is not a contiguous
+    1-D uint8 tensor on `device` of at least its query's bytes: the library gets an address and no size to check."""
+    need = _blob_bytes.get(which)
+    if need is None:
+        need = _blob_bytes[which] = _query(_BLOB_QUERY[which])
+    if not isinstance(blob, torch.Tensor) or not blob.is_cuda or blob.device != device or blob.dtype != torch.uint8 \
+            or blob.dim() != 1 or blob.numel() < need or not blob.is_contiguous() or blob.data_ptr() & 15:
+        got = f"{blob.dtype} {list(blob.shape)} on {blob.device}" if isinstance(blob, torch.Tensor) else type(blob).__name__
+        raise RuntimeError(f"{who}: the {which} blob must be a contiguous, 16-byte aligned uint8 [{need}] tensor on {device} (pack_"
+                           f"{'feature_' if which == 'feature' else ''}weights(...).to(device)), got {got}")
+
+
+def _check_workspace(ws, device, who, align=256):
+    """The refusal of a workspace that is not a contiguous 1-D uint8 tensor on `device`, aligned as its entry point asks:
+    its numel() travels as its size in bytes.  Whether it is large enough is the library's check."""
+    if not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.device != device or ws.dtype != torch.uint8 \
+            or ws.dim() != 1 or not ws.is_contiguous() or ws.data_ptr() & (align - 1):
+        got = f"{ws.dtype} {list(ws.shape)} on {ws.device}" if isinstance(ws, torch.Tensor) else type(ws).__name__
+        raise RuntimeError(f"{who}: workspace must be a contiguous, {align}-byte aligned 1-D uint8 tensor on {device}, got {got}")
+
+
+def _rt_arg(rt, N, device, who):
+    """rt [(N-1),12] of relative_proj on `device`; with one view there is nothing to read and None may stand for it."""
+    if N == 1 and rt is None:
+        return None
+    if N == 1 and isinstance(rt, torch.Tensor) and rt.dim() == 2:
+        return _dev_in(rt, f"{who}: rt", shape=(rt.shape[0], 12), device=device)
+    return _dev_in(rt, f"{who}: rt", shape=(N - 1, 12), device=device)
 
 
 # reference parameter names, relative to `cost_regularization.` (models/mvsnet.py:35-62)
@@ -268,22 +325,40 @@ def pack_weights(state: dict, eps: float = 1e-5) -> torch.Tensor:
 def relative_proj(proj: torch.Tensor) -> torch.Tensor:
     """proj [N,4,4] cuda -> rt [(N-1),12] cuda (models/module.py:107-109)."""
     proj = _dev_f32(proj, "proj_matrices")
+    if proj.dim() != 3 or tuple(proj.shape[1:]) != (4, 4):
+        raise RuntimeError(f"proj_matrices must be [N,4,4], got {list(proj.shape)}")
     N = proj.shape[0]
-    rt = torch.empty((max(N - 1, 1), 12), dtype=torch.float32, device=proj.device)
-    check(load().mvs_relative_proj(proj.data_ptr(), rt.data_ptr(), N, _stream(proj.device)))
+    _aligned16("relative_proj", proj_matrices=proj)
+    with torch.cuda.device(proj.device):
+        rt = torch.empty((max(N - 1, 1), 12), dtype=torch.float32, device=proj.device)
+        check(load().mvs_relative_proj(proj.data_ptr(), rt.data_ptr(), N, _stream(proj.device)))
     return rt
+
+
+def _depth_values_arg(depth_values, device, who, D=None):
+    """depth_values [D] on `device` (D given: exactly that many)."""
+    if isinstance(depth_values, torch.Tensor) and depth_values.dim() != 1:
+        raise RuntimeError(f"{who}: depth_values must be [D], got {list(depth_values.shape)}")
+    return _dev_in(depth_values, f"{who}: depth_values", shape=None if D is None else (D,), device=device)
 
 
 def warp_variance(feats, rt, depth_values, workspace, dtype=MVS_F32):
     """feats [N,32,h,w], rt [(N-1),12], depth_values [D] -> C8-planar volume [4,D,h,w,8]."""
     feats = _dev_f32(feats, "features")
+    if feats.dim() != 4 or feats.shape[1] % 8:
+        raise RuntimeError(f"warp_variance: features must be [N,C,h,w] with 8 | C, got {list(feats.shape)}")
     N, C, h, w = feats.shape
+    dev = feats.device
+    rt = _rt_arg(rt, N, dev, "warp_variance")
+    depth_values = _depth_values_arg(depth_values, dev, "warp_variance")
     D = depth_values.shape[0]
-    var = torch.empty((C // 8, D, h, w, 8), dtype=TORCH_DTYPES[dtype], device=feats.device)
-    check(load().mvs_warp_variance(feats.data_ptr(), rt.data_ptr(),
-                                   _dev_f32(depth_values, "depth_values").data_ptr(),
-                                   var.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                   N, C, D, h, w, dtype, _stream(feats.device)))
+    _check_workspace(workspace, dev, "warp_variance")
+    _aligned16("warp_variance", rt=rt, depth_values=depth_values)
+    with torch.cuda.device(dev):
+        var = torch.empty((C // 8, D, h, w, 8), dtype=TORCH_DTYPES[dtype], device=dev)
+        check(load().mvs_warp_variance(feats.data_ptr(), None if rt is None else rt.data_ptr(), depth_values.data_ptr(),
+                                       var.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                       N, C, D, h, w, dtype, _stream(dev)))
     return var
 
 
@@ -291,24 +366,36 @@ def costreg_forward(var, blob, workspace, dtype=MVS_F32):
     """var [4,D,h,w,8] (C8-planar) -> cost logits [D,h,w] fp32."""
     if var.dtype != TORCH_DTYPES[dtype] or not var.is_cuda or not var.is_contiguous():
         raise RuntimeError(f"variance volume must be a contiguous CUDA tensor of {TORCH_DTYPES[dtype]}")
+    if var.dim() != 5 or var.shape[0] != 4 or var.shape[4] != 8 or var.numel() == 0:
+        raise RuntimeError(f"costreg_forward: the variance volume must be C8-planar [4,D,h,w,8], got {list(var.shape)}")
     _, D, h, w, _ = var.shape
-    cost = torch.empty((D, h, w), dtype=torch.float32, device=var.device)
-    check(load().mvs_costreg_forward(var.data_ptr(), blob.data_ptr(), cost.data_ptr(),
-                                     workspace.data_ptr(), workspace.numel(), D, h, w, dtype,
-                                     _stream(var.device)))
+    _check_blob(blob, "weights", var.device, "costreg_forward")
+    _check_workspace(workspace, var.device, "costreg_forward")
+    _aligned16("costreg_forward", var=var)
+    with torch.cuda.device(var.device):
+        cost = torch.empty((D, h, w), dtype=torch.float32, device=var.device)
+        check(load().mvs_costreg_forward(var.data_ptr(), blob.data_ptr(), cost.data_ptr(),
+                                         workspace.data_ptr(), workspace.numel(), D, h, w, dtype,
+                                         _stream(var.device)))
     return cost
 
 
 def conv_layer(layer, x, skip, blob, dtype=MVS_F32):
     """One CostRegNet layer on C8-planar tensors [Cin/8,D,h,w,8] -> [Cout/8,D',h',w',8]."""
     ci, co = _LAYER_CH[layer]
+    if not isinstance(x, torch.Tensor) or x.dim() != 5 or x.numel() == 0:
+        raise RuntimeError(f"layer {layer}: input must be a C8-planar [Cin/8,D,h,w,8] tensor")
     planes, Di, Hi, Wi, c8 = x.shape
     if planes * c8 != ci or c8 != 8:
         raise RuntimeError(f"layer {layer}: input has {planes}x{c8} channels, expected {ci}")
     if x.dtype != TORCH_DTYPES[dtype] or (skip is not None and skip.dtype != TORCH_DTYPES[dtype]):
         raise RuntimeError(f"layer {layer}: tensors are {x.dtype}, storage dtype says {TORCH_DTYPES[dtype]}")
-    if not x.is_cuda or not x.is_contiguous() or (skip is not None and not skip.is_contiguous()):
+    if not x.is_cuda or not x.is_contiguous() or (skip is not None and not (skip.is_cuda and skip.is_contiguous())):
         raise RuntimeError(f"layer {layer}: needs contiguous CUDA(ROCm) tensors")
+    if skip is not None and skip.device != x.device:
+        raise RuntimeError(f"layer {layer}: x and skip must be on one device")
+    _check_blob(blob, "weights", x.device, f"layer {layer}")
+    _aligned16(f"layer {layer}", x=x, skip=skip)
     if 7 <= layer <= 9:
         odims = (2 * Di, 2 * Hi, 2 * Wi)
     elif layer in (1, 3, 5):
@@ -316,18 +403,21 @@ def conv_layer(layer, x, skip, blob, dtype=MVS_F32):
     else:
         odims = (Di, Hi, Wi)
     oshape = odims if layer == 10 else (co // 8,) + odims + (8,)
-    y = torch.empty(oshape, dtype=torch.float32 if layer == 10 else TORCH_DTYPES[dtype], device=x.device)
     if skip is not None and tuple(skip.shape) != tuple(oshape):
         raise RuntimeError(f"layer {layer}: skip shape {tuple(skip.shape)} != {oshape}")
-    check(load().mvs_conv_layer(layer, x.data_ptr(), 0 if skip is None else skip.data_ptr(),
-                                y.data_ptr(), blob.data_ptr(), Di, Hi, Wi, dtype,
-                                _stream(x.device)))
+    with torch.cuda.device(x.device):
+        y = torch.empty(oshape, dtype=torch.float32 if layer == 10 else TORCH_DTYPES[dtype], device=x.device)
+        check(load().mvs_conv_layer(layer, x.data_ptr(), 0 if skip is None else skip.data_ptr(),
+                                    y.data_ptr(), blob.data_ptr(), Di, Hi, Wi, dtype,
+                                    _stream(x.device)))
     return y
 
 
 def conv11_prob(x, skip, blob, dtype=MVS_F32):
     """Layers 9 + 10 in one kernel: x [2,Di,Hi,Wi,8], skip [1,2Di,2Hi,2Wi,8] (storage dtype) -> fp32 cost logits
     [2Di,2Hi,2Wi]."""
+    if not isinstance(x, torch.Tensor) or not isinstance(skip, torch.Tensor) or x.dim() != 5 or x.numel() == 0:
+        raise RuntimeError("conv11_prob: x and skip must be C8-planar tensors")
     planes, Di, Hi, Wi, c8 = x.shape
     if planes != 2 or c8 != 8 or tuple(skip.shape) != (1, 2 * Di, 2 * Hi, 2 * Wi, 8):
         raise RuntimeError(f"conv11_prob: shapes {tuple(x.shape)} / {tuple(skip.shape)}")
@@ -335,21 +425,33 @@ def conv11_prob(x, skip, blob, dtype=MVS_F32):
         raise RuntimeError(f"conv11_prob: tensors must be {TORCH_DTYPES[dtype]}")
     if not (x.is_cuda and skip.is_cuda and x.is_contiguous() and skip.is_contiguous()):
         raise RuntimeError("conv11_prob: needs contiguous CUDA(ROCm) tensors")
-    cost = torch.empty((2 * Di, 2 * Hi, 2 * Wi), dtype=torch.float32, device=x.device)
-    check(load().mvs_conv11_prob(x.data_ptr(), skip.data_ptr(), cost.data_ptr(), blob.data_ptr(), Di, Hi, Wi,
-                                 dtype, _stream(x.device)))
+    if skip.device != x.device:
+        raise RuntimeError("conv11_prob: x and skip must be on one device")
+    _check_blob(blob, "weights", x.device, "conv11_prob")
+    _aligned16("conv11_prob", x=x, skip=skip)
+    with torch.cuda.device(x.device):
+        cost = torch.empty((2 * Di, 2 * Hi, 2 * Wi), dtype=torch.float32, device=x.device)
+        check(load().mvs_conv11_prob(x.data_ptr(), skip.data_ptr(), cost.data_ptr(), blob.data_ptr(), Di, Hi, Wi,
+                                     dtype, _stream(x.device)))
+    return cost
+
+
+def _cost_arg(cost, who):
+    cost = _dev_f32(cost, "cost")
+    if cost.dim() != 3:
+        raise RuntimeError(f"{who}: cost must be [D,h,w], got {list(cost.shape)}")
     return cost
 
 
 def softargmin_conf(cost, depth_values):
-    cost = _dev_f32(cost, "cost")
+    cost = _cost_arg(cost, "softargmin_conf")
     D, h, w = cost.shape
-    depth = torch.empty((h, w), dtype=torch.float32, device=cost.device)
-    conf = torch.empty_like(depth)
-    check(load().mvs_softargmin_conf(cost.data_ptr(),
-                                     _dev_f32(depth_values, "depth_values").data_ptr(),
-                                     depth.data_ptr(), conf.data_ptr(), D, h, w,
-                                     _stream(cost.device)))
+    depth_values = _depth_values_arg(depth_values, cost.device, "softargmin_conf", D)
+    with torch.cuda.device(cost.device):
+        depth = torch.empty((h, w), dtype=torch.float32, device=cost.device)
+        conf = torch.empty_like(depth)
+        check(load().mvs_softargmin_conf(cost.data_ptr(), depth_values.data_ptr(), depth.data_ptr(), conf.data_ptr(),
+                                         D, h, w, _stream(cost.device)))
     return depth, conf
 
 
@@ -357,32 +459,37 @@ def warp_variance_backward(feats, rt, depth_values, grad_var, out=None):
     """Adjoint of warp_variance (fp32): feats [N,32,h,w], rt [(N-1),12], depth_values [D], grad_var [32,D,h,w]
     (NCDHW) -> grad_feats [N,32,h,w] (into `out` when given).  Enqueued on the current stream."""
     feats = _dev_f32(feats, "features")
-    grad_var = _dev_f32(grad_var, "grad_var")
+    if feats.dim() != 4:
+        raise RuntimeError(f"warp_variance_backward: features must be [N,C,h,w], got {list(feats.shape)}")
     N, C, h, w = feats.shape
+    dev = feats.device
+    depth_values = _depth_values_arg(depth_values, dev, "warp_variance_backward")
     D = depth_values.shape[0]
-    if tuple(grad_var.shape) != (C, D, h, w):
-        raise RuntimeError(f"grad_var {tuple(grad_var.shape)} must be [{C},{D},{h},{w}]")
-    if out is None:
-        out = torch.empty_like(feats)
-    else:
-        _check_out(out, feats.shape, torch.float32, feats.device, "warp_variance_backward: out",
-                   "float32 tensor shaped like feats")
-    check(load().mvs_warp_variance_backward(feats.data_ptr(), _dev_f32(rt, "rt").data_ptr(),
-                                            _dev_f32(depth_values, "depth_values").data_ptr(), grad_var.data_ptr(),
-                                            out.data_ptr(), N, C, D, h, w, _stream(feats.device)))
+    grad_var = _dev_in(grad_var, "grad_var", shape=(C, D, h, w), device=dev)
+    rt = _rt_arg(rt, N, dev, "warp_variance_backward")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty_like(feats)
+        else:
+            _check_out(out, feats.shape, torch.float32, dev, "warp_variance_backward: out",
+                       "float32 tensor shaped like feats")
+        _aligned16("warp_variance_backward", features=feats, rt=rt, depth_values=depth_values, grad_var=grad_var, out=out)
+        check(load().mvs_warp_variance_backward(feats.data_ptr(), None if rt is None else rt.data_ptr(),
+                                                depth_values.data_ptr(), grad_var.data_ptr(), out.data_ptr(),
+                                                N, C, D, h, w, _stream(dev)))
     return out
 
 
 def softargmin_backward(cost, depth_values, grad_depth):
     """Adjoint of softargmin_conf's depth: cost [D,h,w], depth_values [D], grad_depth [h,w] -> grad_cost [D,h,w]."""
-    cost = _dev_f32(cost, "cost")
+    cost = _cost_arg(cost, "softargmin_backward")
     D, h, w = cost.shape
-    grad_depth = _dev_f32(grad_depth, "grad_depth")
-    if tuple(grad_depth.shape) != (h, w):
-        raise RuntimeError(f"grad_depth {tuple(grad_depth.shape)} must be [{h},{w}]")
-    gc = torch.empty_like(cost)
-    check(load().mvs_softargmin_backward(cost.data_ptr(), _dev_f32(depth_values, "depth_values").data_ptr(),
-                                         grad_depth.data_ptr(), gc.data_ptr(), D, h, w, _stream(cost.device)))
+    grad_depth = _dev_in(grad_depth, "grad_depth", shape=(h, w), device=cost.device)
+    depth_values = _depth_values_arg(depth_values, cost.device, "softargmin_backward", D)
+    with torch.cuda.device(cost.device):
+        gc = torch.empty_like(cost)
+        check(load().mvs_softargmin_backward(cost.data_ptr(), depth_values.data_ptr(), grad_depth.data_ptr(),
+                                             gc.data_ptr(), D, h, w, _stream(cost.device)))
     return gc
 
 
@@ -399,33 +506,48 @@ def _cl_volume(t, name):
     return t
 
 
+def _check_stride(dims, stride, who):
+    """The library takes D, H, W of the full-resolution side and an int stride: dims the stride does not divide would be
+    floored here and the kernel would then read or write a volume the caller does not have."""
+    if stride not in (1, 2):
+        raise RuntimeError(f"{who}: stride {stride!r} (1 or 2)")
+    if any(d % stride for d in dims):      # the library's words for it
+        raise RuntimeError(f"{who}: stride 2 needs even D,H,W (got {','.join(str(d) for d in dims)})")
+
+
 def conv3d_train_forward(x, w, bias, stride, flip_transpose=False):
     """x [D,H,W,Cin], w [Cout,Cin,3,3,3] ([Cin,Cout,3,3,3] with flip_transpose) -> y [D/s,H/s,W/s,Cout]."""
-    x, w = _cl_volume(x, "x"), _dev_f32(w, "weight")
+    x = _cl_volume(x, "x")
+    w = _dev_in(w, "weight", device=x.device)
     D, H, W, Cin = x.shape
-    Cout = w.shape[1] if flip_transpose else w.shape[0]
     if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3) or (w.shape[0] if flip_transpose else w.shape[1]) != Cin:
         raise RuntimeError(f"weight {tuple(w.shape)} does not fit a 3x3x3 convolution of {Cin} channels")
+    Cout = w.shape[1] if flip_transpose else w.shape[0]
+    _check_stride((D, H, W), stride, "conv3d_train_forward")
     if bias is not None:
-        bias = _dev_f32(bias, "bias")
-    y = torch.empty((D // stride, H // stride, W // stride, Cout), dtype=torch.float32, device=x.device)
-    check(load().mvs_conv3d_train_forward(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
-                                          y.data_ptr(), Cin, Cout, D, H, W, stride, int(bool(flip_transpose)),
-                                          _stream(x.device)))
+        bias = _dev_in(bias, "bias", shape=(Cout,), device=x.device)
+    with torch.cuda.device(x.device):
+        y = torch.empty((D // stride, H // stride, W // stride, Cout), dtype=torch.float32, device=x.device)
+        check(load().mvs_conv3d_train_forward(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
+                                              y.data_ptr(), Cin, Cout, D, H, W, stride, int(bool(flip_transpose)),
+                                              _stream(x.device)))
     return y
 
 
 def conv3d_train_backward_data(gy, w, stride):
     """gy [D/s,H/s,W/s,Cout], w [Cout,Cin,3,3,3] -> gx [D,H,W,Cin] (every voxel written)."""
-    gy, w = _cl_volume(gy, "gy"), _dev_f32(w, "weight")
+    gy = _cl_volume(gy, "gy")
+    w = _dev_in(w, "weight", device=gy.device)
     Do, Ho, Wo, Cout = gy.shape
     if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3) or w.shape[0] != Cout:
         raise RuntimeError(f"weight {tuple(w.shape)} does not fit a gradient of {Cout} channels")
     Cin = w.shape[1]
+    _check_stride((), stride, "conv3d_train_backward_data")
     D, H, W = Do * stride, Ho * stride, Wo * stride
-    gx = torch.empty((D, H, W, Cin), dtype=torch.float32, device=gy.device)
-    check(load().mvs_conv3d_train_backward_data(gy.data_ptr(), w.data_ptr(), gx.data_ptr(), Cin, Cout, D, H, W,
-                                                stride, _stream(gy.device)))
+    with torch.cuda.device(gy.device):
+        gx = torch.empty((D, H, W, Cin), dtype=torch.float32, device=gy.device)
+        check(load().mvs_conv3d_train_backward_data(gy.data_ptr(), w.data_ptr(), gx.data_ptr(), Cin, Cout, D, H, W,
+                                                    stride, _stream(gy.device)))
     return gx
 
 
@@ -434,14 +556,19 @@ def conv3d_train_backward_weight(x, gy, stride, with_bias=False):
     x, gy = _cl_volume(x, "x"), _cl_volume(gy, "gy")
     D, H, W, Cin = x.shape
     Cout = gy.shape[3]
+    _check_stride((D, H, W), stride, "conv3d_train_backward_weight")
     if tuple(gy.shape[:3]) != (D // stride, H // stride, W // stride):
         raise RuntimeError(f"gy {tuple(gy.shape)} does not fit x {tuple(x.shape)} at stride {stride}")
-    ws = torch.empty(conv3d_train_workspace_bytes(Cin, Cout, D, H, W, stride), dtype=torch.uint8, device=x.device)
-    gw = torch.empty((Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    gb = torch.empty((Cout,), dtype=torch.float32, device=x.device) if with_bias else None
-    check(load().mvs_conv3d_train_backward_weight(x.data_ptr(), gy.data_ptr(), gw.data_ptr(),
-                                                  None if gb is None else gb.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                  Cin, Cout, D, H, W, stride, _stream(x.device)))
+    if gy.device != x.device:
+        raise RuntimeError("conv3d_train_backward_weight: x and gy must be on one device")
+    nbytes = conv3d_train_workspace_bytes(Cin, Cout, D, H, W, stride)
+    with torch.cuda.device(x.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        gw = torch.empty((Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+        gb = torch.empty((Cout,), dtype=torch.float32, device=x.device) if with_bias else None
+        check(load().mvs_conv3d_train_backward_weight(x.data_ptr(), gy.data_ptr(), gw.data_ptr(),
+                                                      None if gb is None else gb.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      Cin, Cout, D, H, W, stride, _stream(x.device)))
     return (gw, gb) if with_bias else gw
 
 
@@ -457,10 +584,12 @@ def _cl_rows(t, name):
     return t
 
 
-def _channel_vector(t, C, name):
+def _channel_vector(t, C, name, device=None):
     t = _dev_f32(t, name)
     if tuple(t.shape) != (C,):
         raise RuntimeError(f"{name} {tuple(t.shape)} must be [{C}]")
+    if device is not None and t.device != device:
+        raise RuntimeError(f"{name} is on {t.device}, not on {device}: the tensors of one call must be on one device")
     return t
 
 
@@ -470,27 +599,32 @@ def bn3d_train_forward(y, gamma, beta, skip=None, running_mean=None, running_var
     skip with batch statistics.  running_mean / running_var [C] (both or neither) are updated in place."""
     y = _cl_rows(y, "y")
     M, C = y.shape
-    gamma, beta = _channel_vector(gamma, C, "gamma"), _channel_vector(beta, C, "beta")
+    dev = y.device
+    gamma, beta = _channel_vector(gamma, C, "gamma", dev), _channel_vector(beta, C, "beta", dev)
     if skip is not None:
         skip = _cl_rows(skip, "skip")
-        if skip.shape != y.shape:
-            raise RuntimeError(f"skip {tuple(skip.shape)} must be shaped like y {tuple(y.shape)}")
+        if skip.shape != y.shape or skip.device != dev:
+            raise RuntimeError(f"skip {tuple(skip.shape)} must be shaped like y {tuple(y.shape)} and on its device")
     if (running_mean is None) != (running_var is None):
         raise RuntimeError("running_mean and running_var must both be given or both be None")
     if running_mean is not None:
         for t, name in ((running_mean, "running_mean"), (running_var, "running_var")):
-            if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (C,) or not t.is_contiguous():
-                raise RuntimeError(f"{name} must be a contiguous float32 CUDA tensor [{C}] (it is updated in place)")
-    ws = torch.empty(bn3d_train_workspace_bytes(C, M), dtype=torch.uint8, device=y.device)
-    out = torch.empty_like(y)
-    mean = torch.empty((C,), dtype=torch.float32, device=y.device)
-    invstd = torch.empty_like(mean)
-    check(load().mvs_bn3d_train_forward(y.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                        None if skip is None else skip.data_ptr(), out.data_ptr(), mean.data_ptr(),
-                                        invstd.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
-                                        None if running_var is None else running_var.data_ptr(), float(momentum),
-                                        float(eps), int(bool(relu)), C, M, ws.data_ptr(), ws.numel(),
-                                        _stream(y.device)))
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (C,) \
+                    or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError(f"{name} must be a contiguous float32 CUDA tensor [{C}] on y's device (it is updated in "
+                                   "place)")
+    nbytes = bn3d_train_workspace_bytes(C, M)
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty_like(y)
+        mean = torch.empty((C,), dtype=torch.float32, device=dev)
+        invstd = torch.empty_like(mean)
+        check(load().mvs_bn3d_train_forward(y.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                            None if skip is None else skip.data_ptr(), out.data_ptr(), mean.data_ptr(),
+                                            invstd.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
+                                            None if running_var is None else running_var.data_ptr(), float(momentum),
+                                            float(eps), int(bool(relu)), C, M, ws.data_ptr(), ws.numel(),
+                                            _stream(dev)))
     return out, mean, invstd
 
 
@@ -499,17 +633,20 @@ def bn3d_train_backward(y, grad_out, gamma, beta, save_mean, save_invstd, relu=T
     grad_out is the gradient of relu(bn(y)) (+ skip: the skip's own gradient is grad_out itself)."""
     y, grad_out = _cl_rows(y, "y"), _cl_rows(grad_out, "grad_out")
     M, C = y.shape
-    if grad_out.shape != y.shape:
-        raise RuntimeError(f"grad_out {tuple(grad_out.shape)} must be shaped like y {tuple(y.shape)}")
-    vec = [_channel_vector(t, C, n) for t, n in ((gamma, "gamma"), (beta, "beta"), (save_mean, "save_mean"),
-                                                 (save_invstd, "save_invstd"))]
-    ws = torch.empty(bn3d_train_workspace_bytes(C, M), dtype=torch.uint8, device=y.device)
-    gy = torch.empty_like(y)
-    gg = torch.empty((C,), dtype=torch.float32, device=y.device)
-    gb = torch.empty_like(gg)
-    check(load().mvs_bn3d_train_backward(y.data_ptr(), grad_out.data_ptr(), *[t.data_ptr() for t in vec],
-                                         gy.data_ptr(), gg.data_ptr(), gb.data_ptr(), int(bool(relu)), C, M,
-                                         ws.data_ptr(), ws.numel(), _stream(y.device)))
+    dev = y.device
+    if grad_out.shape != y.shape or grad_out.device != dev:
+        raise RuntimeError(f"grad_out {tuple(grad_out.shape)} must be shaped like y {tuple(y.shape)} and on its device")
+    vec = [_channel_vector(t, C, n, dev) for t, n in ((gamma, "gamma"), (beta, "beta"), (save_mean, "save_mean"),
+                                                      (save_invstd, "save_invstd"))]
+    nbytes = bn3d_train_workspace_bytes(C, M)
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        gy = torch.empty_like(y)
+        gg = torch.empty((C,), dtype=torch.float32, device=dev)
+        gb = torch.empty_like(gg)
+        check(load().mvs_bn3d_train_backward(y.data_ptr(), grad_out.data_ptr(), *[t.data_ptr() for t in vec],
+                                             gy.data_ptr(), gg.data_ptr(), gb.data_ptr(), int(bool(relu)), C, M,
+                                             ws.data_ptr(), ws.numel(), _stream(dev)))
     return gy, gg, gb
 
 
@@ -532,23 +669,58 @@ def volume_relayout(src, direction, out=None):
         oshape = (C,) + dims
     else:
         raise RuntimeError(f"volume_relayout: direction {direction!r} (0 or 1)")
-    if out is None:
-        out = torch.empty(oshape, dtype=torch.float32, device=src.device)
-    else:
-        _check_out(out, oshape, torch.float32, src.device, "volume_relayout: out", f"float32 tensor {oshape}")
-    check(load().mvs_volume_relayout(src.data_ptr(), out.data_ptr(), C, dims[0] * dims[1] * dims[2], direction,
-                                     _stream(src.device)))
+    with torch.cuda.device(src.device):
+        if out is None:
+            out = torch.empty(oshape, dtype=torch.float32, device=src.device)
+        else:
+            _check_out(out, oshape, torch.float32, src.device, "volume_relayout: out", f"float32 tensor {oshape}")
+        check(load().mvs_volume_relayout(src.data_ptr(), out.data_ptr(), C, dims[0] * dims[1] * dims[2], direction,
+                                         _stream(src.device)))
     return out
+
+
+def _depth_call_args(who, dev, N, h, w, proj, depth_values, blob, workspace, depth_out, conf_out, fblob=None):
+    """What depth_infer, depth_infer_views and forward_images check alike, on the device `dev` of their first tensor:
+    proj [N,4,4] and depth_values [D] (returned contiguous), the blob(s), the workspace and the two [h,w] outputs."""
+    proj = _dev_in(proj, f"{who}: proj_matrices", shape=(N, 4, 4), device=dev)
+    depth_values = _depth_values_arg(depth_values, dev, who)
+    if fblob is not None:
+        _check_blob(fblob, "feature", dev, who)
+    _check_blob(blob, "weights", dev, who)
+    _check_workspace(workspace, dev, who)
+    _check_out(depth_out, (h, w), torch.float32, dev, f"{who}: depth_out", f"float32 [{h},{w}] tensor on {dev}")
+    _check_out(conf_out, (h, w), torch.float32, dev, f"{who}: conf_out", f"float32 [{h},{w}] tensor on {dev}")
+    _aligned16(who, proj_matrices=proj, depth_values=depth_values)
+    return proj, depth_values
+
+
+_workspace_bytes = {}      # (N, C, D, h, w, dtype) -> mvs_query_workspace's answer
 
 
 def depth_infer(feats, proj, depth_values, blob, workspace, depth_out, conf_out, dtype=MVS_F32):
     """Whole path for one batch item; outputs are written into depth_out / conf_out [h,w]."""
+    feats = _dev_f32(feats, "features")
+    if feats.dim() != 4:
+        raise RuntimeError(f"depth_infer: feats must be [N,C,h,w], got {list(feats.shape)}")
     N, C, h, w = feats.shape
+    dev = feats.device
+    depth_values = _depth_values_arg(depth_values, dev, "depth_infer")
     D = depth_values.shape[0]
-    check(load().mvs_depth_infer(feats.data_ptr(), proj.data_ptr(), depth_values.data_ptr(),
-                                 blob.data_ptr(), depth_out.data_ptr(), conf_out.data_ptr(),
-                                 workspace.data_ptr(), workspace.numel(), N, C, D, h, w, dtype,
-                                 _stream(feats.device)))
+    # the library's own answers first, with its status: the shape domain (1, 2), then a workspace that is too small (3)
+    key = (N, C, D, h, w, dtype)
+    need = _workspace_bytes.get(key)
+    if need is None:      # a refusal raises and is asked again next time; an answer is kept: one dict lookup per map
+        need = _workspace_bytes[key] = query_workspace(*key)
+    _check_workspace(workspace, dev, "depth_infer")
+    if workspace.numel() < need:
+        raise MvsError(3, f"workspace needs >= {need} bytes, got {workspace.numel()}")
+    proj, depth_values = _depth_call_args("depth_infer", dev, N, h, w, proj, depth_values, blob, workspace, depth_out,
+                                          conf_out)
+    with torch.cuda.device(dev):
+        check(load().mvs_depth_infer(feats.data_ptr(), proj.data_ptr(), depth_values.data_ptr(),
+                                     blob.data_ptr(), depth_out.data_ptr(), conf_out.data_ptr(),
+                                     workspace.data_ptr(), workspace.numel(), N, C, D, h, w, dtype,
+                                     _stream(dev)))
 
 
 def _view_ids_arg(view_ids):
@@ -589,15 +761,15 @@ def depth_infer_views(feats, view_ids, proj, depth_values, blob, workspace, dept
             raise RuntimeError(f"depth_infer_views: {name} must be a contiguous float32 [{h},{w}] tensor, "
                                f"got {t.dtype} {tuple(t.shape)}")
     feats = _dev_f32(feats, "features")
-    proj = _dev_f32(proj, "proj_matrices")
-    depth_values = _dev_f32(depth_values, "depth_values")
-    if not (depth_out.is_cuda and conf_out.is_cuda and workspace.is_cuda):
-        raise RuntimeError("depth_infer_views: outputs and workspace must live on the GPU")
+    dev = feats.device
+    proj, depth_values = _depth_call_args("depth_infer_views", dev, N, h, w, proj, depth_values, blob, workspace,
+                                          depth_out, conf_out)
     D = depth_values.shape[0]
-    check(load().mvs_depth_infer_views(feats.data_ptr(), V, ids.ctypes.data, proj.data_ptr(), depth_values.data_ptr(),
-                                       blob.data_ptr(), depth_out.data_ptr(), conf_out.data_ptr(),
-                                       workspace.data_ptr(), workspace.numel(), N, C, D, h, w, dtype,
-                                       _stream(feats.device)))
+    with torch.cuda.device(dev):
+        check(load().mvs_depth_infer_views(feats.data_ptr(), V, ids.ctypes.data, proj.data_ptr(), depth_values.data_ptr(),
+                                           blob.data_ptr(), depth_out.data_ptr(), conf_out.data_ptr(),
+                                           workspace.data_ptr(), workspace.numel(), N, C, D, h, w, dtype,
+                                           _stream(dev)))
 
 
 def alloc_workspace(N, C, D, h, w, device, dtype=MVS_F32) -> torch.Tensor:
@@ -654,20 +826,25 @@ def filter_depth(depth, conf, ref_mats, pair_mats, ref_idx, src_idx, photomask=0
     pair_mats = _dev_f32(pair_mats, "pair_mats")
     if ref_idx.dtype != torch.int32 or src_idx.dtype != torch.int32 or not ref_idx.is_cuda or not src_idx.is_cuda:
         raise RuntimeError("filter_depth: ref_idx / src_idx must be int32 tensors on the GPU")
+    if any(t.device != dev for t in (conf, ref_mats, pair_mats, ref_idx, src_idx)):
+        raise RuntimeError("filter_depth: depth, conf, ref_mats, pair_mats, ref_idx and src_idx must be on one device")
+    if src_idx.dim() != 2:
+        raise RuntimeError(f"filter_depth: src_idx must be [R,S], got {list(src_idx.shape)}")
     R, S = src_idx.shape
     if tuple(ref_mats.shape) != (R, FILTER_REF_FLOATS) or tuple(pair_mats.shape) != (R, S, FILTER_PAIR_FLOATS) \
             or ref_idx.numel() != R:
         raise RuntimeError("filter_depth: ref_mats / pair_mats / ref_idx do not match src_idx's [R,S]")
     ref_idx, src_idx = ref_idx.contiguous(), src_idx.contiguous()
-    geo = torch.empty((R, h, w), dtype=torch.int32, device=dev)
-    avg = torch.empty((R, h, w), dtype=torch.float64, device=dev)
-    masks = torch.empty((R, 3, h, w), dtype=torch.uint8, device=dev)
-    xyz = torch.empty((R, h * w, 3), dtype=torch.float64, device=dev)
-    check(load().mvs_filter_depth(depth.data_ptr(), conf.data_ptr(), ref_mats.data_ptr(),
-                                  pair_mats.data_ptr(), ref_idx.data_ptr(), src_idx.data_ptr(),
-                                  V, R, S, h, w, float(photomask), int(geomask), float(condmask_pixel),
-                                  float(condmask_depth), geo.data_ptr(), avg.data_ptr(), masks.data_ptr(),
-                                  xyz.data_ptr(), _stream(dev)))
+    with torch.cuda.device(dev):
+        geo = torch.empty((R, h, w), dtype=torch.int32, device=dev)
+        avg = torch.empty((R, h, w), dtype=torch.float64, device=dev)
+        masks = torch.empty((R, 3, h, w), dtype=torch.uint8, device=dev)
+        xyz = torch.empty((R, h * w, 3), dtype=torch.float64, device=dev)
+        check(load().mvs_filter_depth(depth.data_ptr(), conf.data_ptr(), ref_mats.data_ptr(),
+                                      pair_mats.data_ptr(), ref_idx.data_ptr(), src_idx.data_ptr(),
+                                      V, R, S, h, w, float(photomask), int(geomask), float(condmask_pixel),
+                                      float(condmask_depth), geo.data_ptr(), avg.data_ptr(), masks.data_ptr(),
+                                      xyz.data_ptr(), _stream(dev)))
     return geo, avg, masks, xyz
 
 
@@ -1163,17 +1340,22 @@ def feature_layer(layer, x, fblob):
     x = _dev_f32(x, "x")
     ci, co, k, s = FEATURE_LAYERS[layer]
     if layer == 0:
-        N, c, H, W = x.shape
-        if c != 3:
+        if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"feature layer 0 wants [N,3,H,W] images, got {tuple(x.shape)}")
+        N, c, H, W = x.shape
     else:
+        if x.dim() != 5:
+            raise RuntimeError(f"feature layer {layer} wants C8-planar input with {ci} channels, got {tuple(x.shape)}")
         pl, N, H, W, e = x.shape
         if pl * e != ci or e != 8:
             raise RuntimeError(f"feature layer {layer} wants C8-planar input with {ci} channels, got {tuple(x.shape)}")
     Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
-    y = torch.empty((co // 8, N, Ho, Wo, 8), dtype=torch.float32, device=x.device)
-    check(load().mvs_feature_layer(layer, x.data_ptr(), y.data_ptr(), fblob.data_ptr(), N, H, W,
-                                   _stream(x.device)))
+    _check_blob(fblob, "feature", x.device, f"feature layer {layer}")
+    _aligned16(f"feature layer {layer}", x=x)
+    with torch.cuda.device(x.device):
+        y = torch.empty((co // 8, N, Ho, Wo, 8), dtype=torch.float32, device=x.device)
+        check(load().mvs_feature_layer(layer, x.data_ptr(), y.data_ptr(), fblob.data_ptr(), N, H, W,
+                                       _stream(x.device)))
     return y
 
 
@@ -1186,6 +1368,8 @@ def _image_arg(imgs, what):
         raise RuntimeError(f"{what}: images must be a CUDA(ROCm) tensor")
     if imgs.dim() != 4:
         raise RuntimeError(f"{what} wants [N,3,H,W] (float32 / uint8) or [N,H,W,3] (uint8) images, got {tuple(imgs.shape)}")
+    if imgs.numel() == 0:
+        raise RuntimeError(f"{what}: images are empty: {list(imgs.shape)}")
     if imgs.dtype == torch.uint8:
         imgs = imgs.contiguous()
         if imgs.shape[1] == 3:
@@ -1203,9 +1387,12 @@ def feature_conv01(imgs, fblob):
     """conv0 + conv1 of FeatureNet as the one fused kernel the net runs: imgs [N,3,H,W] fp32 (or uint8, see
     _image_arg) -> C8-planar [1,N,H,W,8].  For parity tests and per-kernel timing."""
     imgs, fmt, N, H, W = _image_arg(imgs, "feature_conv01")
-    y = torch.empty((1, N, H, W, 8), dtype=torch.float32, device=imgs.device)
-    check(load().mvs_feature_conv01_fmt(imgs.data_ptr(), fmt, y.data_ptr(), fblob.data_ptr(), N, H, W,
-                                        _stream(imgs.device)))
+    _check_blob(fblob, "feature", imgs.device, "feature_conv01")
+    _aligned16("feature_conv01", imgs=imgs)
+    with torch.cuda.device(imgs.device):
+        y = torch.empty((1, N, H, W, 8), dtype=torch.float32, device=imgs.device)
+        check(load().mvs_feature_conv01_fmt(imgs.data_ptr(), fmt, y.data_ptr(), fblob.data_ptr(), N, H, W,
+                                            _stream(imgs.device)))
     return y
 
 
@@ -1213,17 +1400,22 @@ def feature_net(imgs, fblob, workspace=None, out=None):
     """FeatureNet.forward on the GPU: imgs [N,3,H,W] fp32 (or uint8, see _image_arg) -> [N,32,H/4,W/4] fp32 (NCHW),
     written into `out` when given (a contiguous tensor of that shape)."""
     imgs, fmt, N, H, W = _image_arg(imgs, "feature_net")
-    nbytes = query_feature_workspace(N, H, W)
-    if workspace is None:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=imgs.device)
+    dev = imgs.device
+    _check_blob(fblob, "feature", dev, "feature_net")
     h4, w4 = ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1
-    if out is None:
-        out = torch.empty((N, 32, h4, w4), dtype=torch.float32, device=imgs.device)
-    else:
-        _check_out(out, (N, 32, h4, w4), torch.float32, imgs.device, "feature_net: out",
-                   f"float32 [{N},32,{h4},{w4}] tensor on {imgs.device}")
-    check(load().mvs_feature_net_fmt(imgs.data_ptr(), fmt, fblob.data_ptr(), out.data_ptr(), workspace.data_ptr(),
-                                     workspace.numel(), N, H, W, _stream(imgs.device)))
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = torch.empty(query_feature_workspace(N, H, W), dtype=torch.uint8, device=dev)
+        else:
+            _check_workspace(workspace, dev, "feature_net")
+        if out is None:
+            out = torch.empty((N, 32, h4, w4), dtype=torch.float32, device=dev)
+        else:
+            _check_out(out, (N, 32, h4, w4), torch.float32, dev, "feature_net: out",
+                       f"float32 [{N},32,{h4},{w4}] tensor on {dev}")
+        _aligned16("feature_net", imgs=imgs, out=out)
+        check(load().mvs_feature_net_fmt(imgs.data_ptr(), fmt, fblob.data_ptr(), out.data_ptr(), workspace.data_ptr(),
+                                         workspace.numel(), N, H, W, _stream(dev)))
     return out
 
 
@@ -1231,18 +1423,16 @@ def forward_images(imgs, proj, depth_values, fblob, blob, workspace, depth_out, 
     """MVSNet.forward of one batch item from images: imgs [N,3,H,W] fp32 (or uint8, see _image_arg), proj [N,4,4],
     depth_values [D]."""
     imgs, fmt, N, H, W = _image_arg(imgs, "forward_images")
-    proj = _dev_f32(proj, "proj_matrices")
-    depth_values = _dev_f32(depth_values, "depth_values")
-    if tuple(proj.shape) != (N, 4, 4):
-        raise RuntimeError(f"forward_images: imgs {tuple(imgs.shape)} / proj {tuple(proj.shape)}")
-    D = depth_values.numel()
-    if tuple(depth_out.shape) != (H // 4, W // 4) or tuple(conf_out.shape) != (H // 4, W // 4) \
-            or not depth_out.is_contiguous() or not conf_out.is_contiguous():
-        raise RuntimeError("forward_images: depth_out / conf_out must be contiguous [H/4, W/4] float32")
-    check(load().mvs_forward_images_fmt(imgs.data_ptr(), fmt, proj.data_ptr(), depth_values.data_ptr(),
-                                        fblob.data_ptr(), blob.data_ptr(), depth_out.data_ptr(),
-                                        conf_out.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                        N, H, W, D, dtype, _stream(imgs.device)))
+    dev = imgs.device
+    _aligned16("forward_images", imgs=imgs)
+    proj, depth_values = _depth_call_args("forward_images", dev, N, H // 4, W // 4, proj, depth_values, blob, workspace,
+                                          depth_out, conf_out, fblob=fblob)
+    D = depth_values.shape[0]
+    with torch.cuda.device(dev):
+        check(load().mvs_forward_images_fmt(imgs.data_ptr(), fmt, proj.data_ptr(), depth_values.data_ptr(),
+                                            fblob.data_ptr(), blob.data_ptr(), depth_out.data_ptr(),
+                                            conf_out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                            N, H, W, D, dtype, _stream(dev)))
 
 
 # ---- depth error against ground truth (reference train.py:302-358) ---------------------------
@@ -1288,7 +1478,9 @@ def depth_metrics(depth_est, depth_gt, mask, thresholds=(1.0, 2.0, 4.0, 8.0), su
     err = torch.empty((B, h, w), dtype=torch.float32, device=dev) if errmap else None
     with torch.cuda.device(dev):
         nbytes = query_metrics_workspace(B, h, w)
-        if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        if workspace is not None and isinstance(workspace, torch.Tensor) and workspace.device == dev:
+            _check_workspace(workspace, dev, "depth_metrics", align=8)
+        if workspace is None or workspace.numel() < nbytes or workspace.device != dev:      # replaced, not refused
             workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         check(load().mvs_depth_metrics(est.data_ptr(), gt.data_ptr(), mask.data_ptr(), B, h, w,
                                        th.ctypes.data if th.size else None, int(th.size), sums_out.data_ptr(),

@@ -24,6 +24,22 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// The alignment rule of include/mvs_abi.h: the kernels read and write public tensors 16 bytes at a time where their
+// shapes allow it (float4 / f32x4 loads, 16-byte LDS-staged epilogues) and read the blobs with uniform loads, which drop
+// low address bits.  The pointers named in the calls below are the ones the compiled kernels touch wider than an element,
+// or whose uniform reads the compiler is free to merge; include/mvs_abi.h says which is which, per entry point.  A data
+// pointer gives MVS_ERR_BAD_SHAPE, a blob MVS_ERR_WORKSPACE, on the host, before anything is enqueued.
+// NULL passes: whether a pointer may be NULL is the caller's own check.
+int check_align16(const char* who, std::initializer_list<NamedPtr> data, std::initializer_list<NamedPtr> blobs) {
+    for (const NamedPtr& q : data)
+        if (reinterpret_cast<uintptr_t>(q.p) & 15)
+            return fail(MVS_ERR_BAD_SHAPE, "%s: %s at %p must be 16-byte aligned", who, q.name, q.p);
+    for (const NamedPtr& q : blobs)
+        if (reinterpret_cast<uintptr_t>(q.p) & 15)
+            return fail(MVS_ERR_WORKSPACE, "%s: %s at %p must be 16-byte aligned", who, q.name, q.p);
+    return MVS_OK;
+}
+
 int check_hip(hipError_t e, const char* what) {
     if (e == hipSuccess) return MVS_OK;
     return fail(MVS_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -195,6 +211,7 @@ int mvs_pack_weights(const float* const* conv_weights, const float* const* bn_pa
 int mvs_relative_proj(const float* proj, float* rt_out, int N, void* stream) {
     if (!proj || !rt_out) return fail(MVS_ERR_NULL, "mvs_relative_proj: NULL argument");
     if (N < 1 || N > 64) return fail(MVS_ERR_BAD_SHAPE, "N=%d outside [1,64]", N);
+    if (int st = check_align16("mvs_relative_proj", {{"proj", proj}, {"rt_out", rt_out}}, {})) return st;
     if (N == 1) return MVS_OK;
     return launch_relative_proj(proj, rt_out, N, static_cast<hipStream_t>(stream));
 }
@@ -232,6 +249,9 @@ int mvs_warp_variance(const float* feats, const float* rt, const float* depth_va
                       void* var_out, void* workspace, size_t workspace_bytes, int N, int C, int D,
                       int h, int w, int dtype, void* stream) {
     if (!feats) return fail(MVS_ERR_NULL, "mvs_warp_variance: NULL argument");
+    if (int st = check_dims(N, C, D, h, w, dtype)) return st;
+    if (int st = check_align16("mvs_warp_variance", {{"rt", rt}, {"depth_values", depth_values}, {"var_out", var_out}}, {}))
+        return st;
     return warp_variance_impl(feats, identity_views(N), rt, depth_values, var_out, workspace, workspace_bytes, N, C,
                               D, h, w, dtype, stream);
 }
@@ -278,6 +298,9 @@ int mvs_costreg_forward(const void* var, const void* weights_blob, float* cost_o
                         void* workspace, size_t workspace_bytes, int D, int h, int w, int dtype,
                         void* stream) {
     if (!var) return fail(MVS_ERR_NULL, "mvs_costreg_forward: NULL argument");
+    if (int st = check_dims(1, kC, D, h, w, dtype)) return st;
+    if (int st = check_align16("mvs_costreg_forward", {{"var", var}, {"cost_out", cost_out}}, {{"weights_blob", weights_blob}}))
+        return st;
     return costreg_impl(var, weights_blob, cost_out, workspace, workspace_bytes, D, h, w, dtype, stream);
 }
 
@@ -296,6 +319,8 @@ int mvs_conv_layer(int layer, const void* x, const void* skip, void* y, const vo
     if (layer == 10 && (5 * (size_t)Hi + 9) * (size_t)Wi + 33 > kMaxProbHaloVoxels)   // Hi*Wi < 2^28 here: no wrap
         return fail(MVS_ERR_BAD_SHAPE, "layer 10: plane of %d,%d exceeds the 31-bit halo offsets of the prob kernel "
                     "((5 Hi + 9) Wi + 33 < 2^28)", Hi, Wi);
+    if (int st = check_align16("mvs_conv_layer", {{"x", x}, {"skip", skip}, {"y", y}}, {{"weights_blob", weights_blob}}))
+        return st;
     return launch_conv_layer(layer, x, skip, y, static_cast<const float*>(weights_blob), Di, Hi, Wi,
                              dtype, static_cast<hipStream_t>(stream));
 }
@@ -307,6 +332,9 @@ int mvs_conv11_prob(const void* x, const void* skip, float* cost_out, const void
         return fail(MVS_ERR_BAD_DTYPE, "mvs_conv11_prob: unknown dtype %d", dtype);
     if (Di < 1 || Hi < 1 || Wi < 1 || product_exceeds(Di, Hi, Wi, (((size_t)1 << 31) - 1) / 64))
         return fail(MVS_ERR_BAD_SHAPE, "mvs_conv11_prob: input dims %d,%d,%d outside Di*Hi*Wi*64 in [64, 2^31)", Di, Hi, Wi);
+    if (int st = check_align16("mvs_conv11_prob", {{"x", x}, {"skip", skip}, {"cost_out", cost_out}},
+                               {{"weights_blob", weights_blob}}))
+        return st;
     return launch_conv11_prob(x, skip, cost_out, static_cast<const float*>(weights_blob), Di, Hi, Wi, dtype,
                               static_cast<hipStream_t>(stream));
 }
@@ -330,6 +358,9 @@ int mvs_warp_variance_backward(const float* feats, const float* rt, const float*
     // the forward's shape domain; every index of the kernel stays inside it (size_t volume offsets, int texel
     // offsets below h*w < 2^24)
     if (int st = check_dims(N, C, D, h, w, MVS_F32)) return st;
+    if (int st = check_align16("mvs_warp_variance_backward", {{"feats", feats}, {"rt", rt}, {"depth_values", depth_values},
+                                                              {"grad_var", grad_var}, {"grad_feats", grad_feats}}, {}))
+        return st;
     return launch_warp_variance_backward(feats, rt, depth_values, grad_var, grad_feats, N, D, h, w,
                                          static_cast<hipStream_t>(stream));
 }
@@ -351,10 +382,12 @@ int mvs_softargmin_backward(const float* cost, const float* depth_values, const 
 static int depth_infer_impl(const float* feats, const ViewTable& views, const float* proj, const float* depth_values,
                             const void* weights_blob, float* depth_out, float* conf_out, void* workspace,
                             size_t workspace_bytes, int N, int C, int D, int h, int w, int dtype,
-                            void* stream) {
+                            void* stream, const char* who) {
     if (!proj || !depth_values || !weights_blob || !depth_out || !conf_out || !workspace)
         return fail(MVS_ERR_NULL, "mvs_depth_infer: NULL argument");
     if (int st = check_dims(N, C, D, h, w, dtype)) return st;
+    if (int st = check_align16(who, {{"proj", proj}, {"depth_values", depth_values}}, {{"weights_blob", weights_blob}}))
+        return st;
     const Workspace W = workspace_layout(N, C, D, h, w, dtype);
     if (workspace_bytes < W.total)
         return fail(MVS_ERR_WORKSPACE, "workspace needs >= %zu bytes, got %zu", W.total, workspace_bytes);
@@ -389,7 +422,7 @@ int mvs_depth_infer(const float* feats, const float* proj, const float* depth_va
                     void* stream) {
     if (!feats) return fail(MVS_ERR_NULL, "mvs_depth_infer: NULL argument");
     return depth_infer_impl(feats, identity_views(N), proj, depth_values, weights_blob, depth_out, conf_out,
-                            workspace, workspace_bytes, N, C, D, h, w, dtype, stream);
+                            workspace, workspace_bytes, N, C, D, h, w, dtype, stream, "mvs_depth_infer");
 }
 
 // mvs_depth_infer with its N views picked from a bank of V feature maps: only the table the
@@ -408,7 +441,7 @@ int mvs_depth_infer_views(const float* feats, int V, const int* view_idx, const 
         views.v[n] = view_idx[n];
     }
     return depth_infer_impl(feats, views, proj, depth_values, weights_blob, depth_out, conf_out, workspace,
-                            workspace_bytes, N, C, D, h, w, dtype, stream);
+                            workspace_bytes, N, C, D, h, w, dtype, stream, "mvs_depth_infer_views");
 }
 
 // ---- FeatureNet (models/mvsnet.py:10-30) and the whole MVSNet.forward from images -------------
@@ -480,6 +513,7 @@ int mvs_feature_layer(int layer, const float* x, float* y, const void* feature_b
     if (!x || !y || !feature_blob) return fail(MVS_ERR_NULL, "mvs_feature_layer: NULL argument");
     if (layer < 0 || layer >= MVS_FEATURE_LAYERS) return fail(MVS_ERR_BAD_SHAPE, "feature layer %d outside [0,8)", layer);
     if (int st = check_image_dims(N, Hi, Wi)) return st;
+    if (int st = check_align16("mvs_feature_layer", {{"x", x}, {"y", y}}, {{"feature_blob", feature_blob}})) return st;
     return launch_feature_layer(layer, x, y, static_cast<const float*>(feature_blob), N, Hi, Wi,
                                 static_cast<hipStream_t>(stream));
 }
@@ -490,6 +524,8 @@ int mvs_feature_conv01_fmt(const void* imgs, int image_format, float* y, const v
     if (image_format < MVS_IMG_F32_CHW || image_format > MVS_IMG_U8_HWC)
         return fail(MVS_ERR_BAD_DTYPE, "mvs_feature_conv01_fmt: unknown image format %d", image_format);
     if (int st = check_image_dims(N, H, W)) return st;
+    if (int st = check_align16("mvs_feature_conv01_fmt", {{"imgs", imgs}, {"y", y}}, {{"feature_blob", feature_blob}}))
+        return st;
     return launch_feature_conv01(imgs, image_format, y, static_cast<const float*>(feature_blob), N, H, W,
                                  static_cast<hipStream_t>(stream));
 }
@@ -506,6 +542,8 @@ int mvs_feature_net_fmt(const void* imgs, int image_format, const void* feature_
     if (image_format < MVS_IMG_F32_CHW || image_format > MVS_IMG_U8_HWC)
         return fail(MVS_ERR_BAD_DTYPE, "mvs_feature_net: unknown image format %d", image_format);
     if (int st = check_image_dims(N, H, W)) return st;
+    if (int st = check_align16("mvs_feature_net", {{"imgs", imgs}, {"feats_out", feats_out}}, {{"feature_blob", feature_blob}}))
+        return st;
     const FeatWorkspace F = feat_workspace_layout(N, H, W);
     if (workspace_bytes < F.total)
         return fail(MVS_ERR_WORKSPACE, "feature workspace needs >= %zu bytes, got %zu", F.total, workspace_bytes);
@@ -551,6 +589,10 @@ int mvs_forward_images_fmt(const void* imgs, int image_format, const float* proj
     const int h = H / 4, w = W / 4;
     if (int st = check_dims(N, kC, D, h, w, dtype)) return st;
     if (int st = check_image_dims(N, H, W)) return st;
+    // proj, depth_values and weights_blob here as well: depth_infer_impl runs after FeatureNet has been enqueued
+    if (int st = check_align16("mvs_forward_images", {{"imgs", imgs}, {"proj", proj}, {"depth_values", depth_values}},
+                               {{"feature_blob", feature_blob}, {"weights_blob", weights_blob}}))
+        return st;
     const Workspace Wd = workspace_layout(N, kC, D, h, w, dtype);
     const FeatWorkspace F = feat_workspace_layout(N, H, W);
     if (workspace_bytes < Wd.total + F.total)
@@ -573,7 +615,7 @@ int mvs_forward_images_fmt(const void* imgs, int image_format, const float* proj
     if (narrow)
         if (int st = launch_narrow_features(c8, feats_t, (size_t)N * kC * h * w, dtype, s)) return st;
     return depth_infer_impl(nullptr, identity_views(N), proj, depth_values, weights_blob, depth_out, conf_out,
-                            workspace, Wd.total, N, kC, D, h, w, dtype, stream);
+                            workspace, Wd.total, N, kC, D, h, w, dtype, stream, "mvs_forward_images");
 }
 
 int mvs_homo_warp(const float* src_fea, const float* rt, const float* depth_values, float* out,
@@ -586,6 +628,7 @@ int mvs_homo_warp(const float* src_fea, const float* rt, const float* depth_valu
     if (hw >= ((size_t)1 << 31) || hw * D > kMaxHomoWarpThreads || hw * D > kMaxHomoWarpOutput / C)
         return fail(MVS_ERR_BAD_SHAPE, "mvs_homo_warp: C,D,h,w = %d,%d,%d,%d: h*w >= 2^31, D*h*w > 2^39-512 or "
                     "C*D*h*w > 2^61", C, D, h, w);
+    if (int st = check_align16("mvs_homo_warp", {{"rt", rt}}, {})) return st;
     return launch_homo_warp(src_fea, rt, depth_values, out, C, D, h, w, static_cast<hipStream_t>(stream));
 }
 

@@ -1,5 +1,6 @@
 // mvs_internal.h -- shared host-side definitions of libmvs_hip.so (not part of the ABI).
 #pragma once
+#include <initializer_list>
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -206,6 +207,13 @@ __host__ __device__ constexpr Deconv16Tap deconv16_tap(int ks, int q) {
 // thread-local error text
 int fail(int code, const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);
+// the 16-byte alignment rule of include/mvs_abi.h (mvs_host.hip): data pointers -> MVS_ERR_BAD_SHAPE, blobs ->
+// MVS_ERR_WORKSPACE; NULL passes
+struct NamedPtr {
+    const char* name;
+    const void* p;
+};
+int check_align16(const char* who, std::initializer_list<NamedPtr> data, std::initializer_list<NamedPtr> blobs);
 
 // the switches of launch_plan.h's Options, read from the environment once on first use
 const Options& options();

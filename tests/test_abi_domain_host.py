@@ -178,6 +178,40 @@ SPECS = {
                                     rules=[(dict(D=1 << 30, h=1 << 15, w=1 << 15), 1)]),
 }
 
+# The alignment rule of include/mvs_abi.h: entry point -> (data pointers, blobs).  A data pointer at +4 of its good
+# (256-byte aligned, fake) address gives BAD_SHAPE, a blob at +4 WORKSPACE, with every other argument good.  The workspace
+# has its own "+16" case above (it is held to 256 bytes); HOST arrays (view_idx) are not device addresses.
+ALIGN = {
+    "mvs_relative_proj": (("proj", "rt_out"), ()),
+    "mvs_warp_variance": (("rt", "depth_values", "var_out"), ()),
+    "mvs_costreg_forward": (("var", "cost_out"), ("weights_blob",)),
+    "mvs_conv_layer": (("x", "skip", "y"), ("weights_blob",)),
+    "mvs_conv11_prob": (("x", "skip", "cost_out"), ("weights_blob",)),
+    "mvs_depth_infer": (("proj", "depth_values"), ("weights_blob",)),
+    "mvs_depth_infer_views": (("proj", "depth_values"), ("weights_blob",)),
+    "mvs_homo_warp": (("rt",), ()),
+    "mvs_feature_layer": (("x", "y"), ("feature_blob",)),
+    "mvs_feature_conv01_fmt": (("imgs", "y"), ("feature_blob",)),
+    "mvs_feature_net": (("imgs", "feats_out"), ("feature_blob",)),
+    "mvs_feature_net_fmt": (("imgs", "feats_out"), ("feature_blob",)),
+    "mvs_forward_images": (("imgs", "proj", "depth_values"), ("feature_blob", "weights_blob")),
+    "mvs_forward_images_fmt": (("imgs", "proj", "depth_values"), ("feature_blob", "weights_blob")),
+    "mvs_warp_variance_backward": (("feats", "rt", "depth_values", "grad_var", "grad_feats"), ()),
+}
+# the pointers the header states are per element, or asks nothing of: no refusal to sweep (the per-element ones run one
+# element into a larger allocation in tests/test_gpu_wrapper_contract.py)
+NOT_HELD = {
+    "mvs_warp_variance": ("feats",),
+    "mvs_depth_infer": ("feats", "depth_out", "conf_out"),
+    "mvs_depth_infer_views": ("feats", "depth_out", "conf_out"),
+    "mvs_homo_warp": ("src_fea", "depth_values", "out"),
+    "mvs_forward_images": ("depth_out", "conf_out"),
+    "mvs_forward_images_fmt": ("depth_out", "conf_out"),
+    "mvs_softargmin_conf": ("cost", "depth_values", "depth_out", "conf_out"),
+    "mvs_softargmin_backward": ("cost", "depth_values", "grad_depth", "grad_cost"),
+    "mvs_depth_regression": ("p", "depth_values", "depth_out"),
+}
+
 # entry points whose own host file holds them to their stated domain in this way
 COVERED = {
     "mvs_filter_compose": "test_filter_ref_host.py",
@@ -241,6 +275,9 @@ def cases_of(name, spec, protos):
     if "ws" in spec:
         out.append(("workspace one byte short", {"workspace_bytes": "ws-1"}, WORKSPACE))
         out.append(("workspace at +16", {"workspace": "misaligned", "workspace_bytes": "ws"}, WORKSPACE))
+    data, blobs = ALIGN.get(name, ((), ()))
+    out += [(f"{p} at +4", {p: "plus4"}, BAD_SHAPE) for p in data]
+    out += [(f"blob {p} at +4", {p: "plus4"}, WORKSPACE) for p in blobs]
     if spec.get("pack"):
         nconv, nbn = (11, 40) if spec["pack"] == "costreg" else (8, 28)
         out += [(f"conv_weights[{l}]=NULL", {"null_conv": l}, NULL) for l in range(nconv)]
@@ -305,6 +342,8 @@ def _sweep(part):
                     v = ctypes.c_void_p(blob.ctypes.data)
                 elif p == "workspace" and ov.get(p) == "misaligned":
                     v = ctypes.c_void_p(0x100000 * fake + 16)
+                elif ov.get(p) == "plus4":
+                    v = ctypes.c_void_p(0x100000 * fake + 4)
                 else:
                     v = ctypes.c_void_p(0x100000 * fake)      # 256-byte aligned, never dereferenced
             elif p == "workspace_bytes":
@@ -421,6 +460,13 @@ def test_every_entry_point_pointer_and_integer_of_the_header_has_its_cases():
                 below = spec.get("dtypes", {}) if p in ("dtype", "image_format") else spec.get("below", {})
                 if p not in below or not any(v < 0 or v == 0 for v in below[p]):
                     missing.append(f"{name}: int {p} has no below-range case")
+        if any(kind == "ptr" and p == "stream" for kind, p in params):      # a device entry point: the alignment cases
+            data, blobs = ALIGN.get(name, ((), ()))
+            free = NOT_HELD.get(name, ())
+            for kind, p in params:
+                if kind == "ptr" and p not in ("stream", "workspace") + tuple(spec.get("host", ())) and p not in data + blobs + free:
+                    missing.append(f"{name}: pointer {p} has neither an alignment case nor a NOT_HELD entry")
+            assert not set(data + blobs + free) - {p for _, p in params} and not set(free) & set(data + blobs), name
         stale = [k for k in list(spec.get("below", {})) + list(spec.get("above", {})) + list(spec.get("optional", {}))
                  if k not in [p for _, p in params]]
         assert not stale, (name, stale)

@@ -1,0 +1,1132 @@
+"""The contract between the Python wrappers (scene_3dreconstruction_mvsnet_amd/_lib.py, module.py) and the device entry
+points of libmvs_hip.so, and the harness that holds every wrapper to it without launching anything.
+
+The contract.  A wrapper either raises RuntimeError before any device entry point is called, or every call it makes is
+HONEST: each pointer argument is NULL where the header allows NULL; or the address of a host array where the header says
+HOST; or the address of a live tensor that is on the CUDA device whose stream the call carries, is contiguous, has the
+dtype the header states for that parameter and holds at least the bytes the header states for it under the integer
+arguments of the same call (a workspace: at least the `workspace_bytes` passed; a blob: at least its mvs_query_*).  The
+call is made with that device current.  The address of a non-contiguous argument is never honest, whatever else lives
+there.
+
+The harness.  `Recorder` stands in for `_lib.load()`: it forwards the entry points that do no device work
+(mvs_abi_version, mvs_last_error_string, every mvs_query_*, the three HOST functions) to the real library and records
+and judges everything else, returning 0, so no kernel is launched while it is installed.  `EXTENTS` restates, per device
+entry point and pointer parameter, the dtype and the bytes of the headers (parameter names from the headers' prototypes,
+positions from `_lib._ABI`, byte counts of the workspaces and blobs from the library's own queries).  Device tensors are
+`Dev`, a torch.Tensor subclass whose __torch_function__ re-wraps and registers every result: on a machine without a GPU
+it sits on host memory and reports a CUDA device (`World(fake=True)`), on a GPU it wraps real CUDA tensors, so one
+table serves tests/test_wrapper_contract_host.py and tests/test_gpu_wrapper_contract.py.  `torch.empty` of the wrapped
+modules goes through a proxy that registers what the wrappers allocate.  Tensors made inside a wrapper are held by weak
+references: a temporary whose address is handed over after the temporary died is reported.
+
+`CASES` is the table: per wrapper one good call at the smallest admitted shape and, per tensor parameter, the defects
+host / dtype / strided / short / shape / other_device (outputs: strided and offset-shape as well), each expected to be
+`refused`, `copied` (a contiguous copy is handed over, not the view) or `library:<entry point>/<case>`: the call is
+honest and the named case of SPECS in tests/test_abi_domain_host.py pins the library's refusal.  A fourth expectation,
+`honest`, is written out where the defect leaves a good call of other integers that nobody can refuse (the only tensor of
+a call on another device; the tensor the wrapper reads V, P or n from, one row shorter): the call is still judged.  An
+`exempt` entry quotes the header sentence that makes a defect meaningless for a parameter."""
+import ast
+import contextlib
+import ctypes
+import inspect
+import os
+import re
+import weakref
+
+import numpy as np
+import torch
+from torch.utils._pytree import tree_flatten, tree_map
+
+import test_abi_domain_host as dom
+from scene_3dreconstruction_mvsnet_amd import _lib, module, mvsnet
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+f32, f64, i32, i64, u8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
+STREAM_BASE = 0x5000          # the stand-in stream handle of device k is STREAM_BASE + k
+
+# ---- the headers' prototypes ------------------------------------------------------------------------------------------
+HOST_ENTRIES = ("mvs_pack_weights", "mvs_pack_feature_weights", "mvs_filter_compose")
+
+
+def prototypes():
+    """{entry point: [(kind, name)]} of every header in _lib._ABI; kind is 'ptr' or the C type."""
+    out = {}
+    for header in _lib._ABI:
+        text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
+        for name, params in re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.M | re.S):
+            plist = []
+            for param in ([] if params.strip() == "void" else params.split(",")):
+                param = " ".join(param.split())
+                array = param.endswith("]")
+                param = re.sub(r"\[\w*\]$", "", param).strip()
+                pname = re.search(r"(\w+)$", param).group(1)
+                ctype = " ".join(re.sub(r"\bconst\b", " ", param[:-len(pname)]).split())
+                plist.append(("ptr" if array or "*" in ctype else ctype, pname))
+            out[name] = plist
+    return out
+
+
+PROTOS = prototypes()
+ALL_ENTRIES = tuple(n for table in _lib._ABI.values() for n in table)
+FORWARDED = tuple(n for n in ALL_ENTRIES if n.startswith("mvs_query_") or n in HOST_ENTRIES
+                  or n in ("mvs_abi_version", "mvs_last_error_string"))
+DEVICE_ENTRIES = tuple(n for n in ALL_ENTRIES if n not in FORWARDED)
+
+
+# ---- EXTENTS: dtype and bytes of every pointer parameter, restated from the headers -----------------------------------
+class Ptr:
+    """One pointer parameter: `dtype` (a torch dtype, a tuple of them, or a function of the call's integers), `nbytes`
+    (a function of the call's integers), `null` (True, or a function of the integers: NULL is allowed), `host`."""
+
+    def __init__(self, dtype=None, nbytes=None, null=False, host=False):
+        self.dtype, self.nbytes, self.null, self.host = dtype, nbytes, null, host
+
+    def dtypes(self, a):
+        d = self.dtype(a) if callable(self.dtype) else self.dtype
+        return d if isinstance(d, tuple) else (d,)
+
+    def nullable(self, a):
+        return self.null(a) if callable(self.null) else self.null
+
+
+def _st(a):
+    return _lib.TORCH_DTYPES[a["dtype"]]
+
+
+def _es(a):
+    return 4 if a["dtype"] == 0 else 2
+
+
+def F(n, null=False):
+    return Ptr(f32, lambda a: 4 * n(a), null)
+
+
+HOSTP = Ptr(host=True)
+HOSTP_NULL = Ptr(host=True, null=True)
+WS = Ptr(u8, lambda a: a["workspace_bytes"])
+BLOB = Ptr(u8, lambda a: _lib.query_weights_blob())
+FBLOB = Ptr(u8, lambda a: _lib.query_feature_blob())
+_CH = dom._COSTREG_CH
+_FL = _lib.FEATURE_LAYERS
+
+
+def _conv_out(a):
+    l, d = a["layer"], (a["Di"], a["Hi"], a["Wi"])
+    d = tuple(2 * v for v in d) if 7 <= l <= 9 else tuple(v // 2 for v in d) if l in (1, 3, 5) else d
+    return d[0] * d[1] * d[2]
+
+
+def _img(a):
+    return f32 if a.get("image_format", 0) == 0 else u8
+
+
+def _img_bytes(a):
+    return a["N"] * 3 * a["H"] * a["W"] * (4 if a.get("image_format", 0) == 0 else 1)
+
+
+def _quarter(v):
+    return ((v - 1) // 2 + 1 - 1) // 2 + 1
+
+
+def _feat_out(a):
+    s = _FL[a["layer"]][3]
+    return _FL[a["layer"]][1] * a["N"] * ((a["Hi"] - 1) // s + 1) * ((a["Wi"] - 1) // s + 1)
+
+
+def _xyz(dkey, nkey):
+    return Ptr(lambda a: f64 if a[dkey] == 1 else f32, lambda a: a[nkey] * 3 * (8 if a[dkey] == 1 else 4))
+
+
+def _host_ints(address, n):
+    return list((ctypes.c_int * n).from_address(address)) if address else [0] * n
+
+
+_vol = lambda a: a["D"] * a["h"] * a["w"]                                  # noqa: E731
+_pix = lambda a: a["h"] * a["w"]                                           # noqa: E731
+_cvol = lambda a: a["D"] * a["H"] * a["W"]                                 # noqa: E731
+_cvol_out = lambda a: _cvol(a) // a["stride"] ** 3                         # noqa: E731
+_mc = lambda a: a["M"] * a["C"]                                            # noqa: E731
+_c = lambda a: a["C"]                                                      # noqa: E731
+_cap_null = lambda a: a["capacity"] == 0                                   # noqa: E731
+KEEP = Ptr((u8, torch.bool), lambda a: a["P"])
+_DEPTH_COMMON = dict(proj=F(lambda a: a["N"] * 16), depth_values=F(lambda a: a["D"]), weights_blob=BLOB,
+                     depth_out=F(_pix), conf_out=F(_pix), workspace=WS)
+_FWD_COMMON = dict(proj=F(lambda a: a["N"] * 16), depth_values=F(lambda a: a["D"]), feature_blob=FBLOB, weights_blob=BLOB,
+                   depth_out=F(lambda a: (a["H"] // 4) * (a["W"] // 4)), conf_out=F(lambda a: (a["H"] // 4) * (a["W"] // 4)),
+                   workspace=WS)
+_BOX = dict(box_min=HOSTP, box_max=HOSTP)
+
+EXTENTS = {
+    "mvs_relative_proj": dict(proj=F(lambda a: a["N"] * 16), rt_out=F(lambda a: (a["N"] - 1) * 12)),
+    "mvs_warp_variance": dict(feats=F(lambda a: a["N"] * a["C"] * _pix(a)), rt=F(lambda a: (a["N"] - 1) * 12, lambda a: a["N"] == 1),
+                              depth_values=F(lambda a: a["D"]), var_out=Ptr(_st, lambda a: a["C"] * _vol(a) * _es(a)),
+                              workspace=WS),
+    "mvs_costreg_forward": dict(var=Ptr(_st, lambda a: 32 * _vol(a) * _es(a)), weights_blob=BLOB, cost_out=F(_vol), workspace=WS),
+    "mvs_conv_layer": dict(x=Ptr(_st, lambda a: _CH[a["layer"]][0] * a["Di"] * a["Hi"] * a["Wi"] * _es(a)),
+                           skip=Ptr(_st, lambda a: _CH[a["layer"]][1] * _conv_out(a) * _es(a), lambda a: not 7 <= a["layer"] <= 9),
+                           y=Ptr(lambda a: f32 if a["layer"] == 10 else _st(a),
+                                 lambda a: _conv_out(a) * (4 if a["layer"] == 10 else _CH[a["layer"]][1] * _es(a))),
+                           weights_blob=BLOB),
+    "mvs_conv11_prob": dict(x=Ptr(_st, lambda a: 16 * a["Di"] * a["Hi"] * a["Wi"] * _es(a)),
+                            skip=Ptr(_st, lambda a: 64 * a["Di"] * a["Hi"] * a["Wi"] * _es(a)),
+                            cost_out=F(lambda a: 8 * a["Di"] * a["Hi"] * a["Wi"]), weights_blob=BLOB),
+    "mvs_softargmin_conf": dict(cost=F(_vol), depth_values=F(lambda a: a["D"]), depth_out=F(_pix), conf_out=F(_pix)),
+    "mvs_depth_infer": dict(_DEPTH_COMMON, feats=F(lambda a: a["N"] * a["C"] * _pix(a))),
+    "mvs_depth_infer_views": dict(_DEPTH_COMMON, feats=F(lambda a: a["V"] * a["C"] * _pix(a)), view_idx=HOSTP),
+    "mvs_homo_warp": dict(src_fea=F(lambda a: a["C"] * _pix(a)), rt=F(lambda a: 12), depth_values=F(lambda a: a["D"]),
+                          out=F(lambda a: a["C"] * _vol(a))),
+    "mvs_depth_regression": dict(p=F(_vol), depth_values=F(lambda a: a["D"]), depth_out=F(_pix)),
+    "mvs_filter_depth": dict(depth=F(lambda a: a["V"] * _pix(a)), conf=F(lambda a: a["V"] * _pix(a)),
+                             ref_mats=F(lambda a: a["R"] * 30), pair_mats=F(lambda a: a["R"] * a["S"] * 42),
+                             ref_idx=Ptr(i32, lambda a: a["R"] * 4), src_idx=Ptr(i32, lambda a: a["R"] * a["S"] * 4),
+                             geo_sum=Ptr(i32, lambda a: a["R"] * _pix(a) * 4), depth_avg=Ptr(f64, lambda a: a["R"] * _pix(a) * 8),
+                             masks=Ptr(u8, lambda a: a["R"] * 3 * _pix(a)), xyz_world=Ptr(f64, lambda a: a["R"] * _pix(a) * 24)),
+    "mvs_feature_layer": dict(x=F(lambda a: (3 if a["layer"] == 0 else _FL[a["layer"]][0]) * a["N"] * a["Hi"] * a["Wi"]),
+                              y=F(_feat_out), feature_blob=FBLOB),
+    "mvs_feature_conv01_fmt": dict(imgs=Ptr(_img, _img_bytes), y=F(lambda a: a["N"] * a["H"] * a["W"] * 8), feature_blob=FBLOB),
+    "mvs_feature_net": dict(imgs=Ptr(_img, _img_bytes), feature_blob=FBLOB,
+                            feats_out=F(lambda a: a["N"] * 32 * _quarter(a["H"]) * _quarter(a["W"])), workspace=WS),
+    "mvs_forward_images": dict(_FWD_COMMON, imgs=Ptr(_img, _img_bytes)),
+    "mvs_depth_metrics": dict(depth_est=F(lambda a: a["B"] * _pix(a)), depth_gt=F(lambda a: a["B"] * _pix(a)),
+                              mask=F(lambda a: a["B"] * _pix(a)), thresholds=Ptr(host=True, null=lambda a: a["n_thres"] == 0),
+                              sums_out=Ptr(f64, lambda a: a["B"] * (3 + a["n_thres"]) * 8),
+                              errmap_out=F(lambda a: a["B"] * _pix(a), True), workspace=WS),
+    "mvs_warp_variance_backward": dict(feats=F(lambda a: a["N"] * a["C"] * _pix(a)),
+                                       rt=F(lambda a: (a["N"] - 1) * 12, lambda a: a["N"] == 1), depth_values=F(lambda a: a["D"]),
+                                       grad_var=F(lambda a: a["C"] * _vol(a)), grad_feats=F(lambda a: a["N"] * a["C"] * _pix(a))),
+    "mvs_softargmin_backward": dict(cost=F(_vol), depth_values=F(lambda a: a["D"]), grad_depth=F(_pix), grad_cost=F(_vol)),
+    "mvs_conv3d_train_forward": dict(x=F(lambda a: _cvol(a) * a["Cin"]), w=F(lambda a: 27 * a["Cin"] * a["Cout"]),
+                                     bias=F(lambda a: a["Cout"], True), y=F(lambda a: _cvol_out(a) * a["Cout"])),
+    "mvs_conv3d_train_backward_data": dict(gy=F(lambda a: _cvol_out(a) * a["Cout"]), w=F(lambda a: 27 * a["Cin"] * a["Cout"]),
+                                           gx=F(lambda a: _cvol(a) * a["Cin"])),
+    "mvs_conv3d_train_backward_weight": dict(x=F(lambda a: _cvol(a) * a["Cin"]), gy=F(lambda a: _cvol_out(a) * a["Cout"]),
+                                             gw=F(lambda a: 27 * a["Cin"] * a["Cout"]), gbias=F(lambda a: a["Cout"], True),
+                                             workspace=WS),
+    "mvs_bn3d_train_forward": dict(y=F(_mc), gamma=F(_c), beta=F(_c), skip=F(_mc, True), out=F(_mc), save_mean=F(_c),
+                                   save_invstd=F(_c), running_mean=F(_c, True), running_var=F(_c, True), workspace=WS),
+    "mvs_bn3d_train_backward": dict(y=F(_mc), grad_out=F(_mc), gamma=F(_c), beta=F(_c), save_mean=F(_c), save_invstd=F(_c),
+                                    grad_y=F(_mc), grad_gamma=F(_c), grad_beta=F(_c), workspace=WS),
+    "mvs_volume_relayout": dict(src=F(lambda a: a["C"] * a["V"]), dst=F(lambda a: a["C"] * a["V"])),
+    "mvs_fuse_points": dict(xyz_world=Ptr(f64, lambda a: a["R"] * _pix(a) * 24), masks=Ptr((u8, torch.bool), lambda a: a["R"] * 3 * _pix(a)),
+                            images=Ptr(u8, lambda a: a["V"] * 3 * 16 * _pix(a)), ref_idx=Ptr(i32, lambda a: a["R"] * 4),
+                            xyz_out=F(lambda a: a["capacity"] * 3, _cap_null), rgb_out=Ptr(u8, lambda a: a["capacity"] * 3, _cap_null),
+                            counts_out=Ptr(i32, lambda a: (a["R"] + 1) * 4), workspace=WS),
+    "mvs_cloud_downsample": dict(_BOX, xyz=_xyz("xyz_dtype", "P"), rgb=Ptr(u8, lambda a: a["P"] * 3),
+                                 xyz_out=F(lambda a: a["capacity"] * 3, _cap_null),
+                                 rgb_out=Ptr(u8, lambda a: a["capacity"] * 3, _cap_null), counts_out=Ptr(i64, lambda a: 16),
+                                 workspace=WS),
+    "mvs_cloud_normals": dict(_BOX, xyz=_xyz("xyz_dtype", "P"), view_starts=Ptr(i64, lambda a: (a["R"] + 1) * 8, lambda a: a["R"] == 0),
+                              centres=Ptr(f64, lambda a: a["R"] * 24, lambda a: a["R"] == 0), normals_out=F(lambda a: a["P"] * 3),
+                              nbr_out=Ptr(i32, lambda a: a["P"] * a["knn"] * 4, True), counts_out=Ptr(i64, lambda a: 24), workspace=WS),
+    "mvs_cloud_outliers": dict(_BOX, xyz=_xyz("xyz_dtype", "P"), dist_out=Ptr(f64, lambda a: a["P"] * 8), keep_out=KEEP,
+                               xyz_masked_out=Ptr(lambda a: f64 if a["xyz_dtype"] == 1 else f32,
+                                                  lambda a: a["P"] * 3 * (8 if a["xyz_dtype"] == 1 else 4), True),
+                               counts_out=Ptr(i64, lambda a: 24), stats_out=Ptr(f64, lambda a: 24), workspace=WS),
+    "mvs_cloud_distance": dict(_BOX, ref_xyz=_xyz("ref_dtype", "P"), query_xyz=_xyz("query_dtype", "N"),
+                               thresholds=Ptr(host=True, null=lambda a: a["T"] == 0), dist_out=Ptr(f64, lambda a: a["N"] * 8),
+                               idx_out=Ptr(i32, lambda a: a["N"] * 4, True), counts_out=Ptr(i64, lambda a: (2 + a["T"]) * 8),
+                               stats_out=Ptr(f64, lambda a: 16), workspace=WS),
+    "mvs_cloud_reduce": dict(_BOX, xyz=_xyz("dtype", "P"), keep_out=KEEP, counts_out=Ptr(i64, lambda a: 32), workspace=WS),
+    "mvs_cloud_select": dict(xyz=_xyz("dtype", "P"),
+                             obs_mask=Ptr((u8, torch.bool), lambda a: int(np.prod(_host_ints(a["n"], 3))), True),
+                             n=HOSTP_NULL, origin=HOSTP_NULL, plane=HOSTP_NULL, keep_out=KEEP, counts_out=Ptr(i64, lambda a: 24)),
+    "mvs_cloud_cluster": dict(_BOX, xyz=_xyz("dtype", "P"), labels_out=Ptr(i32, lambda a: a["P"] * 4), keep_out=KEEP,
+                              counts_out=Ptr(i64, lambda a: 56), workspace=WS),
+}
+EXTENTS["mvs_feature_net_fmt"] = EXTENTS["mvs_feature_net"]
+EXTENTS["mvs_forward_images_fmt"] = EXTENTS["mvs_forward_images"]
+EXTENTS["mvs_cloud_downsample_normals"] = dict(EXTENTS["mvs_cloud_downsample"], normals=F(lambda a: a["P"] * 3),
+                                               normals_out=F(lambda a: a["capacity"] * 3, _cap_null))
+
+
+# ---- device tensors and the world that watches them --------------------------------------------------------------------
+_WORLD = None
+
+
+class Meta:
+    def __init__(self, t):
+        with torch._C.DisableTorchFunctionSubclass():
+            self.ptr, self.nbytes = t.data_ptr(), t.numel() * t.element_size()
+            self.dtype, self.contiguous, self.ndim = t.dtype, t.is_contiguous(), t.dim()
+            real = torch.Tensor.device.__get__(t)
+            self.storage = t.untyped_storage().data_ptr()
+        dev = t.__dict__.get("_dev") if isinstance(t, Dev) else None
+        dev = dev or real
+        self.is_cuda, self.index = dev.type == "cuda", dev.index
+
+
+class World:
+    """Who is alive and what was called.  fake=True: no GPU; `Dev` tensors sit on the host and report a CUDA device."""
+
+    def __init__(self, fake):
+        self.fake = fake
+        self.notes = []           # (weak reference, Meta) of every device tensor made while this world is installed
+        self.passed = []          # the tensors the case passed, held
+        self.calls = []           # (entry point, args, problems)
+        self.devstack = [0]       # fake only: what torch.cuda.device() made current
+
+    def note(self, t):
+        self.notes.append((weakref.ref(t), Meta(t)))
+
+    def current_device(self):
+        return self.devstack[-1] if self.fake else torch.cuda.current_device()
+
+    def at(self, ptr):
+        """(live metas, dead metas) of the noted tensors that start at `ptr`.  A view that died while a tensor of the same
+        storage lives (`x[b].data_ptr()`) is alive: its memory is."""
+        storages = {m.storage for r, m in self.notes if r() is not None}
+        here = [m for _, m in self.notes if m.ptr == ptr]
+        return [m for m in here if m.storage in storages], [m for m in here if m.storage not in storages]
+
+    def problems(self):
+        return [f"{name}: {p}" for name, _, probs in self.calls for p in probs]
+
+
+class Dev(torch.Tensor):
+    """A device tensor the world watches.  `_dev` is the CUDA device it reports in a fake world, else None."""
+
+    @staticmethod
+    def wrap(t, dev=None):
+        with torch._C.DisableTorchFunctionSubclass():
+            r = t.as_subclass(Dev)
+        r._dev = dev
+        if _WORLD is not None:
+            _WORLD.note(r)
+        return r
+
+    @property
+    def device(self):
+        d = self.__dict__.get("_dev")
+        if d is not None:
+            return d
+        with torch._C.DisableTorchFunctionSubclass():
+            return torch.Tensor.device.__get__(self)
+
+    @property
+    def is_cuda(self):
+        return self.device.type == "cuda"
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        flat, _ = tree_flatten((args, kwargs))
+        inputs = [a for a in flat if isinstance(a, torch.Tensor)]
+        src = next((a.__dict__.get("_dev") for a in inputs if isinstance(a, Dev)), None)
+        fake = _WORLD is not None and _WORLD.fake
+        target = [src]
+        if fake:
+            def strip(x):
+                if isinstance(x, torch.device) or (isinstance(x, str) and x.split(":")[0] in ("cuda", "cpu")):
+                    x = torch.device(x)
+                    target[0] = x if x.type == "cuda" else None
+                    return torch.device("cpu")
+                return x
+            args, kwargs = tree_map(strip, (args, kwargs))
+            if getattr(func, "__name__", "") == "cpu":
+                target[0] = None
+        with torch._C.DisableTorchFunctionSubclass():
+            out = func(*args, **kwargs)
+
+        def rewrap(x):
+            if not isinstance(x, torch.Tensor):
+                return x
+            same = any(x is a for a in inputs)
+            if same and (not isinstance(x, Dev) or x.__dict__.get("_dev") == target[0]):
+                return x
+            if same:                  # a move between the fake devices: another tensor, as a real move gives
+                with torch._C.DisableTorchFunctionSubclass():
+                    x = x.clone()
+            return Dev.wrap(x, target[0])
+        return tree_map(rewrap, out)
+
+
+def _like_a_device_allocation(t):
+    """A copy of a host tensor that starts on a 256-byte boundary, as every allocation of torch's CUDA allocator does
+    (the host allocator gives 64)."""
+    with torch._C.DisableTorchFunctionSubclass():
+        n = t.numel() * t.element_size()
+        buf = torch.empty(n + 256, dtype=u8)
+        off = (-buf.data_ptr()) % 256
+        out = buf[off:off + n].view(t.dtype).view(t.shape)
+        out.copy_(t)
+    return out
+
+
+class _FakeDeviceCtx:
+    """torch.cuda.device of a fake world: remembers which device the block made current."""
+
+    def __init__(self, device):
+        self.index = device if isinstance(device, int) else (torch.device(device).index or 0)
+
+    def __enter__(self):
+        _WORLD.devstack.append(self.index)
+
+    def __exit__(self, *exc):
+        _WORLD.devstack.pop()
+        return False
+
+
+class _TorchProxy:
+    """`torch` as the wrapped modules see it: torch.empty on a CUDA device gives a registered `Dev`."""
+
+    def __init__(self, real, world):
+        self._real, self._world = real, world
+
+    def __getattr__(self, name):
+        return getattr(self._real, name)
+
+    def empty(self, *size, dtype=None, device=None, **kw):
+        if len(size) == 1 and not isinstance(size[0], int):
+            size = tuple(size[0])
+        dev = None if device is None else self._real.device(device)
+        if dev is None or dev.type != "cuda":
+            return self._real.empty(size, dtype=dtype, device=device, **kw)
+        if self._world.fake:
+            return Dev.wrap(_like_a_device_allocation(self._real.empty(size, dtype=dtype, **kw)), dev)
+        return Dev.wrap(self._real.empty(size, dtype=dtype, device=dev, **kw))
+
+
+def _address(v):
+    if v is None:
+        return 0
+    if isinstance(v, int):
+        return v
+    if isinstance(v, ctypes.c_void_p):
+        return v.value or 0
+    if isinstance(v, (ctypes.Array, ctypes.Structure)):
+        return ctypes.addressof(v)
+    if hasattr(v, "_obj"):          # ctypes.byref
+        return ctypes.addressof(v._obj)
+    raise TypeError(f"pointer argument {v!r}")
+
+
+def _number(v):
+    return v.value if hasattr(v, "value") else v
+
+
+def honest(call, world):
+    """The problems of one recorded call (entry point, args) under the contract; empty when it is honest.  Judged when
+    the call is made: a tensor counts if it is alive then."""
+    name, args = call
+    proto = PROTOS[name]
+    if len(args) != len(proto):
+        return [f"{len(args)} arguments for {len(proto)} parameters"]
+    a = {p: (_address(v) if kind == "ptr" else _number(v)) for (kind, p), v in zip(proto, args)}
+    device = a["stream"] - STREAM_BASE
+    out = []
+    if world.current_device() != device:
+        out.append(f"called with device {world.current_device()} current, its tensors and stream are device {device}'s")
+    strided_args = {Meta(t).ptr for t in world.passed if not Meta(t).contiguous}
+    for kind, p in proto:
+        if kind != "ptr" or p == "stream":
+            continue
+        spec, ptr = EXTENTS[name][p], a[p]
+        if ptr == 0:
+            if not spec.nullable(a):
+                out.append(f"{p} is NULL")
+            continue
+        live, dead = world.at(ptr)
+        if spec.host:
+            if any(m.is_cuda for m in live):
+                out.append(f"{p} is HOST in the header and got a device tensor's address")
+            continue
+        if ptr in strided_args:
+            out.append(f"{p} is the address of a non-contiguous argument")
+            continue
+        if not live:
+            out.append(f"{p} is the address of " + ("a tensor that died before the call" if dead else "no tensor the wrapper was given or made"))
+            continue
+        need, dtypes = spec.nbytes(a), spec.dtypes(a)
+        reasons = []
+        for m in live:
+            r = ("a host tensor" if not m.is_cuda else f"on device {m.index}, the call is device {device}'s" if m.index != device
+                 else "not contiguous" if not m.contiguous else f"{m.dtype}, the header says {' or '.join(map(str, dtypes))}"
+                 if m.dtype not in dtypes else f"{m.nbytes} bytes, the header asks for {need}" if m.nbytes < need else None)
+            if r is None:
+                break
+            reasons.append(r)
+        else:
+            out.append(f"{p} is {reasons[0]}")
+    return out
+
+
+class Recorder:
+    """Stands in for _lib.load(): forwards what does no device work, records and judges the rest, launches nothing."""
+
+    def __init__(self, world, real):
+        self._world, self._real = world, real
+
+    def __getattr__(self, name):
+        if name in FORWARDED:
+            return getattr(self._real, name)
+        if name not in DEVICE_ENTRIES:
+            raise AttributeError(name)
+
+        def entry(*args):
+            self._world.calls.append((name, args, honest((name, args), self._world)))
+            return 0
+        return entry
+
+
+@contextlib.contextmanager
+def installed(world):
+    """While active: `world` watches, the Recorder is the library of _lib, module and mvsnet, and their `torch` is the
+    proxy.  In a fake world torch.cuda.device is the stand-in above."""
+    global _WORLD
+    real_lib = _lib.load()
+    saved = dict(load=_lib.load, stream=_lib._stream, pack=_lib.pack_weights, fpack=_lib.pack_feature_weights,
+                 cuda_device=torch.cuda.device, world=_WORLD)
+    rec = Recorder(world, real_lib)
+    _WORLD = world
+    _lib.load = lambda: rec
+    _lib._stream = lambda device: STREAM_BASE + (torch.device(device).index or 0)
+    _lib.pack_weights = lambda *a, **k: Dev.wrap(saved["pack"](*a, **k))
+    _lib.pack_feature_weights = lambda *a, **k: Dev.wrap(saved["fpack"](*a, **k))
+    for mod in (_lib, module, mvsnet):
+        mod.torch = _TorchProxy(torch, world)
+    if world.fake:
+        torch.cuda.device = _FakeDeviceCtx
+    try:
+        yield rec
+    finally:
+        _WORLD = saved["world"]
+        _lib.load, _lib._stream = saved["load"], saved["stream"]
+        _lib.pack_weights, _lib.pack_feature_weights = saved["pack"], saved["fpack"]
+        torch.cuda.device = saved["cuda_device"]
+        for mod in (_lib, module, mvsnet):
+            mod.torch = torch
+
+
+# ---- makers: the tensors of a case -------------------------------------------------------------------------------------
+_model = []
+
+
+def packed_blobs():
+    """(CostRegNet blob, FeatureNet blob) of one seeded model: host uint8 tensors, packed once."""
+    if not _model:
+        from scene_3dreconstruction_mvsnet_amd import MVSNet, synthetic
+        torch.manual_seed(0)
+        m = MVSNet(refine=False, debug=0)
+        synthetic.randomize_bn_(m, seed=0, prob_gain=30.0)
+        m.eval()
+        _model.append((m, _lib.pack_weights(m._packable_state("cost_regularization")),
+                       _lib.pack_feature_weights(m._packable_state("feature"))))
+    return _model[0][1], _model[0][2]
+
+
+class Maker:
+    """mode 'fake': Dev on the host that reports cuda:<index>; 'rec': Dev around real CUDA tensors; 'plain': CUDA
+    tensors as any caller has them (the real launches).  Values are seeded: the same case gets the same numbers."""
+
+    def __init__(self, mode, index=0):
+        self.mode, self.index = mode, index
+        self.gen = torch.Generator().manual_seed(7)
+
+    def place(self, t, index=None):
+        index = self.index if index is None else index
+        if self.mode == "fake":
+            return Dev.wrap(_like_a_device_allocation(t), torch.device("cuda", index))
+        t = t.to(torch.device("cuda", index))
+        return Dev.wrap(t) if self.mode == "rec" else t
+
+    def f(self, *shape, lo=0.5, hi=1.5, dtype=f32):
+        return self.place((torch.rand(shape, generator=self.gen, dtype=torch.float64) * (hi - lo) + lo).to(dtype))
+
+    def ints(self, values, dtype=i32):
+        return self.place(torch.tensor(values, dtype=dtype))
+
+    def u8(self, *shape):
+        return self.place(torch.randint(0, 256, shape, generator=self.gen, dtype=u8))
+
+    def ws(self, nbytes):
+        return self.place(torch.zeros(nbytes, dtype=u8))
+
+    def depths(self, D):
+        return self.place(425.0 + 2.5 * torch.arange(D, dtype=f32))
+
+    def proj(self, *lead):
+        """[..., N, 4, 4]: near-identity cameras (invertible, every view in front of the depth planes)."""
+        p = torch.eye(4, dtype=f32).expand(*lead, 4, 4) + 0.01 * torch.rand((*lead, 4, 4), generator=self.gen, dtype=f32)
+        return self.place(p.contiguous())
+
+    def rt(self, n):
+        one = torch.tensor([1, 0, 0, 0, 1, 0, 0, 0, 1, 0.5, 0.25, 0], dtype=f32)
+        return self.place((one.expand(n, 12) + 0.01 * torch.rand((n, 12), generator=self.gen, dtype=f32)).contiguous())
+
+    def blob(self, which):
+        return self.place(packed_blobs()[0 if which == "costreg" else 1].clone())
+
+    def like(self, t, shape=None, dtype=None, index=None, strided=False):
+        """A defect's tensor: `t`'s values are not kept (zeros; uint8 / float alike)."""
+        shape = tuple(t.shape) if shape is None else tuple(shape)
+        dtype = t.dtype if dtype is None else dtype
+        if strided:
+            return self.place(torch.zeros(shape[:-1] + (2 * shape[-1],), dtype=dtype), index)[..., ::2]
+        return self.place(torch.zeros(shape, dtype=dtype), index)
+
+
+# ---- the table ---------------------------------------------------------------------------------------------------------
+class Case:
+    """One wrapper: `build(m)` -> the keyword arguments of a good call (tensors, tuples of tensors, plain values);
+    `roles`: tensor leaf -> 'in' | 'out' | 'ws' | 'blob'; `entries`: the device entry points the good call records;
+    `shapes`: leaf -> [(label, shape)] relations the docstring states, each expected to be refused; `expect`:
+    (leaf, defect) -> expectation where it is not the role's default; `exempt`: (leaf, defect) -> (header, quoted text)."""
+
+    def __init__(self, name, fn, build, roles, entries, shapes=None, expect=None, exempt=None, covers=(), reproducible=True,
+                 inout=False, written=None, align=True, per_element=()):
+        self.name, self.fn, self.build, self.roles, self.entries = name, fn, build, roles, tuple(entries)
+        self.shapes, self.expect, self.exempt = shapes or {}, expect or {}, exempt or {}
+        self.covers = tuple(covers) or (name.split("@")[0],)
+        # for the real launches: `reproducible` False where the header says the bits change from run to run; `inout`: the
+        # 'out' leaves are updated in place; `written(outs)`: the part of the outputs the header says is written
+        self.reproducible, self.inout, self.written = reproducible, inout, written
+        # the entry points hold their pointers to 16 bytes (workspaces: 256) and the wrapper says so first: a contiguous
+        # view one element into a larger tensor is refused
+        self.align = align
+        # leaves the header states are per element: a view one element into a larger tensor is handed over as it is
+        # (`honest`), and tests/test_gpu_wrapper_contract.py launches it and compares with the aligned call
+        self.per_element = tuple(per_element)
+
+
+def Unaligned(*args, **kw):
+    """A case whose entry points state their own alignment (training: the library refuses; metrics and the soft-argmin
+    calls: per element, run so by their own GPU tests; filter, fusion and the cloud headers: outside the rule): no
+    `misaligned` row."""
+    return Case(*args, align=False, **kw)
+
+
+DEFECTS = ("host", "dtype:float64", "dtype:int32", "strided", "short", "other_device", "offset-shape")
+
+
+def leaves(kwargs):
+    """[(leaf name, tensor)]: 'key' for a tensor argument, 'key[i]' for the tensors of a tuple argument."""
+    out = []
+    for k, v in kwargs.items():
+        if isinstance(v, torch.Tensor):
+            out.append((k, v))
+        elif isinstance(v, (tuple, list)) and any(isinstance(x, torch.Tensor) for x in v):
+            out += [(f"{k}[{i}]", x) for i, x in enumerate(v) if isinstance(x, torch.Tensor)]
+    return out
+
+
+def replaced(kwargs, leaf, new):
+    out = dict(kwargs)
+    m = re.fullmatch(r"(\w+)\[(\d+)\]", leaf)
+    if m:
+        seq = list(out[m.group(1)])
+        seq[int(m.group(2))] = new
+        out[m.group(1)] = tuple(seq)
+    else:
+        out[leaf] = new
+    return out
+
+
+def defects_of(case, leaf, t):
+    """The defect labels that apply to one tensor leaf of a case (before exemptions)."""
+    with torch._C.DisableTorchFunctionSubclass():
+        floating = t.dtype.is_floating_point
+        other = "dtype:float32" if t.dtype == f64 else "dtype:float64"
+    out = ["host", other] + (["dtype:int32"] if floating else []) + ["strided", "short", "other_device"]
+    if case.roles[leaf] == "out":
+        out.append("offset-shape")
+    if case.align or leaf in case.per_element:
+        out.append("misaligned")
+    return out + [f"shape:{label}" for label, _ in case.shapes.get(leaf, [])]
+
+
+def default_expectation(role, defect):
+    if defect == "strided" and role == "in":
+        return "copied"
+    return "refused"
+
+
+def expectation(case, leaf, defect):
+    if defect == "misaligned" and leaf in case.per_element:
+        return "honest"
+    return case.expect.get((leaf, defect), default_expectation(case.roles[leaf], defect))
+
+
+def make_defect(case, m, leaf, t, defect):
+    with torch._C.DisableTorchFunctionSubclass():
+        shape, dtype = tuple(t.shape), t.dtype
+    if defect == "host":      # a watched host tensor: what a wrapper's `.to(device)` makes of it is seen (fake world: served)
+        return Dev.wrap(torch.zeros(shape, dtype=dtype))
+    if defect.startswith("dtype:"):
+        return m.like(t, dtype=getattr(torch, defect[6:]))
+    if defect == "strided":
+        return m.like(t, strided=True)
+    if defect == "short":
+        return m.like(t, shape=(shape[0] - 1,) + shape[1:])
+    if defect == "other_device":
+        return m.like(t, index=m.index + 1)
+    if defect == "offset-shape":
+        n = int(np.prod(shape))
+        return m.like(t, shape=(n,) if len(shape) > 1 else (1, n))
+    if defect == "misaligned":
+        n = int(np.prod(shape))
+        return m.like(t, shape=(n + 1,))[1:].view(shape)
+    if defect.startswith("shape:"):
+        return m.like(t, shape=dict(case.shapes[leaf])[defect[6:]])
+    raise KeyError(defect)
+
+
+def run_case(case, mode, leaf=None, defect=None, index=0, all_host=False):
+    """-> (verdict, detail, entry points called).  verdict: 'refused' (RuntimeError before any recorded call), 'copied'
+    (every call honest, the defective tensor's address not handed over), 'honest' (every call honest), 'late' (raised
+    after a device call), 'dishonest', or 'error:<type>' for any other exception."""
+    world = World(fake=(mode == "fake"))
+    m = Maker(mode, index)
+    raised = bad_ptr = None
+    with installed(world):
+        kwargs = case.build(m)
+        if all_host:
+            for lf, t in leaves(kwargs):
+                kwargs = replaced(kwargs, lf, make_defect(case, m, lf, t, "host"))
+        elif defect is not None:
+            bad = make_defect(case, m, leaf, dict(leaves(kwargs))[leaf], defect)
+            bad_ptr = Meta(bad).ptr
+            kwargs = replaced(kwargs, leaf, bad)
+        world.passed = [t for _, t in leaves(kwargs)]
+        for t in world.passed:
+            if not isinstance(t, Dev):
+                world.note(t)
+        try:
+            case.fn(**kwargs)
+        except RuntimeError as e:
+            raised = e
+        except Exception as e:      # noqa: BLE001 -- a wrapper that dies of a TypeError is a finding, not a refusal
+            return f"error:{type(e).__name__}", str(e), [c[0] for c in world.calls]
+    called = [c[0] for c in world.calls]
+    probs = world.problems()
+    if raised is not None:
+        if not called:
+            return "refused", str(raised), called
+        return "late", f"raised after {called}: {raised}", called
+    if probs:
+        return "dishonest", "; ".join(probs), called
+    handed = {_address(v) for name, args, _ in world.calls for (kind, _), v in zip(PROTOS[name], args) if kind == "ptr"}
+    return ("copied" if bad_ptr is not None and bad_ptr not in handed else "honest"), "", called
+
+
+def library_case_exists(expect):
+    """`library:<entry point>/<case label>` names a case of SPECS in tests/test_abi_domain_host.py."""
+    ep, label = expect[len("library:"):].split("/", 1)
+    return ep in dom.SPECS and any(lb == label for lb, _, _ in dom.cases_of(ep, dom.SPECS[ep], dom.prototypes()))
+
+
+def agrees(expect, verdict):
+    return verdict == ("honest" if expect.startswith("library:") else expect)
+
+
+EXPECTATIONS = ("refused", "copied", "honest")      # or library:<entry point>/<case>
+
+
+# -- the good calls.  D = h = w = 8, N = 3, images 8 x 8 (32 x 32 where the maps are a quarter), C = 8, M = 64 rows.
+N, D8 = 3, 8
+BOX = dict(box_min=(0.0, 0.0, 0.0), box_max=(8.0, 8.0, 8.0))
+_H = "mvs_abi.h"
+
+
+def _hdr(text, header=_H):
+    return (header, text)
+
+
+def _F64(header):
+    return (header, "MVS_CLOUD_F32 | MVS_CLOUD_F64")
+
+
+def _b_relative_proj(m):
+    return dict(proj=m.proj(N))
+
+
+def _b_warp_variance(m):
+    return dict(feats=m.f(N, 32, 8, 8), rt=m.rt(N - 1), depth_values=m.depths(8),
+                workspace=m.ws(_lib.query_workspace(N, 32, 8, 8, 8)))
+
+
+def _b_costreg_forward(m):
+    return dict(var=m.f(4, 8, 8, 8, 8), blob=m.blob("costreg"), workspace=m.ws(_lib.query_workspace(1, 32, 8, 8, 8)))
+
+
+def _b_conv_layer9(m):
+    return dict(layer=9, x=m.f(2, 4, 4, 4, 8), skip=m.f(1, 8, 8, 8, 8), blob=m.blob("costreg"))
+
+
+def _b_conv_layer0(m):
+    return dict(layer=0, x=m.f(4, 8, 8, 8, 8), skip=None, blob=m.blob("costreg"))
+
+
+def _b_conv11_prob(m):
+    return dict(x=m.f(2, 4, 4, 4, 8), skip=m.f(1, 8, 8, 8, 8), blob=m.blob("costreg"))
+
+
+def _b_softargmin_conf(m):
+    return dict(cost=m.f(8, 8, 8), depth_values=m.depths(8))
+
+
+def _b_warp_variance_backward(m):
+    return dict(feats=m.f(N, 32, 8, 8), rt=m.rt(N - 1), depth_values=m.depths(8), grad_var=m.f(32, 8, 8, 8),
+                out=m.f(N, 32, 8, 8))
+
+
+def _b_softargmin_backward(m):
+    return dict(cost=m.f(8, 8, 8), depth_values=m.depths(8), grad_depth=m.f(8, 8))
+
+
+def _b_conv3d_forward(m):
+    return dict(x=m.f(8, 8, 8, 8, lo=-1, hi=1), w=m.f(16, 8, 3, 3, 3, lo=-1, hi=1), bias=m.f(16), stride=2)
+
+
+def _b_conv3d_backward_data(m):
+    return dict(gy=m.f(4, 4, 4, 16, lo=-1, hi=1), w=m.f(16, 8, 3, 3, 3, lo=-1, hi=1), stride=2)
+
+
+def _b_conv3d_backward_weight(m):
+    return dict(x=m.f(8, 8, 8, 8, lo=-1, hi=1), gy=m.f(4, 4, 4, 16, lo=-1, hi=1), stride=2, with_bias=True)
+
+
+def _b_bn3d_forward(m):
+    return dict(y=m.f(64, 8, lo=-1, hi=1), gamma=m.f(8), beta=m.f(8), skip=m.f(64, 8), running_mean=m.f(8), running_var=m.f(8))
+
+
+def _b_bn3d_backward(m):
+    return dict(y=m.f(64, 8, lo=-1, hi=1), grad_out=m.f(64, 8, lo=-1, hi=1), gamma=m.f(8), beta=m.f(8), save_mean=m.f(8, lo=-0.1, hi=0.1),
+                save_invstd=m.f(8))
+
+
+def _b_relayout0(m):
+    return dict(src=m.f(1, 8, 8, 8, 8), direction=0, out=m.f(8, 8, 8, 8))
+
+
+def _b_relayout1(m):
+    return dict(src=m.f(8, 8, 8, 8), direction=1, out=m.f(8, 8, 8, 8))
+
+
+def _b_depth_infer(m):
+    return dict(feats=m.f(N, 32, 8, 8), proj=m.proj(N), depth_values=m.depths(8), blob=m.blob("costreg"),
+                workspace=m.ws(_lib.query_workspace(N, 32, 8, 8, 8)), depth_out=m.f(8, 8), conf_out=m.f(8, 8))
+
+
+def _b_depth_infer_views(m):
+    return dict(_b_depth_infer(m), feats=m.f(4, 32, 8, 8), view_ids=[2, 0, 3])
+
+
+def _b_filter_depth(m):
+    return dict(depth=m.f(2, 8, 8), conf=m.f(2, 8, 8), ref_mats=m.f(2, 30), pair_mats=m.f(2, 1, 42),
+                ref_idx=m.ints([0, 1]), src_idx=m.ints([[1], [0]]))
+
+
+def _b_fuse_points(m):
+    return dict(xyz_world=m.f(2, 64, 3, dtype=f64), masks=m.u8(2, 3, 8, 8), images=m.u8(2, 3, 32, 32), ref_idx=m.ints([0, 1]),
+                out=(m.f(128, 3), m.u8(128, 3), m.ints([0, 0, 0])))
+
+
+def _cloud(m, P=64):
+    return m.f(P, 3, lo=0.5, hi=7.5)
+
+
+def _b_cloud_downsample(m):
+    return dict(BOX, xyz=_cloud(m), rgb=m.u8(64, 3), voxel_size=2.0, out=(m.f(64, 3), m.u8(64, 3), m.ints([0, 0], i64)))
+
+
+def _b_cloud_downsample_normals(m):
+    return dict(BOX, xyz=_cloud(m), rgb=m.u8(64, 3), normals=m.f(64, 3), voxel_size=2.0,
+                out=(m.f(64, 3), m.u8(64, 3), m.f(64, 3), m.ints([0, 0], i64)))
+
+
+def _b_cloud_normals(m):
+    return dict(BOX, xyz=_cloud(m), cell=2.0, knn=4, view_starts=m.ints([0, 32, 64], i64), centres=m.f(2, 3, dtype=f64),
+                neighbours=True, out=(m.f(64, 3), m.ints([[0] * 4] * 64), m.ints([0, 0, 0], i64)))
+
+
+def _b_cloud_outliers(m):
+    return dict(BOX, xyz=_cloud(m), cell=2.0, nb_neighbors=4, masked=True,
+                out=(m.f(64, dtype=f64), m.ints([False] * 64, torch.bool), m.f(64, 3), m.ints([0] * 3, i64), m.f(3, dtype=f64)))
+
+
+def _b_cloud_distance(m):
+    return dict(BOX, ref=_cloud(m), query=_cloud(m, 32), cell=2.0, max_dist=4.0, thresholds=(0.5, 1.0), indices=True,
+                out=(m.f(32, dtype=f64), m.ints([0] * 32), m.ints([0] * 4, i64), m.f(2, dtype=f64)))
+
+
+def _b_cloud_reduce(m):
+    return dict(BOX, xyz=_cloud(m), cell=2.0, min_dist=0.5, out=(m.ints([False] * 64, torch.bool), m.ints([0] * 4, i64)))
+
+
+def _b_cloud_select(m):
+    return dict(xyz=_cloud(m), mask=m.u8(4, 4, 4), origin=(0.0, 0.0, 0.0), res=2.0, plane=(0.0, 0.0, 1.0, 0.0),
+                out=(m.ints([False] * 64, torch.bool), m.ints([0] * 3, i64)))
+
+
+def _b_cloud_cluster(m):
+    return dict(BOX, xyz=_cloud(m), cell=2.0, eps=1.0, min_points=2,
+                out=(m.ints([0] * 64), m.ints([False] * 64, torch.bool), m.ints([0] * 7, i64)))
+
+
+def _b_feature_layer0(m):
+    return dict(layer=0, x=m.f(1, 3, 8, 8, lo=0, hi=1), fblob=m.blob("feature"))
+
+
+def _b_feature_layer2(m):
+    return dict(layer=2, x=m.f(1, 1, 8, 8, 8), fblob=m.blob("feature"))
+
+
+def _b_feature_conv01(m):
+    return dict(imgs=m.f(1, 3, 8, 8, lo=0, hi=1), fblob=m.blob("feature"))
+
+
+def _b_feature_net(m):
+    return dict(imgs=m.f(1, 3, 8, 8, lo=0, hi=1), fblob=m.blob("feature"), workspace=m.ws(_lib.query_feature_workspace(1, 8, 8)),
+                out=m.f(1, 32, 2, 2))
+
+
+def _b_feature_net_u8(m):
+    return dict(_b_feature_net(m), imgs=m.u8(1, 8, 8, 3))
+
+
+def _b_forward_images(m):
+    return dict(imgs=m.f(N, 3, 32, 32, lo=0, hi=1), proj=m.proj(N), depth_values=m.depths(8), fblob=m.blob("feature"),
+                blob=m.blob("costreg"), workspace=m.ws(_lib.query_forward_workspace(N, 32, 32, 8)), depth_out=m.f(8, 8),
+                conf_out=m.f(8, 8))
+
+
+def _b_depth_metrics(m):
+    return dict(depth_est=m.f(2, 8, 8), depth_gt=m.f(2, 8, 8), mask=m.f(2, 8, 8, lo=0, hi=1), sums_out=m.f(2, 7, dtype=f64),
+                errmap=True, workspace=m.ws(_lib.query_metrics_workspace(2, 8, 8)))
+
+
+def _b_homo_warping(m):
+    return dict(src_fea=m.f(2, 32, 8, 8), src_proj=m.proj(2), ref_proj=m.proj(2), depth_values=m.f(2, 8, lo=425, hi=445))
+
+
+def _b_depth_regression(m):
+    return dict(p=m.f(2, 8, 8, 8, lo=0, hi=0.25), depth_values=m.f(2, 8, lo=425, hi=445))
+
+
+def _rows_written(count_of):
+    """Outputs whose rows at and beyond a count are not written: the written rows and the counts."""
+    def written(outs):
+        *rows, counts = outs
+        n = int(count_of(counts))
+        return tuple(r[:n] for r in rows) + (counts,)
+    return written
+
+
+_WS_SHORT = "workspace one byte short"
+_IN, _OUT = "in", "out"
+_OUT3 = {"out[0]": _OUT, "out[1]": _OUT, "out[2]": _OUT}
+
+CASES = [
+    Case("relative_proj", _lib.relative_proj, _b_relative_proj, dict(proj=_IN), ["mvs_relative_proj"],
+         exempt={("proj", "short"): _hdr("proj   dev fp32 [N][4][4]      rt_out dev fp32 [(N-1)][12]")},
+         shapes=dict(proj=[("[N,3,4]", (N, 3, 4))]), expect={("proj", "other_device"): "honest"}),
+    Case("warp_variance", _lib.warp_variance, _b_warp_variance, dict(feats=_IN, rt=_IN, depth_values=_IN, workspace="ws"),
+         ["mvs_warp_variance"], shapes=dict(depth_values=[("[1,D]", (1, 8))], feats=[("C=16", (N, 16, 8, 8))]),
+         per_element=("feats",),
+         expect={("workspace", "short"): f"library:mvs_warp_variance/{_WS_SHORT}",
+                 ("feats", "shape:C=16"): "library:mvs_warp_variance/rule {'C': 16}",
+                 ("depth_values", "short"): "library:mvs_warp_variance/rule {'D': 12}"}),
+    Case("costreg_forward", _lib.costreg_forward, _b_costreg_forward, dict(var=_IN, blob="blob", workspace="ws"),
+         ["mvs_costreg_forward"], shapes=dict(var=[("[4,D,h,w,4]", (4, 8, 8, 8, 4))]),
+         expect={("var", "strided"): "refused", ("workspace", "short"): f"library:mvs_costreg_forward/{_WS_SHORT}"},
+         exempt={("var", "short"): _hdr("var           dev C8-planar [4][D][h][w][8] in `dtype` (from mvs_warp_variance)")}),
+    Case("conv_layer@9", _lib.conv_layer, _b_conv_layer9, dict(x=_IN, skip=_IN, blob="blob"), ["mvs_conv_layer"],
+         shapes=dict(skip=[("[1,8,8,4,8]", (1, 8, 8, 4, 8))]),
+         expect={("x", "strided"): "refused", ("skip", "strided"): "refused"}),
+    Case("conv_layer@0", _lib.conv_layer, _b_conv_layer0, dict(x=_IN, blob="blob"), ["mvs_conv_layer"],
+         expect={("x", "strided"): "refused"}),
+    Case("conv11_prob", _lib.conv11_prob, _b_conv11_prob, dict(x=_IN, skip=_IN, blob="blob"), ["mvs_conv11_prob"],
+         expect={("x", "strided"): "refused", ("skip", "strided"): "refused"}),
+    Unaligned("softargmin_conf", _lib.softargmin_conf, _b_softargmin_conf, dict(cost=_IN, depth_values=_IN), ["mvs_softargmin_conf"],
+              per_element=("cost",),
+         shapes=dict(depth_values=[("[1,D]", (1, 8))])),
+    Case("warp_variance_backward", _lib.warp_variance_backward, _b_warp_variance_backward,
+         dict(feats=_IN, rt=_IN, depth_values=_IN, grad_var=_IN, out=_OUT), ["mvs_warp_variance_backward"],
+         shapes=dict(grad_var=[("[C,D-1,h,w]", (32, 7, 8, 8))]), reproducible=False),
+    Unaligned("softargmin_backward", _lib.softargmin_backward, _b_softargmin_backward, dict(cost=_IN, depth_values=_IN, grad_depth=_IN),
+         ["mvs_softargmin_backward"], shapes=dict(grad_depth=[("[h,w-1]", (8, 7))])),
+    Unaligned("conv3d_train_forward", _lib.conv3d_train_forward, _b_conv3d_forward, dict(x=_IN, w=_IN, bias=_IN),
+         ["mvs_conv3d_train_forward"], shapes=dict(x=[("odd D at stride 2", (7, 8, 8, 8)), ("odd W at stride 2", (8, 8, 7, 8))],
+                                                   w=[("Cin+8", (16, 16, 3, 3, 3))])),
+    Unaligned("conv3d_train_backward_data", _lib.conv3d_train_backward_data, _b_conv3d_backward_data, dict(gy=_IN, w=_IN),
+         ["mvs_conv3d_train_backward_data"], shapes=dict(gy=[("Cout-8", (4, 4, 4, 8))]),
+         exempt={("gy", "short"): _hdr("mvs_conv3d_train_backward_data: gx [D][H][W][Cin] from gy [D/s][H/s][W/s][Cout]; every voxel of gx is written."),
+                 ("w", "short"): _hdr("mvs_conv3d_train_backward_data: gx [D][H][W][Cin] from gy [D/s][H/s][W/s][Cout]; every voxel of gx is written.")}),
+    Unaligned("conv3d_train_backward_weight", _lib.conv3d_train_backward_weight, _b_conv3d_backward_weight, dict(x=_IN, gy=_IN),
+         ["mvs_conv3d_train_backward_weight"], shapes=dict(x=[("odd H at stride 2", (8, 7, 8, 8))])),
+    Unaligned("bn3d_train_forward", _lib.bn3d_train_forward, _b_bn3d_forward,
+         dict(y=_IN, gamma=_IN, beta=_IN, skip=_IN, running_mean=_OUT, running_var=_OUT), ["mvs_bn3d_train_forward"],
+         inout=True),
+    Unaligned("bn3d_train_backward", _lib.bn3d_train_backward, _b_bn3d_backward,
+         dict(y=_IN, grad_out=_IN, gamma=_IN, beta=_IN, save_mean=_IN, save_invstd=_IN), ["mvs_bn3d_train_backward"]),
+    Unaligned("volume_relayout@0", _lib.volume_relayout, _b_relayout0, dict(src=_IN, out=_OUT), ["mvs_volume_relayout"]),
+    Unaligned("volume_relayout@1", _lib.volume_relayout, _b_relayout1, dict(src=_IN, out=_OUT), ["mvs_volume_relayout"]),
+    Case("depth_infer", _lib.depth_infer, _b_depth_infer,
+         dict(feats=_IN, proj=_IN, depth_values=_IN, blob="blob", workspace="ws", depth_out=_OUT, conf_out=_OUT), ["mvs_depth_infer"],
+         shapes=dict(proj=[("[N-1,4,4]", (N - 1, 4, 4))], depth_values=[("[1,D]", (1, 8))]),
+         per_element=("feats", "depth_out", "conf_out")),      # the library is asked first here: short ones are refused
+    Case("depth_infer_views", _lib.depth_infer_views, _b_depth_infer_views,
+         dict(feats=_IN, proj=_IN, depth_values=_IN, blob="blob", workspace="ws", depth_out=_OUT, conf_out=_OUT),
+         ["mvs_depth_infer_views"], shapes=dict(proj=[("[N,4,3]", (N, 4, 3))], depth_values=[("[1,D]", (1, 8))]),
+         per_element=("feats", "depth_out", "conf_out"),
+         expect={("workspace", "short"): f"library:mvs_depth_infer_views/{_WS_SHORT}",
+                 ("depth_values", "short"): "library:mvs_depth_infer_views/rule {'D': 12}"},
+         exempt={("feats", "short"): _hdr("feats     dev fp32 [V][C][h][w]  (any V >= 1; e.g. FeatureNet outputs of every view of a scan)")}),
+    Unaligned("filter_depth", _lib.filter_depth, _b_filter_depth,
+         dict(depth=_IN, conf=_IN, ref_mats=_IN, pair_mats=_IN, ref_idx=_IN, src_idx=_IN), ["mvs_filter_depth"]),
+    Unaligned("fuse_points", _lib.fuse_points, _b_fuse_points, dict(_OUT3, xyz_world=_IN, masks=_IN, images=_IN, ref_idx=_IN),
+         ["mvs_fuse_points"], expect={("images", "short"): "honest"},      # V is read from images
+         written=_rows_written(lambda counts: min(int(counts[-1]), 128))),
+    Unaligned("cloud_downsample", _lib.cloud_downsample, _b_cloud_downsample, dict(_OUT3, xyz=_IN, rgb=_IN), ["mvs_cloud_downsample"],
+         covers=("cloud_downsample", "_downsample"), written=_rows_written(lambda counts: counts[1]), exempt={("xyz", "dtype:float64"): _F64("mvs_cloud_abi.h")}),
+    Unaligned("cloud_downsample_normals", _lib.cloud_downsample_normals, _b_cloud_downsample_normals,
+         {**_OUT3, "out[3]": _OUT, "xyz": _IN, "rgb": _IN, "normals": _IN}, ["mvs_cloud_downsample_normals"],
+         covers=("cloud_downsample_normals", "_downsample"), written=_rows_written(lambda counts: counts[1]), exempt={("xyz", "dtype:float64"): _F64("mvs_normals_abi.h")}),
+    Unaligned("cloud_normals", _lib.cloud_normals, _b_cloud_normals, dict(_OUT3, xyz=_IN, view_starts=_IN, centres=_IN),
+         ["mvs_cloud_normals"], exempt={("xyz", "dtype:float64"): _F64("mvs_normals_abi.h")}),
+    Unaligned("cloud_outliers", _lib.cloud_outliers, _b_cloud_outliers,
+         {**_OUT3, "out[3]": _OUT, "out[4]": _OUT, "xyz": _IN}, ["mvs_cloud_outliers"],
+         exempt={("xyz", "dtype:float64"): _F64("mvs_outliers_abi.h")}),
+    Unaligned("cloud_distance", _lib.cloud_distance, _b_cloud_distance, {**_OUT3, "out[3]": _OUT, "ref": _IN, "query": _IN},
+         ["mvs_cloud_distance"], expect={("ref", "short"): "honest"},      # P is read from ref
+         exempt={("ref", "dtype:float64"): _F64("mvs_distance_abi.h"), ("query", "dtype:float64"): _F64("mvs_distance_abi.h")}),
+    Unaligned("cloud_reduce", _lib.cloud_reduce, _b_cloud_reduce, {"out[0]": _OUT, "out[1]": _OUT, "xyz": _IN}, ["mvs_cloud_reduce"],
+         exempt={("xyz", "dtype:float64"): _F64("mvs_reduce_abi.h")}),
+    Unaligned("cloud_select", _lib.cloud_select, _b_cloud_select, {"out[0]": _OUT, "out[1]": _OUT, "xyz": _IN, "mask": _IN},
+         ["mvs_cloud_select"], expect={("mask", "short"): "honest"},      # n is read from mask
+         exempt={("xyz", "dtype:float64"): _F64("mvs_reduce_abi.h")}),
+    Unaligned("cloud_cluster", _lib.cloud_cluster, _b_cloud_cluster, dict(_OUT3, xyz=_IN), ["mvs_cloud_cluster"],
+         exempt={("xyz", "dtype:float64"): _F64("mvs_cluster_abi.h")}),
+    Case("feature_layer@0", _lib.feature_layer, _b_feature_layer0, dict(x=_IN, fblob="blob"), ["mvs_feature_layer"]),
+    Case("feature_layer@2", _lib.feature_layer, _b_feature_layer2, dict(x=_IN, fblob="blob"), ["mvs_feature_layer"]),
+    Case("feature_conv01", _lib.feature_conv01, _b_feature_conv01, dict(imgs=_IN, fblob="blob"), ["mvs_feature_conv01_fmt"]),
+    Case("feature_net", _lib.feature_net, _b_feature_net, dict(imgs=_IN, fblob="blob", workspace="ws", out=_OUT),
+         ["mvs_feature_net_fmt"], expect={("workspace", "short"): f"library:mvs_feature_net_fmt/{_WS_SHORT}"}),
+    Case("feature_net@u8", _lib.feature_net, _b_feature_net_u8, dict(imgs=_IN, fblob="blob", workspace="ws", out=_OUT),
+         ["mvs_feature_net_fmt"], expect={("workspace", "short"): f"library:mvs_feature_net_fmt/{_WS_SHORT}"}),
+    Case("forward_images", _lib.forward_images, _b_forward_images,
+         dict(imgs=_IN, proj=_IN, depth_values=_IN, fblob="blob", blob="blob", workspace="ws", depth_out=_OUT, conf_out=_OUT),
+         ["mvs_forward_images_fmt"], shapes=dict(proj=[("[N-1,4,4]", (N - 1, 4, 4))], depth_values=[("[1,D]", (1, 8))]),
+         per_element=("depth_out", "conf_out"),
+         expect={("workspace", "short"): f"library:mvs_forward_images_fmt/{_WS_SHORT}",
+                 ("depth_values", "short"): "library:mvs_forward_images_fmt/rule {'D': 12}"}),
+    Unaligned("depth_metrics", _lib.depth_metrics, _b_depth_metrics,
+         dict(depth_est=_IN, depth_gt=_IN, mask=_IN, sums_out=_OUT, workspace="ws"), ["mvs_depth_metrics"],
+         # a workspace that is too small or elsewhere is replaced by one of the wrapper's own, as it always was
+         expect={("workspace", "host"): "copied", ("workspace", "short"): "copied", ("workspace", "other_device"): "copied"}),
+    Case("homo_warping", module.homo_warping, _b_homo_warping, dict(src_fea=_IN, src_proj=_IN, ref_proj=_IN, depth_values=_IN),
+         ["mvs_relative_proj", "mvs_homo_warp"], shapes=dict(depth_values=[("[B,D,1]", (2, 8, 1))]),
+         align=False, per_element=("src_fea", "depth_values"),
+         # the matrices are stacked and cast to float32, as the reference's float() does: a copy is handed over
+         expect={(p, d): "copied" for p in ("src_proj", "ref_proj") for d in ("dtype:float64", "dtype:int32")}),
+    Unaligned("depth_regression", module.depth_regression, _b_depth_regression, dict(p=_IN, depth_values=_IN), ["mvs_depth_regression"],
+              per_element=("p",),
+         shapes=dict(depth_values=[("[B,D-3]", (2, 5)), ("[D-3]", (5,))]),
+         # depth_values is moved to p's device, as it always was
+         expect={("p", "other_device"): "honest", ("depth_values", "other_device"): "copied", ("depth_values", "host"): "copied"}),
+]
+CASE = {c.name: c for c in CASES}
+
+
+def table_rows(case, mode="fake"):
+    """[(leaf, defect)] of one case, exemptions left out."""
+    with installed(World(fake=(mode == "fake"))):
+        kwargs = case.build(Maker(mode))
+    return [(leaf, d) for leaf, t in leaves(kwargs) for d in defects_of(case, leaf, t) if (leaf, d) not in case.exempt]
+
+
+def all_rows():
+    return [(c.name, leaf, d) for c in CASES for leaf, d in table_rows(c)]
+
+
+# ---- which functions must be in the table -----------------------------------------------------------------------------
+def functions_that_name_a_device_entry_point():
+    """{module.function: {entry points}} of _lib.py and module.py: an attribute `.mvs_x` or a string constant "mvs_x"
+    in the function's code (its docstring is prose and does not count)."""
+    out = {}
+    for mod in (_lib, module):
+        tree = ast.parse(inspect.getsource(mod))
+        for node in tree.body:
+            if not isinstance(node, ast.FunctionDef):
+                continue
+            names = set()
+            for sub in ast.walk(node):
+                if isinstance(sub, ast.Attribute) and sub.attr in DEVICE_ENTRIES:
+                    names.add(sub.attr)
+                elif isinstance(sub, ast.Constant) and isinstance(sub.value, str) and sub.value in DEVICE_ENTRIES:
+                    names.add(sub.value)
+            if names:
+                out[node.name] = names
+    return out
+
+
+def _one_element_in(arena, t, role):
+    """`t` as a contiguous view one element into a larger tensor of the arena (an input: with its values)."""
+    n = t.numel()
+    if role == "out":
+        return arena.carve((n + 1,), t.dtype, "out")[1:].view(t.shape)
+    flat = torch.zeros(n + 1, dtype=t.dtype, device=t.device)
+    flat[1:] = t.reshape(-1)
+    return arena.put(flat, "in")[1:].view(t.shape)
+
+
+def real_outputs(case, leaf, arena, strided, offset=False):
+    """One real launch (no Recorder) of the case's good call with every tensor carved from `arena` (a guarded.Arena or
+    guarded.Plain): `leaf` as a [..., ::2] view of a tensor twice as wide (strided) or as its contiguous clone.  Returns
+    the outputs the header says are written."""
+    kwargs = case.build(Maker("plain"))
+    outs = []
+    for lf, t in leaves(kwargs):
+        role = case.roles[lf]
+        if lf == leaf and offset:
+            new = _one_element_in(arena, t, role)
+            assert new.is_contiguous() and new.data_ptr() % 16 == t.element_size() % 16
+            if role == "out":
+                outs.append(new)
+        elif lf == leaf and strided:
+            parent = torch.zeros(tuple(t.shape[:-1]) + (2 * t.shape[-1],), dtype=t.dtype, device=t.device)
+            parent[..., ::2] = t
+            new = arena.put(parent, "in")[..., ::2]
+            assert not new.is_contiguous() and torch.equal(new, t)
+        elif role == "out":
+            new = arena.put(t, "inout") if case.inout else arena.carve(tuple(t.shape), t.dtype, "out")
+            outs.append(new)
+        elif role == "ws":
+            new = arena.carve(tuple(t.shape), t.dtype, "scratch")
+        else:
+            new = arena.put(t, "in")
+        kwargs = replaced(kwargs, lf, new)
+    with arena.intercept(_lib), arena.intercept(module):
+        ret = case.fn(**kwargs)
+    if ret is not None:
+        outs = [ret] if isinstance(ret, torch.Tensor) else [o for o in ret if o is not None]
+    return case.written(outs) if case.written else tuple(outs)
+
+
+def sweep(mode="fake"):
+    """Every row of the table -> [(case, leaf, defect, expectation, verdict, detail)], the good calls first (leaf None)."""
+    out = []
+    for c in CASES:
+        v, detail, called = run_case(c, mode)
+        out.append((c.name, None, "good", "honest", v if set(c.entries) <= set(called) or v != "honest" else "honest-but-" + str(called), detail))
+        for leaf, d in table_rows(c, mode):
+            if d == "other_device" and mode != "fake" and torch.cuda.device_count() < 2:
+                continue
+            v, detail, _ = run_case(c, mode, leaf, d)
+            out.append((c.name, leaf, d, expectation(c, leaf, d), v, detail))
+    return out
+
+
+def violations(rows):
+    return [r for r in rows if not agrees(r[3], r[4])]
+
+
+if __name__ == "__main__":      # the sweep as a list: python tests/wrapper_contract.py
+    rows = sweep()
+    bad = violations(rows)
+    for name, leaf, d, want, got, detail in bad:
+        print(f"{name:30s} {str(leaf):14s} {d:22s} expected {want:10s} got {got:10s} {detail[:int(os.environ.get('WIDTH', 150))]}")
+    print(f"{len(bad)} violations in {len(rows)} rows")
