@@ -97,10 +97,3 @@ def run_once(key, argv, **kwargs):
     if key not in _once:
         _once[key] = run(argv, **kwargs)
     return _once[key]
-
-
-def refusal_records(test_file):
-    """{(ep, case): record} of the "R " lines that `test_file --refusals` prints in a child that sees no device."""
-    r = run_once(test_file, [test_file, "--refusals"], timeout=300, gpu=False)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return {(x["ep"], x["case"]): x for x in r.records("R ")}

@@ -1,15 +1,18 @@
 """The shape domain include/mvs_abi.h states for every depth-path entry point, held to the library from the refused
-side with fake pointers (256-byte aligned addresses that are never dereferenced: every refusal is decided on the host
-before anything is enqueued).  The whole sweep runs in a child process that sees no device (HIP_VISIBLE_DEVICES and
-ROCR_VISIBLE_DEVICES empty), so a call the library fails to refuse cannot reach hardware: its first HIP call fails, it
-comes back as MVS_ERR_HIP (4) and is reported as "reached a HIP call".  The accepted side of a bound is asserted only
-through the mvs_query_* functions, which do no device work.  A second child repeats the sweep under
-MVS_FORCE_DIRECT=1 (the environment is read once per process).
+side with made-up pointers (256-byte aligned addresses that are never dereferenced: every refusal is decided on the host
+before anything is enqueued).  The whole sweep is run by tests/refusals.py in a child process that sees no device, so a
+call the library fails to refuse cannot reach hardware: it comes back as MVS_ERR_HIP (4) and is reported as "reached a
+HIP call".  The accepted side of a bound is asserted only through the mvs_query_* functions, which do no device work.  A
+second child repeats the sweep under MVS_FORCE_DIRECT=1 (the environment is read once per process).
 
-SPECS is keyed by entry point.  The completeness test parses the header's prototypes: a device entry point without an
-entry, a pointer parameter with neither a NULL case nor an `optional` entry, or an int parameter without a below-range
-case fails this file."""
+SPECS is keyed by entry point.  The completeness test reads the prototypes of every header of include/ and the tables
+of every host module: an entry point with a `stream` parameter without cases in a no-device child, a pointer parameter
+with neither a NULL case nor an `optional` entry, or, in mvs_abi.h, an int parameter without a below-range case or a
+device pointer without an alignment case fails this file."""
 import ctypes
+import functools
+import glob
+import importlib
 import json
 import os
 import re
@@ -19,14 +22,9 @@ import threading
 import numpy as np
 import pytest
 
-import gpu_child
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
-
-OK, BAD_SHAPE, BAD_DTYPE, WORKSPACE, HIP, NULL = 0, 1, 2, 3, 4, 5
+import refusals
+from refusals import BAD_DTYPE, BAD_SHAPE, HERE, NULL, OK, WORKSPACE
+from scene_3dreconstruction_mvsnet_amd import _lib
 
 # ---- Python restatements of the library's byte counts (csrc/mvs_internal.h) ---------------------------------------
 _LEVEL_OUT = (0, 1, 1, 2, 2, 3, 3, 2, 1, 0)
@@ -69,8 +67,8 @@ _FEATURE_CH = ((3, 8, 3), (8, 8, 3), (8, 16, 5), (16, 16, 3), (16, 16, 3), (16, 
 # below / above: int argument -> out-of-range values (-> `code`, BAD_SHAPE unless stated); an `above` value may be a
 #           dict that moves other arguments too (a bound on a product)
 # rules:    (override, code) for the rules that tie arguments together
-# ws:       restated smallest workspace (blob) of the good call: one byte less and a pointer at +16 give WORKSPACE
-# host:     arguments that are real host arrays
+# sizes:    `need` restates the smallest workspace of the call: one byte less and a pointer at +16 give WORKSPACE
+# host:     arguments that are real host arrays, built in the child (tests/refusals.py)
 VOL = dict(N=3, C=32, D=16, h=16, w=24, dtype=0)
 VOL_BELOW = dict(N=[0, -8], C=[0, -8], D=[0, -8], h=[0, -8], w=[0, -8])
 G30 = 1 << 30         # cubed it is 0 mod 2^64: a product formed in size_t would pass every "< 2^31" test
@@ -89,20 +87,52 @@ FWD_RULES = [(dict(H=68), 1), (dict(W=100), 1), (dict(H=80), 1), (dict(W=112), 1
 BIG = 4096
 PIX_MAX = (1 << 31) - 256
 
+
+
+@functools.lru_cache(None)
+def _pack_arrays(kind):
+    """conv weights, BatchNorm vectors, bias and blob of a pack call: real host arrays, made once in the child"""
+    if kind == "costreg":
+        convs = [np.ones(27 * ci * co, np.float32) for ci, co in _COSTREG_CH]
+        bns = [np.ones(_COSTREG_CH[k // 4][1], np.float32) for k in range(40)]
+        return convs, bns, np.ones(1, np.float32), np.zeros(_lib.query_weights_blob(), np.uint8)
+    convs = [np.ones(k * k * ci * co, np.float32) for ci, co, k in _FEATURE_CH]
+    bns = [np.ones(_FEATURE_CH[k // 4][1], np.float32) for k in range(28)]
+    return convs, bns, np.ones(32, np.float32), np.zeros(_lib.query_feature_blob(), np.uint8)
+
+
+def _pack(kind):
+    """The spec entries of a pack function: `null_conv` / `null_bn` name the array whose pointer is NULL."""
+    def pointers(which, null):
+        def build(a, ov):
+            ptrs = [x.ctypes.data for x in _pack_arrays(kind)[which]]
+            if null in ov:
+                ptrs[ov[null]] = None
+            return (ctypes.c_void_p * len(ptrs))(*ptrs)
+        return build
+    bias = "prob_bias" if kind == "costreg" else "feature_bias"
+    return dict(good=dict(eps=1e-5, blob_bytes="blob"), pack=kind, extra=("null_conv", "null_bn"),
+                sizes=dict(blob=lambda a: _pack_arrays(kind)[3].size),
+                host={"conv_weights": pointers(0, "null_conv"), "bn_params": pointers(1, "null_bn"),
+                      bias: lambda a, ov: ctypes.c_void_p(_pack_arrays(kind)[2].ctypes.data),
+                      "blob_out": lambda a, ov: ctypes.c_void_p(_pack_arrays(kind)[3].ctypes.data)})
+
+
+VIEWS = dict(view_idx=lambda a, ov: (ctypes.c_int * 64)(*a["view_idx"]))
+
 SPECS = {
-    "mvs_query_workspace": dict(good=VOL, below=VOL_BELOW, above=VOL_ABOVE, rules=VOL_RULES, dtypes=DTYPES,
-                                host=("bytes",)),
-    "mvs_query_weights_blob": dict(good={}, host=("bytes",)),
-    "mvs_pack_weights": dict(good={}, host=("conv_weights", "bn_params", "prob_bias", "blob_out"), pack="costreg"),
+    "mvs_query_workspace": dict(good=VOL, below=VOL_BELOW, above=VOL_ABOVE, rules=VOL_RULES, dtypes=DTYPES),
+    "mvs_query_weights_blob": dict(good={}),
+    "mvs_pack_weights": _pack("costreg"),
     "mvs_relative_proj": dict(good=dict(N=3), below=dict(N=[0, -8]), above=dict(N=[65])),
     "mvs_warp_variance": dict(good=VOL, below=VOL_BELOW, above=VOL_ABOVE, rules=VOL_RULES + [(dict(rt=None), NULL)],
                               dtypes=DTYPES,
                               optional=dict(rt=dict(with_=dict(N=1), D=0)),
-                              ws=lambda a: feats_region_bytes(a["N"], a["h"], a["w"])),
+                              sizes=dict(need=lambda a: feats_region_bytes(a["N"], a["h"], a["w"]))),
     "mvs_costreg_forward": dict(good=dict(D=16, h=16, w=24, dtype=0),
                                 below={k: VOL_BELOW[k] for k in "Dhw"}, above={k: VOL_ABOVE[k] for k in "Dhw"},
                                 rules=VOL_RULES[:3], dtypes=DTYPES,
-                                ws=lambda a: workspace_bytes(1, a["D"], a["h"], a["w"], a["dtype"])),
+                                sizes=dict(need=lambda a: workspace_bytes(1, a["D"], a["h"], a["w"], a["dtype"]))),
     "mvs_conv_layer": dict(good=dict(layer=0, Di=8, Hi=8, Wi=8, dtype=0),
                            below=dict(layer=[-1], Di=[0, -8], Hi=[0, -8], Wi=[0, -8]),
                            above=dict(layer=[11], Di=[dict(Di=1 << 28, Hi=1, Wi=1)], Hi=[dict(Di=1, Hi=1 << 28, Wi=1)],
@@ -130,13 +160,13 @@ SPECS = {
                                            w=[dict(h=1, w=PIX_MAX + 1)]),
                                 rules=[(dict(D=8, h=65536, w=65536), 1), (dict(D=8, h=46341, w=46341), 1)]),
     "mvs_depth_infer": dict(good=VOL, below=VOL_BELOW, above=VOL_ABOVE, rules=VOL_RULES, dtypes=DTYPES,
-                            ws=lambda a: workspace_bytes(a["N"], a["D"], a["h"], a["w"], a["dtype"])),
-    "mvs_depth_infer_views": dict(good=dict(VOL, V=5), host=("view_idx",),
+                            sizes=dict(need=lambda a: workspace_bytes(a["N"], a["D"], a["h"], a["w"], a["dtype"]))),
+    "mvs_depth_infer_views": dict(good=dict(VOL, V=5, view_idx=lambda a: list(range(max(a["N"], 0) % 64))), host=VIEWS,
                                   below=dict(VOL_BELOW, V=[0, -8]), above=VOL_ABOVE,
                                   rules=VOL_RULES + [(dict(view_idx=[0, -1, 2]), 1), (dict(view_idx=[0, 1, 5]), 1),
                                                      (dict(view_idx=[5, 1, 2]), 1)],
                                   dtypes=DTYPES,
-                                  ws=lambda a: workspace_bytes(a["N"], a["D"], a["h"], a["w"], a["dtype"])),
+                                  sizes=dict(need=lambda a: workspace_bytes(a["N"], a["D"], a["h"], a["w"], a["dtype"]))),
     "mvs_homo_warp": dict(good=dict(C=32, D=16, h=16, w=24),
                           below=dict(C=[0, -8], D=[0, -8], h=[0, -8, 1], w=[0, -8, 1]),
                           above=dict(C=[dict(C=(1 << 23) + 1, D=1 << 18, h=1 << 10, w=1 << 10)],
@@ -146,10 +176,9 @@ SPECS = {
     "mvs_depth_regression": dict(good=dict(D=16, h=16, w=24), below=dict(D=[0, -8], h=[0, -8], w=[0, -8]),
                                  above=dict(h=[dict(h=PIX_MAX + 1, w=1)], w=[dict(h=1, w=PIX_MAX + 1)]),
                                  rules=[(dict(D=8, h=65536, w=65536), 1)]),
-    "mvs_query_feature_blob": dict(good={}, host=("bytes",)),
-    "mvs_pack_feature_weights": dict(good={}, host=("conv_weights", "bn_params", "feature_bias", "blob_out"),
-                                     pack="feature"),
-    "mvs_query_feature_workspace": dict(good=IMG, below=IMG_BELOW, above=IMG_ABOVE, host=("bytes",)),
+    "mvs_query_feature_blob": dict(good={}),
+    "mvs_pack_feature_weights": _pack("feature"),
+    "mvs_query_feature_workspace": dict(good=IMG, below=IMG_BELOW, above=IMG_ABOVE),
     "mvs_feature_layer": dict(good=dict(layer=0, N=2, Hi=64, Wi=96),
                               below=dict(layer=[-1], N=[0, -8], Hi=[0, -8, 3], Wi=[0, -8, 3]),
                               above=dict(layer=[8], N=[65536], Hi=[dict(N=1, Hi=1 << 26, Wi=4), dict(N=2, Hi=G30, Wi=G30)],
@@ -157,21 +186,20 @@ SPECS = {
     "mvs_feature_conv01_fmt": dict(good=dict(IMG, image_format=0), below=IMG_BELOW, above=IMG_ABOVE,
                                    dtypes=dict(image_format=[3, -1])),
     "mvs_feature_net": dict(good=IMG, below=IMG_BELOW, above=IMG_ABOVE,
-                            ws=lambda a: feature_workspace_bytes(a["N"], a["H"], a["W"])),
+                            sizes=dict(need=lambda a: feature_workspace_bytes(a["N"], a["H"], a["W"]))),
     "mvs_feature_net_fmt": dict(good=dict(IMG, image_format=2), below=IMG_BELOW, above=IMG_ABOVE,
                                 dtypes=dict(image_format=[3, -1]),
-                                ws=lambda a: feature_workspace_bytes(a["N"], a["H"], a["W"])),
-    "mvs_query_forward_workspace": dict(good=FWD, below=FWD_BELOW, above=FWD_ABOVE, rules=FWD_RULES, dtypes=DTYPES,
-                                        host=("bytes",)),
+                                sizes=dict(need=lambda a: feature_workspace_bytes(a["N"], a["H"], a["W"]))),
+    "mvs_query_forward_workspace": dict(good=FWD, below=FWD_BELOW, above=FWD_ABOVE, rules=FWD_RULES, dtypes=DTYPES),
     "mvs_forward_images": dict(good=FWD, below=FWD_BELOW, above=FWD_ABOVE, rules=FWD_RULES, dtypes=DTYPES,
-                               ws=lambda a: forward_workspace_bytes(a["N"], a["H"], a["W"], a["D"], a["dtype"])),
+                               sizes=dict(need=lambda a: forward_workspace_bytes(a["N"], a["H"], a["W"], a["D"], a["dtype"]))),
     "mvs_forward_images_fmt": dict(good=dict(FWD, image_format=1), below=FWD_BELOW, above=FWD_ABOVE, rules=FWD_RULES,
                                    dtypes=dict(DTYPES, image_format=[3, -1]),
-                                   ws=lambda a: forward_workspace_bytes(a["N"], a["H"], a["W"], a["D"], a["dtype"])),
+                                   sizes=dict(need=lambda a: forward_workspace_bytes(a["N"], a["H"], a["W"], a["D"], a["dtype"]))),
     "mvs_warp_variance_backward": dict(good=dict(N=3, C=32, D=16, h=16, w=24),
                                        below=VOL_BELOW, above=VOL_ABOVE, rules=VOL_RULES + [(dict(rt=None), NULL)],
                                        optional=dict(rt=dict(with_=dict(N=1), D=0))),
-    # covered by its own host file, swept here for the one row of the oversized table it owns
+    # also in tests/test_training_host.py, swept here for the one row of the oversized table it owns
     "mvs_softargmin_backward": dict(good=dict(D=16, h=16, w=24), below=dict(D=[0, -8], h=[0, -8], w=[0, -8]),
                                     above=dict(D=[(1 << 24) + 1], h=[dict(h=PIX_MAX + 1, w=1)],
                                                w=[dict(h=1, w=PIX_MAX + 1)]),
@@ -212,38 +240,8 @@ NOT_HELD = {
     "mvs_depth_regression": ("p", "depth_values", "depth_out"),
 }
 
-# entry points whose own host file holds them to their stated domain in this way
-COVERED = {
-    "mvs_filter_compose": "test_filter_ref_host.py",
-    "mvs_filter_depth": "test_filter_ref_host.py",
-    "mvs_query_metrics_workspace": "test_metrics_host.py",
-    "mvs_depth_metrics": "test_metrics_host.py",
-    "mvs_query_conv3d_train_workspace": "test_train_conv_host.py",
-    "mvs_conv3d_train_forward": "test_train_conv_host.py",
-    "mvs_conv3d_train_backward_data": "test_train_conv_host.py",
-    "mvs_conv3d_train_backward_weight": "test_train_conv_host.py",
-    "mvs_query_bn3d_train_workspace": "test_bn3d_ref_host.py",
-    "mvs_bn3d_train_forward": "test_bn3d_ref_host.py",
-    "mvs_bn3d_train_backward": "test_bn3d_ref_host.py",
-    "mvs_volume_relayout": "test_bn3d_ref_host.py",
-}
 NO_ARGUMENTS = ("mvs_abi_version", "mvs_last_error_string")
 # `stream` may be NULL everywhere (the default stream): every case of the sweep passes NULL and still gets its code
-
-
-def prototypes():
-    """{entry point: [(kind, name)]} from include/mvs_abi.h; kind is 'ptr', 'int', 'size_t', 'float', 'double' or
-    'long long'."""
-    header = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
-    out = {}
-    for name, params in re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(([^)]*)\)\s*;", header, flags=re.M):
-        plist = []
-        for param in ([] if params.strip() == "void" else params.split(",")):
-            pname = re.search(r"(\w+)\s*$", param).group(1)
-            ctype = " ".join(re.sub(r"\bconst\b", " ", re.sub(r"\w+\s*$", "", param.strip())).split())
-            plist.append(("ptr" if "*" in ctype else ctype, pname))
-        out[name] = plist
-    return out
 
 
 def _as_list(v):
@@ -272,9 +270,9 @@ def cases_of(name, spec, protos):
             out.append((f"{arg}={v}", {arg: v}, BAD_DTYPE))
     for ov, code in spec.get("rules", []):
         out.append((f"rule {ov}", ov, code))
-    if "ws" in spec:
-        out.append(("workspace one byte short", {"workspace_bytes": "ws-1"}, WORKSPACE))
-        out.append(("workspace at +16", {"workspace": "misaligned", "workspace_bytes": "ws"}, WORKSPACE))
+    if "need" in spec.get("sizes", {}):
+        out.append(("workspace one byte short", {"workspace_bytes": "need-1"}, WORKSPACE))
+        out.append(("workspace at +16", {"workspace": "plus16", "workspace_bytes": "need"}, WORKSPACE))
     data, blobs = ALIGN.get(name, ((), ()))
     out += [(f"{p} at +4", {p: "plus4"}, BAD_SHAPE) for p in data]
     out += [(f"blob {p} at +4", {p: "plus4"}, WORKSPACE) for p in blobs]
@@ -287,94 +285,17 @@ def cases_of(name, spec, protos):
 
 
 # ---- the child --------------------------------------------------------------------------------------------------------
-def _sweep(part):
-    from scene_3dreconstruction_mvsnet_amd import _lib
-    lib = _lib.load()
-    protos = prototypes()
-    keep = []
+def REFUSALS(part):
+    """The table tests/refusals.py runs.  "main" is every case but the ones whose plain size_t product wraps (two or more
+    dims of 2^30), which run in a child of their own ("wrap"): a library that divides by the wrapped zero dies there and
+    nowhere else."""
+    protos = refusals.prototypes("mvs_abi.h")
+    return {name: dict(spec, cases=[(label, ov, want, "") for label, ov, want in cases_of(name, spec, protos)
+                                    if (label.count(str(G30)) >= 2) == (part == "wrap")]) for name, spec in SPECS.items()}
 
-    def pack_arrays(kind):
-        if kind == "costreg":
-            convs = [np.ones(27 * ci * co, np.float32) for ci, co in _COSTREG_CH]
-            bns = [np.ones(_COSTREG_CH[k // 4][1], np.float32) for k in range(40)]
-            bias, nbytes = np.ones(1, np.float32), _lib.query_weights_blob()
-        else:
-            convs = [np.ones(k * k * ci * co, np.float32) for ci, co, k in _FEATURE_CH]
-            bns = [np.ones(_FEATURE_CH[k // 4][1], np.float32) for k in range(28)]
-            bias, nbytes = np.ones(32, np.float32), _lib.query_feature_blob()
-        return convs, bns, bias, nbytes
 
-    def call(name, spec, ov):
-        a = dict(spec["good"])
-        a.update({k: v for k, v in ov.items() if k in a})
-        args, fake = [], 0
-        n_out = ctypes.c_size_t(0)
-        convs = bns = None
-        if spec.get("pack"):
-            convs, bns, bias, blob_need = pack_arrays(spec["pack"])
-            blob = np.zeros(blob_need, np.uint8)
-        for kind, p in protos[name]:
-            if kind == "ptr":
-                fake += 1
-                if p in ov and ov[p] is None:
-                    v = None
-                elif p == "stream":
-                    v = None
-                elif p == "bytes":
-                    v = ctypes.byref(n_out)
-                elif p == "view_idx":
-                    arr = (ctypes.c_int * 64)(*ov.get("view_idx", list(range(max(a["N"], 0) % 64))))
-                    keep.append(arr)
-                    v = ctypes.cast(arr, ctypes.c_void_p)
-                elif p == "conv_weights":
-                    ptrs = [c.ctypes.data for c in convs]
-                    if "null_conv" in ov:
-                        ptrs[ov["null_conv"]] = None
-                    v = (ctypes.c_void_p * len(ptrs))(*ptrs)
-                elif p == "bn_params":
-                    ptrs = [b.ctypes.data for b in bns]
-                    if "null_bn" in ov:
-                        ptrs[ov["null_bn"]] = None
-                    v = (ctypes.c_void_p * len(ptrs))(*ptrs)
-                elif p in ("prob_bias", "feature_bias"):
-                    v = ctypes.c_void_p(bias.ctypes.data)
-                elif p == "blob_out":
-                    v = ctypes.c_void_p(blob.ctypes.data)
-                elif p == "workspace" and ov.get(p) == "misaligned":
-                    v = ctypes.c_void_p(0x100000 * fake + 16)
-                elif ov.get(p) == "plus4":
-                    v = ctypes.c_void_p(0x100000 * fake + 4)
-                else:
-                    v = ctypes.c_void_p(0x100000 * fake)      # 256-byte aligned, never dereferenced
-            elif p == "workspace_bytes":
-                need = spec["ws"](a) if "ws" in spec else 0
-                v = {"ws-1": need - 1, "ws": need}.get(ov.get(p), 1 << 46)
-            elif p == "blob_bytes":
-                v = blob_need - 1 if ov.get(p) == "blob-1" else blob_need
-            elif kind == "float":
-                v = 1e-5
-            else:
-                v = a[p]
-            args.append(v)
-        st = getattr(lib, name)(*args)
-        return st, (lib.mvs_last_error_string() or b"").decode("utf-8", "replace")
-
-    # One line per record, flushed: if the library takes the process down, what came before is still reported.  Before
-    # every case a refusal nobody else makes sets the thread's error string, so a refusal that forgot its own message
-    # shows as `stale`.
-    def sentinel():
-        assert lib.mvs_query_feature_workspace(1, 3, 2, ctypes.byref(ctypes.c_size_t(0))) == BAD_SHAPE
-        return lib.mvs_last_error_string()
-    for name, spec in SPECS.items():
-        for label, ov, want in cases_of(name, spec, protos):
-            if (label.count(str(G30)) >= 2) != (part == "wrap"):      # two or more dims of 2^30: the wrapping products
-                continue
-            before = sentinel().decode("utf-8", "replace")
-            print("R " + json.dumps(dict(ep=name, case=label, want=want, got=None, err="")), flush=True)   # about to call
-            got, err = call(name, spec, ov)
-            print("R " + json.dumps(dict(ep=name, case=label, want=want, got=got, err=err, stale=err == before)), flush=True)
-
-    # the error string is thread-local: a refusal on a second thread leaves this thread's string alone
+def error_string_of_two_threads(lib):
+    """the error string is thread-local: a refusal on a second thread leaves this thread's string alone"""
     assert lib.mvs_query_workspace(0, 32, 16, 16, 24, 0, ctypes.byref(ctypes.c_size_t(0))) == BAD_SHAPE
     mine = lib.mvs_last_error_string()
     other = {}
@@ -385,39 +306,35 @@ def _sweep(part):
     t = threading.Thread(target=refuse_elsewhere)
     t.start()
     t.join()
-    threads = dict(mine_before=mine.decode(), mine_after=lib.mvs_last_error_string().decode(), other=other)
-    print("T " + json.dumps(dict(threads=threads, force_direct=os.environ.get("MVS_FORCE_DIRECT", ""))), flush=True)
+    return dict(mine_before=mine.decode(), mine_after=lib.mvs_last_error_string().decode(), other=other)
+
+
+def refusals_epilogue(lib):
+    """what the child prints after its sweep"""
+    print("T " + json.dumps(dict(threads=error_string_of_two_threads(lib), force_direct=os.environ.get("MVS_FORCE_DIRECT", ""))),
+          flush=True)
 
 
 # ---- the tests --------------------------------------------------------------------------------------------------------
-# (force_direct, part): "main" is every case but the ones whose plain size_t product wraps (D = h = w = 2^30), which
-# run in a child of their own ("wrap"): a library that divides by the wrapped zero dies there and nowhere else
-CHILDREN = {"default": (False, "main"), "MVS_FORCE_DIRECT=1": (True, "main"), "default/wrap": (False, "wrap")}
+CHILDREN = {"default": (False, "main"), "MVS_FORCE_DIRECT=1": (True, "main"), "default/wrap": (False, "wrap")}       # (force_direct, part)
+
+
 def sweep(child):
     force_direct, part = CHILDREN[child]
-    r = gpu_child.run_once((__file__, child), [os.path.abspath(__file__), "--sweep", part], timeout=300, gpu=False,
-                           env={"MVS_FORCE_DIRECT": "1"} if force_direct else None)
-    # the line after the call replaces the one before it
-    records = {(rec["ep"], rec["case"]): rec for rec in r.records("R ")}
+    env = {"MVS_FORCE_DIRECT": "1"} if force_direct else None
+    r, records = refusals.run(__name__, part, env)
     tail = r.records("T ")
     if tail:
         assert tail[-1]["force_direct"] == ("1" if force_direct else "")
-    return dict(records=list(records.values()), rc=r.returncode, stderr=r.stderr[-2000:],
+    return dict(records=list(records.values()), part=part, env=env, stderr=r.stderr[-2000:],
                 threads=tail[-1]["threads"] if tail else None)
 
 
 @pytest.mark.parametrize("child", list(CHILDREN))
 def test_every_out_of_domain_call_is_refused_with_its_status(child):
     res = sweep(child)
-    records = res["records"]
-    wrong = [r for r in records if r["got"] != r["want"]]
-    for r in wrong:
-        what = "the process died in this call" if r["got"] is None else \
-            "reached a HIP call" if r["got"] == HIP else f"returned {r['got']}"
-        print(f"{r['ep']}: {r['case']}: {what}, expected {r['want']} ({r['err']})")
-    assert not wrong, f"{len(wrong)} of {len(records)} cases, first: {wrong[0]}"
-    assert res["rc"] == 0, f"sweep child ended with status {res['rc']}:\n{res['stderr']}"
-    assert len(records) > (400 if CHILDREN[child][1] == "main" else 10)
+    n = refusals.check(sys.modules[__name__], part=res["part"], env=res["env"])
+    assert n == len(res["records"]) > (400 if res["part"] == "main" else 10)
 
 
 @pytest.mark.parametrize("child", list(CHILDREN))
@@ -434,28 +351,46 @@ def test_a_refusal_on_another_thread_leaves_this_threads_error_string():
     assert t["mine_before"] and t["mine_before"] == t["mine_after"] != t["other"]["err"]
 
 
+def host_tables():
+    """{entry point: [spec with its cases]} over the tables of every host module that has one"""
+    out = {}
+    for path in sorted(glob.glob(os.path.join(HERE, "test_*_host.py"))):
+        if re.search(r"^(def )?REFUSALS\b", open(path).read(), flags=re.M):
+            module = importlib.import_module(os.path.basename(path)[:-3])
+            parts = ("main", "wrap") if callable(module.REFUSALS) else (None,)
+            for part in parts:
+                for name, spec in refusals.table_of(module, part).items():
+                    out.setdefault(name, []).append(spec)
+    return out
+
+
+# pointers the library takes as NULL without a refusal of their own and without a word in a header (none so far)
+NOT_REFUSED = {}
+
+
 def test_every_entry_point_pointer_and_integer_of_the_header_has_its_cases():
-    protos = prototypes()
-    from scene_3dreconstruction_mvsnet_amd import _lib
-    assert set(protos) == set(_lib.SYMBOLS)
+    protos = refusals.all_prototypes()
+    assert set(refusals.prototypes("mvs_abi.h")) == set(_lib.SYMBOLS)
+    tables = host_tables()
     missing = []
+    # every header: a device entry point has its cases in a no-device child, and every pointer of an entry point with
+    # cases has a NULL case or is stated optional
     for name, params in protos.items():
-        if name in NO_ARGUMENTS:
-            assert not params
+        specs = tables.get(name, [])
+        if not specs:
+            if any(p == "stream" for _, p in params):
+                missing.append(f"{name}: takes a stream and has no cases in a no-device child")
             continue
-        if name in COVERED and name not in SPECS:
-            assert os.path.exists(os.path.join(HERE, COVERED[name])), COVERED[name]
-            assert name in open(os.path.join(HERE, COVERED[name])).read(), (name, COVERED[name])
-            continue
-        if name not in SPECS:
-            missing.append(f"{name}: no table entry")
-            continue
-        spec = SPECS[name]
-        cases = cases_of(name, spec, protos)
-        nulled = {k for _, ov, code in cases if code == NULL for k, v in ov.items() if v is None}
+        nulled = {k for spec in specs for _, ov, code, _ in spec["cases"] if code == NULL for k, v in ov.items() if v is None}
+        optional = {p for spec in specs for p in spec.get("optional", ())} | set(NOT_REFUSED.get(name, ()))
         for kind, p in params:
-            if kind == "ptr" and p != "stream" and p not in nulled and p not in spec.get("optional", {}):
+            if kind == "ptr" and p != "stream" and p not in nulled | optional:
                 missing.append(f"{name}: pointer {p} has neither a NULL case nor an optional entry")
+    assert not set(tables) - set(protos) and not set(NOT_REFUSED) - set(protos)
+    # mvs_abi.h: the below-range and the alignment rule
+    for name, spec in SPECS.items():
+        params = protos[name]
+        for kind, p in params:
             if kind == "int":
                 below = spec.get("dtypes", {}) if p in ("dtype", "image_format") else spec.get("below", {})
                 if p not in below or not any(v < 0 or v == 0 for v in below[p]):
@@ -471,11 +406,18 @@ def test_every_entry_point_pointer_and_integer_of_the_header_has_its_cases():
                  if k not in [p for _, p in params]]
         assert not stale, (name, stale)
     assert not missing, "\n".join(missing)
-    assert not (set(SPECS) | set(COVERED)) - set(protos)
+    assert not set(SPECS) - set(refusals.prototypes("mvs_abi.h"))
+    for name in NO_ARGUMENTS:
+        assert not protos[name]
+
+
+def test_the_abi_version_is_still_2():
+    """the library-wide fact the per-header declaration tests used to repeat"""
+    assert _lib.load().mvs_abi_version() == 2 == _lib.ABI_VERSION
+    assert re.search(r"^#define MVS_ABI_VERSION 2$", refusals.header_text("mvs_abi.h"), flags=re.M)
 
 
 def _query(fn, *args):
-    from scene_3dreconstruction_mvsnet_amd import _lib
     n = ctypes.c_size_t(0)
     return getattr(_lib.load(), fn)(*args, ctypes.byref(n)), int(n.value)
 
@@ -518,8 +460,3 @@ def test_the_added_refusals_sit_above_the_largest_shape_of_the_limit_tests():
     assert _query("mvs_query_forward_workspace", 3, 4 * h, 4 * w, D, 0)[0] == OK
     assert D * h * w < 2 ** 28 and (D // 2) * (h // 2) * (w // 2) * 64 < 2 ** 31       # mvs_conv_layer, mvs_conv11_prob
     assert h * w <= PIX_MAX and D <= 1 << 24                                            # mvs_softargmin_conf
-
-
-if __name__ == "__main__":
-    assert sys.argv[1] == "--sweep" and sys.argv[2] in ("main", "wrap")
-    _sweep(sys.argv[2])

@@ -1,18 +1,20 @@
 """Host side of the training batch-norm (csrc/train_bn3d.hip, training.batch_norm_relu): the fp32 emulation of the
 kernels stays inside the bounds that tests/bn3d_ref.py derives, every listed defect is caught by a named case, the C
-ABI refuses what it must before anything is enqueued (the pointers below are never dereferenced), the workspace formula
-is pinned from both sides, and the Python layer refuses CPU tensors and unknown implementations."""
+ABI refuses what it must before anything is enqueued (tests/refusals.py makes the calls in a child process that sees no
+device), the workspace formula is pinned from both sides, and the Python layer refuses CPU tensors and unknown
+implementations."""
 import ctypes
 import itertools
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 import bn3d_ref as R
+import refusals
+from refusals import BAD_SHAPE, NULL, WORKSPACE
 from scene_3dreconstruction_mvsnet_amd import MVSNet, _lib, training
-
-_FAKE = [ctypes.c_void_p(0x100000 * (i + 1)) for i in range(10)]   # 256-byte aligned, never dereferenced
 
 
 def run_emulation(C, M, kind, relu, skip, running, seed=0, defects=()):
@@ -117,30 +119,46 @@ def test_exact_probes_hold_in_the_emulation():
 
 
 # ---------------------------------------------------------------- 3. the C ABI's refusals
-GOOD = dict(C=32, M=192)
+FORWARD, BACKWARD, RELAYOUT = "mvs_bn3d_train_forward", "mvs_bn3d_train_backward", "mvs_volume_relayout"
+GOOD = dict(C=32, M=192, relu=1)
+FORWARD_TENSORS = ("y", "gamma", "beta", "skip", "out", "save_mean", "save_invstd")
+NULLS = {FORWARD: ("y", "gamma", "beta", "out", "save_mean", "save_invstd", "workspace",    # skip may be NULL, and the running
+                   "running_mean", "running_var"),                                          # buffers, but only both together
+         BACKWARD: ("y", "grad_out", "gamma", "beta", "save_mean", "save_invstd", "grad_y", "grad_gamma", "grad_beta", "workspace"),
+         RELAYOUT: ("src", "dst")}
+BAD_SHAPES = [dict(C=0), dict(C=4), dict(C=12), dict(C=24), dict(C=128), dict(C=-8),      # C not in {8, 16, 32, 64}
+              dict(M=1), dict(M=0), dict(M=-5),                                           # M < 2
+              dict(C=64, M=1 << 25), dict(C=8, M=1 << 28), dict(C=32, M=1 << 40)]         # M * C >= 2^31
+BAD_RELAYOUTS = [dict(C=C, V=V, direction=d) for C, V, d in [(12, 512, 0), (32, 0, 0), (32, 510, 1), (32, -4, 1), (32, 512, 2),
+                                                             (32, 512, -1), (32, 1 << 26, 0), (64, 1 << 25, 1)]]
+SIZES = R.CASES + [(8, 192 * 128 * 160), (16, 96 * 64 * 80), (64, 24 * 16 * 20), (8, 1024), (8, 1025), (64, 128), (64, 129)]
 
 
-def _forward(null=None, ws_bytes=1 << 40, ws_ptr=None, unaligned=None, **kw):
-    a = dict(GOOD, **kw)
-    p = list(_FAKE)   # y gamma beta skip out save_mean save_invstd running_mean running_var workspace
-    if null is not None:
-        for k in (null if isinstance(null, tuple) else (null,)):
-            p[k] = None
-    if unaligned is not None:
-        p[unaligned] = ctypes.c_void_p(p[unaligned].value + 4)
-    if ws_ptr is not None:
-        p[9] = ctypes.c_void_p(ws_ptr)
-    return _lib.load().mvs_bn3d_train_forward(*p[:9], 0.1, 1e-5, 1, a["C"], a["M"], p[9], ws_bytes, None)
+def _short(C, M):
+    """the workspace refusals of one size: one byte short, and exactly enough but misaligned"""
+    return [(dict(C=C, M=M, workspace_bytes="need-1"), WORKSPACE, ""),
+            (dict(C=C, M=M, workspace_bytes="need", workspace="plus16"), WORKSPACE, "aligned")]
 
 
-def _backward(null=None, ws_bytes=1 << 40, ws_ptr=None, **kw):
-    a = dict(GOOD, **kw)
-    p = list(_FAKE)   # y grad_out gamma beta save_mean save_invstd grad_y grad_gamma grad_beta workspace
-    if null is not None:
-        p[null] = None
-    if ws_ptr is not None:
-        p[9] = ctypes.c_void_p(ws_ptr)
-    return _lib.load().mvs_bn3d_train_backward(*p[:9], 1, a["C"], a["M"], p[9], ws_bytes, None)
+def _common(name):
+    return [*[(bad, BAD_SHAPE, "") for bad in BAD_SHAPES], *[({p: None}, NULL, "NULL") for p in NULLS[name]],
+            *[c for size in SIZES for c in _short(*size)]]
+
+
+# every refusal below is run by tests/refusals.py in a child that sees no device; the tests look their record up
+_need = dict(need=lambda a: _lib.bn3d_train_workspace_bytes(a["C"], a["M"]))
+REFUSALS = {
+    FORWARD: dict(good=dict(GOOD, momentum=0.1, eps=1e-5), optional=("skip",), sizes=_need,
+                  cases=refusals.cases(*_common(FORWARD), *[({p: "plus4"}, BAD_SHAPE, "16 bytes") for p in FORWARD_TENSORS])),
+    BACKWARD: dict(good=GOOD, sizes=_need, cases=refusals.cases(*_common(BACKWARD))),
+    RELAYOUT: dict(good=dict(C=32, V=512, direction=0),
+                   cases=refusals.cases(*[({p: None}, NULL, "") for p in NULLS[RELAYOUT]],
+                                        *[(bad, BAD_SHAPE, "") for bad in BAD_RELAYOUTS], (dict(src="plus4"), BAD_SHAPE, ""))),
+}
+
+
+def _refused(name, **ov):
+    return refusals.expect(sys.modules[__name__], name, ov)
 
 
 def _query(**kw):
@@ -149,15 +167,11 @@ def _query(**kw):
     return _lib.load().mvs_query_bn3d_train_workspace(a["C"], a["M"], ctypes.byref(n)), int(n.value)
 
 
-BAD_SHAPES = [dict(C=0), dict(C=4), dict(C=12), dict(C=24), dict(C=128), dict(C=-8),      # C not in {8, 16, 32, 64}
-              dict(M=1), dict(M=0), dict(M=-5),                                           # M < 2
-              dict(C=64, M=1 << 25), dict(C=8, M=1 << 28), dict(C=32, M=1 << 40)]         # M * C >= 2^31
-
-
 @pytest.mark.parametrize("shape", BAD_SHAPES)
 def test_bad_shapes_are_refused_by_every_entry_point(shape):
-    for f in (_forward, _backward, lambda **kw: _query(**kw)[0]):
-        assert f(**shape) == 1                                # MVS_ERR_BAD_SHAPE
+    for name in (FORWARD, BACKWARD):
+        assert _refused(name, **shape) == BAD_SHAPE
+    assert _query(**shape)[0] == BAD_SHAPE
     assert _lib.load().mvs_last_error_string()
 
 
@@ -166,43 +180,31 @@ def test_the_largest_legal_sizes_are_accepted_by_the_query():
 
 
 def test_null_pointers_are_refused():
-    for k in (0, 1, 2, 4, 5, 6, 9):                           # skip (3) and the running buffers (7, 8) may be NULL
-        assert _forward(null=k) == 5, k
-    assert _forward(null=7) == 5 and _forward(null=8) == 5    # ... but only both together
-    for k in range(10):
-        assert _backward(null=k) == 5, k
-    assert b"NULL" in _lib.load().mvs_last_error_string()
-    assert _lib.load().mvs_query_bn3d_train_workspace(32, 192, None) == 5
-    lib = _lib.load()
-    assert lib.mvs_volume_relayout(None, _FAKE[1], 32, 512, 0, None) == 5
-    assert lib.mvs_volume_relayout(_FAKE[0], None, 32, 512, 0, None) == 5
+    for name, pointers in NULLS.items():
+        for p in pointers:
+            assert _refused(name, **{p: None}) == NULL, (name, p)
+    assert _lib.load().mvs_query_bn3d_train_workspace(32, 192, None) == NULL
 
 
 def test_unaligned_tensors_are_refused():
-    for k in range(7):
-        assert _forward(unaligned=k) == 1, k
-    assert b"16 bytes" in _lib.load().mvs_last_error_string()
+    for p in FORWARD_TENSORS:
+        assert _refused(FORWARD, **{p: "plus4"}) == BAD_SHAPE, p
 
 
 def test_relayout_refuses_bad_shapes():
-    lib = _lib.load()
-    a, b = _FAKE[0], _FAKE[1]
-    for C, V, direction in [(12, 512, 0), (32, 0, 0), (32, 510, 1), (32, -4, 1), (32, 512, 2), (32, 512, -1),
-                            (32, 1 << 26, 0), (64, 1 << 25, 1)]:
-        assert lib.mvs_volume_relayout(a, b, C, V, direction, None) == 1, (C, V, direction)
-    assert lib.mvs_volume_relayout(ctypes.c_void_p(0x100004), b, 32, 512, 0, None) == 1
+    for bad in BAD_RELAYOUTS:
+        assert _refused(RELAYOUT, **bad) == BAD_SHAPE, bad
+    assert _refused(RELAYOUT, src="plus4") == BAD_SHAPE
 
 
-@pytest.mark.parametrize("C,M", R.CASES + [(8, 192 * 128 * 160), (16, 96 * 64 * 80), (64, 24 * 16 * 20), (8, 1024),
-                                           (8, 1025), (64, 128), (64, 129)])
+@pytest.mark.parametrize("C,M", SIZES)
 def test_workspace_query_agrees_with_its_formula_and_one_byte_less_is_refused(C, M):
     st, n = _query(C=C, M=M)
     assert st == 0 and n == R.workspace_bytes(C, M) == _lib.bn3d_train_workspace_bytes(C, M), (C, M, n)
     assert n % 256 == 0 and n >= -(-M // (8192 // C)) * 2 * C * 4
-    for f in (_forward, _backward):
-        assert f(C=C, M=M, ws_bytes=n - 1) == 3               # MVS_ERR_WORKSPACE
-        assert f(C=C, M=M, ws_bytes=n, ws_ptr=0x500010) == 3  # misaligned
-    assert b"aligned" in _lib.load().mvs_last_error_string()
+    for name in (FORWARD, BACKWARD):
+        for ov, want, _ in _short(C, M):
+            assert _refused(name, **ov) == want == WORKSPACE
 
 
 # ---------------------------------------------------------------- 4. the Python layer

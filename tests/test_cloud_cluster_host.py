@@ -4,10 +4,7 @@ sequential traversal it claims to equal and both to scikit-learn's DBSCAN; the u
 the sanitizers.  Every refusal is decided before the first HIP call, so the fake device pointers are never dereferenced;
 the refusals run in a child process that sees no device (HIP_VISIBLE_DEVICES and ROCR_VISIBLE_DEVICES empty), where a call
 the library failed to refuse would come back as MVS_ERR_HIP (4) instead of reaching hardware."""
-import ctypes
-import json
 import os
-import re
 import subprocess
 import sys
 
@@ -21,176 +18,99 @@ for path in (REPO, HERE):
         sys.path.insert(0, path)
 
 import cluster_ref as CR  # noqa: E402
-import gpu_child  # noqa: E402
 import normals_ref  # noqa: E402
+import refusals  # noqa: E402
 
-HEADER = os.path.join(REPO, "include", "mvs_cluster_abi.h")
-OK, BAD_SHAPE, BAD_DTYPE, WORKSPACE, HIP, NULL = 0, 1, 2, 3, 4, 5
-BIN = ((-305.0, -205.0, -20.0), (305.0, 205.0, 220.0))
-NAN, INF = float("nan"), float("inf")
+from refusals import BAD_DTYPE, BAD_SHAPE, BIN, HIP, INF, NAN, NULL, OK, WORKSPACE  # noqa: E402
 INT_MAX = (1 << 31) - 1
 
 # ---------------------------------------------------------------- the refusal cases (shared by the child and the tests)
-# mvs_cloud_cluster: pointer slots xyz box_min box_max labels_out keep_out counts_out workspace
-GOOD = dict(dtype=0, P=5000, lo=BIN[0], hi=BIN[1], cell=5.0, eps=2.0, min_points=10, min_size=1)
-CASES = [(f"null {k}", dict(null=[k]), NULL, "NULL") for k in range(7)]
+GOOD = dict(dtype=0, P=5000, box_min=BIN[0], box_max=BIN[1], cell=5.0, eps=2.0, min_points=10, min_size=1)
+CASES = [(f"null {p}", {p: None}, NULL, "NULL") for p in ("xyz", "box_min", "box_max", "labels_out", "keep_out", "counts_out", "workspace")]
 CASES += [
     ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
     ("P = 2^31", dict(P=1 << 31), BAD_SHAPE, "2^31"),
-    ("P = 2^31 - 1 is legal", dict(P=(1 << 31) - 1, ws_bytes=0), WORKSPACE, "workspace"),
+    ("P = 2^31 - 1 is legal", dict(P=(1 << 31) - 1, workspace_bytes=0), WORKSPACE, "workspace"),
     ("eps nan", dict(eps=NAN), BAD_SHAPE, "eps"),
     ("eps < 0", dict(eps=-0.2), BAD_SHAPE, "eps"),
     ("eps inf", dict(eps=INF), BAD_SHAPE, "eps"),
     ("eps -inf", dict(eps=-INF), BAD_SHAPE, "eps"),
-    ("eps 0 is legal", dict(eps=0.0, ws_bytes=0), WORKSPACE, "workspace"),
-    ("eps 1e300 is legal", dict(eps=1e300, ws_bytes=0), WORKSPACE, "workspace"),
+    ("eps 0 is legal", dict(eps=0.0, workspace_bytes=0), WORKSPACE, "workspace"),
+    ("eps 1e300 is legal", dict(eps=1e300, workspace_bytes=0), WORKSPACE, "workspace"),
     ("min_points 0", dict(min_points=0), BAD_SHAPE, "min_points = 0"),
     ("min_points -1", dict(min_points=-1), BAD_SHAPE, "min_points = -1"),
-    ("min_points 1 is legal", dict(min_points=1, ws_bytes=0), WORKSPACE, "workspace"),
-    ("min_points 2^31 - 1 is legal", dict(min_points=INT_MAX, ws_bytes=0), WORKSPACE, "workspace"),
+    ("min_points 1 is legal", dict(min_points=1, workspace_bytes=0), WORKSPACE, "workspace"),
+    ("min_points 2^31 - 1 is legal", dict(min_points=INT_MAX, workspace_bytes=0), WORKSPACE, "workspace"),
     ("min_size 0", dict(min_size=0), BAD_SHAPE, "min_size = 0"),
     ("min_size -1", dict(min_size=-1), BAD_SHAPE, "min_size = -1"),
-    ("min_size 1 is legal", dict(min_size=1, ws_bytes=0), WORKSPACE, "workspace"),
-    ("min_size 2^31 - 1 is legal", dict(min_size=INT_MAX, ws_bytes=0), WORKSPACE, "workspace"),
+    ("min_size 1 is legal", dict(min_size=1, workspace_bytes=0), WORKSPACE, "workspace"),
+    ("min_size 2^31 - 1 is legal", dict(min_size=INT_MAX, workspace_bytes=0), WORKSPACE, "workspace"),
     ("cell 0", dict(cell=0.0), BAD_SHAPE, "cell"),
     ("cell < 0", dict(cell=-5.0), BAD_SHAPE, "cell"),
     ("cell nan", dict(cell=NAN), BAD_SHAPE, "cell"),
     ("cell inf", dict(cell=INF), BAD_SHAPE, "cell"),
-    ("box nan", dict(lo=(NAN, 0, 0)), BAD_SHAPE, "box axis 0"),
-    ("box -inf", dict(lo=(0, -INF, 0)), BAD_SHAPE, "box axis 1"),
-    ("box inf", dict(hi=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
-    ("min > max", dict(lo=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
-    ("a box that is a point is legal", dict(lo=(1, 2, 3), hi=(1, 2, 3), ws_bytes=0), WORKSPACE, "workspace"),
-    ("1291^3 cells", dict(lo=(0, 0, 0), hi=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
-    ("1290^3 cells are legal", dict(lo=(0, 0, 0), hi=(1289, 1289, 1289), cell=1.0, ws_bytes=0), WORKSPACE, "workspace"),
-    ("one axis of 3e9", dict(lo=(0, 0, 0), hi=(3e9, 0, 0), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("box nan", dict(box_min=(NAN, 0, 0)), BAD_SHAPE, "box axis 0"),
+    ("box -inf", dict(box_min=(0, -INF, 0)), BAD_SHAPE, "box axis 1"),
+    ("box inf", dict(box_max=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
+    ("min > max", dict(box_min=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
+    ("a box that is a point is legal", dict(box_min=(1, 2, 3), box_max=(1, 2, 3), workspace_bytes=0), WORKSPACE, "workspace"),
+    ("1291^3 cells", dict(box_min=(0, 0, 0), box_max=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("1290^3 cells are legal", dict(box_min=(0, 0, 0), box_max=(1289, 1289, 1289), cell=1.0, workspace_bytes=0), WORKSPACE, "workspace"),
+    ("one axis of 3e9", dict(box_min=(0, 0, 0), box_max=(3e9, 0, 0), cell=1.0), BAD_SHAPE, "2^31 cells"),
     ("dtype 2", dict(dtype=2), BAD_DTYPE, "dtype 2"),
     ("dtype -1", dict(dtype=-1), BAD_DTYPE, "dtype -1"),
-    ("one byte short", dict(ws_bytes="need-1"), WORKSPACE, "workspace"),
-    ("the normals' size is too small", dict(ws_bytes="normals"), WORKSPACE, "workspace"),
-    ("no workspace", dict(ws_bytes=0), WORKSPACE, "workspace"),
-    ("misaligned workspace", dict(ws_bytes="need", ws_ptr=0x900004), WORKSPACE, "aligned"),
-    ("everything right reaches HIP", dict(ws_bytes="need"), HIP, ""),
-    ("f64 reaches HIP", dict(ws_bytes="need", dtype=1), HIP, ""),
-    ("the largest integers reach HIP", dict(ws_bytes="need", min_points=INT_MAX, min_size=INT_MAX), HIP, ""),
-    ("eps 0 reaches HIP", dict(ws_bytes="need", eps=0.0), HIP, ""),
-    ("P == 0 reaches HIP", dict(P=0, ws_bytes="need"), HIP, ""),
+    ("one byte short", dict(workspace_bytes="need-1"), WORKSPACE, "workspace"),
+    ("the normals' size is too small", dict(workspace_bytes="normals"), WORKSPACE, "workspace"),
+    ("no workspace", dict(workspace_bytes=0), WORKSPACE, "workspace"),
+    ("misaligned workspace", dict(workspace_bytes="need", workspace="plus4"), WORKSPACE, "aligned"),
+    ("everything right reaches HIP", dict(workspace_bytes="need"), HIP, ""),
+    ("f64 reaches HIP", dict(workspace_bytes="need", dtype=1), HIP, ""),
+    ("the largest integers reach HIP", dict(workspace_bytes="need", min_points=INT_MAX, min_size=INT_MAX), HIP, ""),
+    ("eps 0 reaches HIP", dict(workspace_bytes="need", eps=0.0), HIP, ""),
+    ("P == 0 reaches HIP", dict(P=0, workspace_bytes="need"), HIP, ""),
 ]
-# mvs_query_cluster_workspace: null = which of (box_min, box_max, bytes) is NULL
 Q_CASES = [
-    ("null box_min", dict(null=0), NULL, "NULL"), ("null box_max", dict(null=1), NULL, "NULL"),
-    ("null bytes", dict(null=2), NULL, "NULL"), ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
+    ("null box_min", dict(box_min=None), NULL, "NULL"), ("null box_max", dict(box_max=None), NULL, "NULL"),
+    ("null bytes", dict(bytes=None), NULL, "NULL"), ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
     ("P = 2^31", dict(P=1 << 31), BAD_SHAPE, "2^31"), ("cell 0", dict(cell=0.0), BAD_SHAPE, "cell"),
     ("cell nan", dict(cell=NAN), BAD_SHAPE, "cell"), ("cell inf", dict(cell=INF), BAD_SHAPE, "cell"),
-    ("box inf", dict(hi=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
-    ("min > max", dict(lo=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
-    ("1291^3 cells", dict(lo=(0, 0, 0), hi=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("box inf", dict(box_max=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
+    ("min > max", dict(box_min=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
+    ("1291^3 cells", dict(box_min=(0, 0, 0), box_max=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
     ("fine", dict(), OK, ""), ("P == 0 is fine", dict(P=0), OK, ""), ("P = 2^31 - 1 is fine", dict(P=(1 << 31) - 1), OK, ""),
 ]
 
 
-def _box(lo, hi):
-    return (ctypes.c_double * 3)(*lo), (ctypes.c_double * 3)(*hi)
+def _bytes_of(ref):
+    return lambda a: ref.workspace_bytes(a["P"], a["box_min"], a["box_max"], a["cell"])
 
 
-def _fake(k):
-    return ctypes.c_void_p(0x100000 * (k + 1))        # aligned, never dereferenced
+REFUSALS = {
+    "mvs_cloud_cluster": dict(good=GOOD, host=refusals.BOX, cases=CASES,
+                              sizes=dict(need=_bytes_of(CR), normals=_bytes_of(normals_ref))),
+    "mvs_query_cluster_workspace": dict(good=GOOD, host=refusals.BOX, cases=Q_CASES),
+}
 
 
-def _call(lib, ov):
-    a = dict(GOOD, **{k: v for k, v in ov.items() if k in GOOD})
-    lo, hi = _box(a["lo"], a["hi"])
-    p = [_fake(k) for k in range(7)]
-    p[1], p[2] = ctypes.c_void_p(ctypes.addressof(lo)), ctypes.c_void_p(ctypes.addressof(hi))
-    for k in ov.get("null", []):
-        p[k] = None
-    if "ws_ptr" in ov:
-        p[6] = ctypes.c_void_p(ov["ws_ptr"])
-    ws = ov.get("ws_bytes", 1 << 44)
-    if ws == "normals":
-        ws = normals_ref.workspace_bytes(a["P"], a["lo"], a["hi"], a["cell"])
-    elif isinstance(ws, str):
-        ws = CR.workspace_bytes(a["P"], a["lo"], a["hi"], a["cell"]) - (ws == "need-1")
-    return lib.mvs_cloud_cluster(p[0], a["dtype"], a["P"], p[1], p[2], a["cell"], a["eps"], a["min_points"], a["min_size"],
-                                 p[3], p[4], p[5], p[6], ws, None)
-
-
-def _call_query(lib, ov):
-    a = dict(GOOD, **{k: v for k, v in ov.items() if k in GOOD})
-    lo, hi = _box(a["lo"], a["hi"])
-    n = ctypes.c_size_t(0)
-    args = [ctypes.c_void_p(ctypes.addressof(lo)), ctypes.c_void_p(ctypes.addressof(hi)), ctypes.byref(n)]
-    if "null" in ov:
-        args[ov["null"]] = None
-    return lib.mvs_query_cluster_workspace(a["P"], args[0], args[1], a["cell"], args[2])
-
-
-ENTRY_POINTS = (("cluster", CASES, _call), ("query", Q_CASES, _call_query))
-
-
-def _child():
-    from scene_3dreconstruction_mvsnet_amd import _lib
-    lib = _lib.load()
-    for ep, cases, call in ENTRY_POINTS:
-        for label, ov, want, _ in cases:
-            # a refusal nobody else makes sets the thread's error string: a refusal without its own message shows as stale
-            assert lib.mvs_query_feature_workspace(1, 3, 2, ctypes.byref(ctypes.c_size_t(0))) == BAD_SHAPE
-            before = lib.mvs_last_error_string()
-            got = call(lib, ov)
-            err = lib.mvs_last_error_string() or b""
-            print("R " + json.dumps(dict(ep=ep, case=label, got=got, err=err.decode("utf-8", "replace"), stale=err == before)),
-                  flush=True)
-
-
-@pytest.mark.parametrize("ep,cases", [(ep, cases) for ep, cases, _ in ENTRY_POINTS])
+@pytest.mark.parametrize("ep,cases", [("cluster", CASES), ("query", Q_CASES)])
 def test_every_refusal_comes_with_its_status_and_its_message(ep, cases):
-    records = gpu_child.refusal_records(os.path.abspath(__file__))
-    assert len({label for label, *_ in cases}) == len(cases)
-    wrong = []
-    for label, _, want, text in cases:
-        rec = records[(ep, label)]
-        if rec["got"] != want or (want not in (HIP, OK) and (rec["stale"] or text not in rec["err"])):
-            wrong.append((label, want, rec["got"], rec["err"]))
-    assert not wrong, wrong
+    name, = [n for n, spec in REFUSALS.items() if spec["cases"] is cases and ep in n]
+    refusals.check(sys.modules[__name__], (name,))
 
 
 # ---------------------------------------------------------------- declarations
-import test_host_logic  # noqa: E402
 from scene_3dreconstruction_mvsnet_amd import _lib, fusion, reconstruct  # noqa: E402
 
 
-def _plain_prototypes(src):
-    """Comments inside prototypes dropped and `double name[3]` written `double* name`, which is the same C parameter."""
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    return re.sub(r"(\w+)\s*\[\s*\d+\s*\]", r"* \1", src)
-
-
 def test_cluster_symbols_are_the_declarations_of_the_cluster_header():
-    src = open(HEADER).read()
-    declared = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", src, flags=re.M)
-    assert declared == ["mvs_query_cluster_workspace", "mvs_cloud_cluster"]
-    assert list(_lib.CLUSTER_SYMBOLS) == declared == list(_lib._ABI["mvs_cluster_abi.h"])
-    others = [s for h, table in _lib._ABI.items() if h != "mvs_cluster_abi.h" for s in table]
-    assert not set(declared) & set(others)
-    prototypes = test_host_logic.header_argtypes(_plain_prototypes(src))
-    assert sorted(prototypes) == sorted(declared)
-    for name, kinds in prototypes.items():
-        assert _lib._ABI["mvs_cluster_abi.h"][name] == kinds, name
-        assert list(getattr(_lib.load(), name).argtypes) == kinds, name
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
+    src = refusals.check_header("mvs_cluster_abi.h", _lib.CLUSTER_SYMBOLS)
+    assert list(_lib.CLUSTER_SYMBOLS) == ["mvs_query_cluster_workspace", "mvs_cloud_cluster"]
     assert '#include "mvs_abi.h"' in src and '#include "mvs_normals_abi.h"' in src
-    assert int(re.search(r"^#define MVS_CLUSTER_COUNTERS (\d+)", src, flags=re.M).group(1)) == CR.COUNTERS
-    assert "Likewise include/mvs_cluster_abi.h" in open(os.path.join(REPO, "include", "mvs_abi.h")).read()
-    for other in sorted(set(_lib._ABI) - {"mvs_cluster_abi.h"}):
-        text = open(os.path.join(REPO, "include", other)).read()
-        assert not re.search(r"^int\s+mvs_\w*cluster", text, flags=re.M), other
+    assert refusals.define(src, "MVS_CLUSTER_COUNTERS") == CR.COUNTERS
+    assert "Likewise include/mvs_cluster_abi.h" in refusals.header_text("mvs_abi.h")
     # the invariant, the traversal argument and what was not compared are said where the contract is
     assert "EVERY VALUE EVER STORED IN parent[i] IS <= i" in src and "in ascending order of their" in src
     assert "never compared with Open3D" in src
-    assert sorted(_lib._ABI) == sorted(f for f in os.listdir(os.path.join(REPO, "include")) if f.endswith(".h"))
-    assert _lib.load().mvs_abi_version() == 2 == _lib.ABI_VERSION
 
 
 # ---------------------------------------------------------------- workspace formula
@@ -415,8 +335,3 @@ def test_the_command_line_takes_the_cluster_flags(monkeypatch):
     with pytest.raises(Exception):
         reconstruct.main(common)
     assert seen["cluster_eps"] is None            # the stage is off unless asked for
-
-
-if __name__ == "__main__":
-    assert sys.argv[1] == "--refusals"
-    _child()

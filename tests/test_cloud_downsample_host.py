@@ -1,23 +1,57 @@
 """Host-side checks of the cloud crop + voxel downsample (include/mvs_cloud_abi.h, csrc/cloud_downsample.hip): none needs
-a GPU.  Every refusal of mvs_cloud_downsample is decided before its first HIP call, so the fake device pointers are never
-dereferenced; the two box pointers are host memory and real."""
+a GPU.  Every refusal of mvs_cloud_downsample is decided before its first HIP call; the calls are made by tests/refusals.py
+in a child process that sees no device, with made-up device pointers that are never dereferenced."""
 import ctypes
-import os
-import re
+import sys
 
 import numpy as np
 import pytest
 
 import cloud_ref
-from test_host_logic import header_argtypes
+import refusals
+from refusals import BAD_DTYPE, BAD_SHAPE, BIN, INF, NAN, NULL, OK, WORKSPACE
 from scene_3dreconstruction_mvsnet_amd import _lib, fusion, reconstruct
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLOUD_HEADER = os.path.join(REPO, "include", "mvs_cloud_abi.h")
-OK, BAD_SHAPE, BAD_DTYPE, WORKSPACE, NULL = 0, 1, 2, 3, 5
-_FAKE = [ctypes.c_void_p(0x100000 * (i + 1)) for i in range(6)]   # aligned, never dereferenced
-BIN = ((-305.0, -205.0, -20.0), (305.0, 205.0, 220.0))
-GOOD = dict(dtype=_lib.MVS_CLOUD_F32, P=5000, lo=BIN[0], hi=BIN[1], v=5.0, scale=0.01, capacity=100)
+GOOD = dict(xyz_dtype=_lib.MVS_CLOUD_F32, P=5000, box_min=BIN[0], box_max=BIN[1], voxel_size=5.0, scale=0.01, capacity=100)
+PTRS = ("xyz", "rgb", "box_min", "box_max", "xyz_out", "rgb_out", "counts_out", "workspace")
+BAD_BOXES = [dict(box_min=(NAN, 0, 0)), dict(box_min=(0, -INF, 0)), dict(box_max=(305, 205, INF)), dict(box_max=(305, NAN, 220)),
+             dict(box_min=(306, -205, -20)), dict(box_min=(-305, -205, 220.5)),                          # min > max on one axis
+             dict(box_min=(0, 0, 0), box_max=(1290, 1290, 1290), voxel_size=1.0),                        # 1292^3 >= 2^31 cells
+             dict(box_min=(0, 0, 0), box_max=(3e9, 0, 0), voxel_size=1.0),                               # one axis alone
+             dict(box_min=(-1e308, 0, 0), box_max=(1e308, 1, 1), voxel_size=1e-300),       # the span and the quotient overflow
+             dict(box_min=(0, 0, 0), box_max=(1, 1, 1), voxel_size=5e-324)]
+BAD_SIZES = [dict(voxel_size=0.0), dict(voxel_size=-5.0), dict(voxel_size=NAN), dict(voxel_size=INF), dict(P=-1), dict(P=1 << 31),
+             dict(P=1 << 40)]
+BAD = BAD_BOXES + BAD_SIZES + [dict(capacity=-1), dict(scale=NAN), dict(scale=INF), dict(scale=-INF)]
+DTYPES = [2, -1, 7]
+SHAPES = [(5000, BIN[0], BIN[1], 5.0), (1, BIN[0], BIN[1], 5.0), (1024, BIN[0], BIN[1], 5.0), (1025, BIN[0], BIN[1], 5.0),
+          (70001, BIN[0], BIN[1], 2.5), (1000, (-24, -24, 0), (24, 24, 32), 0.4), (3, (0, 0, 0), (0, 0, 0), 1.0),
+          (64, (0, 0, 0), (10, 10, 10), 5.0)]
+
+
+def _short(P, lo, hi, v):
+    """the three workspace refusals of one shape: from below, none, exactly enough but 4- and not 8-byte aligned"""
+    k = dict(P=P, box_min=lo, box_max=hi, voxel_size=v)
+    return [(dict(k, workspace_bytes="need-1"), WORKSPACE, ""), (dict(k, workspace_bytes=0), WORKSPACE, ""),
+            (dict(k, workspace_bytes="need", workspace="plus4"), WORKSPACE, "aligned")]
+
+
+# every refusal of mvs_cloud_downsample, run by tests/refusals.py in a child that sees no device (the two box pointers are
+# host memory and real); the tests look their record up
+REFUSALS = {"mvs_cloud_downsample": dict(
+    good=GOOD, host=refusals.BOX, optional=("xyz_out", "rgb_out"),
+    sizes=dict(need=lambda a: _lib.query_cloud_workspace(a["P"], a["box_min"], a["box_max"], a["voxel_size"])),
+    cases=refusals.cases(
+        *[({p: None}, NULL, "NULL") for p in PTRS],
+        (dict(xyz_out=None, capacity=0, workspace_bytes=0), WORKSPACE, ""),
+        (dict(rgb_out=None, capacity=0, workspace_bytes=0), WORKSPACE, ""),
+        (dict(counts_out=None, capacity=0, workspace_bytes=0), NULL, ""),        # counts_out is always written
+        *[(bad, BAD_SHAPE, "") for bad in BAD], *[(dict(xyz_dtype=d), BAD_DTYPE, "dtype") for d in DTYPES],
+        *[c for shape in SHAPES for c in _short(*shape)]))}
+
+
+def _refused(**ov):
+    return refusals.expect(sys.modules[__name__], "mvs_cloud_downsample", ov)
 
 
 def _box(lo, hi):
@@ -30,71 +64,27 @@ def _query(P, lo, hi, v):
     return _lib.load().mvs_query_cloud_workspace(P, ctypes.addressof(a), ctypes.addressof(b), v, ctypes.byref(n)), int(n.value)
 
 
-def _down(null=None, ws_bytes=1 << 44, ws_ptr=None, **kw):
-    a = dict(GOOD, **kw)
-    lo, hi = _box(a["lo"], a["hi"])
-    # xyz rgb box_min box_max xyz_out rgb_out counts_out workspace
-    p = [_FAKE[0], _FAKE[1], ctypes.c_void_p(ctypes.addressof(lo)), ctypes.c_void_p(ctypes.addressof(hi)), _FAKE[2], _FAKE[3],
-         _FAKE[4], _FAKE[5]]
-    if null is not None:
-        p[null] = None
-    if ws_ptr is not None:
-        p[7] = ctypes.c_void_p(ws_ptr)
-    return _lib.load().mvs_cloud_downsample(p[0], a["dtype"], p[1], a["P"], p[2], p[3], a["v"], a["scale"], a["capacity"],
-                                            p[4], p[5], p[6], p[7], ws_bytes, None)
-
-
 # ---------------------------------------------------------------- declarations
-def _plain_prototypes(src):
-    """The header's text with the comments inside prototypes dropped and `double name[3]` written `double* name`, which
-    is the same C parameter: what test_host_logic.header_argtypes reads."""
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    return re.sub(r"(\w+)\s*\[\s*\d+\s*\]", r"* \1", src)
-
-
 def test_cloud_symbols_are_the_declarations_of_the_cloud_header():
-    src = open(CLOUD_HEADER).read()
-    declared = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", src, flags=re.M)
-    assert sorted(declared) == sorted(_lib.CLOUD_SYMBOLS) and len(set(declared)) == len(declared) == 2
-    assert not set(_lib.CLOUD_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.FUSE_SYMBOLS))
-    prototypes = header_argtypes(_plain_prototypes(src))
-    assert sorted(prototypes) == sorted(declared)
-    for name, kinds in prototypes.items():
-        assert _lib._ABI["mvs_cloud_abi.h"][name] == kinds, name
-        assert list(getattr(_lib.load(), name).argtypes) == kinds, name
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
-    assert '#include "mvs_abi.h"' in src
+    src = refusals.check_header("mvs_cloud_abi.h", _lib.CLOUD_SYMBOLS)
+    assert len(_lib.CLOUD_SYMBOLS) == 2 and '#include "mvs_abi.h"' in src
     for name, value in (("MVS_CLOUD_F32", _lib.MVS_CLOUD_F32), ("MVS_CLOUD_F64", _lib.MVS_CLOUD_F64),
                         ("MVS_CLOUD_CHUNK", _lib.CLOUD_CHUNK), ("MVS_CLOUD_TILE", _lib.CLOUD_TILE),
                         ("MVS_CLOUD_SCAN_WIDTH", _lib.CLOUD_SCAN_WIDTH), ("MVS_CLOUD_RECORD", _lib.CLOUD_RECORD)):
-        assert int(re.search(rf"^#define {name} (\d+)", src, flags=re.M).group(1)) == value
-    # the other two headers do not declare them; the main one names this header
-    main = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
-    fuse = open(os.path.join(REPO, "include", "mvs_fuse_abi.h")).read()
-    assert "mvs_cloud_abi.h" in main
-    for other in (main, fuse):
-        assert not re.search(r"^int\s+mvs_(query_cloud|cloud)", other, flags=re.M)
-
-
-def test_the_abi_version_is_still_2():
-    assert _lib.load().mvs_abi_version() == 2 == _lib.ABI_VERSION
-    main = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
-    assert re.search(r"^#define MVS_ABI_VERSION 2$", main, flags=re.M)
+        assert refusals.define(src, name) == value
+    assert "mvs_cloud_abi.h" in refusals.header_text("mvs_abi.h")        # the main header names this one
 
 
 # ---------------------------------------------------------------- refusals
 @pytest.mark.parametrize("which", range(8))
 def test_a_null_pointer_is_refused(which):
-    assert _down(null=which) == NULL
-    assert b"NULL" in _lib.load().mvs_last_error_string()
+    assert _refused(**{PTRS[which]: None}) == NULL
 
 
 def test_null_outputs_pass_only_at_capacity_zero_and_then_the_next_check_decides():
-    assert _down(null=4, capacity=0, ws_bytes=0) == WORKSPACE
-    assert _down(null=5, capacity=0, ws_bytes=0) == WORKSPACE
-    assert _down(null=6, capacity=0, ws_bytes=0) == NULL        # counts_out is always written
+    assert _refused(xyz_out=None, capacity=0, workspace_bytes=0) == WORKSPACE
+    assert _refused(rgb_out=None, capacity=0, workspace_bytes=0) == WORKSPACE
+    assert _refused(counts_out=None, capacity=0, workspace_bytes=0) == NULL
     lo, hi = _box(*BIN)
     n = ctypes.c_size_t(0)
     q = _lib.load().mvs_query_cloud_workspace
@@ -103,23 +93,12 @@ def test_null_outputs_pass_only_at_capacity_zero_and_then_the_next_check_decides
     assert q(10, ctypes.addressof(lo), None, 5.0, ctypes.byref(n)) == NULL
 
 
-NAN, INF = float("nan"), float("inf")
-BAD_BOXES = [dict(lo=(NAN, 0, 0)), dict(lo=(0, -INF, 0)), dict(hi=(305, 205, INF)), dict(hi=(305, NAN, 220)),
-             dict(lo=(306, -205, -20)), dict(lo=(-305, -205, 220.5)),              # min > max on one axis
-             dict(lo=(0, 0, 0), hi=(1290, 1290, 1290), v=1.0),                     # 1292^3 >= 2^31 cells
-             dict(lo=(0, 0, 0), hi=(3e9, 0, 0), v=1.0),                            # one axis alone
-             dict(lo=(-1e308, 0, 0), hi=(1e308, 1, 1), v=1e-300),                  # the span and the quotient overflow
-             dict(lo=(0, 0, 0), hi=(1, 1, 1), v=5e-324)]
-BAD_SIZES = [dict(v=0.0), dict(v=-5.0), dict(v=NAN), dict(v=INF), dict(P=-1), dict(P=1 << 31), dict(P=1 << 40)]
-
-
-@pytest.mark.parametrize("bad", BAD_BOXES + BAD_SIZES + [dict(capacity=-1), dict(scale=NAN), dict(scale=INF), dict(scale=-INF)])
+@pytest.mark.parametrize("bad", BAD)
 def test_bad_shapes_are_refused(bad):
-    assert _down(**bad) == BAD_SHAPE, bad
-    assert _lib.load().mvs_last_error_string()
+    assert _refused(**bad) == BAD_SHAPE, bad
     if "capacity" not in bad and "scale" not in bad:
         a = dict(GOOD, **bad)
-        assert _query(a["P"], a["lo"], a["hi"], a["v"])[0] == BAD_SHAPE
+        assert _query(a["P"], a["box_min"], a["box_max"], a["voxel_size"])[0] == BAD_SHAPE
 
 
 def test_the_largest_legal_sizes_and_the_degenerate_box_are_accepted_by_the_query():
@@ -134,25 +113,18 @@ def test_the_largest_legal_sizes_and_the_degenerate_box_are_accepted_by_the_quer
     assert cloud_ref.grid_shape(*BIN, 5.0) == [124, 84, 50]         # the bin at 5 mm
 
 
-@pytest.mark.parametrize("dtype", [2, -1, 7])
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_only_float32_and_float64_points_are_taken(dtype):
-    assert _down(dtype=dtype) == BAD_DTYPE
-    assert b"dtype" in _lib.load().mvs_last_error_string()
+    assert _refused(xyz_dtype=dtype) == BAD_DTYPE
 
 
-@pytest.mark.parametrize("P,lo,hi,v", [(5000, BIN[0], BIN[1], 5.0), (1, BIN[0], BIN[1], 5.0), (1024, BIN[0], BIN[1], 5.0),
-                                       (1025, BIN[0], BIN[1], 5.0), (70001, BIN[0], BIN[1], 2.5),
-                                       (1000, (-24, -24, 0), (24, 24, 32), 0.4), (3, (0, 0, 0), (0, 0, 0), 1.0),
-                                       (64, (0, 0, 0), (10, 10, 10), 5.0)])
+@pytest.mark.parametrize("P,lo,hi,v", SHAPES)
 def test_workspace_query_agrees_with_its_formula_and_one_byte_less_is_refused(P, lo, hi, v):
     st, n = _query(P, lo, hi, v)
     assert st == OK and n == cloud_ref.workspace_bytes(P, lo, hi, v) == _lib.query_cloud_workspace(P, lo, hi, v)
     assert n % 8 == 0
-    k = dict(P=P, lo=lo, hi=hi, v=v)
-    assert _down(ws_bytes=n - 1, **k) == WORKSPACE        # from below
-    assert _down(ws_bytes=0, **k) == WORKSPACE
-    assert _down(ws_bytes=n, ws_ptr=0x500004, **k) == WORKSPACE      # exactly enough, 4- but not 8-byte aligned
-    assert b"aligned" in _lib.load().mvs_last_error_string()
+    for ov, want, _ in _short(P, lo, hi, v):
+        assert _refused(**ov) == want == WORKSPACE
     # the formula from the other side: every term is the smallest that holds what the header says it holds
     cells = int(np.prod(cloud_ref.grid_shape(lo, hi, v)))
     tiles = -(-cells // _lib.CLOUD_TILE)

@@ -2,11 +2,8 @@
 a GPU.  Every refusal is decided before the first HIP call, so the fake device pointers are never dereferenced; the
 refusals run in a child process that sees no device (HIP_VISIBLE_DEVICES and ROCR_VISIBLE_DEVICES empty), where a call the
 library failed to refuse would come back as MVS_ERR_HIP (4) instead of reaching hardware."""
-import ctypes
-import json
 import math
 import os
-import re
 import sys
 
 import numpy as np
@@ -18,171 +15,91 @@ for path in (REPO, HERE):
     if path not in sys.path:
         sys.path.insert(0, path)
 
-import gpu_child  # noqa: E402
 import normals_ref  # noqa: E402
 import outliers_ref  # noqa: E402
+import refusals  # noqa: E402
 
-HEADER = os.path.join(REPO, "include", "mvs_outliers_abi.h")
-OK, BAD_SHAPE, BAD_DTYPE, WORKSPACE, HIP, NULL = 0, 1, 2, 3, 4, 5
-BIN = ((-305.0, -205.0, -20.0), (305.0, 205.0, 220.0))
-NAN, INF = float("nan"), float("inf")
+from refusals import BAD_DTYPE, BAD_SHAPE, BIN, HIP, INF, NAN, NULL, OK, WORKSPACE  # noqa: E402
 
 # ---------------------------------------------------------------- the refusal cases (shared by the child and the tests)
-# mvs_cloud_outliers: pointer slots xyz box_min box_max dist_out keep_out xyz_masked_out counts_out stats_out workspace
-GOOD = dict(dtype=0, P=5000, lo=BIN[0], hi=BIN[1], cell=5.0, nb=20, ratio=2.0)
-CASES = [(f"null {k}", dict(null=[k]), NULL, "NULL") for k in (0, 1, 2, 3, 4, 6, 7, 8)]
+GOOD = dict(xyz_dtype=0, P=5000, box_min=BIN[0], box_max=BIN[1], cell=5.0, nb_neighbors=20, std_ratio=2.0)
+CASES = [(f"null {p}", {p: None}, NULL, "NULL") for p in ("xyz", "box_min", "box_max", "dist_out", "keep_out", "counts_out", "stats_out", "workspace")]
 CASES += [
-    ("xyz_masked_out may be NULL", dict(null=[5], ws_bytes=0), WORKSPACE, "workspace"),
+    ("xyz_masked_out may be NULL", dict(xyz_masked_out=None, workspace_bytes=0), WORKSPACE, "workspace"),
     ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
     ("P = 2^31", dict(P=1 << 31), BAD_SHAPE, "2^31"),
     ("P = 2^40", dict(P=1 << 40), BAD_SHAPE, "2^31"),
-    ("nb 1", dict(nb=1), BAD_SHAPE, "nb_neighbors = 1"),
-    ("nb 0", dict(nb=0), BAD_SHAPE, "nb_neighbors = 0"),
-    ("nb -5", dict(nb=-5), BAD_SHAPE, "nb_neighbors = -5"),
-    ("nb 65", dict(nb=65), BAD_SHAPE, "nb_neighbors = 65"),
-    ("nb 2 is legal", dict(nb=2, ws_bytes=0), WORKSPACE, "workspace"),
-    ("nb 64 is legal", dict(nb=64, ws_bytes=0), WORKSPACE, "workspace"),
-    ("ratio 0", dict(ratio=0.0), BAD_SHAPE, "std_ratio"),
-    ("ratio < 0", dict(ratio=-2.0), BAD_SHAPE, "std_ratio"),
-    ("ratio nan", dict(ratio=NAN), BAD_SHAPE, "std_ratio"),
-    ("ratio inf", dict(ratio=INF), BAD_SHAPE, "std_ratio"),
+    ("nb 1", dict(nb_neighbors=1), BAD_SHAPE, "nb_neighbors = 1"),
+    ("nb 0", dict(nb_neighbors=0), BAD_SHAPE, "nb_neighbors = 0"),
+    ("nb -5", dict(nb_neighbors=-5), BAD_SHAPE, "nb_neighbors = -5"),
+    ("nb 65", dict(nb_neighbors=65), BAD_SHAPE, "nb_neighbors = 65"),
+    ("nb 2 is legal", dict(nb_neighbors=2, workspace_bytes=0), WORKSPACE, "workspace"),
+    ("nb 64 is legal", dict(nb_neighbors=64, workspace_bytes=0), WORKSPACE, "workspace"),
+    ("ratio 0", dict(std_ratio=0.0), BAD_SHAPE, "std_ratio"),
+    ("ratio < 0", dict(std_ratio=-2.0), BAD_SHAPE, "std_ratio"),
+    ("ratio nan", dict(std_ratio=NAN), BAD_SHAPE, "std_ratio"),
+    ("ratio inf", dict(std_ratio=INF), BAD_SHAPE, "std_ratio"),
     ("cell 0", dict(cell=0.0), BAD_SHAPE, "cell"),
     ("cell < 0", dict(cell=-5.0), BAD_SHAPE, "cell"),
     ("cell nan", dict(cell=NAN), BAD_SHAPE, "cell"),
     ("cell inf", dict(cell=INF), BAD_SHAPE, "cell"),
-    ("box nan", dict(lo=(NAN, 0, 0)), BAD_SHAPE, "box axis 0"),
-    ("box -inf", dict(lo=(0, -INF, 0)), BAD_SHAPE, "box axis 1"),
-    ("box inf", dict(hi=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
-    ("min > max", dict(lo=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
-    ("1291^3 cells", dict(lo=(0, 0, 0), hi=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
-    ("one axis of 3e9", dict(lo=(0, 0, 0), hi=(3e9, 0, 0), cell=1.0), BAD_SHAPE, "2^31 cells"),
-    ("denormal cell", dict(lo=(0, 0, 0), hi=(1, 1, 1), cell=5e-324), BAD_SHAPE, "2^31 cells"),
-    ("dtype 2", dict(dtype=2), BAD_DTYPE, "dtype"),
-    ("dtype -1", dict(dtype=-1), BAD_DTYPE, "dtype"),
-    ("one byte short", dict(ws_bytes="need-1"), WORKSPACE, "workspace"),
-    ("the normals' size is too small", dict(ws_bytes="normals"), WORKSPACE, "workspace"),
-    ("no workspace", dict(ws_bytes=0), WORKSPACE, "workspace"),
-    ("misaligned workspace", dict(ws_bytes="need", ws_ptr=0x900004), WORKSPACE, "aligned"),
-    ("everything right reaches HIP", dict(ws_bytes="need"), HIP, ""),
-    ("everything right at f64 reaches HIP", dict(ws_bytes="need", dtype=1), HIP, ""),
-    ("P == 0 reaches HIP", dict(P=0, ws_bytes="need"), HIP, ""),
+    ("box nan", dict(box_min=(NAN, 0, 0)), BAD_SHAPE, "box axis 0"),
+    ("box -inf", dict(box_min=(0, -INF, 0)), BAD_SHAPE, "box axis 1"),
+    ("box inf", dict(box_max=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
+    ("min > max", dict(box_min=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
+    ("1291^3 cells", dict(box_min=(0, 0, 0), box_max=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("one axis of 3e9", dict(box_min=(0, 0, 0), box_max=(3e9, 0, 0), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("denormal cell", dict(box_min=(0, 0, 0), box_max=(1, 1, 1), cell=5e-324), BAD_SHAPE, "2^31 cells"),
+    ("dtype 2", dict(xyz_dtype=2), BAD_DTYPE, "dtype"),
+    ("dtype -1", dict(xyz_dtype=-1), BAD_DTYPE, "dtype"),
+    ("one byte short", dict(workspace_bytes="need-1"), WORKSPACE, "workspace"),
+    ("the normals' size is too small", dict(workspace_bytes="normals"), WORKSPACE, "workspace"),
+    ("no workspace", dict(workspace_bytes=0), WORKSPACE, "workspace"),
+    ("misaligned workspace", dict(workspace_bytes="need", workspace="plus4"), WORKSPACE, "aligned"),
+    ("everything right reaches HIP", dict(workspace_bytes="need"), HIP, ""),
+    ("everything right at f64 reaches HIP", dict(workspace_bytes="need", xyz_dtype=1), HIP, ""),
+    ("P == 0 reaches HIP", dict(P=0, workspace_bytes="need"), HIP, ""),
 ]
-# mvs_query_outliers_workspace: P, lo, hi, cell, null = which of (box_min, box_max, bytes) is NULL
 Q_CASES = [
-    ("null box_min", dict(null=0), NULL, "NULL"), ("null box_max", dict(null=1), NULL, "NULL"),
-    ("null bytes", dict(null=2), NULL, "NULL"), ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
+    ("null box_min", dict(box_min=None), NULL, "NULL"), ("null box_max", dict(box_max=None), NULL, "NULL"),
+    ("null bytes", dict(bytes=None), NULL, "NULL"), ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
     ("P = 2^31", dict(P=1 << 31), BAD_SHAPE, "2^31"), ("cell 0", dict(cell=0.0), BAD_SHAPE, "cell"),
-    ("min > max", dict(lo=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
-    ("1291^3 cells", dict(lo=(0, 0, 0), hi=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("min > max", dict(box_min=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
+    ("1291^3 cells", dict(box_min=(0, 0, 0), box_max=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
     ("fine", dict(), OK, ""),
 ]
 
 
-def _box(lo, hi):
-    return (ctypes.c_double * 3)(*lo), (ctypes.c_double * 3)(*hi)
+def _bytes_of(ref):
+    return lambda a: ref.workspace_bytes(a["P"], a["box_min"], a["box_max"], a["cell"])
 
 
-def _fake(k):
-    return ctypes.c_void_p(0x100000 * (k + 1))        # aligned, never dereferenced
-
-
-def _call(lib, ov):
-    a = dict(GOOD, **{k: v for k, v in ov.items() if k in GOOD})
-    lo, hi = _box(a["lo"], a["hi"])
-    p = [_fake(k) for k in range(9)]
-    p[1], p[2] = ctypes.c_void_p(ctypes.addressof(lo)), ctypes.c_void_p(ctypes.addressof(hi))
-    for k in ov.get("null", []):
-        p[k] = None
-    if "ws_ptr" in ov:
-        p[8] = ctypes.c_void_p(ov["ws_ptr"])
-    ws = ov.get("ws_bytes", 1 << 44)
-    if ws == "normals":
-        ws = normals_ref.workspace_bytes(a["P"], a["lo"], a["hi"], a["cell"])
-    elif isinstance(ws, str):
-        ws = outliers_ref.workspace_bytes(a["P"], a["lo"], a["hi"], a["cell"]) - (ws == "need-1")
-    return lib.mvs_cloud_outliers(p[0], a["dtype"], a["P"], p[1], p[2], a["cell"], a["nb"], a["ratio"], p[3], p[4], p[5],
-                                  p[6], p[7], p[8], ws, None)
-
-
-def _call_query(lib, ov):
-    a = dict(GOOD, **{k: v for k, v in ov.items() if k in GOOD})
-    lo, hi = _box(a["lo"], a["hi"])
-    n = ctypes.c_size_t(0)
-    args = [ctypes.c_void_p(ctypes.addressof(lo)), ctypes.c_void_p(ctypes.addressof(hi)), ctypes.byref(n)]
-    if "null" in ov:
-        args[ov["null"]] = None
-    return lib.mvs_query_outliers_workspace(a["P"], args[0], args[1], a["cell"], args[2])
-
-
-def _child():
-    from scene_3dreconstruction_mvsnet_amd import _lib
-    lib = _lib.load()
-    for ep, cases, call in (("outliers", CASES, _call), ("query", Q_CASES, _call_query)):
-        for label, ov, want, _ in cases:
-            # a refusal nobody else makes sets the thread's error string: a refusal without its own message shows as stale
-            assert lib.mvs_query_feature_workspace(1, 3, 2, ctypes.byref(ctypes.c_size_t(0))) == BAD_SHAPE
-            before = lib.mvs_last_error_string()
-            got = call(lib, ov)
-            err = lib.mvs_last_error_string() or b""
-            print("R " + json.dumps(dict(ep=ep, case=label, got=got, err=err.decode("utf-8", "replace"), stale=err == before)),
-                  flush=True)
+REFUSALS = {
+    "mvs_cloud_outliers": dict(good=GOOD, host=refusals.BOX, optional=("xyz_masked_out",), cases=CASES,
+                               sizes=dict(need=_bytes_of(outliers_ref), normals=_bytes_of(normals_ref))),
+    "mvs_query_outliers_workspace": dict(good=GOOD, host=refusals.BOX, cases=Q_CASES),
+}
 
 
 @pytest.mark.parametrize("ep,cases", [("outliers", CASES), ("query", Q_CASES)])
 def test_every_refusal_comes_with_its_status_and_its_message(ep, cases):
-    records = gpu_child.refusal_records(os.path.abspath(__file__))
-    assert len({label for label, *_ in cases}) == len(cases)
-    wrong = []
-    for label, _, want, text in cases:
-        rec = records[(ep, label)]
-        if rec["got"] != want or (want not in (HIP, OK) and (rec["stale"] or text not in rec["err"])):
-            wrong.append((label, want, rec["got"], rec["err"]))
-    assert not wrong, wrong
+    name, = [n for n, spec in REFUSALS.items() if spec["cases"] is cases and ep in n]
+    refusals.check(sys.modules[__name__], (name,))
 
 
 # ---------------------------------------------------------------- declarations
-from test_host_logic import header_argtypes  # noqa: E402
 from scene_3dreconstruction_mvsnet_amd import _lib, fusion, reconstruct  # noqa: E402
 
 
-def _plain_prototypes(src):
-    """Comments inside prototypes dropped and `double name[3]` written `double* name`, which is the same C parameter."""
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    return re.sub(r"(\w+)\s*\[\s*\d+\s*\]", r"* \1", src)
-
-
 def test_outliers_symbols_are_the_declarations_of_the_outliers_header():
-    src = open(HEADER).read()
-    declared = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", src, flags=re.M)
-    assert declared == ["mvs_query_outliers_workspace", "mvs_cloud_outliers"]
-    assert list(_lib.OUTLIERS_SYMBOLS) == declared == list(_lib._ABI["mvs_outliers_abi.h"])
-    assert not set(declared) & (set(_lib.SYMBOLS) | set(_lib.FUSE_SYMBOLS) | set(_lib.CLOUD_SYMBOLS) | set(_lib.NORMALS_SYMBOLS))
-    prototypes = header_argtypes(_plain_prototypes(src))
-    assert sorted(prototypes) == sorted(declared)
-    for name, kinds in prototypes.items():
-        assert _lib._ABI["mvs_outliers_abi.h"][name] == kinds, name
-        assert list(getattr(_lib.load(), name).argtypes) == kinds, name
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
+    src = refusals.check_header("mvs_outliers_abi.h", _lib.OUTLIERS_SYMBOLS)
+    assert list(_lib.OUTLIERS_SYMBOLS) == ["mvs_query_outliers_workspace", "mvs_cloud_outliers"]
     assert '#include "mvs_abi.h"' in src and '#include "mvs_normals_abi.h"' in src
     for name, value in (("MVS_OUTLIERS_BLOCK", _lib.OUTLIERS_BLOCK), ("MVS_OUTLIERS_SCALARS", _lib.OUTLIERS_SCALARS)):
-        assert int(re.search(rf"^#define {name} (\d+)", src, flags=re.M).group(1)) == value == getattr(outliers_ref, name[13:])
-    # the other headers declare none of them; the main one names this header; the header says what it is
-    main = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
-    assert "mvs_outliers_abi.h" in main
-    for other in ("mvs_abi.h", "mvs_fuse_abi.h", "mvs_cloud_abi.h", "mvs_normals_abi.h"):
-        text = open(os.path.join(REPO, "include", other)).read()
-        assert not re.search(r"^int\s+mvs_\w*outliers", text, flags=re.M), other
+        assert refusals.define(src, name) == value == getattr(outliers_ref, name[13:])
+    # the main header names this one; the header says what it is
+    assert "mvs_outliers_abi.h" in refusals.header_text("mvs_abi.h")
     assert "RemoveStatisticalOutliers is restated" in src and "nothing here was compared against it" in src
-    # every key of the one table is a header of include/, and every header there is a key
-    assert sorted(_lib._ABI) == sorted(f for f in os.listdir(os.path.join(REPO, "include")) if f.endswith(".h"))
-
-
-def test_the_abi_version_is_still_2():
-    assert _lib.load().mvs_abi_version() == 2 == _lib.ABI_VERSION
-    main = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
-    assert re.search(r"^#define MVS_ABI_VERSION 2$", main, flags=re.M)
 
 
 # ---------------------------------------------------------------- workspace formula
@@ -372,8 +289,3 @@ def test_the_command_line_takes_the_outlier_flags(monkeypatch):
         reconstruct.main(["--testpath", "/nonexistent/x", "--testlist", "/nonexistent/y", "--loadckpt", "/nonexistent/z",
                           "--downsample_mm", "5"])
     assert seen["outlier_knn"] is None and seen["outlier_std"] == 2.0
-
-
-if __name__ == "__main__":
-    assert sys.argv[1] == "--refusals"
-    _child()

@@ -4,9 +4,7 @@ Every refusal is decided before the first HIP call, so the fake device pointers 
 in a child process that sees no device (HIP_VISIBLE_DEVICES and ROCR_VISIBLE_DEVICES empty), where a call the library
 failed to refuse would come back as MVS_ERR_HIP (4) instead of reaching hardware."""
 import ctypes
-import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -18,76 +16,70 @@ for path in (REPO, HERE):
     if path not in sys.path:
         sys.path.insert(0, path)
 
-import gpu_child  # noqa: E402
 import normals_ref  # noqa: E402
 import reduce_ref as RR  # noqa: E402
+import refusals  # noqa: E402
 
-HEADER = os.path.join(REPO, "include", "mvs_reduce_abi.h")
-OK, BAD_SHAPE, BAD_DTYPE, WORKSPACE, HIP, NULL = 0, 1, 2, 3, 4, 5
-BIN = ((-305.0, -205.0, -20.0), (305.0, 205.0, 220.0))
-NAN, INF = float("nan"), float("inf")
+from refusals import BAD_DTYPE, BAD_SHAPE, BIN, HIP, INF, NAN, NULL, OK, WORKSPACE  # noqa: E402
 
 # ---------------------------------------------------------------- the refusal cases (shared by the child and the tests)
-# mvs_cloud_reduce: pointer slots xyz box_min box_max keep_out counts_out workspace
-GOOD = dict(dtype=0, P=5000, lo=BIN[0], hi=BIN[1], cell=5.0, min_dist=0.2, seed=0, max_rounds=64)
-CASES = [(f"null {k}", dict(null=[k]), NULL, "NULL") for k in range(6)]
+GOOD = dict(dtype=0, P=5000, box_min=BIN[0], box_max=BIN[1], cell=5.0, min_dist=0.2, seed=0, max_rounds=64)
+CASES = [(f"null {p}", {p: None}, NULL, "NULL") for p in ("xyz", "box_min", "box_max", "keep_out", "counts_out", "workspace")]
 CASES += [
     ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
     ("P = 2^31", dict(P=1 << 31), BAD_SHAPE, "2^31"),
-    ("P = 2^31 - 1 is legal", dict(P=(1 << 31) - 1, ws_bytes=0), WORKSPACE, "workspace"),
+    ("P = 2^31 - 1 is legal", dict(P=(1 << 31) - 1, workspace_bytes=0), WORKSPACE, "workspace"),
     ("min_dist nan", dict(min_dist=NAN), BAD_SHAPE, "min_dist"),
     ("min_dist < 0", dict(min_dist=-0.2), BAD_SHAPE, "min_dist"),
     ("min_dist inf", dict(min_dist=INF), BAD_SHAPE, "min_dist"),
     ("min_dist -inf", dict(min_dist=-INF), BAD_SHAPE, "min_dist"),
-    ("min_dist 0 is legal", dict(min_dist=0.0, ws_bytes=0), WORKSPACE, "workspace"),
-    ("min_dist 1e300 is legal", dict(min_dist=1e300, ws_bytes=0), WORKSPACE, "workspace"),
+    ("min_dist 0 is legal", dict(min_dist=0.0, workspace_bytes=0), WORKSPACE, "workspace"),
+    ("min_dist 1e300 is legal", dict(min_dist=1e300, workspace_bytes=0), WORKSPACE, "workspace"),
     ("max_rounds 0", dict(max_rounds=0), BAD_SHAPE, "max_rounds = 0"),
     ("max_rounds -1", dict(max_rounds=-1), BAD_SHAPE, "max_rounds = -1"),
     ("max_rounds 257", dict(max_rounds=257), BAD_SHAPE, "max_rounds = 257"),
-    ("max_rounds 1 is legal", dict(max_rounds=1, ws_bytes=0), WORKSPACE, "workspace"),
-    ("max_rounds 256 is legal", dict(max_rounds=256, ws_bytes=0), WORKSPACE, "workspace"),
+    ("max_rounds 1 is legal", dict(max_rounds=1, workspace_bytes=0), WORKSPACE, "workspace"),
+    ("max_rounds 256 is legal", dict(max_rounds=256, workspace_bytes=0), WORKSPACE, "workspace"),
     ("cell 0", dict(cell=0.0), BAD_SHAPE, "cell"),
     ("cell < 0", dict(cell=-5.0), BAD_SHAPE, "cell"),
     ("cell nan", dict(cell=NAN), BAD_SHAPE, "cell"),
     ("cell inf", dict(cell=INF), BAD_SHAPE, "cell"),
-    ("box nan", dict(lo=(NAN, 0, 0)), BAD_SHAPE, "box axis 0"),
-    ("box -inf", dict(lo=(0, -INF, 0)), BAD_SHAPE, "box axis 1"),
-    ("box inf", dict(hi=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
-    ("min > max", dict(lo=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
-    ("1291^3 cells", dict(lo=(0, 0, 0), hi=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
-    ("1290^3 cells are legal", dict(lo=(0, 0, 0), hi=(1289, 1289, 1289), cell=1.0, ws_bytes=0), WORKSPACE, "workspace"),
-    ("one axis of 3e9", dict(lo=(0, 0, 0), hi=(3e9, 0, 0), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("box nan", dict(box_min=(NAN, 0, 0)), BAD_SHAPE, "box axis 0"),
+    ("box -inf", dict(box_min=(0, -INF, 0)), BAD_SHAPE, "box axis 1"),
+    ("box inf", dict(box_max=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
+    ("min > max", dict(box_min=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
+    ("1291^3 cells", dict(box_min=(0, 0, 0), box_max=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("1290^3 cells are legal", dict(box_min=(0, 0, 0), box_max=(1289, 1289, 1289), cell=1.0, workspace_bytes=0), WORKSPACE, "workspace"),
+    ("one axis of 3e9", dict(box_min=(0, 0, 0), box_max=(3e9, 0, 0), cell=1.0), BAD_SHAPE, "2^31 cells"),
     ("dtype 2", dict(dtype=2), BAD_DTYPE, "dtype 2"),
     ("dtype -1", dict(dtype=-1), BAD_DTYPE, "dtype -1"),
-    ("one byte short", dict(ws_bytes="need-1"), WORKSPACE, "workspace"),
-    ("the normals' size is too small", dict(ws_bytes="normals"), WORKSPACE, "workspace"),
-    ("no workspace", dict(ws_bytes=0), WORKSPACE, "workspace"),
-    ("misaligned workspace", dict(ws_bytes="need", ws_ptr=0x900004), WORKSPACE, "aligned"),
-    ("everything right reaches HIP", dict(ws_bytes="need"), HIP, ""),
-    ("f64 reaches HIP", dict(ws_bytes="need", dtype=1), HIP, ""),
-    ("the largest seed reaches HIP", dict(ws_bytes="need", seed=(1 << 64) - 1), HIP, ""),
-    ("P == 0 reaches HIP", dict(P=0, ws_bytes="need"), HIP, ""),
+    ("one byte short", dict(workspace_bytes="need-1"), WORKSPACE, "workspace"),
+    ("the normals' size is too small", dict(workspace_bytes="normals"), WORKSPACE, "workspace"),
+    ("no workspace", dict(workspace_bytes=0), WORKSPACE, "workspace"),
+    ("misaligned workspace", dict(workspace_bytes="need", workspace="plus4"), WORKSPACE, "aligned"),
+    ("everything right reaches HIP", dict(workspace_bytes="need"), HIP, ""),
+    ("f64 reaches HIP", dict(workspace_bytes="need", dtype=1), HIP, ""),
+    ("the largest seed reaches HIP", dict(workspace_bytes="need", seed=(1 << 64) - 1), HIP, ""),
+    ("P == 0 reaches HIP", dict(P=0, workspace_bytes="need"), HIP, ""),
 ]
-# mvs_query_reduce_workspace: null = which of (box_min, box_max, bytes) is NULL
 Q_CASES = [
-    ("null box_min", dict(null=0), NULL, "NULL"), ("null box_max", dict(null=1), NULL, "NULL"),
-    ("null bytes", dict(null=2), NULL, "NULL"), ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
+    ("null box_min", dict(box_min=None), NULL, "NULL"), ("null box_max", dict(box_max=None), NULL, "NULL"),
+    ("null bytes", dict(bytes=None), NULL, "NULL"), ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
     ("P = 2^31", dict(P=1 << 31), BAD_SHAPE, "2^31"), ("cell 0", dict(cell=0.0), BAD_SHAPE, "cell"),
     ("cell nan", dict(cell=NAN), BAD_SHAPE, "cell"), ("cell inf", dict(cell=INF), BAD_SHAPE, "cell"),
-    ("box inf", dict(hi=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
-    ("min > max", dict(lo=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
-    ("1291^3 cells", dict(lo=(0, 0, 0), hi=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
+    ("box inf", dict(box_max=(305, 205, INF)), BAD_SHAPE, "box axis 2"),
+    ("min > max", dict(box_min=(306, -205, -20)), BAD_SHAPE, "box axis 0"),
+    ("1291^3 cells", dict(box_min=(0, 0, 0), box_max=(1290, 1290, 1290), cell=1.0), BAD_SHAPE, "2^31 cells"),
     ("fine", dict(), OK, ""), ("P == 0 is fine", dict(P=0), OK, ""), ("P = 2^31 - 1 is fine", dict(P=(1 << 31) - 1), OK, ""),
 ]
-# mvs_cloud_select: pointer slots xyz obs_mask n origin plane keep_out counts_out
 S_GOOD = dict(dtype=0, P=5000, n=(12, 10, 8), origin=(-3.0, 2.0, 0.5), res=10.0, plane=(0.0, 0.0, 1.0, -2.0))
-S_CASES = [(f"null {k}", dict(null=[k]), NULL, "NULL") for k in (0, 5, 6)]
+S_CASES = [(f"null {p}", {p: None}, NULL, "NULL") for p in ("xyz", "keep_out", "counts_out")]
 S_CASES += [
-    ("a mask with a null n", dict(null=[2]), NULL, "NULL n or origin"),
-    ("a mask with a null origin", dict(null=[3]), NULL, "NULL n or origin"),
-    ("no mask: n and origin may be NULL", dict(null=[1, 2, 3]), HIP, ""),
-    ("no plane", dict(null=[4]), HIP, ""),
-    ("neither", dict(null=[1, 2, 3, 4]), HIP, ""),
+    ("a mask with a null n", dict(n=None), NULL, "NULL n or origin"),
+    ("a mask with a null origin", dict(origin=None), NULL, "NULL n or origin"),
+    ("no mask: n and origin may be NULL", dict(obs_mask=None, n=None, origin=None), HIP, ""),
+    ("no plane", dict(plane=None), HIP, ""),
+    ("neither", dict(obs_mask=None, n=None, origin=None, plane=None), HIP, ""),
     ("P < 0", dict(P=-1), BAD_SHAPE, "P = -1"),
     ("P = 2^31", dict(P=1 << 31), BAD_SHAPE, "2^31"),
     ("P = 2^31 - 1 reaches HIP", dict(P=(1 << 31) - 1), HIP, ""),
@@ -101,7 +93,7 @@ S_CASES += [
     ("res < 0", dict(res=-10.0), BAD_SHAPE, "res"),
     ("res nan", dict(res=NAN), BAD_SHAPE, "res"),
     ("res inf", dict(res=INF), BAD_SHAPE, "res"),
-    ("res 0 without a mask", dict(res=0.0, null=[1, 2, 3]), BAD_SHAPE, "res"),
+    ("res 0 without a mask", dict(res=0.0, obs_mask=None, n=None, origin=None), BAD_SHAPE, "res"),
     ("origin nan", dict(origin=(0.0, NAN, 0.0)), BAD_SHAPE, "origin[1]"),
     ("origin inf", dict(origin=(0.0, 0.0, -INF)), BAD_SHAPE, "origin[2]"),
     ("plane nan", dict(plane=(NAN, 0.0, 1.0, 0.0)), BAD_SHAPE, "plane[0]"),
@@ -113,121 +105,38 @@ S_CASES += [
 ]
 
 
-def _box(lo, hi):
-    return (ctypes.c_double * 3)(*lo), (ctypes.c_double * 3)(*hi)
+def _bytes_of(ref):
+    return lambda a: ref.workspace_bytes(a["P"], a["box_min"], a["box_max"], a["cell"])
 
 
-def _fake(k):
-    return ctypes.c_void_p(0x100000 * (k + 1))        # aligned, never dereferenced
+REFUSALS = {
+    "mvs_cloud_reduce": dict(good=GOOD, host=refusals.BOX, cases=CASES,
+                             sizes=dict(need=_bytes_of(RR), normals=_bytes_of(normals_ref))),
+    "mvs_query_reduce_workspace": dict(good=GOOD, host=refusals.BOX, cases=Q_CASES),
+    "mvs_cloud_select": dict(good=S_GOOD, host=dict(n=ctypes.c_int, origin=ctypes.c_double, plane=ctypes.c_double),
+                             optional=("obs_mask", "plane"), cases=S_CASES),
+}
 
 
-def _call(lib, ov):
-    a = dict(GOOD, **{k: v for k, v in ov.items() if k in GOOD})
-    lo, hi = _box(a["lo"], a["hi"])
-    p = [_fake(k) for k in range(6)]
-    p[1], p[2] = ctypes.c_void_p(ctypes.addressof(lo)), ctypes.c_void_p(ctypes.addressof(hi))
-    for k in ov.get("null", []):
-        p[k] = None
-    if "ws_ptr" in ov:
-        p[5] = ctypes.c_void_p(ov["ws_ptr"])
-    ws = ov.get("ws_bytes", 1 << 44)
-    if ws == "normals":
-        ws = normals_ref.workspace_bytes(a["P"], a["lo"], a["hi"], a["cell"])
-    elif isinstance(ws, str):
-        ws = RR.workspace_bytes(a["P"], a["lo"], a["hi"], a["cell"]) - (ws == "need-1")
-    return lib.mvs_cloud_reduce(p[0], a["dtype"], a["P"], p[1], p[2], a["cell"], a["min_dist"], a["seed"], a["max_rounds"],
-                                p[3], p[4], p[5], ws, None)
-
-
-def _call_query(lib, ov):
-    a = dict(GOOD, **{k: v for k, v in ov.items() if k in GOOD})
-    lo, hi = _box(a["lo"], a["hi"])
-    n = ctypes.c_size_t(0)
-    args = [ctypes.c_void_p(ctypes.addressof(lo)), ctypes.c_void_p(ctypes.addressof(hi)), ctypes.byref(n)]
-    if "null" in ov:
-        args[ov["null"]] = None
-    return lib.mvs_query_reduce_workspace(a["P"], args[0], args[1], a["cell"], args[2])
-
-
-def _call_select(lib, ov):
-    a = dict(S_GOOD, **{k: v for k, v in ov.items() if k in S_GOOD})
-    n, origin, plane = (ctypes.c_int * 3)(*a["n"]), (ctypes.c_double * 3)(*a["origin"]), (ctypes.c_double * 4)(*a["plane"])
-    p = [_fake(k) for k in range(7)]
-    p[2], p[3], p[4] = (ctypes.c_void_p(ctypes.addressof(x)) for x in (n, origin, plane))
-    for k in ov.get("null", []):
-        p[k] = None
-    return lib.mvs_cloud_select(p[0], a["dtype"], a["P"], p[1], p[2], p[3], a["res"], p[4], p[5], p[6], None)
-
-
-ENTRY_POINTS = (("reduce", CASES, _call), ("query", Q_CASES, _call_query), ("select", S_CASES, _call_select))
-
-
-def _child():
-    from scene_3dreconstruction_mvsnet_amd import _lib
-    lib = _lib.load()
-    for ep, cases, call in ENTRY_POINTS:
-        for label, ov, want, _ in cases:
-            # a refusal nobody else makes sets the thread's error string: a refusal without its own message shows as stale
-            assert lib.mvs_query_feature_workspace(1, 3, 2, ctypes.byref(ctypes.c_size_t(0))) == BAD_SHAPE
-            before = lib.mvs_last_error_string()
-            got = call(lib, ov)
-            err = lib.mvs_last_error_string() or b""
-            print("R " + json.dumps(dict(ep=ep, case=label, got=got, err=err.decode("utf-8", "replace"), stale=err == before)),
-                  flush=True)
-
-
-@pytest.mark.parametrize("ep,cases", [(ep, cases) for ep, cases, _ in ENTRY_POINTS])
+@pytest.mark.parametrize("ep,cases", [("reduce", CASES), ("query", Q_CASES), ("select", S_CASES)])
 def test_every_refusal_comes_with_its_status_and_its_message(ep, cases):
-    records = gpu_child.refusal_records(os.path.abspath(__file__))
-    assert len({label for label, *_ in cases}) == len(cases)
-    wrong = []
-    for label, _, want, text in cases:
-        rec = records[(ep, label)]
-        if rec["got"] != want or (want not in (HIP, OK) and (rec["stale"] or text not in rec["err"])):
-            wrong.append((label, want, rec["got"], rec["err"]))
-    assert not wrong, wrong
+    name, = [n for n, spec in REFUSALS.items() if spec["cases"] is cases and ep in n]
+    refusals.check(sys.modules[__name__], (name,))
 
 
 # ---------------------------------------------------------------- declarations
-import test_host_logic  # noqa: E402
 from scene_3dreconstruction_mvsnet_amd import _lib, eval_cloud, fusion, reconstruct  # noqa: E402
 
 
-def _plain_prototypes(src):
-    """Comments inside prototypes dropped and `double name[3]` written `double* name`, which is the same C parameter."""
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    return re.sub(r"(\w+)\s*\[\s*\d+\s*\]", r"* \1", src)
-
-
-def test_reduce_symbols_are_the_declarations_of_the_reduce_header(monkeypatch):
-    src = open(HEADER).read()
-    declared = re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", src, flags=re.M)
-    assert declared == ["mvs_query_reduce_workspace", "mvs_cloud_reduce", "mvs_cloud_select"]
-    assert list(_lib.REDUCE_SYMBOLS) == declared == list(_lib._ABI["mvs_reduce_abi.h"])
-    others = [s for h, table in _lib._ABI.items() if h != "mvs_reduce_abi.h" for s in table]
-    assert not set(declared) & set(others)
-    monkeypatch.setitem(test_host_logic._C_SCALARS, "unsigned long long", ctypes.c_ulonglong)      # the seed
-    prototypes = test_host_logic.header_argtypes(_plain_prototypes(src))
-    assert sorted(prototypes) == sorted(declared)
-    for name, kinds in prototypes.items():
-        assert _lib._ABI["mvs_reduce_abi.h"][name] == kinds, name
-        assert list(getattr(_lib.load(), name).argtypes) == kinds, name
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
+def test_reduce_symbols_are_the_declarations_of_the_reduce_header():
+    src = refusals.check_header("mvs_reduce_abi.h", _lib.REDUCE_SYMBOLS)
+    assert list(_lib.REDUCE_SYMBOLS) == ["mvs_query_reduce_workspace", "mvs_cloud_reduce", "mvs_cloud_select"]
     assert '#include "mvs_abi.h"' in src and '#include "mvs_normals_abi.h"' in src
-    assert int(re.search(r"^#define MVS_REDUCE_ROUNDS_MAX (\d+)", src, flags=re.M).group(1)) == 256 == _lib.REDUCE_ROUNDS_MAX \
-        == RR.ROUNDS_MAX
-    main = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
-    assert "Likewise include/mvs_reduce_abi.h" in main
-    for other in sorted(set(_lib._ABI) - {"mvs_reduce_abi.h"}):
-        text = open(os.path.join(REPO, "include", other)).read()
-        assert not re.search(r"^int\s+mvs_\w*(reduce|select)", text, flags=re.M), other
+    assert refusals.define(src, "MVS_REDUCE_ROUNDS_MAX") == 256 == _lib.REDUCE_ROUNDS_MAX == RR.ROUNDS_MAX
+    assert "Likewise include/mvs_reduce_abi.h" in refusals.header_text("mvs_abi.h")
     # what is still not DTU's is said where the contract is
     assert "randperm is replaced by the hash" in src and "nothing here was compared against the MATLAB code" in src
     assert "per-scan tables are not built" in src
-    assert sorted(_lib._ABI) == sorted(f for f in os.listdir(os.path.join(REPO, "include")) if f.endswith(".h"))
-    assert _lib.load().mvs_abi_version() == 2 == _lib.ABI_VERSION
 
 
 # ---------------------------------------------------------------- workspace formula
@@ -480,8 +389,3 @@ def test_the_command_lines_take_the_dtu_flags(monkeypatch, tmp_path):
     assert kw["plane"].tolist() == [0.0, 0.0, 1.0, -2.0]
     none = argparse.Namespace(reduce_dist=None, reduce_seed=0, reduce_gt=False, obs_mask=None, plane=None)
     assert eval_cloud.dtu_options(none) == dict(reduce=None, obs_mask=None, plane=None)
-
-
-if __name__ == "__main__":
-    assert sys.argv[1] == "--refusals"
-    _child()

@@ -6,22 +6,24 @@ lies within the dense bound, and every mutation of that restatement is CAUGHT by
     ReLU(shift0) in the fused kernel's padding ring           -> crafted probe, variant "shift"
     a residue in the padded panel slots                       -> padded-tap probe
     the tap with the least weight mass dropped                -> dense bound, standard-normal input
-Also the C-ABI refusals of mvs_feature_conv01_fmt (nothing is launched, so no GPU is needed).
+Also the C-ABI refusals of mvs_feature_conv01_fmt (tests/refusals.py makes the calls in a child that sees no device).
 
 Worst |reference fp32 - fp64 chain| / chained bound over the fixtures and the ragged oracle case: 5.5e-8 (printed by
 test_fp64_chain_reproduces_the_reference; recorded as featnet_ref.REFERENCE_WORST).
 """
-import ctypes
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
 
 import featnet_ref as R
 import probes
+import refusals
 from conftest import REPO, load_fixture, load_weights
 from oracle import oracle as orc
+from refusals import BAD_DTYPE, BAD_SHAPE, NULL
 from scene_3dreconstruction_mvsnet_amd import _lib
 
 ST = R.fstate(load_weights())
@@ -206,26 +208,33 @@ def test_fused_emulation_passes_and_the_relu_shift_ring_is_caught():
 
 
 # ---- the C ABI refuses bad arguments and enqueues nothing ------------------------------------------------------------
-def _conv01(N=2, H=32, W=32, fmt=0, null=None):
-    ptrs = {"imgs": ctypes.c_void_p(0x1000), "y": ctypes.c_void_p(0x2000), "blob": ctypes.c_void_p(0x3000)}   # never dereferenced
-    if null:
-        ptrs[null] = None
-    return _lib.load().mvs_feature_conv01_fmt(ptrs["imgs"], fmt, ptrs["y"], ptrs["blob"], N, H, W, None)
+# every refusal of mvs_feature_conv01_fmt, run by tests/refusals.py in a child that sees no device; the tests look their
+# record up
+NULLS = dict(imgs="imgs", y="y", blob="feature_blob")
+FORMATS = [-1, 3]
+BAD_SHAPES = [dict(H=3), dict(W=3), dict(N=0), dict(N=65536, H=4, W=4), dict(N=1, H=16384, W=16384), dict(N=52, H=2048, W=2560),
+              dict(N=2, H=16384, W=8192)]
+REFUSALS = {"mvs_feature_conv01_fmt": dict(
+    good=dict(N=2, H=32, W=32, image_format=0),
+    cases=refusals.cases(*[({p: None}, NULL, "NULL") for p in NULLS.values()],
+                         *[(dict(image_format=f), BAD_DTYPE, "") for f in FORMATS], *[(bad, BAD_SHAPE, "") for bad in BAD_SHAPES]))}
 
 
-@pytest.mark.parametrize("null", ["imgs", "y", "blob"])
+def _refused(**ov):
+    return refusals.expect(sys.modules[__name__], "mvs_feature_conv01_fmt", ov)
+
+
+@pytest.mark.parametrize("null", list(NULLS))
 def test_conv01_refuses_null(null):
-    assert _conv01(null=null) == 5                               # MVS_ERR_NULL
-    assert b"NULL" in _lib.load().mvs_last_error_string()
+    assert _refused(**{NULLS[null]: None}) == NULL
 
 
-@pytest.mark.parametrize("fmt", [-1, 3])
+@pytest.mark.parametrize("fmt", FORMATS)
 def test_conv01_refuses_unknown_format(fmt):
-    assert _conv01(fmt=fmt) == 2                                 # MVS_ERR_BAD_DTYPE
+    assert _refused(image_format=fmt) == BAD_DTYPE
 
 
-@pytest.mark.parametrize("shape", [dict(H=3), dict(W=3), dict(N=0), dict(N=65536, H=4, W=4), dict(N=1, H=16384, W=16384),
-                                   dict(N=52, H=2048, W=2560), dict(N=2, H=16384, W=8192)])
+@pytest.mark.parametrize("shape", BAD_SHAPES)
 def test_conv01_refuses_bad_shape(shape):
-    assert _conv01(**shape) == 1                                 # MVS_ERR_BAD_SHAPE
+    assert _refused(**shape) == BAD_SHAPE
     assert "mvs_feature_conv01_fmt" in _lib.SYMBOLS

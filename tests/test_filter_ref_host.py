@@ -2,19 +2,19 @@
 reference's recorded outputs (tests/golden/fx_filter.npz), every path of the census is reached by the scene that owns
 it, the left-out share stays under its cap, every named defect is caught by its scene -- and the two K-swap defects are
 NOT caught on a scene whose views share one K --, mvs_filter_compose reproduces the reference's float32 inverses and
-products slot by slot, and the C ABI refuses bad sizes and NULLs before anything is enqueued (the pointers below are
-never dereferenced)."""
-import ctypes
+products slot by slot, and the C ABI refuses bad sizes and NULLs before anything is enqueued (mvs_filter_depth is called
+by tests/refusals.py in a child process that sees no device; mvs_filter_compose takes host memory only)."""
+import sys
 
 import numpy as np
 import pytest
 
 import filter_ref as R
+import refusals
 from conftest import load_fixture
 from oracle import filter_oracle as fo
+from refusals import BAD_SHAPE, NULL
 from scene_3dreconstruction_mvsnet_amd import _lib
-
-_FAKE = [ctypes.c_void_p(0x100000 * (i + 1)) for i in range(10)]   # never dereferenced
 
 
 @pytest.fixture(scope="module")
@@ -130,25 +130,19 @@ def test_compose_slots_against_the_reference_products(fx):
             assert np.abs(pm[r, j, :12].reshape(3, 4) - EE[a, b][:3]).max() > 1e-2
 
 
-GOOD = dict(V=3, R=2, S=2, h=8, w=8)
+GOOD = dict(V=3, R=2, S=2, h=8, w=8, photomask=0.8, geomask=3, condmask_pixel=1.0, condmask_depth=0.01)
+PTRS = ("depth", "conf", "ref_mats", "pair_mats", "ref_idx", "src_idx", "geo_sum", "depth_avg", "masks", "xyz_world")
+BAD_SIZES = [dict(h=32768), dict(w=32768), dict(R=65536), dict(V=0), dict(R=0), dict(S=0), dict(h=0), dict(w=0), dict(h=-1)]
+# every refusal of mvs_filter_depth, run by tests/refusals.py in a child that sees no device; the tests look their record up
+REFUSALS = {"mvs_filter_depth": dict(good=GOOD, cases=refusals.cases(*[(bad, BAD_SHAPE, "") for bad in BAD_SIZES],
+                                                                       *[({p: None}, NULL, "NULL") for p in PTRS]))}
 
 
-def _filter(null=None, **kw):
-    a = dict(GOOD, **kw)
-    p = list(_FAKE)
-    if null is not None:
-        p[null] = None
-    return _lib.load().mvs_filter_depth(*p[:6], a["V"], a["R"], a["S"], a["h"], a["w"], 0.8, 3, 1.0, 0.01, *p[6:10], None)
-
-
-@pytest.mark.parametrize("shape", [dict(h=32768), dict(w=32768), dict(R=65536), dict(V=0), dict(R=0), dict(S=0), dict(h=0),
-                                   dict(w=0), dict(h=-1)])
+@pytest.mark.parametrize("shape", BAD_SIZES)
 def test_filter_depth_refuses_bad_sizes(shape):
-    assert _filter(**shape) == 1                                  # MVS_ERR_BAD_SHAPE
-    assert _lib.load().mvs_last_error_string()
+    assert refusals.expect(sys.modules[__name__], "mvs_filter_depth", shape) == BAD_SHAPE
 
 
 def test_filter_depth_refuses_each_null():
-    for k in range(10):
-        assert _filter(null=k) == 5, k                            # MVS_ERR_NULL
-    assert b"NULL" in _lib.load().mvs_last_error_string()
+    for p in PTRS:
+        assert refusals.expect(sys.modules[__name__], "mvs_filter_depth", {p: None}) == NULL, p

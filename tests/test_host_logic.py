@@ -1,56 +1,21 @@
 """CPU-side checks: the C-ABI library loads and exports every declared symbol, argument
 validation / error strings, weight packing (BN fold + layout) and the drop-in module's
 checkpoint-key compatibility.  No kernel is launched here (no GPU in this suite)."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import refusals
 from conftest import REPO, load_weights
 from scene_3dreconstruction_mvsnet_amd import MVSNet, _lib
 
 
-_C_SCALARS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double,
-              "long long": ctypes.c_longlong}
-
-
-def header_argtypes(header):
-    """{entry point: the ctypes argument list its prototype in the header text asks for}: `size_t*` is
-    POINTER(c_size_t), a pointer to pointers (`const float* const*`) POINTER(c_void_p), any other pointer c_void_p, and
-    int, size_t, float, double and long long their ctypes."""
-    out = {}
-    for name, params in re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(([^)]*)\)\s*;", header, flags=re.M):
-        kinds = []
-        for param in ([] if params.strip() == "void" else params.split(",")):
-            ctype = " ".join(re.sub(r"\bconst\b", " ", re.sub(r"\w+\s*$", "", param.strip())).replace("*", " * ").split())
-            if ctype.count("*") == 2:
-                kinds.append(ctypes.POINTER(ctypes.c_void_p))
-            elif ctype == "size_t *":
-                kinds.append(ctypes.POINTER(ctypes.c_size_t))
-            elif ctype.endswith("*"):
-                kinds.append(ctypes.c_void_p)
-            else:
-                kinds.append(_C_SCALARS[ctype])
-        out[name] = kinds
-    return out
-
-
 def test_library_exports_every_declared_symbol():
-    header = open(os.path.join(REPO, "include", "mvs_abi.h")).read()
-    declared = set(re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
-    # every argument list handed to ctypes is its prototype's: same length, same kind at every position
-    prototypes = header_argtypes(header)
-    assert set(prototypes) == declared
-    for name, kinds in prototypes.items():
-        assert _lib._ABI["mvs_abi.h"][name] == kinds, name
-        assert list(getattr(_lib.load(), name).argtypes) == kinds, name
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
+    """mvs_abi.h's declarations are SYMBOLS, and every argument list handed to ctypes is its prototype's: same length,
+    same kind at every position (refusals.check_header, which every header's host file calls)"""
+    refusals.check_header("mvs_abi.h", _lib.SYMBOLS)
     assert _lib.load().mvs_abi_version() == 2
 
 

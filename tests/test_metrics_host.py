@@ -1,13 +1,17 @@
-"""Ground-truth metrics, host side: the C-ABI refusals of mvs_depth_metrics (no kernel is launched) and the
+"""Ground-truth metrics, host side: the C-ABI refusals of mvs_depth_metrics (no kernel is launched: tests/refusals.py makes
+the calls in a child process that sees no device) and the
 sums -> scalar-dict step of metrics.py against the reference's values (tests/golden/fx_gt.npz)."""
 import ctypes
 import math
 import os
+import sys
 
 import numpy as np
 import pytest
 
+import refusals
 from conftest import GOLDEN
+from refusals import BAD_SHAPE, NULL, WORKSPACE
 from scene_3dreconstruction_mvsnet_amd import _lib
 from scene_3dreconstruction_mvsnet_amd.metrics import KEYS, batch_scalars, final_scalars
 
@@ -33,37 +37,38 @@ def host_sums(est, gt, mask, thresholds=THRES):
 
 
 # ---- the C ABI refuses bad arguments and enqueues nothing -----------------------------------------
-def _call(B=2, h=8, w=8, n_thres=4, null=None, ws_bytes=None):
-    lib = _lib.load()
-    fake = [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(5)]   # never dereferenced: refused first
-    th = (ctypes.c_float * 9)(*([1.0] * 9))
-    ptrs = {"est": fake[0], "gt": fake[1], "mask": fake[2], "sums": fake[3], "ws": fake[4], "thres": th}
-    if null:
-        ptrs[null] = None
-    if ws_bytes is None:     # a workspace that would be large enough, so the shape is what gets refused
-        ws_bytes = 1 << 40
-    return lib.mvs_depth_metrics(ptrs["est"], ptrs["gt"], ptrs["mask"], B, h, w, ptrs["thres"], n_thres,
-                                 ptrs["sums"], None, ptrs["ws"], ws_bytes, None)
+# every refusal of mvs_depth_metrics, run by tests/refusals.py in a child that sees no device; the tests look their record up
+NULLS = dict(est="depth_est", gt="depth_gt", mask="mask", sums="sums_out", ws="workspace", thres="thresholds")
+BAD_SHAPES = [dict(B=0), dict(h=0), dict(w=0), dict(n_thres=9), dict(n_thres=-1), dict(B=2, h=32768, w=32768), dict(B=-1)]
+SHORT = [dict(B=2, h=37, w=53, workspace_bytes="need-1"), dict(B=2, h=37, w=53, workspace_bytes=0)]
+REFUSALS = {"mvs_depth_metrics": dict(
+    good=dict(B=2, h=8, w=8, thresholds=(1.0,) * 9, n_thres=4, errmap_out=None), host=dict(thresholds=ctypes.c_float),
+    optional=("errmap_out",), sizes=dict(need=lambda a: _lib.query_metrics_workspace(a["B"], a["h"], a["w"])),
+    cases=refusals.cases(*[({p: None}, NULL, "NULL") for p in NULLS.values()], *[(bad, BAD_SHAPE, "") for bad in BAD_SHAPES],
+                         *[(short, WORKSPACE, "") for short in SHORT]))}
 
 
-@pytest.mark.parametrize("null", ["est", "gt", "mask", "sums", "ws", "thres"])
+def _refused(**ov):
+    return refusals.expect(sys.modules[__name__], "mvs_depth_metrics", ov)
+
+
+@pytest.mark.parametrize("null", list(NULLS))
 def test_null_pointer_is_refused(null):
-    assert _call(null=null) == 5                                  # MVS_ERR_NULL
-    assert b"NULL" in _lib.load().mvs_last_error_string()
+    assert _refused(**{NULLS[null]: None}) == NULL
 
 
-@pytest.mark.parametrize("shape", [dict(B=0), dict(h=0), dict(w=0), dict(n_thres=9), dict(n_thres=-1),
-                                   dict(B=2, h=32768, w=32768), dict(B=-1)])
+@pytest.mark.parametrize("shape", BAD_SHAPES)
 def test_bad_shape_is_refused(shape):
-    assert _call(**shape) == 1                                    # MVS_ERR_BAD_SHAPE
+    assert _refused(**shape) == BAD_SHAPE
 
 
 def test_short_workspace_is_refused():
     lib = _lib.load()
     need = ctypes.c_size_t(0)
     assert lib.mvs_query_metrics_workspace(2, 37, 53, ctypes.byref(need)) == 0 and need.value > 0
-    assert _call(B=2, h=37, w=53, ws_bytes=need.value - 1) == 3   # MVS_ERR_WORKSPACE
-    assert _call(B=2, h=37, w=53, ws_bytes=0) == 3
+    assert need.value == _lib.query_metrics_workspace(2, 37, 53)      # the size the child's "need" is
+    for short in SHORT:
+        assert _refused(**short) == WORKSPACE
 
 
 def test_workspace_query():

@@ -39,6 +39,7 @@ import numpy as np
 import torch
 from torch.utils._pytree import tree_flatten, tree_map
 
+import refusals
 import test_abi_domain_host as dom
 from scene_3dreconstruction_mvsnet_amd import _lib, module, mvsnet
 
@@ -49,27 +50,7 @@ STREAM_BASE = 0x5000          # the stand-in stream handle of device k is STREAM
 
 # ---- the headers' prototypes ------------------------------------------------------------------------------------------
 HOST_ENTRIES = ("mvs_pack_weights", "mvs_pack_feature_weights", "mvs_filter_compose")
-
-
-def prototypes():
-    """{entry point: [(kind, name)]} of every header in _lib._ABI; kind is 'ptr' or the C type."""
-    out = {}
-    for header in _lib._ABI:
-        text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-        for name, params in re.findall(r"^(?:int|const char\*)\s+(mvs_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.M | re.S):
-            plist = []
-            for param in ([] if params.strip() == "void" else params.split(",")):
-                param = " ".join(param.split())
-                array = param.endswith("]")
-                param = re.sub(r"\[\w*\]$", "", param).strip()
-                pname = re.search(r"(\w+)$", param).group(1)
-                ctype = " ".join(re.sub(r"\bconst\b", " ", param[:-len(pname)]).split())
-                plist.append(("ptr" if array or "*" in ctype else ctype, pname))
-            out[name] = plist
-    return out
-
-
-PROTOS = prototypes()
+PROTOS = refusals.all_prototypes()      # {entry point: [(kind, name)]} of every header; kind is 'ptr' or the C type
 ALL_ENTRIES = tuple(n for table in _lib._ABI.values() for n in table)
 FORWARDED = tuple(n for n in ALL_ENTRIES if n.startswith("mvs_query_") or n in HOST_ENTRIES
                   or n in ("mvs_abi_version", "mvs_last_error_string"))
@@ -714,7 +695,7 @@ def run_case(case, mode, leaf=None, defect=None, index=0, all_host=False):
 def library_case_exists(expect):
     """`library:<entry point>/<case label>` names a case of SPECS in tests/test_abi_domain_host.py."""
     ep, label = expect[len("library:"):].split("/", 1)
-    return ep in dom.SPECS and any(lb == label for lb, _, _ in dom.cases_of(ep, dom.SPECS[ep], dom.prototypes()))
+    return ep in dom.SPECS and any(lb == label for lb, _, _ in dom.cases_of(ep, dom.SPECS[ep], refusals.prototypes("mvs_abi.h")))
 
 
 def agrees(expect, verdict):
