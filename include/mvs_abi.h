@@ -69,7 +69,8 @@ extern "C" {
  * Likewise include/mvs_outliers_abi.h: statistical outlier removal among the points of a cloud inside a box.
  * Likewise include/mvs_distance_abi.h: the distance from every point of one cloud to the nearest point of another.
  * Likewise include/mvs_reduce_abi.h: DTU's point reduction, observability mask and ground-plane filter of a cloud.
- * Likewise include/mvs_cluster_abi.h: the density-connected components (DBSCAN) of a cloud and the mask of the large ones. */
+ * Likewise include/mvs_cluster_abi.h: the density-connected components (DBSCAN) of a cloud and the mask of the large ones.
+ * Likewise include/ext/mvs_register_abi.h: the rigid registration of one cloud onto another (ICP). */
 #define MVS_ABI_VERSION 2
 
 typedef enum mvs_status {

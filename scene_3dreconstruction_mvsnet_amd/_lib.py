@@ -142,6 +142,17 @@ DISTANCE_SYMBOLS = tuple(_ABI["mvs_distance_abi.h"])
 REDUCE_SYMBOLS = tuple(_ABI["mvs_reduce_abi.h"])
 CLUSTER_SYMBOLS = tuple(_ABI["mvs_cluster_abi.h"])
 
+# The headers under include/ext/, kept in a table of their own: `_ABI` is exactly the headers of include/*.h.  load()
+# applies both; tests/test_cloud_register_host.py holds this one to its prototypes.
+_ABI_EXT = {
+    "ext/mvs_register_abi.h": {
+        "mvs_query_register_workspace": [_ll, _ll, _vp, _vp, _d, _i, _szp],
+        "mvs_cloud_register": [_vp, _i, _ll, _vp, _vp, _i, _ll, _vp, _vp, _d, _d, _vp, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _sz, _vp],
+    },
+}
+REGISTER_SYMBOLS = tuple(_ABI_EXT["ext/mvs_register_abi.h"])
+
 
 class MvsError(RuntimeError):
     """Non-zero status from libmvs_hip.so (decoded with mvs_last_error_string)."""
@@ -164,10 +175,10 @@ def load():
                 "There is no CPU/PyTorch fallback for the MVSNet depth path.")
         lib = ctypes.CDLL(LIB_PATH)
         for name in (SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS + OUTLIERS_SYMBOLS + DISTANCE_SYMBOLS
-                     + REDUCE_SYMBOLS + CLUSTER_SYMBOLS):
+                     + REDUCE_SYMBOLS + CLUSTER_SYMBOLS + REGISTER_SYMBOLS):
             if not hasattr(lib, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}")
-        for prototypes in _ABI.values():
+        for prototypes in list(_ABI.values()) + list(_ABI_EXT.values()):
             for name, argtypes in prototypes.items():
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
@@ -1305,6 +1316,80 @@ def cloud_cluster(xyz, box_min, box_max, cell, eps, min_points=10, min_size=1, o
                                        labels.data_ptr(), keep.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
                                        _stream(dev)))
     return labels, keep, counts
+
+
+# ---- rigid registration, ICP (include/ext/mvs_register_abi.h, csrc/cloud_register.hip) ----
+# MVS_REGISTER_ITERATIONS_MAX, _TERMS, _HISTORY, _GROUP, _FANIN, _SCALARS
+REGISTER_ITERATIONS_MAX, REGISTER_TERMS, REGISTER_HISTORY, REGISTER_GROUP, REGISTER_FANIN, REGISTER_SCALARS = 1000, 31, 19, 32, 256, 512
+REGISTER_STOPS = {1: "converged", 2: "max_iterations", 3: "degenerate"}     # MVS_REGISTER_STOP_*
+
+
+def query_register_workspace(P, N, box_min, box_max, cell, max_iterations=30) -> int:
+    lo, hi = _box_arg(box_min, box_max, "query_register_workspace")
+    return _query("mvs_query_register_workspace", int(P), int(N), lo, hi, float(cell), int(max_iterations))
+
+
+def cloud_register(target, source, box_min, box_max, cell, max_dist, target_normals=None, init=None, max_iterations=30,
+                   rel_fitness=1e-6, rel_rmse=1e-6, history=False, systems=False, indices=False, out=None):
+    """The rigid transform that lays `source` onto `target` by iterative closest point, with the semantics of Open3D's
+    registration_icp (include/ext/mvs_register_abi.h), on the device.
+
+    target float32 or float64 [P,3] and source float32 or float64 [N,3] on one device (they may be the same tensor);
+    target_normals: [P,3] of target's dtype -> point-to-plane, None -> point-to-point; box_min, box_max: 3 host numbers
+    each, the box of `target`; cell: the search grid's cell edge (it changes the time, never the result); max_dist >= 0,
+    +inf allowed; init: 16 host numbers (4 x 4, row-major, last row 0 0 0 1) or None for the identity; rel_fitness,
+    rel_rmse >= 0: the changes of fitness and rmse below which the loop stops.  Returns (transformation float64 [4,4],
+    counts int64 [4]: counted sources, inliers, iterations run, stop reason (REGISTER_STOPS), stats float64 [2]: fitness
+    and inlier rmse, history float64 [max_iterations + 1, 19] or None: T_k, fitness, rmse, inliers of every evaluation
+    (NaN after the stop), systems float64 [max_iterations, 31] or None: the reduced sums of every step, idx int32 [N] or
+    None: the target row of every source in the last evaluation, -1 for none), all on the device.  `out` = (the same six,
+    None where not wanted) receives the results.  Enqueued on the current stream; nothing synchronises."""
+    import math
+    import numpy as np
+    target, source = _cloud_xyz(target, "cloud_register"), _cloud_xyz(source, "cloud_register")
+    dev = target.device
+    if source.device != dev:
+        raise RuntimeError("cloud_register: target and source must be on one device")
+    P, N, cap, its = target.shape[0], source.shape[0], float(max_dist), int(max_iterations)
+    if target_normals is not None:
+        if P == 0:
+            raise RuntimeError("cloud_register: target_normals of an empty target (pass None)")
+        target_normals = _cloud_rows(target_normals, "target_normals", target.dtype, P, dev, "cloud_register")
+    if not 0 <= its <= REGISTER_ITERATIONS_MAX:
+        raise RuntimeError(f"cloud_register: max_iterations = {its} (need 0 <= max_iterations <= {REGISTER_ITERATIONS_MAX})")
+    if not cap >= 0.0:
+        raise RuntimeError(f"cloud_register: max_dist = {cap} (need max_dist >= 0; +inf is allowed)")
+    rel_fitness, rel_rmse = float(rel_fitness), float(rel_rmse)
+    if not (rel_fitness >= 0.0 and rel_rmse >= 0.0):
+        raise RuntimeError(f"cloud_register: rel_fitness = {rel_fitness}, rel_rmse = {rel_rmse} (need both >= 0)")
+    T0 = None
+    if init is not None:
+        if isinstance(init, torch.Tensor):
+            if init.device.type != "cpu":
+                raise RuntimeError(f"cloud_register: init must be host numbers (got a tensor on {init.device}): it travels "
+                                   "in the kernel arguments, reading device memory would sync")
+        flat = np.asarray(init, dtype=np.float64).reshape(-1).tolist()
+        if len(flat) != 16 or not all(math.isfinite(x) for x in flat) or flat[12:] != [0.0, 0.0, 0.0, 1.0]:
+            raise RuntimeError("cloud_register: init must be 16 finite numbers, a 4 x 4 matrix whose last row is 0 0 0 1")
+        T0 = (_d * 16)(*flat)
+    lo, hi = _box_arg(box_min, box_max, "cloud_register")
+    nbytes = _query("mvs_query_register_workspace", P, N, lo, hi, float(cell), its)
+    with torch.cuda.device(dev):
+        T, counts, stats, hist, system, idx = _outputs("cloud_register", dev, [
+            ("transformation", (4, 4), torch.float64, True), ("counts", (4,), torch.int64, True),
+            ("stats", (2,), torch.float64, True), ("history", (its + 1, REGISTER_HISTORY), torch.float64, history),
+            ("systems", (its, REGISTER_TERMS), torch.float64, systems), ("idx", (N,), torch.int32, indices)], out)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        # P == 0, N == 0: the library does not read the empty cloud; it gets the workspace's address in place of an empty
+        # tensor's.  An empty systems or idx tensor is not written either
+        check(load().mvs_cloud_register(
+            target.data_ptr() if P else ws.data_ptr(), _xyz_code(target), P,
+            None if target_normals is None else target_normals.data_ptr(),
+            source.data_ptr() if N else ws.data_ptr(), _xyz_code(source), N, lo, hi, float(cell), cap, T0, its, rel_fitness,
+            rel_rmse, T.data_ptr(), counts.data_ptr(), stats.data_ptr(), None if hist is None else hist.data_ptr(),
+            None if system is None or its == 0 else system.data_ptr(), None if idx is None or N == 0 else idx.data_ptr(),
+            ws.data_ptr(), ws.numel(), _stream(dev)))
+    return T, counts, stats, hist, system, idx
 
 
 # ---- FeatureNet (reference models/mvsnet.py:10-30) -------------------------------------------

@@ -3,13 +3,16 @@ precision / recall / F-score at thresholds (fusion.evaluate_cloud, include/mvs_d
 
     python -m scene_3dreconstruction_mvsnet_amd.eval_cloud --pred A.ply --gt B.ply [--max_dist 20 --thresholds 1 2 5
         --box x0 y0 z0 x1 y1 z1 --cell C --json OUT
-        --reduce_dist 0.2 [--reduce_seed 0] [--reduce_gt] --obs_mask FILE --plane FILE]
+        --reduce_dist 0.2 [--reduce_seed 0] [--reduce_gt] --obs_mask FILE --plane FILE
+        --register_dist D [--register_iters 30] [--register_point_to_point]]
 
 Both files are read with fusion.read_ply (binary little-endian or ascii vertices).  The dict is printed as one JSON line
 and, with --json, written to OUT.  Without the last line of options this is the definition of the distances alone; with
 them DTU's point reduction, observability mask (ObsMask/ObsMaskN_10.mat or an .npz) and ground-plane filter
 (ObsMask/PlaneN.mat or an .npz) are applied in DTU's order (see fusion.evaluate_cloud, which also says what is still
-not DTU's); units are those of the files.
+not DTU's); units are those of the files.  --register_dist D first lays the reconstruction onto the ground truth by ICP
+(fusion.register_cloud: pairs within D, point-to-plane on the ground truth's estimated normals unless
+--register_point_to_point), for clouds that do not share a frame exactly.
 reconstruct.py takes the same options with --gt_ply.
 """
 from __future__ import annotations
@@ -36,6 +39,11 @@ def add_score_arguments(p):
                    help="DTU's observability mask (.mat or .npz with ObsMask, BB, Res): accuracy over the observed points")
     p.add_argument("--plane", default=None, metavar="FILE",
                    help="DTU's ground plane (.mat or .npz with P): completeness over the ground truth above it")
+    p.add_argument("--register_dist", type=float, default=None, metavar="D",
+                   help="align the reconstruction onto the ground truth by ICP first, pairing points within D")
+    p.add_argument("--register_iters", type=int, default=30, help="the most ICP iterations (needs --register_dist)")
+    p.add_argument("--register_point_to_point", action="store_true",
+                   help="point-to-point ICP instead of point-to-plane (needs --register_dist)")
 
 
 def dtu_options(args, scan=None):
@@ -51,6 +59,14 @@ def dtu_options(args, scan=None):
                 plane=None if args.plane is None else fusion.read_plane(name(args.plane)))
 
 
+def register_options(args):
+    """The register keyword of fusion.evaluate_cloud from the options of add_score_arguments."""
+    if args.register_dist is None and (args.register_point_to_point or args.register_iters != 30):
+        raise SystemExit("--register_iters and --register_point_to_point need --register_dist")
+    return None if args.register_dist is None else dict(max_dist=args.register_dist, max_iterations=args.register_iters,
+                                                        point_to_plane=not args.register_point_to_point)
+
+
 def score(pred_xyz, gt_xyz, args, device=None, scan=None):
     """fusion.evaluate_cloud of two host arrays [.,3] with the options of add_score_arguments."""
     import numpy as np
@@ -63,7 +79,7 @@ def score(pred_xyz, gt_xyz, args, device=None, scan=None):
     box = None if args.box is None else (args.box[:3], args.box[3:])
     pred, gt = (torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (pred_xyz, gt_xyz))
     return fusion.evaluate_cloud(pred, gt, max_dist=args.max_dist, thresholds=tuple(args.thresholds), box=box, cell=args.cell,
-                                 **dtu_options(args, scan))
+                                 register=register_options(args), **dtu_options(args, scan))
 
 
 def main(argv=None):

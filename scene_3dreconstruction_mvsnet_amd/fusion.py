@@ -398,6 +398,48 @@ def cloud_distance(query, ref, max_dist=float("inf"), thresholds=(), box=None, c
     return (dist, counts, stats, idx) if return_indices else (dist, counts, stats)
 
 
+def register_cloud(source, target, max_dist, target_normals=None, init=None, max_iterations=30, rel_fitness=1e-6,
+                   rel_rmse=1e-6, box=None, cell=None):
+    """The rigid transform that lays `source` onto `target` (both float32 or float64 [.,3] on the GPU) by iterative
+    closest point on the device (mvs_cloud_register, include/ext/mvs_register_abi.h), with the semantics of Open3D's
+    registration_icp: every iteration pairs each transformed source point with its nearest target point within max_dist
+    and takes the rigid motion that brings the pairs closest -- point-to-plane with target_normals ([P,3], e.g.
+    estimate_normals(target)[0]; their sign does not matter), point-to-point without.  It stops when fitness and rmse both
+    change by less than rel_fitness and rel_rmse, after max_iterations, or when too few pairs are left.  A source row
+    with a NaN is left out: a cluster is registered by passing the cloud with every other row set to NaN.  init: 4 x 4
+    host numbers, default identity.  box = (min, max) limits the target points that are searched; it defaults to the
+    bounding box of target's finite points grown by max_dist (one host synchronisation; with a box given nothing
+    synchronises).  cell as in cloud_distance.
+    Returns a dict of device tensors: transformation float64 [4,4] (apply it with transform_cloud), fitness (inliers /
+    counted sources) and inlier_rmse float64 scalars, iterations and stop int64 scalars (stop: 1 converged,
+    2 max_iterations, 3 degenerate; _lib.REGISTER_STOPS), history float64 [max_iterations + 1, 19]: the transform (16),
+    fitness, rmse and inlier count of every evaluation, NaN after the last."""
+    for name, t in (("source", source), ("target", target)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"register_cloud: {name} must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    if box is None:
+        lo, hi = _finite_box(target)
+        grow = float(max_dist) if np.isfinite(max_dist) and max_dist > 0 else 0.0
+        lo, hi = [v - grow for v in lo], [v + grow for v in hi]
+    else:
+        lo, hi = box
+    if cell is None:
+        cell = distance_cell((lo, hi), target.shape[0])
+    if target_normals is not None and isinstance(target_normals, torch.Tensor) and target_normals.dtype != target.dtype:
+        target_normals = target_normals.to(target.dtype)
+    T, counts, stats, history, _, _ = _lib.cloud_register(target, source, lo, hi, cell, max_dist, target_normals=target_normals,
+                                                          init=init, max_iterations=max_iterations, rel_fitness=rel_fitness,
+                                                          rel_rmse=rel_rmse, history=True)
+    return dict(transformation=T, fitness=stats[0], inlier_rmse=stats[1], iterations=counts[2], stop=counts[3], history=history)
+
+
+def transform_cloud(xyz, T):
+    """R x + t for every row x of xyz ([P,3], any float dtype, any device) under the 4 x 4 transform T (a tensor or host
+    numbers), computed in float64 and returned in xyz's dtype.  Plain torch."""
+    T = torch.as_tensor(T, dtype=torch.float64).to(xyz.device).reshape(4, 4)
+    return (xyz.double() @ T[:3, :3].T + T[:3, 3]).to(xyz.dtype)
+
+
 def reduce_cell(box, P, min_dist):
     """The cell edge reduce_cloud picks: min_dist, so that a member's candidates are the 27 cells around it, but never
     below distance_cell(box, P), which keeps the grid inside DISTANCE_CELL_BUDGET however small min_dist is against the
@@ -524,7 +566,7 @@ def read_plane(path):
 
 
 def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), box=None, cell=None, reduce=None,
-                   obs_mask=None, plane=None):
+                   obs_mask=None, plane=None, register=None):
     """The measure a reconstruction is judged by, both directions of `cloud_distance` on the device:
         accuracy      from every point of pred_xyz to the nearest point of gt_xyz
         completeness  from every point of gt_xyz to the nearest point of pred_xyz
@@ -552,9 +594,30 @@ def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), 
     select_cloud per direction ("accuracy", "completeness").
     What this still is not: DTU's tables.  MATLAB's randperm is replaced by a stated hash, so the kept points differ from
     those of any MATLAB run while their distribution is the same; nothing was compared against the MATLAB code or real
-    DTU files; the per-scan tables are not built."""
+    DTU files; the per-scan tables are not built.
+
+    register = dict(max_dist=..., point_to_plane=True, knn=30, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
+    init=None) first lays the reconstruction onto the ground truth with `register_cloud` (ICP), for clouds that do not
+    share a frame exactly: a laser scan, a CAD model, another rig.  Point-to-plane takes the ground truth's normals from
+    `estimate_normals` over `knn` neighbours.  Everything above is then measured on the moved reconstruction, and the dict
+    gains `transformation` (4 x 4), `register_fitness` and `register_rmse`.  Without it nothing changes."""
     thresholds = [float(t) for t in thresholds]
     T = len(thresholds)
+    registered = None
+    if register is not None:
+        opt = dict(dict(point_to_plane=True, knn=30, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6, init=None), **register)
+        unknown = set(opt) - {"max_dist", "point_to_plane", "knn", "max_iterations", "rel_fitness", "rel_rmse", "init"}
+        if unknown or "max_dist" not in opt:
+            raise ValueError(f"evaluate_cloud: register needs max_dist and takes point_to_plane, knn, max_iterations, "
+                             f"rel_fitness, rel_rmse, init (unknown: {sorted(unknown)})")
+        for name, t in (("pred_xyz", pred_xyz), ("gt_xyz", gt_xyz)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError(f"evaluate_cloud: {name} must be a CUDA(ROCm) tensor; there is no CPU implementation")
+        normals = estimate_normals(gt_xyz, knn=opt["knn"])[0] if opt["point_to_plane"] and gt_xyz.shape[0] else None
+        registered = register_cloud(pred_xyz, gt_xyz, opt["max_dist"], target_normals=normals, init=opt["init"],
+                                    max_iterations=opt["max_iterations"], rel_fitness=opt["rel_fitness"],
+                                    rel_rmse=opt["rel_rmse"])
+        pred_xyz = transform_cloud(pred_xyz, registered["transformation"])
     pairs =((pred_xyz, gt_xyz), (gt_xyz, pred_xyz))
     dtu = reduce is not None or obs_mask is not None or plane is not None
     if dtu:
@@ -587,6 +650,8 @@ def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), 
         parts += [counts.double(), stats, median.reshape(1)]
     if dtu:
         parts += [c.double() for c in selected] + [c.double() for c in reduction.values()]
+    if registered is not None:
+        parts += [registered["transformation"].reshape(16), registered["fitness"].reshape(1), registered["inlier_rmse"].reshape(1)]
     host = torch.cat(parts).cpu().tolist()                # the one copy; every count is below 2^31, exact as a double
     out = {}
     for name, v in (("accuracy", host[:T + 5]), ("completeness", host[T + 5:])):
@@ -598,9 +663,12 @@ def evaluate_cloud(pred_xyz, gt_xyz, max_dist=20.0, thresholds=(1.0, 2.0, 5.0), 
     out["fscore"] = [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(out["precision"], out["recall"])]
     out["max_dist"], out["thresholds"] = float(max_dist), thresholds
     if dtu:
-        tail = [int(v) for v in host[2 * (T + 5):]]
+        tail = [int(v) for v in host[2 * (T + 5):2 * (T + 5) + 6 + 4 * len(reduction)]]
         out["selection"] = dict(accuracy=tail[0:3], completeness=tail[3:6])
         out["reduction"] = {name: tail[6 + 4 * k:10 + 4 * k] for k, name in enumerate(reduction)}
+    if registered is not None:
+        out["transformation"] = [host[-18 + 4 * r:-14 + 4 * r] for r in range(4)]
+        out["register_fitness"], out["register_rmse"] = host[-2], host[-1]
     return out
 
 

@@ -25,7 +25,8 @@ clusters of fewer than --cluster_min_size points are dropped.
 --gt_ply PATH scores every scan's fused cloud (the full one, as it is written) against the ground-truth cloud of PATH on
 the GPU and prints the result as `<scan>: score {json}`; --max_dist, --thresholds, --box, --cell and --json are eval_cloud's
 (--json receives {scan: result}), and so are DTU's steps: --reduce_dist, --reduce_seed, --reduce_gt, --obs_mask FILE and
---plane FILE.  PATH and the two FILEs may hold `{scan}`.  Nothing else about the run changes.
+--plane FILE, and the ICP alignment before them: --register_dist D, --register_iters, --register_point_to_point.  PATH and
+the two FILEs may hold `{scan}`.  Nothing else about the run changes.
 """
 from __future__ import annotations
 
@@ -99,6 +100,8 @@ def main(argv=None):
         p.error("--box and --json need --gt_ply")
     if args.gt_ply is None and (args.reduce_dist is not None or args.obs_mask is not None or args.plane is not None):
         p.error("--reduce_dist, --obs_mask and --plane need --gt_ply")
+    if args.gt_ply is None and args.register_dist is not None:
+        p.error("--register_dist needs --gt_ply")
     if args.reduce_dist is None and (args.reduce_gt or args.reduce_seed != 0):
         p.error("--reduce_seed and --reduce_gt need --reduce_dist")
     if len(args.thresholds) > 8:
