@@ -49,9 +49,12 @@ __global__ __launch_bounds__(256) void conv3d_direct_kernel(const float* __restr
         ow = (int)(vi % Wo); oh = (int)((vi / Wo) % Ho); od = (int)(vi / ((size_t)Wo * Ho));
     }
 
+    // the folded shift is added LAST, as in the MFMA kernels: a trained BatchNorm's shift can be far larger than the
+    // sum of the products, and an accumulator that starts from it rounds every one of the 27 CIN additions at the
+    // shift's magnitude (conv6: 1728 roundings instead of one)
     float acc[CPT];
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) acc[j] = bias[co0 + j];
+    for (int j = 0; j < CPT; ++j) acc[j] = 0.0f;
 
     const int pcls = DECONV ? (int)blockIdx.z : 0;
     for (int kd = 0; kd < 3; ++kd) {
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(256) void conv3d_direct_kernel(const float* __restr
     for (int j = 0; j < CPT; ++j) {
         const int co = co0 + j;
         const size_t o = (COUT == 1) ? vi : ((size_t)(co >> 3) * nvox + vi) * 8 + (co & 7);
-        float v = acc[j];
+        float v = acc[j] + bias[co];
         if (RELU) v = relu(v);
         if (SKIP) v += skip[o];  // skip + relu(bn(deconv(x)))   (models/mvsnet.py:69-71)
         y[o] = v;
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(256) void deconv3d_direct_kernel(const float* __res
 
     float acc0[CPT], acc1[CPT];
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) { acc0[j] = bias[co0 + j]; acc1[j] = acc0[j]; }
+    for (int j = 0; j < CPT; ++j) { acc0[j] = 0.0f; acc1[j] = 0.0f; }   // the shift is added last (conv3d_direct_kernel)
 
     const bool x1ok = xi + 1 < Wi;
     for (int kd = 0; kd < 3; ++kd) {
@@ -194,11 +197,12 @@ __global__ __launch_bounds__(256) void deconv3d_direct_kernel(const float* __res
         const float4 s0 = *reinterpret_cast<const float4*>(skip + o);
         const float4 s1 = *reinterpret_cast<const float4*>(skip + o + 8);
         // skip + relu(bn(deconv(x)))   (models/mvsnet.py:69-71)
+        const float4 b4 = *reinterpret_cast<const float4*>(bias + co);
         float4 r0, r1;
-        r0.x = relu(acc0[j + 0]) + s0.x; r0.y = relu(acc0[j + 1]) + s0.y;
-        r0.z = relu(acc0[j + 2]) + s0.z; r0.w = relu(acc0[j + 3]) + s0.w;
-        r1.x = relu(acc1[j + 0]) + s1.x; r1.y = relu(acc1[j + 1]) + s1.y;
-        r1.z = relu(acc1[j + 2]) + s1.z; r1.w = relu(acc1[j + 3]) + s1.w;
+        r0.x = relu(acc0[j + 0] + b4.x) + s0.x; r0.y = relu(acc0[j + 1] + b4.y) + s0.y;
+        r0.z = relu(acc0[j + 2] + b4.z) + s0.z; r0.w = relu(acc0[j + 3] + b4.w) + s0.w;
+        r1.x = relu(acc1[j + 0] + b4.x) + s1.x; r1.y = relu(acc1[j + 1] + b4.y) + s1.y;
+        r1.z = relu(acc1[j + 2] + b4.z) + s1.z; r1.w = relu(acc1[j + 3] + b4.w) + s1.w;
         *reinterpret_cast<float4*>(y + o) = r0;
         *reinterpret_cast<float4*>(y + o + 8) = r1;
     }
