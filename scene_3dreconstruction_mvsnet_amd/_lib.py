@@ -143,15 +143,20 @@ REDUCE_SYMBOLS = tuple(_ABI["mvs_reduce_abi.h"])
 CLUSTER_SYMBOLS = tuple(_ABI["mvs_cluster_abi.h"])
 
 # The headers under include/ext/, kept in a table of their own: `_ABI` is exactly the headers of include/*.h.  load()
-# applies both; tests/test_cloud_register_host.py holds this one to its prototypes.
+# applies both; tests/test_cloud_register_host.py and tests/test_cloud_planes_host.py hold this one to its prototypes.
 _ABI_EXT = {
     "ext/mvs_register_abi.h": {
         "mvs_query_register_workspace": [_ll, _ll, _vp, _vp, _d, _i, _szp],
         "mvs_cloud_register": [_vp, _i, _ll, _vp, _vp, _i, _ll, _vp, _vp, _d, _d, _vp, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp, _sz, _vp],
     },
+    "ext/mvs_planes_abi.h": {
+        "mvs_query_planes_workspace": [_ll, _i, _i, _szp],
+        "mvs_cloud_planes": [_vp, _i, _ll, _vp, _vp, _d, _i, _i, _ll, _ull, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    },
 }
 REGISTER_SYMBOLS = tuple(_ABI_EXT["ext/mvs_register_abi.h"])
+PLANES_SYMBOLS = tuple(_ABI_EXT["ext/mvs_planes_abi.h"])
 
 
 class MvsError(RuntimeError):
@@ -175,7 +180,7 @@ def load():
                 "There is no CPU/PyTorch fallback for the MVSNet depth path.")
         lib = ctypes.CDLL(LIB_PATH)
         for name in (SYMBOLS + FUSE_SYMBOLS + CLOUD_SYMBOLS + NORMALS_SYMBOLS + OUTLIERS_SYMBOLS + DISTANCE_SYMBOLS
-                     + REDUCE_SYMBOLS + CLUSTER_SYMBOLS + REGISTER_SYMBOLS):
+                     + REDUCE_SYMBOLS + CLUSTER_SYMBOLS + REGISTER_SYMBOLS + PLANES_SYMBOLS):
             if not hasattr(lib, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}")
         for prototypes in list(_ABI.values()) + list(_ABI_EXT.values()):
@@ -1390,6 +1395,71 @@ def cloud_register(target, source, box_min, box_max, cell, max_dist, target_norm
             None if system is None or its == 0 else system.data_ptr(), None if idx is None or N == 0 else idx.data_ptr(),
             ws.data_ptr(), ws.numel(), _stream(dev)))
     return T, counts, stats, hist, system, idx
+
+
+# ---- plane segmentation, RANSAC (include/ext/mvs_planes_abi.h, csrc/cloud_planes.hip) ----
+# MVS_PLANES_CANDIDATES_MAX, _MAX, _SUMS, _TILE, _GROUP, _FANIN, _SCALARS
+PLANES_CANDIDATES_MAX, PLANES_MAX, PLANES_SUMS, PLANES_TILE, PLANES_GROUP, PLANES_FANIN, PLANES_SCALARS = 8192, 64, 9, 1024, 256, 256, 512
+PLANES_STOPS = {1: "max_planes", 2: "no_plane", 3: "exhausted"}     # MVS_PLANES_STOP_*
+
+
+def query_planes_workspace(P, num_candidates, max_planes=1) -> int:
+    return _query("mvs_query_planes_workspace", int(P), int(num_candidates), int(max_planes))
+
+
+def cloud_planes(xyz, box_min, box_max, dist, num_candidates=1000, max_planes=1, min_inliers=3, seed=0, toward=None,
+                 cand_counts=False, sums=False, out=None):
+    """The dominant planes of the points of the cloud inside the box, one RANSAC round per plane over the points that have
+    no plane yet (Open3D's segment_plane applied repeatedly, as include/ext/mvs_planes_abi.h defines it), on the device.
+
+    xyz float32 or float64 [P,3]; box_min, box_max: 3 host numbers each; dist finite and >= 0: how far from a plane its
+    points may lie; num_candidates in [1, 8192]: the planes through three points tried per round; max_planes in [1, 64];
+    min_inliers >= 3: a round whose best candidate counts fewer ends the call; seed an integer modulo 2^64; toward: 3 host
+    numbers, the side every normal is turned to, or None.  Returns (planes float64 [max_planes,4]: (n, d) with
+    n . x + d = 0, NaN for the rounds that gave none, rounds int64 [max_planes,4]: active members, winning candidate, its
+    count, final inliers, counts int64 [4]: points inside the box, planes found, points on planes, stop reason
+    (PLANES_STOPS), labels int32 [P]: the plane's number, -1 on no plane, -2 outside the box, cand_counts int32
+    [max_planes,num_candidates] or None, sums float64 [max_planes,9] or None), all on the device.  `out` = (the same six,
+    None where not wanted) receives the results.  Enqueued on the current stream; nothing synchronises."""
+    import math
+    xyz = _cloud_xyz(xyz, "cloud_planes")
+    dev = xyz.device
+    P, t, K, rounds, least = xyz.shape[0], float(dist), int(num_candidates), int(max_planes), int(min_inliers)
+    if not (0.0 <= t < float("inf")):
+        raise RuntimeError(f"cloud_planes: dist = {t} (need a finite dist >= 0)")
+    if not 1 <= K <= PLANES_CANDIDATES_MAX:
+        raise RuntimeError(f"cloud_planes: num_candidates = {K} (need 1 <= num_candidates <= {PLANES_CANDIDATES_MAX})")
+    if not 1 <= rounds <= PLANES_MAX:
+        raise RuntimeError(f"cloud_planes: max_planes = {rounds} (need 1 <= max_planes <= {PLANES_MAX})")
+    if not 3 <= least < 1 << 62:
+        raise RuntimeError(f"cloud_planes: min_inliers = {least} (need min_inliers >= 3)")
+    side = None
+    if toward is not None:
+        if isinstance(toward, torch.Tensor):
+            if toward.device.type != "cpu":
+                raise RuntimeError(f"cloud_planes: toward must be host numbers (got a tensor on {toward.device}): it travels "
+                                   "in the kernel arguments, reading device memory would sync")
+            toward = toward.tolist()
+        flat = [float(v) for v in toward]
+        if len(flat) != 3 or not all(math.isfinite(v) for v in flat):
+            raise RuntimeError("cloud_planes: toward must be 3 finite numbers")
+        side = (_d * 3)(*flat)
+    lo, hi = _box_arg(box_min, box_max, "cloud_planes")
+    nbytes = _query("mvs_query_planes_workspace", P, K, rounds)
+    with torch.cuda.device(dev):
+        planes, rnds, counts, labels, cand, sm = _outputs("cloud_planes", dev, [
+            ("planes", (rounds, 4), torch.float64, True), ("rounds", (rounds, 4), torch.int64, True),
+            ("counts", (4,), torch.int64, True), ("labels", (P,), torch.int32, True),
+            ("cand_counts", (rounds, K), torch.int32, cand_counts), ("sums", (rounds, PLANES_SUMS), torch.float64, sums)], out)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        # P == 0: the library reads no point and writes no label; it gets the workspace's address in place of the empty
+        # tensors'
+        check(load().mvs_cloud_planes(
+            xyz.data_ptr() if P else ws.data_ptr(), _xyz_code(xyz), P, lo, hi, t, K, rounds, least,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, side, planes.data_ptr(), rnds.data_ptr(), counts.data_ptr(),
+            labels.data_ptr() if P else ws.data_ptr(), None if cand is None else cand.data_ptr(),
+            None if sm is None else sm.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return planes, rnds, counts, labels, cand, sm
 
 
 # ---- FeatureNet (reference models/mvsnet.py:10-30) -------------------------------------------

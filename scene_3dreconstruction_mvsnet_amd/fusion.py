@@ -21,6 +21,9 @@ to DTU's MATLAB code; `read_ply` reads the clouds back.
 marks the clusters above a size, on the device (mvs_cloud_cluster, include/mvs_cluster_abi.h): the step the reference
 leaves to the user of the cloud, and the remedy for small dense blobs of wrong depth; `downsample=dict(clusters=...)`,
 off by default.
+`segment_planes` takes the supporting planes out of a cloud by RANSAC, round after round (Open3D's segment_plane applied
+repeatedly), on the device (mvs_cloud_planes, include/ext/mvs_planes_abi.h): on a bin scan the floor and the walls tie
+every part into one cluster, so it runs before `cluster_cloud`; `downsample=dict(planes=...)`, off by default.
 
 Differences from the reference, flagged rather than hidden:
   * cv2.remap is restated inside the kernel (1/32-pixel quantised bilinear, zero border); OpenCV is
@@ -497,6 +500,55 @@ def cluster_cloud(xyz, eps, min_points=10, min_size=1, box=None, cell=None, mask
     return labels, keep, counts, torch.where(keep[:, None], xyz, torch.full_like(xyz, float("nan")))
 
 
+PLANES_DEFAULTS = dict(max_planes=1, num_candidates=1000, min_inliers=3, seed=0, remove=True)
+
+
+def planes_options(opt):
+    """The options of reconstruct_scan's plane stage, downsample['planes'], with their defaults: dict(dist, max_planes=1,
+    num_candidates=1000, min_inliers=None -> 3, seed=0, remove=True); None stays None.  dist has no default."""
+    if opt is None:
+        return None
+    opt = dict(opt)
+    unknown = set(opt) - {"dist"} - set(PLANES_DEFAULTS)
+    if unknown:
+        raise ValueError(f"downsample['planes']: unknown keys {sorted(unknown)} (dist, max_planes, num_candidates, "
+                         "min_inliers, seed, remove)")
+    if "dist" not in opt:
+        raise ValueError("downsample['planes'] needs dist, how far from a plane its points may lie, in the cloud's units")
+    out = dict(PLANES_DEFAULTS, **opt)
+    if out["min_inliers"] is None:
+        out["min_inliers"] = 3
+    return dict(dist=float(out["dist"]), max_planes=int(out["max_planes"]), num_candidates=int(out["num_candidates"]),
+                min_inliers=int(out["min_inliers"]), seed=int(out["seed"]), remove=bool(out["remove"]))
+
+
+def segment_planes(xyz, dist, max_planes=1, num_candidates=1000, min_inliers=None, seed=0, box=None, toward=None, masked=False):
+    """The supporting planes of a cloud by RANSAC on the device (mvs_cloud_planes, include/ext/mvs_planes_abi.h): what
+    Open3D's segment_plane gives when it is applied again and again to the rest.  Among the points of xyz (float32 or
+    float64 [P,3], on the GPU) inside `box` = (min, max), every round draws num_candidates planes through three of the
+    points that have no plane yet (by a hash of seed, round and candidate), takes the one with the most points within
+    `dist`, refits it to those by least squares and gives the points within `dist` of the refitted plane its number.  It
+    stops after max_planes rounds, when the best candidate has fewer than min_inliers points (default 3), or when fewer
+    than three points are left.  toward: 3 host numbers, the side every normal is turned to (a camera, the bin's inside);
+    without it the largest component of a normal is positive.  box defaults to the bounding box of the finite points (one
+    host synchronisation; with a box given nothing synchronises).
+    Returns (planes float64 [max_planes,4]: (n, d) of n . x + d = 0 with |n| = 1, NaN for rounds that gave none, labels
+    int32 [P]: the plane's number, -1 on no plane, -2 outside the box, counts int64 [4]: points inside the box, planes
+    found, points on planes, stop reason (1 max_planes, 2 no_plane, 3 exhausted; _lib.PLANES_STOPS), rounds int64
+    [max_planes,4]: active points, winning candidate, its count, final inliers) on the device.  A plane is the P of
+    select_cloud and evaluate_cloud(plane=).  With masked=True a fifth item follows: xyz with NaN in the rows that lie on
+    a plane, ready for cluster_cloud and register_cloud."""
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise RuntimeError("segment_planes: xyz must be a CUDA(ROCm) tensor; there is no CPU implementation")
+    lo, hi = _finite_box(xyz) if box is None else box
+    planes, rounds, counts, labels, _, _ = _lib.cloud_planes(xyz, lo, hi, dist, num_candidates=num_candidates,
+                                                             max_planes=max_planes, min_inliers=3 if min_inliers is None else min_inliers,
+                                                             seed=seed, toward=toward)
+    if not masked:
+        return planes, labels, counts, rounds
+    return planes, labels, counts, rounds, torch.where((labels >= 0)[:, None], torch.full_like(xyz, float("nan")), xyz)
+
+
 def select_cloud(xyz, obs_mask=None, plane=None):
     """DTU's observability mask and ground-plane filter on the device (mvs_cloud_select, include/mvs_reduce_abi.h).
     obs_mask = dict(mask=uint8 or bool [n0,n1,n2] (a tensor on xyz's device, or a numpy array), origin=(3,), res=float),
@@ -727,19 +779,27 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
     inside the crop box after the outlier stage (on its masked cloud, if asked for) and before the voxel downsample, which
     takes the cloud with the noise and the clusters below min_size masked out too.  eps is in the cloud's units and has no
     default.  The return gains one last item, after the outliers' when both are asked for: dict(counts int64 [7], keep
-    bool [P], labels int32 [P]) as numpy arrays over the fused cloud."""
+    bool [P], labels int32 [P]) as numpy arrays over the fused cloud.
+    downsample=dict(..., planes=dict(dist=D, max_planes=1, num_candidates=1000, min_inliers=None, seed=0, remove=True))
+    runs `segment_planes` among the points inside the crop box after the outlier stage (on its masked cloud) and before
+    the cluster stage: the bin's floor and walls, which would otherwise tie every part into one cluster.  With remove=True
+    the cluster stage and the voxel downsample take the cloud without the plane points; with remove=False the points are
+    labelled only.  dist is in the cloud's units and has no default.  The return gains one item, after the outliers' and
+    before the clusters': dict(planes float64 [max_planes,4], rounds int64 [max_planes,4], counts int64 [4], labels int32
+    [P]) as numpy arrays, labels over the fused cloud."""
     import copy
-    normals_opt = outliers_opt = clusters_opt = None
+    normals_opt = outliers_opt = clusters_opt = planes_opt = None
     if downsample is not None:
         downsample = dict(downsample)
         ds_ply = downsample.pop("plyfilename", None)
         normals_opt = downsample.pop("normals", None)
         outliers_opt = downsample.pop("outliers", None)
         clusters_opt = downsample.pop("clusters", None)
+        planes_opt = planes_options(downsample.pop("planes", None))
         unknown = set(downsample) - {"voxel_size", "box", "scale"}
         if unknown:
             raise ValueError(f"downsample: unknown keys {sorted(unknown)} (voxel_size, box, scale, plyfilename, normals, "
-                             "outliers, clusters)")
+                             "outliers, planes, clusters)")
         if normals_opt is not None:
             normals_opt = dict(dict(knn=30, margin=20.0, cell=5.0), **normals_opt)
             unknown = set(normals_opt) - {"knn", "margin", "cell"}
@@ -843,6 +903,12 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
         if outliers_opt is not None:
             keep, _, out_counts, out_stats, ds_in = remove_outliers(xyz, box=downsample.get("box"), masked=True,
                                                                     **outliers_opt)
+        if planes_opt is not None:
+            crop = bin_box() if downsample.get("box") is None else downsample["box"]
+            remove = planes_opt.pop("remove")
+            pl_planes, pl_labels, pl_counts, pl_rounds, pl_masked = segment_planes(ds_in, box=crop, masked=True, **planes_opt)
+            if remove:
+                ds_in = pl_masked
         if clusters_opt is not None:
             crop = bin_box() if downsample.get("box") is None else downsample["box"]
             cl_labels, cl_keep, cl_counts, ds_in = cluster_cloud(ds_in, box=crop, masked=True, **clusters_opt)
@@ -854,6 +920,9 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
             ds_vertices, ds_colours = _packed_to_host(*downsample_cloud(ds_in, rgb, **downsample))
         if outliers_opt is not None:
             outliers = dict(counts=out_counts.cpu().numpy(), stats=out_stats.cpu().numpy(), keep=keep.cpu().numpy())
+        if planes_opt is not None:
+            planes = dict(planes=pl_planes.cpu().numpy(), rounds=pl_rounds.cpu().numpy(), counts=pl_counts.cpu().numpy(),
+                          labels=pl_labels.cpu().numpy())
         if clusters_opt is not None:
             clusters = dict(counts=cl_counts.cpu().numpy(), keep=cl_keep.cpu().numpy(), labels=cl_labels.cpu().numpy())
         vertices, colours = _packed_to_host(xyz, rgb)      # the one copy of the full cloud
@@ -861,7 +930,8 @@ def reconstruct_scan(model, dataset, scan=None, n_view_filter=10, photomask=0.8,
         write_ply(plyfilename, vertices, colours)
     if downsample is None:
         return vertices, colours
-    tail = (() if outliers_opt is None else (outliers,)) + (() if clusters_opt is None else (clusters,))
+    tail = (() if outliers_opt is None else (outliers,)) + (() if planes_opt is None else (planes,)) \
+        + (() if clusters_opt is None else (clusters,))
     if normals_opt is None:
         if ds_ply:
             write_ply(ds_ply, ds_vertices, ds_colours)

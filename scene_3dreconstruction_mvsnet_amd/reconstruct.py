@@ -21,6 +21,11 @@ its K nearest neighbours there is not below mean + --outlier_std standard deviat
 --cluster_eps E (with --downsample_mm) adds fusion.cluster_cloud after that and before the voxel filter: DBSCAN among the
 points of the box with radius E (the cloud's units) and --cluster_min_points neighbours for a core point; the noise and the
 clusters of fewer than --cluster_min_size points are dropped.
+--segment_dist D (with --downsample_mm) adds fusion.segment_planes before the clustering: --segment_planes rounds of RANSAC
+with --segment_candidates candidate planes each take the bin's floor and walls out (the points within D of each plane,
+the cloud's units), so that the parts no longer hang together through them; --segment_keep labels the planes and removes
+nothing; --segment_out FILE.npz ({scan} is replaced) receives the planes, the first as the array P that eval_cloud --plane reads
+(not written when no plane is found; the largest component of its normal is positive, which decides the side --plane keeps).
 
 --gt_ply PATH scores every scan's fused cloud (the full one, as it is written) against the ground-truth cloud of PATH on
 the GPU and prints the result as `<scan>: score {json}`; --max_dist, --thresholds, --box, --cell and --json are eval_cloud's
@@ -41,6 +46,28 @@ from .mvsnet import _load_checkpoint
 def downsampled_name(voxel_mm):
     """eval.py:836's file name: fused_dwnsmpld_5mm.ply for 5 and 5.0, fused_dwnsmpld_2.5mm.ply for 2.5."""
     return f"fused_dwnsmpld_{voxel_mm:g}mm.ply"
+
+
+def segment_options(args):
+    """downsample['planes'] of the --segment_* flags, or None without --segment_dist."""
+    if args.segment_dist is None:
+        return None
+    return dict(dist=args.segment_dist, max_planes=args.segment_planes, num_candidates=args.segment_candidates,
+                min_inliers=3 if args.segment_min_inliers is None else args.segment_min_inliers, seed=args.segment_seed,
+                remove=not args.segment_keep)
+
+
+def write_planes(path, planes):
+    """--segment_out: the arrays P (the first plane: fusion.read_plane reads it back, eval_cloud --plane applies it), planes,
+    rounds and counts of reconstruct_scan's planes item.  Refused when no plane was found: P would be NaN, and the plane
+    filter would read it without a word.  The sign of P is the segmentation's without `toward`: the largest component of
+    the normal is positive, so the side select_cloud keeps (n . x + d > 0) is the side that component points to, not
+    necessarily the scene's upper side; negate P where the other side is wanted."""
+    import numpy as np
+    if int(np.asarray(planes["counts"])[1]) < 1:
+        raise ValueError(f"write_planes: no plane was found (counts {np.asarray(planes['counts']).tolist()}): nothing to write to {path}")
+    np.savez(path, P=np.asarray(planes["planes"], np.float64)[0], planes=planes["planes"], rounds=planes["rounds"],
+             counts=planes["counts"])
 
 
 def main(argv=None):
@@ -92,6 +119,17 @@ def main(argv=None):
                    help="a core point has at least M points within E, itself counted")
     p.add_argument("--cluster_min_size", type=int, default=1, metavar="S",
                    help="a cluster is kept while it has at least S points (1 drops the noise only)")
+    p.add_argument("--segment_dist", type=float, default=None, metavar="D",
+                   help="with --downsample_mm: take the dominant planes of the box out before the clustering (RANSAC; a "
+                        "point belongs to a plane within D, the cloud's units)")
+    p.add_argument("--segment_planes", type=int, default=1, metavar="N", help="the most planes that are taken out")
+    p.add_argument("--segment_candidates", type=int, default=1000, metavar="K", help="candidate planes tried per round")
+    p.add_argument("--segment_min_inliers", type=int, default=None, metavar="N",
+                   help="stop when the best candidate of a round has fewer points (default 3)")
+    p.add_argument("--segment_seed", type=int, default=0)
+    p.add_argument("--segment_keep", action="store_true", help="label the planes' points only, remove nothing")
+    p.add_argument("--segment_out", default=None, metavar="FILE.npz",
+                   help="write the planes there: P (the first, what --plane reads), planes, rounds, counts ({scan} is replaced)")
     p.add_argument("--gt_ply", default=None, metavar="PATH",
                    help="score each scan's fused cloud against this ground-truth PLY ({scan} is replaced by the scan's name)")
     add_score_arguments(p)
@@ -116,6 +154,12 @@ def main(argv=None):
         p.error("--cluster_eps needs --downsample_mm")
     if args.cluster_eps is None and (args.cluster_min_points != 10 or args.cluster_min_size != 1):
         p.error("--cluster_min_points and --cluster_min_size need --cluster_eps")
+    if args.downsample_mm is None and args.segment_dist is not None:
+        p.error("--segment_dist needs --downsample_mm")
+    if args.segment_dist is None and (args.segment_planes != 1 or args.segment_candidates != 1000 or args.segment_seed != 0
+                                      or args.segment_min_inliers is not None or args.segment_keep or args.segment_out):
+        p.error("--segment_planes, --segment_candidates, --segment_min_inliers, --segment_seed, --segment_keep and "
+                "--segment_out need --segment_dist")
     box = None
     if args.downsample_mm is not None:
         box = (args.crop_box[:3], args.crop_box[3:]) if args.crop_box else bin_box(args.bin_dims, args.bin_delta)
@@ -138,6 +182,8 @@ def main(argv=None):
                 downsample["normals"] = dict(knn=args.normals_knn, margin=args.normals_margin_mm)
             if args.outlier_knn is not None:
                 downsample["outliers"] = dict(nb_neighbors=args.outlier_knn, std_ratio=args.outlier_std)
+            if segment_options(args) is not None:
+                downsample["planes"] = segment_options(args)
             if args.cluster_eps is not None:
                 downsample["clusters"] = dict(eps=args.cluster_eps, min_points=args.cluster_min_points,
                                               min_size=args.cluster_min_size)
@@ -154,10 +200,20 @@ def main(argv=None):
                 print(f"{scan}: normals of {estimated} of {members} points in the grown box; {open_} of them could have "
                       f"had a nearer neighbour outside it")
             if args.outlier_knn is not None:
-                outliers = got[-2] if args.cluster_eps is not None else got[-1]
+                outliers = got[-1 - (args.cluster_eps is not None) - (args.segment_dist is not None)]
                 members, valid, kept = (int(x) for x in outliers["counts"])
                 print(f"{scan}: {kept} of {members} points in the box kept ({valid} with a neighbour elsewhere; mean distance "
                       f"below {outliers['stats'][2]:g})")
+            if args.segment_dist is not None:
+                planes = got[-2] if args.cluster_eps is not None else got[-1]
+                members, found, on_planes, stop = (int(x) for x in planes["counts"])
+                print(f"{scan}: {found} planes among {members} points in the box hold {on_planes} of them"
+                      f"{' (labelled, not removed)' if args.segment_keep else ''}")
+                if args.segment_out and found == 0:
+                    print(f"{scan}: no plane was found, --segment_out is not written")
+                elif args.segment_out:
+                    write_planes(args.segment_out.replace("{scan}", scan), planes)
+                    written.append(args.segment_out.replace("{scan}", scan))
             if args.cluster_eps is not None:
                 members, core, border, noise, clusters, kept, largest = (int(x) for x in got[-1]["counts"])
                 print(f"{scan}: {clusters} clusters among {members} points in the box ({core} core, {border} border, {noise} "
